@@ -16,7 +16,10 @@ ONE clock: `value`, `ms_per_step` and `roofline` all come from the HIP events th
 on the launch stream (MAX over ranks); the host wall clock over the same region is reported beside it
 (`wall_ms_per_step`).
 
-Beside the headline (all untimed w.r.t. `value`):
+A plain run sets up, warms up, times the K steps, writes the last step's spectra if --dump-outputs DIR is given
+(DIR/spectra.npy: a fixed, seeded sample of 1024 frames as float32 [frame, bin, re/im]) and prints the line.
+With --full it also measures, beside the headline (all untimed w.r.t. `value`):
+  parity_rel_l2_vs_f64  the last frame of the last block vs the CPU oracle (f64 FIR + f64 FFT)
   l3_resident       the round-1 form of the step (ONE 2^24 block re-run in place: 256 MiB = Infinity-Cache resident)
   direct_form       the same stream through the fused direct-form kernel (MFMA Toeplitz FIR + FFT)
   fast_convolution  the same stream through overlap-save FIR + batched FFT (two launches per block)
@@ -24,6 +27,7 @@ Beside the headline (all untimed w.r.t. `value`):
                     (firpfbch 64 ch, 2^26 samples), C5 (firpfbch2 256 ch, 2^26 samples, one GPU, all sub-bands)
   cpu_baseline      the CPU oracle (C restatement of yagi's algorithm, kind "port") on a bounded sample of the same
                     stream: one thread (the reference is single-threaded) and an all-cores time-sharded leg
+  c5_sharded        N > 1 only: the sharded C5 channelizer with its exchange step (see below)
 
 Multi-GPU: the headline shards into independent streams: each rank filters its own stream, no
 data-path collective => "scaling": "weak"; value = all ranks' samples / max time.
@@ -31,6 +35,7 @@ data-path collective => "scaling": "weak"; value = all ranks' samples / max time
 sub-bands sharded over the ranks, RCCL all-gather, assemble (strong scaling: the 2^26-sample block is fixed).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1 without WORLD_SIZE: starts its own N rank processes)
+    python bench.py --gpus N --steps K --warmup W --full   (the headline and every leg above)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).
@@ -56,6 +61,8 @@ BYTES_PER_SAMPLE = 16               # 8 B read + 8 B spectrum written (fused; SU
 FLOP_PER_SAMPLE = 4 * TAPS + 60     # 1024 FIR + 5 N log2 N / N FFT
 HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 FP32_PEAK_TFLOPS = 157.3
+DUMP_FRAMES = 1024                  # --dump-outputs: 1024 x 4096 complex f32 = 32 MiB
+DUMP_SEED = 0x59414749
 
 
 # ------------------------------------------------------------------------------------------------
@@ -92,6 +99,11 @@ def cpu_baseline(h, scale, budget_s=8.0, threads=None):
         avail = len(os.sched_getaffinity(0))
     except AttributeError:
         avail = os.cpu_count() or 1
+    # a thread budget given to the process bounds the pool: threads beyond the CPUs it may use only time-slice, and
+    # every thread does the same number of passes, so the leg's wall time grows with the excess
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        avail = min(avail, int(omp))
     T = max(1, min(threads or avail, avail))
     per = 512                                                      # frames per thread and pass
     passes = max(1, int(round(single * 1e6 * budget_s / 1.5 / (per * NFFT))))
@@ -123,6 +135,20 @@ def cpu_baseline(h, scale, budget_s=8.0, threads=None):
                                   f"with a {halo}-sample halo each (time-sharded), {dt_all:.1f} s wall",
                         "speedup_vs_1_thread": round(rate / single, 2)}
     return out
+
+
+def dump_outputs(d, y):
+    """the last timed step's spectra, as a caller of the stream receives them: a fixed, seeded sample of DUMP_FRAMES
+    4096-bin frames (every frame if there are fewer) in stream order, float32 [frame, bin, re/im], to d/spectra.npy"""
+    import numpy as np
+    import torch
+    frames = y.view(-1, NFFT)
+    nf = frames.shape[0]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(nf, min(DUMP_FRAMES, nf), replace=False))
+    sel = frames[torch.from_numpy(idx).to(frames.device)]
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "spectra.npy", torch.view_as_real(sel).cpu().numpy())
 
 
 def self_launch(n):
@@ -184,10 +210,18 @@ def main():
                     help="0 auto (= 4 at 256 taps), 1 fused direct-form (sliding VALU FIR), 2 fused MFMA Toeplitz "
                          "FIR, 3 fast convolution (overlap-save kernel + batched FFT, two launches), "
                          "4 frequency-domain filter with frame-boundary correction (one launch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed legs (configs, other algorithms)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, run the untimed legs: parity vs the CPU oracle, other algorithms, "
+                         "configs, PCIe-inclusive and plain-call legs, the CPU baseline, and at N > 1 the sharded C5")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's spectra to DIR/spectra.npy (a fixed, seeded sample of "
+                         f"{DUMP_FRAMES} frames, float32 [frame, bin, re/im]; rank 0's stream)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the untimed GPU legs (configs, other algorithms)")
     ap.add_argument("--cpu-threads", type=int, default=0,
-                    help="threads of the all-cores CPU leg (0 = every core this process may run on)")
+                    help="with --full: threads of the all-cores CPU leg (0 = every core this process may run on, "
+                         "at most OMP_NUM_THREADS when that is set)")
     ap.add_argument("--c5-chunks", type=int, default=8, help="--workload c5: chunks per block (gather of chunk k "
                                                               "overlaps the shard kernel of chunk k+1)")
     ap.add_argument("--dist-backend", default="nccl",
@@ -197,6 +231,8 @@ def main():
                     help="headline through plain block calls on one stream instead of the pipelined calls "
                          "(yagi_hip_firfft_crcf_set_pipeline: consecutive blocks overlap on two streams of the object)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "stream":
+        ap.error("--dump-outputs writes the headline stream's spectra: use it with --workload stream")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
 
@@ -311,13 +347,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall, dev_ms = float(t[0]), float(t[1])
 
+    if rank == 0 and args.dump_outputs:          # before the --full legs, which reuse y as their output buffer
+        dump_outputs(args.dump_outputs, y)
+
     # N > 1: the one path with a real exchange step (C5: firpfbch2 sub-bands sharded over the ranks, RCCL all-gather,
     # SURVEY 8e) rides along as an untimed extra so the scaling run measures it on real xGMI; `value` is unaffected.
     # It runs HERE, before rank 0's single-rank extras, so no rank waits in a collective while rank 0 is busy elsewhere.
     # A watchdog (armed behind a barrier every rank has reached) ends a collective that never completes: rank 0 still
     # prints the headline line, and every rank leaves with a NON-ZERO code so the driver records the hang.
     c5_result = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         import copy
 
         def bail():
@@ -349,7 +388,7 @@ def main():
     # in-run parity spot check (rank 0): last frame of the last block vs the oracle (f64 FIR + f64 FFT)
     # on the same input; its 255-sample halo is the preceding samples of the stream
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             from oracle import oracle
             f = nb * nframes - 1
@@ -362,7 +401,7 @@ def main():
             parity = f"unavailable: {e}"
 
     extras = {}
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         reps = max(3, min(args.steps, 10))
         # (1) the round-1 form: ONE block re-run in place (256 MiB working set = the Infinity Cache)
         qr = ya.FirFftStream(h, NFFT)
@@ -618,13 +657,14 @@ def main():
                          "fp32": {"achieved_tflops": round(flop_per_sample * n / kern_s / 1e12, 2),
                                   "peak_tflops": FP32_PEAK_TFLOPS, "flop_per_sample": flop_per_sample,
                                   "frac": round(flop_per_sample * n / kern_s / 1e12 / FP32_PEAK_TFLOPS, 4)}},
-            "parity_rel_l2_vs_f64": parity,
         }
+        if args.full:
+            out["parity_rel_l2_vs_f64"] = parity
         out.update(extras)
     if rank == 0 and c5_result is not None:
         out["c5_sharded"] = c5_result
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from oracle import oracle
             out["cpu_baseline"] = cpu_baseline(oracle.fir_design_kaiser(TAPS, 0.2, 60.0), scale,
                                                threads=args.cpu_threads or None)

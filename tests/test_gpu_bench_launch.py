@@ -16,7 +16,7 @@ ROOT = Path(__file__).resolve().parent.parent
 def test_bench_self_launch_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "2",
-                        "--warmup", "1", "--blocks", "2", "--prewarm-ms", "0", "--no-cpu-baseline"],
+                        "--warmup", "1", "--blocks", "2", "--prewarm-ms", "0", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
