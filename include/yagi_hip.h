@@ -383,6 +383,86 @@ YAGI_RESAMP2_API(rrrf, float, float)
 YAGI_RESAMP2_API(crcf, yagi_cf32, float)
 YAGI_RESAMP2_API(cccf, yagi_cf32, yagi_cf32)
 
+/* ---- Resamp<T,Coeff>: src/filter/resampler/resamp.rs:8-165 (arbitrary-rate resampler) ---------------------------
+ *   create          new(rate, m, fc, as_, npfb)   :24-71   checks in the reference's order and wording; npfb is rounded
+ *                   up to 2^bits (math/mod.rs:80-92, npfb 0 -> VALUE, bits outside [1,16] -> CONFIG); Kaiser design
+ *                   of 2 m npfb + 1 taps at fc/npfb, normalised to DC gain npfb (sequential f32 sum), bank =
+ *                   FirPfbFilter::new(npfb, h, 2 m npfb) (the last tap dropped, :56)
+ *   create_default  new_default(rate)             :73-84   m 7, fc 0.25, 60 dB, npfb 256
+ *   create_taps     the bank from external taps h[0 .. 2 m npfb) (npfb a power of two in [2, 2^16]); for exact tests
+ *   clone / reset   derive(Clone) :8 / reset() :86-89 (phase 0, window zeroed)
+ *   set_rate / adjust_rate / get_rate  :95-118     rate in [0.004, 250]; step = round(2^24 / rate) in f32
+ *   get_delay       get_delay() :91-93 (= m)
+ *   get_num_output  get_num_output(nx) :128-139   closed form, no device work
+ *   execute         execute(x, y) :141-154        one sample in; *nw = the outputs written (ny_cap = y's length)
+ *   execute_block   execute_block(x, y) :156-165  nx samples in
+ *   ny_cap < get_num_output(nx) is YAGI_ERR_RANGE (the reference panics on the slice).  Every path (host per-sample,
+ *   host block, device block) leaves the same window and phase, so calls may be mixed.
+ * Device form: resamp_kernel -- the control loop only adds integers, so with A_j = p0 + j step output j of a call
+ * comes after input A_j >> 24 and uses branch (A_j & 0xFFFFFF) >> (24 - bits): every output is an independent 2m-tap
+ * dot product and the host knows the output count before the launch.  symsync and the timing-phase setters (commented
+ * out in the reference, :120-126) are not provided. */
+#define YAGI_RESAMP_API(K, T, C)                                                                    \
+    typedef struct yagi_hip_resamp_##K##_s *yagi_hip_resamp_##K;                                    \
+    int yagi_hip_resamp_##K##_create(float rate, size_t m, float fc, float as_, size_t npfb,        \
+                                     yagi_hip_resamp_##K *q);                                       \
+    int yagi_hip_resamp_##K##_create_default(float rate, yagi_hip_resamp_##K *q);                   \
+    int yagi_hip_resamp_##K##_create_taps(float rate, size_t m, size_t npfb, const C *h,            \
+                                          size_t h_len, yagi_hip_resamp_##K *q);                    \
+    int yagi_hip_resamp_##K##_destroy(yagi_hip_resamp_##K q);                                       \
+    int yagi_hip_resamp_##K##_clone(yagi_hip_resamp_##K q, yagi_hip_resamp_##K *out);               \
+    int yagi_hip_resamp_##K##_set_stream(yagi_hip_resamp_##K q, yagi_stream_t s);                   \
+    int yagi_hip_resamp_##K##_reset(yagi_hip_resamp_##K q);                                         \
+    int yagi_hip_resamp_##K##_set_rate(yagi_hip_resamp_##K q, float rate);                          \
+    int yagi_hip_resamp_##K##_adjust_rate(yagi_hip_resamp_##K q, float gamma);                      \
+    int yagi_hip_resamp_##K##_get_rate(yagi_hip_resamp_##K q, float *rate);                         \
+    int yagi_hip_resamp_##K##_get_delay(yagi_hip_resamp_##K q, size_t *delay);                      \
+    int yagi_hip_resamp_##K##_get_num_output(yagi_hip_resamp_##K q, size_t nx, size_t *ny);         \
+    int yagi_hip_resamp_##K##_execute(yagi_hip_resamp_##K q, T x, T *y, size_t ny_cap, size_t *nw); \
+    int yagi_hip_resamp_##K##_execute_block(yagi_hip_resamp_##K q, const T *x, size_t nx, T *y,     \
+                                            size_t ny_cap, size_t *nw);                             \
+    int yagi_hip_resamp_##K##_execute_block_dev(yagi_hip_resamp_##K q, const T *x_dev, size_t nx,   \
+                                                T *y_dev, size_t ny_cap, size_t *nw);
+
+YAGI_RESAMP_API(rrrf, float, float)
+YAGI_RESAMP_API(crcf, yagi_cf32, float)
+YAGI_RESAMP_API(cccf, yagi_cf32, yagi_cf32)
+
+/* ---- MsResamp<T,Coeff>: src/filter/resampler/msresamp.rs:10-176 (multi-stage arbitrary-rate resampler) -----------
+ *   create(rate, as_)   new() :28-79  rate > 1: interpolator, else decimator; S half-band stages bring the rest into
+ *                       (1, 2] (interp) or [0.5, 1] (decim).  Built as MsResamp2 create(type, S, 0.4, 0.0, as_) -- the
+ *                       Kaiser half-band stand-in for the reference's Parks-McClellan design, as documented at
+ *                       MsResamp2 above (same structure, different tap values) -- and Resamp(rate_arbitrary, 7,
+ *                       min(0.515 rate_arbitrary, 0.49), as_, 256).
+ *   clone / reset       derive(Clone) :10 / reset() :81-85
+ *   get_rate / get_delay  :105-107 / :87-103 (a float)
+ *   get_params          type (1 = interp), number of half-band stages, the arbitrary rate
+ *   get_num_output      :109-120
+ *   execute[_dev]       execute(x, y) :122-176; interp: Resamp then the 2^S interpolator on its output; decim: the
+ *                       half-band chain over groups of 2^S inputs (the 0 .. 2^S-1 left over are carried to the next
+ *                       call), then Resamp.  *nw = outputs written; ny_cap < get_num_output(nx) is YAGI_ERR_RANGE.
+ *                       The intermediate stream stays on the device. */
+#define YAGI_MSRESAMP_API(K, T, C)                                                                  \
+    typedef struct yagi_hip_msresamp_##K##_s *yagi_hip_msresamp_##K;                                \
+    int yagi_hip_msresamp_##K##_create(float rate, float as_, yagi_hip_msresamp_##K *q);            \
+    int yagi_hip_msresamp_##K##_destroy(yagi_hip_msresamp_##K q);                                   \
+    int yagi_hip_msresamp_##K##_clone(yagi_hip_msresamp_##K q, yagi_hip_msresamp_##K *out);         \
+    int yagi_hip_msresamp_##K##_set_stream(yagi_hip_msresamp_##K q, yagi_stream_t s);               \
+    int yagi_hip_msresamp_##K##_reset(yagi_hip_msresamp_##K q);                                     \
+    int yagi_hip_msresamp_##K##_get_rate(yagi_hip_msresamp_##K q, float *rate);                     \
+    int yagi_hip_msresamp_##K##_get_delay(yagi_hip_msresamp_##K q, float *delay);                   \
+    int yagi_hip_msresamp_##K##_get_params(yagi_hip_msresamp_##K q, int *interp,                    \
+                                           size_t *num_halfband_stages, float *rate_arbitrary);     \
+    int yagi_hip_msresamp_##K##_get_num_output(yagi_hip_msresamp_##K q, size_t nx, size_t *ny);     \
+    int yagi_hip_msresamp_##K##_execute(yagi_hip_msresamp_##K q, const T *x, size_t nx, T *y,       \
+                                        size_t ny_cap, size_t *nw);                                 \
+    int yagi_hip_msresamp_##K##_execute_dev(yagi_hip_msresamp_##K q, const T *x_dev, size_t nx,     \
+                                            T *y_dev, size_t ny_cap, size_t *nw);
+
+YAGI_MSRESAMP_API(rrrf, float, float)
+YAGI_MSRESAMP_API(crcf, yagi_cf32, float)
+YAGI_MSRESAMP_API(cccf, yagi_cf32, yagi_cf32)
+
 /* Which kernel execute_block uses.  0 = auto (always a direct form), 1 = general direct-form kernels
  * (fir_kernels.hip: register-window kernel for blocks >= 512 samples, interleaved-output kernel below; both add
  * the taps in the reference's order and never touch a tap past h_len, so a NaN poisons exactly h_len outputs),

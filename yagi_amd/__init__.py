@@ -11,6 +11,8 @@ The classes keep the reference's names, argument meaning and error behaviour
     Error variants             src/error.rs:4-14
     FirPfbCh / FirPfbCh2       (absent from the reference: src/multichannel/mod.rs is empty)
     FirFftStream               the headline composition FirFilter::execute_block -> Fft::run
+    Rresamp / Resamp2 / MsResamp2  src/filter/resampler/{rresamp,resamp2,msresamp2}.rs
+    Resamp / MsResamp          src/filter/resampler/resamp.rs:8-165, msresamp.rs:10-176
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -28,7 +30,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "FftFilt", "Fft", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "FftFilt", "Fft", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -738,6 +740,137 @@ class MsResamp2(_FirBase):
 
     def execute(self, x):                                     # :137-152
         return self.execute_block(x, 1)
+
+
+class Resamp(_FirBase):
+    """Resamp<T,Coeff> (src/filter/resampler/resamp.rs): arbitrary-rate resampler, rate in [0.004, 250], a bank of
+    npfb (rounded up to a power of two) branches of 2m taps selected by a 24-bit fractional phase."""
+
+    def __init__(self, kind, rate, m, fc, as_, npfb):          # new(rate, m, fc, as_, npfb) :24-71
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_resamp_{kind}_"
+        hd = C.c_void_p()
+        _check(self._fn("create")(rate, m, fc, as_, npfb, C.byref(hd)))
+        self._h = hd
+
+    @classmethod
+    def _from(cls, kind, creator, *args):
+        self = object.__new__(cls)
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_resamp_{kind}_"
+        hd = C.c_void_p()
+        _check(self._fn(creator)(*args, C.byref(hd)))
+        self._h = hd
+        return self
+
+    @classmethod
+    def new_default(cls, kind, rate):                         # :73-84  m 7, fc 0.25, 60 dB, npfb 256
+        return cls._from(kind, "create_default", rate)
+
+    @classmethod
+    def from_taps(cls, kind, rate, m, npfb, h):
+        """the bank from external taps h[0 .. 2 m npfb) (npfb a power of two in [2, 2^16])"""
+        if kind not in KINDS:
+            raise ConfigError(f"unknown type combination {kind!r}")
+        h = _arr(h, KINDS[kind][1])
+        return cls._from(kind, "create_taps", rate, m, npfb, _ptr(h), h.size)
+
+    def set_scale(self, scale):
+        raise ConfigError("Resamp has no scale (resamp.rs)")
+
+    get_scale = set_scale
+
+    def set_rate(self, rate):                                 # :95-106
+        _check(self._fn("set_rate")(self._h, rate))
+
+    def adjust_rate(self, gamma):                             # :112-118
+        _check(self._fn("adjust_rate")(self._h, gamma))
+
+    def get_rate(self):                                       # :108-110
+        r = C.c_float()
+        _check(self._fn("get_rate")(self._h, C.byref(r)))
+        return np.float32(r.value)
+
+    def get_delay(self):                                      # :91-93
+        d = C.c_size_t()
+        _check(self._fn("get_delay")(self._h, C.byref(d)))
+        return d.value
+
+    def get_num_output(self, num_input):                      # :128-139
+        n = C.c_size_t()
+        _check(self._fn("get_num_output")(self._h, num_input, C.byref(n)))
+        return n.value
+
+    def execute(self, x):                                     # :141-154  one sample in
+        y = np.empty(max(self.get_num_output(1), 1), self.T)
+        nw = C.c_size_t()
+        _check(self._fn("execute")(self._h, _byval(x, self._Tc), _ptr(y), y.size, C.byref(nw)))
+        return y[: nw.value]
+
+    def execute_block(self, x):                               # :156-165
+        x = _arr(x, self.T)
+        y = np.empty(max(self.get_num_output(x.size), 1), self.T)
+        nw = C.c_size_t()
+        _check(self._fn("execute_block")(self._h, _ptr(x), x.size, _ptr(y), y.size, C.byref(nw)))
+        return y[: nw.value]
+
+    def execute_block_dev(self, x_dev, nx, y_dev, ny_cap):
+        """nx device samples in; y_dev holds ny_cap samples (>= get_num_output(nx)); returns the outputs written"""
+        nw = C.c_size_t()
+        _check(self._fn("execute_block_dev")(self._h, _devptr(x_dev), nx, _devptr(y_dev), ny_cap, C.byref(nw)))
+        return nw.value
+
+
+class MsResamp(_FirBase):
+    """MsResamp<T,Coeff> (src/filter/resampler/msresamp.rs): any rate > 0 as MsResamp2 half-band stages (Kaiser
+    prototypes, see MsResamp2) around a Resamp for the remaining factor in [0.5, 2]."""
+    DECIM, INTERP = 0, 1
+
+    def __init__(self, kind, rate, as_=60.0):                 # new(rate, as_) :28-79
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_msresamp_{kind}_"
+        hd = C.c_void_p()
+        _check(self._fn("create")(rate, as_, C.byref(hd)))
+        self._h = hd
+
+    def set_scale(self, scale):
+        raise ConfigError("MsResamp has no scale (msresamp.rs)")
+
+    get_scale = set_scale
+
+    def get_rate(self):                                       # :105-107
+        r = C.c_float()
+        _check(self._fn("get_rate")(self._h, C.byref(r)))
+        return np.float32(r.value)
+
+    def get_delay(self):                                      # :87-103
+        d = C.c_float()
+        _check(self._fn("get_delay")(self._h, C.byref(d)))
+        return np.float32(d.value)
+
+    def get_params(self):
+        """(type, number of half-band stages, arbitrary rate)"""
+        it, ns, ra = C.c_int(), C.c_size_t(), C.c_float()
+        _check(self._fn("get_params")(self._h, C.byref(it), C.byref(ns), C.byref(ra)))
+        return it.value, ns.value, np.float32(ra.value)
+
+    def get_num_output(self, num_input):                      # :109-120
+        n = C.c_size_t()
+        _check(self._fn("get_num_output")(self._h, num_input, C.byref(n)))
+        return n.value
+
+    def execute(self, x):                                     # :122-176
+        x = _arr(x, self.T)
+        y = np.empty(max(self.get_num_output(x.size), 1), self.T)
+        nw = C.c_size_t()
+        _check(self._fn("execute")(self._h, _ptr(x), x.size, _ptr(y), y.size, C.byref(nw)))
+        return y[: nw.value]
+
+    def execute_dev(self, x_dev, nx, y_dev, ny_cap):
+        """nx device samples in; y_dev holds ny_cap samples (>= get_num_output(nx)); returns the outputs written"""
+        nw = C.c_size_t()
+        _check(self._fn("execute_dev")(self._h, _devptr(x_dev), nx, _devptr(y_dev), ny_cap, C.byref(nw)))
+        return nw.value
 
 
 class FftFilt(_FirBase):

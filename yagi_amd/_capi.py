@@ -273,3 +273,34 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
     _sig(p + "get_params", vp, C.POINTER(ci), C.POINTER(sz), C.POINTER(f32), vp)
     _sig(p + "execute_block", vp, vp, sz, vp, sz)
     _sig(p + "execute_block_dev", vp, vp, sz, vp, sz)
+
+# ---- Resamp / MsResamp (arbitrary-rate resamplers) ---------------------------------------------
+for _k, (_T, _Cc) in KIND_TYPES.items():
+    p = f"yagi_hip_resamp_{_k}_"
+    _sig(p + "create", f32, sz, f32, f32, sz, pvp)
+    _sig(p + "create_default", f32, pvp)
+    _sig(p + "create_taps", f32, sz, sz, vp, sz, pvp)
+    _sig(p + "destroy", vp)
+    _sig(p + "clone", vp, pvp)
+    _sig(p + "set_stream", vp, vp)
+    _sig(p + "reset", vp)
+    _sig(p + "set_rate", vp, f32)
+    _sig(p + "adjust_rate", vp, f32)
+    _sig(p + "get_rate", vp, C.POINTER(f32))
+    _sig(p + "get_delay", vp, C.POINTER(sz))
+    _sig(p + "get_num_output", vp, sz, C.POINTER(sz))
+    _sig(p + "execute", vp, _T, vp, sz, C.POINTER(sz))
+    _sig(p + "execute_block", vp, vp, sz, vp, sz, C.POINTER(sz))
+    _sig(p + "execute_block_dev", vp, vp, sz, vp, sz, C.POINTER(sz))
+    p = f"yagi_hip_msresamp_{_k}_"
+    _sig(p + "create", f32, f32, pvp)
+    _sig(p + "destroy", vp)
+    _sig(p + "clone", vp, pvp)
+    _sig(p + "set_stream", vp, vp)
+    _sig(p + "reset", vp)
+    _sig(p + "get_rate", vp, C.POINTER(f32))
+    _sig(p + "get_delay", vp, C.POINTER(f32))
+    _sig(p + "get_params", vp, C.POINTER(ci), C.POINTER(sz), C.POINTER(f32))
+    _sig(p + "get_num_output", vp, sz, C.POINTER(sz))
+    _sig(p + "execute", vp, vp, sz, vp, sz, C.POINTER(sz))
+    _sig(p + "execute_dev", vp, vp, sz, vp, sz, C.POINTER(sz))

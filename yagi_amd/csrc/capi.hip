@@ -3149,3 +3149,474 @@ struct MsResamp2Obj {
 YAGI_RESAMP2_IMPL(rrrf, RRRF, float, float)
 YAGI_RESAMP2_IMPL(crcf, CRCF, yagi_cf32, float)
 YAGI_RESAMP2_IMPL(cccf, CCCF, yagi_cf32, yagi_cf32)
+
+// ---- Resamp (src/filter/resampler/resamp.rs) ------------------------------------------------------------
+namespace yagi {
+
+constexpr size_t kResampHostMax = 32;    // execute_block on host data: up to this many inputs on the host mirror
+
+// the kernel stages at least one output's 2m + 1 input samples in its 48 KiB of LDS (fir_kernels.hip: launch_resamp)
+template <class T>
+static int resamp_check_len(size_t m) {
+    if (m > ((size_t)1 << 20) || (2 * m + 1) * sizeof(T) > ((size_t)48 << 10))
+        return fail(YAGI_ERR_CONFIG, "resamp: filter semi-length %zu too large for this engine", m);
+    return YAGI_OK;
+}
+
+template <class K>
+struct ResampObj {
+    using T = typename K::T;
+    using C = typename K::C;
+    FirPfb<K> bank;                      // 2^bits branches of 2m taps (resamp.rs:56)
+    size_t m = 0;
+    int bits = 0;
+    float r = 0.0f;
+    uint32_t step = 0, phase = 0;        // :12-13, 24 fractional bits
+
+    int set_rate(float rate) {                                                       // :95-106
+        if (rate <= 0.0f) return fail(YAGI_ERR_CONFIG, "resampling rate must be greater than zero");
+        if (rate < 0.004f || rate > 250.0f) return fail(YAGI_ERR_CONFIG, "resampling rate must be in [0.004,250]");
+        r = rate;
+        step = (uint32_t)std::round(16777216.0f / r);       // f32 division, half away from zero, as Rust's round()
+        return YAGI_OK;
+    }
+    int init(float rate, size_t m_, size_t npfb, const C *h, size_t h_len) {
+        if (m_ == 0) return fail(YAGI_ERR_CONFIG, "filter semi-length must be greater than zero");
+        if (npfb < 2 || npfb > ((size_t)1 << 16) || (npfb & (npfb - 1)))
+            return fail(YAGI_ERR_CONFIG, "number of filter banks must be a power of two in [2,2^16]");
+        YG_TRY(resamp_check_len<T>(m_));
+        if (h_len < 2 * m_ * npfb) return fail(YAGI_ERR_CONFIG, "resamp: need 2*m*npfb filter coefficients");
+        YG_TRY(bank.init(npfb, h, 2 * m_ * npfb));
+        m = m_;
+        bits = 0;
+        while (((size_t)1 << bits) < npfb) ++bits;
+        YG_TRY(set_rate(rate));
+        phase = 0;
+        return YAGI_OK;
+    }
+    // closed form of get_num_output (:128-139): A_j = phase + j step < 2^24 nx; *next = the phase after the call
+    size_t num_output(size_t nx, uint32_t *next = nullptr) const {
+        const unsigned __int128 end = (unsigned __int128)nx << 24;
+        size_t n = 0;
+        if (end > phase) n = (size_t)((end - phase + step - 1) / step);
+        if (next) *next = (uint32_t)((unsigned __int128)phase + (unsigned __int128)n * step - end);
+        return n;
+    }
+    // execute(x) on the host mirror (:141-154): push, then the branch outputs while phase <= 0xFFFFFF
+    size_t one_host(T x, T *y) {
+        bank.w.push(x);
+        size_t n = 0;
+        while (phase <= 0x00ffffffu) {
+            const uint32_t idx = phase >> (24 - bits);
+            y[n++] = host_fir_window_dot<T, C>(bank.w.host(), (size_t)bank.Ls, bank.hb.data() + (size_t)idx * bank.Ls,
+                                               bank.scale);
+            phase += step;
+        }
+        phase -= 1u << 24;
+        return n;
+    }
+    int block_host_mirror(const T *x, size_t nx, T *y) {
+        YG_TRY(bank.w.ensure_host(bank.st));
+        size_t ny = 0;
+        for (size_t i = 0; i < nx; ++i) ny += one_host(x[i], y + ny);
+        return YAGI_OK;
+    }
+    // nx inputs on the device -> ny = num_output(nx) outputs; window and phase advanced
+    int block_dev(const T *x, size_t nx, T *y, size_t ny) {
+        YG_TRY(bank.w.ensure_dev(bank.st));
+        if (nx == 0) return YAGI_OK;
+        uint32_t next = 0;
+        if (num_output(nx, &next) != ny) return fail(YAGI_ERR_INTERNAL, "resamp: output count mismatch");
+        if (ny == 0) {
+            YG_TRY(bank.w.advance(x, nx, bank.st));
+        } else {
+            YG_TRY((launch_resamp<K>(bank.w.dev(), x, bank.taps.template as<C>(), bank.Ls, bits, step, phase, y, ny, nx,
+                                     bank.st, bank.w.next())));
+            bank.w.flip();                          // the kernel's last workgroup wrote the next window
+        }
+        phase = next;
+        return YAGI_OK;
+    }
+    int block_host(const T *x, size_t nx, T *y, size_t ny) {
+        if (nx == 0) return YAGI_OK;
+        if (nx <= kResampHostMax) return block_host_mirror(x, nx, y);
+        YG_TRY(bank.ws.x.ensure(nx * sizeof(T)));
+        YG_TRY(bank.ws.y.ensure(ny * sizeof(T)));
+        YG_TRY(upload(bank.ws.x.p, x, nx * sizeof(T), bank.st));
+        YG_TRY(block_dev(bank.ws.x.template as<T>(), nx, bank.ws.y.template as<T>(), ny));
+        return download(y, bank.ws.y.p, ny * sizeof(T), bank.st);
+    }
+    int clone_into(ResampObj &o) {                 // derive(Clone) :8
+        YG_TRY(bank.w.ensure_dev(bank.st));
+        o.bank.st = bank.st;
+        o.bank.nf = bank.nf;
+        o.bank.Ls = bank.Ls;
+        o.bank.hb = bank.hb;
+        o.bank.scale = bank.scale;
+        YG_TRY(o.bank.taps.alloc(o.bank.hb.size() * sizeof(C)));
+        YG_TRY(upload(o.bank.taps.p, o.bank.hb.data(), o.bank.hb.size() * sizeof(C), o.bank.st));
+        YG_TRY(o.bank.w.clone_from(bank.w, bank.st));
+        o.m = m; o.bits = bits; o.r = r; o.step = step; o.phase = phase;
+        return YAGI_OK;
+    }
+};
+
+// new(rate, m, fc, as_, npfb) :24-71 up to the bank: checks in the reference's order, Kaiser design of 2 m npfb + 1 taps
+// normalised to DC gain npfb (sequential f32 sum, like iter().sum()); *npfb_out = 2^nextpow2(npfb)
+template <class T, class C>
+static int resamp_design(float rate, size_t m, float fc, float as_, size_t npfb, std::vector<C> &h, size_t *npfb_out) {
+    if (rate <= 0.0f) return fail(YAGI_ERR_CONFIG, "resampling rate must be greater than zero");
+    if (m == 0) return fail(YAGI_ERR_CONFIG, "filter semi-length must be greater than zero");
+    if (fc <= 0.0f || fc >= 0.5f) return fail(YAGI_ERR_CONFIG, "filter cutoff must be in (0,0.5)");
+    if (as_ <= 0.0f) return fail(YAGI_ERR_CONFIG, "filter stop-band suppression must be greater than zero");
+    if (npfb == 0) return fail(YAGI_ERR_VALUE, "nextpow2(), input must be greater than zero");   // math/mod.rs:80-92
+    int bits = 0;
+    while (bits < 64 && ((size_t)1 << bits) < npfb) ++bits;
+    if (bits < 1 || bits > 16) return fail(YAGI_ERR_CONFIG, "number of filter banks must be in (2^0,2^16)");
+    npfb = (size_t)1 << bits;
+    YG_TRY(resamp_check_len<T>(m));
+    std::vector<float> hf;
+    YG_TRY(design_kaiser(2 * m * npfb + 1, fc / (float)npfb, as_, 0.0f, hf));
+    float gain = 0.0f;
+    for (float v : hf) gain += v;
+    gain = (float)npfb / gain;
+    h.resize(hf.size());
+    for (size_t i = 0; i < hf.size(); ++i) h[i] = to_c(hf[i] * gain, (C *)nullptr);
+    *npfb_out = npfb;
+    return YAGI_OK;
+}
+
+}  // namespace yagi
+
+#define YAGI_RESAMP_IMPL(K, KT, T, C)                                                               \
+    struct yagi_hip_resamp_##K##_s : ResampObj<KT> {};                                              \
+    extern "C" {                                                                                    \
+    int yagi_hip_resamp_##K##_create_taps(float rate, size_t m, size_t npfb, const C *h,            \
+                                          size_t h_len, yagi_hip_resamp_##K *q) try {               \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        CHECK_PTR(h);                                                                               \
+        auto o = std::make_unique<yagi_hip_resamp_##K##_s>();                                       \
+        YG_TRY(o->init(rate, m, npfb, h, h_len));                                                   \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_create(float rate, size_t m, float fc, float as_, size_t npfb,        \
+                                     yagi_hip_resamp_##K *q) try {                                  \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        std::vector<C> h;                                                                           \
+        YG_TRY((resamp_design<T, C>(rate, m, fc, as_, npfb, h, &npfb)));                                 \
+        return yagi_hip_resamp_##K##_create_taps(rate, m, npfb, h.data(), h.size(), q);             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_create_default(float rate, yagi_hip_resamp_##K *q) try {  /* :73-84 */ \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        if (rate <= 0.0f) return fail(YAGI_ERR_CONFIG, "resampling rate must be greater than zero"); \
+        return yagi_hip_resamp_##K##_create(rate, 7, 0.25f, 60.0f, 256, q);                         \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_destroy(yagi_hip_resamp_##K q) try { delete q; return YAGI_OK; } catch (...) { return ::yagi::api_exception(); } \
+    int yagi_hip_resamp_##K##_clone(yagi_hip_resamp_##K q, yagi_hip_resamp_##K *out) try {          \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = nullptr;                                                                             \
+        auto o = std::make_unique<yagi_hip_resamp_##K##_s>();                                       \
+        YG_TRY(q->clone_into(*o));                                                                  \
+        *out = o.release();                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_set_stream(yagi_hip_resamp_##K q, yagi_stream_t s) try {              \
+        CHECK_Q(q);                                                                                 \
+        if (q->bank.st == to_stream(s)) return YAGI_OK;                                             \
+        YG_HIP(hipStreamSynchronize(q->bank.st));                                                   \
+        q->bank.st = to_stream(s);                                                                  \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_reset(yagi_hip_resamp_##K q) try {                  /* :86-89 */      \
+        CHECK_Q(q);                                                                                 \
+        q->phase = 0;                                                                               \
+        return q->bank.w.reset(q->bank.st);                                                         \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_set_rate(yagi_hip_resamp_##K q, float rate) try {                     \
+        CHECK_Q(q);                                                                                 \
+        return q->set_rate(rate);                                                                   \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_adjust_rate(yagi_hip_resamp_##K q, float gamma) try { /* :112-118 */  \
+        CHECK_Q(q);                                                                                 \
+        if (gamma <= 0.0f)                                                                          \
+            return fail(YAGI_ERR_CONFIG, "resampling adjustment (%g) must be greater than zero", (double)gamma); \
+        return q->set_rate(q->r * gamma);                                                           \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_get_rate(yagi_hip_resamp_##K q, float *rate) try {                    \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(rate);                                                                            \
+        *rate = q->r;                                                                               \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_get_delay(yagi_hip_resamp_##K q, size_t *delay) try {                 \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(delay);                                                                           \
+        *delay = q->m;                                                                              \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_get_num_output(yagi_hip_resamp_##K q, size_t nx, size_t *ny) try {    \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(ny);                                                                              \
+        *ny = q->num_output(nx);                                                                    \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_execute(yagi_hip_resamp_##K q, T x, T *y, size_t ny_cap, size_t *nw) try { \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(nw);                                                                              \
+        *nw = 0;                                                                                    \
+        const size_t ny = q->num_output(1);                                                         \
+        if (ny > ny_cap) return fail(YAGI_ERR_RANGE, "resamp: output holds %zu samples, %zu needed", ny_cap, ny); \
+        if (ny) CHECK_PTR(y);                                                                       \
+        YG_TRY(q->block_host_mirror(&x, 1, y));                                                     \
+        *nw = ny;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_execute_block(yagi_hip_resamp_##K q, const T *x, size_t nx, T *y,     \
+                                            size_t ny_cap, size_t *nw) try {                        \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(nw);                                                                              \
+        *nw = 0;                                                                                    \
+        const size_t ny = q->num_output(nx);                                                        \
+        if (ny > ny_cap) return fail(YAGI_ERR_RANGE, "resamp: output holds %zu samples, %zu needed", ny_cap, ny); \
+        if (nx == 0) return YAGI_OK;                                                                \
+        CHECK_PTR(x);                                                                               \
+        if (ny) CHECK_PTR(y);                                                                       \
+        YG_TRY(q->block_host(x, nx, y, ny));                                                        \
+        *nw = ny;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_resamp_##K##_execute_block_dev(yagi_hip_resamp_##K q, const T *x, size_t nx, T *y, \
+                                                size_t ny_cap, size_t *nw) try {                    \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(nw);                                                                              \
+        *nw = 0;                                                                                    \
+        const size_t ny = q->num_output(nx);                                                        \
+        if (ny > ny_cap) return fail(YAGI_ERR_RANGE, "resamp: output holds %zu samples, %zu needed", ny_cap, ny); \
+        if (nx == 0) return YAGI_OK;                                                                \
+        CHECK_PTR(x);                                                                               \
+        if (ny) {                                                                                   \
+            CHECK_PTR(y);                                                                           \
+            CHECK_NOALIAS(x, nx, y, ny);                                                            \
+        }                                                                                           \
+        YG_TRY(q->block_dev(x, nx, y, ny));                                                         \
+        *nw = ny;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    }
+
+YAGI_RESAMP_IMPL(rrrf, RRRF, float, float)
+YAGI_RESAMP_IMPL(crcf, CRCF, yagi_cf32, float)
+YAGI_RESAMP_IMPL(cccf, CCCF, yagi_cf32, yagi_cf32)
+
+// ---- MsResamp (src/filter/resampler/msresamp.rs) -------------------------------------------------------
+namespace yagi {
+
+// H2 / HR: the C-ABI object types of MsResamp2 and Resamp of the same type combination (made through their create())
+template <class K, class H2, class HR>
+struct MsResampObj {
+    using T = typename K::T;
+    using C = typename K::C;
+    hipStream_t st = nullptr;
+    bool interp = false;
+    float rate = 0.0f, rate_arbitrary = 0.0f;
+    size_t num_stages = 0;
+    std::unique_ptr<H2> half;            // halfband_resamp :18
+    std::unique_ptr<HR> arb;             // arbitrary_resamp :19
+    DevBuf carry;                        // decimator: the buffer_index (< 2^S) inputs not yet through the half-band chain
+    size_t carry_len = 0;
+    DevBuf mid;                          // the stream between the two parts
+    Workspace ws;
+
+    size_t group() const { return (size_t)1 << num_stages; }
+    size_t num_output(size_t nx) const {                                             // :109-120
+        if (interp) return arb->num_output(nx) << num_stages;
+        return arb->num_output((carry_len + nx) >> num_stages);
+    }
+    float delay() const {                                                            // :87-103
+        const float dh = half->delay(), da = (float)arb->m;
+        if (num_stages == 0) return da;
+        if (interp) return dh / rate_arbitrary + da;
+        return dh + (float)group() * da;
+    }
+    int copy_dev(T *dst, const T *src, size_t n) {
+        if (n) YG_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, st));
+        return YAGI_OK;
+    }
+    // nx inputs -> ny = num_output(nx) outputs, device pointers
+    int exec_dev(const T *x, size_t nx, T *y, size_t ny) {
+        if (nx == 0) return YAGI_OK;
+        if (num_stages == 0) return arb->block_dev(x, nx, y, ny);
+        if (interp) {                                                                // :129-142
+            const size_t n1 = arb->num_output(nx);
+            YG_TRY(mid.ensure(n1 * sizeof(T)));
+            YG_TRY(arb->block_dev(x, nx, mid.template as<T>(), n1));
+            return half->block_dev(mid.template as<T>(), n1, y);
+        }
+        // decimator (:144-168): groups of 2^S inputs through the half-band chain, the first one completing the carry
+        const size_t R = group(), total = carry_len + nx, groups = total >> num_stages, left = total & (R - 1);
+        T *cb = carry.template as<T>();
+        if (groups == 0) {
+            YG_TRY(copy_dev(cb + carry_len, x, nx));
+            carry_len += nx;
+            return YAGI_OK;
+        }
+        YG_TRY(mid.ensure(groups * sizeof(T)));
+        T *mb = mid.template as<T>();
+        size_t g = 0, xo = 0;
+        if (carry_len) {
+            xo = R - carry_len;
+            YG_TRY(copy_dev(cb + carry_len, x, xo));
+            YG_TRY(half->block_dev(cb, 1, mb));
+            g = 1;
+        }
+        if (groups > g) YG_TRY(half->block_dev(x + xo, groups - g, mb + g));
+        YG_TRY(copy_dev(cb, x + (nx - left), left));
+        carry_len = left;
+        return arb->block_dev(mb, groups, y, ny);
+    }
+    int exec_host(const T *x, size_t nx, T *y, size_t ny) {
+        if (nx == 0) return YAGI_OK;
+        YG_TRY(ws.x.ensure(nx * sizeof(T)));
+        YG_TRY(ws.y.ensure(ny * sizeof(T)));
+        YG_TRY(upload(ws.x.p, x, nx * sizeof(T), st));
+        YG_TRY(exec_dev(ws.x.template as<T>(), nx, ws.y.template as<T>(), ny));
+        return download(y, ws.y.p, ny * sizeof(T), st);
+    }
+};
+
+}  // namespace yagi
+
+#define YAGI_MSRESAMP_IMPL(K, KT, T, C)                                                             \
+    struct yagi_hip_msresamp_##K##_s : MsResampObj<KT, yagi_hip_msresamp2_##K##_s, yagi_hip_resamp_##K##_s> {}; \
+    extern "C" {                                                                                    \
+    int yagi_hip_msresamp_##K##_create(float rate, float as_, yagi_hip_msresamp_##K *q) try {       \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        if (rate <= 0.0f) return fail(YAGI_ERR_CONFIG, "resampling rate must be greater than zero"); \
+        auto o = std::make_unique<yagi_hip_msresamp_##K##_s>();                                     \
+        o->rate = rate;                                                                             \
+        o->interp = rate > 1.0f;                                           /* msresamp.rs:33 */     \
+        o->rate_arbitrary = rate;                                                                   \
+        if (o->interp) {                                                   /* :38-51 */             \
+            while (o->rate_arbitrary > 2.0f) { ++o->num_stages; o->rate_arbitrary *= 0.5f; }        \
+        } else {                                                                                    \
+            while (o->rate_arbitrary < 0.5f) { ++o->num_stages; o->rate_arbitrary *= 2.0f; }        \
+        }                                                                                           \
+        yagi_hip_msresamp2_##K h2 = nullptr;                                                        \
+        YG_TRY(yagi_hip_msresamp2_##K##_create(o->interp ? 1 : 0, o->num_stages, 0.4f, 0.0f, as_, &h2)); \
+        o->half.reset(h2);                                                                          \
+        yagi_hip_resamp_##K hr = nullptr;                                                           \
+        const float ra = o->rate_arbitrary;                                                         \
+        YG_TRY(yagi_hip_resamp_##K##_create(ra, 7, std::min(0.515f * ra, 0.49f), as_, 256, &hr));   \
+        o->arb.reset(hr);                                                                           \
+        YG_TRY(o->carry.alloc(o->group() * sizeof(T)));                                             \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_msresamp_##K##_destroy(yagi_hip_msresamp_##K q) try { delete q; return YAGI_OK; } catch (...) { return ::yagi::api_exception(); } \
+    int yagi_hip_msresamp_##K##_clone(yagi_hip_msresamp_##K q, yagi_hip_msresamp_##K *out) try {    \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = nullptr;                                                                             \
+        auto o = std::make_unique<yagi_hip_msresamp_##K##_s>();                                     \
+        o->st = q->st;                                                                              \
+        o->interp = q->interp;                                                                      \
+        o->rate = q->rate;                                                                          \
+        o->rate_arbitrary = q->rate_arbitrary;                                                      \
+        o->num_stages = q->num_stages;                                                              \
+        yagi_hip_msresamp2_##K h2 = nullptr;                                                        \
+        YG_TRY(yagi_hip_msresamp2_##K##_clone(q->half.get(), &h2));                                 \
+        o->half.reset(h2);                                                                          \
+        yagi_hip_resamp_##K hr = nullptr;                                                           \
+        YG_TRY(yagi_hip_resamp_##K##_clone(q->arb.get(), &hr));                                     \
+        o->arb.reset(hr);                                                                           \
+        YG_TRY(o->carry.alloc(o->group() * sizeof(T)));                                             \
+        o->carry_len = q->carry_len;                                                                \
+        YG_TRY(o->copy_dev(o->carry.template as<T>(), q->carry.template as<T>(), q->carry_len));    \
+        YG_HIP(hipStreamSynchronize(o->st));                                                        \
+        *out = o.release();                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_msresamp_##K##_set_stream(yagi_hip_msresamp_##K q, yagi_stream_t s) try {          \
+        CHECK_Q(q);                                                                                 \
+        if (q->st == to_stream(s)) return YAGI_OK;                                                  \
+        YG_HIP(hipStreamSynchronize(q->st));                                                        \
+        YG_TRY(yagi_hip_msresamp2_##K##_set_stream(q->half.get(), s));                              \
+        YG_TRY(yagi_hip_resamp_##K##_set_stream(q->arb.get(), s));                                  \
+        q->st = to_stream(s);                                                                       \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_msresamp_##K##_reset(yagi_hip_msresamp_##K q) try {              /* :81-85 */      \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(yagi_hip_msresamp2_##K##_reset(q->half.get()));                                      \
+        YG_TRY(yagi_hip_resamp_##K##_reset(q->arb.get()));                                          \
+        q->carry_len = 0;                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_msresamp_##K##_get_rate(yagi_hip_msresamp_##K q, float *rate) try {                \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(rate);                                                                            \
+        *rate = q->rate;                                                                            \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_msresamp_##K##_get_delay(yagi_hip_msresamp_##K q, float *delay) try {              \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(delay);                                                                           \
+        *delay = q->delay();                                                                        \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_msresamp_##K##_get_params(yagi_hip_msresamp_##K q, int *interp,                    \
+                                           size_t *num_halfband_stages, float *rate_arbitrary) try { \
+        CHECK_Q(q);                                                                                 \
+        if (interp) *interp = q->interp ? 1 : 0;                                                    \
+        if (num_halfband_stages) *num_halfband_stages = q->num_stages;                              \
+        if (rate_arbitrary) *rate_arbitrary = q->rate_arbitrary;                                    \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_msresamp_##K##_get_num_output(yagi_hip_msresamp_##K q, size_t nx, size_t *ny) try { \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(ny);                                                                              \
+        *ny = q->num_output(nx);                                                                    \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_msresamp_##K##_execute(yagi_hip_msresamp_##K q, const T *x, size_t nx, T *y,       \
+                                        size_t ny_cap, size_t *nw) try {                            \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(nw);                                                                              \
+        *nw = 0;                                                                                    \
+        const size_t ny = q->num_output(nx);                                                        \
+        if (ny > ny_cap) return fail(YAGI_ERR_RANGE, "msresamp: output holds %zu samples, %zu needed", ny_cap, ny); \
+        if (nx == 0) return YAGI_OK;                                                                \
+        CHECK_PTR(x);                                                                               \
+        if (ny) CHECK_PTR(y);                                                                       \
+        YG_TRY(q->exec_host(x, nx, y, ny));                                                         \
+        *nw = ny;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_msresamp_##K##_execute_dev(yagi_hip_msresamp_##K q, const T *x, size_t nx, T *y,   \
+                                            size_t ny_cap, size_t *nw) try {                        \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(nw);                                                                              \
+        *nw = 0;                                                                                    \
+        const size_t ny = q->num_output(nx);                                                        \
+        if (ny > ny_cap) return fail(YAGI_ERR_RANGE, "msresamp: output holds %zu samples, %zu needed", ny_cap, ny); \
+        if (nx == 0) return YAGI_OK;                                                                \
+        CHECK_PTR(x);                                                                               \
+        if (ny) {                                                                                   \
+            CHECK_PTR(y);                                                                           \
+            CHECK_NOALIAS(x, nx, y, ny);                                                            \
+        }                                                                                           \
+        YG_TRY(q->exec_dev(x, nx, y, ny));                                                          \
+        *nw = ny;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    }
+
+YAGI_MSRESAMP_IMPL(rrrf, RRRF, float, float)
+YAGI_MSRESAMP_IMPL(crcf, CRCF, yagi_cf32, float)
+YAGI_MSRESAMP_IMPL(cccf, CCCF, yagi_cf32, yagi_cf32)

@@ -804,4 +804,103 @@ template int launch_rresamp<RRRF>(const float *, const float *, const float *, i
 template int launch_rresamp<CRCF>(const cf32 *, const cf32 *, const float *, int, int, int, float, cf32 *, size_t, hipStream_t, cf32 *);
 template int launch_rresamp<CCCF>(const cf32 *, const cf32 *, const cf32 *, int, int, int, cf32, cf32 *, size_t, hipStream_t, cf32 *);
 
+// ---------------------------------------------------------------------------------------------
+// Resamp<T,Coeff>::execute_block (resamp.rs:141-165).  The control loop only adds integers (phase += step per output,
+// phase -= 2^24 per input), so with A_j = p0 + j*step (64-bit) output j of the call comes after input i_j = A_j >> 24
+// has been pushed and uses branch (A_j & 0xFFFFFF) >> (24 - bits):
+//     y[j] = sum_k hb[b_j][k] X[i_j - k]        (scale 1, firpfb.rs:277-286)
+// One workgroup per `tile` consecutive outputs; the host picks the tile so that the input span
+// [i_{j0} - (Ls-1), i_{j0+tile-1}] fits the LDS.  One lane per output; the bank is gathered through L1/L2.
+// ---------------------------------------------------------------------------------------------
+template <class K>
+__global__ void __launch_bounds__(256)
+resamp_kernel(const typename K::T *__restrict__ win, const typename K::T *__restrict__ x,
+              const typename K::C *__restrict__ hb, int Ls, int bits, uint32_t step, uint32_t p0,
+              typename K::T *__restrict__ y, size_t ny, size_t nx, int tile, typename K::T *__restrict__ win_next) {
+    using T = typename K::T;
+    using C = typename K::C;
+    extern __shared__ __align__(16) unsigned char smem[];
+    T *xs = reinterpret_cast<T *>(smem);
+    write_next_window(win, x, nx, Ls, win_next);
+    const uint64_t j0 = (uint64_t)blockIdx.x * (uint64_t)tile;
+    const int nt = (int)((ny - j0) < (uint64_t)tile ? (ny - j0) : (uint64_t)tile);
+    const uint64_t a0 = (uint64_t)p0 + j0 * step;
+    const uint64_t i_first = a0 >> 24, i_last = (a0 + (uint64_t)(nt - 1) * step) >> 24;
+    const long long base = (long long)i_first - (Ls - 1);
+    const int span = (int)(i_last - i_first) + Ls;
+    batched_for<256>(span, [&](int i) { return load_stream(win, x, base + i, Ls); }, [&](int i, T v) { xs[i] = v; });
+    __syncthreads();
+    const int shift = 24 - bits;
+    for (int o = threadIdx.x; o < nt; o += 256) {
+        const uint64_t a = a0 + (uint64_t)o * step;
+        const int li = (int)((a >> 24) - i_first);
+        const uint32_t br = ((uint32_t)a & 0xFFFFFFu) >> shift;
+        const C *hrow = hb + (size_t)br * Ls;
+        const T *xp = xs + (Ls - 1) + li;
+        // one FMA chain in tap order (bit-identical to the per-sample loop on exact data), four taps' reads together
+        T acc = zero_of<T>();
+        int k = 0;
+        if constexpr (std::is_same<C, float>::value) {
+            if ((Ls & 1) == 0) {                    // even rows (Ls = 2m) start 8-byte aligned: the taps in pairs
+                const float2 *h2 = reinterpret_cast<const float2 *>(hrow);
+                for (; k + 4 <= Ls; k += 4) {
+                    const T x0 = xp[-k], x1 = xp[-k - 1], x2 = xp[-k - 2], x3 = xp[-k - 3];
+                    const float2 ha = h2[k >> 1], hc = h2[(k >> 1) + 1];
+                    acc = mac(acc, x0, ha.x);
+                    acc = mac(acc, x1, ha.y);
+                    acc = mac(acc, x2, hc.x);
+                    acc = mac(acc, x3, hc.y);
+                }
+                if (k < Ls) {
+                    const float2 ha = h2[k >> 1];
+                    acc = mac(acc, xp[-k], ha.x);
+                    acc = mac(acc, xp[-k - 1], ha.y);
+                    k += 2;
+                }
+            }
+        }
+        for (; k + 4 <= Ls; k += 4) {
+            const T x0 = xp[-k], x1 = xp[-k - 1], x2 = xp[-k - 2], x3 = xp[-k - 3];
+            const C h0 = hrow[k], h1 = hrow[k + 1], h2 = hrow[k + 2], h3 = hrow[k + 3];
+            acc = mac(acc, x0, h0);
+            acc = mac(acc, x1, h1);
+            acc = mac(acc, x2, h2);
+            acc = mac(acc, x3, h3);
+        }
+        for (; k < Ls; ++k) acc = mac(acc, xp[-k], hrow[k]);
+        y[j0 + o] = acc;
+    }
+}
+
+// input span of `t` consecutive outputs, an upper bound over every starting phase
+static inline uint64_t resamp_span(uint64_t t, uint32_t step, int Ls) {
+    return (((t - 1) * (uint64_t)step) >> 24) + 1 + (uint64_t)Ls;
+}
+
+template <class K>
+int launch_resamp(const typename K::T *win, const typename K::T *x, const typename K::C *hb, int Ls, int bits,
+                  uint32_t step, uint32_t p0, typename K::T *y, size_t ny, size_t nx, hipStream_t st,
+                  typename K::T *win_next) {
+    using T = typename K::T;
+    if (ny == 0) return YAGI_OK;
+    if (bits < 1 || bits > 16 || step == 0) return fail(YAGI_ERR_CONFIG, "resamp: bad schedule (bits %d, step %u)", bits, step);
+    // outputs per tile: up to 1024 (four per lane), fewer where 1/rate makes the input span outgrow the LDS
+    const uint64_t cap = kFirLdsBudget / sizeof(T);
+    if (resamp_span(1, step, Ls) > cap) return fail(YAGI_ERR_CONFIG, "resamp: branch length %d does not fit the LDS", Ls);
+    uint64_t tile = 1024;
+    const uint64_t room = cap - (uint64_t)Ls - 1;                       // >= 0 after the check above
+    const uint64_t fit = (((room + 1) << 24) - 1) / step + 1;           // largest t with ((t-1) step) >> 24 <= room
+    if (fit < tile) tile = fit;
+    while (tile > 1 && resamp_span(tile, step, Ls) > cap) --tile;
+    const size_t nblk = (ny + tile - 1) / tile;
+    if (nblk > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "block too large");
+    const size_t lds = (size_t)resamp_span(tile, step, Ls) * sizeof(T);
+    resamp_kernel<K><<<(unsigned)nblk, 256, lds, st>>>(win, x, hb, Ls, bits, step, p0, y, ny, nx, (int)tile, win_next);
+    YG_LAUNCH_CHECK();
+    return YAGI_OK;
+}
+template int launch_resamp<RRRF>(const float *, const float *, const float *, int, int, uint32_t, uint32_t, float *, size_t, size_t, hipStream_t, float *);
+template int launch_resamp<CRCF>(const cf32 *, const cf32 *, const float *, int, int, uint32_t, uint32_t, cf32 *, size_t, size_t, hipStream_t, cf32 *);
+template int launch_resamp<CCCF>(const cf32 *, const cf32 *, const cf32 *, int, int, uint32_t, uint32_t, cf32 *, size_t, size_t, hipStream_t, cf32 *);
+
 }  // namespace yagi

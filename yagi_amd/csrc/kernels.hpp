@@ -70,6 +70,14 @@ int launch_rresamp(const typename K::T *win, const typename K::T *x, const typen
                    int Ls, typename K::C scale, typename K::T *y, size_t nblocks, hipStream_t st,
                    typename K::T *win_next = nullptr /* see launch_fir_block */);
 
+// Resamp: ny outputs of one call of nx inputs that starts at phase p0 (u32, 24 fractional bits):
+// A_j = p0 + j*step,  y[j] = sum_k hb[(A_j & 0xFFFFFF) >> (24-bits)][k] X[(A_j >> 24) - k].  Branches hb [2^bits][Ls].
+// win_next: the window after all nx inputs (see launch_fir_block); the caller handles ny == 0 itself.
+template <class K>
+int launch_resamp(const typename K::T *win, const typename K::T *x, const typename K::C *hb, int Ls, int bits,
+                  uint32_t step, uint32_t p0, typename K::T *y, size_t ny, size_t nx, hipStream_t st,
+                  typename K::T *win_next = nullptr);
+
 // ---- stream_kernels.hip (crcf M=1 hot case; headline fused FIR -> 4096-pt FFT) -----------------
 // taps_pad = h zero-padded to Lp = roundup(L, 32) floats.
 constexpr int kSlideMaxTaps = 1024;
