@@ -246,68 +246,91 @@ def test_firpfbch2_sharded_c_abi_rccl_chunked(ya, oracle):
 
 
 def test_config_c4_firpfbch_64ch_full_size(ya, oracle):
-    """BASELINE config C4 at full size: M 64, m 8 (p = 16), 2^26 complex samples generated on the device (runs of
-    256 frames per column group: 16 half tiles each, the prefetch path).  Sampled frames -- first frames, every
-    kind of run / tile boundary, the last frame -- against the oracle run on the p frames that reach them."""
+    """BASELINE config C4 at full size: M 64, m 8 (p = 16), 2^26 complex samples generated on the device = 2^20 frames
+    (4096 workgroups of four runs of 64 frames: 8 half tiles each, one in flight).  Sampled frames -- first frames,
+    run / tile boundaries, the last frame -- against the oracle run on the p frames that reach them, then every frame
+    against the complex128 reference (tests/chan_ref.py) on the device."""
+    import torch
+    from chan_ref import GPU_FRAME_TAU, FirPfbChRef, FrameCheck
     M, m = 64, 8
     p = 2 * m
     h = oracle.fir_design_kaiser(2 * M * m + 1, 0.5 / M, 60.0)
     n = 1 << 26
     nfr = n // M
-    dx = ya.gen_complex_dev(SEED + 4, n)
-    dy = ya.DeviceArray(n, np.complex64)
+    dx = torch.empty(n, dtype=torch.complex64, device="cuda")
+    ya.gen_complex_dev(SEED + 4, n, out=dx)
+    dy = torch.empty(n, dtype=torch.complex64, device="cuda")
     q = ya.FirPfbCh(M, p, h)
     q.analyzer_execute_dev(dx, nfr, dy)
     ya.synchronize()
-    for f in (0, 1, 7, 8, 15, 16, 255, 256, 257, 1023, 1024, 4 * 256 * 1000 + 9, nfr - 257, nfr - 1):
+    for f in (0, 1, 7, 8, 15, 16, 63, 64, 65, 255, 256, 257, 1023, 1024, 4 * 64 * 1000 + 9, 4 * 256 * 1000 + 9,
+              nfr - 257, nfr - 65, nfr - 1):
         lo = max(0, f - (p - 1))
-        xs = dx.to_numpy((f + 1 - lo) * M, offset=lo * M)
+        xs = dx[lo * M: (f + 1) * M].cpu().numpy()
         want = oracle.FirPfbCh(M, p, h).analyzer_execute(xs)[-1]
-        got = dy.to_numpy(M, offset=f * M)
+        got = dy[f * M: (f + 1) * M].cpu().numpy()
         assert rel_l2(got, want) <= 2e-6, f
     # second call continues the stream (history = last p-1 frames of the first block)
-    dx2 = ya.gen_complex_dev(SEED + 4, 64 * M, first=n)
-    dy2 = ya.DeviceArray(64 * M, np.complex64)
+    dx2 = torch.empty(64 * M, dtype=torch.complex64, device="cuda")
+    ya.gen_complex_dev(SEED + 4, 64 * M, out=dx2, first=n)
+    dy2 = torch.empty(64 * M, dtype=torch.complex64, device="cuda")
     q.analyzer_execute_dev(dx2, 64, dy2)
     ya.synchronize()
-    xs = np.concatenate([dx.to_numpy((p - 1) * M, offset=n - (p - 1) * M), dx2.to_numpy(3 * M)])
+    xs = np.concatenate([dx[n - (p - 1) * M:].cpu().numpy(), dx2[: 3 * M].cpu().numpy()])
     want = oracle.FirPfbCh(M, p, h).analyzer_execute(xs)[-3:]
-    assert rel_l2(dy2.to_numpy(3 * M).reshape(3, M), want) <= 2e-6
+    assert rel_l2(dy2[: 3 * M].cpu().numpy().reshape(3, M), want) <= 2e-6
+    ref = FirPfbChRef(M, p, h, device="cuda")
+    fc = FrameCheck(nfr + 64, device="cuda")
+    for xb, yb, base in ((dx, dy, 0), (dx2, dy2, nfr)):
+        for f0, r in ref.analyzer_chunks(xb):
+            fc.add(base + f0, r, yb.view(-1, M)[f0: f0 + r.shape[0]])
+    worst, f, rel = fc.worst()
+    print(f"C4: worst frame ratio {worst:.3e} at frame {f}, rel L2 {rel:.3e}")
+    assert worst <= GPU_FRAME_TAU and rel <= 2e-6, (worst, f, rel)
 
 
 def test_config_c5_firpfbch2_256ch_full_size(ya, oracle):
     """BASELINE config C5 (one GPU's part and the whole band): M 256, m 4, 2^26 complex samples = 524 288 steps
-    (runs of 512 steps).  Sampled steps vs the oracle on the 2m + 1 steps that reach them; one sub-band shard of
-    8 equals the matching channels."""
+    (4096 workgroups, runs of 128 steps).  Sampled steps vs the oracle on the 2m + 1 steps that reach them; one
+    sub-band shard of 8 equals the matching channels; then every step of the whole band and of the shard against the
+    complex128 reference (tests/chan_ref.py) on the device."""
+    import torch
+    from chan_ref import GPU_FRAME_TAU, FirPfbCh2Ref, FrameCheck, shard_columns
     M, m = 256, 4
     M2 = M // 2
     h = oracle.fir_design_kaiser(2 * M * m + 1, 1.0 / M, 60.0)
     h = (h * M / h.sum()).astype(np.float32)
     n = 1 << 26
     ns = n // M2
-    dx = ya.gen_complex_dev(SEED + 5, n)
-    dy = ya.DeviceArray(ns * M, np.complex64)
+    dx = torch.empty(n, dtype=torch.complex64, device="cuda")
+    ya.gen_complex_dev(SEED + 5, n, out=dx)
+    dy = torch.empty(ns * M, dtype=torch.complex64, device="cuda")
     q = ya.FirPfbCh2(M, m, h)
     q.analyzer_execute_dev(dx, ns, dy)
     ya.synchronize()
     reach = 4 * m + 2                                   # history is (2m-1) M + M/2 samples = 4m - 1 steps; even start
-    for s in (0, 1, 2, 15, 16, 17, 511, 512, 513, 512 * 300 + 6, 512 * 300 + 7, ns - 513, ns - 2, ns - 1):
+    for s in (0, 1, 2, 15, 16, 17, 127, 128, 129, 511, 512, 513, 128 * 1200 + 6, 128 * 1200 + 7, 512 * 300 + 6,
+              512 * 300 + 7, ns - 513, ns - 129, ns - 2, ns - 1):
         lo = max(0, s - reach) & ~1                     # even first step keeps the oracle's step parity
-        xs = dx.to_numpy((s + 1 - lo) * M2, offset=lo * M2)
+        xs = dx[lo * M2: (s + 1) * M2].cpu().numpy()
         want = oracle.FirPfbCh2(M, m, h).analyzer_execute(xs)[-1]
-        if lo > 0:                                      # zero history differs from the stream's only beyond reach
-            got = dy.to_numpy(M, offset=s * M)
-            assert rel_l2(got, want) <= 3e-6, s
-        else:
-            assert rel_l2(dy.to_numpy(M, offset=s * M), want) <= 3e-6, s
+        assert rel_l2(dy[s * M: (s + 1) * M].cpu().numpy(), want) <= 3e-6, s
     R, r = 8, 3
-    shard = ya.DeviceArray(ns * (M // R), np.complex64)
+    shard = torch.empty(ns * (M // R), dtype=torch.complex64, device="cuda")
     qs = ya.FirPfbCh2(M, m, h)
     qs.analyzer_execute_shard_dev(dx, ns, r, R, shard)
     ya.synchronize()
     for s in (0, 513, ns - 1):
-        full = dy.to_numpy(M, offset=s * M)
-        assert rel_l2(shard.to_numpy(M // R, offset=s * (M // R)), full[r::R]) <= 3e-6, s
+        full = dy[s * M: (s + 1) * M].cpu().numpy()
+        assert rel_l2(shard[s * (M // R): (s + 1) * (M // R)].cpu().numpy(), full[r::R]) <= 3e-6, s
+    fc, fs = FrameCheck(ns, device="cuda"), FrameCheck(ns, device="cuda")
+    for s0, ref in FirPfbCh2Ref(M, m, h, device="cuda").analyzer_chunks(dx):
+        fc.add(s0, ref, dy.view(ns, M)[s0: s0 + ref.shape[0]])
+        fs.add(s0, shard_columns(ref, r, R), shard.view(ns, M // R)[s0: s0 + ref.shape[0]])
+    for what, c in (("whole band", fc), ("shard", fs)):
+        worst, s, rel = c.worst()
+        print(f"C5 {what}: worst step ratio {worst:.3e} at step {s}, rel L2 {rel:.3e}")
+        assert worst <= GPU_FRAME_TAU and rel <= 3e-6, (what, worst, s, rel)
 
 
 @pytest.mark.parametrize("M,m,nfr", [(4, 2, 50), (8, 4, 333), (64, 8, 200), (6, 3, 77), (10, 2, 100), (256, 4, 65), (1, 3, 20),
