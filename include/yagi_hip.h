@@ -463,6 +463,51 @@ YAGI_MSRESAMP_API(rrrf, float, float)
 YAGI_MSRESAMP_API(crcf, yagi_cf32, float)
 YAGI_MSRESAMP_API(cccf, yagi_cf32, yagi_cf32)
 
+/* ---- IirFilter<T,Coeff>: src/filter/iir/iirfilt.rs:23-481, iirfiltsos.rs:1-127 (infinite impulse response filter) ---
+ *   create(b, nb, a, na)      new() :65-100  transfer function, normalised by a[0] in f32; n = max(na, nb) <= 33 (a
+ *                             config error beyond: f32 TF filters are unusable past about 8 coefficients, :53-56).
+ *                             na != nb: the shorter vector is zero-padded to n (the reference panics there).
+ *   create_sos(b, a, nsos)    new_sos() :111-137  b, a = [nsos][3], each section normalised by its own a0; any nsos
+ *   create_dc_blocker(alpha)  :290-305    create_integrator / create_differentiator :204-288 (Pintelon 8th order, 4
+ *                             sections through iir_design_d2sos)    create_pll(w, zeta, k) :310-330 (active lag)
+ *   clone / reset             derive(Clone) (the copy's VecDeque is contiguous: head 0) / reset() :333-343
+ *   set_scale / get_scale / get_length  (n for TF, 2 nsos for SOS)
+ *   execute / execute_block   :385-407 (nx != ny is a config error); up to 32 host samples run on the host mirror of
+ *                             the state in the reference's order, longer host blocks stage through the device
+ *   execute_block_dev         asynchronous on the object's stream, no host synchronisation; the state stays on the
+ *                             device.  All paths leave the same state, so calls may be mixed.
+ *   freqresponse / get_psd / groupdelay  :416-480 on the host (iir_group_delay, design/mod.rs:771)
+ * Device form: iir_kernels.hip -- chunked state scan with an f64 cross-chunk combine.
+ * new_prototype / new_lowpass (Butterworth, Chebyshev, elliptic, Bessel design) are not provided. */
+#define YAGI_IIRFILT_API(K, T, C)                                                                   \
+    typedef struct yagi_hip_iirfilt_##K##_s *yagi_hip_iirfilt_##K;                                  \
+    int yagi_hip_iirfilt_##K##_create(const C *b, size_t nb, const C *a, size_t na,                 \
+                                      yagi_hip_iirfilt_##K *q);                                     \
+    int yagi_hip_iirfilt_##K##_create_sos(const C *b, const C *a, size_t nsos, yagi_hip_iirfilt_##K *q); \
+    int yagi_hip_iirfilt_##K##_create_dc_blocker(float alpha, yagi_hip_iirfilt_##K *q);             \
+    int yagi_hip_iirfilt_##K##_create_integrator(yagi_hip_iirfilt_##K *q);                          \
+    int yagi_hip_iirfilt_##K##_create_differentiator(yagi_hip_iirfilt_##K *q);                      \
+    int yagi_hip_iirfilt_##K##_create_pll(float w, float zeta, float k, yagi_hip_iirfilt_##K *q);   \
+    int yagi_hip_iirfilt_##K##_destroy(yagi_hip_iirfilt_##K q);                                     \
+    int yagi_hip_iirfilt_##K##_clone(yagi_hip_iirfilt_##K q, yagi_hip_iirfilt_##K *out);            \
+    int yagi_hip_iirfilt_##K##_set_stream(yagi_hip_iirfilt_##K q, yagi_stream_t s);                 \
+    int yagi_hip_iirfilt_##K##_reset(yagi_hip_iirfilt_##K q);                                       \
+    int yagi_hip_iirfilt_##K##_set_scale(yagi_hip_iirfilt_##K q, C scale);                          \
+    int yagi_hip_iirfilt_##K##_get_scale(yagi_hip_iirfilt_##K q, C *scale);                         \
+    int yagi_hip_iirfilt_##K##_get_length(yagi_hip_iirfilt_##K q, size_t *len);                     \
+    int yagi_hip_iirfilt_##K##_execute(yagi_hip_iirfilt_##K q, T x, T *y);                          \
+    int yagi_hip_iirfilt_##K##_execute_block(yagi_hip_iirfilt_##K q, const T *x, size_t nx, T *y,   \
+                                             size_t ny);                                            \
+    int yagi_hip_iirfilt_##K##_execute_block_dev(yagi_hip_iirfilt_##K q, const T *x_dev, size_t n,  \
+                                                 T *y_dev);                                         \
+    int yagi_hip_iirfilt_##K##_freqresponse(yagi_hip_iirfilt_##K q, float fc, yagi_cf32 *H);        \
+    int yagi_hip_iirfilt_##K##_get_psd(yagi_hip_iirfilt_##K q, float fc, float *psd);               \
+    int yagi_hip_iirfilt_##K##_groupdelay(yagi_hip_iirfilt_##K q, float fc, float *gd);
+
+YAGI_IIRFILT_API(rrrf, float, float)
+YAGI_IIRFILT_API(crcf, yagi_cf32, float)
+YAGI_IIRFILT_API(cccf, yagi_cf32, yagi_cf32)
+
 /* Which kernel execute_block uses.  0 = auto (always a direct form), 1 = general direct-form kernels
  * (fir_kernels.hip: register-window kernel for blocks >= 512 samples, interleaved-output kernel below; both add
  * the taps in the reference's order and never touch a tap past h_len, so a NaN poisons exactly h_len outputs),

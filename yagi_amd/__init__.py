@@ -30,7 +30,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "FftFilt", "Fft", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "FftFilt", "Fft", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -819,6 +819,92 @@ class Resamp(_FirBase):
         nw = C.c_size_t()
         _check(self._fn("execute_block_dev")(self._h, _devptr(x_dev), nx, _devptr(y_dev), ny_cap, C.byref(nw)))
         return nw.value
+
+
+class IirFilter(_FirBase):
+    """IirFilter<T,Coeff> (src/filter/iir/iirfilt.rs): transfer-function (n = max(na, nb) <= 33; the shorter of b and
+    a is zero-padded) or second-order-section form.  Block calls on the device run the chunked state scan of
+    iir_kernels.hip; execute() and short host blocks run the reference's recurrence on the host mirror of the state."""
+
+    def __init__(self, kind, b, a):                           # new(b, a) :65-100
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_iirfilt_{kind}_"
+        b, a = _arr(b, self.Cdt), _arr(a, self.Cdt)
+        hd = C.c_void_p()
+        _check(self._fn("create")(_ptr(b), b.size, _ptr(a), a.size, C.byref(hd)))
+        self._h = hd
+
+    @classmethod
+    def _from(cls, kind, creator, *args):
+        self = object.__new__(cls)
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_iirfilt_{kind}_"
+        hd = C.c_void_p()
+        _check(self._fn(creator)(*args, C.byref(hd)))
+        self._h = hd
+        return self
+
+    @classmethod
+    def new_sos(cls, kind, b, a, nsos):                       # :111-137  b, a = [nsos][3]
+        if kind not in KINDS:
+            raise ConfigError(f"unknown type combination {kind!r}")
+        b, a = _arr(b, KINDS[kind][1]).ravel(), _arr(a, KINDS[kind][1]).ravel()
+        if b.size < 3 * nsos or a.size < 3 * nsos:
+            raise ConfigError("second-order sections need 3*nsos coefficients in b and a")
+        return cls._from(kind, "create_sos", _ptr(b), _ptr(a), nsos)
+
+    @classmethod
+    def new_dc_blocker(cls, kind, alpha):                     # :290-305
+        return cls._from(kind, "create_dc_blocker", alpha)
+
+    @classmethod
+    def new_integrator(cls, kind):                            # :204-246
+        return cls._from(kind, "create_integrator")
+
+    @classmethod
+    def new_differentiator(cls, kind):                        # :248-288
+        return cls._from(kind, "create_differentiator")
+
+    @classmethod
+    def new_pll(cls, kind, w, zeta, k):                       # :310-330
+        return cls._from(kind, "create_pll", w, zeta, k)
+
+    def get_length(self):                                     # :410-413
+        n = C.c_size_t()
+        _check(self._fn("get_length")(self._h, C.byref(n)))
+        return n.value
+
+    def execute(self, x):                                     # :385-390
+        y = np.zeros(1, self.T)
+        _check(self._fn("execute")(self._h, _byval(x, self._Tc), _ptr(y)))
+        return y[0]
+
+    def execute_block(self, x, y=None):                       # :393-407
+        x = _arr(x, self.T)
+        if y is None:
+            y = np.empty_like(x)
+        elif y.dtype != self.T or not y.flags.c_contiguous:
+            raise ConfigError("output must be a contiguous array of the sample type")
+        _check(self._fn("execute_block")(self._h, _ptr(x), x.size, _ptr(y), y.size))
+        return y
+
+    def execute_block_dev(self, x_dev, n, y_dev):
+        _check(self._fn("execute_block_dev")(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+    def freqresponse(self, fc):                               # :416-451
+        h = cf32()
+        _check(self._fn("freqresponse")(self._h, fc, C.byref(h)))
+        return np.complex64(complex(h.re, h.im))
+
+    def get_psd(self, fc):                                    # :453-457
+        v = C.c_float()
+        _check(self._fn("get_psd")(self._h, fc, C.byref(v)))
+        return np.float32(v.value)
+
+    def groupdelay(self, fc):                                 # :459-480
+        v = C.c_float()
+        _check(self._fn("groupdelay")(self._h, fc, C.byref(v)))
+        return np.float32(v.value)
 
 
 class MsResamp(_FirBase):

@@ -304,3 +304,26 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
     _sig(p + "get_num_output", vp, sz, C.POINTER(sz))
     _sig(p + "execute", vp, vp, sz, vp, sz, C.POINTER(sz))
     _sig(p + "execute_dev", vp, vp, sz, vp, sz, C.POINTER(sz))
+
+# ---- IirFilter -------------------------------------------------------------------------------------
+for _k, (_T, _Cc) in KIND_TYPES.items():
+    p = f"yagi_hip_iirfilt_{_k}_"
+    _sig(p + "create", vp, sz, vp, sz, pvp)
+    _sig(p + "create_sos", vp, vp, sz, pvp)
+    _sig(p + "create_dc_blocker", f32, pvp)
+    _sig(p + "create_integrator", pvp)
+    _sig(p + "create_differentiator", pvp)
+    _sig(p + "create_pll", f32, f32, f32, pvp)
+    _sig(p + "destroy", vp)
+    _sig(p + "clone", vp, pvp)
+    _sig(p + "set_stream", vp, vp)
+    _sig(p + "reset", vp)
+    _sig(p + "set_scale", vp, _Cc)
+    _sig(p + "get_scale", vp, vp)
+    _sig(p + "get_length", vp, C.POINTER(sz))
+    _sig(p + "execute", vp, _T, vp)
+    _sig(p + "execute_block", vp, vp, sz, vp, sz)
+    _sig(p + "execute_block_dev", vp, vp, sz, vp)
+    _sig(p + "freqresponse", vp, f32, C.POINTER(cf32))
+    _sig(p + "get_psd", vp, f32, C.POINTER(f32))
+    _sig(p + "groupdelay", vp, f32, C.POINTER(f32))

@@ -12,6 +12,7 @@
 // state; reset() zeroes it.
 #include <cmath>
 #include <cstdlib>
+#include <complex>
 #include <memory>
 
 #include <algorithm>
@@ -3620,3 +3621,456 @@ struct MsResampObj {
 YAGI_MSRESAMP_IMPL(rrrf, RRRF, float, float)
 YAGI_MSRESAMP_IMPL(crcf, CRCF, yagi_cf32, float)
 YAGI_MSRESAMP_IMPL(cccf, CCCF, yagi_cf32, yagi_cf32)
+
+// ---- IirFilter (src/filter/iir/iirfilt.rs, iirfiltsos.rs) -----------------------------------------------------------
+// State: TF = the VecDeque's logical v[0 .. n-1) (newest first) plus its physical head, which decides where the
+// reference splits its dot products; SOS = [v0, v1] per section.  A host mirror serves execute() and short host blocks
+// (host.cpp, the reference's order bit for bit); every group of the device path keeps its part of the state in a small
+// device buffer.  The two copies are synchronised lazily, like DevWindow.
+namespace yagi {
+
+template <class T, class C> T host_iir_tf_step(T *s, size_t S, size_t *head, const C *a, const C *b, T x);   // host.cpp
+template <class T, class C> T host_iir_sos_step(T *s, size_t nsec, const C *b, const C *a, T x);
+template <class T, class C> T host_iir_scale(T y, C scale);
+int design_iir_pintelon(bool differentiator, float *b, float *a);
+int design_pll_active_lag(float w, float zeta, float k, float *b, float *a);
+int iir_group_delay(const float *b, size_t nb, const float *a, size_t na, float fc, float *out);
+
+constexpr size_t kIirHostMax = 32;    // execute_block on host data: up to this many samples on the host mirror
+
+static inline float c_re(float v) { return v; }
+static inline float c_re(cf32 v) { return v.re; }
+static inline cf32 c_div(cf32 a, cf32 b) {     // num-complex Div
+    const float d = b.re * b.re + b.im * b.im;
+    return cf32{(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
+}
+static inline float c_div(float a, float b) { return a / b; }
+static inline std::complex<double> c_64(float v) { return {(double)v, 0.0}; }
+static inline std::complex<double> c_64(cf32 v) { return {(double)v.re, (double)v.im}; }
+static inline cf32 c_f32(cf32 v) { return v; }
+static inline cf32 c_f32(float v) { return cf32{v, 0.0f}; }
+static inline cf32 c_mul32(cf32 a, cf32 b) { return cf32{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+static inline cf32 c_add32(cf32 a, cf32 b) { return cf32{a.re + b.re, a.im + b.im}; }
+static inline cf32 c_polar(float th) { return cf32{std::cos(th), std::sin(th)}; }
+
+// one kernel pass: the whole TF filter or up to kIirSosGroup sections
+template <class K>
+struct IirGroup {
+    using M = typename IirF64<K>::M;
+    using V = typename IirF64<K>::V;
+    IirParams<K> p{};
+    size_t off = 0;                 // first state entry of this group in the object's state
+    DevBuf tab, state, z, agg, init;
+
+    // A = the state transition with zero input, column j = one step from the unit state e_j, in f64 from the
+    // normalised f32 coefficients; P_0 = A^T by squaring, P_k = P_{k-1}^2
+    int build(hipStream_t st) {
+        const int S = p.S;
+        using cd = std::complex<double>;
+        std::vector<cd> A((size_t)S * S), s(S), t(S);
+        for (int j = 0; j < S; ++j) {
+            std::fill(s.begin(), s.end(), cd(0.0));
+            s[j] = 1.0;
+            if (!p.sos) {
+                cd w = 0.0;
+                for (int i = 1; i <= S; ++i) w -= c_64(p.a[i]) * s[i - 1];
+                t[0] = w;
+                for (int i = 1; i < S; ++i) t[i] = s[i - 1];
+            } else {
+                cd u = 0.0;
+                for (int k = 0; k < p.n; ++k) {
+                    const cd v1 = s[2 * k], v2 = s[2 * k + 1];
+                    const cd v0 = u - c_64(p.a[3 * k + 1]) * v1 - c_64(p.a[3 * k + 2]) * v2;
+                    u = c_64(p.b[3 * k]) * v0 + c_64(p.b[3 * k + 1]) * v1 + c_64(p.b[3 * k + 2]) * v2;
+                    t[2 * k] = v0;
+                    t[2 * k + 1] = v1;
+                }
+            }
+            for (int i = 0; i < S; ++i) A[(size_t)i * S + j] = t[i];
+        }
+        auto sq = [S](const std::vector<cd> &X) {
+            std::vector<cd> Y((size_t)S * S, cd(0.0));
+            for (int i = 0; i < S; ++i)
+                for (int k = 0; k < S; ++k) {
+                    const cd x = X[(size_t)i * S + k];
+                    if (x == cd(0.0)) continue;
+                    for (int j = 0; j < S; ++j) Y[(size_t)i * S + j] += x * X[(size_t)k * S + j];
+                }
+            return Y;
+        };
+        for (int t2 = 1; t2 < p.T; t2 <<= 1) A = sq(A);
+        std::vector<M> h((size_t)kIirLevels * S * S);
+        for (int k = 0; k < kIirLevels; ++k) {
+            if (k) A = sq(A);
+            for (size_t e = 0; e < (size_t)S * S; ++e) store(h[(size_t)k * S * S + e], A[e]);
+        }
+        YG_TRY(tab.alloc(h.size() * sizeof(M)));
+        YG_TRY(upload(tab.p, h.data(), h.size() * sizeof(M), st));
+        YG_TRY(state.alloc((size_t)S * sizeof(typename K::T)));
+        return YAGI_OK;
+    }
+    static void store(double &d, std::complex<double> v) { d = v.real(); }
+    static void store(dcplx &d, std::complex<double> v) { d = dcplx{v.real(), v.imag()}; }
+    int run(const typename K::T *x, size_t n, typename K::T *y, hipStream_t st) {
+        using T = typename K::T;
+        const size_t nc = (n + (size_t)p.T - 1) / (size_t)p.T;
+        const size_t G = (nc + kIirWg - 1) / kIirWg;
+        YG_TRY(z.ensure(nc * (size_t)p.S * sizeof(T)));
+        YG_TRY(agg.ensure(G * (size_t)p.S * sizeof(V)));
+        YG_TRY(init.ensure(G * (size_t)p.S * sizeof(V)));
+        return launch_iir<K>(p, x, n, y, state.template as<T>(), z.template as<T>(), agg.p, init.p, tab.p, kIirLevels, st);
+    }
+};
+
+template <class K>
+struct IirObj {
+    using T = typename K::T;
+    using C = typename K::C;
+    hipStream_t st = nullptr;
+    bool sos = false;
+    size_t n = 0, nb = 0, na = 0, nsos = 0;     // get_length() = n (TF) or 2 nsos (SOS)
+    std::vector<C> b, a;                        // TF: normalised, zero-padded to n; SOS: normalised per section
+    std::vector<C> braw, araw;                  // SOS: as given (freqresponse reads them, iirfilt.rs:437-447)
+    C scale = one_of<C>();
+    size_t head = 0;                            // TF: the VecDeque's physical head
+    std::vector<T> hs;                          // host mirror of the state
+    bool host_valid = true, dev_valid = true;
+    std::vector<std::unique_ptr<IirGroup<K>>> groups;
+    DevBuf xs, ys, mid;
+
+    size_t S() const { return hs.size(); }
+    static int chunk_len(int S) {               // the combine (2 x 6 levels of S^2 f64 MACs per chunk) <= ~1/4
+        int T = 64;
+        while (T < 256 && T < 8 * S) T <<= 1;
+        return T;
+    }
+    int build() {
+        YG_TRY(require_device());
+        if (!sos) {
+            auto g = std::make_unique<IirGroup<K>>();
+            g->p.sos = 0;
+            g->p.n = (int)n;
+            g->p.S = (int)n - 1;
+            for (size_t i = 0; i < n; ++i) { g->p.b[i] = b[i]; g->p.a[i] = a[i]; }
+            groups.push_back(std::move(g));
+        } else {
+            for (size_t s0 = 0; s0 < nsos; s0 += kIirSosGroup) {
+                auto g = std::make_unique<IirGroup<K>>();
+                const size_t ns = std::min((size_t)kIirSosGroup, nsos - s0);
+                g->p.sos = 1;
+                g->p.n = (int)ns;
+                g->p.S = (int)(2 * ns);
+                g->off = 2 * s0;
+                for (size_t i = 0; i < 3 * ns; ++i) { g->p.b[i] = b[3 * s0 + i]; g->p.a[i] = a[3 * s0 + i]; }
+                groups.push_back(std::move(g));
+            }
+        }
+        for (auto &g : groups) {
+            g->p.T = chunk_len(g->p.S);
+            g->p.scale = one_of<C>();
+            YG_TRY(g->build(st));
+        }
+        hs.assign(sos ? 2 * nsos : n - 1, T{});
+        host_valid = true;
+        dev_valid = false;
+        return YAGI_OK;
+    }
+    int init_tf(const C *b_, size_t nb_, const C *a_, size_t na_) {        // new() :65-100
+        if (nb_ == 0) return fail(YAGI_ERR_CONFIG, "numerator length cannot be zero");
+        if (na_ == 0) return fail(YAGI_ERR_CONFIG, "denominator length cannot be zero");
+        nb = nb_; na = na_;
+        n = std::max(na, nb);
+        if (n > (size_t)kIirTfMaxN)
+            return fail(YAGI_ERR_CONFIG, "iirfilt: transfer-function filters are limited to %d coefficients (got %zu): "
+                        "in f32 they are unusable beyond about 8 (iirfilt.rs:53-56); use second-order sections",
+                        kIirTfMaxN, n);
+        const C a0 = a_[0];
+        b.assign(n, C{});
+        a.assign(n, C{});
+        for (size_t i = 0; i < nb; ++i) b[i] = c_div(b_[i], a0);
+        for (size_t i = 0; i < na; ++i) a[i] = c_div(a_[i], a0);
+        sos = false;
+        return build();
+    }
+    int init_sos(const C *b_, const C *a_, size_t nsos_) {                  // new_sos() :111-137
+        if (nsos_ == 0) return fail(YAGI_ERR_CONFIG, "filter must have at least one 2nd-order section");
+        nsos = nsos_;
+        n = 2 * nsos;
+        braw.assign(b_, b_ + 3 * nsos);
+        araw.assign(a_, a_ + 3 * nsos);
+        b.resize(3 * nsos);
+        a.resize(3 * nsos);
+        for (size_t k = 0; k < nsos; ++k) {                                  // IirFilterSos::set_coefficients
+            const C a0 = a_[3 * k];
+            for (int i = 0; i < 3; ++i) {
+                b[3 * k + i] = c_div(b_[3 * k + i], a0);
+                a[3 * k + i] = c_div(a_[3 * k + i], a0);
+            }
+        }
+        sos = true;
+        return build();
+    }
+    int ensure_host() {
+        if (host_valid) return YAGI_OK;
+        for (auto &g : groups) YG_TRY(download(hs.data() + g->off, g->state.p, (size_t)g->p.S * sizeof(T), st));
+        host_valid = true;
+        return YAGI_OK;
+    }
+    int ensure_dev() {
+        if (dev_valid) return YAGI_OK;
+        for (auto &g : groups) YG_TRY(upload(g->state.p, hs.data() + g->off, (size_t)g->p.S * sizeof(T), st));
+        dev_valid = true;
+        return YAGI_OK;
+    }
+    int reset() {                                                            // :333-343 (the deque keeps its head)
+        std::fill(hs.begin(), hs.end(), T{});
+        host_valid = true;
+        dev_valid = false;
+        return YAGI_OK;
+    }
+    T one_host(T x) {                                                        // execute() :385-390
+        T y = sos ? host_iir_sos_step<T, C>(hs.data(), nsos, b.data(), a.data(), x)
+                  : host_iir_tf_step<T, C>(hs.data(), hs.size(), &head, a.data(), b.data(), x);
+        return host_iir_scale<T, C>(y, scale);
+    }
+    int block_host_mirror(const T *x, size_t nx, T *y) {
+        YG_TRY(ensure_host());
+        dev_valid = false;
+        for (size_t i = 0; i < nx; ++i) y[i] = one_host(x[i]);
+        return YAGI_OK;
+    }
+    int block_dev(const T *x, size_t nx, T *y) {
+        if (nx == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        host_valid = false;
+        const size_t ng = groups.size();
+        if (ng > 1) YG_TRY(mid.ensure(nx * sizeof(T)));
+        const T *in = x;
+        for (size_t g = 0; g < ng; ++g) {
+            IirGroup<K> &G = *groups[g];
+            T *out = ((ng - 1 - g) % 2 == 0) ? y : mid.template as<T>();
+            G.p.scale = (g + 1 == ng) ? scale : one_of<C>();
+            if (!sos) G.p.head0 = (uint32_t)head;
+            YG_TRY(G.run(in, nx, out, st));
+            in = out;
+        }
+        if (!sos) head = (head + n - nx % n) % n;
+        return YAGI_OK;
+    }
+    int block_host(const T *x, size_t nx, T *y) {
+        if (nx == 0) return YAGI_OK;
+        if (nx <= kIirHostMax) return block_host_mirror(x, nx, y);
+        YG_TRY(xs.ensure(nx * sizeof(T)));
+        YG_TRY(ys.ensure(nx * sizeof(T)));
+        YG_TRY(upload(xs.p, x, nx * sizeof(T), st));
+        YG_TRY(block_dev(xs.template as<T>(), nx, ys.template as<T>()));
+        return download(y, ys.p, nx * sizeof(T), st);
+    }
+    // derive(Clone): VecDeque::clone rebuilds the deque contiguously, so the copy's head is 0 (same logical state)
+    int clone_into(IirObj &o) {
+        YG_TRY(ensure_host());
+        o.st = st; o.sos = sos; o.n = n; o.nb = nb; o.na = na; o.nsos = nsos;
+        o.b = b; o.a = a; o.braw = braw; o.araw = araw; o.scale = scale;
+        YG_TRY(o.build());
+        o.hs = hs;
+        o.head = 0;
+        return YAGI_OK;
+    }
+    // freqresponse (:416-451), Complex32 arithmetic as the reference spells it
+    cf32 freqresponse(float fc) const {
+        const float tp = 2.0f * 3.14159265358979323846f;
+        cf32 h;
+        if (!sos) {
+            cf32 hb{0.0f, 0.0f}, ha{0.0f, 0.0f};
+            for (size_t i = 0; i < nb; ++i) hb = c_add32(hb, c_mul32(c_f32(b[i]), c_polar(tp * fc * (float)i)));
+            for (size_t i = 0; i < na; ++i) ha = c_add32(ha, c_mul32(c_f32(a[i]), c_polar(tp * fc * (float)i)));
+            h = c_div(hb, ha);
+        } else {
+            h = cf32{1.0f, 0.0f};
+            for (size_t k = 0; k < nsos; ++k) {
+                const cf32 hb = c_add32(c_add32(c_mul32(c_f32(braw[3 * k]), c_polar(tp * fc * 0.0f)),
+                                                c_mul32(c_f32(braw[3 * k + 1]), c_polar(tp * fc * 1.0f))),
+                                        c_mul32(c_f32(braw[3 * k + 2]), c_polar(tp * fc * 2.0f)));
+                const cf32 ha = c_add32(c_add32(c_mul32(c_f32(araw[3 * k]), c_polar(tp * fc * 0.0f)),
+                                                c_mul32(c_f32(araw[3 * k + 1]), c_polar(tp * fc * 1.0f))),
+                                        c_mul32(c_f32(araw[3 * k + 2]), c_polar(tp * fc * 2.0f)));
+                h = c_mul32(h, c_div(hb, ha));
+            }
+        }
+        return c_mul32(h, c_f32(scale));
+    }
+    int groupdelay(float fc, float *out) const {                             // :454-480
+        if (!sos) {
+            std::vector<float> br(nb), ar(na);
+            for (size_t i = 0; i < nb; ++i) br[i] = c_re(b[i]);
+            for (size_t i = 0; i < na; ++i) ar[i] = c_re(a[i]);
+            return iir_group_delay(br.data(), nb, ar.data(), na, fc, out);
+        }
+        float gd = 0.0f;
+        for (size_t k = 0; k < nsos; ++k) {                                  // iirfiltsos.rs:120-126
+            const float bs[3] = {c_re(b[3 * k]), c_re(b[3 * k + 1]), c_re(b[3 * k + 2])};
+            const float as[3] = {c_re(a[3 * k]), c_re(a[3 * k + 1]), c_re(a[3 * k + 2])};
+            float g = 0.0f;
+            YG_TRY(iir_group_delay(bs, 3, as, 3, fc, &g));
+            gd += (g + 2.0f) - 2.0f;
+        }
+        *out = gd;
+        return YAGI_OK;
+    }
+};
+
+}  // namespace yagi
+
+#define YAGI_IIRFILT_IMPL(K, KT, T, C)                                                              \
+    struct yagi_hip_iirfilt_##K##_s : IirObj<KT> {};                                                \
+    extern "C" {                                                                                    \
+    int yagi_hip_iirfilt_##K##_create(const C *b, size_t nb, const C *a, size_t na,                 \
+                                      yagi_hip_iirfilt_##K *q) try {                                \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        YG_TRY(require_device());                                                                   \
+        if (nb) CHECK_PTR(b);                                                                       \
+        if (na) CHECK_PTR(a);                                                                       \
+        auto o = std::make_unique<yagi_hip_iirfilt_##K##_s>();                                      \
+        YG_TRY(o->init_tf(b, nb, a, na));                                                           \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_create_sos(const C *b, const C *a, size_t nsos,                      \
+                                          yagi_hip_iirfilt_##K *q) try {                            \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        YG_TRY(require_device());                                                                   \
+        if (nsos) { CHECK_PTR(b); CHECK_PTR(a); }                                                   \
+        auto o = std::make_unique<yagi_hip_iirfilt_##K##_s>();                                      \
+        YG_TRY(o->init_sos(b, a, nsos));                                                            \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_create_dc_blocker(float alpha, yagi_hip_iirfilt_##K *q) try {  /* :290-305 */ \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        YG_TRY(require_device());                                                                   \
+        if (alpha <= 0.0f) return fail(YAGI_ERR_CONFIG, "DC-blocking filter bandwidth must be greater than zero"); \
+        const C bf[2] = {to_c(1.0f, (C *)nullptr), to_c(-1.0f, (C *)nullptr)};                     \
+        const C af[2] = {to_c(1.0f, (C *)nullptr), to_c(-1.0f + alpha, (C *)nullptr)};              \
+        YG_TRY(yagi_hip_iirfilt_##K##_create(bf, 2, af, 2, q));                                     \
+        (*q)->scale = to_c(std::sqrt(1.0f - alpha), (C *)nullptr);                                  \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    static int iirfilt_##K##_pintelon(bool diff, yagi_hip_iirfilt_##K *q) {                         \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        YG_TRY(require_device());                                                                   \
+        float bf[12] = {}, af[12] = {};                                                             \
+        YG_TRY(design_iir_pintelon(diff, bf, af));                                                  \
+        C bc[12], ac[12];                                                                           \
+        for (int i = 0; i < 12; ++i) { bc[i] = to_c(bf[i], (C *)nullptr); ac[i] = to_c(af[i], (C *)nullptr); } \
+        return yagi_hip_iirfilt_##K##_create_sos(bc, ac, 4, q);                                     \
+    }                                                                                               \
+    int yagi_hip_iirfilt_##K##_create_integrator(yagi_hip_iirfilt_##K *q) try {  /* :204-246 */     \
+        return iirfilt_##K##_pintelon(false, q);                                                    \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_create_differentiator(yagi_hip_iirfilt_##K *q) try {  /* :248-288 */ \
+        return iirfilt_##K##_pintelon(true, q);                                                     \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_create_pll(float w, float zeta, float k, yagi_hip_iirfilt_##K *q) try { /* :310-330 */ \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        YG_TRY(require_device());                                                                   \
+        if (w <= 0.0f || w >= 1.0f) return fail(YAGI_ERR_CONFIG, "PLL bandwidth must be in (0,1)"); \
+        if (zeta <= 0.0f || zeta >= 1.0f) return fail(YAGI_ERR_CONFIG, "PLL damping factor must be in (0,1)"); \
+        if (k <= 0.0f) return fail(YAGI_ERR_CONFIG, "PLL loop gain must be greater than zero");     \
+        float bf[3], af[3];                                                                         \
+        YG_TRY(design_pll_active_lag(w, zeta, k, bf, af));                                          \
+        C bc[3], ac[3];                                                                             \
+        for (int i = 0; i < 3; ++i) { bc[i] = to_c(bf[i], (C *)nullptr); ac[i] = to_c(af[i], (C *)nullptr); } \
+        return yagi_hip_iirfilt_##K##_create_sos(bc, ac, 1, q);                                     \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_destroy(yagi_hip_iirfilt_##K q) try {                                \
+        if (q) (void)hipStreamSynchronize(q->st);                                                   \
+        delete q;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_clone(yagi_hip_iirfilt_##K q, yagi_hip_iirfilt_##K *out) try {       \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = nullptr;                                                                             \
+        auto o = std::make_unique<yagi_hip_iirfilt_##K##_s>();                                      \
+        YG_TRY(q->clone_into(*o));                                                                  \
+        *out = o.release();                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_set_stream(yagi_hip_iirfilt_##K q, yagi_stream_t s) try {            \
+        CHECK_Q(q);                                                                                 \
+        if (q->st == to_stream(s)) return YAGI_OK;                                                  \
+        YG_HIP(hipStreamSynchronize(q->st));                                                        \
+        q->st = to_stream(s);                                                                       \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_reset(yagi_hip_iirfilt_##K q) try {                                  \
+        CHECK_Q(q);                                                                                 \
+        return q->reset();                                                                          \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_set_scale(yagi_hip_iirfilt_##K q, C scale) try {                     \
+        CHECK_Q(q);                                                                                 \
+        q->scale = scale;                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_get_scale(yagi_hip_iirfilt_##K q, C *scale) try {                    \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(scale);                                                                           \
+        *scale = q->scale;                                                                          \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_get_length(yagi_hip_iirfilt_##K q, size_t *len) try {                \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(len);                                                                             \
+        *len = q->n;                                                                                \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_execute(yagi_hip_iirfilt_##K q, T x, T *y) try {                     \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(y);                                                                               \
+        return q->block_host_mirror(&x, 1, y);                                                      \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_execute_block(yagi_hip_iirfilt_##K q, const T *x, size_t nx, T *y,   \
+                                             size_t ny) try {                                       \
+        CHECK_Q(q);                                                                                 \
+        if (nx != ny) return fail(YAGI_ERR_CONFIG, "input and output block lengths must be equal"); \
+        if (nx == 0) return YAGI_OK;                                                                \
+        CHECK_PTR(x);                                                                               \
+        CHECK_PTR(y);                                                                               \
+        return q->block_host(x, nx, y);                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_execute_block_dev(yagi_hip_iirfilt_##K q, const T *x, size_t n, T *y) try { \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x);                                                                               \
+        CHECK_PTR(y);                                                                               \
+        CHECK_NOALIAS(x, n, y, n);                                                                  \
+        return q->block_dev(x, n, y);                                                               \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_freqresponse(yagi_hip_iirfilt_##K q, float fc, yagi_cf32 *H) try {   \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(H);                                                                               \
+        *H = q->freqresponse(fc);                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_get_psd(yagi_hip_iirfilt_##K q, float fc, float *psd) try { /* :453-457 */ \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(psd);                                                                             \
+        const yagi_cf32 h = q->freqresponse(fc);                                                    \
+        *psd = 10.0f * std::log10(h.re * h.re - h.im * -h.im);                                      \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_groupdelay(yagi_hip_iirfilt_##K q, float fc, float *gd) try {        \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(gd);                                                                              \
+        return q->groupdelay(fc, gd);                                                               \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    }
+
+YAGI_IIRFILT_IMPL(rrrf, RRRF, float, float)
+YAGI_IIRFILT_IMPL(crcf, CRCF, yagi_cf32, float)
+YAGI_IIRFILT_IMPL(cccf, CCCF, yagi_cf32, yagi_cf32)

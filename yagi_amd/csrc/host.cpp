@@ -1,6 +1,7 @@
 // host.cpp -- host-only pieces of libyagi_hip.so: error reporting and the design-time scalar
 // maths the constructors need (Kaiser-windowed sinc taps).  Design code runs once per object
 // on the CPU in the reference as well; it is not on the hot path.
+#include <algorithm>
 #include <cmath>
 
 #include "common.hpp"
@@ -237,6 +238,216 @@ template float host_fir_window_dot<float, float>(const float *, size_t, const fl
 template cf32 host_fir_window_dot<cf32, float>(const cf32 *, size_t, const float *, float);
 template cf32 host_fir_window_dot<cf32, cf32>(const cf32 *, size_t, const cf32 *, cf32);
 
+
+// IirFilter per-sample steps on the host mirror of the state (capi.hip IirObj), in the reference's order.
+// Transfer function (iirfilt.rs:359-374): s = the VecDeque's logical v[0 .. n-1) (newest first), *head = its physical
+// head; rotate_right(1) moves the head back one slot and as_slices() then splits the dot products at n - head
+// (dotprod/mod.rs:75-121: each slice summed left to right from zero, then l + r).  Returns the unscaled output.
+template <class T, class C>
+T host_iir_tf_step(T *s, size_t S, size_t *head, const C *a, const C *b, T x) {
+    const size_t n = S + 1;
+    *head = (*head == 0) ? n - 1 : *head - 1;
+    const size_t split = (*head == 0) ? n : n - *head;
+    T l{}, r{};
+    l = h_add(l, h_mul(T{}, a[0]));                     // v[0] = 0 during the feedback sum
+    for (size_t i = 1; i < n; ++i) {
+        const T q = h_mul(s[i - 1], a[i]);
+        if (i < split) l = h_add(l, q); else r = h_add(r, q);
+    }
+    const T v0 = h_add(l, r);
+    T w;
+    if constexpr (sizeof(T) == sizeof(float)) w = x - v0;
+    else w = T{x.re - v0.re, x.im - v0.im};
+    l = h_add(T{}, h_mul(w, b[0]));
+    r = T{};
+    for (size_t i = 1; i < n; ++i) {
+        const T q = h_mul(s[i - 1], b[i]);
+        if (i < split) l = h_add(l, q); else r = h_add(r, q);
+    }
+    for (size_t i = S; i > 1; --i) s[i - 1] = s[i - 2];
+    if (S) s[0] = w;
+    return h_add(l, r);
+}
+// Second-order sections (iirfiltsos.rs:103-117): s[2k], s[2k+1] = v[0], v[1] of section k; b, a = [nsec][3]
+template <class T, class C>
+T host_iir_sos_step(T *s, size_t nsec, const C *b, const C *a, T x) {
+    T u = x;
+    for (size_t k = 0; k < nsec; ++k) {
+        const T v2 = s[2 * k + 1], v1 = s[2 * k];
+        const T p1 = h_mul(v1, a[3 * k + 1]), p2 = h_mul(v2, a[3 * k + 2]);
+        T v0;
+        if constexpr (sizeof(T) == sizeof(float)) v0 = (u - p1) - p2;
+        else v0 = T{(u.re - p1.re) - p2.re, (u.im - p1.im) - p2.im};
+        u = h_add(h_add(h_mul(v0, b[3 * k]), h_mul(v1, b[3 * k + 1])), h_mul(v2, b[3 * k + 2]));
+        s[2 * k] = v0;
+        s[2 * k + 1] = v1;
+    }
+    return u;
+}
+template <class T, class C> T host_iir_scale(T y, C scale) { return h_mul(y, scale); }
+template float host_iir_tf_step<float, float>(float *, size_t, size_t *, const float *, const float *, float);
+template cf32 host_iir_tf_step<cf32, float>(cf32 *, size_t, size_t *, const float *, const float *, cf32);
+template cf32 host_iir_tf_step<cf32, cf32>(cf32 *, size_t, size_t *, const cf32 *, const cf32 *, cf32);
+template float host_iir_sos_step<float, float>(float *, size_t, const float *, const float *, float);
+template cf32 host_iir_sos_step<cf32, float>(cf32 *, size_t, const float *, const float *, cf32);
+template cf32 host_iir_sos_step<cf32, cf32>(cf32 *, size_t, const cf32 *, const cf32 *, cf32);
+template float host_iir_scale<float, float>(float, float);
+template cf32 host_iir_scale<cf32, float>(cf32, float);
+template cf32 host_iir_scale<cf32, cf32>(cf32, cf32);
+
+// ---- IIR design helpers, f32 like the reference --------------------------------------------------------------------
+namespace {
+struct c32 { float re, im; };
+inline c32 cadd(c32 a, c32 b) { return c32{a.re + b.re, a.im + b.im}; }
+inline c32 cmul(c32 a, c32 b) { return c32{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+inline c32 cneg(c32 a) { return c32{-a.re, -a.im}; }
+inline c32 cconj(c32 a) { return c32{a.re, -a.im}; }
+inline c32 polar(float r, float th) { return c32{r * std::cos(th), r * std::sin(th)}; }
+inline c32 cdiv(c32 a, c32 b) {     // num-complex Div
+    const float d = b.re * b.re + b.im * b.im;
+    return c32{(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
+}
+
+// find_conjugate_pairs + cleanup (design/mod.rs:77-193)
+int cplxpair(const c32 *z, size_t n, float tol, c32 *p) {
+    std::vector<bool> paired(n, false);
+    size_t num_pairs = 0, k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (paired[i] || std::fabs(z[i].im) < tol) continue;
+        for (size_t j = i + 1; j < n; ++j) {
+            if (paired[j] || std::fabs(z[j].im) < tol) continue;
+            if (std::fabs(z[i].im + z[j].im) < tol && std::fabs(z[i].re - z[j].re) < tol) {
+                p[k] = z[i];
+                p[k + 1] = z[j];
+                paired[i] = paired[j] = true;
+                ++num_pairs;
+                k += 2;
+                break;
+            }
+        }
+    }
+    if (k > n) return fail(YAGI_ERR_RANGE, "invalid derived order");
+    for (size_t i = 0; i < n; ++i) {
+        if (paired[i]) continue;
+        if (std::fabs(z[i].im) < tol) {
+            p[k++] = z[i];
+            paired[i] = true;
+        }
+    }
+    for (size_t i = 0; i < num_pairs; ++i) {
+        p[2 * i] = (p[2 * i + 1].im < 0.0f) ? p[2 * i + 1] : cconj(p[2 * i + 1]);
+        p[2 * i + 1] = cconj(p[2 * i]);
+    }
+    for (size_t i = 0; i < num_pairs; ++i)
+        for (size_t j = num_pairs - 1; j > i; --j)
+            if (p[2 * (j - 1)].re > p[2 * j].re) {
+                std::swap(p[2 * (j - 1)], p[2 * j]);
+                std::swap(p[2 * (j - 1) + 1], p[2 * j + 1]);
+            }
+    for (size_t i = 2 * num_pairs; i < n; ++i)
+        for (size_t j = n - 1; j > i; --j)
+            if (p[j - 1].re > p[j].re) std::swap(p[j - 1], p[j]);
+    return YAGI_OK;
+}
+
+// iir_design_d2sos (design/mod.rs:415-502)
+int d2sos(const c32 *zd, const c32 *pd, size_t n, c32 k, float *b, float *a) {
+    const float tol = 1e-6f;
+    std::vector<c32> zp(n), pp(n);
+    if (cplxpair(zd, n, tol, zp.data()) != YAGI_OK) return fail(YAGI_ERR_INTERNAL, "could not associate complex pairs (zeros)");
+    if (cplxpair(pd, n, tol, pp.data()) != YAGI_OK) return fail(YAGI_ERR_INTERNAL, "could not associate complex pairs (poles)");
+    const size_t r = n % 2, L = (n - r) / 2;
+    for (size_t i = 0; i < L; ++i) {
+        const c32 p0 = cneg(pp[2 * i]), p1 = cneg(pp[2 * i + 1]);
+        const c32 z0 = cneg(zp[2 * i]), z1 = cneg(zp[2 * i + 1]);
+        a[3 * i] = 1.0f;
+        a[3 * i + 1] = cadd(p0, p1).re;
+        a[3 * i + 2] = cmul(p0, p1).re;
+        b[3 * i] = 1.0f;
+        b[3 * i + 1] = cadd(z0, z1).re;
+        b[3 * i + 2] = cmul(z0, z1).re;
+    }
+    if (r == 1) {
+        const c32 p0 = cneg(pp[n - 1]), z0 = cneg(zp[n - 1]);
+        a[3 * L] = 1.0f; a[3 * L + 1] = p0.re; a[3 * L + 2] = 0.0f;
+        b[3 * L] = 1.0f; b[3 * L + 1] = z0.re; b[3 * L + 2] = 0.0f;
+    }
+    const float kr = k.re;
+    const float sgn = kr < 0.0f ? -1.0f : 1.0f;
+    const float g = std::pow(kr * sgn, 1.0f / (float)(L + r));
+    for (size_t i = 0; i < L + r; ++i) { b[3 * i] *= g; b[3 * i + 1] *= g; b[3 * i + 2] *= g; }
+    b[0] *= sgn; b[1] *= sgn; b[2] *= sgn;
+    return YAGI_OK;
+}
+}  // namespace
+
+// new_integrator (iirfilt.rs:204-246) / new_differentiator (:248-288): [Pintelon:1990] digital z/p/k -> 4 sections
+int design_iir_pintelon(bool differentiator, float *b, float *a) {
+    const float d = 3.14159265358979323846f / 180.0f;
+    c32 z[8], p[8], k;
+    if (!differentiator) {
+        const float zr[8] = {1.175839f * -1.0f, 3.371020f, 3.371020f, 4.549710f, 4.549710f, 5.223966f, 5.223966f, 5.443743f};
+        const float zt[8] = {0, -125.1125f, 125.1125f, -80.96404f, 80.96404f, -40.09347f, 40.09347f, 0};
+        const float pr[8] = {0.5805235f * -1.0f, 0.2332021f, 0.2332021f, 0.1814755f, 0.1814755f, 0.1641457f, 0.1641457f, 1.0f};
+        const float pt[8] = {0, -114.0968f, 114.0968f, -66.33969f, 66.33969f, -21.89539f, 21.89539f, 0};
+        for (int i = 0; i < 8; ++i) {
+            const bool real = (i == 0 || i == 7);
+            const c32 u = polar(1.0f, d * zt[i]), v = polar(1.0f, d * pt[i]);
+            z[i] = real ? c32{zr[i], 0.0f} : c32{zr[i] * u.re, zr[i] * u.im};
+            p[i] = real ? c32{pr[i], 0.0f} : c32{pr[i] * v.re, pr[i] * v.im};
+        }
+        k = c32{(float)(-1.89213380759321e-05 / 0.9695401191711425781), 0.0f};
+    } else {
+        const float zr[8] = {1.702575f * -1.0f, 5.877385f, 5.877385f, 4.197421f, 4.197421f, 5.350284f, 5.350284f, 1.0f};
+        const float zt[8] = {0, -221.4063f, 221.4063f, -144.5972f, 144.5972f, -66.88802f, 66.88802f, 0};
+        const float pr[8] = {0.8476936f * -1.0f, 0.2990781f, 0.2990781f, 0.2232427f, 0.2232427f, 0.1958670f, 0.1958670f, 0.1886088f};
+        const float pt[8] = {0, -125.5188f, 125.5188f, -81.52326f, 81.52326f, -40.51510f, 40.51510f, 0};
+        for (int i = 0; i < 8; ++i) {
+            const bool real = (i == 0 || i == 7);
+            const c32 u = polar(1.0f, d * zt[i]), v = polar(1.0f, d * pt[i]);
+            z[i] = real ? c32{zr[i], 0.0f} : c32{zr[i] * u.re, zr[i] * u.im};
+            p[i] = real ? c32{pr[i], 0.0f} : c32{pr[i] * v.re, pr[i] * v.im};
+        }
+        k = c32{(float)(2.09049284907492e-05 / 1.033477783203125000), 0.0f};
+    }
+    return d2sos(z, p, 8, k, b, a);
+}
+
+// iir_design_pll_active_lag (design/pll.rs:16-39)
+int design_pll_active_lag(float w, float zeta, float k, float *b, float *a) {
+    if (w <= 0.0f) return fail(YAGI_ERR_CONFIG, "bandwidth must be greater than 0");
+    if (zeta <= 0.0f) return fail(YAGI_ERR_CONFIG, "damping factor must be greater than 0");
+    if (k <= 0.0f) return fail(YAGI_ERR_CONFIG, "gain must be greater than 0");
+    const float wn = w, t1 = k / (wn * wn), t2 = 2.0f * zeta / wn - 1.0f / k;
+    b[0] = 2.0f * k * (1.0f + t2 / 2.0f);
+    b[1] = 2.0f * k * 2.0f;
+    b[2] = 2.0f * k * (1.0f - t2 / 2.0f);
+    a[0] = 1.0f + t1 / 2.0f;
+    a[1] = -t1;
+    a[2] = -1.0f + t1 / 2.0f;
+    return YAGI_OK;
+}
+
+// iir_group_delay (design/mod.rs:771-818)
+int iir_group_delay(const float *b, size_t nb, const float *a, size_t na, float fc, float *out) {
+    if (nb == 0) return fail(YAGI_ERR_CONFIG, "iir_group_delay(), numerator length must be greater than zero");
+    if (na == 0) return fail(YAGI_ERR_CONFIG, "iir_group_delay(), denominator length must be greater than zero");
+    if (fc < -0.5f || fc > 0.5f) return fail(YAGI_ERR_CONFIG, "iir_group_delay(), _fc must be in [-0.5,0.5]");
+    const size_t nc = na + nb - 1;
+    std::vector<float> c(nc, 0.0f);
+    for (size_t i = 0; i < na; ++i)
+        for (size_t j = 0; j < nb; ++j) c[i + j] += a[na - i - 1] * b[j];
+    c32 t0{0.0f, 0.0f}, t1{0.0f, 0.0f};
+    for (size_t i = 0; i < nc; ++i) {
+        const c32 e = polar(1.0f, 2.0f * 3.14159265358979323846f * fc * (float)i);
+        const c32 c0{c[i] * e.re, c[i] * e.im};
+        t0 = cadd(t0, c32{c0.re * (float)i, c0.im * (float)i});
+        t1 = cadd(t1, c0);
+    }
+    if (std::hypot(t1.re, t1.im) < 1e-5f) { *out = 0.0f; return YAGI_OK; }
+    *out = cdiv(t0, t1).re - (float)(na - 1);
+    return YAGI_OK;
+}
 }  // namespace yagi
 
 extern "C" {

@@ -219,4 +219,39 @@ int launch_firpfbch2(const cf32 *hist, int hist_len, const cf32 *x, const float 
 int launch_firpfbch2_assemble(const cf32 *gathered, size_t nsteps, int M, int nranks, cf32 *y,
                               hipStream_t st);
 
+// ---- iir_kernels.hip -----------------------------------------------------------------------
+// IirFilter (src/filter/iir/iirfilt.rs) as a chunked state scan.  The block is cut into chunks of T samples, one per
+// lane, 64 chunks per workgroup.  The state of S entries after a chunk is A^T s0 + z, z = the chunk's final state from
+// zero; the f64 power tables P_k = A^(T 2^k) (host-computed, [levels][S][S]) carry states across chunks.
+//   phase A: every chunk from zero state (f32) -> z[c]; inclusive in-workgroup scan (f64) -> agg[g]
+//   phase B: one workgroup scans agg[0 .. G-1) seeded with the carried state -> init[g] (state before workgroup g)
+//   phase C: every chunk from its exact initial state (f64 scan rounded once to f32) -> y = scale * y; the chunk that
+//            holds the last sample writes the carried state
+constexpr int kIirTfMaxN = 33;    // transfer-function form: n = max(na, nb) <= 33 (S = n - 1 <= 32)
+constexpr int kIirSosGroup = 16;  // second-order sections per kernel pass (longer cascades run as groups)
+constexpr int kIirLevels = 40;    // power-table levels kept per group
+constexpr int kIirWg = 64;        // chunks (lanes) per workgroup
+
+template <class K>
+struct IirParams {
+    typename K::C b[3 * kIirSosGroup];    // TF: b[0..n), a[0..n) normalised, zero-padded to n; SOS: [sec][3]
+    typename K::C a[3 * kIirSosGroup];
+    typename K::C scale;
+    int sos;            // 0: transfer function, 1: second-order sections
+    int n;              // TF: n = S + 1; SOS: sections in this group
+    int S;              // state entries
+    int T;              // chunk length (power of two)
+    uint32_t head0;     // TF: physical head of the reference's VecDeque before the block's first rotate
+};
+// f64 element types of the combine: the state (real for rrrf, complex otherwise) and the matrix (complex for cccf)
+struct dcplx { double re, im; };
+template <class K> struct IirF64 { using V = dcplx; using M = double; };
+template <> struct IirF64<RRRF> { using V = double; using M = double; };
+template <> struct IirF64<CCCF> { using V = dcplx; using M = dcplx; };
+
+// scratch: z [ceil(n/T)][S] of T, agg and init [G][S] of IirF64<K>::V; state: S samples of T, read and rewritten
+template <class K>
+int launch_iir(const IirParams<K> &p, const typename K::T *x, size_t n, typename K::T *y, typename K::T *state,
+               typename K::T *z, void *agg, void *init, const void *ptab, int levels, hipStream_t st);
+
 }  // namespace yagi
