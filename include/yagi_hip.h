@@ -719,6 +719,52 @@ int yagi_hip_firpfbch2_crcf_analyzer_execute_sharded_dev(yagi_hip_firpfbch2_crcf
                                                          size_t nsteps, yagi_hip_comm comm, int nchunks,
                                                          yagi_cf32 *y_dev);
 
+/* ---- Osc: src/nco/osc.rs:13-201, nco.rs, vco.rs (numerically controlled / voltage-controlled oscillator) -------------
+ *   create(scheme)            new() :37-57  YAGI_OSC_NCO (1024-entry sine table, nearest entry) or YAGI_OSC_VCO
+ *                             (1024 {value, skew} pairs, linear interpolation); PLL bandwidth 0.1
+ *   clone / reset             derive(Clone) / reset() :60-63 (theta = d_theta = 0; the PLL gains stay)
+ *   set/adjust_frequency, set/adjust_phase   :66-83 through constrain() :191-201 with wrapping adds; an input the
+ *                             reference never returns from (an infinity, or a magnitude at which adding 2 pi leaves the
+ *                             f32 unchanged) is YAGI_ERR_CONFIG; NaN gives 0 like Rust's saturating `as u32`
+ *   step / get_phase / get_frequency / sin / cos / sin_cos / cexp   :86-133
+ *   pll_set_bandwidth / pll_step   :138-150 (a negative bandwidth is YAGI_ERR_CONFIG: the reference panics)
+ *   mix_up / mix_down         :155-176 on one sample, on the host
+ *   mix_block_up/down         :161-188 on host slices; nx != ny is YAGI_ERR_RANGE.  Up to 4096 samples run on the host,
+ *                             longer slices stage through the device; both give the same bits and the same theta.
+ *   mix_block_up/down_dev     device buffers, asynchronous on the object's stream; x_dev == y_dev (in place) is allowed,
+ *                             any other overlap is YAGI_ERR_CONFIG.  theta advances by n d_theta mod 2^32 at once, so
+ *                             host and device calls may be mixed freely.
+ *   get_state                 EXTENSION (not in the reference): the raw u32 words theta and d_theta.
+ * Every output word equals the reference's sequential loop.  Device form: osc_kernels.hip. */
+#define YAGI_OSC_NCO 0
+#define YAGI_OSC_VCO 1
+typedef struct yagi_hip_osc_s *yagi_hip_osc;
+int yagi_hip_osc_create(int scheme, yagi_hip_osc *q);
+int yagi_hip_osc_destroy(yagi_hip_osc q);
+int yagi_hip_osc_clone(yagi_hip_osc q, yagi_hip_osc *out);
+int yagi_hip_osc_set_stream(yagi_hip_osc q, yagi_stream_t s);
+int yagi_hip_osc_reset(yagi_hip_osc q);
+int yagi_hip_osc_set_frequency(yagi_hip_osc q, float dtheta);
+int yagi_hip_osc_adjust_frequency(yagi_hip_osc q, float df);
+int yagi_hip_osc_set_phase(yagi_hip_osc q, float phi);
+int yagi_hip_osc_adjust_phase(yagi_hip_osc q, float dphi);
+int yagi_hip_osc_step(yagi_hip_osc q);
+int yagi_hip_osc_get_phase(yagi_hip_osc q, float *phi);
+int yagi_hip_osc_get_frequency(yagi_hip_osc q, float *f);
+int yagi_hip_osc_get_state(yagi_hip_osc q, uint32_t *theta, uint32_t *d_theta);
+int yagi_hip_osc_sin(yagi_hip_osc q, float *s);
+int yagi_hip_osc_cos(yagi_hip_osc q, float *c);
+int yagi_hip_osc_sin_cos(yagi_hip_osc q, float *s, float *c);
+int yagi_hip_osc_cexp(yagi_hip_osc q, yagi_cf32 *y);
+int yagi_hip_osc_pll_set_bandwidth(yagi_hip_osc q, float bw);
+int yagi_hip_osc_pll_step(yagi_hip_osc q, float dphi);
+int yagi_hip_osc_mix_up(yagi_hip_osc q, yagi_cf32 x, yagi_cf32 *y);
+int yagi_hip_osc_mix_down(yagi_hip_osc q, yagi_cf32 x, yagi_cf32 *y);
+int yagi_hip_osc_mix_block_up(yagi_hip_osc q, const yagi_cf32 *x, size_t nx, yagi_cf32 *y, size_t ny);
+int yagi_hip_osc_mix_block_down(yagi_hip_osc q, const yagi_cf32 *x, size_t nx, yagi_cf32 *y, size_t ny);
+int yagi_hip_osc_mix_block_up_dev(yagi_hip_osc q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_osc_mix_block_down_dev(yagi_hip_osc q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
+
 /* ---- design helper exposed for hosts that want the taps (kaiser.rs:16-51) ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);
 

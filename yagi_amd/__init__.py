@@ -13,6 +13,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     FirFftStream               the headline composition FirFilter::execute_block -> Fft::run
     Rresamp / Resamp2 / MsResamp2  src/filter/resampler/{rresamp,resamp2,msresamp2}.rs
     Resamp / MsResamp          src/filter/resampler/resamp.rs:8-165, msresamp.rs:10-176
+    Osc, OscScheme             src/nco/osc.rs:13-201 (nco.rs, vco.rs)
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -30,7 +31,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "FftFilt", "Fft", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "Osc", "OscScheme", "FftFilt", "Fft", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -905,6 +906,120 @@ class IirFilter(_FirBase):
         v = C.c_float()
         _check(self._fn("groupdelay")(self._h, fc, C.byref(v)))
         return np.float32(v.value)
+
+
+class OscScheme(enum.Enum):
+    """nco::OscScheme (src/nco/osc.rs:13-17)"""
+    Nco = 0
+    Vco = 1
+
+
+class Osc(_Handle):
+    """nco::Osc (src/nco/osc.rs): NCO (1024-entry sine table) or VCO (interpolated table) with PLL and mixers.  The
+    state (two u32 words, the PLL gains) lives on the host; mix_block_*_dev runs osc_kernels.hip on device arrays and
+    every output word equals the reference's sequential loop."""
+    _prefix = "yagi_hip_osc_"
+
+    def __init__(self, scheme):                               # new() :37-57
+        scheme = OscScheme(scheme)
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_osc_create(scheme.value, C.byref(hd)))
+        self._h = hd
+        self.scheme = scheme
+
+    def clone(self):                                          # derive(Clone)
+        new = object.__new__(type(self))
+        new.scheme = self.scheme
+        h = C.c_void_p()
+        _check(lib.yagi_hip_osc_clone(self._h, C.byref(h)))
+        new._h = h
+        return new
+
+    def set_frequency(self, dtheta):                          # :66-68
+        _check(lib.yagi_hip_osc_set_frequency(self._h, dtheta))
+
+    def adjust_frequency(self, df):                           # :71-73
+        _check(lib.yagi_hip_osc_adjust_frequency(self._h, df))
+
+    def set_phase(self, phi):                                 # :76-78
+        _check(lib.yagi_hip_osc_set_phase(self._h, phi))
+
+    def adjust_phase(self, dphi):                             # :81-83
+        _check(lib.yagi_hip_osc_adjust_phase(self._h, dphi))
+
+    def step(self):                                           # :86-88
+        _check(lib.yagi_hip_osc_step(self._h))
+
+    def _f32(self, name):
+        v = C.c_float()
+        _check(getattr(lib, self._prefix + name)(self._h, C.byref(v)))
+        return np.float32(v.value)
+
+    def get_phase(self):                                      # :91-93
+        return self._f32("get_phase")
+
+    def get_frequency(self):                                  # :96-103
+        return self._f32("get_frequency")
+
+    def sin(self):                                            # :106-111
+        return self._f32("sin")
+
+    def cos(self):                                            # :114-119
+        return self._f32("cos")
+
+    def sin_cos(self):                                        # :122-127  (sin, cos)
+        s, c = C.c_float(), C.c_float()
+        _check(lib.yagi_hip_osc_sin_cos(self._h, C.byref(s), C.byref(c)))
+        return np.float32(s.value), np.float32(c.value)
+
+    def cexp(self):                                           # :130-133
+        v = cf32()
+        _check(lib.yagi_hip_osc_cexp(self._h, C.byref(v)))
+        return np.complex64(complex(v.re, v.im))
+
+    def get_state(self):
+        """extension: the raw u32 words (theta, d_theta)"""
+        t, d = C.c_uint32(), C.c_uint32()
+        _check(lib.yagi_hip_osc_get_state(self._h, C.byref(t), C.byref(d)))
+        return t.value, d.value
+
+    def pll_set_bandwidth(self, bw):                          # :138-144
+        _check(lib.yagi_hip_osc_pll_set_bandwidth(self._h, bw))
+
+    def pll_step(self, dphi):                                 # :147-150
+        _check(lib.yagi_hip_osc_pll_step(self._h, dphi))
+
+    def _mix1(self, name, x):
+        y = cf32()
+        _check(getattr(lib, self._prefix + name)(self._h, _byval(x, cf32), C.byref(y)))
+        return np.complex64(complex(y.re, y.im))
+
+    def mix_up(self, x):                                      # :155-158
+        return self._mix1("mix_up", x)
+
+    def mix_down(self, x):                                    # :173-176
+        return self._mix1("mix_down", x)
+
+    def _block(self, name, x, y):
+        x = _arr(x, np.complex64)
+        if y is None:
+            y = np.empty_like(x)
+        elif not (isinstance(y, np.ndarray) and y.dtype == np.complex64 and y.flags.c_contiguous):
+            raise ConfigError("output must be a C-contiguous complex64 array")
+        _check(getattr(lib, self._prefix + name)(self._h, _ptr(x), x.size, _ptr(y), y.size))
+        return y
+
+    def mix_block_up(self, x, y=None):                        # :161-170 (len(x) != len(y) -> RangeError)
+        return self._block("mix_block_up", x, y)
+
+    def mix_block_down(self, x, y=None):                      # :179-188
+        return self._block("mix_block_down", x, y)
+
+    def mix_block_up_dev(self, x_dev, n, y_dev):
+        _check(lib.yagi_hip_osc_mix_block_up_dev(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+    def mix_block_down_dev(self, x_dev, n, y_dev):
+        _check(lib.yagi_hip_osc_mix_block_down_dev(self._h, _devptr(x_dev), n, _devptr(y_dev)))
 
 
 class MsResamp(_FirBase):

@@ -327,3 +327,26 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
     _sig(p + "freqresponse", vp, f32, C.POINTER(cf32))
     _sig(p + "get_psd", vp, f32, C.POINTER(f32))
     _sig(p + "groupdelay", vp, f32, C.POINTER(f32))
+
+# ---- Osc ---------------------------------------------------------------------------------------
+u32 = C.c_uint32
+_p = "yagi_hip_osc_"
+_sig(_p + "create", ci, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+for _n in ("set_frequency", "adjust_frequency", "set_phase", "adjust_phase", "pll_set_bandwidth", "pll_step"):
+    _sig(_p + _n, vp, f32)
+_sig(_p + "step", vp)
+for _n in ("get_phase", "get_frequency", "sin", "cos"):
+    _sig(_p + _n, vp, C.POINTER(f32))
+_sig(_p + "sin_cos", vp, C.POINTER(f32), C.POINTER(f32))
+_sig(_p + "cexp", vp, C.POINTER(cf32))
+_sig(_p + "get_state", vp, C.POINTER(u32), C.POINTER(u32))
+_sig(_p + "mix_up", vp, cf32, C.POINTER(cf32))
+_sig(_p + "mix_down", vp, cf32, C.POINTER(cf32))
+_sig(_p + "mix_block_up", vp, vp, sz, vp, sz)
+_sig(_p + "mix_block_down", vp, vp, sz, vp, sz)
+_sig(_p + "mix_block_up_dev", vp, vp, sz, vp)
+_sig(_p + "mix_block_down_dev", vp, vp, sz, vp)

@@ -4074,3 +4074,250 @@ struct IirObj {
 YAGI_IIRFILT_IMPL(rrrf, RRRF, float, float)
 YAGI_IIRFILT_IMPL(crcf, CRCF, yagi_cf32, float)
 YAGI_IIRFILT_IMPL(cccf, CCCF, yagi_cf32, yagi_cf32)
+
+// ---- Osc (src/nco/osc.rs, nco.rs, vco.rs) -----------------------------------------------------------------------------
+// The state is the reference's: two u32 words and the PLL gains, kept on the host.  A block call passes theta0 and
+// d_theta to the kernel by value and advances theta by n d_theta mod 2^32 at once, so device calls need no
+// synchronisation and the per-sample calls on the host (host.cpp) always see the carried phase.
+namespace yagi {
+
+void osc_device_table(int vco, std::vector<float> &out);                 // host.cpp
+int osc_constrain(float theta, uint32_t *out);
+float osc_phase(uint32_t theta);
+float osc_frequency(uint32_t d_theta);
+void osc_sin_cos(int vco, uint32_t theta, float *s, float *c);
+cf32 osc_mix(int vco, uint32_t theta, bool down, cf32 x);
+
+constexpr size_t kOscHostMax = 4096;    // mix_block on host slices: up to this many samples on the host
+
+struct OscObj {
+    hipStream_t st = nullptr;
+    int vco = 0;
+    uint32_t theta = 0, d_theta = 0;
+    float alpha = 0.0f, beta = 0.0f;
+    DevBuf tab, xs, ys;
+
+    int init(int scheme) {                                                   // new() :37-57
+        if (scheme != YAGI_OSC_NCO && scheme != YAGI_OSC_VCO) return fail(YAGI_ERR_CONFIG, "osc: unknown scheme %d", scheme);
+        vco = scheme == YAGI_OSC_VCO;
+        std::vector<float> h;
+        osc_device_table(vco, h);
+        YG_TRY(tab.alloc(h.size() * sizeof(float)));
+        YG_TRY(upload(tab.p, h.data(), h.size() * sizeof(float), st));
+        YG_TRY(pll_set_bandwidth(0.1f));                                     // PLL_BANDWIDTH_DEFAULT
+        theta = d_theta = 0;
+        return YAGI_OK;
+    }
+    int pll_set_bandwidth(float bw) {                                        // :138-144
+        if (bw < 0.0f) return fail(YAGI_ERR_CONFIG, "Bandwidth must be positive");
+        alpha = bw;
+        beta = std::sqrt(bw);
+        return YAGI_OK;
+    }
+    int pll_step(float dphi) {                                               // :147-150 (both words first: no half update)
+        uint32_t df = 0, dp = 0;
+        YG_TRY(osc_constrain(dphi * alpha, &df));
+        YG_TRY(osc_constrain(dphi * beta, &dp));
+        d_theta += df;
+        theta += dp;
+        return YAGI_OK;
+    }
+    void block_host(const cf32 *x, size_t n, cf32 *y, bool down) {         // :161-188, mix then step
+        for (size_t i = 0; i < n; ++i) {
+            y[i] = osc_mix(vco, theta, down, x[i]);
+            theta += d_theta;
+        }
+    }
+    int block_dev(const cf32 *x, size_t n, cf32 *y, bool down) {
+        if (n == 0) return YAGI_OK;
+        YG_TRY(launch_osc_mix(vco, down, tab.p, theta, d_theta, x, y, n, st));
+        theta += (uint32_t)n * d_theta;
+        return YAGI_OK;
+    }
+    int block_host_slices(const cf32 *x, size_t n, cf32 *y, bool down) {
+        if (n <= kOscHostMax) {
+            block_host(x, n, y, down);
+            return YAGI_OK;
+        }
+        YG_TRY(xs.ensure(n * sizeof(cf32)));
+        YG_TRY(ys.ensure(n * sizeof(cf32)));
+        YG_TRY(upload(xs.p, x, n * sizeof(cf32), st));
+        YG_TRY(block_dev(xs.as<cf32>(), n, ys.as<cf32>(), down));
+        return download(y, ys.p, n * sizeof(cf32), st);
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_osc_s : OscObj {};
+
+extern "C" {
+
+int yagi_hip_osc_create(int scheme, yagi_hip_osc *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    YG_TRY(require_device());
+    auto o = std::make_unique<yagi_hip_osc_s>();
+    YG_TRY(o->init(scheme));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_destroy(yagi_hip_osc q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_clone(yagi_hip_osc q, yagi_hip_osc *out) try {                  // derive(Clone)
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    auto o = std::make_unique<yagi_hip_osc_s>();
+    o->st = q->st;
+    YG_TRY(o->init(q->vco ? YAGI_OSC_VCO : YAGI_OSC_NCO));
+    o->theta = q->theta;
+    o->d_theta = q->d_theta;
+    o->alpha = q->alpha;
+    o->beta = q->beta;
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_set_stream(yagi_hip_osc q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_reset(yagi_hip_osc q) try {                                     // :60-63
+    CHECK_Q(q);
+    q->theta = q->d_theta = 0;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_set_frequency(yagi_hip_osc q, float dtheta) try {               // :66-68
+    CHECK_Q(q);
+    return osc_constrain(dtheta, &q->d_theta);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_adjust_frequency(yagi_hip_osc q, float df) try {                // :71-73
+    CHECK_Q(q);
+    uint32_t w = 0;
+    YG_TRY(osc_constrain(df, &w));
+    q->d_theta += w;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_set_phase(yagi_hip_osc q, float phi) try {                      // :76-78
+    CHECK_Q(q);
+    return osc_constrain(phi, &q->theta);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_adjust_phase(yagi_hip_osc q, float dphi) try {                  // :81-83
+    CHECK_Q(q);
+    uint32_t w = 0;
+    YG_TRY(osc_constrain(dphi, &w));
+    q->theta += w;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_step(yagi_hip_osc q) try {                                      // :86-88
+    CHECK_Q(q);
+    q->theta += q->d_theta;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_get_phase(yagi_hip_osc q, float *phi) try {                     // :91-93
+    CHECK_Q(q);
+    CHECK_PTR(phi);
+    *phi = osc_phase(q->theta);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_get_frequency(yagi_hip_osc q, float *f) try {                   // :96-103
+    CHECK_Q(q);
+    CHECK_PTR(f);
+    *f = osc_frequency(q->d_theta);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_get_state(yagi_hip_osc q, uint32_t *theta, uint32_t *d_theta) try {   // extension
+    CHECK_Q(q);
+    CHECK_PTR(theta);
+    CHECK_PTR(d_theta);
+    *theta = q->theta;
+    *d_theta = q->d_theta;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_sin(yagi_hip_osc q, float *s) try {                             // :106-111
+    CHECK_Q(q);
+    CHECK_PTR(s);
+    float c = 0.0f;
+    osc_sin_cos(q->vco, q->theta, s, &c);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_cos(yagi_hip_osc q, float *c) try {                             // :114-119
+    CHECK_Q(q);
+    CHECK_PTR(c);
+    float s = 0.0f;
+    osc_sin_cos(q->vco, q->theta, &s, c);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_sin_cos(yagi_hip_osc q, float *s, float *c) try {               // :122-127
+    CHECK_Q(q);
+    CHECK_PTR(s);
+    CHECK_PTR(c);
+    osc_sin_cos(q->vco, q->theta, s, c);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_cexp(yagi_hip_osc q, yagi_cf32 *y) try {                        // :130-133
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    float s = 0.0f, c = 0.0f;
+    osc_sin_cos(q->vco, q->theta, &s, &c);
+    *y = yagi_cf32{c, s};
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_pll_set_bandwidth(yagi_hip_osc q, float bw) try {
+    CHECK_Q(q);
+    return q->pll_set_bandwidth(bw);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_pll_step(yagi_hip_osc q, float dphi) try {
+    CHECK_Q(q);
+    return q->pll_step(dphi);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_mix_up(yagi_hip_osc q, yagi_cf32 x, yagi_cf32 *y) try {         // :155-158
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    *y = osc_mix(q->vco, q->theta, false, x);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_mix_down(yagi_hip_osc q, yagi_cf32 x, yagi_cf32 *y) try {       // :173-176
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    *y = osc_mix(q->vco, q->theta, true, x);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+static int osc_mix_block(yagi_hip_osc q, const yagi_cf32 *x, size_t nx, yagi_cf32 *y, size_t ny, bool down) {
+    CHECK_Q(q);
+    if (nx != ny) return fail(YAGI_ERR_RANGE, "Input and output slices must have the same length");
+    if (nx == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    return q->block_host_slices(x, nx, y, down);
+}
+int yagi_hip_osc_mix_block_up(yagi_hip_osc q, const yagi_cf32 *x, size_t nx, yagi_cf32 *y, size_t ny) try {   // :161-170
+    return osc_mix_block(q, x, nx, y, ny, false);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_mix_block_down(yagi_hip_osc q, const yagi_cf32 *x, size_t nx, yagi_cf32 *y, size_t ny) try { // :179-188
+    return osc_mix_block(q, x, nx, y, ny, true);
+} catch (...) { return ::yagi::api_exception(); }
+static int osc_mix_block_dev(yagi_hip_osc q, const yagi_cf32 *x, size_t n, yagi_cf32 *y, bool down) {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    // in place (x == y) is fine: each lane reads its samples, then writes them; a partial overlap is not
+    if (x != y && x < y + n && y < x + n)
+        return fail(YAGI_ERR_CONFIG, "input and output buffers overlap without being the same buffer");
+    return q->block_dev(x, n, y, down);
+}
+int yagi_hip_osc_mix_block_up_dev(yagi_hip_osc q, const yagi_cf32 *x, size_t n, yagi_cf32 *y) try {
+    return osc_mix_block_dev(q, x, n, y, false);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_osc_mix_block_down_dev(yagi_hip_osc q, const yagi_cf32 *x, size_t n, yagi_cf32 *y) try {
+    return osc_mix_block_dev(q, x, n, y, true);
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"

@@ -448,6 +448,124 @@ int iir_group_delay(const float *b, size_t nb, const float *a, size_t na, float 
     *out = cdiv(t0, t1).re - (float)(na - 1);
     return YAGI_OK;
 }
+
+// ---- Osc (src/nco/osc.rs, nco.rs, vco.rs) ---------------------------------------------------------------------------
+// Both lookup tables, built once in the reference's order with libm sinf, and the per-sample operations on the u32
+// phase.  Every f32 expression is spelled as the reference writes it, one rounding per operation (the x86-64 host
+// target has no FMA, so -ffp-contract cannot fuse anything here).
+namespace {
+constexpr float kOscPi = 3.14159265358979323846f;      // std::f32::consts::PI
+constexpr float kOscTwoPi = 2.0f * kOscPi;             // exact
+
+struct OscTables {
+    float nco[1024];                                   // nco.rs:19-28
+    float vco_v[1024], vco_s[1024];                    // vco.rs:34-77 (value, skew)
+    OscTables() {
+        for (int i = 0; i < 1024; ++i) nco[i] = sinf(2.0f * kOscPi * (float)i / 1024.0f);
+        auto fp_sin = [](uint32_t th) { return sinf((float)th * kOscPi / 2147483648.0f); };   // vco.rs:79-81
+        uint32_t th = 0;
+        const uint32_t dth = 0xFFFFFFFFu / 1024u;      // u32::MAX / 1024 = 2^22 - 1
+        for (int i = 0; i < 256; ++i) {
+            const float value = fp_sin(th);
+            const float next = fp_sin(th + dth);
+            const float skew = (next - value) / (float)dth;
+            vco_v[i] = value;
+            vco_s[i] = skew;
+            vco_v[i + 512] = -value;
+            vco_s[i + 512] = -skew;
+            th += dth;
+        }
+        vco_v[256] = 1.0f;
+        vco_s[256] = -vco_s[255];
+        vco_v[768] = -vco_v[256];
+        vco_s[768] = vco_s[255];
+        for (int i = 1; i < 256; ++i) {                // mirror [0, pi/2] onto [pi/2, pi] and [3pi/2, 2pi]
+            const int k = i + 256;
+            const float value = vco_v[256 - i];
+            const float skew = vco_s[256 - i - 1];
+            vco_v[k] = value;
+            vco_s[k] = -skew;
+            vco_v[k + 512] = -value;
+            vco_s[k + 512] = skew;
+        }
+    }
+};
+const OscTables &osc_tables() {
+    static const OscTables t;                          // thread-safe, built once
+    return t;
+}
+}  // namespace
+
+// the device images: NCO float2 {sin[i], sin[(i + 256) & 1023]}; VCO float4 {v[i], s[i], v[i'], s[i']}, i' = (i + 256) & 1023
+void osc_device_table(int vco, std::vector<float> &out) {
+    const OscTables &t = osc_tables();
+    out.clear();
+    for (int i = 0; i < 1024; ++i) {
+        const int j = (i + 256) & 1023;
+        if (!vco) {
+            out.push_back(t.nco[i]);
+            out.push_back(t.nco[j]);
+        } else {
+            out.push_back(t.vco_v[i]);
+            out.push_back(t.vco_s[i]);
+            out.push_back(t.vco_v[j]);
+            out.push_back(t.vco_s[j]);
+        }
+    }
+}
+
+// constrain (osc.rs:191-201).  Rust's `as u32` saturates (NaN -> 0); the while loops are kept, so 99.0 or -pi land on
+// the reference's word.  Where the reference never returns (an infinity, or a magnitude at which adding 2 pi no
+// longer changes the f32) this is a config error.
+int osc_constrain(float theta, uint32_t *out) {
+    while (theta >= kOscTwoPi) {
+        const float t = theta - kOscTwoPi;
+        if (t == theta) return fail(YAGI_ERR_CONFIG, "osc: phase/frequency %g cannot be reduced modulo 2 pi in f32", theta);
+        theta = t;
+    }
+    while (theta < 0.0f) {
+        const float t = theta + kOscTwoPi;
+        if (t == theta) return fail(YAGI_ERR_CONFIG, "osc: phase/frequency %g cannot be reduced modulo 2 pi in f32", theta);
+        theta = t;
+    }
+    const float v = (theta / kOscTwoPi) * 4294967296.0f;   // u32::MAX as f32 == 2^32
+    if (!(v > 0.0f)) *out = 0u;                             // NaN, zero, negative zero
+    else if (v >= 4294967296.0f) *out = 0xFFFFFFFFu;
+    else *out = (uint32_t)v;
+    return YAGI_OK;
+}
+
+// get_phase / get_frequency (osc.rs:91-103)
+float osc_phase(uint32_t theta) { return 2.0f * kOscPi * (float)theta / 4294967296.0f; }
+float osc_frequency(uint32_t d_theta) {
+    const float d = 2.0f * kOscPi * (float)d_theta / 4294967296.0f;
+    return d > kOscPi ? d - 2.0f * kOscPi : d;
+}
+
+// sin_cos (nco.rs:41-51, vco.rs:99-112)
+void osc_sin_cos(int vco, uint32_t theta, float *s, float *c) {
+    const OscTables &t = osc_tables();
+    if (!vco) {
+        const uint32_t i = ((theta + (1u << 21)) >> 22) & 1023u;
+        *s = t.nco[i];
+        *c = t.nco[(i + 256) & 1023u];
+    } else {
+        const uint32_t i = theta >> 22, j = (i + 256) & 1023u;
+        const float acc = (float)(theta & 0x3FFFFFu);       // == the low 22 bits of theta + 2^30
+        const float ps = acc * t.vco_s[i], pc = acc * t.vco_s[j];
+        *s = t.vco_v[i] + ps;
+        *c = t.vco_v[j] + pc;
+    }
+}
+
+// mix_up / mix_down (osc.rs:155-176): x * (cos + i sin), x * conj(cos + i sin), num_complex's Mul
+cf32 osc_mix(int vco, uint32_t theta, bool down, cf32 x) {
+    float s, c;
+    osc_sin_cos(vco, theta, &s, &c);
+    if (down) s = -s;
+    const float rr = x.re * c, ii = x.im * s, ri = x.re * s, ir = x.im * c;
+    return cf32{rr - ii, ri + ir};
+}
 }  // namespace yagi
 
 extern "C" {

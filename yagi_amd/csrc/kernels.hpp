@@ -254,4 +254,15 @@ template <class K>
 int launch_iir(const IirParams<K> &p, const typename K::T *x, size_t n, typename K::T *y, typename K::T *state,
                typename K::T *z, void *agg, void *init, const void *ptab, int levels, hipStream_t st);
 
+// ---- osc_kernels.hip -----------------------------------------------------------------------
+// Osc::mix_block_up / mix_block_down (src/nco/osc.rs) on device buffers: y[j] = x[j] * (cos + i sin)(theta0 + j dtheta),
+// conjugated for `down`; vco selects the table (host.cpp: osc_device_table, 1024 float2 for the NCO, 1024 float4 for
+// the VCO).  x == y (in place) is allowed; x and y must be 8-byte aligned, 16-byte alignment of both gives 16-byte
+// accesses.
+constexpr int kOscWg = 512;        // threads per workgroup
+constexpr int kOscUnroll = 4;      // loads in flight per lane
+constexpr int kOscWgPerCu = 2;     // persistent grid: 2 workgroups per CU
+int launch_osc_mix(int vco, bool down, const void *tab, uint32_t theta0, uint32_t dtheta, const cf32 *x, cf32 *y,
+                   size_t n, hipStream_t st);
+
 }  // namespace yagi
