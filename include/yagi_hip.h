@@ -765,6 +765,44 @@ int yagi_hip_osc_mix_block_down(yagi_hip_osc q, const yagi_cf32 *x, size_t nx, y
 int yagi_hip_osc_mix_block_up_dev(yagi_hip_osc q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
 int yagi_hip_osc_mix_block_down_dev(yagi_hip_osc q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
 
+/* ---- FirHilbertFilter: src/filter/fir/firhilb.rs:1-263 (FIR Hilbert transform) -------------------------------------
+ *   create(m, as_)            new() :38-84  m < 2 is YAGI_ERR_CONFIG; |as_| is used; hq = 2m taps of the Kaiser
+ *                             half-band filter (4m + 1 taps, fc 0.25) times sin(pi/2 t), every other one reversed
+ *   clone / reset             derive(Clone) / reset() :87-93 (the four windows and the toggle are zeroed)
+ *   r2c_execute               :104-137 one real sample -> one complex sample
+ *   c2r_execute               :149-180 one complex sample -> (lower side-band, upper side-band)
+ *   decim_execute             :191-211 x[0..2) -> one complex sample
+ *   interp_execute            :233-248 one complex sample -> y[0..2)
+ *   decim/interp_execute_block   :220-262 on host slices: decim nx = 2 ny, interp ny = 2 nx, else YAGI_ERR_RANGE
+ *   r2c/c2r_execute_block     EXTENSION: n repeated per-sample calls; r2c ny = nx, c2r ny = 2 nx (the (lsb, usb) pair
+ *                             of input i at y[2i], y[2i + 1]).  Up to 4096 units run on the host, longer slices stage
+ *                             through the device; both give the same bits.
+ *   *_execute_block_dev       device buffers, n units (decim: n outputs from 2n inputs), asynchronous on the object's
+ *                             stream; buffers 4-byte aligned; x and y overlapping is YAGI_ERR_CONFIG.
+ *   design                    EXTENSION: the 2m taps hq, no device needed.
+ * All four modes share the four windows and the toggle, as in the reference, so calls of every mode and form may be
+ * mixed on one object.  Every output word equals the reference's sequential loop.  Device form: firhilb_kernels.hip
+ * (DESIGN.md section 4). */
+typedef struct yagi_hip_firhilb_s *yagi_hip_firhilb;
+int yagi_hip_firhilb_create(size_t m, float as_, yagi_hip_firhilb *q);
+int yagi_hip_firhilb_destroy(yagi_hip_firhilb q);
+int yagi_hip_firhilb_clone(yagi_hip_firhilb q, yagi_hip_firhilb *out);
+int yagi_hip_firhilb_set_stream(yagi_hip_firhilb q, yagi_stream_t s);
+int yagi_hip_firhilb_reset(yagi_hip_firhilb q);
+int yagi_hip_firhilb_r2c_execute(yagi_hip_firhilb q, float x, yagi_cf32 *y);
+int yagi_hip_firhilb_c2r_execute(yagi_hip_firhilb q, yagi_cf32 x, float *y0, float *y1);
+int yagi_hip_firhilb_decim_execute(yagi_hip_firhilb q, const float *x, yagi_cf32 *y);
+int yagi_hip_firhilb_interp_execute(yagi_hip_firhilb q, yagi_cf32 x, float *y);
+int yagi_hip_firhilb_r2c_execute_block(yagi_hip_firhilb q, const float *x, size_t nx, yagi_cf32 *y, size_t ny);
+int yagi_hip_firhilb_c2r_execute_block(yagi_hip_firhilb q, const yagi_cf32 *x, size_t nx, float *y, size_t ny);
+int yagi_hip_firhilb_decim_execute_block(yagi_hip_firhilb q, const float *x, size_t nx, yagi_cf32 *y, size_t ny);
+int yagi_hip_firhilb_interp_execute_block(yagi_hip_firhilb q, const yagi_cf32 *x, size_t nx, float *y, size_t ny);
+int yagi_hip_firhilb_r2c_execute_block_dev(yagi_hip_firhilb q, const float *x_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_firhilb_c2r_execute_block_dev(yagi_hip_firhilb q, const yagi_cf32 *x_dev, size_t n, float *y_dev);
+int yagi_hip_firhilb_decim_execute_block_dev(yagi_hip_firhilb q, const float *x_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_firhilb_interp_execute_block_dev(yagi_hip_firhilb q, const yagi_cf32 *x_dev, size_t n, float *y_dev);
+int yagi_hip_firhilb_design(size_t m, float as_, float *hq);
+
 /* ---- design helper exposed for hosts that want the taps (kaiser.rs:16-51) ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);
 

@@ -31,8 +31,8 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "Osc", "OscScheme", "FftFilt", "Fft", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
-    "fir_design_kaiser", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "Osc", "OscScheme", "FirHilbertFilter", "FftFilt", "Fft", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
 
@@ -185,6 +185,13 @@ def fir_design_kaiser(n, fc, as_, mu=0.0):
     h = np.zeros(max(int(n), 1), np.float32)
     _check(lib.yagi_hip_fir_design_kaiser(n, fc, as_, mu, _ptr(h)))
     return h[:n]
+
+
+def firhilb_design(m, as_):
+    """extension: the 2m quadrature taps hq of FirHilbertFilter::new (src/filter/fir/firhilb.rs:43-64)"""
+    hq = np.zeros(2 * max(int(m), 1), np.float32)
+    _check(lib.yagi_hip_firhilb_design(m, as_, _ptr(hq)))
+    return hq
 
 
 # ---- dotprod (trait DotProd, src/dotprod/mod.rs:13-73) ----------------------------------------
@@ -1020,6 +1027,88 @@ class Osc(_Handle):
 
     def mix_block_down_dev(self, x_dev, n, y_dev):
         _check(lib.yagi_hip_osc_mix_block_down_dev(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+
+class FirHilbertFilter(_Handle):
+    """FirHilbertFilter (src/filter/fir/firhilb.rs): real <-> complex Hilbert transform, 2:1 real-to-complex decimator,
+    1:2 complex-to-real interpolator.  The four windows and the toggle are shared by every mode; the per-sample calls run
+    on the host, the *_dev block forms run firhilb_kernels.hip on device arrays, and every output word equals the
+    reference's sequential loop."""
+    _prefix = "yagi_hip_firhilb_"
+
+    def __init__(self, m, as_):                              # new() :38-84
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_firhilb_create(m, as_, C.byref(hd)))
+        self._h = hd
+        self.m = int(m)
+
+    def clone(self):                                          # derive(Clone)
+        new = object.__new__(type(self))
+        new.m = self.m
+        h = C.c_void_p()
+        _check(lib.yagi_hip_firhilb_clone(self._h, C.byref(h)))
+        new._h = h
+        return new
+
+    def r2c_execute(self, x):                                 # :104-137
+        y = cf32()
+        _check(lib.yagi_hip_firhilb_r2c_execute(self._h, float(np.float32(x)), C.byref(y)))
+        return np.complex64(complex(y.re, y.im))
+
+    def c2r_execute(self, x):                                 # :149-180  (lsb, usb)
+        a, b = C.c_float(), C.c_float()
+        _check(lib.yagi_hip_firhilb_c2r_execute(self._h, _byval(x, cf32), C.byref(a), C.byref(b)))
+        return np.float32(a.value), np.float32(b.value)
+
+    def decim_execute(self, x):                               # :191-211, x: 2 real samples
+        x = _arr(x, np.float32)
+        if x.size < 2:
+            raise RangeError("decim_execute needs 2 input samples")
+        y = cf32()
+        _check(lib.yagi_hip_firhilb_decim_execute(self._h, _ptr(x), C.byref(y)))
+        return np.complex64(complex(y.re, y.im))
+
+    def interp_execute(self, x, y=None):                      # :233-248 -> 2 real samples
+        y = _out(y, 2, np.float32)
+        _check(lib.yagi_hip_firhilb_interp_execute(self._h, _byval(x, cf32), _ptr(y)))
+        return y
+
+    def _block(self, name, x, xdt, y, ydt, ny):
+        x = _arr(x, xdt)
+        y = np.empty(ny(x.size), ydt) if y is None else y
+        if not (isinstance(y, np.ndarray) and y.dtype == np.dtype(ydt) and y.flags.c_contiguous):
+            raise ConfigError(f"output must be a C-contiguous {np.dtype(ydt).name} array")
+        _check(getattr(lib, self._prefix + name)(self._h, _ptr(x), x.size, _ptr(y), y.size))
+        return y
+
+    def decim_execute_block(self, x, y=None):                 # :220-225: 2n real -> n complex (else RangeError)
+        return self._block("decim_execute_block", x, np.float32, y, np.complex64, lambda n: n // 2)
+
+    def interp_execute_block(self, x, y=None):                # :257-262: n complex -> 2n real
+        return self._block("interp_execute_block", x, np.complex64, y, np.float32, lambda n: 2 * n)
+
+    def r2c_execute_block(self, x, y=None):
+        """extension: n repeated r2c_execute calls, n real -> n complex"""
+        return self._block("r2c_execute_block", x, np.float32, y, np.complex64, lambda n: n)
+
+    def c2r_execute_block(self, x, y=None):
+        """extension: n repeated c2r_execute calls, n complex -> 2n real, (lsb, usb) of input i at y[2i], y[2i + 1]"""
+        return self._block("c2r_execute_block", x, np.complex64, y, np.float32, lambda n: 2 * n)
+
+    def _dev(self, name, x_dev, n, y_dev):
+        _check(getattr(lib, self._prefix + name)(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+    def decim_execute_block_dev(self, x_dev, n, y_dev):      # x_dev: 2n float32, y_dev: n complex64
+        self._dev("decim_execute_block_dev", x_dev, n, y_dev)
+
+    def interp_execute_block_dev(self, x_dev, n, y_dev):     # x_dev: n complex64, y_dev: 2n float32
+        self._dev("interp_execute_block_dev", x_dev, n, y_dev)
+
+    def r2c_execute_block_dev(self, x_dev, n, y_dev):        # x_dev: n float32, y_dev: n complex64
+        self._dev("r2c_execute_block_dev", x_dev, n, y_dev)
+
+    def c2r_execute_block_dev(self, x_dev, n, y_dev):        # x_dev: n complex64, y_dev: 2n float32
+        self._dev("c2r_execute_block_dev", x_dev, n, y_dev)
 
 
 class MsResamp(_FirBase):

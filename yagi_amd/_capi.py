@@ -350,3 +350,19 @@ _sig(_p + "mix_block_up", vp, vp, sz, vp, sz)
 _sig(_p + "mix_block_down", vp, vp, sz, vp, sz)
 _sig(_p + "mix_block_up_dev", vp, vp, sz, vp)
 _sig(_p + "mix_block_down_dev", vp, vp, sz, vp)
+
+# ---- FirHilbertFilter --------------------------------------------------------------------------
+_p = "yagi_hip_firhilb_"
+_sig(_p + "create", sz, f32, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "r2c_execute", vp, f32, C.POINTER(cf32))
+_sig(_p + "c2r_execute", vp, cf32, C.POINTER(f32), C.POINTER(f32))
+_sig(_p + "decim_execute", vp, vp, C.POINTER(cf32))
+_sig(_p + "interp_execute", vp, cf32, vp)
+for _n in ("r2c", "c2r", "decim", "interp"):
+    _sig(_p + _n + "_execute_block", vp, vp, sz, vp, sz)
+    _sig(_p + _n + "_execute_block_dev", vp, vp, sz, vp)
+_sig(_p + "design", sz, f32, vp)

@@ -4321,3 +4321,274 @@ int yagi_hip_osc_mix_block_down_dev(yagi_hip_osc q, const yagi_cf32 *x, size_t n
 } catch (...) { return ::yagi::api_exception(); }
 
 }  // extern "C"
+
+// ---- FirHilbertFilter (src/filter/fir/firhilb.rs) ---------------------------------------------------------------------
+// The state is the reference's: four Window<f32> of 2m samples and the toggle.  The per-sample calls run on a host
+// mirror of the four windows (host.cpp: firhilb_dot, the reference's order); block calls run firhilb_kernels.hip on the
+// device copy, which the kernels' state launch rewrites into the other of two buffers.  The two copies are synchronised
+// lazily (DevWindow's pattern), and the host advances the toggle by the call's length at the call, so every mode may
+// follow every other without a reset and without waiting for a kernel.
+namespace yagi {
+
+int firhilb_design(size_t m, float as_, std::vector<float> &hq);          // host.cpp
+float firhilb_dot(const float *hq, const float *w, size_t L);
+
+constexpr size_t kFirhilbHostMax = 4096;    // block calls on host slices: up to this many units on the host
+
+struct FirHilbObj {
+    hipStream_t st = nullptr;
+    int m = 0, L = 0;
+    bool toggle = false;
+    std::vector<float> hq;
+    std::vector<float> hw;               // host mirror: w0, w1, w2, w3, L each, oldest first
+    DevBuf taps, win[2], xs, ys;
+    int cur = 0;
+    bool host_valid = true, dev_valid = true;
+
+    int init(size_t m_, float as_) {                                         // new() :38-84
+        YG_TRY(firhilb_design(m_, as_, hq));
+        m = (int)m_;
+        L = 2 * m;
+        YG_TRY(taps.alloc(hq.size() * sizeof(float)));
+        YG_TRY(upload(taps.p, hq.data(), hq.size() * sizeof(float), st));
+        for (auto &b : win) YG_TRY(b.alloc((size_t)4 * L * sizeof(float)));
+        return reset();
+    }
+    int reset() {                                                            // :87-93
+        hw.assign((size_t)4 * L, 0.0f);
+        YG_HIP(hipMemsetAsync(win[cur].p, 0, (size_t)4 * L * sizeof(float), st));
+        toggle = false;
+        host_valid = dev_valid = true;
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        if (host_valid) return YAGI_OK;
+        YG_TRY(download(hw.data(), win[cur].p, hw.size() * sizeof(float), st));
+        host_valid = true;
+        return YAGI_OK;
+    }
+    int ensure_dev() {
+        if (dev_valid) return YAGI_OK;
+        YG_TRY(upload(win[cur].p, hw.data(), hw.size() * sizeof(float), st));
+        dev_valid = true;
+        return YAGI_OK;
+    }
+    float *w(int i) { return hw.data() + (size_t)i * L; }
+    void push(int i, float v) {                                              // Window::push: drop the oldest
+        float *p = w(i);
+        std::memmove(p, p + 1, (size_t)(L - 1) * sizeof(float));
+        p[L - 1] = v;
+    }
+    float index(int i) { return w(i)[m - 1]; }                               // Window::index(m - 1)
+    float dot(int i) { return firhilb_dot(hq.data(), w(i), (size_t)L); }     // hq.dotprod(window.read())
+
+    // the per-sample calls (after ensure_host)
+    cf32 r2c(float x) {                                                      // :104-137
+        cf32 y;
+        if (!toggle) { push(0, x); y = cf32{index(0), dot(1)}; }
+        else         { push(1, x); y = cf32{index(1), dot(0)}; }
+        toggle = !toggle;
+        dev_valid = false;
+        return y;
+    }
+    void c2r(cf32 x, float *y) {                                             // :149-180
+        float yi, yq;
+        if (!toggle) { push(0, x.re); push(1, x.im); yi = index(0); yq = dot(3); }
+        else         { push(2, x.re); push(3, x.im); yi = index(2); yq = dot(1); }
+        toggle = !toggle;
+        dev_valid = false;
+        y[0] = yi + yq;
+        y[1] = yi - yq;
+    }
+    cf32 decim(const float *x) {                                             // :191-211
+        push(1, x[0]);
+        const float yq = dot(1);
+        push(0, x[1]);
+        const float yi = index(0);
+        cf32 y = toggle ? cf32{-yi, -yq} : cf32{yi, yq};
+        toggle = !toggle;
+        dev_valid = false;
+        return y;
+    }
+    void interp(cf32 x, float *y) {                                          // :233-248
+        const float vi = toggle ? -x.re : x.re, vq = toggle ? -x.im : x.im;
+        push(0, vq);
+        y[0] = index(0);
+        push(1, vi);
+        y[1] = dot(1);
+        toggle = !toggle;
+        dev_valid = false;
+    }
+    void block_host(int mode, const float *x, size_t n, float *y) {
+        for (size_t i = 0; i < n; ++i) {
+            switch (mode) {
+            case FIRHILB_R2C: { const cf32 v = r2c(x[i]); y[2 * i] = v.re; y[2 * i + 1] = v.im; break; }
+            case FIRHILB_C2R: c2r(cf32{x[2 * i], x[2 * i + 1]}, y + 2 * i); break;
+            case FIRHILB_DECIM: { const cf32 v = decim(x + 2 * i); y[2 * i] = v.re; y[2 * i + 1] = v.im; break; }
+            default: interp(cf32{x[2 * i], x[2 * i + 1]}, y + 2 * i); break;
+            }
+        }
+    }
+    int block_dev(int mode, const float *x, size_t n, float *y) {
+        if (n == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        const int nxt = cur ^ 1;
+        YG_TRY(launch_firhilb(mode, m, taps.as<float>(), win[cur].as<float>(), win[nxt].as<float>(), toggle ? 1 : 0,
+                              x, n, y, st));
+        cur = nxt;
+        host_valid = false;
+        if (n & 1) toggle = !toggle;
+        return YAGI_OK;
+    }
+    int block_host_slices(int mode, const float *x, size_t n, float *y) {
+        const size_t xf = (mode == FIRHILB_R2C) ? n : 2 * n;                  // floats in and out
+        const size_t yf = 2 * n;
+        if (n <= kFirhilbHostMax) {
+            YG_TRY(ensure_host());
+            block_host(mode, x, n, y);
+            return YAGI_OK;
+        }
+        YG_TRY(xs.ensure(xf * sizeof(float)));
+        YG_TRY(ys.ensure(yf * sizeof(float)));
+        YG_TRY(upload(xs.p, x, xf * sizeof(float), st));
+        YG_TRY(block_dev(mode, xs.as<float>(), n, ys.as<float>()));
+        return download(y, ys.p, yf * sizeof(float), st);
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_firhilb_s : FirHilbObj {};
+
+extern "C" {
+
+int yagi_hip_firhilb_create(size_t m, float as_, yagi_hip_firhilb *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    YG_TRY(require_device());
+    auto o = std::make_unique<yagi_hip_firhilb_s>();
+    YG_TRY(o->init(m, as_));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_destroy(yagi_hip_firhilb q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_clone(yagi_hip_firhilb q, yagi_hip_firhilb *out) try {       // derive(Clone)
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_firhilb_s>();
+    o->st = q->st;
+    o->m = q->m;
+    o->L = q->L;
+    o->hq = q->hq;
+    YG_TRY(o->taps.alloc(o->hq.size() * sizeof(float)));
+    YG_TRY(upload(o->taps.p, o->hq.data(), o->hq.size() * sizeof(float), o->st));
+    for (auto &b : o->win) YG_TRY(b.alloc((size_t)4 * o->L * sizeof(float)));
+    o->hw = q->hw;
+    o->toggle = q->toggle;
+    o->host_valid = true;
+    o->dev_valid = false;
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_set_stream(yagi_hip_firhilb q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_reset(yagi_hip_firhilb q) try {                              // :87-93
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_r2c_execute(yagi_hip_firhilb q, float x, yagi_cf32 *y) try {          // :104-137
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    YG_TRY(q->ensure_host());
+    *y = q->r2c(x);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_c2r_execute(yagi_hip_firhilb q, yagi_cf32 x, float *y0, float *y1) try {   // :149-180
+    CHECK_Q(q);
+    CHECK_PTR(y0);
+    CHECK_PTR(y1);
+    YG_TRY(q->ensure_host());
+    float y[2];
+    q->c2r(x, y);
+    *y0 = y[0];
+    *y1 = y[1];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_decim_execute(yagi_hip_firhilb q, const float *x, yagi_cf32 *y) try { // :191-211, x[0..2)
+    CHECK_Q(q);
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    YG_TRY(q->ensure_host());
+    *y = q->decim(x);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_interp_execute(yagi_hip_firhilb q, yagi_cf32 x, float *y) try {       // :233-248, y[0..2)
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    YG_TRY(q->ensure_host());
+    q->interp(x, y);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+// host slices: nx and ny are element counts of the caller's arrays; n = the number of units
+static int firhilb_block(yagi_hip_firhilb q, int mode, const void *x, size_t nx, void *y, size_t ny) {
+    CHECK_Q(q);
+    size_t n = 0;
+    bool ok = false;
+    switch (mode) {
+    case FIRHILB_R2C: n = nx; ok = ny == nx; break;                // n real -> n complex
+    case FIRHILB_C2R: n = nx; ok = ny == 2 * nx; break;            // n complex -> 2n real
+    case FIRHILB_DECIM: n = ny; ok = nx == 2 * ny; break;          // 2n real -> n complex
+    default: n = nx; ok = ny == 2 * nx; break;                     // n complex -> 2n real
+    }
+    if (!ok) return fail(YAGI_ERR_RANGE, "firhilb: input (%zu) and output (%zu) lengths do not match", nx, ny);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    return q->block_host_slices(mode, static_cast<const float *>(x), n, static_cast<float *>(y));
+}
+static int firhilb_block_dev(yagi_hip_firhilb q, int mode, const void *x, size_t n, void *y) {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    const size_t xb = (mode == FIRHILB_R2C ? n : 2 * n) * sizeof(float), yb = 2 * n * sizeof(float);
+    YG_TRY(check_noalias(x, xb, y, yb));
+    return q->block_dev(mode, static_cast<const float *>(x), n, static_cast<float *>(y));
+}
+int yagi_hip_firhilb_r2c_execute_block(yagi_hip_firhilb q, const float *x, size_t nx, yagi_cf32 *y, size_t ny) try {
+    return firhilb_block(q, FIRHILB_R2C, x, nx, y, ny);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_c2r_execute_block(yagi_hip_firhilb q, const yagi_cf32 *x, size_t nx, float *y, size_t ny) try {
+    return firhilb_block(q, FIRHILB_C2R, x, nx, y, ny);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_decim_execute_block(yagi_hip_firhilb q, const float *x, size_t nx, yagi_cf32 *y, size_t ny) try {
+    return firhilb_block(q, FIRHILB_DECIM, x, nx, y, ny);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_interp_execute_block(yagi_hip_firhilb q, const yagi_cf32 *x, size_t nx, float *y, size_t ny) try {
+    return firhilb_block(q, FIRHILB_INTERP, x, nx, y, ny);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_r2c_execute_block_dev(yagi_hip_firhilb q, const float *x_dev, size_t n, yagi_cf32 *y_dev) try {
+    return firhilb_block_dev(q, FIRHILB_R2C, x_dev, n, y_dev);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_c2r_execute_block_dev(yagi_hip_firhilb q, const yagi_cf32 *x_dev, size_t n, float *y_dev) try {
+    return firhilb_block_dev(q, FIRHILB_C2R, x_dev, n, y_dev);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_decim_execute_block_dev(yagi_hip_firhilb q, const float *x_dev, size_t n, yagi_cf32 *y_dev) try {
+    return firhilb_block_dev(q, FIRHILB_DECIM, x_dev, n, y_dev);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firhilb_interp_execute_block_dev(yagi_hip_firhilb q, const yagi_cf32 *x_dev, size_t n, float *y_dev) try {
+    return firhilb_block_dev(q, FIRHILB_INTERP, x_dev, n, y_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"

@@ -566,6 +566,30 @@ cf32 osc_mix(int vco, uint32_t theta, bool down, cf32 x) {
     const float rr = x.re * c, ii = x.im * s, ri = x.re * s, ir = x.im * c;
     return cf32{rr - ii, ri + ir};
 }
+
+// ---- FirHilbertFilter (src/filter/fir/firhilb.rs) -------------------------------------------------------------------
+// new() :38-64: the Kaiser half-band filter of 4m + 1 taps times Complex32::from_polar(1, pi/2 t).im (libm sinf, f32),
+// then every other tap, reversed: hq[j] = h[h_len - i - 1], i = 1, 3, ..
+int firhilb_design(size_t m, float as_, std::vector<float> &hq) {
+    if (m < 2) return fail(YAGI_ERR_CONFIG, "filter semi-length (m) must be at least 2");
+    const size_t h_len = 4 * m + 1;
+    std::vector<float> h;
+    YG_TRY(design_kaiser(h_len, 0.25f, std::fabs(as_), 0.0f, h));
+    for (size_t i = 0; i < h_len; ++i) {
+        const float t = (float)i - (float)(h_len - 1) / 2.0f;
+        const float im = 1.0f * sinf(0.5f * kOscPi * t);
+        h[i] = h[i] * im;
+    }
+    hq.clear();
+    for (size_t i = 1; i < h_len; i += 2) hq.push_back(h[h_len - i - 1]);
+    return YAGI_OK;
+}
+// hq.dotprod(window.read()): products and adds unfused, left to right from the oldest sample, from +0.0
+float firhilb_dot(const float *hq, const float *w, size_t L) {
+    float s = 0.0f;
+    for (size_t k = 0; k < L; ++k) s = s + hq[k] * w[k];
+    return s;
+}
 }  // namespace yagi
 
 extern "C" {
@@ -580,4 +604,13 @@ int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h
     std::memcpy(h, v.data(), n * sizeof(float));
     return YAGI_OK;
 }
+
+// extension: the 2m taps of FirHilbertFilter::new (firhilb.rs:43-64); no device needed
+int yagi_hip_firhilb_design(size_t m, float as_, float *hq) try {
+    std::vector<float> v;
+    YG_TRY(yagi::firhilb_design(m, as_, v));
+    if (!hq) return yagi::fail(YAGI_ERR_CONFIG, "null output pointer");
+    std::memcpy(hq, v.data(), v.size() * sizeof(float));
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
 }

@@ -265,4 +265,17 @@ constexpr int kOscWgPerCu = 2;     // persistent grid: 2 workgroups per CU
 int launch_osc_mix(int vco, bool down, const void *tab, uint32_t theta0, uint32_t dtheta, const cf32 *x, cf32 *y,
                    size_t n, hipStream_t st);
 
+// ---- firhilb_kernels.hip -------------------------------------------------------------------
+// FirHilbertFilter (src/filter/fir/firhilb.rs) block calls on device buffers, n units (r2c: n real -> n complex; c2r:
+// n complex -> 2n real; decim: 2n real -> n complex; interp: n complex -> 2n real).  win: the four windows w0..w3 of
+// 2m floats, oldest first; win_next receives the windows the call leaves; toggle is the toggle at the call.  x and y
+// must not overlap and be 4-byte aligned.  m <= kFirhilbFastM takes the LDS-staged sliding form.
+enum { FIRHILB_R2C = 0, FIRHILB_C2R = 1, FIRHILB_DECIM = 2, FIRHILB_INTERP = 3 };
+constexpr int kFirhilbWg = 256;                        // threads per workgroup
+constexpr int kFirhilbR = 8;                           // consecutive pairs per lane
+constexpr int kFirhilbTile = kFirhilbWg * kFirhilbR;   // pairs per workgroup
+constexpr int kFirhilbFastM = 512;
+int launch_firhilb(int mode, int m, const float *hq, const float *win, float *win_next, int toggle, const float *x,
+                   size_t n, float *y, hipStream_t st);
+
 }  // namespace yagi
