@@ -299,6 +299,27 @@ def test_bitwise_sos(ya, kind, nsos):
     assert np.array_equal(y, r.execute_block(xs))
 
 
+@pytest.mark.parametrize("form", ["tf", "sos"])
+def test_reset_then_device_block_then_per_sample(ya, form):
+    """reset() after a device block zeroes the host mirror and leaves the device copy stale: the next device block
+    must upload the zeros and the per-sample calls after it must fetch the state it left.  The whole sequence equals
+    a fresh filter's, bit for bit (integer data: the transfer-function deque's kept head moves no bit)."""
+    rng = np.random.default_rng(300)
+    kind = "crcf"
+    if form == "tf":
+        b, a = TF_INT[3]
+        q, r = ya.IirFilter(kind, np.array(b, CDT[kind]), np.array(a, CDT[kind])), Seq32(kind, b, a)
+    else:
+        b, a = sos_int(4)
+        q, r = ya.IirFilter.new_sos(kind, b.astype(CDT[kind]), a.astype(CDT[kind]), 4), Seq32(kind, b, a, nsos=4)
+    x = int_signal(rng, kind, 2000)
+    run_dev(ya, q, x[:700])                             # the device copy is current and not zero
+    q.reset()
+    y = np.concatenate([run_dev(ya, q, x[700:1500]), np.array([q.execute(v) for v in x[1500:1540]], DT[kind]),
+                        run_dev(ya, q, x[1540:])])
+    assert np.array_equal(y, r.execute_block(x[700:]))
+
+
 # ---- accuracy on float data --------------------------------------------------------------------------------------
 def stable_sos(rng, kind, nsos, rmax=0.995):
     b, a = [], []

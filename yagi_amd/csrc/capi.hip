@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "objstate.hpp"
 
 namespace yagi {
 
@@ -41,19 +42,6 @@ template <> float one_of<float>() { return 1.0f; }
 template <> cf32 one_of<cf32>() { return cf32{1.0f, 0.0f}; }
 static cf32 to_c(float v, cf32 *) { return cf32{v, 0.0f}; }
 static float to_c(float v, float *) { return v; }
-
-static int upload(void *dst, const void *src, size_t bytes, hipStream_t st) {
-    if (bytes == 0) return YAGI_OK;
-    YG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
-    YG_HIP(hipStreamSynchronize(st));
-    return YAGI_OK;
-}
-static int download(void *dst, const void *src, size_t bytes, hipStream_t st) {
-    if (bytes == 0) return YAGI_OK;
-    YG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
-    YG_HIP(hipStreamSynchronize(st));
-    return YAGI_OK;
-}
 
 // Pipelined block calls (yagi_hip_firfft_crcf_set_pipeline, yagi_hip_firfilt_*_set_pipeline).  Consecutive blocks of the stream depend on each other
 // only through the L-sample filter window, and that window is INPUT data (the previous block's last L samples), which
@@ -96,8 +84,7 @@ template <class T>
 struct DevWindow {
     int len = 0;
     static constexpr int kBufs = 3;   // a ring of three: kernels write window b+1 into next() while block b reads dev()
-    DevBuf buf[kBufs];
-    int cur = 0;
+    PingPong<kBufs> ring;
     // Host mirror for the per-sample calls (push / execute / execute_one: firfilt.rs:220-261, firpfb.rs:255-286,
     // firdecim.rs:179-191).  hbuf[hend - len, hend) = the last len samples, oldest first -- Window<T>::read()'s layout
     // (window.rs:77-85): a push appends, and when the slack behind the window is used up the window moves back to the
@@ -107,7 +94,7 @@ struct DevWindow {
     static constexpr size_t kSlack = 4096;
     std::vector<T> hbuf;
     size_t hend = 0;
-    bool host_valid = true, dev_valid = true;
+    Mirror mirror;
     uint64_t npush = 0;               // samples pushed since the window was made: the ring position of FirFilter's VecDeque
     StreamPipe pipe;                  // pipelined block calls (objects that offer set_pipeline)
 
@@ -141,30 +128,30 @@ struct DevWindow {
         pipe.busy[i] = true;
         ++pipe.calls;
         pipe.prev_tail = x + (n - (size_t)len);
-        host_valid = false;
+        mirror.dev_written();
         return YAGI_OK;
     }
-    bool can_pipe(size_t n) const { return pipe.on && dev_valid && n >= (size_t)len; }
+    bool can_pipe(size_t n) const { return pipe.on && mirror.dev_current() && n >= (size_t)len; }
 
     int init(int n, hipStream_t st) {
         len = n;
-        for (auto &b : buf) YG_TRY(b.alloc((size_t)n * sizeof(T)));
+        YG_TRY(ring.alloc((size_t)n * sizeof(T)));
         hbuf.assign((size_t)n + kSlack, T{});
         npush = 0;
         return reset(st);
     }
     int reset(hipStream_t st) {       // zeroes the samples in place; the ring position is kept (firfilt.rs:209-213)
         YG_TRY(join(st));
-        YG_HIP(hipMemsetAsync(buf[cur].p, 0, (size_t)len * sizeof(T), st));
+        YG_HIP(hipMemsetAsync(ring.cur(), 0, (size_t)len * sizeof(T), st));
         std::fill(hbuf.begin(), hbuf.begin() + len, T{});
         hend = (size_t)len;
-        host_valid = dev_valid = true;
+        mirror.in_sync();
         return YAGI_OK;
     }
-    const T *dev() const { return buf[cur].template as<T>(); }
+    const T *dev() const { return ring.template cur<T>(); }
     // for kernels that write the next window themselves: the other buffer, then flip()
-    T *next() { return buf[(cur + 1) % kBufs].template as<T>(); }
-    void flip() { cur = (cur + 1) % kBufs; host_valid = false; }
+    T *next() { return ring.template next<T>(); }
+    void flip() { ring.flip(); mirror.dev_written(); }
     // window <- last len of (window ++ x_dev[0..n))
     int advance(const T *x_dev, size_t n, hipStream_t st) {
         if (n == 0) return YAGI_OK;
@@ -180,33 +167,27 @@ struct DevWindow {
         }
         hbuf[hend++] = v;
         ++npush;
-        dev_valid = false;
+        mirror.host_written();
     }
     // the device window is what the block kernels read: bring it up to date with the host mirror
     int ensure_dev(hipStream_t st) {
         YG_TRY(join(st));
-        if (dev_valid) return YAGI_OK;
-        YG_HIP(hipMemcpyAsync(buf[cur].p, host(), (size_t)len * sizeof(T), hipMemcpyHostToDevice, st));
-        YG_HIP(hipStreamSynchronize(st));
-        dev_valid = true;
-        return YAGI_OK;
+        return mirror.need_dev([&] { return upload(ring.cur(), host(), (size_t)len * sizeof(T), st); });
     }
     // the host mirror is what the per-sample calls read: fetch the window a block kernel left on the device
     int ensure_host(hipStream_t st) {
         YG_TRY(join(st));
-        if (host_valid) return YAGI_OK;
-        YG_HIP(hipMemcpyAsync(hbuf.data(), buf[cur].p, (size_t)len * sizeof(T), hipMemcpyDeviceToHost, st));
-        YG_HIP(hipStreamSynchronize(st));
-        hend = (size_t)len;
-        host_valid = true;
-        return YAGI_OK;
+        return mirror.need_host([&] {
+            hend = (size_t)len;                       // read only once the copy has arrived
+            return download(hbuf.data(), ring.cur(), (size_t)len * sizeof(T), st);
+        });
     }
     int clone_from(const DevWindow &o, hipStream_t st) {       // o.ensure_dev() has run
         YG_TRY(init(o.len, st));
-        YG_HIP(hipMemcpyAsync(buf[cur].p, o.buf[o.cur].p, (size_t)len * sizeof(T), hipMemcpyDeviceToDevice, st));
+        YG_HIP(hipMemcpyAsync(ring.cur(), o.ring.cur(), (size_t)len * sizeof(T), hipMemcpyDeviceToDevice, st));
         YG_HIP(hipStreamSynchronize(st));
         npush = o.npush;
-        host_valid = false;
+        mirror.dev_written();
         return YAGI_OK;
     }
 };
@@ -214,11 +195,6 @@ struct DevWindow {
 // the per-sample arithmetic (host.cpp): the reference's own sequential sums, products unfused
 template <class T, class C> T host_fir_ring_dot(const T *w, size_t L, size_t head, const C *h, C scale);
 template <class T, class C> T host_fir_window_dot(const T *w, size_t L, const C *h, C scale);
-
-// workspaces shared by the host-pointer entry points of one object
-struct Workspace {
-    DevBuf x, y, scratch;
-};
 
 // ---------------------------------------------------------------------------------------------
 // FirFilter<T,C>
@@ -242,7 +218,7 @@ struct FirFilt {
     float hfreq_s_scale = 0.f;
     bool conv_ready = false;
     DevWindow<T> w;
-    Workspace ws;
+    Staging ws;
     int kernel_choice = 0;     // 0 auto, 1 general, 2 sliding (crcf), 3 MFMA Toeplitz (crcf, L <= 256), 4 fast convolution
     int prepare_conv();
 
@@ -251,22 +227,19 @@ struct FirFilt {
         if (n > (size_t)1 << 24) return fail(YAGI_ERR_CONFIG, "filter too long");
         h.assign(hh, hh + n);
         L = (int)n;
-        YG_TRY(taps.alloc(n * sizeof(C)));
-        YG_TRY(upload(taps.p, h.data(), n * sizeof(C), st));
+        YG_TRY(fill(taps, h.data(), n * sizeof(C), st));
         conv_ready = false;
         hfreq_s_valid = false;
         if (K::id == 1) {
             Lp = (L + 31) / 32 * 32;
             std::vector<float> hp((size_t)Lp, 0.0f);
             std::memcpy(hp.data(), h.data(), n * sizeof(float));
-            YG_TRY(taps_pad.alloc((size_t)Lp * sizeof(float)));
-            YG_TRY(upload(taps_pad.p, hp.data(), (size_t)Lp * sizeof(float), st));
+            YG_TRY(fill(taps_pad, hp.data(), (size_t)Lp * sizeof(float), st));
             Lm = mfma_lp_for(L);
             if (Lm) {
                 std::vector<float> ap(toeplitz_pack_floats(Lm));
                 pack_toeplitz_taps(reinterpret_cast<const float *>(h.data()), L, Lm, ap.data());
-                YG_TRY(apack.alloc(ap.size() * sizeof(float)));
-                YG_TRY(upload(apack.p, ap.data(), ap.size() * sizeof(float), st));
+                YG_TRY(fill(apack, ap.data(), ap.size() * sizeof(float), st));
             }
         }
         return YAGI_OK;
@@ -359,7 +332,7 @@ struct FirDecim {
     C scale = one_of<C>();
     DevBuf taps;
     DevWindow<T> w;
-    Workspace ws;
+    Staging ws;
 
     int init(size_t m, const C *hh, size_t n) {
         if (n == 0) return fail(YAGI_ERR_CONFIG, "filter length must be greater than zero");
@@ -369,8 +342,7 @@ struct FirDecim {
         h.assign(hh, hh + n);
         L = (int)n;
         M = (int)m;
-        YG_TRY(taps.alloc(n * sizeof(C)));
-        YG_TRY(upload(taps.p, h.data(), n * sizeof(C), st));
+        YG_TRY(fill(taps, h.data(), n * sizeof(C), st));
         return w.init(L, st);
     }
     // n outputs from n*M device samples
@@ -396,7 +368,7 @@ struct FirPfb {
     C scale = one_of<C>();
     DevBuf taps;
     DevWindow<T> w;
-    Workspace ws;
+    Staging ws;
 
     int init(size_t num_filters, const C *hh, size_t h_len) {
         if (num_filters == 0) return fail(YAGI_ERR_CONFIG, "number of filters must be greater than zero");
@@ -410,8 +382,7 @@ struct FirPfb {
         hb.resize((size_t)nf * Ls);
         for (int i = 0; i < nf; ++i)
             for (int k = 0; k < Ls; ++k) hb[(size_t)i * Ls + k] = hh[i + (size_t)k * nf];
-        YG_TRY(taps.alloc(hb.size() * sizeof(C)));
-        YG_TRY(upload(taps.p, hb.data(), hb.size() * sizeof(C), st));
+        YG_TRY(fill(taps, hb.data(), hb.size() * sizeof(C), st));
         return w.init(Ls, st);
     }
     int check_branch(size_t i) const {
@@ -432,7 +403,7 @@ struct FirPfb {
 struct FftPlan {
     FftPlanDev d;
     DevBuf tw;
-    Workspace ws;
+    Staging ws;
     DevBuf bs_w, bs_bf, bs_twf, bs_twb, bs_scratch;      // Bluestein resources (sizes with a large prime factor)
     std::unique_ptr<FftPlan> bs_fwd, bs_bwd;             // Bluestein over m > 8192: the m-point plans
     std::unique_ptr<FftPlan> fs_p1, fs_p2;               // four-step: the n1- and n2-point plans
@@ -468,8 +439,7 @@ static int make_twiddles(int n, int dir, DevBuf &buf, bool half_too = false) {
             const double a = s * 2.0 * M_PI * (double)m / (double)(n / 2);
             t[(size_t)n + m] = cf32{(float)std::cos(a), (float)std::sin(a)};
         }
-    YG_TRY(buf.alloc(t.size() * sizeof(cf32)));
-    return upload(buf.p, t.data(), t.size() * sizeof(cf32), nullptr);
+    return fill(buf, t.data(), t.size() * sizeof(cf32), nullptr);
 }
 
 // twiddle table of the 4096-point stream kernels: W_4096^m (m < 4096, forward) followed by six 256-entry rows the
@@ -487,8 +457,7 @@ static int make_stream_twiddles(DevBuf &buf) {
         tab[4096 + 1024 + t] = W((t & 15u) * (t >> 4));
         tab[4096 + 1280 + t] = W(16u * (((t & 15u) * (t >> 4)) & 255u));
     }
-    YG_TRY(buf.alloc(tab.size() * sizeof(cf32)));
-    return upload(buf.p, tab.data(), tab.size() * sizeof(cf32), nullptr);
+    return fill(buf, tab.data(), tab.size() * sizeof(cf32), nullptr);
 }
 
 // W_n^m for any m < n as a product of two exact entries: tab[m & 4095] = W_n^{m & 4095}, tab[4096 + (m >> 12)] = W_n^{4096 (m >> 12)}
@@ -504,8 +473,7 @@ static int make_split_twiddles(size_t n, int dir, DevBuf &buf) {
         const double a = s * 2.0 * M_PI * (double)(4096 * j) / (double)n;
         tab[4096 + j] = cf32{(float)std::cos(a), (float)std::sin(a)};
     }
-    YG_TRY(buf.alloc(tab.size() * sizeof(cf32)));
-    return upload(buf.p, tab.data(), tab.size() * sizeof(cf32), nullptr);
+    return fill(buf, tab.data(), tab.size() * sizeof(cf32), nullptr);
 }
 
 static int fft_plan_init(FftPlan &p, size_t n, int dir) {
@@ -601,8 +569,7 @@ static int fft_plan_init(FftPlan &p, size_t n, int dir) {
             b[k] = cw;
             if (k) b[m - k] = cw;
         }
-        YG_TRY(p.bs_w.alloc(n * sizeof(cf32)));
-        YG_TRY(upload(p.bs_w.p, w.data(), n * sizeof(cf32), nullptr));
+        YG_TRY(fill(p.bs_w, w.data(), n * sizeof(cf32), nullptr));
         // 2 x 64 MiB of scratch (more for one big transform).  With 2 x 16 MiB the five-stage form was launch-bound on long
         // batches (n = 12 289: 2400 launches of ~9 us for 2^28 points): 0.20 -> 0.30 TB/s, n = 509: 0.42 -> 0.59; 2 x 128 MiB the same
         static const int bs_lg = getenv("YAGI_HIP_BS_CHUNK_LOG2") ? atoi(getenv("YAGI_HIP_BS_CHUNK_LOG2")) : 23;
@@ -669,8 +636,7 @@ int FirFilt<K>::prepare_conv() {
             }
             hp[k] = cf32{(float)re, (float)im};
         }
-        YG_TRY(hfreq.alloc(4096 * sizeof(cf32)));
-        YG_TRY(upload(hfreq.p, hp.data(), 4096 * sizeof(cf32), st));
+        YG_TRY(fill(hfreq, hp.data(), 4096 * sizeof(cf32), st));
         // reversed taps g[j] = h[L-1-j] of the frame-boundary correction (freq_kernels.hip)
         if (K::id == 1 && L <= 257) {
             std::vector<float> g(256, 0.0f);
@@ -686,8 +652,7 @@ int FirFilt<K>::prepare_conv() {
                 }
                 gf[k] = cf32{(float)(re / 512.0), (float)(-im / 512.0)};
             }
-            YG_TRY(gfft.alloc(512 * sizeof(cf32)));
-            YG_TRY(upload(gfft.p, gf.data(), 512 * sizeof(cf32), st));
+            YG_TRY(fill(gfft, gf.data(), 512 * sizeof(cf32), st));
         }
         YG_HIP(hipStreamSynchronize(st));      // the host vectors go out of scope
     }
@@ -704,7 +669,7 @@ struct FirFft {
     DevBuf tw;
     FftPlan plan;              // nfft != 4096: overlap-save FIR, then this plan over the frames
     int variant = 0;
-    DevBuf xin, yout;
+    Staging ws;
     DevBuf scratch;            // variant 3: the FIR output stream between the two kernels
     int join() { return fir.w.join(fir.st); }
 };
@@ -718,7 +683,7 @@ struct PfbCh {
     DevBuf h, tw;
     DevWindow<cf32> hist;      // (p-1)*M samples (at least 1 kept so the buffers exist)
     DevWindow<cf32> syn_hist;  // synthesizer: the last (p-1)*M channel samples (its own state, like liquid's separate objects)
-    Workspace ws;
+    Staging ws;
 };
 struct PfbCh2 {
     hipStream_t st = nullptr;
@@ -728,7 +693,7 @@ struct PfbCh2 {
     uint64_t step = 0;
     DevWindow<cf32> syn_hist;  // synthesizer: the last (4m-1)*M channel samples; its own step parity
     uint64_t syn_step = 0;
-    Workspace ws;
+    Staging ws;
     DevBuf shard, gathered;    // sharded analyzer: this rank's sub-bands, and every rank's ([rank][step][M/R] per chunk)
 };
 
@@ -872,16 +837,14 @@ static int firfilt_block_host(FirFilt<K> *q, const typename K::T *x, size_t nx, 
     if (nx == 0) return YAGI_OK;
     CHECK_PTR(x);
     CHECK_PTR(y);
-    YG_TRY(q->ws.x.ensure(nx * sizeof(T)));
-    YG_TRY(q->ws.y.ensure(nx * sizeof(T)));
-    YG_TRY(q->w.join(q->st));                            // the workspace is reused: host-pointer calls never pipeline
-    YG_TRY(upload(q->ws.x.p, x, nx * sizeof(T), q->st));
-    const bool was = q->w.pipe.on;
-    q->w.pipe.on = false;
-    const int rc = q->block_dev(q->ws.x.template as<T>(), nx, q->ws.y.template as<T>());
-    q->w.pipe.on = was;
-    YG_TRY(rc);
-    return download(y, q->ws.y.p, nx * sizeof(T), q->st);
+    YG_TRY(q->w.join(q->st));                            // the staging buffers are reused: host-pointer calls never pipeline
+    return q->ws.run(q->st, x, nx, y, nx, [&](const T *xd, T *yd) {
+        const bool was = q->w.pipe.on;
+        q->w.pipe.on = false;
+        const int rc = q->block_dev(xd, nx, yd);
+        q->w.pipe.on = was;
+        return rc;
+    });
 }
 
 template <class K>
@@ -892,11 +855,7 @@ static int firdecim_block_host(FirDecim<K> *q, const typename K::T *x, size_t nx
     CHECK_PTR(x);
     CHECK_PTR(y);
     const size_t nin = n * (size_t)q->M;
-    YG_TRY(q->ws.x.ensure(nin * sizeof(T)));
-    YG_TRY(q->ws.y.ensure(n * sizeof(T)));
-    YG_TRY(upload(q->ws.x.p, x, nin * sizeof(T), q->st));
-    YG_TRY(q->block_dev(q->ws.x.template as<T>(), n, q->ws.y.template as<T>()));
-    return download(y, q->ws.y.p, n * sizeof(T), q->st);
+    return q->ws.run(q->st, x, nin, y, n, [&](const T *xd, T *yd) { return q->block_dev(xd, n, yd); });
 }
 
 template <class K>
@@ -907,11 +866,7 @@ static int firpfb_block_host(FirPfb<K> *q, size_t i, const typename K::T *x, siz
     if (n == 0) return YAGI_OK;
     CHECK_PTR(x);
     CHECK_PTR(y);
-    YG_TRY(q->ws.x.ensure(n * sizeof(T)));
-    YG_TRY(q->ws.y.ensure(n * sizeof(T)));
-    YG_TRY(upload(q->ws.x.p, x, n * sizeof(T), q->st));
-    YG_TRY(q->block_dev(i, q->ws.x.template as<T>(), n, q->ws.y.template as<T>()));
-    return download(y, q->ws.y.p, n * sizeof(T), q->st);
+    return q->ws.run(q->st, x, n, y, n, [&](const T *xd, T *yd) { return q->block_dev(i, xd, n, yd); });
 }
 
 }  // namespace yagi
@@ -1282,8 +1237,7 @@ static int taps_groupdelay(const std::vector<C> &h, float fc, float *out) {
         o->Ls = q->Ls;                                                                              \
         o->hb = q->hb;                                                                              \
         o->scale = q->scale;                                                                        \
-        YG_TRY(o->taps.alloc(o->hb.size() * sizeof(C)));                                            \
-        YG_TRY(upload(o->taps.p, o->hb.data(), o->hb.size() * sizeof(C), o->st));                   \
+        YG_TRY(fill(o->taps, o->hb.data(), o->hb.size() * sizeof(C), o->st));                       \
         YG_TRY(o->w.clone_from(q->w, q->st));                                                       \
         *out = o.release();                                                                         \
         return YAGI_OK;                                                                             \
@@ -1429,11 +1383,8 @@ int yagi_hip_fft_run(yagi_hip_fft plan, const yagi_cf32 *input, size_t n_in, yag
     if (n_in != n || n_out != n) return fail(YAGI_ERR_CONFIG, "fft buffers must hold exactly %zu samples", n);
     CHECK_PTR(input);
     CHECK_PTR(output);
-    YG_TRY(plan->ws.x.ensure(n * sizeof(cf32)));
-    YG_TRY(plan->ws.y.ensure(n * sizeof(cf32)));
-    YG_TRY(upload(plan->ws.x.p, input, n * sizeof(cf32), nullptr));
-    YG_TRY(launch_fft_batch(plan->d, plan->ws.x.as<cf32>(), plan->ws.y.as<cf32>(), 1, nullptr));
-    return download(output, plan->ws.y.p, n * sizeof(cf32), nullptr);
+    return plan->ws.run(nullptr, input, n, output, n,
+                        [&](const cf32 *xd, cf32 *yd) { return launch_fft_batch(plan->d, xd, yd, 1, nullptr); });
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_fft_shift_dev(yagi_cf32 *buf, size_t n, size_t batch, yagi_stream_t s) try {
     if (n == 0 || batch == 0) return YAGI_OK;
@@ -1446,8 +1397,7 @@ int yagi_hip_fft_shift(yagi_cf32 *buf, size_t n) try {
     CHECK_PTR(buf);
     YG_TRY(require_device());
     DevBuf d;
-    YG_TRY(d.alloc(n * sizeof(cf32)));
-    YG_TRY(upload(d.p, buf, n * sizeof(cf32), nullptr));
+    YG_TRY(fill(d, buf, n * sizeof(cf32), nullptr));
     YG_TRY(launch_fft_shift(d.as<cf32>(), n, 1, nullptr));
     return download(buf, d.p, n * sizeof(cf32), nullptr);
 } catch (...) { return ::yagi::api_exception(); }
@@ -1494,11 +1444,7 @@ struct FirInterp {
     }
     int block_host(const T *x, size_t n, T *y) {
         if (n == 0) return YAGI_OK;
-        YG_TRY(bank.ws.x.ensure(n * sizeof(T)));
-        YG_TRY(bank.ws.y.ensure(n * (size_t)interp * sizeof(T)));
-        YG_TRY(upload(bank.ws.x.p, x, n * sizeof(T), bank.st));
-        YG_TRY(block_dev(bank.ws.x.template as<T>(), n, bank.ws.y.template as<T>()));
-        return download(y, bank.ws.y.p, n * (size_t)interp * sizeof(T), bank.st);
+        return bank.ws.run(bank.st, x, n, y, n * (size_t)interp, [&](const T *xd, T *yd) { return block_dev(xd, n, yd); });
     }
 };
 
@@ -1571,8 +1517,7 @@ struct FirInterp {
         o->bank.Ls = q->bank.Ls;                                                                    \
         o->bank.hb = q->bank.hb;                                                                    \
         o->bank.scale = q->bank.scale;                                                              \
-        YG_TRY(o->bank.taps.alloc(o->bank.hb.size() * sizeof(C)));                                  \
-        YG_TRY(upload(o->bank.taps.p, o->bank.hb.data(), o->bank.hb.size() * sizeof(C), o->bank.st)); \
+        YG_TRY(fill(o->bank.taps, o->bank.hb.data(), o->bank.hb.size() * sizeof(C), o->bank.st));   \
         YG_TRY(o->bank.w.clone_from(q->bank.w, q->bank.st));                                        \
         *out = o.release();                                                                         \
         return YAGI_OK;                                                                             \
@@ -1684,11 +1629,8 @@ struct RresampObj {
     }
     int blocks_host(const T *x, size_t nblocks, T *y) {
         if (nblocks == 0) return YAGI_OK;
-        YG_TRY(bank.ws.x.ensure(nblocks * (size_t)Q * sizeof(T)));
-        YG_TRY(bank.ws.y.ensure(nblocks * (size_t)P * sizeof(T)));
-        YG_TRY(upload(bank.ws.x.p, x, nblocks * (size_t)Q * sizeof(T), bank.st));
-        YG_TRY(blocks_dev(bank.ws.x.template as<T>(), nblocks, bank.ws.y.template as<T>()));
-        return download(y, bank.ws.y.p, nblocks * (size_t)P * sizeof(T), bank.st);
+        return bank.ws.run(bank.st, x, nblocks * (size_t)Q, y, nblocks * (size_t)P,
+                           [&](const T *xd, T *yd) { return blocks_dev(xd, nblocks, yd); });
     }
 };
 
@@ -1745,8 +1687,7 @@ struct RresampObj {
         o->bank.Ls = q->bank.Ls;                                                                    \
         o->bank.hb = q->bank.hb;                                                                    \
         o->bank.scale = q->bank.scale;                                                              \
-        YG_TRY(o->bank.taps.alloc(o->bank.hb.size() * sizeof(C)));                                  \
-        YG_TRY(upload(o->bank.taps.p, o->bank.hb.data(), o->bank.hb.size() * sizeof(C), o->bank.st)); \
+        YG_TRY(fill(o->bank.taps, o->bank.hb.data(), o->bank.hb.size() * sizeof(C), o->bank.st));   \
         YG_TRY(o->bank.w.clone_from(q->bank.w, q->bank.st));                                        \
         o->P = q->P; o->Q = q->Q; o->m = q->m; o->block_len = q->block_len;                         \
         *out = o.release();                                                                         \
@@ -1839,7 +1780,7 @@ struct SpgramObj {
     DevWindow<T> buf;
     DevBuf w, psd, out, tbuf, fbuf, part;
     FftPlan plan;
-    Workspace ws;
+    Staging ws;
     std::vector<T> queue;                // samples push()ed since the last flush
     size_t sample_timer = 0;
     uint64_t num_samples = 0, num_samples_total = 0, num_transforms = 0, num_transforms_total = 0;
@@ -1873,8 +1814,7 @@ struct SpgramObj {
         }
         g = 1.0f / std::sqrt(g);
         for (auto &v : wv) v = g * v;
-        YG_TRY(w.alloc(wlen_ * sizeof(float)));
-        YG_TRY(upload(w.p, wv.data(), wlen_ * sizeof(float), st));
+        YG_TRY(fill(w, wv.data(), wlen_ * sizeof(float), st));
         YG_TRY(psd.alloc(nfft_ * sizeof(float)));
         YG_TRY(out.alloc(nfft_ * sizeof(float)));
         YG_TRY(fft_plan_init(plan, nfft_, YAGI_FFT_FORWARD));
@@ -1947,8 +1887,7 @@ struct SpgramObj {
     }
     int write_host(const T *x, size_t n) {
         if (n == 0) return YAGI_OK;
-        YG_TRY(ws.x.ensure(n * sizeof(T)));
-        YG_TRY(upload(ws.x.p, x, n * sizeof(T), st));
+        YG_TRY(ws.put(st, x, n));
         return write_dev(ws.x.as<T>(), n);
     }
     int flush() {
@@ -2116,10 +2055,9 @@ struct FftFiltObj {
     C scale = one_of<C>();          // stored divided by 2n like the reference (fftfilt.rs:95-97)
     FftPlan fwd, bwd;
     DevBuf hfreq;                   // FFT{[h;0]}, 2n points
-    DevBuf w[2];                    // overlap tail, n points, ping-pong
-    int cur = 0;
+    PingPong<> w;                   // overlap tail, n points
     DevBuf tbuf, fbuf;              // [nblocks][2n] time / frequency buffers
-    Workspace ws;
+    Staging ws;
     // h_len <= 2049: the blocks of one call are contiguous in the stream and what FftFilt computes is the
     // stream's linear convolution with h, whatever the block length -- so the call goes to the one-launch
     // overlap-save kernel (4096-point transforms chained in registers) and the carried state is the last h_len
@@ -2151,14 +2089,13 @@ struct FftFiltObj {
         YG_TRY(hfreq.alloc(2 * nn * sizeof(cf32)));
         YG_TRY(upload(tbuf.p, tb.data(), 2 * nn * sizeof(cf32), st));
         YG_TRY(launch_fft_batch(fwd.d, tbuf.as<cf32>(), hfreq.as<cf32>(), 1, st));
-        YG_TRY(w[0].alloc(nn * sizeof(cf32)));
-        YG_TRY(w[1].alloc(nn * sizeof(cf32)));
+        YG_TRY(w.alloc(nn * sizeof(cf32)));
         scale = div_scalar(one_of<C>(), 2.0f * (float)n);
         return reset();
     }
     int reset() {
         if (use_conv) return fir.w.reset(st);
-        YG_HIP(hipMemsetAsync(w[cur].p, 0, (size_t)n * sizeof(cf32), st));
+        YG_HIP(hipMemsetAsync(w.cur(), 0, (size_t)n * sizeof(cf32), st));
         return YAGI_OK;
     }
     int blocks_dev(const T *x, size_t nblocks, T *y) {
@@ -2175,19 +2112,15 @@ struct FftFiltObj {
         YG_TRY(launch_fft_batch(fwd.d, tbuf.as<cf32>(), fbuf.as<cf32>(), nblocks, st));
         YG_TRY(launch_fftfilt_mul(fbuf.as<cf32>(), hfreq.as<cf32>(), (int)n2, nblocks, st));
         YG_TRY(launch_fft_batch(bwd.d, fbuf.as<cf32>(), tbuf.as<cf32>(), nblocks, st));
-        YG_TRY((launch_fftfilt_ola<T, C>(tbuf.as<cf32>(), w[cur].as<cf32>(), n, nblocks, scale, y,
-                                         w[1 - cur].as<cf32>(), st)));
-        cur = 1 - cur;
+        YG_TRY((launch_fftfilt_ola<T, C>(tbuf.as<cf32>(), w.cur<cf32>(), n, nblocks, scale, y,
+                                         w.next<cf32>(), st)));
+        w.flip();
         return YAGI_OK;
     }
     int blocks_host(const T *x, size_t nblocks, T *y) {
         if (nblocks == 0) return YAGI_OK;
-        const size_t bytes = nblocks * (size_t)n * sizeof(T);
-        YG_TRY(ws.x.ensure(bytes));
-        YG_TRY(ws.y.ensure(bytes));
-        YG_TRY(upload(ws.x.p, x, bytes, st));
-        YG_TRY(blocks_dev(ws.x.as<T>(), nblocks, ws.y.as<T>()));
-        return download(y, ws.y.p, bytes, st);
+        const size_t len = nblocks * (size_t)n;
+        return ws.run(st, x, len, y, len, [&](const T *xd, T *yd) { return blocks_dev(xd, nblocks, yd); });
     }
 };
 
@@ -2221,7 +2154,7 @@ struct FftFiltObj {
             YG_TRY(q->fir.w.ensure_dev(q->st));                                                          \
             YG_TRY(o->fir.w.clone_from(q->fir.w, q->st));                                           \
         } else {                                                                                    \
-            YG_HIP(hipMemcpyAsync(o->w[o->cur].p, q->w[q->cur].p, (size_t)q->n * sizeof(cf32),      \
+            YG_HIP(hipMemcpyAsync(o->w.cur(), q->w.cur(), (size_t)q->n * sizeof(cf32),              \
                                   hipMemcpyDeviceToDevice, q->st));                                 \
         YG_HIP(hipStreamSynchronize(q->st));                                                    \
         }                                                                                           \
@@ -2422,14 +2355,12 @@ int yagi_hip_firfft_crcf_execute(yagi_hip_firfft_crcf q, const yagi_cf32 *x, siz
     if (nframes == 0) return YAGI_OK;
     CHECK_PTR(x);
     CHECK_PTR(spectra);
-    const size_t bytes = nframes * q->nfft * sizeof(cf32);
+    const size_t n = nframes * q->nfft;
     YG_TRY(q->join());
-    YG_TRY(q->xin.ensure(bytes));
-    YG_TRY(q->yout.ensure(bytes));
-    YG_TRY(upload(q->xin.p, x, bytes, q->fir.st));
-    YG_TRY(yagi_hip_firfft_crcf_execute_dev(q, q->xin.as<cf32>(), nframes, q->yout.as<cf32>()));
-    YG_TRY(q->join());
-    return download(spectra, q->yout.p, bytes, q->fir.st);
+    return q->ws.run(q->fir.st, x, n, spectra, n, [&](const cf32 *xd, cf32 *yd) {
+        YG_TRY(yagi_hip_firfft_crcf_execute_dev(q, xd, nframes, yd));
+        return q->join();
+    });
 } catch (...) { return ::yagi::api_exception(); }
 
 }  // extern "C"
@@ -2451,8 +2382,7 @@ int yagi_hip_firpfbch_crcf_create(size_t M, size_t p, const float *h, yagi_hip_f
     auto o = std::make_unique<yagi_hip_firpfbch_crcf_s>();
     o->M = (int)M;
     o->p = (int)p;
-    YG_TRY(o->h.alloc(M * p * sizeof(float)));
-    YG_TRY(upload(o->h.p, h, M * p * sizeof(float), nullptr));
+    YG_TRY(fill(o->h, h, M * p * sizeof(float), nullptr));
     YG_TRY(make_twiddles((int)M, YAGI_FFT_FORWARD, o->tw));
     const size_t hl = (p - 1) * M;
     YG_TRY(o->hist.init((int)(hl ? hl : 1), nullptr));
@@ -2501,12 +2431,9 @@ int yagi_hip_firpfbch_crcf_analyzer_execute(yagi_hip_firpfbch_crcf q, const yagi
     if (nframes == 0) return YAGI_OK;
     CHECK_PTR(x);
     CHECK_PTR(y);
-    const size_t bytes = nframes * (size_t)q->M * sizeof(cf32);
-    YG_TRY(q->ws.x.ensure(bytes));
-    YG_TRY(q->ws.y.ensure(bytes));
-    YG_TRY(upload(q->ws.x.p, x, bytes, q->st));
-    YG_TRY(yagi_hip_firpfbch_crcf_analyzer_execute_dev(q, q->ws.x.as<cf32>(), nframes, q->ws.y.as<cf32>()));
-    return download(y, q->ws.y.p, bytes, q->st);
+    const size_t n = nframes * (size_t)q->M;
+    return q->ws.run(q->st, x, n, y, n,
+                     [&](const cf32 *xd, cf32 *yd) { return yagi_hip_firpfbch_crcf_analyzer_execute_dev(q, xd, nframes, yd); });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_firpfbch_crcf_synthesizer_execute_dev(yagi_hip_firpfbch_crcf q, const yagi_cf32 *x, size_t nframes, yagi_cf32 *y) try {
@@ -2524,12 +2451,9 @@ int yagi_hip_firpfbch_crcf_synthesizer_execute(yagi_hip_firpfbch_crcf q, const y
     if (nframes == 0) return YAGI_OK;
     CHECK_PTR(x);
     CHECK_PTR(y);
-    const size_t bytes = nframes * (size_t)q->M * sizeof(cf32);
-    YG_TRY(q->ws.x.ensure(bytes));
-    YG_TRY(q->ws.y.ensure(bytes));
-    YG_TRY(upload(q->ws.x.p, x, bytes, q->st));
-    YG_TRY(yagi_hip_firpfbch_crcf_synthesizer_execute_dev(q, q->ws.x.as<cf32>(), nframes, q->ws.y.as<cf32>()));
-    return download(y, q->ws.y.p, bytes, q->st);
+    const size_t n = nframes * (size_t)q->M;
+    return q->ws.run(q->st, x, n, y, n,
+                     [&](const cf32 *xd, cf32 *yd) { return yagi_hip_firpfbch_crcf_synthesizer_execute_dev(q, xd, nframes, yd); });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_firpfbch2_crcf_create(size_t M, size_t m, const float *h, yagi_hip_firpfbch2_crcf *q) try {
@@ -2544,8 +2468,7 @@ int yagi_hip_firpfbch2_crcf_create(size_t M, size_t m, const float *h, yagi_hip_
     o->M = (int)M;
     o->m = (int)m;
     const size_t hl = 2 * M * m;
-    YG_TRY(o->h.alloc(hl * sizeof(float)));
-    YG_TRY(upload(o->h.p, h, hl * sizeof(float), nullptr));
+    YG_TRY(fill(o->h, h, hl * sizeof(float), nullptr));
     YG_TRY(make_twiddles((int)M, YAGI_FFT_FORWARD, o->tw));
     YG_TRY(o->hist.init((int)((2 * m - 1) * M + M / 2), nullptr));
     YG_TRY(o->syn_hist.init((int)((4 * m - 1) * M), nullptr));
@@ -2608,12 +2531,10 @@ int yagi_hip_firpfbch2_crcf_synthesizer_execute(yagi_hip_firpfbch2_crcf q, const
     if (nsteps == 0) return YAGI_OK;
     CHECK_PTR(x);
     CHECK_PTR(y);
-    const size_t in_bytes = nsteps * (size_t)q->M * sizeof(cf32), out_bytes = in_bytes / 2;
-    YG_TRY(q->ws.x.ensure(in_bytes));
-    YG_TRY(q->ws.y.ensure(out_bytes));
-    YG_TRY(upload(q->ws.x.p, x, in_bytes, q->st));
-    YG_TRY(yagi_hip_firpfbch2_crcf_synthesizer_execute_dev(q, q->ws.x.as<cf32>(), nsteps, q->ws.y.as<cf32>()));
-    return download(y, q->ws.y.p, out_bytes, q->st);
+    const size_t nin = nsteps * (size_t)q->M;
+    return q->ws.run(q->st, x, nin, y, nin / 2, [&](const cf32 *xd, cf32 *yd) {
+        return yagi_hip_firpfbch2_crcf_synthesizer_execute_dev(q, xd, nsteps, yd);
+    });
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_firpfbch2_crcf_analyzer_execute_shard_dev(yagi_hip_firpfbch2_crcf q, const yagi_cf32 *x, size_t nsteps,
                                                        int rank, int nranks, yagi_cf32 *y) try {
@@ -2637,12 +2558,9 @@ int yagi_hip_firpfbch2_crcf_analyzer_execute(yagi_hip_firpfbch2_crcf q, const ya
     if (nsteps == 0) return YAGI_OK;
     CHECK_PTR(x);
     CHECK_PTR(y);
-    const size_t bin = nsteps * (size_t)(q->M / 2) * sizeof(cf32), bout = nsteps * (size_t)q->M * sizeof(cf32);
-    YG_TRY(q->ws.x.ensure(bin));
-    YG_TRY(q->ws.y.ensure(bout));
-    YG_TRY(upload(q->ws.x.p, x, bin, q->st));
-    YG_TRY(yagi_hip_firpfbch2_crcf_analyzer_execute_dev(q, q->ws.x.as<cf32>(), nsteps, q->ws.y.as<cf32>()));
-    return download(y, q->ws.y.p, bout, q->st);
+    return q->ws.run(q->st, x, nsteps * (size_t)(q->M / 2), y, nsteps * (size_t)q->M, [&](const cf32 *xd, cf32 *yd) {
+        return yagi_hip_firpfbch2_crcf_analyzer_execute_dev(q, xd, nsteps, yd);
+    });
 } catch (...) { return ::yagi::api_exception(); }
 // sub-bands sharded over the ranks of `comm`: shard kernel (this stream) -> RCCL all-gather -> assemble (the
 // communicator's stream), chunk by chunk so chunk k's exchange runs beside chunk k+1's kernel
@@ -2729,11 +2647,10 @@ struct Resamp2Obj {
     int m = 0;
     std::vector<C> h1;             // h1[i] = h[h_len - 2i - 2] (resamp2.rs:66-70)
     DevBuf h1d;
-    DevBuf state[2];               // [w0 (2m, oldest first)][w1 (2m)], ping-pong
-    int cur = 0;
+    PingPong<> state;              // [w0 (2m, oldest first)][w1 (2m)]
     int toggle = 0;
     C scale;
-    Workspace ws;
+    Staging ws;
 
     // new() from the designed half-band prototype hf[4m+1] (:44-88)
     int init(const float *hf, size_t m_, float f0) {
@@ -2750,34 +2667,34 @@ struct Resamp2Obj {
         h1.resize(2 * m_);
         for (size_t i = 0; i < 2 * m_; ++i) h1[i] = h[h_len - 2 * i - 2];
         scale = to_c(1.0f, (C *)nullptr);
-        YG_TRY(h1d.alloc(h1.size() * sizeof(C)));
-        YG_TRY(upload(h1d.p, h1.data(), h1.size() * sizeof(C), st));
-        YG_TRY(state[0].alloc(4 * m_ * sizeof(T)));
-        YG_TRY(state[1].alloc(4 * m_ * sizeof(T)));
+        YG_TRY(fill(h1d, h1.data(), h1.size() * sizeof(C), st));
+        YG_TRY(state.alloc(4 * m_ * sizeof(T)));
         return reset();
     }
     int reset() {                                                   // :90-94
         toggle = 0;
-        YG_HIP(hipMemsetAsync(state[cur].p, 0, 4 * (size_t)m * sizeof(T), st));
+        YG_HIP(hipMemsetAsync(state.cur(), 0, 4 * (size_t)m * sizeof(T), st));
         return YAGI_OK;
     }
     static size_t out_count(int mode, size_t nx) {
         return mode == kR2Filter || mode == kR2Interp ? 2 * nx : mode == kR2Decim ? nx / 2 : nx;
     }
     // the reference's slices carry their lengths (copy_from_slice / indexing panics on a mismatch); the C ABI checks
-    static int check_lengths(int mode, size_t nx, size_t ny) {
+    static int check_form(int mode, size_t nx) {
         if (mode < kR2Filter || mode > kR2Interp) return fail(YAGI_ERR_CONFIG, "resamp2: unknown form %d", mode);
         if (mode != kR2Filter && mode != kR2Interp && (nx & 1))
             return fail(YAGI_ERR_CONFIG, "resamp2: this form consumes pairs of samples (got %zu)", nx);
+        return YAGI_OK;
+    }
+    static int check_lengths(int mode, size_t nx, size_t ny) {
+        YG_TRY(check_form(mode, nx));
         if (ny != out_count(mode, nx))
             return fail(YAGI_ERR_CONFIG, "resamp2: form %d turns %zu samples into %zu, the output holds %zu", mode, nx,
                         out_count(mode, nx), ny);
         return YAGI_OK;
     }
     int block_dev(int mode, const T *x, size_t nx, T *y) {
-        if (mode < kR2Filter || mode > kR2Interp) return fail(YAGI_ERR_CONFIG, "resamp2: unknown form %d", mode);
-        if (mode != kR2Filter && mode != kR2Interp && (nx & 1))
-            return fail(YAGI_ERR_CONFIG, "resamp2: this form consumes pairs of samples (got %zu)", nx);
+        YG_TRY(check_form(mode, nx));
         if (nx == 0) return YAGI_OK;
         if (mode == kR2Decim && nx >= ((size_t)1 << 19) && m <= 64) {
             // a long decimator block: the one-stage case of the MsResamp2 chain kernels (the same sums in the same order;
@@ -2785,25 +2702,21 @@ struct Resamp2Obj {
             const int mk = m;
             const C sc = scale;
             const C *hp = h1d.template as<C>();
-            const T *sp = state[cur].template as<T>();
-            T *sn = state[1 - cur].template as<T>();
+            const T *sp = state.cur<T>();
+            T *sn = state.next<T>();
             YG_TRY((launch_msresamp2_decim<T, C>(1, &mk, &sc, &hp, &sp, &sn, x, y, nx / 2, st)));
         } else {
-            YG_TRY((launch_resamp2<T, C>(mode, state[cur].template as<T>(), x, nx, h1d.template as<C>(), m, scale, toggle, y,
-                                         state[1 - cur].template as<T>(), st)));
+            YG_TRY((launch_resamp2<T, C>(mode, state.cur<T>(), x, nx, h1d.template as<C>(), m, scale, toggle, y,
+                                         state.next<T>(), st)));
         }
-        cur = 1 - cur;
+        state.flip();
         if (mode == kR2Filter) toggle = (toggle + (int)(nx & 1)) & 1;
         return YAGI_OK;
     }
     int block_host(int mode, const T *x, size_t nx, T *y) {
         if (nx == 0) return YAGI_OK;
-        const size_t ny = out_count(mode, nx);
-        YG_TRY(ws.x.ensure(nx * sizeof(T)));
-        YG_TRY(ws.y.ensure((ny ? ny : 1) * sizeof(T)));
-        YG_TRY(upload(ws.x.p, x, nx * sizeof(T), st));
-        YG_TRY(block_dev(mode, ws.x.template as<T>(), nx, ws.y.template as<T>()));
-        return download(y, ws.y.p, ny * sizeof(T), st);
+        // room for one output even where ny == 0 (a one-sample decimator block): the kernel is handed a buffer
+        return ws.run(st, x, nx, y, out_count(mode, nx), [&](const T *xd, T *yd) { return block_dev(mode, xd, nx, yd); }, 1);
     }
     int clone_into(Resamp2Obj &o) const {
         o.st = st;
@@ -2811,12 +2724,9 @@ struct Resamp2Obj {
         o.h1 = h1;
         o.toggle = toggle;
         o.scale = scale;
-        o.cur = 0;
-        YG_TRY(o.h1d.alloc(h1.size() * sizeof(C)));
-        YG_TRY(upload(o.h1d.p, h1.data(), h1.size() * sizeof(C), st));
-        YG_TRY(o.state[0].alloc(4 * (size_t)m * sizeof(T)));
-        YG_TRY(o.state[1].alloc(4 * (size_t)m * sizeof(T)));
-        YG_HIP(hipMemcpyAsync(o.state[0].p, state[cur].p, 4 * (size_t)m * sizeof(T), hipMemcpyDeviceToDevice, st));
+        YG_TRY(fill(o.h1d, h1.data(), h1.size() * sizeof(C), st));
+        YG_TRY(o.state.alloc(4 * (size_t)m * sizeof(T)));
+        YG_HIP(hipMemcpyAsync(o.state.cur(), state.cur(), 4 * (size_t)m * sizeof(T), hipMemcpyDeviceToDevice, st));
         YG_HIP(hipStreamSynchronize(st));
         return YAGI_OK;
     }
@@ -2852,7 +2762,7 @@ struct MsResamp2Obj {
     std::vector<size_t> m_stage;
     std::vector<std::unique_ptr<Resamp2Obj<K>>> stage;
     DevBuf buf[2];
-    Workspace ws;
+    Staging ws;
 
     // n execute() calls: interpolator n -> n * rate, decimator n * rate -> n (msresamp2.rs:137-152, :181 copy_from_slice)
     int check_lengths(size_t nx, size_t ny, size_t *n) const {
@@ -2909,11 +2819,11 @@ struct MsResamp2Obj {
                 mk[k] = o.m;
                 sc[k] = o.scale;
                 h1[k] = o.h1d.template as<C>();
-                sta[k] = o.state[o.cur].template as<T>();
-                stn[k] = o.state[1 - o.cur].template as<T>();
+                sta[k] = o.state.template cur<T>();
+                stn[k] = o.state.template next<T>();
             }
             YG_TRY((launch_msresamp2_interp<T, C>(ns, mk, sc, h1, sta, stn, x, y, n, st)));
-            for (size_t g = 0; g < num_stages; ++g) stage[g]->cur = 1 - stage[g]->cur;
+            for (size_t g = 0; g < num_stages; ++g) stage[g]->state.flip();
         } else if (interp) {                                         // stage s doubles n 2^s samples (:154-175)
             size_t cnt = n;
             for (size_t s = 0; s < num_stages; ++s) {
@@ -2936,11 +2846,11 @@ struct MsResamp2Obj {
                 mk[k] = o.m;
                 sc[k] = o.scale;
                 h1[k] = o.h1d.template as<C>();
-                sta[k] = o.state[o.cur].template as<T>();
-                stn[k] = o.state[1 - o.cur].template as<T>();
+                sta[k] = o.state.template cur<T>();
+                stn[k] = o.state.template next<T>();
             }
             YG_TRY((launch_msresamp2_decim<T, C>(ns, mk, sc, h1, sta, stn, x, y, n, st)));
-            for (size_t g = 0; g < num_stages; ++g) stage[g]->cur = 1 - stage[g]->cur;
+            for (size_t g = 0; g < num_stages; ++g) stage[g]->state.flip();
         } else {                                                     // stages g = S-1 .. 0, each halves (:177-197)
             size_t cnt = big;
             for (size_t s = 0; s < num_stages; ++s) {
@@ -2968,11 +2878,7 @@ struct MsResamp2Obj {
     int block_host(const T *x, size_t n, T *y) {
         if (n == 0) return YAGI_OK;
         const size_t nin = interp ? n : n * rate, nout = interp ? n * rate : n;
-        YG_TRY(ws.x.ensure(nin * sizeof(T)));
-        YG_TRY(ws.y.ensure(nout * sizeof(T)));
-        YG_TRY(upload(ws.x.p, x, nin * sizeof(T), st));
-        YG_TRY(block_dev(ws.x.template as<T>(), n, ws.y.template as<T>()));
-        return download(y, ws.y.p, nout * sizeof(T), st);
+        return ws.run(st, x, nin, y, nout, [&](const T *xd, T *yd) { return block_dev(xd, n, yd); });
     }
     float delay() const {                                            // :118-135
         float d = 0.0f;
@@ -3241,11 +3147,7 @@ struct ResampObj {
     int block_host(const T *x, size_t nx, T *y, size_t ny) {
         if (nx == 0) return YAGI_OK;
         if (nx <= kResampHostMax) return block_host_mirror(x, nx, y);
-        YG_TRY(bank.ws.x.ensure(nx * sizeof(T)));
-        YG_TRY(bank.ws.y.ensure(ny * sizeof(T)));
-        YG_TRY(upload(bank.ws.x.p, x, nx * sizeof(T), bank.st));
-        YG_TRY(block_dev(bank.ws.x.template as<T>(), nx, bank.ws.y.template as<T>(), ny));
-        return download(y, bank.ws.y.p, ny * sizeof(T), bank.st);
+        return bank.ws.run(bank.st, x, nx, y, ny, [&](const T *xd, T *yd) { return block_dev(xd, nx, yd, ny); });
     }
     int clone_into(ResampObj &o) {                 // derive(Clone) :8
         YG_TRY(bank.w.ensure_dev(bank.st));
@@ -3254,8 +3156,7 @@ struct ResampObj {
         o.bank.Ls = bank.Ls;
         o.bank.hb = bank.hb;
         o.bank.scale = bank.scale;
-        YG_TRY(o.bank.taps.alloc(o.bank.hb.size() * sizeof(C)));
-        YG_TRY(upload(o.bank.taps.p, o.bank.hb.data(), o.bank.hb.size() * sizeof(C), o.bank.st));
+        YG_TRY(fill(o.bank.taps, o.bank.hb.data(), o.bank.hb.size() * sizeof(C), o.bank.st));
         YG_TRY(o.bank.w.clone_from(bank.w, bank.st));
         o.m = m; o.bits = bits; o.r = r; o.step = step; o.phase = phase;
         return YAGI_OK;
@@ -3431,7 +3332,7 @@ struct MsResampObj {
     DevBuf carry;                        // decimator: the buffer_index (< 2^S) inputs not yet through the half-band chain
     size_t carry_len = 0;
     DevBuf mid;                          // the stream between the two parts
-    Workspace ws;
+    Staging ws;
 
     size_t group() const { return (size_t)1 << num_stages; }
     size_t num_output(size_t nx) const {                                             // :109-120
@@ -3482,11 +3383,7 @@ struct MsResampObj {
     }
     int exec_host(const T *x, size_t nx, T *y, size_t ny) {
         if (nx == 0) return YAGI_OK;
-        YG_TRY(ws.x.ensure(nx * sizeof(T)));
-        YG_TRY(ws.y.ensure(ny * sizeof(T)));
-        YG_TRY(upload(ws.x.p, x, nx * sizeof(T), st));
-        YG_TRY(exec_dev(ws.x.template as<T>(), nx, ws.y.template as<T>(), ny));
-        return download(y, ws.y.p, ny * sizeof(T), st);
+        return ws.run(st, x, nx, y, ny, [&](const T *xd, T *yd) { return exec_dev(xd, nx, yd, ny); });
     }
 };
 
@@ -3704,8 +3601,7 @@ struct IirGroup {
             if (k) A = sq(A);
             for (size_t e = 0; e < (size_t)S * S; ++e) store(h[(size_t)k * S * S + e], A[e]);
         }
-        YG_TRY(tab.alloc(h.size() * sizeof(M)));
-        YG_TRY(upload(tab.p, h.data(), h.size() * sizeof(M), st));
+        YG_TRY(fill(tab, h.data(), h.size() * sizeof(M), st));
         YG_TRY(state.alloc((size_t)S * sizeof(typename K::T)));
         return YAGI_OK;
     }
@@ -3734,9 +3630,10 @@ struct IirObj {
     C scale = one_of<C>();
     size_t head = 0;                            // TF: the VecDeque's physical head
     std::vector<T> hs;                          // host mirror of the state
-    bool host_valid = true, dev_valid = true;
+    Mirror mirror;
     std::vector<std::unique_ptr<IirGroup<K>>> groups;
-    DevBuf xs, ys, mid;
+    DevBuf mid;
+    Staging ws;
 
     size_t S() const { return hs.size(); }
     static int chunk_len(int S) {               // the combine (2 x 6 levels of S^2 f64 MACs per chunk) <= ~1/4
@@ -3771,8 +3668,7 @@ struct IirObj {
             YG_TRY(g->build(st));
         }
         hs.assign(sos ? 2 * nsos : n - 1, T{});
-        host_valid = true;
-        dev_valid = false;
+        mirror.host_written();
         return YAGI_OK;
     }
     int init_tf(const C *b_, size_t nb_, const C *a_, size_t na_) {        // new() :65-100
@@ -3811,21 +3707,21 @@ struct IirObj {
         return build();
     }
     int ensure_host() {
-        if (host_valid) return YAGI_OK;
-        for (auto &g : groups) YG_TRY(download(hs.data() + g->off, g->state.p, (size_t)g->p.S * sizeof(T), st));
-        host_valid = true;
-        return YAGI_OK;
+        return mirror.need_host([&]() -> int {
+            for (auto &g : groups) YG_TRY(download(hs.data() + g->off, g->state.p, (size_t)g->p.S * sizeof(T), st));
+            return YAGI_OK;
+        });
     }
     int ensure_dev() {
-        if (dev_valid) return YAGI_OK;
-        for (auto &g : groups) YG_TRY(upload(g->state.p, hs.data() + g->off, (size_t)g->p.S * sizeof(T), st));
-        dev_valid = true;
-        return YAGI_OK;
+        return mirror.need_dev([&]() -> int {
+            for (auto &g : groups) YG_TRY(upload(g->state.p, hs.data() + g->off, (size_t)g->p.S * sizeof(T), st));
+            return YAGI_OK;
+        });
     }
-    int reset() {                                                            // :333-343 (the deque keeps its head)
+    int reset() {                         // :333-343 (the deque keeps its head); the device copy follows at its next use
         std::fill(hs.begin(), hs.end(), T{});
-        host_valid = true;
-        dev_valid = false;
+        mirror.in_sync();                 // every entry of the host copy is new, whatever it missed before ...
+        mirror.host_written();            // ... and the device copy has not seen it
         return YAGI_OK;
     }
     T one_host(T x) {                                                        // execute() :385-390
@@ -3835,14 +3731,14 @@ struct IirObj {
     }
     int block_host_mirror(const T *x, size_t nx, T *y) {
         YG_TRY(ensure_host());
-        dev_valid = false;
+        mirror.host_written();
         for (size_t i = 0; i < nx; ++i) y[i] = one_host(x[i]);
         return YAGI_OK;
     }
     int block_dev(const T *x, size_t nx, T *y) {
         if (nx == 0) return YAGI_OK;
         YG_TRY(ensure_dev());
-        host_valid = false;
+        mirror.dev_written();
         const size_t ng = groups.size();
         if (ng > 1) YG_TRY(mid.ensure(nx * sizeof(T)));
         const T *in = x;
@@ -3860,11 +3756,7 @@ struct IirObj {
     int block_host(const T *x, size_t nx, T *y) {
         if (nx == 0) return YAGI_OK;
         if (nx <= kIirHostMax) return block_host_mirror(x, nx, y);
-        YG_TRY(xs.ensure(nx * sizeof(T)));
-        YG_TRY(ys.ensure(nx * sizeof(T)));
-        YG_TRY(upload(xs.p, x, nx * sizeof(T), st));
-        YG_TRY(block_dev(xs.template as<T>(), nx, ys.template as<T>()));
-        return download(y, ys.p, nx * sizeof(T), st);
+        return ws.run(st, x, nx, y, nx, [&](const T *xd, T *yd) { return block_dev(xd, nx, yd); });
     }
     // derive(Clone): VecDeque::clone rebuilds the deque contiguously, so the copy's head is 0 (same logical state)
     int clone_into(IirObj &o) {
@@ -4095,15 +3987,15 @@ struct OscObj {
     int vco = 0;
     uint32_t theta = 0, d_theta = 0;
     float alpha = 0.0f, beta = 0.0f;
-    DevBuf tab, xs, ys;
+    DevBuf tab;
+    Staging ws;
 
     int init(int scheme) {                                                   // new() :37-57
         if (scheme != YAGI_OSC_NCO && scheme != YAGI_OSC_VCO) return fail(YAGI_ERR_CONFIG, "osc: unknown scheme %d", scheme);
         vco = scheme == YAGI_OSC_VCO;
         std::vector<float> h;
         osc_device_table(vco, h);
-        YG_TRY(tab.alloc(h.size() * sizeof(float)));
-        YG_TRY(upload(tab.p, h.data(), h.size() * sizeof(float), st));
+        YG_TRY(fill(tab, h.data(), h.size() * sizeof(float), st));
         YG_TRY(pll_set_bandwidth(0.1f));                                     // PLL_BANDWIDTH_DEFAULT
         theta = d_theta = 0;
         return YAGI_OK;
@@ -4139,11 +4031,7 @@ struct OscObj {
             block_host(x, n, y, down);
             return YAGI_OK;
         }
-        YG_TRY(xs.ensure(n * sizeof(cf32)));
-        YG_TRY(ys.ensure(n * sizeof(cf32)));
-        YG_TRY(upload(xs.p, x, n * sizeof(cf32), st));
-        YG_TRY(block_dev(xs.as<cf32>(), n, ys.as<cf32>(), down));
-        return download(y, ys.p, n * sizeof(cf32), st);
+        return ws.run(st, x, n, y, n, [&](const cf32 *xd, cf32 *yd) { return block_dev(xd, n, yd, down); });
     }
 };
 
@@ -4341,36 +4229,36 @@ struct FirHilbObj {
     bool toggle = false;
     std::vector<float> hq;
     std::vector<float> hw;               // host mirror: w0, w1, w2, w3, L each, oldest first
-    DevBuf taps, win[2], xs, ys;
-    int cur = 0;
-    bool host_valid = true, dev_valid = true;
+    DevBuf taps;
+    PingPong<> win;
+    Staging ws;
+    Mirror mirror;
 
     int init(size_t m_, float as_) {                                         // new() :38-84
         YG_TRY(firhilb_design(m_, as_, hq));
         m = (int)m_;
         L = 2 * m;
-        YG_TRY(taps.alloc(hq.size() * sizeof(float)));
-        YG_TRY(upload(taps.p, hq.data(), hq.size() * sizeof(float), st));
-        for (auto &b : win) YG_TRY(b.alloc((size_t)4 * L * sizeof(float)));
+        YG_TRY(fill(taps, hq.data(), hq.size() * sizeof(float), st));
+        YG_TRY(win.alloc((size_t)4 * L * sizeof(float)));
         return reset();
     }
     int reset() {                                                            // :87-93
         hw.assign((size_t)4 * L, 0.0f);
-        YG_HIP(hipMemsetAsync(win[cur].p, 0, (size_t)4 * L * sizeof(float), st));
+        YG_HIP(hipMemsetAsync(win.cur(), 0, (size_t)4 * L * sizeof(float), st));
         toggle = false;
-        host_valid = dev_valid = true;
+        mirror.in_sync();
         return YAGI_OK;
     }
     int ensure_host() {
-        if (host_valid) return YAGI_OK;
-        YG_TRY(download(hw.data(), win[cur].p, hw.size() * sizeof(float), st));
-        host_valid = true;
-        return YAGI_OK;
+        return mirror.need_host([&] { return download(hw.data(), win.cur(), hw.size() * sizeof(float), st); });
     }
     int ensure_dev() {
-        if (dev_valid) return YAGI_OK;
-        YG_TRY(upload(win[cur].p, hw.data(), hw.size() * sizeof(float), st));
-        dev_valid = true;
+        return mirror.need_dev([&] { return upload(win.cur(), hw.data(), hw.size() * sizeof(float), st); });
+    }
+    // entry to the per-sample path: the host mirror is current and about to be written
+    int enter_host() {
+        YG_TRY(ensure_host());
+        mirror.host_written();
         return YAGI_OK;
     }
     float *w(int i) { return hw.data() + (size_t)i * L; }
@@ -4382,13 +4270,12 @@ struct FirHilbObj {
     float index(int i) { return w(i)[m - 1]; }                               // Window::index(m - 1)
     float dot(int i) { return firhilb_dot(hq.data(), w(i), (size_t)L); }     // hq.dotprod(window.read())
 
-    // the per-sample calls (after ensure_host)
+    // the per-sample calls (after enter_host)
     cf32 r2c(float x) {                                                      // :104-137
         cf32 y;
         if (!toggle) { push(0, x); y = cf32{index(0), dot(1)}; }
         else         { push(1, x); y = cf32{index(1), dot(0)}; }
         toggle = !toggle;
-        dev_valid = false;
         return y;
     }
     void c2r(cf32 x, float *y) {                                             // :149-180
@@ -4396,7 +4283,6 @@ struct FirHilbObj {
         if (!toggle) { push(0, x.re); push(1, x.im); yi = index(0); yq = dot(3); }
         else         { push(2, x.re); push(3, x.im); yi = index(2); yq = dot(1); }
         toggle = !toggle;
-        dev_valid = false;
         y[0] = yi + yq;
         y[1] = yi - yq;
     }
@@ -4407,7 +4293,6 @@ struct FirHilbObj {
         const float yi = index(0);
         cf32 y = toggle ? cf32{-yi, -yq} : cf32{yi, yq};
         toggle = !toggle;
-        dev_valid = false;
         return y;
     }
     void interp(cf32 x, float *y) {                                          // :233-248
@@ -4417,7 +4302,6 @@ struct FirHilbObj {
         push(1, vi);
         y[1] = dot(1);
         toggle = !toggle;
-        dev_valid = false;
     }
     void block_host(int mode, const float *x, size_t n, float *y) {
         for (size_t i = 0; i < n; ++i) {
@@ -4432,11 +4316,9 @@ struct FirHilbObj {
     int block_dev(int mode, const float *x, size_t n, float *y) {
         if (n == 0) return YAGI_OK;
         YG_TRY(ensure_dev());
-        const int nxt = cur ^ 1;
-        YG_TRY(launch_firhilb(mode, m, taps.as<float>(), win[cur].as<float>(), win[nxt].as<float>(), toggle ? 1 : 0,
-                              x, n, y, st));
-        cur = nxt;
-        host_valid = false;
+        YG_TRY(launch_firhilb(mode, m, taps.as<float>(), win.cur<float>(), win.next<float>(), toggle ? 1 : 0, x, n, y, st));
+        win.flip();
+        mirror.dev_written();
         if (n & 1) toggle = !toggle;
         return YAGI_OK;
     }
@@ -4444,15 +4326,11 @@ struct FirHilbObj {
         const size_t xf = (mode == FIRHILB_R2C) ? n : 2 * n;                  // floats in and out
         const size_t yf = 2 * n;
         if (n <= kFirhilbHostMax) {
-            YG_TRY(ensure_host());
+            YG_TRY(enter_host());
             block_host(mode, x, n, y);
             return YAGI_OK;
         }
-        YG_TRY(xs.ensure(xf * sizeof(float)));
-        YG_TRY(ys.ensure(yf * sizeof(float)));
-        YG_TRY(upload(xs.p, x, xf * sizeof(float), st));
-        YG_TRY(block_dev(mode, xs.as<float>(), n, ys.as<float>()));
-        return download(y, ys.p, yf * sizeof(float), st);
+        return ws.run(st, x, xf, y, yf, [&](const float *xd, float *yd) { return block_dev(mode, xd, n, yd); });
     }
 };
 
@@ -4486,13 +4364,11 @@ int yagi_hip_firhilb_clone(yagi_hip_firhilb q, yagi_hip_firhilb *out) try {     
     o->m = q->m;
     o->L = q->L;
     o->hq = q->hq;
-    YG_TRY(o->taps.alloc(o->hq.size() * sizeof(float)));
-    YG_TRY(upload(o->taps.p, o->hq.data(), o->hq.size() * sizeof(float), o->st));
-    for (auto &b : o->win) YG_TRY(b.alloc((size_t)4 * o->L * sizeof(float)));
+    YG_TRY(fill(o->taps, o->hq.data(), o->hq.size() * sizeof(float), o->st));
+    YG_TRY(o->win.alloc((size_t)4 * o->L * sizeof(float)));
     o->hw = q->hw;
     o->toggle = q->toggle;
-    o->host_valid = true;
-    o->dev_valid = false;
+    o->mirror.host_written();
     *out = o.release();
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
@@ -4510,7 +4386,7 @@ int yagi_hip_firhilb_reset(yagi_hip_firhilb q) try {                            
 int yagi_hip_firhilb_r2c_execute(yagi_hip_firhilb q, float x, yagi_cf32 *y) try {          // :104-137
     CHECK_Q(q);
     CHECK_PTR(y);
-    YG_TRY(q->ensure_host());
+    YG_TRY(q->enter_host());
     *y = q->r2c(x);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
@@ -4518,7 +4394,7 @@ int yagi_hip_firhilb_c2r_execute(yagi_hip_firhilb q, yagi_cf32 x, float *y0, flo
     CHECK_Q(q);
     CHECK_PTR(y0);
     CHECK_PTR(y1);
-    YG_TRY(q->ensure_host());
+    YG_TRY(q->enter_host());
     float y[2];
     q->c2r(x, y);
     *y0 = y[0];
@@ -4529,14 +4405,14 @@ int yagi_hip_firhilb_decim_execute(yagi_hip_firhilb q, const float *x, yagi_cf32
     CHECK_Q(q);
     CHECK_PTR(x);
     CHECK_PTR(y);
-    YG_TRY(q->ensure_host());
+    YG_TRY(q->enter_host());
     *y = q->decim(x);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_firhilb_interp_execute(yagi_hip_firhilb q, yagi_cf32 x, float *y) try {       // :233-248, y[0..2)
     CHECK_Q(q);
     CHECK_PTR(y);
-    YG_TRY(q->ensure_host());
+    YG_TRY(q->enter_host());
     q->interp(x, y);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
