@@ -548,6 +548,34 @@ int yagi_hip_fft_shift(yagi_cf32 *buf, size_t n);
 int yagi_hip_fft_shift_dev(yagi_cf32 *buf_dev, size_t n, size_t batch, yagi_stream_t s);
 int yagi_hip_fft_run_oneshot(const yagi_cf32 *input, yagi_cf32 *output, size_t n, int direction);
 
+/* describe: which form run / run_batch_dev take for this plan and how they cut a batch (read-only; the values come from
+ * the plan fields and the predicate the dispatch itself uses, so a test can say which loop it drove):
+ *   path         the form of the transform
+ *   batch_chunk  transforms per pass of that form's outer loop over its scratch; 0 = one launch whatever the batch
+ *   n1, n2       the split n = n1 n2 of two_pass / tile256 / mixed_two_pass / four_step, else 0
+ *   bluestein_m  the power-of-two convolution length of bluestein / bluestein_fused, else 0
+ *   nested_*     the plan that form hands its sub-transforms to through the same dispatch: the m-point plan of
+ *                bluestein, the n2-point plan of tile256 (n2 > 256) and four_step; nested_n = 0 where there is none */
+typedef enum {
+    YAGI_FFT_PATH_ONE_KERNEL = 0,       /* n <= 8192: one launch, one HBM round trip */
+    YAGI_FFT_PATH_BLUESTEIN_FUSED = 1,  /* chirp-z over m = 4096 / 8192 in one kernel */
+    YAGI_FFT_PATH_BLUESTEIN = 2,        /* chirp-z in five stages over the scratch */
+    YAGI_FFT_PATH_TWO_PASS = 3,         /* 2^14, 2^15: column / row launches */
+    YAGI_FFT_PATH_TILE256 = 4,          /* powers of two from 2^16: 256 x n2 */
+    YAGI_FFT_PATH_MIXED_TWO_PASS = 5,   /* n1 n2, both factors <= 1024: column / row launches */
+    YAGI_FFT_PATH_FOUR_STEP = 6         /* n1 n2, transposes around the sub-transforms */
+} yagi_hip_fft_path;
+typedef struct {
+    int path;                           /* yagi_hip_fft_path */
+    size_t batch_chunk;
+    size_t n1, n2;
+    size_t bluestein_m;
+    size_t nested_n;
+    int nested_path;
+    size_t nested_batch_chunk;
+} yagi_hip_fft_info;
+int yagi_hip_fft_describe(yagi_hip_fft plan, yagi_hip_fft_info *info);
+
 /* ---- Spgram<T>: src/fft/spgram.rs (Welch spectral periodogram; the in-tree consumer of window -> FFT) ----
  *   spgramcf = Spgram<Complex32>, spgramf = Spgram<f32>.
  *   create          new(nfft, wtype, window_len, delay)   :49-125  (nfft < 2, window_len > nfft, window_len == 0,

@@ -126,15 +126,22 @@ def test_config_c3_fft_4096_batch_65536(ya, oracle):
 @pytest.mark.parametrize("n", [16, 128, 256, 512, 1024, 2048, 8192, 100, 1000, 509, 2039, 4093])
 def test_fft_large_batch_on_device(ya, oracle, n):
     """many workgroups / several transforms per workgroup / a partial last workgroup (and, for 509, several
-    passes through the Bluestein scratch; 2039 and 4093: the one-kernel Bluestein form, odd n = transforms that start
+    passes through the Bluestein scratch: the batch is raised above what describe() says one pass holds; 2039 and 4093: the one-kernel Bluestein form, odd n = transforms that start
     on 8-byte boundaries only): 2^21+ points on device buffers, sampled transforms vs the f64 DFT"""
     batch = (1 << 21) // n + 3
+    plan = ya.Fft(n, ya.Direction.Forward)
+    seams = ()
+    if n == 509:                                       # two full passes through the Bluestein scratch and a ragged third
+        chunk = plan.describe().batch_chunk
+        assert plan.describe().path == ya.FftPath.bluestein and chunk > 0
+        batch = max(batch, 2 * chunk + 3)
+        assert batch > chunk and batch % chunk != 0
+        seams = (chunk - 1, chunk, 2 * chunk - 1, 2 * chunk)
     dx = ya.gen_complex_dev(SEED + 3, batch * n)
     dy = ya.DeviceArray(batch * n, np.complex64)
-    plan = ya.Fft(n, ya.Direction.Forward)
     plan.run_batch_dev(dx, dy, batch)
     ya.synchronize()
-    for b in (0, 1, 5, batch // 2, batch - 2, batch - 1):
+    for b in (0, 1, 5, batch // 2, batch - 2, batch - 1) + seams:
         truth = oracle.dft_f64(dx.to_numpy(n, offset=b * n))
         assert rel_l2(dy.to_numpy(n, offset=b * n), truth) <= 1e-5, b
 

@@ -20,6 +20,7 @@ Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <
 kernel through the C ABI (include/yagi_hip.h); importing this package fails if the library is
 not built, and every call fails with DeviceError if no GPU is present.
 """
+import collections
 import ctypes as C
 import enum
 
@@ -31,7 +32,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "Osc", "OscScheme", "FirHilbertFilter", "FftFilt", "Fft", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "Osc", "OscScheme", "FirHilbertFilter", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -1202,6 +1203,21 @@ class FftFilt(_FirBase):
 
 
 # ---- Fft (src/fft/mod.rs:33-69) ---------------------------------------------------------------
+class FftPath(enum.IntEnum):
+    """yagi_hip_fft_path: the form run / run_batch_dev take for a plan"""
+    one_kernel = 0
+    bluestein_fused = 1
+    bluestein = 2
+    two_pass = 3
+    tile256 = 4
+    mixed_two_pass = 5
+    four_step = 6
+
+
+FftInfo = collections.namedtuple("FftInfo", "path batch_chunk n1 n2 bluestein_m nested")
+FftNestedInfo = collections.namedtuple("FftNestedInfo", "n path batch_chunk")
+
+
 class Fft(_Handle):
     _prefix = "yagi_hip_fft_"
 
@@ -1217,6 +1233,14 @@ class Fft(_Handle):
         y = _out(output, self.n, np.complex64)
         _check(lib.yagi_hip_fft_run(self._h, _ptr(x), x.size, _ptr(y), y.size))
         return y
+
+    def describe(self):
+        """which form this plan takes and how it cuts a batch into passes over its scratch (yagi_hip_fft_describe);
+        batch_chunk = 0: one launch whatever the batch; nested: the plan the sub-transforms go to, or None"""
+        i = _capi.fft_info()
+        _check(lib.yagi_hip_fft_describe(self._h, C.byref(i)))
+        nested = FftNestedInfo(i.nested_n, FftPath(i.nested_path), i.nested_batch_chunk) if i.nested_n else None
+        return FftInfo(FftPath(i.path), i.batch_chunk, i.n1, i.n2, i.bluestein_m, nested)
 
     def run_batch_dev(self, in_dev, out_dev, batch, stream=None):
         _check(lib.yagi_hip_fft_run_batch_dev(self._h, _devptr(in_dev), _devptr(out_dev), batch, stream))

@@ -200,6 +200,13 @@ _sig("yagi_hip_fft_create", sz, ci, pvp)
 _sig("yagi_hip_fft_destroy", vp)
 _sig("yagi_hip_fft_clone", vp, pvp)
 _sig("yagi_hip_fft_len", vp, C.POINTER(sz))
+class fft_info(C.Structure):
+    """yagi_hip_fft_info"""
+    _fields_ = [("path", ci), ("batch_chunk", sz), ("n1", sz), ("n2", sz), ("bluestein_m", sz),
+                ("nested_n", sz), ("nested_path", ci), ("nested_batch_chunk", sz)]
+
+
+_sig("yagi_hip_fft_describe", vp, C.POINTER(fft_info))
 _sig("yagi_hip_fft_run", vp, vp, sz, vp, sz)
 _sig("yagi_hip_fft_run_batch_dev", vp, vp, vp, sz, vp)
 _sig("yagi_hip_fft_shift", vp, sz)

@@ -1368,6 +1368,12 @@ int yagi_hip_fft_len(yagi_hip_fft plan, size_t *n) try {
     *n = (size_t)plan->d.n;
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_fft_describe(yagi_hip_fft plan, yagi_hip_fft_info *info) try {
+    CHECK_Q(plan);
+    CHECK_PTR(info);
+    fft_describe(plan->d, *info);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_fft_run_batch_dev(yagi_hip_fft plan, const yagi_cf32 *in, yagi_cf32 *out, size_t batch,
                                yagi_stream_t s) try {
     CHECK_Q(plan);

@@ -336,7 +336,7 @@ static int launch_fft_two_pass(const FftPlanDev &p, const cf32 *in, cf32 *out, s
         YG_LAUNCH_CHECK();
         return YAGI_OK;
     };
-    const size_t chunk = (size_t)p.fs_chunk * 2;                 // the whole scratch holds the one intermediate
+    const size_t chunk = fft_batch_chunk(p);                     // 2 fs_chunk: the whole scratch holds the one intermediate
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const unsigned nb = (unsigned)((batch - b0) < chunk ? (batch - b0) : chunk);
         const float2 *src = reinterpret_cast<const float2 *>(in) + b0 * n;
@@ -432,8 +432,9 @@ static int launch_fft_tile256(const FftPlanDev &p, const cf32 *in, cf32 *out, si
     const float2 *tw256 = reinterpret_cast<const float2 *>(f1.tw);
     const float2 *wlo = reinterpret_cast<const float2 *>(p.fs_wlo), *whi = reinterpret_cast<const float2 *>(p.fs_whi);
     const bool fwd = p.dir == YAGI_FFT_FORWARD;
-    for (size_t b0 = 0; b0 < batch; b0 += (size_t)p.fs_chunk) {
-        const unsigned nb = (unsigned)((batch - b0) < (size_t)p.fs_chunk ? (batch - b0) : (size_t)p.fs_chunk);
+    const size_t chunk = fft_batch_chunk(p);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const unsigned nb = (unsigned)((batch - b0) < chunk ? (batch - b0) : chunk);
         const float2 *src = reinterpret_cast<const float2 *>(in) + b0 * n;
         float2 *dst = reinterpret_cast<float2 *>(out) + b0 * n;
         launch_tile256<0>(fwd, dim3((unsigned)(n2 / 16), nb), src, s0, tw256, wlo, whi, n2, st);
@@ -535,7 +536,7 @@ static int launch_fft_mixed_two_pass(const FftPlanDev &p, const cf32 *in, cf32 *
         YG_LAUNCH_CHECK();
         return YAGI_OK;
     };
-    const size_t chunk = (size_t)p.fs_chunk * 2;                 // the whole scratch holds the one intermediate (half of it: 3-8 % slower)
+    const size_t chunk = fft_batch_chunk(p);                     // 2 fs_chunk: the whole scratch holds the one intermediate (half of it: 3-8 % slower)
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const unsigned nb = (unsigned)((batch - b0) < chunk ? (batch - b0) : chunk);
         const float2 *src = reinterpret_cast<const float2 *>(in) + b0 * n;
@@ -553,8 +554,9 @@ static int launch_fft_four_step(const FftPlanDev &p, const cf32 *in, cf32 *out, 
     float2 *s0 = reinterpret_cast<float2 *>(p.fs_scratch), *s1 = s0 + (size_t)p.fs_chunk * n;
     const float2 *wlo = reinterpret_cast<const float2 *>(p.fs_wlo4), *whi = reinterpret_cast<const float2 *>(p.fs_whi4);
     const unsigned g1 = (unsigned)((n1 + 31) / 32), g2 = (unsigned)((n2 + 31) / 32);
-    for (size_t b0 = 0; b0 < batch; b0 += (size_t)p.fs_chunk) {
-        const unsigned nb = (unsigned)((batch - b0) < (size_t)p.fs_chunk ? (batch - b0) : (size_t)p.fs_chunk);
+    const size_t chunk = fft_batch_chunk(p);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const unsigned nb = (unsigned)((batch - b0) < chunk ? (batch - b0) : chunk);
         const float2 *src = reinterpret_cast<const float2 *>(in) + b0 * n;
         float2 *dst = reinterpret_cast<float2 *>(out) + b0 * n;
         // x[n1][n2] -> A[n2][n1]
@@ -636,9 +638,21 @@ bluestein_fused_kernel(const float2 *__restrict__ in, float2 *__restrict__ out, 
     }
 }
 
+// the m-point plans of the five-stage form: full plans with their own (four-step) resources when m > 8192, else the
+// one-kernel transform over the plan's own W_m tables
+static FftPlanDev bluestein_sub_plan(const FftPlanDev &p, int dir) {
+    const bool fwd = dir == YAGI_FFT_FORWARD;
+    if (p.bs_fwd && p.bs_bwd) return fwd ? *p.bs_fwd : *p.bs_bwd;
+    FftPlanDev f;
+    f.n = p.bs_m;
+    f.dir = dir;
+    f.tw = fwd ? p.bs_twf : p.bs_twb;
+    return f;
+}
+
 static int launch_fft_bluestein(const FftPlanDev &p, const cf32 *in, cf32 *out, size_t batch, hipStream_t st) {
     const int m = p.bs_m;
-    if ((m == 4096 || m == 8192) && !p.bs_fwd) {
+    if (fft_path(p) == YAGI_FFT_PATH_BLUESTEIN_FUSED) {
         if (batch > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "batch too large");
         const float2 *fin = reinterpret_cast<const float2 *>(in), *w = reinterpret_cast<const float2 *>(p.bs_w);
         const float2 *bf = reinterpret_cast<const float2 *>(p.bs_bf);
@@ -649,21 +663,12 @@ static int launch_fft_bluestein(const FftPlanDev &p, const cf32 *in, cf32 *out, 
         YG_LAUNCH_CHECK();
         return YAGI_OK;
     }
-    FftPlanDev fwd, bwd;
-    if (p.bs_fwd && p.bs_bwd) {          // m > 8192: full plans with their own (four-step) resources
-        fwd = *p.bs_fwd;
-        bwd = *p.bs_bwd;
-    } else {
-        fwd.n = bwd.n = m;
-        fwd.dir = YAGI_FFT_FORWARD;
-        bwd.dir = YAGI_FFT_BACKWARD;
-        fwd.tw = p.bs_twf;
-        bwd.tw = p.bs_twb;
-    }
+    const FftPlanDev fwd = bluestein_sub_plan(p, YAGI_FFT_FORWARD), bwd = bluestein_sub_plan(p, YAGI_FFT_BACKWARD);
     float2 *s0 = reinterpret_cast<float2 *>(p.bs_scratch), *s1 = s0 + (size_t)p.bs_chunk * m;
     const float2 *w = reinterpret_cast<const float2 *>(p.bs_w);
-    for (size_t b0 = 0; b0 < batch; b0 += (size_t)p.bs_chunk) {
-        const size_t nb = (batch - b0) < (size_t)p.bs_chunk ? (batch - b0) : (size_t)p.bs_chunk;
+    const size_t chunk = fft_batch_chunk(p);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t nb = (batch - b0) < chunk ? (batch - b0) : chunk;
         size_t g = (nb * (size_t)m + 255) / 256;
         if (g > 16384) g = 16384;
         bluestein_pre_kernel<<<(unsigned)g, 256, 0, st>>>(reinterpret_cast<const float2 *>(in) + b0 * p.n, w, p.n, m, nb, s0);
@@ -676,6 +681,58 @@ static int launch_fft_bluestein(const FftPlanDev &p, const cf32 *in, cf32 *out, 
         YG_LAUNCH_CHECK();
     }
     return YAGI_OK;
+}
+
+// The one place that says which form a plan takes (launch_fft_batch dispatches on it, yagi_hip_fft_describe reports it).
+yagi_hip_fft_path fft_path(const FftPlanDev &p) {
+    if (p.n == 4096) return YAGI_FFT_PATH_ONE_KERNEL;            // fft4096_kernel, whatever else the plan holds
+    if (p.bs_m) return (p.bs_m == 4096 || p.bs_m == 8192) && !p.bs_fwd ? YAGI_FFT_PATH_BLUESTEIN_FUSED : YAGI_FFT_PATH_BLUESTEIN;
+    if (p.fs_n1 && p.fs_wlo) return YAGI_FFT_PATH_TILE256;
+    if (p.fs_n1 && p.fs_wn) return YAGI_FFT_PATH_TWO_PASS;
+    if (p.fs_n1 && p.fs_n1 <= kFftTwoPassMixedMax && p.fs_n2 <= kFftTwoPassMixedMax && p.fs_p1->nfac && p.fs_p2->nfac)
+        return YAGI_FFT_PATH_MIXED_TWO_PASS;
+    if (p.fs_n1) return YAGI_FFT_PATH_FOUR_STEP;
+    return YAGI_FFT_PATH_ONE_KERNEL;
+}
+
+// Transforms per pass of the path's outer loop.  The two-launch forms keep one intermediate, so the whole scratch
+// (2 fs_chunk transforms) serves a pass; tile256 and four-step ping-pong between its halves.
+size_t fft_batch_chunk(const FftPlanDev &p) {
+    switch (fft_path(p)) {
+        case YAGI_FFT_PATH_BLUESTEIN: return (size_t)p.bs_chunk;
+        case YAGI_FFT_PATH_TWO_PASS:
+        case YAGI_FFT_PATH_MIXED_TWO_PASS: return 2 * (size_t)p.fs_chunk;
+        case YAGI_FFT_PATH_TILE256:
+        case YAGI_FFT_PATH_FOUR_STEP: return (size_t)p.fs_chunk;
+        default: return 0;
+    }
+}
+
+bool fft_nested_plan(const FftPlanDev &p, FftPlanDev &sub) {
+    switch (fft_path(p)) {
+        case YAGI_FFT_PATH_BLUESTEIN: sub = bluestein_sub_plan(p, YAGI_FFT_FORWARD); return true;
+        case YAGI_FFT_PATH_TILE256:
+            if (p.fs_n2 == 256) return false;                     // the rows stay in fft_tile256_kernel<MODE 1>
+            sub = *p.fs_p2;
+            return true;
+        case YAGI_FFT_PATH_FOUR_STEP: sub = *p.fs_p2; return true;
+        default: return false;
+    }
+}
+
+void fft_describe(const FftPlanDev &p, yagi_hip_fft_info &info) {
+    info = yagi_hip_fft_info{};
+    info.path = (int)fft_path(p);
+    info.batch_chunk = fft_batch_chunk(p);
+    info.n1 = (size_t)p.fs_n1;
+    info.n2 = (size_t)p.fs_n2;
+    info.bluestein_m = (size_t)p.bs_m;
+    FftPlanDev sub;
+    if (fft_nested_plan(p, sub)) {
+        info.nested_n = (size_t)sub.n;
+        info.nested_path = (int)fft_path(sub);
+        info.nested_batch_chunk = fft_batch_chunk(sub);
+    }
 }
 
 int launch_fft_batch(const FftPlanDev &p, const cf32 *in, cf32 *out, size_t batch, hipStream_t st) {
@@ -693,12 +750,15 @@ int launch_fft_batch(const FftPlanDev &p, const cf32 *in, cf32 *out, size_t batc
         YG_LAUNCH_CHECK();
         return YAGI_OK;
     }
-    if (p.bs_m) return launch_fft_bluestein(p, in, out, batch, st);
-    if (p.fs_n1 && p.fs_wlo) return launch_fft_tile256(p, in, out, batch, st);
-    if (p.fs_n1 && p.fs_wn) return launch_fft_two_pass(p, in, out, batch, st);
-    if (p.fs_n1 && p.fs_n1 <= kFftTwoPassMixedMax && p.fs_n2 <= kFftTwoPassMixedMax && p.fs_p1->nfac && p.fs_p2->nfac)
-        return launch_fft_mixed_two_pass(p, in, out, batch, st);
-    if (p.fs_n1) return launch_fft_four_step(p, in, out, batch, st);
+    switch (fft_path(p)) {
+        case YAGI_FFT_PATH_BLUESTEIN_FUSED:
+        case YAGI_FFT_PATH_BLUESTEIN: return launch_fft_bluestein(p, in, out, batch, st);
+        case YAGI_FFT_PATH_TILE256: return launch_fft_tile256(p, in, out, batch, st);
+        case YAGI_FFT_PATH_TWO_PASS: return launch_fft_two_pass(p, in, out, batch, st);
+        case YAGI_FFT_PATH_MIXED_TWO_PASS: return launch_fft_mixed_two_pass(p, in, out, batch, st);
+        case YAGI_FFT_PATH_FOUR_STEP: return launch_fft_four_step(p, in, out, batch, st);
+        case YAGI_FFT_PATH_ONE_KERNEL: break;
+    }
     if (p.n > kFftMaxLds) return fail(YAGI_ERR_INTERNAL, "fft size %d has no plan resources", p.n);
     if (p.n == 8192) {
         if (batch > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "batch too large");

@@ -168,6 +168,11 @@ constexpr int kFftMaxLds = 8192;     // complex points held in LDS by the one-ke
 constexpr int kFftTwoPassMixedMax = 1024;  // n = n1 n2 with both factors up to this: two launches (fft_mixed_twopass_kernel)
 constexpr size_t kFftMaxPow2 = (size_t)1 << 24;    // largest power of two (four-step); any other n up to 2^23 (Bluestein)
 int launch_fft_batch(const FftPlanDev &p, const cf32 *in, cf32 *out, size_t batch, hipStream_t st);
+// what launch_fft_batch does with this plan: its dispatch and its launchers' outer loops go through these three
+yagi_hip_fft_path fft_path(const FftPlanDev &p);
+size_t fft_batch_chunk(const FftPlanDev &p);                    // transforms per pass of that path's loop, 0 = no loop
+bool fft_nested_plan(const FftPlanDev &p, FftPlanDev &sub);     // the plan the path hands its sub-transforms to, if any
+void fft_describe(const FftPlanDev &p, yagi_hip_fft_info &info);
 int launch_fft_shift(cf32 *buf, size_t n, size_t batch, hipStream_t st);
 
 // ---- fftfilt_kernels.hip (FftFilt, src/filter/fftfilt.rs:103-138) ------------------------------------
