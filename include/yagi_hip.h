@@ -831,6 +831,175 @@ int yagi_hip_firhilb_decim_execute_block_dev(yagi_hip_firhilb q, const float *x_
 int yagi_hip_firhilb_interp_execute_block_dev(yagi_hip_firhilb q, const yagi_cf32 *x_dev, size_t n, float *y_dev);
 int yagi_hip_firhilb_design(size_t m, float as_, float *hq);
 
+/* ---- IIR design, low-pass second-order sections: src/filter/iir/design/mod.rs:567-717, butter.rs, cheby2.rs --------
+ *   yagi_hip_iir_design_lowpass_sos(shape, order, fc, ap, as_, b, a)   iir_design() on its low-pass / SOS branch; b, a
+ *                             hold 3 (L + r) floats, L = order / 2, r = order % 2 (the odd section last, b2 = a2 = 0).
+ *                             No device needed.  fc outside (0, 0.5), ap <= 0, as_ <= 0 and order 0 are YAGI_ERR_CONFIG
+ *                             as in the reference; YAGI_IIRDES_CHEBY1 / ELLIP / BESSEL are YAGI_ERR_CONFIG ("not built").
+ *   iirfilt_*_create_prototype(shape, order, fc, ap, as_)   IirFilter::new_prototype :148-184 (Lowpass, SOS)
+ *   iirfilt_*_create_lowpass(order, fc)                     IirFilter::new_lowpass :189-201 (Butterworth, 0.1, 60) */
+#define YAGI_IIRDES_BUTTER 0
+#define YAGI_IIRDES_CHEBY1 1
+#define YAGI_IIRDES_CHEBY2 2
+#define YAGI_IIRDES_ELLIP 3
+#define YAGI_IIRDES_BESSEL 4
+int yagi_hip_iir_design_lowpass_sos(int shape, size_t order, float fc, float ap, float as_, float *b, float *a);
+int yagi_hip_iirfilt_rrrf_create_prototype(int shape, size_t order, float fc, float ap, float as_, yagi_hip_iirfilt_rrrf *q);
+int yagi_hip_iirfilt_rrrf_create_lowpass(size_t order, float fc, yagi_hip_iirfilt_rrrf *q);
+int yagi_hip_iirfilt_crcf_create_prototype(int shape, size_t order, float fc, float ap, float as_, yagi_hip_iirfilt_crcf *q);
+int yagi_hip_iirfilt_crcf_create_lowpass(size_t order, float fc, yagi_hip_iirfilt_crcf *q);
+int yagi_hip_iirfilt_cccf_create_prototype(int shape, size_t order, float fc, float ap, float as_, yagi_hip_iirfilt_cccf *q);
+int yagi_hip_iirfilt_cccf_create_lowpass(size_t order, float fc, yagi_hip_iirfilt_cccf *q);
+
+/* ---- IirDecimationFilter / IirInterpolationFilter: src/filter/iir/iirdecim.rs, iirinterp.rs ---------------------------
+ * One IirFilter run over a virtual stream of n M filter steps:
+ *   iirdecim   steps i M .. i M + M - 1 read x[i M ..], the output of step i M is kept (iirdecim.rs:128-137)
+ *   iirinterp  step i M reads x[i], the M - 1 steps after it read +0.0, every output is kept (iirinterp.rs:93-103)
+ *   create(M, b, nb, a, na)   new() (transfer function); create_sos(M, b, a, nsos): EXTENSION, external sections
+ *   create_prototype(M, shape, order, fc, ap, as_)   new_prototype() (Lowpass, SOS); iirinterp sets the scale to M (:66-69)
+ *   create_default(M, order)  iirdecim: Butterworth, fc 0.5/M (:63-75); iirinterp: Chebyshev-II, fc 0.5/M, 0.1, 60 (:34-46)
+ *   execute                   iirdecim: x[0..M) -> one sample; iirinterp: one sample -> y[0..M); always on the host mirror
+ *   execute_block(x, n, y)    n units: iirdecim reads n M samples and writes n, iirinterp reads n and writes n M.
+ *                             Up to 32 filter steps run on the host mirror, longer slices stage through the device.
+ *   execute_block_dev         device buffers, asynchronous on the object's stream; x and y overlapping is YAGI_ERR_CONFIG
+ *   groupdelay                the filter's (iirinterp: divided by M, :118-120); get_decim / get_interp: M
+ * M < 2 is YAGI_ERR_CONFIG as in the reference; M > 65536 is YAGI_ERR_CONFIG too (the kernels' 32-bit index split).
+ * Every output word equals IirFilter's over the explicitly built stream. */
+typedef struct yagi_hip_iirdecim_rrrf_s *yagi_hip_iirdecim_rrrf;
+int yagi_hip_iirdecim_rrrf_create(size_t M, const float *b, size_t nb, const float *a, size_t na, yagi_hip_iirdecim_rrrf *q);
+int yagi_hip_iirdecim_rrrf_create_sos(size_t M, const float *b, const float *a, size_t nsos, yagi_hip_iirdecim_rrrf *q);
+int yagi_hip_iirdecim_rrrf_create_prototype(size_t M, int shape, size_t order, float fc, float ap, float as_, yagi_hip_iirdecim_rrrf *q);
+int yagi_hip_iirdecim_rrrf_create_default(size_t M, size_t order, yagi_hip_iirdecim_rrrf *q);
+int yagi_hip_iirdecim_rrrf_destroy(yagi_hip_iirdecim_rrrf q);
+int yagi_hip_iirdecim_rrrf_clone(yagi_hip_iirdecim_rrrf q, yagi_hip_iirdecim_rrrf *out);
+int yagi_hip_iirdecim_rrrf_set_stream(yagi_hip_iirdecim_rrrf q, yagi_stream_t s);
+int yagi_hip_iirdecim_rrrf_reset(yagi_hip_iirdecim_rrrf q);
+int yagi_hip_iirdecim_rrrf_execute(yagi_hip_iirdecim_rrrf q, const float *x, float *y);
+int yagi_hip_iirdecim_rrrf_execute_block(yagi_hip_iirdecim_rrrf q, const float *x, size_t n, float *y);
+int yagi_hip_iirdecim_rrrf_execute_block_dev(yagi_hip_iirdecim_rrrf q, const float *x_dev, size_t n, float *y_dev);
+int yagi_hip_iirdecim_rrrf_groupdelay(yagi_hip_iirdecim_rrrf q, float fc, float *gd);
+int yagi_hip_iirdecim_rrrf_get_decim(yagi_hip_iirdecim_rrrf q, size_t *M);
+int yagi_hip_iirdecim_rrrf_set_scale(yagi_hip_iirdecim_rrrf q, float scale);
+int yagi_hip_iirdecim_rrrf_get_scale(yagi_hip_iirdecim_rrrf q, float *scale);
+typedef struct yagi_hip_iirdecim_crcf_s *yagi_hip_iirdecim_crcf;
+int yagi_hip_iirdecim_crcf_create(size_t M, const float *b, size_t nb, const float *a, size_t na, yagi_hip_iirdecim_crcf *q);
+int yagi_hip_iirdecim_crcf_create_sos(size_t M, const float *b, const float *a, size_t nsos, yagi_hip_iirdecim_crcf *q);
+int yagi_hip_iirdecim_crcf_create_prototype(size_t M, int shape, size_t order, float fc, float ap, float as_, yagi_hip_iirdecim_crcf *q);
+int yagi_hip_iirdecim_crcf_create_default(size_t M, size_t order, yagi_hip_iirdecim_crcf *q);
+int yagi_hip_iirdecim_crcf_destroy(yagi_hip_iirdecim_crcf q);
+int yagi_hip_iirdecim_crcf_clone(yagi_hip_iirdecim_crcf q, yagi_hip_iirdecim_crcf *out);
+int yagi_hip_iirdecim_crcf_set_stream(yagi_hip_iirdecim_crcf q, yagi_stream_t s);
+int yagi_hip_iirdecim_crcf_reset(yagi_hip_iirdecim_crcf q);
+int yagi_hip_iirdecim_crcf_execute(yagi_hip_iirdecim_crcf q, const yagi_cf32 *x, yagi_cf32 *y);
+int yagi_hip_iirdecim_crcf_execute_block(yagi_hip_iirdecim_crcf q, const yagi_cf32 *x, size_t n, yagi_cf32 *y);
+int yagi_hip_iirdecim_crcf_execute_block_dev(yagi_hip_iirdecim_crcf q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_iirdecim_crcf_groupdelay(yagi_hip_iirdecim_crcf q, float fc, float *gd);
+int yagi_hip_iirdecim_crcf_get_decim(yagi_hip_iirdecim_crcf q, size_t *M);
+int yagi_hip_iirdecim_crcf_set_scale(yagi_hip_iirdecim_crcf q, float scale);
+int yagi_hip_iirdecim_crcf_get_scale(yagi_hip_iirdecim_crcf q, float *scale);
+typedef struct yagi_hip_iirdecim_cccf_s *yagi_hip_iirdecim_cccf;
+int yagi_hip_iirdecim_cccf_create(size_t M, const yagi_cf32 *b, size_t nb, const yagi_cf32 *a, size_t na, yagi_hip_iirdecim_cccf *q);
+int yagi_hip_iirdecim_cccf_create_sos(size_t M, const yagi_cf32 *b, const yagi_cf32 *a, size_t nsos, yagi_hip_iirdecim_cccf *q);
+int yagi_hip_iirdecim_cccf_create_prototype(size_t M, int shape, size_t order, float fc, float ap, float as_, yagi_hip_iirdecim_cccf *q);
+int yagi_hip_iirdecim_cccf_create_default(size_t M, size_t order, yagi_hip_iirdecim_cccf *q);
+int yagi_hip_iirdecim_cccf_destroy(yagi_hip_iirdecim_cccf q);
+int yagi_hip_iirdecim_cccf_clone(yagi_hip_iirdecim_cccf q, yagi_hip_iirdecim_cccf *out);
+int yagi_hip_iirdecim_cccf_set_stream(yagi_hip_iirdecim_cccf q, yagi_stream_t s);
+int yagi_hip_iirdecim_cccf_reset(yagi_hip_iirdecim_cccf q);
+int yagi_hip_iirdecim_cccf_execute(yagi_hip_iirdecim_cccf q, const yagi_cf32 *x, yagi_cf32 *y);
+int yagi_hip_iirdecim_cccf_execute_block(yagi_hip_iirdecim_cccf q, const yagi_cf32 *x, size_t n, yagi_cf32 *y);
+int yagi_hip_iirdecim_cccf_execute_block_dev(yagi_hip_iirdecim_cccf q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_iirdecim_cccf_groupdelay(yagi_hip_iirdecim_cccf q, float fc, float *gd);
+int yagi_hip_iirdecim_cccf_get_decim(yagi_hip_iirdecim_cccf q, size_t *M);
+int yagi_hip_iirdecim_cccf_set_scale(yagi_hip_iirdecim_cccf q, yagi_cf32 scale);
+int yagi_hip_iirdecim_cccf_get_scale(yagi_hip_iirdecim_cccf q, yagi_cf32 *scale);
+typedef struct yagi_hip_iirinterp_rrrf_s *yagi_hip_iirinterp_rrrf;
+int yagi_hip_iirinterp_rrrf_create(size_t M, const float *b, size_t nb, const float *a, size_t na, yagi_hip_iirinterp_rrrf *q);
+int yagi_hip_iirinterp_rrrf_create_sos(size_t M, const float *b, const float *a, size_t nsos, yagi_hip_iirinterp_rrrf *q);
+int yagi_hip_iirinterp_rrrf_create_prototype(size_t M, int shape, size_t order, float fc, float ap, float as_, yagi_hip_iirinterp_rrrf *q);
+int yagi_hip_iirinterp_rrrf_create_default(size_t M, size_t order, yagi_hip_iirinterp_rrrf *q);
+int yagi_hip_iirinterp_rrrf_destroy(yagi_hip_iirinterp_rrrf q);
+int yagi_hip_iirinterp_rrrf_clone(yagi_hip_iirinterp_rrrf q, yagi_hip_iirinterp_rrrf *out);
+int yagi_hip_iirinterp_rrrf_set_stream(yagi_hip_iirinterp_rrrf q, yagi_stream_t s);
+int yagi_hip_iirinterp_rrrf_reset(yagi_hip_iirinterp_rrrf q);
+int yagi_hip_iirinterp_rrrf_execute(yagi_hip_iirinterp_rrrf q, float x, float *y);
+int yagi_hip_iirinterp_rrrf_execute_block(yagi_hip_iirinterp_rrrf q, const float *x, size_t n, float *y);
+int yagi_hip_iirinterp_rrrf_execute_block_dev(yagi_hip_iirinterp_rrrf q, const float *x_dev, size_t n, float *y_dev);
+int yagi_hip_iirinterp_rrrf_groupdelay(yagi_hip_iirinterp_rrrf q, float fc, float *gd);
+int yagi_hip_iirinterp_rrrf_get_interp(yagi_hip_iirinterp_rrrf q, size_t *M);
+int yagi_hip_iirinterp_rrrf_set_scale(yagi_hip_iirinterp_rrrf q, float scale);
+int yagi_hip_iirinterp_rrrf_get_scale(yagi_hip_iirinterp_rrrf q, float *scale);
+typedef struct yagi_hip_iirinterp_crcf_s *yagi_hip_iirinterp_crcf;
+int yagi_hip_iirinterp_crcf_create(size_t M, const float *b, size_t nb, const float *a, size_t na, yagi_hip_iirinterp_crcf *q);
+int yagi_hip_iirinterp_crcf_create_sos(size_t M, const float *b, const float *a, size_t nsos, yagi_hip_iirinterp_crcf *q);
+int yagi_hip_iirinterp_crcf_create_prototype(size_t M, int shape, size_t order, float fc, float ap, float as_, yagi_hip_iirinterp_crcf *q);
+int yagi_hip_iirinterp_crcf_create_default(size_t M, size_t order, yagi_hip_iirinterp_crcf *q);
+int yagi_hip_iirinterp_crcf_destroy(yagi_hip_iirinterp_crcf q);
+int yagi_hip_iirinterp_crcf_clone(yagi_hip_iirinterp_crcf q, yagi_hip_iirinterp_crcf *out);
+int yagi_hip_iirinterp_crcf_set_stream(yagi_hip_iirinterp_crcf q, yagi_stream_t s);
+int yagi_hip_iirinterp_crcf_reset(yagi_hip_iirinterp_crcf q);
+int yagi_hip_iirinterp_crcf_execute(yagi_hip_iirinterp_crcf q, yagi_cf32 x, yagi_cf32 *y);
+int yagi_hip_iirinterp_crcf_execute_block(yagi_hip_iirinterp_crcf q, const yagi_cf32 *x, size_t n, yagi_cf32 *y);
+int yagi_hip_iirinterp_crcf_execute_block_dev(yagi_hip_iirinterp_crcf q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_iirinterp_crcf_groupdelay(yagi_hip_iirinterp_crcf q, float fc, float *gd);
+int yagi_hip_iirinterp_crcf_get_interp(yagi_hip_iirinterp_crcf q, size_t *M);
+int yagi_hip_iirinterp_crcf_set_scale(yagi_hip_iirinterp_crcf q, float scale);
+int yagi_hip_iirinterp_crcf_get_scale(yagi_hip_iirinterp_crcf q, float *scale);
+typedef struct yagi_hip_iirinterp_cccf_s *yagi_hip_iirinterp_cccf;
+int yagi_hip_iirinterp_cccf_create(size_t M, const yagi_cf32 *b, size_t nb, const yagi_cf32 *a, size_t na, yagi_hip_iirinterp_cccf *q);
+int yagi_hip_iirinterp_cccf_create_sos(size_t M, const yagi_cf32 *b, const yagi_cf32 *a, size_t nsos, yagi_hip_iirinterp_cccf *q);
+int yagi_hip_iirinterp_cccf_create_prototype(size_t M, int shape, size_t order, float fc, float ap, float as_, yagi_hip_iirinterp_cccf *q);
+int yagi_hip_iirinterp_cccf_create_default(size_t M, size_t order, yagi_hip_iirinterp_cccf *q);
+int yagi_hip_iirinterp_cccf_destroy(yagi_hip_iirinterp_cccf q);
+int yagi_hip_iirinterp_cccf_clone(yagi_hip_iirinterp_cccf q, yagi_hip_iirinterp_cccf *out);
+int yagi_hip_iirinterp_cccf_set_stream(yagi_hip_iirinterp_cccf q, yagi_stream_t s);
+int yagi_hip_iirinterp_cccf_reset(yagi_hip_iirinterp_cccf q);
+int yagi_hip_iirinterp_cccf_execute(yagi_hip_iirinterp_cccf q, yagi_cf32 x, yagi_cf32 *y);
+int yagi_hip_iirinterp_cccf_execute_block(yagi_hip_iirinterp_cccf q, const yagi_cf32 *x, size_t n, yagi_cf32 *y);
+int yagi_hip_iirinterp_cccf_execute_block_dev(yagi_hip_iirinterp_cccf q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_iirinterp_cccf_groupdelay(yagi_hip_iirinterp_cccf q, float fc, float *gd);
+int yagi_hip_iirinterp_cccf_get_interp(yagi_hip_iirinterp_cccf q, size_t *M);
+int yagi_hip_iirinterp_cccf_set_scale(yagi_hip_iirinterp_cccf q, yagi_cf32 scale);
+int yagi_hip_iirinterp_cccf_get_scale(yagi_hip_iirinterp_cccf q, yagi_cf32 *scale);
+
+/* ---- IirHilbertFilter: src/filter/iir/iirhilb.rs (IIR Hilbert transform) -----------------------------------------------
+ * The reference's two real filters with identical coefficients are one crcf filter over a complex stream (re -> filt_0,
+ * im -> filt_1); the four modes are input / output maps of that stream selected by the 2-bit state.
+ *   create(shape, n, ap, as_) new() :15-36  low-pass prototype at fc 0.25 in second-order sections; n == 0 is YAGI_ERR_CONFIG
+ *   create_default(n)         new_default() :38-47  Butterworth, 0.1, 60
+ *   create_sos(b, a, nsos)    EXTENSION: externally designed real sections
+ *   clone / reset             derive(Clone) / reset() :49-53
+ *   r2c / c2r / decim / interp _execute   :55-158 on the host mirror
+ *   *_execute_block(x, n, y)  n units on host slices (decim: 2n real -> n complex; interp: n complex -> 2n real); up to
+ *                             32 filter steps on the host mirror, longer slices stage through the device
+ *   *_execute_block_dev       device buffers, asynchronous on the object's stream; the state advances on the host at
+ *                             once.  decim and interp may run in place (x_dev == y_dev: the same bytes per unit); any
+ *                             other overlap is YAGI_ERR_CONFIG.
+ *   get_state                 EXTENSION: the 2-bit state
+ * DIVERGENCE: decim / interp compute 1 - state on a u8, which underflows in the reference when r2c / c2r left the state
+ * at 2 or 3; here that is YAGI_ERR_MODE ("reset first"). */
+typedef struct yagi_hip_iirhilbf_s *yagi_hip_iirhilbf;
+int yagi_hip_iirhilbf_create(int shape, size_t n, float ap, float as_, yagi_hip_iirhilbf *q);
+int yagi_hip_iirhilbf_create_default(size_t n, yagi_hip_iirhilbf *q);
+int yagi_hip_iirhilbf_create_sos(const float *b, const float *a, size_t nsos, yagi_hip_iirhilbf *q);
+int yagi_hip_iirhilbf_destroy(yagi_hip_iirhilbf q);
+int yagi_hip_iirhilbf_clone(yagi_hip_iirhilbf q, yagi_hip_iirhilbf *out);
+int yagi_hip_iirhilbf_set_stream(yagi_hip_iirhilbf q, yagi_stream_t s);
+int yagi_hip_iirhilbf_reset(yagi_hip_iirhilbf q);
+int yagi_hip_iirhilbf_get_state(yagi_hip_iirhilbf q, int *state);
+int yagi_hip_iirhilbf_r2c_execute(yagi_hip_iirhilbf q, float x, yagi_cf32 *y);
+int yagi_hip_iirhilbf_c2r_execute(yagi_hip_iirhilbf q, yagi_cf32 x, float *y);
+int yagi_hip_iirhilbf_decim_execute(yagi_hip_iirhilbf q, const float *x, yagi_cf32 *y);
+int yagi_hip_iirhilbf_interp_execute(yagi_hip_iirhilbf q, yagi_cf32 x, float *y);
+int yagi_hip_iirhilbf_r2c_execute_block(yagi_hip_iirhilbf q, const float *x, size_t n, yagi_cf32 *y);
+int yagi_hip_iirhilbf_c2r_execute_block(yagi_hip_iirhilbf q, const yagi_cf32 *x, size_t n, float *y);
+int yagi_hip_iirhilbf_decim_execute_block(yagi_hip_iirhilbf q, const float *x, size_t n, yagi_cf32 *y);
+int yagi_hip_iirhilbf_interp_execute_block(yagi_hip_iirhilbf q, const yagi_cf32 *x, size_t n, float *y);
+int yagi_hip_iirhilbf_r2c_execute_block_dev(yagi_hip_iirhilbf q, const float *x_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_iirhilbf_c2r_execute_block_dev(yagi_hip_iirhilbf q, const yagi_cf32 *x_dev, size_t n, float *y_dev);
+int yagi_hip_iirhilbf_decim_execute_block_dev(yagi_hip_iirhilbf q, const float *x_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_iirhilbf_interp_execute_block_dev(yagi_hip_iirhilbf q, const yagi_cf32 *x_dev, size_t n, float *y_dev);
+
 /* ---- design helper exposed for hosts that want the taps (kaiser.rs:16-51) ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);
 

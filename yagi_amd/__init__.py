@@ -32,7 +32,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "Osc", "OscScheme", "FirHilbertFilter", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -878,6 +878,14 @@ class IirFilter(_FirBase):
     def new_pll(cls, kind, w, zeta, k):                       # :310-330
         return cls._from(kind, "create_pll", w, zeta, k)
 
+    @classmethod
+    def new_prototype(cls, kind, shape, order, fc, ap, as_):  # :148-184  (Lowpass, SecondOrderSections)
+        return cls._from(kind, "create_prototype", int(IirFilterShape(shape)), order, fc, ap, as_)
+
+    @classmethod
+    def new_lowpass(cls, kind, order, fc):                    # :189-201
+        return cls._from(kind, "create_lowpass", order, fc)
+
     def get_length(self):                                     # :410-413
         n = C.c_size_t()
         _check(self._fn("get_length")(self._h, C.byref(n)))
@@ -914,6 +922,213 @@ class IirFilter(_FirBase):
         v = C.c_float()
         _check(self._fn("groupdelay")(self._h, fc, C.byref(v)))
         return np.float32(v.value)
+
+
+class IirFilterShape(enum.IntEnum):
+    """design::IirFilterShape (src/filter/iir/design/mod.rs:32-38); Butter and Cheby2 are built"""
+    Butter = 0
+    Cheby1 = 1
+    Cheby2 = 2
+    Ellip = 3
+    Bessel = 4
+
+
+def iir_design_lowpass_sos(shape, order, fc, ap=0.1, as_=60.0):
+    """iir_design() (design/mod.rs:567-717), low-pass band, second-order sections: (b, a), each [(order + 1) // 2][3].
+    No device needed."""
+    ns = max((order + 1) // 2, 1)
+    b, a = np.zeros(3 * ns, np.float32), np.zeros(3 * ns, np.float32)
+    _check(lib.yagi_hip_iir_design_lowpass_sos(int(IirFilterShape(shape)), order, fc, ap, as_, _ptr(b), _ptr(a)))
+    return b.reshape(ns, 3), a.reshape(ns, 3)
+
+
+class _IirRateBase(_FirBase):
+    """shared by IirDecimationFilter and IirInterpolationFilter: one IirFilter over the virtual stream of n*M steps"""
+    _name = _get = None
+
+    def __init__(self, kind, M, b, a):                        # new(M, b, a)
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_{self._name}_{kind}_"
+        b, a = _arr(b, self.Cdt), _arr(a, self.Cdt)
+        hd = C.c_void_p()
+        _check(self._fn("create")(M, _ptr(b), b.size, _ptr(a), a.size, C.byref(hd)))
+        self._h = hd
+
+    @classmethod
+    def _from(cls, kind, creator, *args):
+        self = object.__new__(cls)
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_{cls._name}_{kind}_"
+        hd = C.c_void_p()
+        _check(self._fn(creator)(*args, C.byref(hd)))
+        self._h = hd
+        return self
+
+    @classmethod
+    def new_sos(cls, kind, M, b, a, nsos):                    # extension: external second-order sections
+        if kind not in KINDS:
+            raise ConfigError(f"unknown type combination {kind!r}")
+        b, a = _arr(b, KINDS[kind][1]).ravel(), _arr(a, KINDS[kind][1]).ravel()
+        if b.size < 3 * nsos or a.size < 3 * nsos:
+            raise ConfigError("second-order sections need 3*nsos coefficients in b and a")
+        return cls._from(kind, "create_sos", M, _ptr(b), _ptr(a), nsos)
+
+    @classmethod
+    def new_prototype(cls, kind, M, shape, order, fc, ap, as_):
+        return cls._from(kind, "create_prototype", M, int(IirFilterShape(shape)), order, fc, ap, as_)
+
+    @classmethod
+    def new_default(cls, kind, M, order):
+        return cls._from(kind, "create_default", M, order)
+
+    def get_rate(self):
+        m = C.c_size_t()
+        _check(self._fn(self._get)(self._h, C.byref(m)))
+        return m.value
+
+    def groupdelay(self, fc):
+        v = C.c_float()
+        _check(self._fn("groupdelay")(self._h, fc, C.byref(v)))
+        return np.float32(v.value)
+
+    def execute_block_dev(self, x_dev, n, y_dev):
+        """n units on device arrays (decimator: n*M samples in, n out; interpolator: n in, n*M out)"""
+        _check(self._fn("execute_block_dev")(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+
+class IirDecimationFilter(_IirRateBase):
+    """IirDecimationFilter<T,Coeff> (src/filter/iir/iirdecim.rs): the filter runs over all n*M inputs and the output of
+    step i*M is kept.  new_default: Butterworth, fc 0.5/M (:63-75)."""
+    _name, _get = "iirdecim", "get_decim"
+    get_decim = _IirRateBase.get_rate
+
+    def execute(self, x):                                     # :128-137  x[M] -> one sample
+        x = _arr(x, self.T)
+        if x.size != self.get_rate():
+            raise ConfigError("execute() takes exactly M samples")
+        y = np.zeros(1, self.T)
+        _check(self._fn("execute")(self._h, _ptr(x), _ptr(y)))
+        return y[0]
+
+    def execute_block(self, x, n=None):                       # :145-149  n*M samples -> n
+        x = _arr(x, self.T)
+        m = self.get_rate()
+        n = x.size // m if n is None else n
+        if x.size < n * m:
+            raise ConfigError("execute_block() needs n*M input samples")
+        y = np.empty(n, self.T)
+        _check(self._fn("execute_block")(self._h, _ptr(x), n, _ptr(y)))
+        return y
+
+
+class IirInterpolationFilter(_IirRateBase):
+    """IirInterpolationFilter<T,Coeff> (src/filter/iir/iirinterp.rs): x[i] at step i*M, +0.0 at the M - 1 steps after
+    it, every output kept.  new_default: Chebyshev-II, fc 0.5/M, 0.1, 60 (:34-46); prototypes set the scale to M."""
+    _name, _get = "iirinterp", "get_interp"
+    get_interp = _IirRateBase.get_rate
+
+    def execute(self, x):                                     # :93-103  one sample -> y[M]
+        y = np.zeros(self.get_rate(), self.T)
+        _check(self._fn("execute")(self._h, _byval(x, self._Tc), _ptr(y)))
+        return y
+
+    def execute_block(self, x):                               # :106-115  n samples -> n*M
+        x = _arr(x, self.T)
+        y = np.empty(x.size * self.get_rate(), self.T)
+        _check(self._fn("execute_block")(self._h, _ptr(x), x.size, _ptr(y)))
+        return y
+
+
+class IirHilbertFilter(_Handle):
+    """IirHilbertFilter (src/filter/iir/iirhilb.rs): the reference's two real filters run as one crcf IirFilter over a
+    complex stream, the four modes as input / output maps selected by the 2-bit state.  decim / interp after r2c / c2r
+    left the state at 2 or 3 raise ModeError (the reference underflows a u8): reset first."""
+    _prefix = "yagi_hip_iirhilbf_"
+
+    def __init__(self, shape, n, ap, as_):                    # new() :15-36
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_iirhilbf_create(int(IirFilterShape(shape)), n, ap, as_, C.byref(hd)))
+        self._h = hd
+
+    @classmethod
+    def new_default(cls, n):                                  # :38-47
+        self = object.__new__(cls)
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_iirhilbf_create_default(n, C.byref(hd)))
+        self._h = hd
+        return self
+
+    @classmethod
+    def new_sos(cls, b, a, nsos):                             # extension: external real sections
+        b, a = _arr(b, np.float32).ravel(), _arr(a, np.float32).ravel()
+        if b.size < 3 * nsos or a.size < 3 * nsos:
+            raise ConfigError("second-order sections need 3*nsos coefficients in b and a")
+        self = object.__new__(cls)
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_iirhilbf_create_sos(_ptr(b), _ptr(a), nsos, C.byref(hd)))
+        self._h = hd
+        return self
+
+    def clone(self):                                          # derive(Clone)
+        new = object.__new__(type(self))
+        h = C.c_void_p()
+        _check(lib.yagi_hip_iirhilbf_clone(self._h, C.byref(h)))
+        new._h = h
+        return new
+
+    def get_state(self):
+        v = C.c_int()
+        _check(lib.yagi_hip_iirhilbf_get_state(self._h, C.byref(v)))
+        return v.value
+
+    def r2c_execute(self, x):                                 # :55-82
+        y = cf32()
+        _check(lib.yagi_hip_iirhilbf_r2c_execute(self._h, float(x), C.byref(y)))
+        return np.complex64(complex(y.re, y.im))
+
+    def c2r_execute(self, x):                                 # :90-117
+        y = C.c_float()
+        _check(lib.yagi_hip_iirhilbf_c2r_execute(self._h, _byval(x, cf32), C.byref(y)))
+        return np.float32(y.value)
+
+    def decim_execute(self, x):                               # :125-139, x: 2 real samples
+        x = _arr(x, np.float32)
+        if x.size != 2:
+            raise ConfigError("decim_execute() takes exactly 2 samples")
+        y = cf32()
+        _check(lib.yagi_hip_iirhilbf_decim_execute(self._h, _ptr(x), C.byref(y)))
+        return np.complex64(complex(y.re, y.im))
+
+    def interp_execute(self, x):                              # :147-158 -> 2 real samples
+        y = np.zeros(2, np.float32)
+        _check(lib.yagi_hip_iirhilbf_interp_execute(self._h, _byval(x, cf32), _ptr(y)))
+        return y
+
+    _SHAPES = {"r2c": (np.float32, 1, np.complex64, 1), "c2r": (np.complex64, 1, np.float32, 1),
+               "decim": (np.float32, 2, np.complex64, 1), "interp": (np.complex64, 1, np.float32, 2)}
+
+    def _block(self, name, x):
+        xdt, xin, ydt, yout = self._SHAPES[name]
+        x = _arr(x, xdt)
+        if x.size % xin:
+            raise ConfigError("decim_execute_block() takes an even number of samples")
+        n = x.size // xin
+        y = np.empty(n * yout, ydt)
+        _check(getattr(lib, f"{self._prefix}{name}_execute_block")(self._h, _ptr(x), n, _ptr(y)))
+        return y
+
+    def r2c_execute_block(self, x): return self._block("r2c", x)          # :84-88
+    def c2r_execute_block(self, x): return self._block("c2r", x)          # :119-123
+    def decim_execute_block(self, x): return self._block("decim", x)      # :141-145: 2n real -> n complex
+    def interp_execute_block(self, x): return self._block("interp", x)    # :160-164: n complex -> 2n real
+
+    def _dev(self, name, x_dev, n, y_dev):
+        _check(getattr(lib, f"{self._prefix}{name}_execute_block_dev")(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+    def r2c_execute_block_dev(self, x_dev, n, y_dev): self._dev("r2c", x_dev, n, y_dev)        # n float32 -> n complex64
+    def c2r_execute_block_dev(self, x_dev, n, y_dev): self._dev("c2r", x_dev, n, y_dev)        # n complex64 -> n float32
+    def decim_execute_block_dev(self, x_dev, n, y_dev): self._dev("decim", x_dev, n, y_dev)    # 2n float32 -> n complex64
+    def interp_execute_block_dev(self, x_dev, n, y_dev): self._dev("interp", x_dev, n, y_dev)  # n complex64 -> 2n float32
 
 
 class OscScheme(enum.Enum):

@@ -335,6 +335,45 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
     _sig(p + "get_psd", vp, f32, C.POINTER(f32))
     _sig(p + "groupdelay", vp, f32, C.POINTER(f32))
 
+# ---- IIR design, IirDecimationFilter, IirInterpolationFilter, IirHilbertFilter --------------------
+_sig("yagi_hip_iir_design_lowpass_sos", ci, sz, f32, f32, f32, vp, vp)
+for _k, (_T, _Cc) in KIND_TYPES.items():
+    _sig(f"yagi_hip_iirfilt_{_k}_create_prototype", ci, sz, f32, f32, f32, pvp)
+    _sig(f"yagi_hip_iirfilt_{_k}_create_lowpass", sz, f32, pvp)
+    for _n, _get, _x in (("iirdecim", "get_decim", vp), ("iirinterp", "get_interp", _T)):
+        p = f"yagi_hip_{_n}_{_k}_"
+        _sig(p + "create", sz, vp, sz, vp, sz, pvp)
+        _sig(p + "create_sos", sz, vp, vp, sz, pvp)
+        _sig(p + "create_prototype", sz, ci, sz, f32, f32, f32, pvp)
+        _sig(p + "create_default", sz, sz, pvp)
+        _sig(p + "destroy", vp)
+        _sig(p + "clone", vp, pvp)
+        _sig(p + "set_stream", vp, vp)
+        _sig(p + "reset", vp)
+        _sig(p + "execute", vp, _x, vp)
+        _sig(p + "execute_block", vp, vp, sz, vp)
+        _sig(p + "execute_block_dev", vp, vp, sz, vp)
+        _sig(p + "groupdelay", vp, f32, C.POINTER(f32))
+        _sig(p + _get, vp, C.POINTER(sz))
+        _sig(p + "set_scale", vp, _Cc)
+        _sig(p + "get_scale", vp, vp)
+_p = "yagi_hip_iirhilbf_"
+_sig(_p + "create", ci, sz, f32, f32, pvp)
+_sig(_p + "create_default", sz, pvp)
+_sig(_p + "create_sos", vp, vp, sz, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "get_state", vp, C.POINTER(ci))
+_sig(_p + "r2c_execute", vp, f32, C.POINTER(cf32))
+_sig(_p + "c2r_execute", vp, cf32, C.POINTER(f32))
+_sig(_p + "decim_execute", vp, vp, C.POINTER(cf32))
+_sig(_p + "interp_execute", vp, cf32, vp)
+for _n in ("r2c", "c2r", "decim", "interp"):
+    _sig(_p + _n + "_execute_block", vp, vp, sz, vp)
+    _sig(_p + _n + "_execute_block_dev", vp, vp, sz, vp)
+
 # ---- Osc ---------------------------------------------------------------------------------------
 u32 = C.c_uint32
 _p = "yagi_hip_osc_"

@@ -3536,6 +3536,7 @@ template <class T, class C> T host_iir_tf_step(T *s, size_t S, size_t *head, con
 template <class T, class C> T host_iir_sos_step(T *s, size_t nsec, const C *b, const C *a, T x);
 template <class T, class C> T host_iir_scale(T y, C scale);
 int design_iir_pintelon(bool differentiator, float *b, float *a);
+int design_iir_lowpass_sos(int shape, size_t order, float fc, float ap, float as_, float *b, float *a);
 int design_pll_active_lag(float w, float zeta, float k, float *b, float *a);
 int iir_group_delay(const float *b, size_t nb, const float *a, size_t na, float fc, float *out);
 
@@ -3613,14 +3614,28 @@ struct IirGroup {
     }
     static void store(double &d, std::complex<double> v) { d = v.real(); }
     static void store(dcplx &d, std::complex<double> v) { d = dcplx{v.real(), v.imag()}; }
-    int run(const typename K::T *x, size_t n, typename K::T *y, hipStream_t st) {
+    int scratch(size_t n) {                     // the scan's own scratch for n filter steps
         using T = typename K::T;
         const size_t nc = (n + (size_t)p.T - 1) / (size_t)p.T;
         const size_t G = (nc + kIirWg - 1) / kIirWg;
         YG_TRY(z.ensure(nc * (size_t)p.S * sizeof(T)));
         YG_TRY(agg.ensure(G * (size_t)p.S * sizeof(V)));
-        YG_TRY(init.ensure(G * (size_t)p.S * sizeof(V)));
+        return init.ensure(G * (size_t)p.S * sizeof(V));
+    }
+    int run(const typename K::T *x, size_t n, typename K::T *y, hipStream_t st) {
+        using T = typename K::T;
+        YG_TRY(scratch(n));
         return launch_iir<K>(p, x, n, y, state.template as<T>(), z.template as<T>(), agg.p, init.p, tab.p, kIirLevels, st);
+    }
+    // the mapped forms over n filter steps (kernels.hpp)
+    int run_rate(const IirRateIo<K> &io, size_t n, hipStream_t st) {
+        using T = typename K::T;
+        YG_TRY(scratch(n));
+        return launch_iir_rate<K>(p, io, n, state.template as<T>(), z.template as<T>(), agg.p, init.p, tab.p, kIirLevels, st);
+    }
+    int run_hilb(const IirHilbIo &io, size_t n, hipStream_t st) {
+        YG_TRY(scratch(n));
+        return launch_iir_hilb(p, io, n, state.template as<cf32>(), z.template as<cf32>(), agg.p, init.p, tab.p, kIirLevels, st);
     }
 };
 
@@ -3638,7 +3653,7 @@ struct IirObj {
     std::vector<T> hs;                          // host mirror of the state
     Mirror mirror;
     std::vector<std::unique_ptr<IirGroup<K>>> groups;
-    DevBuf mid;
+    DevBuf mid, mid2;                           // mid2: the mapped forms' second intermediate (their y is no spare)
     Staging ws;
 
     size_t S() const { return hs.size(); }
@@ -3757,6 +3772,28 @@ struct IirObj {
             in = out;
         }
         if (!sos) head = (head + n - nx % n) % n;
+        return YAGI_OK;
+    }
+    // The mapped forms (IirDecim, IirInterp, IirHilbertFilter): one pass per group over nsteps filter steps.
+    // pass(group, in, out) launches it; in / out are the intermediate streams at the filter's rate, nullptr where the
+    // pass reads the caller's x through the input map (first group) or writes its y through the output map (last).
+    template <class F>
+    int run_groups(size_t nsteps, F &&pass) {
+        YG_TRY(ensure_dev());
+        mirror.dev_written();
+        const size_t ng = groups.size();
+        if (ng > 1) YG_TRY(mid.ensure(nsteps * sizeof(T)));
+        if (ng > 2) YG_TRY(mid2.ensure(nsteps * sizeof(T)));
+        const T *in = nullptr;
+        for (size_t g = 0; g < ng; ++g) {
+            IirGroup<K> &G = *groups[g];
+            T *out = (g + 1 == ng) ? nullptr : (g % 2 == 0 ? mid : mid2).template as<T>();
+            G.p.scale = (g + 1 == ng) ? scale : one_of<C>();
+            if (!sos) G.p.head0 = (uint32_t)head;
+            YG_TRY(pass(G, in, out));
+            in = out;
+        }
+        if (!sos) head = (head + n - nsteps % n) % n;
         return YAGI_OK;
     }
     int block_host(const T *x, size_t nx, T *y) {
@@ -3972,6 +4009,444 @@ struct IirObj {
 YAGI_IIRFILT_IMPL(rrrf, RRRF, float, float)
 YAGI_IIRFILT_IMPL(crcf, CRCF, yagi_cf32, float)
 YAGI_IIRFILT_IMPL(cccf, CCCF, yagi_cf32, yagi_cf32)
+
+// ---- IIR design and the prototype constructors of IirFilter (iirfilt.rs:148-201) ---------------------------------------
+namespace yagi {
+// IirFilter::new_prototype on the low-pass / second-order-section branch
+template <class K>
+static int iir_init_prototype(IirObj<K> &o, int shape, size_t order, float fc, float ap, float as_) {
+    using C = typename K::C;
+    if (order > 4096) return fail(YAGI_ERR_CONFIG, "iir design: filter order %zu too large", order);
+    const size_t ns = (order + 1) / 2;
+    std::vector<float> bf(3 * ns + 3), af(3 * ns + 3);
+    YG_TRY(design_iir_lowpass_sos(shape, order, fc, ap, as_, bf.data(), af.data()));
+    std::vector<C> bc(3 * ns), ac(3 * ns);
+    for (size_t i = 0; i < 3 * ns; ++i) { bc[i] = to_c(bf[i], (C *)nullptr); ac[i] = to_c(af[i], (C *)nullptr); }
+    return o.init_sos(bc.data(), ac.data(), ns);
+}
+}  // namespace yagi
+
+extern "C" int yagi_hip_iir_design_lowpass_sos(int shape, size_t order, float fc, float ap, float as_, float *b, float *a) try {
+    if (order) { CHECK_PTR(b); CHECK_PTR(a); }
+    return design_iir_lowpass_sos(shape, order, fc, ap, as_, b, a);
+} catch (...) { return ::yagi::api_exception(); }
+
+#define YAGI_IIRFILT_PROTO_IMPL(K)                                                                  \
+    extern "C" {                                                                                    \
+    int yagi_hip_iirfilt_##K##_create_prototype(int shape, size_t order, float fc, float ap, float as_, \
+                                                yagi_hip_iirfilt_##K *q) try {                      \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        YG_TRY(require_device());                                                                   \
+        auto o = std::make_unique<yagi_hip_iirfilt_##K##_s>();                                      \
+        YG_TRY(iir_init_prototype(*o, shape, order, fc, ap, as_));                                  \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_iirfilt_##K##_create_lowpass(size_t order, float fc, yagi_hip_iirfilt_##K *q) try { \
+        return yagi_hip_iirfilt_##K##_create_prototype(YAGI_IIRDES_BUTTER, order, fc, 0.1f, 60.0f, q); \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    }
+YAGI_IIRFILT_PROTO_IMPL(rrrf)
+YAGI_IIRFILT_PROTO_IMPL(crcf)
+YAGI_IIRFILT_PROTO_IMPL(cccf)
+
+// ---- IirDecimationFilter / IirInterpolationFilter (src/filter/iir/iirdecim.rs, iirinterp.rs) -------------------------
+// One IirObj run over the virtual stream of n M filter steps: the decimator keeps the output of step i M, the
+// interpolator feeds x[i] at step i M and +0.0 elsewhere.  The kernels map the indices (iir_kernels.hip), so no buffer
+// of n M samples exists on the sparse side.
+namespace yagi {
+
+template <class K, bool INTERP>
+struct IirRateObj {
+    using T = typename K::T;
+    using C = typename K::C;
+    IirObj<K> f;
+    size_t M = 0;
+
+    int set_rate(size_t m) {
+        if (m < 2) return fail(YAGI_ERR_CONFIG, INTERP ? "interp factor must be greater than 1" : "decimation factor must be greater than 1");
+        if (m > kIirMaxRate) return fail(YAGI_ERR_CONFIG, "rates above %u are not built", kIirMaxRate);
+        M = m;
+        return YAGI_OK;
+    }
+    int init_prototype(size_t m, int shape, size_t order, float fc, float ap, float as_) {
+        YG_TRY(set_rate(m));
+        YG_TRY(iir_init_prototype(f, shape, order, fc, ap, as_));
+        if (INTERP) f.scale = to_c((float)M, (C *)nullptr);                 // iirinterp.rs:66-69
+        return YAGI_OK;
+    }
+    void unit_host(const T *x, T *y) {                                       // execute(): iirdecim.rs:128-137, iirinterp.rs:93-103
+        for (size_t i = 0; i < M; ++i) {
+            if (INTERP) {
+                y[i] = f.one_host(i == 0 ? *x : T{});
+            } else {
+                const T v = f.one_host(x[i]);
+                if (i == 0) *y = v;
+            }
+        }
+    }
+    int block_host_mirror(const T *x, size_t nunits, T *y) {
+        YG_TRY(f.ensure_host());
+        f.mirror.host_written();
+        for (size_t i = 0; i < nunits; ++i) unit_host(x + i * (INTERP ? 1 : M), y + i * (INTERP ? M : 1));
+        return YAGI_OK;
+    }
+    int block_dev(const T *x, size_t nunits, T *y) {
+        if (nunits == 0) return YAGI_OK;
+        if (nunits > ((size_t)1 << 62) / M) return fail(YAGI_ERR_CONFIG, "block of %zu units too long", nunits);
+        const size_t steps = nunits * M;
+        return f.run_groups(steps, [&](IirGroup<K> &G, const T *in, T *out) -> int {
+            const bool sparse_in = INTERP && !in, sparse_out = !INTERP && !out;
+            const T *xi = in ? in : x;
+            T *yo = out ? out : y;
+            if (!sparse_in && !sparse_out) return G.run(xi, steps, yo, f.st);        // the plain kernel at the filter's rate
+            return G.run_rate(IirRateIo<K>{xi, yo, (uint32_t)M, sparse_in, sparse_out}, steps, f.st);
+        });
+    }
+    int block_host(const T *x, size_t nunits, T *y) {
+        if (nunits == 0) return YAGI_OK;
+        if (nunits <= kIirHostMax / M) return block_host_mirror(x, nunits, y);
+        const size_t nx = INTERP ? nunits : nunits * M, ny = INTERP ? nunits * M : nunits;
+        return f.ws.run(f.st, x, nx, y, ny, [&](const T *xd, T *yd) { return block_dev(xd, nunits, yd); });
+    }
+    int groupdelay(float fc, float *out) const {
+        YG_TRY(f.groupdelay(fc, out));
+        if (INTERP) *out = *out / (float)M;                                  // iirinterp.rs:118-120
+        return YAGI_OK;
+    }
+};
+
+}  // namespace yagi
+
+#define YAGI_IIRRATE_IMPL(NAME, INTERP, GET, K, KT, T, C, EXEC_X, EXEC_XP)                          \
+    struct yagi_hip_##NAME##_##K##_s : IirRateObj<KT, INTERP> {};                                   \
+    extern "C" {                                                                                    \
+    int yagi_hip_##NAME##_##K##_create(size_t M, const C *b, size_t nb, const C *a, size_t na,      \
+                                       yagi_hip_##NAME##_##K *q) try {                              \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        YG_TRY(require_device());                                                                   \
+        if (nb) CHECK_PTR(b);                                                                       \
+        if (na) CHECK_PTR(a);                                                                       \
+        auto o = std::make_unique<yagi_hip_##NAME##_##K##_s>();                                     \
+        YG_TRY(o->set_rate(M));                                                                     \
+        YG_TRY(o->f.init_tf(b, nb, a, na));                                                         \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_create_sos(size_t M, const C *b, const C *a, size_t nsos,           \
+                                           yagi_hip_##NAME##_##K *q) try {                          \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        YG_TRY(require_device());                                                                   \
+        if (nsos) { CHECK_PTR(b); CHECK_PTR(a); }                                                   \
+        auto o = std::make_unique<yagi_hip_##NAME##_##K##_s>();                                     \
+        YG_TRY(o->set_rate(M));                                                                     \
+        YG_TRY(o->f.init_sos(b, a, nsos));                                                          \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_create_prototype(size_t M, int shape, size_t order, float fc, float ap, float as_, \
+                                                 yagi_hip_##NAME##_##K *q) try {                    \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        YG_TRY(require_device());                                                                   \
+        auto o = std::make_unique<yagi_hip_##NAME##_##K##_s>();                                     \
+        YG_TRY(o->init_prototype(M, shape, order, fc, ap, as_));                                    \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_create_default(size_t M, size_t order, yagi_hip_##NAME##_##K *q) try { \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        return yagi_hip_##NAME##_##K##_create_prototype(M, INTERP ? YAGI_IIRDES_CHEBY2 : YAGI_IIRDES_BUTTER, order, \
+                                                        0.5f / (float)M, 0.1f, 60.0f, q);           \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_destroy(yagi_hip_##NAME##_##K q) try {                              \
+        if (q) (void)hipStreamSynchronize(q->f.st);                                                 \
+        delete q;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_clone(yagi_hip_##NAME##_##K q, yagi_hip_##NAME##_##K *out) try {    \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = nullptr;                                                                             \
+        auto o = std::make_unique<yagi_hip_##NAME##_##K##_s>();                                     \
+        YG_TRY(q->f.clone_into(o->f));                                                              \
+        o->M = q->M;                                                                                \
+        *out = o.release();                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_set_stream(yagi_hip_##NAME##_##K q, yagi_stream_t s) try {          \
+        CHECK_Q(q);                                                                                 \
+        if (q->f.st == to_stream(s)) return YAGI_OK;                                                \
+        YG_HIP(hipStreamSynchronize(q->f.st));                                                      \
+        q->f.st = to_stream(s);                                                                     \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_reset(yagi_hip_##NAME##_##K q) try {                                \
+        CHECK_Q(q);                                                                                 \
+        return q->f.reset();                                                                        \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_execute(yagi_hip_##NAME##_##K q, EXEC_X x, T *y) try {              \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(y);                                                                               \
+        CHECK_PTR(EXEC_XP);                                                                         \
+        return q->block_host_mirror(EXEC_XP, 1, y);                                                 \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_execute_block(yagi_hip_##NAME##_##K q, const T *x, size_t n, T *y) try { \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x);                                                                               \
+        CHECK_PTR(y);                                                                               \
+        return q->block_host(x, n, y);                                                              \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_execute_block_dev(yagi_hip_##NAME##_##K q, const T *x, size_t n, T *y) try { \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x);                                                                               \
+        CHECK_PTR(y);                                                                               \
+        if (n > ((size_t)1 << 58) / q->M) return fail(YAGI_ERR_CONFIG, "block of %zu units too long", n); \
+        CHECK_NOALIAS(x, INTERP ? n : n * q->M, y, INTERP ? n * q->M : n);                          \
+        return q->block_dev(x, n, y);                                                               \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_groupdelay(yagi_hip_##NAME##_##K q, float fc, float *gd) try {      \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(gd);                                                                              \
+        return q->groupdelay(fc, gd);                                                               \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_##GET(yagi_hip_##NAME##_##K q, size_t *M) try {                     \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(M);                                                                               \
+        *M = q->M;                                                                                  \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_set_scale(yagi_hip_##NAME##_##K q, C scale) try {                   \
+        CHECK_Q(q);                                                                                 \
+        q->f.scale = scale;                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_##NAME##_##K##_get_scale(yagi_hip_##NAME##_##K q, C *scale) try {                  \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(scale);                                                                           \
+        *scale = q->f.scale;                                                                        \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    }
+
+YAGI_IIRRATE_IMPL(iirdecim, false, get_decim, rrrf, RRRF, float, float, const float *, x)
+YAGI_IIRRATE_IMPL(iirdecim, false, get_decim, crcf, CRCF, yagi_cf32, float, const yagi_cf32 *, x)
+YAGI_IIRRATE_IMPL(iirdecim, false, get_decim, cccf, CCCF, yagi_cf32, yagi_cf32, const yagi_cf32 *, x)
+YAGI_IIRRATE_IMPL(iirinterp, true, get_interp, rrrf, RRRF, float, float, float, &x)
+YAGI_IIRRATE_IMPL(iirinterp, true, get_interp, crcf, CRCF, yagi_cf32, float, yagi_cf32, &x)
+YAGI_IIRRATE_IMPL(iirinterp, true, get_interp, cccf, CCCF, yagi_cf32, yagi_cf32, yagi_cf32, &x)
+
+// ---- IirHilbertFilter (src/filter/iir/iirhilb.rs) -------------------------------------------------------------------
+// filt_0 and filt_1 share their coefficients and each takes exactly one step per call, so the pair is one crcf filter
+// over u = (input of filt_0, input of filt_1): real coefficients act on re and im separately, in the same operations.
+// The 2-bit state lives on the host and advances by the call's length at once, with no wait on the kernel.
+namespace yagi {
+
+struct IirHilbObj {
+    enum Mode { R2C = 0, C2R = 1, DECIM = 2, INTERP = 3 };
+    IirObj<CRCF> f;
+    uint8_t state = 0;
+
+    int init(int shape, size_t n, float ap, float as_) {                     // new() :15-36
+        if (n == 0) return fail(YAGI_ERR_CONFIG, "filter order must be greater than zero");
+        return iir_init_prototype(f, shape, n, 0.25f, ap, as_);
+    }
+    int reset() {                                                            // :49-53
+        state = 0;
+        return f.reset();
+    }
+    // decim / interp compute 1 - state on a u8 (:137, :157)
+    int check_toggle() const {
+        if (state > 1) return fail(YAGI_ERR_MODE, "iirhilbf: decim / interp after r2c / c2r left the state at %d: reset first", (int)state);
+        return YAGI_OK;
+    }
+    cf32 r2c_one(float x) {                                                  // :55-82
+        cf32 y;
+        switch (state) {
+        case 0: { const cf32 v = f.one_host(cf32{x, 0.0f}); y = cf32{2.0f * v.re, 2.0f * v.im}; break; }
+        case 1: { const cf32 v = f.one_host(cf32{0.0f, -x}); y = cf32{2.0f * -v.im, 2.0f * v.re}; break; }
+        case 2: { const cf32 v = f.one_host(cf32{-x, 0.0f}); y = cf32{2.0f * -v.re, 2.0f * -v.im}; break; }
+        default: { const cf32 v = f.one_host(cf32{0.0f, x}); y = cf32{2.0f * v.im, 2.0f * -v.re}; break; }
+        }
+        state = (state + 1) & 3;
+        return y;
+    }
+    float c2r_one(cf32 x) {                                                  // :90-117
+        float y;
+        switch (state) {
+        case 0: y = f.one_host(cf32{x.re, x.im}).re; break;
+        case 1: y = -f.one_host(cf32{x.im, -x.re}).im; break;
+        case 2: y = -f.one_host(cf32{-x.re, -x.im}).re; break;
+        default: y = f.one_host(cf32{-x.im, x.re}).im; break;
+        }
+        state = (state + 1) & 3;
+        return y;
+    }
+    cf32 decim_one(const float *x) {                                         // :125-139
+        const float xi = state ? -x[0] : x[0], xq = state ? x[1] : -x[1];
+        const cf32 v = f.one_host(cf32{xi, 0.0f});
+        (void)f.one_host(cf32{0.0f, xq});
+        state = 1 - state;
+        return cf32{2.0f * v.re, 2.0f * v.im};
+    }
+    void interp_one(cf32 x, float *y) {                                      // :147-158
+        const cf32 v0 = f.one_host(x), v1 = f.one_host(cf32{0.0f, 0.0f});
+        y[0] = state ? -2.0f * v0.re : 2.0f * v0.re;
+        y[1] = state ? 2.0f * v1.im : -2.0f * v1.im;
+        state = 1 - state;
+    }
+    static size_t in_bytes(int mode, size_t n) { return mode == R2C ? 4 * n : 8 * n; }
+    static size_t out_bytes(int mode, size_t n) { return mode == C2R ? 4 * n : 8 * n; }
+    int block_host_mirror(int mode, const void *x, size_t n, void *y) {
+        if (mode >= DECIM) YG_TRY(check_toggle());
+        YG_TRY(f.ensure_host());
+        f.mirror.host_written();
+        for (size_t i = 0; i < n; ++i) {
+            if (mode == R2C) static_cast<cf32 *>(y)[i] = r2c_one(static_cast<const float *>(x)[i]);
+            else if (mode == C2R) static_cast<float *>(y)[i] = c2r_one(static_cast<const cf32 *>(x)[i]);
+            else if (mode == DECIM) static_cast<cf32 *>(y)[i] = decim_one(static_cast<const float *>(x) + 2 * i);
+            else interp_one(static_cast<const cf32 *>(x)[i], static_cast<float *>(y) + 2 * i);
+        }
+        return YAGI_OK;
+    }
+    int block_dev(int mode, const void *x, size_t n, void *y) {
+        if (mode >= DECIM) YG_TRY(check_toggle());
+        if (n == 0) return YAGI_OK;
+        if (n > ((size_t)1 << 60)) return fail(YAGI_ERR_CONFIG, "block of %zu units too long", n);
+        const size_t steps = mode >= DECIM ? 2 * n : n;
+        const uint32_t phase = mode >= DECIM ? 2u * state : state;
+        static const int imodes[4] = {kHilbInReal, kHilbInCplx, kHilbInReal, kHilbInEven};
+        static const int omodes[4] = {kHilbOutRot2, kHilbOutProj, kHilbOutEven2, kHilbOutProj2};
+        YG_TRY(f.run_groups(steps, [&](IirGroup<CRCF> &G, const cf32 *in, cf32 *out) -> int {
+            if (in && out) return G.run(in, steps, out, f.st);
+            return G.run_hilb(IirHilbIo{in ? (const void *)in : x, out ? (void *)out : y, phase,
+                                        in ? (int)kHilbInPlain : imodes[mode], out ? (int)kHilbOutPlain : omodes[mode]},
+                              steps, f.st);
+        }));
+        state = mode >= DECIM ? (uint8_t)(state ^ (n & 1)) : (uint8_t)((state + n) & 3);
+        return YAGI_OK;
+    }
+    int block_host(int mode, const void *x, size_t n, void *y) {
+        if (n == 0) return YAGI_OK;
+        if ((mode >= DECIM ? 2 * n : n) <= kIirHostMax) return block_host_mirror(mode, x, n, y);
+        if (mode >= DECIM) YG_TRY(check_toggle());
+        YG_TRY(f.ws.x.ensure(in_bytes(mode, n)));
+        YG_TRY(f.ws.y.ensure(out_bytes(mode, n)));
+        YG_TRY(upload(f.ws.x.p, x, in_bytes(mode, n), f.st));
+        YG_TRY(block_dev(mode, f.ws.x.p, n, f.ws.y.p));
+        return download(y, f.ws.y.p, out_bytes(mode, n), f.st);
+    }
+    // device buffers: decim and interp move the same bytes per unit and every tile row is loaded before it is stored,
+    // so x == y is allowed there
+    int block_dev_checked(int mode, const void *x, size_t n, void *y) {
+        if (n == 0) return mode >= DECIM ? check_toggle() : YAGI_OK;
+        if (n > ((size_t)1 << 60)) return fail(YAGI_ERR_CONFIG, "block of %zu units too long", n);
+        if (!(mode >= DECIM && x == y)) YG_TRY(check_noalias(x, in_bytes(mode, n), y, out_bytes(mode, n)));
+        return block_dev(mode, x, n, y);
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_iirhilbf_s : IirHilbObj {};
+extern "C" {
+int yagi_hip_iirhilbf_create(int shape, size_t n, float ap, float as_, yagi_hip_iirhilbf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    YG_TRY(require_device());
+    auto o = std::make_unique<yagi_hip_iirhilbf_s>();
+    YG_TRY(o->init(shape, n, ap, as_));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_create_default(size_t n, yagi_hip_iirhilbf *q) try {       // :38-47
+    return yagi_hip_iirhilbf_create(YAGI_IIRDES_BUTTER, n, 0.1f, 60.0f, q);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_create_sos(const float *b, const float *a, size_t nsos, yagi_hip_iirhilbf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    YG_TRY(require_device());
+    if (nsos) { CHECK_PTR(b); CHECK_PTR(a); }
+    auto o = std::make_unique<yagi_hip_iirhilbf_s>();
+    YG_TRY(o->f.init_sos(b, a, nsos));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_destroy(yagi_hip_iirhilbf q) try {
+    if (q) (void)hipStreamSynchronize(q->f.st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_clone(yagi_hip_iirhilbf q, yagi_hip_iirhilbf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    auto o = std::make_unique<yagi_hip_iirhilbf_s>();
+    YG_TRY(q->f.clone_into(o->f));
+    o->state = q->state;
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_set_stream(yagi_hip_iirhilbf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->f.st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->f.st));
+    q->f.st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_reset(yagi_hip_iirhilbf q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_get_state(yagi_hip_iirhilbf q, int *state) try {
+    CHECK_Q(q);
+    CHECK_PTR(state);
+    *state = q->state;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_r2c_execute(yagi_hip_iirhilbf q, float x, yagi_cf32 *y) try {
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    return q->block_host_mirror(IirHilbObj::R2C, &x, 1, y);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_c2r_execute(yagi_hip_iirhilbf q, yagi_cf32 x, float *y) try {
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    return q->block_host_mirror(IirHilbObj::C2R, &x, 1, y);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_decim_execute(yagi_hip_iirhilbf q, const float *x, yagi_cf32 *y) try {
+    CHECK_Q(q);
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    return q->block_host_mirror(IirHilbObj::DECIM, x, 1, y);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_iirhilbf_interp_execute(yagi_hip_iirhilbf q, yagi_cf32 x, float *y) try {
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    return q->block_host_mirror(IirHilbObj::INTERP, &x, 1, y);
+} catch (...) { return ::yagi::api_exception(); }
+#define YAGI_IIRHILB_BLOCK(NAME, MODE, TX, TY)                                                                      \
+    int yagi_hip_iirhilbf_##NAME##_execute_block(yagi_hip_iirhilbf q, const TX *x, size_t n, TY *y) try {           \
+        CHECK_Q(q);                                                                                                 \
+        if (n) { CHECK_PTR(x); CHECK_PTR(y); }                                                                      \
+        return q->block_host(IirHilbObj::MODE, x, n, y);                                                            \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_iirhilbf_##NAME##_execute_block_dev(yagi_hip_iirhilbf q, const TX *x, size_t n, TY *y) try {       \
+        CHECK_Q(q);                                                                                                 \
+        if (n) { CHECK_PTR(x); CHECK_PTR(y); }                                                                      \
+        return q->block_dev_checked(IirHilbObj::MODE, x, n, y);                                                     \
+    } catch (...) { return ::yagi::api_exception(); }
+YAGI_IIRHILB_BLOCK(r2c, R2C, float, yagi_cf32)
+YAGI_IIRHILB_BLOCK(c2r, C2R, yagi_cf32, float)
+YAGI_IIRHILB_BLOCK(decim, DECIM, float, yagi_cf32)
+YAGI_IIRHILB_BLOCK(interp, INTERP, yagi_cf32, float)
+}  // extern "C"
 
 // ---- Osc (src/nco/osc.rs, nco.rs, vco.rs) -----------------------------------------------------------------------------
 // The state is the reference's: two u32 words and the PLL gains, kept on the host.  A block call passes theta0 and

@@ -413,6 +413,64 @@ int design_iir_pintelon(bool differentiator, float *b, float *a) {
     return d2sos(z, p, 8, k, b, a);
 }
 
+// iir_design (design/mod.rs:567-717), low-pass band and second-order-section format only: the analog prototype of
+// butter.rs:16-48 or cheby2.rs:18-83 (which widens to f64 itself), the prewarp (:207), iir_design_bilinear_a2d
+// (:236-271) and iir_design_d2sos.  b, a hold 3 (L + r) coefficients, L = order / 2, r = order % 2.
+int design_iir_lowpass_sos(int shape, size_t order, float fc, float ap, float as_, float *b, float *a) {
+    if (fc <= 0.0f || fc >= 0.5f) return fail(YAGI_ERR_CONFIG, "cutoff frequency out of range");
+    if (ap <= 0.0f) return fail(YAGI_ERR_CONFIG, "pass-band ripple out of range");
+    if (as_ <= 0.0f) return fail(YAGI_ERR_CONFIG, "stop-band ripple out of range");
+    if (order == 0) return fail(YAGI_ERR_CONFIG, "filter order must be > 0");
+    const size_t n = order, r = n % 2, L = (n - r) / 2;
+    const c32 one{1.0f, 0.0f};
+    auto inv = [](c32 z) {                                   // num-complex inv()
+        const float d = z.re * z.re + z.im * z.im;
+        return c32{z.re / d, -z.im / d};
+    };
+    std::vector<c32> pa, za;
+    if (shape == YAGI_IIRDES_BUTTER) {
+        const float pi = 3.14159265358979323846f;
+        for (size_t i = 0; i < L; ++i) {
+            const float theta = (2.0f * ((float)i + 1.0f) + (float)n - 1.0f) * pi / (2.0f * (float)n);
+            pa.push_back(polar(1.0f, theta));
+            pa.push_back(polar(1.0f, -theta));
+        }
+        if (r) pa.push_back(c32{-1.0f, 0.0f});
+    } else if (shape == YAGI_IIRDES_CHEBY2) {
+        const double pi = 3.14159265358979323846;
+        const float es = std::pow(10.0f, -as_ / 20.0f);
+        const double ew = (double)es, t0 = std::sqrt(1.0 + 1.0 / (ew * ew));
+        const double tp = std::pow(t0 + 1.0 / ew, 1.0 / (double)n), tm = std::pow(t0 - 1.0 / ew, 1.0 / (double)n);
+        const double bb = 0.5 * (tp + tm), aa = 0.5 * (tp - tm);
+        for (size_t i = 0; i < L; ++i) {
+            const double theta = (double)(2 * (i + 1) + n - 1) * pi / (double)(2 * n);
+            pa.push_back(inv(c32{(float)(aa * std::cos(theta)), (float)(-bb * std::sin(theta))}));
+            pa.push_back(inv(c32{(float)(aa * std::cos(theta)), (float)(bb * std::sin(theta))}));
+        }
+        if (r) pa.push_back(inv(c32{(float)-aa, 0.0f}));
+        for (size_t i = 0; i < L; ++i) {
+            const double theta = 0.5 * pi * (double)(2 * (i + 1) - 1) / (double)n;
+            za.push_back(cneg(inv(c32{0.0f, (float)std::cos(theta)})));
+            za.push_back(inv(c32{0.0f, (float)std::cos(theta)}));
+        }
+    } else if (shape == YAGI_IIRDES_CHEBY1 || shape == YAGI_IIRDES_ELLIP || shape == YAGI_IIRDES_BESSEL) {
+        return fail(YAGI_ERR_CONFIG, "iir design: the Chebyshev-I, elliptic and Bessel prototypes are not built");
+    } else {
+        return fail(YAGI_ERR_CONFIG, "iir design: unknown filter shape %d", shape);
+    }
+    const float m = std::tan(3.14159265358979323846f * fc);
+    std::vector<c32> zd(n), pd(n);
+    c32 kd = one;                                            // k0 = 1 for both shapes
+    auto scl = [](c32 z, float v) { return c32{z.re * v, z.im * v}; };
+    auto csub = [](c32 x, c32 y) { return c32{x.re - y.re, x.im - y.im}; };
+    for (size_t i = 0; i < n; ++i) {
+        zd[i] = (i < za.size()) ? cdiv(cadd(one, scl(za[i], m)), csub(one, scl(za[i], m))) : c32{-1.0f, 0.0f};
+        pd[i] = cdiv(cadd(one, scl(pa[i], m)), csub(one, scl(pa[i], m)));
+        kd = cmul(kd, cdiv(csub(one, pd[i]), csub(one, zd[i])));
+    }
+    return d2sos(zd.data(), pd.data(), n, kd, b, a);
+}
+
 // iir_design_pll_active_lag (design/pll.rs:16-39)
 int design_pll_active_lag(float w, float zeta, float k, float *b, float *a) {
     if (w <= 0.0f) return fail(YAGI_ERR_CONFIG, "bandwidth must be greater than 0");

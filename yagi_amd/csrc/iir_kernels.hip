@@ -13,6 +13,8 @@
 // fuse the recurrence); tests/test_iir_isa_cpu.py checks that no f32 FMA is left in the chunk kernels.
 #pragma clang fp contract(off)
 
+#include <type_traits>
+
 #include "kernels.hpp"
 
 namespace yagi {
@@ -200,14 +202,146 @@ __device__ __forceinline__ typename K::T sos_step(typename K::T (&s)[SC], int ns
     return u;
 }
 
+// ---- I/O policies ------------------------------------------------------------------------------------------------
+// A policy says how filter step gi of the call obtains its input and where, if anywhere, its output goes.  load() fills
+// the workgroup's LDS tile (64 chunks x kTs steps) for the time slice at t0, store() empties it; element e = lane + 64 r
+// of the tile is row e / kTs (the chunk), column e % kTs, which is step wg0 + row T + t0 + column.
+template <class K>
+struct PlainPolicy {                     // IirFilter: step gi reads x[gi] and writes y[gi]
+    using T = typename K::T;
+    const T *__restrict__ x;
+    T *__restrict__ y;
+    __device__ __forceinline__ void load(T (*tile)[kTs + 1], uint64_t wg0, uint64_t Tl, int t0, int lane, uint64_t n) const {
+#pragma unroll
+        for (int r = 0; r < kTs; ++r) {
+            const int e = lane + r * kIirWg, j = e / kTs, tt = e % kTs;
+            const uint64_t gi = wg0 + (uint64_t)j * Tl + (uint64_t)(t0 + tt);
+            tile[j][tt] = (gi < n) ? x[gi] : izero<T>();
+        }
+    }
+    __device__ __forceinline__ void store(T (*tile)[kTs + 1], uint64_t wg0, uint64_t Tl, int t0, int lane, uint64_t n) const {
+#pragma unroll
+        for (int r = 0; r < kTs; ++r) {
+            const int e = lane + r * kIirWg, j = e / kTs, tt = e % kTs;
+            const uint64_t gi = wg0 + (uint64_t)j * Tl + (uint64_t)(t0 + tt);
+            if (gi < n) y[gi] = tile[j][tt];
+        }
+    }
+};
+
+// IirDecim / IirInterp: the sparse side holds one sample per M steps, sample gi / M at the steps with gi % M == 0.
+// A 64-bit division per element would bring f32 multiply-adds into the kernel, so the workgroup's first step is split
+// once in 32-bit arithmetic, g W = ((g / M) W) M + (g % M) W with W = 64 T steps per workgroup, and the tile walk
+// carries (quotient, remainder) along: one r step moves 4 rows = 4 T steps.  M <= 2^16 keeps (g % M) W + W < 2^31.
+template <class K>
+struct RatePolicy {
+    using T = typename K::T;
+    const T *x;
+    T *y;
+    uint32_t M, Tc;
+    bool sparse_in, sparse_out;
+    uint32_t off_wg, dq, dm;
+    uint64_t base;
+    __device__ __forceinline__ RatePolicy(const IirRateIo<K> &a, uint32_t g, uint32_t Tchunk)
+        : x(a.x), y(a.y), M(a.M), Tc(Tchunk), sparse_in(a.sparse_in != 0), sparse_out(a.sparse_out != 0) {
+        const uint32_t W = (uint32_t)kIirWg * Tchunk, rs = (uint32_t)(kIirWg / kTs) * Tchunk;
+        off_wg = (g % M) * W;
+        base = (uint64_t)(g / M) * W;
+        dq = rs / M;
+        dm = rs % M;
+    }
+    // f(row, column, step holds a sample and lies inside the call, index of that sample)
+    template <class F>
+    __device__ __forceinline__ void walk(uint64_t wg0, uint64_t Tl, int t0, int lane, uint64_t n, F &&f) const {
+        const int j0 = lane / kTs, tt = lane % kTs;
+        const uint32_t off = off_wg + (uint32_t)j0 * Tc + (uint32_t)(t0 + tt);
+        uint32_t q = off / M, rm = off % M;
+#pragma unroll
+        for (int r = 0; r < kTs; ++r) {
+            const int j = j0 + r * (kIirWg / kTs);
+            const uint64_t gi = wg0 + (uint64_t)j * Tl + (uint64_t)(t0 + tt);
+            f(j, tt, rm == 0 && gi < n, base + q);
+            q += dq;
+            rm += dm;
+            if (rm >= M) { rm -= M; ++q; }
+        }
+    }
+    __device__ __forceinline__ void load(T (*tile)[kTs + 1], uint64_t wg0, uint64_t Tl, int t0, int lane, uint64_t n) const {
+        if (!sparse_in) return PlainPolicy<K>{x, y}.load(tile, wg0, Tl, t0, lane, n);
+        // a step without a sample feeds +0.0 through the full recurrence (the reference calls execute(0.0))
+        walk(wg0, Tl, t0, lane, n, [&](int j, int tt, bool has, uint64_t i) { tile[j][tt] = has ? x[i] : izero<T>(); });
+    }
+    __device__ __forceinline__ void store(T (*tile)[kTs + 1], uint64_t wg0, uint64_t Tl, int t0, int lane, uint64_t n) const {
+        if (!sparse_out) return PlainPolicy<K>{x, y}.store(tile, wg0, Tl, t0, lane, n);
+        walk(wg0, Tl, t0, lane, n, [&](int j, int tt, bool has, uint64_t i) { if (has) y[i] = tile[j][tt]; });
+    }
+};
+
+// IirHilbertFilter: the reference's two real filters are one crcf filter over the complex stream u (re -> filt_0,
+// im -> filt_1).  With k = (phase + gi) & 3 the input map turns x into u and the output map turns the filter output v
+// into y (iirhilb.rs:55-164); negations are sign-bit flips and the factor 2 is exact.  Every chunk and every tile row
+// starts at a multiple of 4 steps, so k follows from the column alone.
+struct HilbPolicy {
+    using T = cf32;
+    const void *x;
+    void *y;
+    uint32_t ph;
+    int im, om;
+    __device__ __forceinline__ HilbPolicy(const IirHilbIo &a, uint32_t, uint32_t) : x(a.x), y(a.y), ph(a.phase), im(a.imode), om(a.omode) {}
+    __device__ __forceinline__ void load(cf32 (*tile)[kTs + 1], uint64_t wg0, uint64_t Tl, int t0, int lane, uint64_t n) const {
+#pragma unroll
+        for (int r = 0; r < kTs; ++r) {
+            const int e = lane + r * kIirWg, j = e / kTs, tt = e % kTs;
+            const uint64_t gi = wg0 + (uint64_t)j * Tl + (uint64_t)(t0 + tt);
+            const uint32_t k = (ph + (uint32_t)(t0 + tt)) & 3u;
+            cf32 u{0.0f, 0.0f};
+            if (im == kHilbInReal) {                        // r2c, decim: (x,0), (0,-x), (-x,0), (0,x)
+                const float v = (gi < n) ? static_cast<const float *>(x)[gi] : 0.0f;
+                const float s = (k == 1 || k == 2) ? -v : v;
+                u = (k & 1u) ? cf32{0.0f, s} : cf32{s, 0.0f};
+            } else if (im == kHilbInCplx) {                 // c2r: x, (im,-re), -x, (-im,re)
+                const cf32 v = (gi < n) ? static_cast<const cf32 *>(x)[gi] : cf32{0.0f, 0.0f};
+                u = (k == 0) ? v : (k == 1) ? cf32{v.im, -v.re} : (k == 2) ? cf32{-v.re, -v.im} : cf32{-v.im, v.re};
+            } else if (im == kHilbInEven) {                 // interp: x at the even steps, (0,0) at the odd ones
+                if (!(tt & 1) && gi < n) u = static_cast<const cf32 *>(x)[gi >> 1];
+            } else {
+                if (gi < n) u = static_cast<const cf32 *>(x)[gi];
+            }
+            tile[j][tt] = u;
+        }
+    }
+    __device__ __forceinline__ void store(cf32 (*tile)[kTs + 1], uint64_t wg0, uint64_t Tl, int t0, int lane, uint64_t n) const {
+#pragma unroll
+        for (int r = 0; r < kTs; ++r) {
+            const int e = lane + r * kIirWg, j = e / kTs, tt = e % kTs;
+            const uint64_t gi = wg0 + (uint64_t)j * Tl + (uint64_t)(t0 + tt);
+            const uint32_t k = (ph + (uint32_t)(t0 + tt)) & 3u;
+            if (gi >= n) continue;
+            const cf32 v = tile[j][tt];
+            if (om == kHilbOutRot2) {                       // r2c: 2 (re,im), 2 (-im,re), 2 (-re,-im), 2 (im,-re)
+                const float a = 2.0f * v.re, b = 2.0f * v.im;
+                static_cast<cf32 *>(y)[gi] = (k == 0) ? cf32{a, b} : (k == 1) ? cf32{-b, a} : (k == 2) ? cf32{-a, -b} : cf32{b, -a};
+            } else if (om == kHilbOutProj || om == kHilbOutProj2) {     // c2r: re, -im, -re, im; interp: twice that
+                const float w = (k & 1u) ? v.im : v.re;
+                const float s = (k == 1 || k == 2) ? -w : w;
+                static_cast<float *>(y)[gi] = (om == kHilbOutProj2) ? 2.0f * s : s;
+            } else if (om == kHilbOutEven2) {               // decim: 2 v at the even steps
+                if (!(tt & 1)) static_cast<cf32 *>(y)[gi >> 1] = cf32{2.0f * v.re, 2.0f * v.im};
+            } else {
+                static_cast<cf32 *>(y)[gi] = v;
+            }
+        }
+    }
+};
+
 // ---- phases A and C ---------------------------------------------------------------------------------------------
 // OUT = false: phase A (zero start, z and the workgroup aggregate); OUT = true: phase C (exact start, y and the state)
-template <class K, bool SOS, int SC, bool OUT>
-__global__ void __launch_bounds__(kIirWg)
-iir_chunk_kernel(const IirParams<K> p, const typename K::T *__restrict__ x, size_t n, typename K::T *__restrict__ y,
-                 typename K::T *__restrict__ z, typename IirF64<K>::V *__restrict__ agg,
-                 const typename IirF64<K>::V *__restrict__ init, typename K::T *__restrict__ state,
-                 const typename IirF64<K>::M *__restrict__ ptab) {
+// n = filter steps of the call
+template <class K, bool SOS, int SC, bool OUT, class IO>
+__device__ __forceinline__ void
+iir_scan_pass(const IirParams<K> &p, const IO &io, size_t n, typename K::T *__restrict__ z,
+              typename IirF64<K>::V *__restrict__ agg, const typename IirF64<K>::V *__restrict__ init,
+              typename K::T *__restrict__ state, const typename IirF64<K>::M *__restrict__ ptab) {
     using T = typename K::T;
     using V = typename IirF64<K>::V;
     using M = typename IirF64<K>::M;
@@ -267,12 +401,7 @@ iir_chunk_kernel(const IirParams<K> p, const typename K::T *__restrict__ x, size
 #pragma unroll 1
     for (int t0 = 0; t0 < p.T; t0 += kTs) {
         __syncthreads();
-#pragma unroll
-        for (int r = 0; r < kTs; ++r) {
-            const int e = lane + r * kIirWg, j = e / kTs, tt = e % kTs;
-            const uint64_t gi = wg0 + (uint64_t)j * Tl + (uint64_t)(t0 + tt);
-            tile[j][tt] = (gi < n) ? x[gi] : izero<T>();
-        }
+        io.load(tile, wg0, Tl, t0, lane, n);
         __syncthreads();
 #pragma unroll 1
         for (int tt = 0; tt < kTs; ++tt) {
@@ -284,12 +413,7 @@ iir_chunk_kernel(const IirParams<K> p, const typename K::T *__restrict__ x, size
         }
         if (OUT) {
             __syncthreads();
-#pragma unroll
-            for (int r = 0; r < kTs; ++r) {
-                const int e = lane + r * kIirWg, j = e / kTs, tt = e % kTs;
-                const uint64_t gi = wg0 + (uint64_t)j * Tl + (uint64_t)(t0 + tt);
-                if (gi < n) y[gi] = tile[j][tt];
-            }
+            io.store(tile, wg0, Tl, t0, lane, n);
         }
     }
 
@@ -312,6 +436,29 @@ iir_chunk_kernel(const IirParams<K> p, const typename K::T *__restrict__ x, size
         for (int i = 0; i < SC; ++i)
             if (i < S) state[i] = s[i];
     }
+}
+
+template <class K, bool SOS, int SC, bool OUT>
+__global__ void __launch_bounds__(kIirWg)
+iir_chunk_kernel(const IirParams<K> p, const typename K::T *__restrict__ x, size_t n, typename K::T *__restrict__ y,
+                 typename K::T *__restrict__ z, typename IirF64<K>::V *__restrict__ agg,
+                 const typename IirF64<K>::V *__restrict__ init, typename K::T *__restrict__ state,
+                 const typename IirF64<K>::M *__restrict__ ptab) {
+    iir_scan_pass<K, SOS, SC, OUT>(p, PlainPolicy<K>{x, y}, n, z, agg, init, state, ptab);
+}
+
+// the mapped forms: A = IirRateIo<K> (IirDecim, IirInterp) or IirHilbIo (IirHilbertFilter)
+template <class K, class A> struct PolicyOf;
+template <class K> struct PolicyOf<K, IirRateIo<K>> { using type = RatePolicy<K>; };
+template <> struct PolicyOf<CRCF, IirHilbIo> { using type = HilbPolicy; };
+
+template <class K, bool SOS, int SC, bool OUT, class A>
+__global__ void __launch_bounds__(kIirWg)
+iirmap_kernel(const IirParams<K> p, const A a, size_t n, typename K::T *__restrict__ z,
+              typename IirF64<K>::V *__restrict__ agg, const typename IirF64<K>::V *__restrict__ init,
+              typename K::T *__restrict__ state, const typename IirF64<K>::M *__restrict__ ptab) {
+    const typename PolicyOf<K, A>::type io(a, (uint32_t)blockIdx.x, (uint32_t)p.T);
+    iir_scan_pass<K, SOS, SC, OUT>(p, io, n, z, agg, init, state, ptab);
 }
 
 // ---- phase B: one wave scans the G - 1 workgroup aggregates, lane l owning 2^lc consecutive ones ------------------
@@ -366,9 +513,12 @@ iir_phase_b(const typename IirF64<K>::V *__restrict__ agg, uint64_t G, int S, in
     }
 }
 
-template <class K, bool SOS, int SC>
-int run_iir(const IirParams<K> &p, const typename K::T *x, size_t n, typename K::T *y, typename K::T *state,
-            typename K::T *z, void *agg, void *init, const void *ptab, int levels, hipStream_t st) {
+// A = PlainArgs<K> launches the plain chunk kernels, any other argument block the mapped ones; phase B is the same
+template <class K> struct PlainArgs { const typename K::T *x; typename K::T *y; };
+
+template <class K, bool SOS, int SC, class A>
+int run_iir(const IirParams<K> &p, const A &a, size_t n, typename K::T *state, typename K::T *z, void *agg, void *init,
+            const void *ptab, int levels, hipStream_t st) {
     using V = typename IirF64<K>::V;
     using M = typename IirF64<K>::M;
     const uint64_t Tl = (uint64_t)p.T;
@@ -379,13 +529,41 @@ int run_iir(const IirParams<K> &p, const typename K::T *x, size_t n, typename K:
     if (12 + lc > levels || G > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "iirfilt: block of %zu samples too long", n);
     const M *P = static_cast<const M *>(ptab);
     V *ag = static_cast<V *>(agg), *in = static_cast<V *>(init);
-    iir_chunk_kernel<K, SOS, SC, false><<<(unsigned)G, kIirWg, 0, st>>>(p, x, n, y, z, ag, in, state, P);
+    if constexpr (std::is_same<A, PlainArgs<K>>::value)
+        iir_chunk_kernel<K, SOS, SC, false><<<(unsigned)G, kIirWg, 0, st>>>(p, a.x, n, a.y, z, ag, in, state, P);
+    else
+        iirmap_kernel<K, SOS, SC, false, A><<<(unsigned)G, kIirWg, 0, st>>>(p, a, n, z, ag, in, state, P);
     YG_LAUNCH_CHECK();
     iir_phase_b<K, SC><<<1, kIirWg, 0, st>>>(ag, G, p.S, lc, state, in, P);
     YG_LAUNCH_CHECK();
-    iir_chunk_kernel<K, SOS, SC, true><<<(unsigned)G, kIirWg, 0, st>>>(p, x, n, y, z, ag, in, state, P);
+    if constexpr (std::is_same<A, PlainArgs<K>>::value)
+        iir_chunk_kernel<K, SOS, SC, true><<<(unsigned)G, kIirWg, 0, st>>>(p, a.x, n, a.y, z, ag, in, state, P);
+    else
+        iirmap_kernel<K, SOS, SC, true, A><<<(unsigned)G, kIirWg, 0, st>>>(p, a, n, z, ag, in, state, P);
     YG_LAUNCH_CHECK();
     return YAGI_OK;
+}
+
+// the state cap of the filter picks the instantiation; TF = false leaves the transfer-function forms out (Hilbert)
+template <class K, bool TF, class A>
+int dispatch_iir(const IirParams<K> &p, const A &a, size_t n, typename K::T *state, typename K::T *z, void *agg,
+                 void *init, const void *ptab, int levels, hipStream_t st) {
+    if (n == 0) return YAGI_OK;
+    if (p.T < kTs || (p.T & (p.T - 1)) || p.n < 1) return fail(YAGI_ERR_INTERNAL, "iirfilt: bad launch shape");
+    if (p.sos) {
+        if (p.n > kIirSosGroup || p.S != 2 * p.n) return fail(YAGI_ERR_INTERNAL, "iirfilt: bad section count");
+        if (p.n <= 4) return run_iir<K, true, 8>(p, a, n, state, z, agg, init, ptab, levels, st);
+        if (p.n <= 8) return run_iir<K, true, 16>(p, a, n, state, z, agg, init, ptab, levels, st);
+        return run_iir<K, true, 2 * kIirSosGroup>(p, a, n, state, z, agg, init, ptab, levels, st);
+    }
+    if constexpr (TF) {
+        if (p.n > kIirTfMaxN || p.S != p.n - 1) return fail(YAGI_ERR_INTERNAL, "iirfilt: bad filter length");
+        if (p.S <= 4) return run_iir<K, false, 4>(p, a, n, state, z, agg, init, ptab, levels, st);
+        if (p.S <= 8) return run_iir<K, false, 8>(p, a, n, state, z, agg, init, ptab, levels, st);
+        if (p.S <= 16) return run_iir<K, false, 16>(p, a, n, state, z, agg, init, ptab, levels, st);
+        return run_iir<K, false, kIirTfMaxN - 1>(p, a, n, state, z, agg, init, ptab, levels, st);
+    }
+    return fail(YAGI_ERR_INTERNAL, "iirfilt: this form runs second-order sections only");
 }
 
 }  // namespace
@@ -393,19 +571,20 @@ int run_iir(const IirParams<K> &p, const typename K::T *x, size_t n, typename K:
 template <class K>
 int launch_iir(const IirParams<K> &p, const typename K::T *x, size_t n, typename K::T *y, typename K::T *state,
                typename K::T *z, void *agg, void *init, const void *ptab, int levels, hipStream_t st) {
-    if (n == 0) return YAGI_OK;
-    if (p.T < kTs || (p.T & (p.T - 1)) || p.n < 1) return fail(YAGI_ERR_INTERNAL, "iirfilt: bad launch shape");
-    if (p.sos) {
-        if (p.n > kIirSosGroup || p.S != 2 * p.n) return fail(YAGI_ERR_INTERNAL, "iirfilt: bad section count");
-        if (p.n <= 4) return run_iir<K, true, 8>(p, x, n, y, state, z, agg, init, ptab, levels, st);
-        if (p.n <= 8) return run_iir<K, true, 16>(p, x, n, y, state, z, agg, init, ptab, levels, st);
-        return run_iir<K, true, 2 * kIirSosGroup>(p, x, n, y, state, z, agg, init, ptab, levels, st);
-    }
-    if (p.n > kIirTfMaxN || p.S != p.n - 1) return fail(YAGI_ERR_INTERNAL, "iirfilt: bad filter length");
-    if (p.S <= 4) return run_iir<K, false, 4>(p, x, n, y, state, z, agg, init, ptab, levels, st);
-    if (p.S <= 8) return run_iir<K, false, 8>(p, x, n, y, state, z, agg, init, ptab, levels, st);
-    if (p.S <= 16) return run_iir<K, false, 16>(p, x, n, y, state, z, agg, init, ptab, levels, st);
-    return run_iir<K, false, kIirTfMaxN - 1>(p, x, n, y, state, z, agg, init, ptab, levels, st);
+    return dispatch_iir<K, true>(p, PlainArgs<K>{x, y}, n, state, z, agg, init, ptab, levels, st);
+}
+
+template <class K>
+int launch_iir_rate(const IirParams<K> &p, const IirRateIo<K> &io, size_t n, typename K::T *state, typename K::T *z,
+                    void *agg, void *init, const void *ptab, int levels, hipStream_t st) {
+    if (io.M < 2 || io.M > kIirMaxRate) return fail(YAGI_ERR_INTERNAL, "iirmap: bad rate");
+    return dispatch_iir<K, true>(p, io, n, state, z, agg, init, ptab, levels, st);
+}
+
+int launch_iir_hilb(const IirParams<CRCF> &p, const IirHilbIo &io, size_t n, cf32 *state, cf32 *z, void *agg, void *init,
+                    const void *ptab, int levels, hipStream_t st) {
+    if (p.T % 4) return fail(YAGI_ERR_INTERNAL, "iirmap: the chunk length must be a multiple of 4");
+    return dispatch_iir<CRCF, false>(p, io, n, state, z, agg, init, ptab, levels, st);
 }
 
 template int launch_iir<RRRF>(const IirParams<RRRF> &, const float *, size_t, float *, float *, float *, void *, void *,
@@ -414,5 +593,11 @@ template int launch_iir<CRCF>(const IirParams<CRCF> &, const cf32 *, size_t, cf3
                               const void *, int, hipStream_t);
 template int launch_iir<CCCF>(const IirParams<CCCF> &, const cf32 *, size_t, cf32 *, cf32 *, cf32 *, void *, void *,
                               const void *, int, hipStream_t);
+template int launch_iir_rate<RRRF>(const IirParams<RRRF> &, const IirRateIo<RRRF> &, size_t, float *, float *, void *,
+                                   void *, const void *, int, hipStream_t);
+template int launch_iir_rate<CRCF>(const IirParams<CRCF> &, const IirRateIo<CRCF> &, size_t, cf32 *, cf32 *, void *,
+                                   void *, const void *, int, hipStream_t);
+template int launch_iir_rate<CCCF>(const IirParams<CCCF> &, const IirRateIo<CCCF> &, size_t, cf32 *, cf32 *, void *,
+                                   void *, const void *, int, hipStream_t);
 
 }  // namespace yagi

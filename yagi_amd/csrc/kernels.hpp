@@ -259,6 +259,33 @@ template <class K>
 int launch_iir(const IirParams<K> &p, const typename K::T *x, size_t n, typename K::T *y, typename K::T *state,
                typename K::T *z, void *agg, void *init, const void *ptab, int levels, hipStream_t st);
 
+// The mapped forms run the same scan over a virtual stream of n filter steps: an input map in front
+// of phases A and C, an output map behind phase C, phase B unchanged.
+// IirDecim / IirInterp: the sparse side holds sample i at step i M; the other steps read +0.0 (sparse_in) or are not
+// stored (sparse_out).  The dense side is the plain x[gi] / y[gi].
+constexpr uint32_t kIirMaxRate = 65536;
+template <class K>
+struct IirRateIo {
+    const typename K::T *x;
+    typename K::T *y;
+    uint32_t M;
+    int sparse_in, sparse_out;
+};
+template <class K>
+int launch_iir_rate(const IirParams<K> &p, const IirRateIo<K> &io, size_t n, typename K::T *state, typename K::T *z,
+                    void *agg, void *init, const void *ptab, int levels, hipStream_t st);
+// IirHilbertFilter over one crcf filter; k = (phase + gi) & 3.  Plain = cf32 x[gi] / y[gi] (cascade passes in between).
+enum { kHilbInPlain = 0, kHilbInReal = 1, kHilbInCplx = 2, kHilbInEven = 3 };
+enum { kHilbOutPlain = 0, kHilbOutRot2 = 1, kHilbOutProj = 2, kHilbOutEven2 = 3, kHilbOutProj2 = 4 };
+struct IirHilbIo {
+    const void *x;      // float (InReal) or cf32
+    void *y;            // float (OutProj, OutProj2) or cf32
+    uint32_t phase;
+    int imode, omode;
+};
+int launch_iir_hilb(const IirParams<CRCF> &p, const IirHilbIo &io, size_t n, cf32 *state, cf32 *z, void *agg, void *init,
+                    const void *ptab, int levels, hipStream_t st);
+
 // ---- osc_kernels.hip -----------------------------------------------------------------------
 // Osc::mix_block_up / mix_block_down (src/nco/osc.rs) on device buffers: y[j] = x[j] * (cos + i sin)(theta0 + j dtheta),
 // conjugated for `down`; vco selects the table (host.cpp: osc_device_table, 1024 float2 for the NCO, 1024 float4 for
