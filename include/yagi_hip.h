@@ -831,6 +831,55 @@ int yagi_hip_firhilb_decim_execute_block_dev(yagi_hip_firhilb q, const float *x_
 int yagi_hip_firhilb_interp_execute_block_dev(yagi_hip_firhilb q, const yagi_cf32 *x_dev, size_t n, float *y_dev);
 int yagi_hip_firhilb_design(size_t m, float as_, float *hq);
 
+/* ---- Fdelay: src/filter/fdelay.rs:1-137 (fractional delay, 0 <= delay <= nmax) --------------------------------------
+ *   create(nmax, m, npfb)     new() :26-53  a zero parameter is YAGI_ERR_CONFIG; the bank is FirPfbFilter::default(npfb,
+ *                             m): Kaiser, 2 npfb m + 1 taps, cut-off 0.5 / npfb, 60 dB, branch length Ls = h_len div npfb
+ *                             (2m, and 2m + 1 for npfb = 1).  Limits of this build: nmax <= 2^24 (where nmax as f32 is exact), Ls <= 4096.
+ *   create_default(nmax)      new_default() :55-57  m = 8, npfb = 64
+ *   clone / reset             derive(Clone) / reset() :59-65 (delay 0, the reference's w_index = nmax - 1, f_index = 0,
+ *                             both windows zeroed)
+ *   get_delay / set_delay / adjust_delay   :67-101 in f32; a delay outside [0, nmax] (NaN included) or a failed
+ *                             adjust_delay is YAGI_ERR_CONFIG and leaves the object unchanged
+ *   get_nmax / get_m / get_npfb   :103-113
+ *   push / write / execute    :115-128 on the host mirror, no launch
+ *   execute_block             :130-136 on host slices (the shorter of nx, ny), staged through the device
+ *   execute_block_dev         device buffers, asynchronous on the object's stream; x and y overlapping is
+ *                             YAGI_ERR_CONFIG
+ *   execute_track             EXTENSION: one delay per sample, equal to `for i: set_delay(delay[i]); push(x[i]);
+ *                             y[i] = execute()`; afterwards get_delay() is delay[n - 1].  The whole delay array is
+ *                             validated before any state moves (YAGI_ERR_CONFIG, object unchanged).
+ *   execute_track_dev         the same on device buffers.  It cannot validate: each delay is CLAMPED into [0, nmax], and
+ *                             anything that is not >= 0 (NaN included) counts as 0.  The next call that needs the lag on
+ *                             the host (get_delay, adjust_delay, a fixed-delay block call, a per-sample call) waits for
+ *                             the stream and reads the last delay back.
+ * Every output word equals the reference's sequential loop, also where the delay changes between or inside calls.
+ * Device form: fdelay_kernels.hip. */
+#define YAGI_FDELAY_API(K, T)                                                                                   \
+    typedef struct yagi_hip_fdelay_##K##_s *yagi_hip_fdelay_##K;                                                     \
+    int yagi_hip_fdelay_##K##_create(size_t nmax, size_t m, size_t npfb, yagi_hip_fdelay_##K *q);                    \
+    int yagi_hip_fdelay_##K##_create_default(size_t nmax, yagi_hip_fdelay_##K *q);                                   \
+    int yagi_hip_fdelay_##K##_destroy(yagi_hip_fdelay_##K q);                                                        \
+    int yagi_hip_fdelay_##K##_clone(yagi_hip_fdelay_##K q, yagi_hip_fdelay_##K *out);                                \
+    int yagi_hip_fdelay_##K##_set_stream(yagi_hip_fdelay_##K q, yagi_stream_t s);                                    \
+    int yagi_hip_fdelay_##K##_reset(yagi_hip_fdelay_##K q);                                                          \
+    int yagi_hip_fdelay_##K##_get_delay(yagi_hip_fdelay_##K q, float *delay);                                        \
+    int yagi_hip_fdelay_##K##_set_delay(yagi_hip_fdelay_##K q, float delay);                                         \
+    int yagi_hip_fdelay_##K##_adjust_delay(yagi_hip_fdelay_##K q, float delta);                                      \
+    int yagi_hip_fdelay_##K##_get_nmax(yagi_hip_fdelay_##K q, size_t *nmax);                                         \
+    int yagi_hip_fdelay_##K##_get_m(yagi_hip_fdelay_##K q, size_t *m);                                               \
+    int yagi_hip_fdelay_##K##_get_npfb(yagi_hip_fdelay_##K q, size_t *npfb);                                         \
+    int yagi_hip_fdelay_##K##_push(yagi_hip_fdelay_##K q, T x);                                                      \
+    int yagi_hip_fdelay_##K##_write(yagi_hip_fdelay_##K q, const T *x, size_t n);                                    \
+    int yagi_hip_fdelay_##K##_execute(yagi_hip_fdelay_##K q, T *y);                                                  \
+    int yagi_hip_fdelay_##K##_execute_block(yagi_hip_fdelay_##K q, const T *x, size_t nx, T *y, size_t ny);          \
+    int yagi_hip_fdelay_##K##_execute_block_dev(yagi_hip_fdelay_##K q, const T *x_dev, size_t n, T *y_dev);          \
+    int yagi_hip_fdelay_##K##_execute_track(yagi_hip_fdelay_##K q, const float *delay, const T *x, size_t n, T *y);  \
+    int yagi_hip_fdelay_##K##_execute_track_dev(yagi_hip_fdelay_##K q, const float *delay_dev, const T *x_dev,       \
+                                                size_t n, T *y_dev);
+YAGI_FDELAY_API(rrrf, float)
+YAGI_FDELAY_API(crcf, yagi_cf32)
+YAGI_FDELAY_API(cccf, yagi_cf32)
+
 /* ---- IIR design, low-pass second-order sections: src/filter/iir/design/mod.rs:567-717, butter.rs, cheby2.rs --------
  *   yagi_hip_iir_design_lowpass_sos(shape, order, fc, ap, as_, b, a)   iir_design() on its low-pass / SOS branch; b, a
  *                             hold 3 (L + r) floats, L = order / 2, r = order % 2 (the odd section last, b2 = a2 = 0).

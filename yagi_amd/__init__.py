@@ -32,7 +32,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "Fdelay", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -1325,6 +1325,90 @@ class FirHilbertFilter(_Handle):
 
     def c2r_execute_block_dev(self, x_dev, n, y_dev):        # x_dev: n complex64, y_dev: 2n float32
         self._dev("c2r_execute_block_dev", x_dev, n, y_dev)
+
+
+class Fdelay(_FirBase):
+    """Fdelay<T,Coeff> (src/filter/fdelay.rs): fractional delay, 0 <= delay <= nmax, as a whole-sample lag in front of
+    one branch of FirPfbFilter::default(npfb, m).  The per-sample calls run on the host; execute_block and the
+    per-sample-delay execute_track run fdelay_kernels.hip, and every output word equals the reference's sequential loop,
+    also where the delay changes between or inside calls."""
+
+    def __init__(self, kind, nmax, m=8, npfb=64):             # new() :26-53, new_default() :55-57
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_fdelay_{kind}_"
+        hd = C.c_void_p()
+        if (m, npfb) == (8, 64):
+            _check(self._fn("create_default")(nmax, C.byref(hd)))
+        else:
+            _check(self._fn("create")(nmax, m, npfb, C.byref(hd)))
+        self._h = hd
+
+    def set_scale(self, scale):
+        raise ConfigError("Fdelay has no scale (fdelay.rs)")
+
+    def get_scale(self):
+        raise ConfigError("Fdelay has no scale (fdelay.rs)")
+
+    def get_delay(self):                                      # :67-69
+        d = C.c_float()
+        _check(self._fn("get_delay")(self._h, C.byref(d)))
+        return np.float32(d.value)
+
+    def set_delay(self, delay):                               # :71-97
+        _check(self._fn("set_delay")(self._h, float(np.float32(delay))))
+
+    def adjust_delay(self, delta):                            # :99-101
+        _check(self._fn("adjust_delay")(self._h, float(np.float32(delta))))
+
+    def _get(self, name):
+        v = C.c_size_t()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return v.value
+
+    def get_nmax(self):                                       # :103-105
+        return self._get("get_nmax")
+
+    def get_m(self):                                          # :107-109
+        return self._get("get_m")
+
+    def get_npfb(self):                                       # :111-113
+        return self._get("get_npfb")
+
+    def push(self, x):                                        # :115-118
+        _check(self._fn("push")(self._h, _byval(x, self._Tc)))
+
+    def write(self, x):                                       # :120-124
+        x = _arr(x, self.T)
+        _check(self._fn("write")(self._h, _ptr(x), x.size))
+
+    def execute(self):                                        # :126-128
+        y = np.zeros(1, self.T)
+        _check(self._fn("execute")(self._h, _ptr(y)))
+        return y[0]
+
+    def execute_block(self, x, y=None):                       # :130-136
+        x = _arr(x, self.T)
+        y = _out(y, x.size, self.T)
+        _check(self._fn("execute_block")(self._h, _ptr(x), x.size, _ptr(y), y.size))
+        return y
+
+    def execute_block_dev(self, x_dev, n, y_dev):
+        _check(self._fn("execute_block_dev")(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+    def execute_track(self, delay, x, y=None):
+        """extension: one delay per sample, `for i: set_delay(delay[i]); push(x[i]); y[i] = execute()`; a delay outside
+        [0, nmax] anywhere in the array is a ConfigError and leaves the object unchanged"""
+        x = _arr(x, self.T)
+        delay = _arr(delay, np.float32)
+        if delay.size != x.size:
+            raise ConfigError("delay and sample blocks must have equal length")
+        y = _out(y, x.size, self.T)
+        _check(self._fn("execute_track")(self._h, _ptr(delay), _ptr(x), x.size, _ptr(y)))
+        return y
+
+    def execute_track_dev(self, delay_dev, x_dev, n, y_dev):
+        """delay_dev: n float32 on the device, each clamped into [0, nmax] (what is not >= 0 counts as 0)"""
+        _check(self._fn("execute_track_dev")(self._h, _devptr(delay_dev), _devptr(x_dev), n, _devptr(y_dev)))
 
 
 class MsResamp(_FirBase):

@@ -412,3 +412,26 @@ for _n in ("r2c", "c2r", "decim", "interp"):
     _sig(_p + _n + "_execute_block", vp, vp, sz, vp, sz)
     _sig(_p + _n + "_execute_block_dev", vp, vp, sz, vp)
 _sig(_p + "design", sz, f32, vp)
+
+# ---- Fdelay ------------------------------------------------------------------------------------
+for _k, (_T, _Cc) in KIND_TYPES.items():
+    _p = f"yagi_hip_fdelay_{_k}_"
+    _sig(_p + "create", sz, sz, sz, pvp)
+    _sig(_p + "create_default", sz, pvp)
+    _sig(_p + "destroy", vp)
+    _sig(_p + "clone", vp, pvp)
+    _sig(_p + "set_stream", vp, vp)
+    _sig(_p + "reset", vp)
+    _sig(_p + "get_delay", vp, C.POINTER(f32))
+    _sig(_p + "set_delay", vp, f32)
+    _sig(_p + "adjust_delay", vp, f32)
+    _sig(_p + "get_nmax", vp, C.POINTER(sz))
+    _sig(_p + "get_m", vp, C.POINTER(sz))
+    _sig(_p + "get_npfb", vp, C.POINTER(sz))
+    _sig(_p + "push", vp, _T)
+    _sig(_p + "write", vp, vp, sz)
+    _sig(_p + "execute", vp, vp)
+    _sig(_p + "execute_block", vp, vp, sz, vp, sz)
+    _sig(_p + "execute_block_dev", vp, vp, sz, vp)
+    _sig(_p + "execute_track", vp, vp, vp, sz, vp)
+    _sig(_p + "execute_track_dev", vp, vp, vp, sz, vp)

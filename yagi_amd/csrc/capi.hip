@@ -4949,3 +4949,354 @@ int yagi_hip_firhilb_interp_execute_block_dev(yagi_hip_firhilb q, const yagi_cf3
 } catch (...) { return ::yagi::api_exception(); }
 
 }  // extern "C"
+
+// ---- Fdelay (src/filter/fdelay.rs) ---------------------------------------------------------------------------------
+// The state is the reference's, cut to what its outputs depend on: the last nmax input samples (its Window of nmax + 1
+// before the next push), the bank's window of Ls delayed samples, and (delay, w_index, f_index).  The per-sample calls
+// run on a host mirror (host.cpp: host_fir_window_dot, the bank's own sum); block and track calls run
+// fdelay_kernels.hip on the device copy, whose state launch writes the other of two buffers.  The two copies are
+// synchronised lazily (DevWindow's pattern).  After a device track the delay in force is known to the device only:
+// the state launch stores it behind the histories and the host fetches those four bytes when it next needs the lag.
+namespace yagi {
+
+// set_delay :72-97 in f32
+static int fdelay_lag(float d, int nmax, int npfb, int *w, int *f) {
+    if (d < 0.0f) return fail(YAGI_ERR_CONFIG, "delay cannot be negative");
+    if (!(d <= (float)nmax)) return fail(YAGI_ERR_CONFIG, "delay (%g) cannot exceed maximum (%d)", (double)d, nmax);
+    const float offset = (float)nmax - d;
+    const float ip = std::floor(offset);
+    const float frac = offset - ip;
+    int wi = (int)ip, fi = (int)std::round((float)npfb * frac);
+    while (fi >= npfb) { ++wi; fi -= npfb; }
+    if (wi > nmax) return fail(YAGI_ERR_INTERNAL, "window index exceeds maximum");
+    *w = wi;
+    *f = fi;
+    return YAGI_OK;
+}
+
+// the last len values of a stream on the host, oldest first; slack behind them so that a push appends
+template <class T>
+struct FdHist {
+    static constexpr size_t kSlack = 4096;
+    std::vector<T> buf;
+    size_t end = 0, len = 0;
+    void init(size_t n) { len = n; buf.assign(n + kSlack, T{}); end = n; }
+    void zero() { std::fill(buf.begin(), buf.begin() + len, T{}); end = len; }
+    T *data() { return buf.data() + (end - len); }
+    void load(const T *src) { std::memcpy(buf.data(), src, len * sizeof(T)); end = len; }
+    void push(T v) {
+        if (end == buf.size()) {
+            std::memmove(buf.data(), data() + 1, (len - 1) * sizeof(T));
+            end = len - 1;
+        }
+        buf[end++] = v;
+    }
+};
+
+template <class K>
+struct FdelayObj {
+    using T = typename K::T;
+    using C = typename K::C;
+    hipStream_t st = nullptr;
+    int nmax = 0, m = 0, npfb = 0, Ls = 0;
+    float delay = 0.0f;
+    int w_index = 0, f_index = 0;
+    bool lag_on_dev = false;             // a device track ran last: (delay, w, f) are behind the device histories
+    std::vector<C> hb;                   // [npfb][Ls], natural order: hb[i][k] = h[i + k npfb]
+    C scale = one_of<C>();
+    DevBuf taps;                         // [npfb][Ls] against the window oldest first
+    PingPong<> state;                    // [nmax X][Ls V][delay]
+    FdHist<T> hx, hv;                    // host mirror of the two histories
+    Staging ws;
+    DevBuf wd;                           // host track form: the delays on the device
+    Mirror mirror;
+
+    size_t state_bytes() const { return fdelay_state_bytes<T>(nmax, Ls); }
+    size_t lag_offset() const { return ((size_t)nmax + (size_t)Ls) * sizeof(T); }
+    FdelayDims dims() const { return FdelayDims{nmax, Ls, npfb}; }
+
+    int alloc_dev() {
+        std::vector<C> hd(hb.size());
+        for (int i = 0; i < npfb; ++i)
+            for (int k = 0; k < Ls; ++k) hd[(size_t)i * Ls + k] = hb[(size_t)i * Ls + (Ls - 1 - k)];
+        YG_TRY(fill(taps, hd.data(), hd.size() * sizeof(C), st));
+        return state.alloc(state_bytes());
+    }
+    int init(size_t nmax_, size_t m_, size_t npfb_) {                        // new() :26-53
+        if (nmax_ == 0) return fail(YAGI_ERR_CONFIG, "maximum delay must be greater than zero");
+        if (m_ == 0) return fail(YAGI_ERR_CONFIG, "filter semi-length must be greater than zero");
+        if (npfb_ == 0) return fail(YAGI_ERR_CONFIG, "number of filters must be greater than zero");
+        if (nmax_ > (size_t)1 << 24)                                         // set_delay's f32 steps are exact up to here
+            return fail(YAGI_ERR_CONFIG, "maximum delay too large");
+        if (npfb_ > (size_t)1 << 20 || m_ > (size_t)kFdMaxLs || 2 * npfb_ * m_ + 1 > (size_t)1 << 24)
+            return fail(YAGI_ERR_CONFIG, "filter bank too large");
+        const size_t h_len = 2 * npfb_ * m_ + 1;                             // FirPfbFilter::default(npfb, m)
+        if (h_len / npfb_ > (size_t)kFdMaxLs) return fail(YAGI_ERR_CONFIG, "filter bank too large");
+        YG_TRY(require_device());
+        std::vector<float> hf;
+        YG_TRY(design_kaiser(h_len, 0.5f / (float)npfb_, 60.0f, 0.0f, hf));
+        nmax = (int)nmax_;
+        m = (int)m_;
+        npfb = (int)npfb_;
+        Ls = (int)(h_len / npfb_);                                           // firpfb.rs:42: 2m, and 2m + 1 for npfb = 1
+        hb.resize((size_t)npfb * Ls);
+        for (int i = 0; i < npfb; ++i)
+            for (int k = 0; k < Ls; ++k) hb[(size_t)i * Ls + k] = to_c(hf[i + (size_t)k * npfb], (C *)nullptr);
+        YG_TRY(alloc_dev());
+        hx.init((size_t)nmax);
+        hv.init((size_t)Ls);
+        return reset();
+    }
+    int reset() {                                                            // :59-65
+        delay = 0.0f;
+        w_index = nmax - 1;
+        f_index = 0;
+        lag_on_dev = false;
+        hx.zero();
+        hv.zero();
+        YG_HIP(hipMemsetAsync(state.cur(), 0, state_bytes(), st));
+        mirror.in_sync();
+        return YAGI_OK;
+    }
+    // (delay, w, f) after a device track: the four bytes the state launch left behind the histories
+    int sync_lag() {
+        if (!lag_on_dev) return YAGI_OK;
+        float d = 0.0f;
+        YG_TRY(download(&d, state.cur<char>() + lag_offset(), sizeof(float), st));
+        YG_TRY(fdelay_lag(d, nmax, npfb, &w_index, &f_index));
+        delay = d;
+        lag_on_dev = false;
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        YG_TRY(sync_lag());
+        return mirror.need_host([&] {
+            std::vector<T> tmp((size_t)nmax + Ls);
+            YG_TRY(download(tmp.data(), state.cur(), tmp.size() * sizeof(T), st));
+            hx.load(tmp.data());
+            hv.load(tmp.data() + nmax);
+            return (int)YAGI_OK;
+        });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] {
+            std::vector<T> tmp((size_t)nmax + Ls + 1, T{});
+            std::memcpy(tmp.data(), hx.data(), (size_t)nmax * sizeof(T));
+            std::memcpy(tmp.data() + nmax, hv.data(), (size_t)Ls * sizeof(T));
+            std::memcpy(tmp.data() + nmax + Ls, &delay, sizeof(float));
+            return upload(state.cur(), tmp.data(), state_bytes(), st);
+        });
+    }
+    int enter_host() {
+        YG_TRY(ensure_host());
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int set_delay(float d) {                                                 // :71-97
+        int w, f;
+        YG_TRY(fdelay_lag(d, nmax, npfb, &w, &f));
+        w_index = w;
+        f_index = f;
+        delay = d;
+        lag_on_dev = false;
+        return YAGI_OK;
+    }
+    void push(T x) {                                                         // :115-118 (after enter_host)
+        const int D = nmax - w_index;
+        const T v = D == 0 ? x : hx.data()[nmax - D];
+        hx.push(x);
+        hv.push(v);
+    }
+    T execute() {                                                            // :126-128
+        return host_fir_window_dot<T, C>(hv.data(), (size_t)Ls, hb.data() + (size_t)f_index * Ls, scale);
+    }
+    int block_dev(const T *x, size_t n, T *y) {
+        if (n == 0) return YAGI_OK;
+        YG_TRY(sync_lag());
+        YG_TRY(ensure_dev());
+        YG_TRY((launch_fdelay<K>(dims(), taps.template as<C>(), scale, state.template cur<T>(), state.template next<T>(),
+                                 nmax - w_index, f_index, delay, nullptr, x, n, y, st)));
+        state.flip();
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+    int track_dev(const float *d, const T *x, size_t n, T *y) {
+        if (n == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        YG_TRY((launch_fdelay<K>(dims(), taps.template as<C>(), scale, state.template cur<T>(), state.template next<T>(),
+                                 0, 0, delay, d, x, n, y, st)));
+        state.flip();
+        mirror.dev_written();
+        lag_on_dev = true;
+        return YAGI_OK;
+    }
+    int track_host(const float *d, const T *x, size_t n, T *y) {
+        if (n == 0) return YAGI_OK;
+        int w = 0, f = 0;
+        for (size_t i = 0; i < n; ++i) YG_TRY(fdelay_lag(d[i], nmax, npfb, &w, &f));   // all of it, before any state moves
+        YG_TRY(wd.ensure(n * sizeof(float)));
+        YG_TRY(upload(wd.p, d, n * sizeof(float), st));
+        YG_TRY(ws.run(st, x, n, y, n, [&](const T *xd, T *yd) { return track_dev(wd.as<float>(), xd, n, yd); }));
+        w_index = w;
+        f_index = f;
+        delay = d[n - 1];
+        lag_on_dev = false;
+        return YAGI_OK;
+    }
+};
+
+}  // namespace yagi
+
+#define YAGI_FDELAY_IMPL(K, KT, T)                                                                  \
+    struct yagi_hip_fdelay_##K##_s : FdelayObj<KT> {};                                              \
+    extern "C" {                                                                                    \
+    int yagi_hip_fdelay_##K##_create(size_t nmax, size_t m, size_t npfb, yagi_hip_fdelay_##K *q) try { \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        auto o = std::make_unique<yagi_hip_fdelay_##K##_s>();                                       \
+        YG_TRY(o->init(nmax, m, npfb));                                                             \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_create_default(size_t nmax, yagi_hip_fdelay_##K *q) try {             \
+        return yagi_hip_fdelay_##K##_create(nmax, 8, 64, q);                                        \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_destroy(yagi_hip_fdelay_##K q) try {                                  \
+        if (q) (void)hipStreamSynchronize(q->st);                                                   \
+        delete q;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_clone(yagi_hip_fdelay_##K q, yagi_hip_fdelay_##K *out) try {          \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = nullptr;                                                                             \
+        YG_TRY(q->ensure_host());                                                                   \
+        auto o = std::make_unique<yagi_hip_fdelay_##K##_s>();                                       \
+        o->st = q->st;                                                                              \
+        o->nmax = q->nmax;                                                                          \
+        o->m = q->m;                                                                                \
+        o->npfb = q->npfb;                                                                          \
+        o->Ls = q->Ls;                                                                              \
+        o->delay = q->delay;                                                                        \
+        o->w_index = q->w_index;                                                                    \
+        o->f_index = q->f_index;                                                                    \
+        o->hb = q->hb;                                                                              \
+        o->scale = q->scale;                                                                        \
+        YG_TRY(o->alloc_dev());                                                                     \
+        o->hx.init((size_t)o->nmax);                                                                \
+        o->hv.init((size_t)o->Ls);                                                                  \
+        o->hx.load(q->hx.data());                                                                   \
+        o->hv.load(q->hv.data());                                                                   \
+        o->mirror.host_written();                                                                   \
+        *out = o.release();                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_set_stream(yagi_hip_fdelay_##K q, yagi_stream_t s) try {              \
+        CHECK_Q(q);                                                                                 \
+        if (q->st == to_stream(s)) return YAGI_OK;                                                  \
+        YG_HIP(hipStreamSynchronize(q->st));                                                        \
+        q->st = to_stream(s);                                                                       \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_reset(yagi_hip_fdelay_##K q) try {                                    \
+        CHECK_Q(q);                                                                                 \
+        return q->reset();                                                                          \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_get_delay(yagi_hip_fdelay_##K q, float *delay) try {                  \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(delay);                                                                           \
+        YG_TRY(q->sync_lag());                                                                      \
+        *delay = q->delay;                                                                          \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_set_delay(yagi_hip_fdelay_##K q, float delay) try {                   \
+        CHECK_Q(q);                                                                                 \
+        return q->set_delay(delay);                                                                 \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_adjust_delay(yagi_hip_fdelay_##K q, float delta) try {                \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(q->sync_lag());                                                                      \
+        return q->set_delay(q->delay + delta);                                                      \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_get_nmax(yagi_hip_fdelay_##K q, size_t *nmax) try {                   \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(nmax);                                                                            \
+        *nmax = (size_t)q->nmax;                                                                    \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_get_m(yagi_hip_fdelay_##K q, size_t *m) try {                         \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(m);                                                                               \
+        *m = (size_t)q->m;                                                                          \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_get_npfb(yagi_hip_fdelay_##K q, size_t *npfb) try {                   \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(npfb);                                                                            \
+        *npfb = (size_t)q->npfb;                                                                    \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_push(yagi_hip_fdelay_##K q, T x) try {                                \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(q->enter_host());                                                                    \
+        q->push(x);                                                                                 \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_write(yagi_hip_fdelay_##K q, const T *x, size_t n) try {              \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x);                                                                               \
+        YG_TRY(q->enter_host());                                                                    \
+        for (size_t i = 0; i < n; ++i) q->push(x[i]);                                               \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_execute(yagi_hip_fdelay_##K q, T *y) try {                            \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(y);                                                                               \
+        YG_TRY(q->ensure_host());                                                                   \
+        *y = q->execute();                                                                          \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_execute_block(yagi_hip_fdelay_##K q, const T *x, size_t nx, T *y,     \
+                                            size_t ny) try {                                        \
+        CHECK_Q(q);                                                                                 \
+        const size_t n = nx < ny ? nx : ny;       /* zip() stops at the shorter slice (:131) */     \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x);                                                                               \
+        CHECK_PTR(y);                                                                               \
+        return q->ws.run(q->st, x, n, y, n, [&](const T *xd, T *yd) { return q->block_dev(xd, n, yd); }); \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_execute_block_dev(yagi_hip_fdelay_##K q, const T *x_dev, size_t n,    \
+                                                T *y_dev) try {                                     \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x_dev);                                                                           \
+        CHECK_PTR(y_dev);                                                                           \
+        CHECK_NOALIAS(x_dev, n, y_dev, n);                                                          \
+        return q->block_dev(x_dev, n, y_dev);                                                       \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_execute_track(yagi_hip_fdelay_##K q, const float *delay, const T *x,  \
+                                            size_t n, T *y) try {                                   \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(delay);                                                                           \
+        CHECK_PTR(x);                                                                               \
+        CHECK_PTR(y);                                                                               \
+        return q->track_host(delay, x, n, y);                                                       \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_fdelay_##K##_execute_track_dev(yagi_hip_fdelay_##K q, const float *delay_dev,      \
+                                                const T *x_dev, size_t n, T *y_dev) try {           \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(delay_dev);                                                                       \
+        CHECK_PTR(x_dev);                                                                           \
+        CHECK_PTR(y_dev);                                                                           \
+        CHECK_NOALIAS(x_dev, n, y_dev, n);                                                          \
+        CHECK_NOALIAS(delay_dev, n, y_dev, n);                                                      \
+        return q->track_dev(delay_dev, x_dev, n, y_dev);                                            \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    }
+
+YAGI_FDELAY_IMPL(rrrf, RRRF, float)
+YAGI_FDELAY_IMPL(crcf, CRCF, yagi_cf32)
+YAGI_FDELAY_IMPL(cccf, CCCF, yagi_cf32)

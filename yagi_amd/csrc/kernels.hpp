@@ -310,4 +310,22 @@ constexpr int kFirhilbFastM = 512;
 int launch_firhilb(int mode, int m, const float *hq, const float *win, float *win_next, int toggle, const float *x,
                    size_t n, float *y, hipStream_t st);
 
+// ---- fdelay_kernels.hip --------------------------------------------------------------------
+// Fdelay (src/filter/fdelay.rs) block calls on device buffers: n samples in, n out.  state = [the last nmax samples of
+// the input X, oldest first][the last Ls values V pushed into the bank][one float: the delay in force]
+// (fdelay_state_bytes); state_next receives the state the call leaves and must not alias state.  H = the bank's rows
+// [npfb][Ls] against the window oldest first.  delay == nullptr: the fixed lag D and branch f for the whole call
+// (delay0 = the delay they came from, stored for the host); else one delay per sample, clamped into [0, nmax] (what is
+// not >= 0 counts as 0).  x and y must not overlap.
+constexpr int kFdWg = 256;                             // threads per workgroup
+constexpr int kFdTrackTile = 1024;                     // outputs per workgroup of the track form
+constexpr size_t kFdLdsBudget = 64 * 1024;             // the track form stages its nmax-deep input halo in LDS below this
+constexpr int kFdMaxLs = 4096;                         // branch length the LDS tiles are sized for
+struct FdelayDims { int nmax, Ls, npfb; };
+template <class T> size_t fdelay_state_bytes(int nmax, int Ls);
+template <class K>
+int launch_fdelay(const FdelayDims &dm, const typename K::C *H, typename K::C scale, const typename K::T *state,
+                  typename K::T *state_next, int D, int f, float delay0, const float *delay, const typename K::T *x,
+                  size_t n, typename K::T *y, hipStream_t st);
+
 }  // namespace yagi
