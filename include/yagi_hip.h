@@ -20,6 +20,12 @@
  *     (thread-local), like the String each Error variant carries.
  *   - Pointers are HOST pointers unless the function name ends in `_dev`, in which case data
  *     pointers are device (HBM) pointers and the call is asynchronous on the handle's stream.
+ *   - ALIGNMENT AND EXTENT: a device operand needs the alignment of its element type and no more (4 bytes for
+ *     `float` and `uint32_t`, 8 bytes for `yagi_cf32`): a stream cut at an odd sample is a legal operand, and the
+ *     kernels take their 16-byte paths only where the pointer they are given allows it.  A call writes exactly its
+ *     documented output range and nothing else, and reads nothing outside its documented input range whose value
+ *     could reach a result.  Where a call reports its own count (`*nw` of the arbitrary resamplers, capacity
+ *     `ny_cap`), exactly `*nw` elements are written and `[*nw, ny_cap)` is left untouched.
  *   - NO ALIASING: the input and output ranges of a `_dev` block call must not overlap (no in-place
  *     execution): the kernels read tile halos and the carried window from the input while other
  *     workgroups already store the output.  Rust's borrows (`&[T]` in, `&mut [T]` out) make such a
@@ -396,7 +402,8 @@ YAGI_RESAMP2_API(cccf, yagi_cf32, yagi_cf32)
  *   get_num_output  get_num_output(nx) :128-139   closed form, no device work
  *   execute         execute(x, y) :141-154        one sample in; *nw = the outputs written (ny_cap = y's length)
  *   execute_block   execute_block(x, y) :156-165  nx samples in
- *   ny_cap < get_num_output(nx) is YAGI_ERR_RANGE (the reference panics on the slice).  Every path (host per-sample,
+ *   ny_cap < get_num_output(nx) is YAGI_ERR_RANGE (the reference panics on the slice); y[*nw .. ny_cap) is not
+ *   written.  Every path (host per-sample,
  *   host block, device block) leaves the same window and phase, so calls may be mixed.
  * Device form: resamp_kernel -- the control loop only adds integers, so with A_j = p0 + j step output j of a call
  * comes after input A_j >> 24 and uses branch (A_j & 0xFFFFFF) >> (24 - bits): every output is an independent 2m-tap
@@ -806,7 +813,7 @@ int yagi_hip_osc_mix_block_down_dev(yagi_hip_osc q, const yagi_cf32 *x_dev, size
  *                             of input i at y[2i], y[2i + 1]).  Up to 4096 units run on the host, longer slices stage
  *                             through the device; both give the same bits.
  *   *_execute_block_dev       device buffers, n units (decim: n outputs from 2n inputs), asynchronous on the object's
- *                             stream; buffers 4-byte aligned; x and y overlapping is YAGI_ERR_CONFIG.
+ *                             stream; x and y overlapping is YAGI_ERR_CONFIG.
  *   design                    EXTENSION: the 2m taps hq, no device needed.
  * All four modes share the four windows and the toggle, as in the reference, so calls of every mode and form may be
  * mixed on one object.  Every output word equals the reference's sequential loop.  Device form: firhilb_kernels.hip

@@ -73,19 +73,32 @@ fft_n256m_kernel(const float2 *__restrict__ in, float2 *__restrict__ out, const 
 // radix-2 stage X[k] = E[k] + W_8192^k O[k], X[k + 4096] = E[k] - W_8192^k O[k] writes both halves
 // coalesced.  `tw` = W_8192 table followed by the W_4096 table (capi.hip: make_twiddles half_too).
 // ---------------------------------------------------------------------------------------------
-template <int SIGN>
+// ALIGNED is chosen by the launch from `& 15` on the input pointer: device operands promise element (8-byte) alignment
+// only, and transforms are 65536 bytes apart, so the test on the base holds for every workgroup.  It is a template
+// parameter, not a branch in the kernel, because the compiler merges a float4 load with the two float2 loads of the
+// same bytes and the aligned instantiation would lose its 16-byte loads (and a workgroup of occupancy).
+template <int SIGN, bool ALIGNED>
 __global__ void __launch_bounds__(256)
 fft8192_kernel(const float2 *__restrict__ in, float2 *__restrict__ out, const float2 *__restrict__ tw) {
     __shared__ float2 lds[kFft4096LdsFloat2];
     const unsigned t = threadIdx.x;
-    const float4 *src = reinterpret_cast<const float4 *>(in + (size_t)blockIdx.x * 8192);
     const float2 *tw4096 = tw + 8192;
     float2 e[16], o[16];
+    if (ALIGNED) {
+        const float4 *src = reinterpret_cast<const float4 *>(in + (size_t)blockIdx.x * 8192);
 #pragma unroll
-    for (unsigned a = 0; a < 16; ++a) {
-        const float4 q = src[256u * a + t];
-        e[a] = make_float2(q.x, q.y);
-        o[a] = make_float2(q.z, q.w);
+        for (unsigned a = 0; a < 16; ++a) {
+            const float4 q = src[256u * a + t];
+            e[a] = make_float2(q.x, q.y);
+            o[a] = make_float2(q.z, q.w);
+        }
+    } else {
+        const float2 *src2 = in + (size_t)blockIdx.x * 8192;
+#pragma unroll
+        for (unsigned a = 0; a < 16; ++a) {
+            e[a] = src2[2u * (256u * a + t)];
+            o[a] = src2[2u * (256u * a + t) + 1u];
+        }
     }
     fft4096_passes_to_regs<SIGN>(e, lds, tw4096);
     fft4096_passes_to_regs<SIGN>(o, lds, tw4096);
@@ -762,8 +775,14 @@ int launch_fft_batch(const FftPlanDev &p, const cf32 *in, cf32 *out, size_t batc
     if (p.n > kFftMaxLds) return fail(YAGI_ERR_INTERNAL, "fft size %d has no plan resources", p.n);
     if (p.n == 8192) {
         if (batch > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "batch too large");
-        if (p.dir == YAGI_FFT_FORWARD) fft8192_kernel<-1><<<(unsigned)batch, 256, 0, st>>>(fin, fout, tw);
-        else fft8192_kernel<+1><<<(unsigned)batch, 256, 0, st>>>(fin, fout, tw);
+        const bool aligned = (reinterpret_cast<unsigned long long>(fin) & 15ull) == 0;
+        if (p.dir == YAGI_FFT_FORWARD) {
+            if (aligned) fft8192_kernel<-1, true><<<(unsigned)batch, 256, 0, st>>>(fin, fout, tw);
+            else fft8192_kernel<-1, false><<<(unsigned)batch, 256, 0, st>>>(fin, fout, tw);
+        } else {
+            if (aligned) fft8192_kernel<+1, true><<<(unsigned)batch, 256, 0, st>>>(fin, fout, tw);
+            else fft8192_kernel<+1, false><<<(unsigned)batch, 256, 0, st>>>(fin, fout, tw);
+        }
         YG_LAUNCH_CHECK();
         return YAGI_OK;
     }

@@ -289,8 +289,8 @@ int launch_iir_hilb(const IirParams<CRCF> &p, const IirHilbIo &io, size_t n, cf3
 // ---- osc_kernels.hip -----------------------------------------------------------------------
 // Osc::mix_block_up / mix_block_down (src/nco/osc.rs) on device buffers: y[j] = x[j] * (cos + i sin)(theta0 + j dtheta),
 // conjugated for `down`; vco selects the table (host.cpp: osc_device_table, 1024 float2 for the NCO, 1024 float4 for
-// the VCO).  x == y (in place) is allowed; x and y must be 8-byte aligned, 16-byte alignment of both gives 16-byte
-// accesses.
+// the VCO).  x == y (in place) is allowed; x and y need only their element alignment (yagi_hip.h), 16-byte alignment
+// of both gives 16-byte accesses.
 constexpr int kOscWg = 512;        // threads per workgroup
 constexpr int kOscUnroll = 4;      // loads in flight per lane
 constexpr int kOscWgPerCu = 2;     // persistent grid: 2 workgroups per CU
@@ -301,7 +301,7 @@ int launch_osc_mix(int vco, bool down, const void *tab, uint32_t theta0, uint32_
 // FirHilbertFilter (src/filter/fir/firhilb.rs) block calls on device buffers, n units (r2c: n real -> n complex; c2r:
 // n complex -> 2n real; decim: 2n real -> n complex; interp: n complex -> 2n real).  win: the four windows w0..w3 of
 // 2m floats, oldest first; win_next receives the windows the call leaves; toggle is the toggle at the call.  x and y
-// must not overlap and be 4-byte aligned.  m <= kFirhilbFastM takes the LDS-staged sliding form.
+// must not overlap; they need only their element alignment (yagi_hip.h).  m <= kFirhilbFastM takes the LDS-staged sliding form.
 enum { FIRHILB_R2C = 0, FIRHILB_C2R = 1, FIRHILB_DECIM = 2, FIRHILB_INTERP = 3 };
 constexpr int kFirhilbWg = 256;                        // threads per workgroup
 constexpr int kFirhilbR = 8;                           // consecutive pairs per lane
