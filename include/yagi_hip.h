@@ -1056,6 +1056,82 @@ int yagi_hip_iirhilbf_c2r_execute_block_dev(yagi_hip_iirhilbf q, const yagi_cf32
 int yagi_hip_iirhilbf_decim_execute_block_dev(yagi_hip_iirhilbf q, const float *x_dev, size_t n, yagi_cf32 *y_dev);
 int yagi_hip_iirhilbf_interp_execute_block_dev(yagi_hip_iirhilbf q, const yagi_cf32 *x_dev, size_t n, float *y_dev);
 
+/* ---- Modem: src/modem/modem.rs:27-575, src/modem/modem/{psk,dpsk,ask,qam,bpsk,qpsk,ook,arb}.rs ----------------------------
+ * Linear modulation and hard / soft demodulation.  Symbols are one byte each in the block forms (bps <= 8); soft bits
+ * are bytes, bps per symbol, most significant bit first (0 = a certain 0, 255 = a certain 1).
+ *   create(scheme)            Modem::new :151-207 for PSK2..256, DPSK2..256, ASK2..256, QAM4..256, BPSK, QPSK, OOK.
+ *                             APSK*, SQAM32/128, V29, ARB*OPT, ARB64VT/UI and PI4DQPSK are YAGI_ERR_CONFIG: their
+ *                             constellations are constants of the reference's source and are not part of this
+ *                             library.  YAGI_MODEM_ARB and YAGI_MODEM_UNKNOWN are YAGI_ERR_CONFIG (use from_table).
+ *   create_from_table(t, n)   Modem::from_table :209-216 (scheme ARB): n = 2, 4, .. 256 points, balanced to zero mean
+ *                             and scaled to unit energy (arb.rs:76-94); anything else is YAGI_ERR_CONFIG.  The mean, the
+ *                             energy and the division are computed in double and rounded to f32 at the end, where the
+ *                             reference sums in f32: each point is within an ulp of the exact balanced, scaled point
+ *   get_constellation         extension: the M points, map[s] = modulate(s) (DPSK: map[k] = polar(1, k 2 pi / M))
+ *   get_neighbours            extension: the soft demodulator's table, *p entries per symbol (0: the scheme has none),
+ *                             nbr[s * p + i]; nbr may be NULL to ask for p alone, else cap >= M * p.  Built as
+ *                             init_demod_soft_tab :465-511, except that the "empty" mark cannot collide with symbol
+ *                             0 at M = 256 (the reference's `M as u8` does): every list is the p nearest other points
+ *   modulate / demodulate / demodulate_soft / get_demodulator_{sample,phase_error,evm}   :243-283 on the host mirror.
+ *                             modulate of a symbol >= M is YAGI_ERR_RANGE
+ *   modulate_block            n symbols -> n samples.  A symbol >= M anywhere fails the call with YAGI_ERR_RANGE and y
+ *                             is not written (host form: checked on the host; _dev form: checked on the device through
+ *                             a flag that the call waits for and reads back)
+ *   demodulate_block          n samples -> n symbols; xhat (may be NULL) receives the re-modulated decisions (x_hat)
+ *   demodulate_soft_block     n samples -> n symbols and n * bps soft bytes
+ * After a demodulating block call the object's r / x_hat (get_demodulator_*) are those of the block's last sample; DPSK's
+ * phase carries across per-sample and block calls in any mixture.  The _dev forms take device pointers of any byte
+ * alignment for symbols and soft bits, run on the object's stream (demodulation asynchronously), and their operands
+ * must not overlap (YAGI_ERR_CONFIG).  The decisions, soft bits and x_hat equal the reference's f32 arithmetic operation
+ * by operation; Arb's hard decision compares squared distances where the reference compares hypot().
+ * Deviation, DPSK modulation: the reference adds sym 2 pi / M into an f32 phase sample by sample and wraps at 2 pi
+ * (dpsk.rs:55-60), whose rounding drifts with the stream's length.  Here the state is the exact running index
+ * k_n = (k_{n-1} + gray_decode(s_n)) mod M and the output map[k_n]: no drift, and a block form.  The modulator's k and
+ * the demodulator's phase are separate states (the reference shares one field between them).
+ * random_symbol is not provided.  Device form: modem_kernels.hip. */
+typedef enum {
+    YAGI_MODEM_UNKNOWN = 0, YAGI_MODEM_PSK2 = 1, YAGI_MODEM_PSK4 = 2, YAGI_MODEM_PSK8 = 3,
+    YAGI_MODEM_PSK16 = 4, YAGI_MODEM_PSK32 = 5, YAGI_MODEM_PSK64 = 6, YAGI_MODEM_PSK128 = 7,
+    YAGI_MODEM_PSK256 = 8, YAGI_MODEM_DPSK2 = 9, YAGI_MODEM_DPSK4 = 10, YAGI_MODEM_DPSK8 = 11,
+    YAGI_MODEM_DPSK16 = 12, YAGI_MODEM_DPSK32 = 13, YAGI_MODEM_DPSK64 = 14, YAGI_MODEM_DPSK128 = 15,
+    YAGI_MODEM_DPSK256 = 16, YAGI_MODEM_ASK2 = 17, YAGI_MODEM_ASK4 = 18, YAGI_MODEM_ASK8 = 19,
+    YAGI_MODEM_ASK16 = 20, YAGI_MODEM_ASK32 = 21, YAGI_MODEM_ASK64 = 22, YAGI_MODEM_ASK128 = 23,
+    YAGI_MODEM_ASK256 = 24, YAGI_MODEM_QAM4 = 25, YAGI_MODEM_QAM8 = 26, YAGI_MODEM_QAM16 = 27,
+    YAGI_MODEM_QAM32 = 28, YAGI_MODEM_QAM64 = 29, YAGI_MODEM_QAM128 = 30, YAGI_MODEM_QAM256 = 31,
+    YAGI_MODEM_APSK4 = 32, YAGI_MODEM_APSK8 = 33, YAGI_MODEM_APSK16 = 34, YAGI_MODEM_APSK32 = 35,
+    YAGI_MODEM_APSK64 = 36, YAGI_MODEM_APSK128 = 37, YAGI_MODEM_APSK256 = 38, YAGI_MODEM_BPSK = 39,
+    YAGI_MODEM_QPSK = 40, YAGI_MODEM_OOK = 41, YAGI_MODEM_SQAM32 = 42, YAGI_MODEM_SQAM128 = 43,
+    YAGI_MODEM_V29 = 44, YAGI_MODEM_ARB16OPT = 45, YAGI_MODEM_ARB32OPT = 46, YAGI_MODEM_ARB64OPT = 47,
+    YAGI_MODEM_ARB128OPT = 48, YAGI_MODEM_ARB256OPT = 49, YAGI_MODEM_ARB64VT = 50, YAGI_MODEM_ARB64UI = 51,
+    YAGI_MODEM_PI4DQPSK = 52, YAGI_MODEM_ARB = 53
+} yagi_modem_scheme;
+typedef struct yagi_hip_modem_s *yagi_hip_modem;
+int yagi_hip_modem_create(int scheme, yagi_hip_modem *q);
+int yagi_hip_modem_create_from_table(const yagi_cf32 *table, size_t n, yagi_hip_modem *q);
+int yagi_hip_modem_destroy(yagi_hip_modem q);
+int yagi_hip_modem_clone(yagi_hip_modem q, yagi_hip_modem *out);
+int yagi_hip_modem_set_stream(yagi_hip_modem q, yagi_stream_t s);
+int yagi_hip_modem_reset(yagi_hip_modem q);
+int yagi_hip_modem_get_bps(yagi_hip_modem q, size_t *bps);
+int yagi_hip_modem_get_scheme(yagi_hip_modem q, int *scheme);
+int yagi_hip_modem_get_constellation_size(yagi_hip_modem q, size_t *m);
+int yagi_hip_modem_get_constellation(yagi_hip_modem q, yagi_cf32 *map);
+int yagi_hip_modem_get_neighbours(yagi_hip_modem q, uint8_t *nbr, size_t cap, size_t *p);
+int yagi_hip_modem_modulate(yagi_hip_modem q, unsigned sym, yagi_cf32 *y);
+int yagi_hip_modem_demodulate(yagi_hip_modem q, yagi_cf32 x, unsigned *sym);
+int yagi_hip_modem_demodulate_soft(yagi_hip_modem q, yagi_cf32 x, unsigned *sym, uint8_t *soft);
+int yagi_hip_modem_get_demodulator_sample(yagi_hip_modem q, yagi_cf32 *x_hat);
+int yagi_hip_modem_get_demodulator_phase_error(yagi_hip_modem q, float *e);
+int yagi_hip_modem_get_demodulator_evm(yagi_hip_modem q, float *evm);
+int yagi_hip_modem_modulate_block(yagi_hip_modem q, const uint8_t *sym, size_t n, yagi_cf32 *y);
+int yagi_hip_modem_modulate_block_dev(yagi_hip_modem q, const uint8_t *sym_dev, size_t n, yagi_cf32 *y_dev);
+int yagi_hip_modem_demodulate_block(yagi_hip_modem q, const yagi_cf32 *x, size_t n, uint8_t *sym, yagi_cf32 *xhat);
+int yagi_hip_modem_demodulate_block_dev(yagi_hip_modem q, const yagi_cf32 *x_dev, size_t n, uint8_t *sym_dev,
+                                        yagi_cf32 *xhat_dev);
+int yagi_hip_modem_demodulate_soft_block(yagi_hip_modem q, const yagi_cf32 *x, size_t n, uint8_t *sym, uint8_t *soft);
+int yagi_hip_modem_demodulate_soft_block_dev(yagi_hip_modem q, const yagi_cf32 *x_dev, size_t n, uint8_t *sym_dev,
+                                             uint8_t *soft_dev);
+
 /* ---- design helper exposed for hosts that want the taps (kaiser.rs:16-51) ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);
 

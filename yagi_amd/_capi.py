@@ -435,3 +435,27 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
     _sig(_p + "execute_block_dev", vp, vp, sz, vp)
     _sig(_p + "execute_track", vp, vp, vp, sz, vp)
     _sig(_p + "execute_track_dev", vp, vp, vp, sz, vp)
+
+# ---- Modem -------------------------------------------------------------------------------------
+_p = "yagi_hip_modem_"
+_sig(_p + "create", ci, pvp)
+_sig(_p + "create_from_table", vp, sz, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "get_bps", vp, C.POINTER(sz))
+_sig(_p + "get_scheme", vp, C.POINTER(ci))
+_sig(_p + "get_constellation_size", vp, C.POINTER(sz))
+_sig(_p + "get_constellation", vp, vp)
+_sig(_p + "get_neighbours", vp, vp, sz, C.POINTER(sz))
+_sig(_p + "modulate", vp, C.c_uint, C.POINTER(cf32))
+_sig(_p + "demodulate", vp, cf32, C.POINTER(C.c_uint))
+_sig(_p + "demodulate_soft", vp, cf32, C.POINTER(C.c_uint), vp)
+_sig(_p + "get_demodulator_sample", vp, C.POINTER(cf32))
+_sig(_p + "get_demodulator_phase_error", vp, C.POINTER(f32))
+_sig(_p + "get_demodulator_evm", vp, C.POINTER(f32))
+for _n in ("modulate_block", "modulate_block_dev"):
+    _sig(_p + _n, vp, vp, sz, vp)
+for _n in ("demodulate_block", "demodulate_block_dev", "demodulate_soft_block", "demodulate_soft_block_dev"):
+    _sig(_p + _n, vp, vp, sz, vp, vp)

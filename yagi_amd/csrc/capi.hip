@@ -5300,3 +5300,312 @@ struct FdelayObj {
 YAGI_FDELAY_IMPL(rrrf, RRRF, float)
 YAGI_FDELAY_IMPL(crcf, CRCF, yagi_cf32)
 YAGI_FDELAY_IMPL(cccf, CCCF, yagi_cf32)
+
+// ---- Modem (src/modem/modem.rs) ------------------------------------------------------------------------------------
+// Construction, the per-sample arithmetic and the kernels are modem_kernels.hip (the file built with contraction off);
+// this is the object: the tables on both sides, and one ModemState (r, x_hat, DPSK's demodulator phase and modulator
+// index) as a host mirror and a device copy that the kernels rewrite into the other of two buffers.  The two copies
+// are synchronised lazily (Mirror), so per-sample and block calls mix freely.
+struct yagi_hip_modem_s {
+    hipStream_t st = nullptr;
+    int scheme = 0;
+    ModemParams P{};
+    std::vector<cf32> map;
+    std::vector<uint8_t> nbr;
+    ModemState hs{};                      // host mirror
+    DevBuf dmap, dnbr, partials, flag;
+    PingPong<> state;
+    Staging ws;                           // host-pointer block calls: x / symbols in, the first output out
+    DevBuf w2;                            // their second output (xhat, soft bits)
+    Mirror mirror;
+
+    static int kind_of(int scheme, int *kind, int *bps) {
+        if (scheme >= YAGI_MODEM_PSK2 && scheme <= YAGI_MODEM_PSK256) return *kind = MODEM_PSK, *bps = scheme - YAGI_MODEM_PSK2 + 1, YAGI_OK;
+        if (scheme >= YAGI_MODEM_DPSK2 && scheme <= YAGI_MODEM_DPSK256) return *kind = MODEM_DPSK, *bps = scheme - YAGI_MODEM_DPSK2 + 1, YAGI_OK;
+        if (scheme >= YAGI_MODEM_ASK2 && scheme <= YAGI_MODEM_ASK256) return *kind = MODEM_ASK, *bps = scheme - YAGI_MODEM_ASK2 + 1, YAGI_OK;
+        if (scheme >= YAGI_MODEM_QAM4 && scheme <= YAGI_MODEM_QAM256) return *kind = MODEM_QAM, *bps = scheme - YAGI_MODEM_QAM4 + 2, YAGI_OK;
+        if (scheme == YAGI_MODEM_BPSK) return *kind = MODEM_BPSK, *bps = 1, YAGI_OK;
+        if (scheme == YAGI_MODEM_QPSK) return *kind = MODEM_QPSK, *bps = 2, YAGI_OK;
+        if (scheme == YAGI_MODEM_OOK) return *kind = MODEM_OOK, *bps = 1, YAGI_OK;
+        if (scheme == YAGI_MODEM_ARB) return fail(YAGI_ERR_CONFIG, "modem: an arbitrary constellation needs create_from_table");
+        if (scheme > YAGI_MODEM_UNKNOWN && scheme < YAGI_MODEM_ARB)
+            return fail(YAGI_ERR_CONFIG, "modem: scheme %d is not built (its constellation is not part of this library)", scheme);
+        return fail(YAGI_ERR_CONFIG, "modulation scheme not supported");
+    }
+    int alloc_dev() {
+        YG_TRY(fill(dmap, map.data(), map.size() * sizeof(cf32), st));
+        YG_TRY(fill(dnbr, nbr.data(), nbr.size(), st));
+        YG_TRY(flag.alloc(sizeof(int)));
+        return state.alloc(sizeof(ModemState));
+    }
+    int init(int scheme_, int kind, int bps, const cf32 *table) {
+        YG_TRY(modem_design(kind, bps, table, P, map, nbr));
+        YG_TRY(require_device());
+        scheme = scheme_;
+        YG_TRY(alloc_dev());
+        return reset();
+    }
+    int reset() {                                                            // :218-224
+        hs = ModemState{cf32{1.0f, 0.0f}, cf32{1.0f, 0.0f}, 0.0f, 0u};
+        mirror.in_sync();
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] { return download(&hs, state.cur(), sizeof(ModemState), st); });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] { return upload(state.cur(), &hs, sizeof(ModemState), st); });
+    }
+    int enter_host() {
+        YG_TRY(ensure_host());
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int modulate(unsigned sym, cf32 *y) {                                    // :243-253
+        if (sym >= (unsigned)P.M) return fail(YAGI_ERR_RANGE, "input symbol exceeds constellation size");
+        if (P.kind == MODEM_DPSK) {
+            YG_TRY(enter_host());
+            hs.k = modem_host_modulate_dpsk(P, sym, hs.k);
+            *y = hs.r = map[hs.k];
+        } else {
+            *y = map[sym];
+        }
+        return YAGI_OK;
+    }
+    int demodulate(cf32 x, unsigned *sym, uint8_t *soft) {
+        YG_TRY(enter_host());
+        *sym = modem_host_demod(P, map.data(), nbr.data(), x, hs, soft);
+        return YAGI_OK;
+    }
+    int modulate_dev(const uint8_t *sym, size_t n, cf32 *y) {
+        if (n == 0) return YAGI_OK;
+        const bool dpsk = P.kind == MODEM_DPSK;
+        if (dpsk) {
+            YG_TRY(ensure_dev());
+            YG_TRY(partials.ensure(modem_num_partials(n) * sizeof(unsigned)));
+        }
+        YG_TRY(launch_modem_modulate(P, dmap.as<cf32>(), state.cur<ModemState>(), state.next<ModemState>(), sym, n, y,
+                                     partials.as<unsigned>(), flag.as<int>(), st));
+        int bad = 0;
+        YG_TRY(download(&bad, flag.p, sizeof(int), st));
+        if (bad) return fail(YAGI_ERR_RANGE, "input symbol exceeds constellation size");
+        if (dpsk) {
+            state.flip();
+            mirror.dev_written();
+        }
+        return YAGI_OK;
+    }
+    int demodulate_dev(const cf32 *x, size_t n, uint8_t *sym, cf32 *xhat, uint8_t *soft) {
+        if (n == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        YG_TRY(launch_modem_demod(P, dmap.as<cf32>(), dnbr.as<uint8_t>(), state.cur<ModemState>(), state.next<ModemState>(),
+                                  x, n, sym, xhat, soft, st));
+        state.flip();
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+    // host slices: x through the staging pair, the second output through w2
+    int demodulate_host(const cf32 *x, size_t n, uint8_t *sym, cf32 *xhat, uint8_t *soft) {
+        if (n == 0) return YAGI_OK;
+        const size_t b2 = xhat ? n * sizeof(cf32) : soft ? n * (size_t)P.bps : 0;
+        YG_TRY(ws.put(st, x, n));
+        YG_TRY(ws.y.ensure(n));
+        if (b2) YG_TRY(w2.ensure(b2));
+        YG_TRY(demodulate_dev(ws.x.as<cf32>(), n, ws.y.as<uint8_t>(), xhat ? w2.as<cf32>() : nullptr,
+                              soft ? w2.as<uint8_t>() : nullptr));
+        YG_TRY(download(sym, ws.y.p, n, st));
+        if (b2) YG_TRY(download(xhat ? (void *)xhat : (void *)soft, w2.p, b2, st));
+        return YAGI_OK;
+    }
+};
+
+#define MODEM_CREATE(...)                                                                           \
+    CHECK_PTR(q);                                                                                   \
+    *q = nullptr;                                                                                   \
+    auto o = std::make_unique<yagi_hip_modem_s>();                                                  \
+    YG_TRY(o->init(__VA_ARGS__));                                                                   \
+    *q = o.release();                                                                               \
+    return YAGI_OK
+
+extern "C" {
+
+int yagi_hip_modem_create(int scheme, yagi_hip_modem *q) try {
+    int kind = 0, bps = 0;
+    YG_TRY(yagi_hip_modem_s::kind_of(scheme, &kind, &bps));
+    MODEM_CREATE(scheme, kind, bps, nullptr);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_create_from_table(const yagi_cf32 *table, size_t n, yagi_hip_modem *q) try {
+    CHECK_PTR(table);
+    int bps = 0;
+    while (bps < 8 && ((size_t)1 << bps) < n) ++bps;
+    if (n < 2 || ((size_t)1 << bps) != n) return fail(YAGI_ERR_CONFIG, "table size must be a power of 2 in 2..256");
+    MODEM_CREATE(YAGI_MODEM_ARB, MODEM_ARB, bps, table);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_destroy(yagi_hip_modem q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_clone(yagi_hip_modem q, yagi_hip_modem *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_modem_s>();
+    o->st = q->st;
+    o->scheme = q->scheme;
+    o->P = q->P;
+    o->map = q->map;
+    o->nbr = q->nbr;
+    o->hs = q->hs;
+    YG_TRY(o->alloc_dev());
+    o->mirror.host_written();
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_set_stream(yagi_hip_modem q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_reset(yagi_hip_modem q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_get_bps(yagi_hip_modem q, size_t *bps) try {
+    CHECK_Q(q);
+    CHECK_PTR(bps);
+    *bps = (size_t)q->P.bps;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_get_scheme(yagi_hip_modem q, int *scheme) try {
+    CHECK_Q(q);
+    CHECK_PTR(scheme);
+    *scheme = q->scheme;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_get_constellation_size(yagi_hip_modem q, size_t *m) try {
+    CHECK_Q(q);
+    CHECK_PTR(m);
+    *m = (size_t)q->P.M;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_get_constellation(yagi_hip_modem q, yagi_cf32 *map) try {
+    CHECK_Q(q);
+    CHECK_PTR(map);
+    std::memcpy(map, q->map.data(), q->map.size() * sizeof(cf32));
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_get_neighbours(yagi_hip_modem q, uint8_t *nbr, size_t cap, size_t *p) try {
+    CHECK_Q(q);
+    CHECK_PTR(p);
+    *p = (size_t)q->P.p;
+    if (!nbr) return YAGI_OK;
+    if (cap < q->nbr.size()) return fail(YAGI_ERR_RANGE, "neighbour table needs %zu bytes", q->nbr.size());
+    if (!q->nbr.empty()) std::memcpy(nbr, q->nbr.data(), q->nbr.size());
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_modulate(yagi_hip_modem q, unsigned sym, yagi_cf32 *y) try {
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    return q->modulate(sym, y);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_demodulate(yagi_hip_modem q, yagi_cf32 x, unsigned *sym) try {
+    CHECK_Q(q);
+    CHECK_PTR(sym);
+    return q->demodulate(x, sym, nullptr);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_demodulate_soft(yagi_hip_modem q, yagi_cf32 x, unsigned *sym, uint8_t *soft) try {
+    CHECK_Q(q);
+    CHECK_PTR(sym);
+    CHECK_PTR(soft);
+    return q->demodulate(x, sym, soft);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_get_demodulator_sample(yagi_hip_modem q, yagi_cf32 *x_hat) try {             // :273-275
+    CHECK_Q(q);
+    CHECK_PTR(x_hat);
+    YG_TRY(q->ensure_host());
+    *x_hat = q->hs.x_hat;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_get_demodulator_phase_error(yagi_hip_modem q, float *e) try {                // :277-279
+    CHECK_Q(q);
+    CHECK_PTR(e);
+    YG_TRY(q->ensure_host());
+    const std::complex<float> r(q->hs.r.re, q->hs.r.im), xh(q->hs.x_hat.re, -q->hs.x_hat.im);
+    *e = r.real() * xh.imag() + r.imag() * xh.real();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_get_demodulator_evm(yagi_hip_modem q, float *evm) try {                      // :281-283
+    CHECK_Q(q);
+    CHECK_PTR(evm);
+    YG_TRY(q->ensure_host());
+    *evm = std::hypot(q->hs.x_hat.re - q->hs.r.re, q->hs.x_hat.im - q->hs.r.im);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_modulate_block(yagi_hip_modem q, const uint8_t *sym, size_t n, yagi_cf32 *y) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(sym);
+    CHECK_PTR(y);
+    for (size_t i = 0; i < n; ++i)
+        if ((int)sym[i] >= q->P.M) return fail(YAGI_ERR_RANGE, "input symbol %zu exceeds constellation size", i);
+    YG_TRY(q->ws.put(q->st, sym, n));
+    YG_TRY(q->ws.y.ensure(n * sizeof(cf32)));
+    YG_TRY(q->modulate_dev(q->ws.x.as<uint8_t>(), n, q->ws.y.as<cf32>()));
+    return download(y, q->ws.y.p, n * sizeof(cf32), q->st);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_modulate_block_dev(yagi_hip_modem q, const uint8_t *sym_dev, size_t n, yagi_cf32 *y_dev) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(sym_dev);
+    CHECK_PTR(y_dev);
+    CHECK_NOALIAS(sym_dev, n, y_dev, n);
+    return q->modulate_dev(sym_dev, n, y_dev);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_demodulate_block(yagi_hip_modem q, const yagi_cf32 *x, size_t n, uint8_t *sym, yagi_cf32 *xhat) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(sym);
+    return q->demodulate_host(x, n, sym, xhat, nullptr);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_demodulate_block_dev(yagi_hip_modem q, const yagi_cf32 *x_dev, size_t n, uint8_t *sym_dev,
+                                        yagi_cf32 *xhat_dev) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x_dev);
+    CHECK_PTR(sym_dev);
+    CHECK_NOALIAS(x_dev, n, sym_dev, n);
+    if (xhat_dev) {
+        CHECK_NOALIAS(x_dev, n, xhat_dev, n);
+        CHECK_NOALIAS(sym_dev, n, xhat_dev, n);
+    }
+    return q->demodulate_dev(x_dev, n, sym_dev, xhat_dev, nullptr);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_demodulate_soft_block(yagi_hip_modem q, const yagi_cf32 *x, size_t n, uint8_t *sym, uint8_t *soft) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(sym);
+    CHECK_PTR(soft);
+    return q->demodulate_host(x, n, sym, nullptr, soft);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_modem_demodulate_soft_block_dev(yagi_hip_modem q, const yagi_cf32 *x_dev, size_t n, uint8_t *sym_dev,
+                                             uint8_t *soft_dev) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x_dev);
+    CHECK_PTR(sym_dev);
+    CHECK_PTR(soft_dev);
+    const size_t ns = n * (size_t)q->P.bps;
+    CHECK_NOALIAS(x_dev, n, sym_dev, n);
+    CHECK_NOALIAS(x_dev, n, soft_dev, ns);
+    CHECK_NOALIAS(sym_dev, n, soft_dev, ns);
+    return q->demodulate_dev(x_dev, n, sym_dev, nullptr, soft_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"

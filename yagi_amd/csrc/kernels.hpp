@@ -2,6 +2,8 @@
 // Every launcher is asynchronous on `st`, performs no allocation and no host synchronisation
 // (so a caller may capture it into a hipGraph), and returns a yagi_status.
 #pragma once
+#include <cstdint>
+
 #include "common.hpp"
 
 namespace yagi {
@@ -327,5 +329,36 @@ template <class K>
 int launch_fdelay(const FdelayDims &dm, const typename K::C *H, typename K::C scale, const typename K::T *state,
                   typename K::T *state_next, int D, int f, float delay0, const float *delay, const typename K::T *x,
                   size_t n, typename K::T *y, hipStream_t st);
+
+// ---- modem_kernels.hip ---------------------------------------------------------------------
+// Modem (src/modem/modem.rs): block modulation and hard / soft demodulation on device buffers, and the same arithmetic
+// on the host (this file is the one built with contraction off).  map = M points, nbr = M * p neighbour indices
+// (p = 0: none).  state / state_next: the object's ModemState on the device; a demodulating call and a DPSK modulation
+// read one and write the other (the caller flips), any other modulation leaves both untouched.
+enum { MODEM_PSK = 0, MODEM_DPSK, MODEM_ASK, MODEM_QAM, MODEM_BPSK, MODEM_QPSK, MODEM_OOK, MODEM_ARB };
+constexpr int kModemWg = 256;                          // threads per workgroup
+constexpr int kModemModTile = 4096;                    // symbols per workgroup of the modulating kernels
+constexpr int kModemDemodTile = 2048;                  // samples per workgroup of the demodulating kernels
+struct ModemParams {
+    int kind, bps, M, p;
+    float ref[8];                                      // reference[] of the linear-array schemes
+    float d_phi, gamma;                                // PSK / DPSK half spacing offset; Arb's soft-bit gain
+};
+struct ModemState {
+    cf32 r, x_hat;                                     // the last demodulated sample and its decision
+    float phi;                                         // DPSK demodulator: the last sample's phase
+    unsigned k;                                        // DPSK modulator: the running index (yagi_hip.h)
+};
+int modem_design(int kind, int bps, const cf32 *table, ModemParams &P, std::vector<cf32> &map, std::vector<uint8_t> &nbr);
+unsigned modem_host_demod(const ModemParams &P, const cf32 *map, const uint8_t *nbr, cf32 x, ModemState &s, uint8_t *soft);
+unsigned modem_host_modulate_dpsk(const ModemParams &P, unsigned sym, unsigned k);
+size_t modem_num_partials(size_t n);                   // words of `partials` a modulating call of n symbols needs
+// soft != nullptr: the soft form (n * bps bytes); xhat may be null.  x, sym, xhat, soft must not overlap.
+int launch_modem_demod(const ModemParams &P, const cf32 *map, const uint8_t *nbr, const ModemState *state,
+                       ModemState *state_next, const cf32 *x, size_t n, uint8_t *sym, cf32 *xhat, uint8_t *soft,
+                       hipStream_t st);
+// *flag is left non-zero when a symbol >= M was found; then y and state_next are not written.
+int launch_modem_modulate(const ModemParams &P, const cf32 *map, const ModemState *state, ModemState *state_next,
+                          const uint8_t *sym, size_t n, cf32 *y, unsigned *partials, int *flag, hipStream_t st);
 
 }  // namespace yagi
