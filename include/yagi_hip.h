@@ -1132,6 +1132,53 @@ int yagi_hip_modem_demodulate_soft_block(yagi_hip_modem q, const yagi_cf32 *x, s
 int yagi_hip_modem_demodulate_soft_block_dev(yagi_hip_modem q, const yagi_cf32 *x_dev, size_t n, uint8_t *sym_dev,
                                              uint8_t *soft_dev);
 
+/* ---- OrdFilt: src/filter/ordfilt.rs:1-66 (order-statistic / median filter over the last n samples) ------------------
+ * Only f32 (rrrf): Complex has no PartialOrd, so the reference's generic T admits nothing else.
+ *   create(n, k)              new() :16-30  n == 0 and k >= n are YAGI_ERR_CONFIG with the reference's messages;
+ *                             n > YAGI_ORDFILT_NMAX is YAGI_ERR_CONFIG too (the device form's LDS tile, a limit of this
+ *                             build; the message names it)
+ *   create_medfilt(m)         new_medfilt() :32-34 = create(2m + 1, m)
+ *   clone / reset             derive(Clone) / reset() :36-38 (the window of n samples is all +0.0)
+ *   get_n / get_k             the window length and the 0-based ascending rank
+ *   push / write              :40-46 on the host mirror, no launch
+ *   execute / execute_one     :48-58 on the host mirror, no launch: a stable sort of a copy of the window (oldest
+ *                             first) under the order below, element k
+ *   execute_block             :60-65 on host slices (n samples in, n out), staged through the device
+ *   execute_block_dev         device buffers, asynchronous on the object's stream.  x_dev and y_dev MUST NOT OVERLAP:
+ *                             a workgroup reads the n - 1 samples in front of its tile while another stores there;
+ *                             overlapping ranges are YAGI_ERR_CONFIG.  n = 0 samples is a no-op.
+ * Every output is a copy of one input sample (or of the +0.0 the window starts with), and equals the reference's
+ * sequential loop bit for bit: -0.0 and +0.0 compare equal and the stable sort keeps the older one first, so which zero
+ * comes out depends on its place in the window, here as there.
+ * THE ONE DEVIATION, NaN.  The reference sorts under partial_cmp(..).unwrap_or(Equal), which is no total order once a NaN
+ * is in the window: Rust's sort may then return any order, or panic.  This build compares a monotone u32 key of the
+ * bits: -0.0 is folded onto +0.0, then negative floats are bit-inverted and non-negative ones get the top bit set.
+ * For windows without NaN that is partial_cmp exactly.  A NaN with the sign bit clear sorts above +inf, one with it set
+ * below -inf (among themselves by payload), and equal keys keep their age order.  Every window then has exactly one
+ * sample of rank k whatever the input.
+ *   set_kernel(choice)        which kernel the block calls run: 0 auto, 1 the LDS form (any n), 2 the register-resident
+ *                             form (2 <= n <= YAGI_ORDFILT_REG_NMAX, else YAGI_ERR_CONFIG).  The forms give the same bits.
+ * Device forms: ordfilt_kernels.hip; a workgroup computes YAGI_ORDFILT_TILE outputs. */
+#define YAGI_ORDFILT_NMAX 1025
+#define YAGI_ORDFILT_TILE 4096
+#define YAGI_ORDFILT_REG_NMAX 9
+typedef struct yagi_hip_ordfilt_rrrf_s *yagi_hip_ordfilt_rrrf;
+int yagi_hip_ordfilt_rrrf_create(size_t n, size_t k, yagi_hip_ordfilt_rrrf *q);
+int yagi_hip_ordfilt_rrrf_create_medfilt(size_t m, yagi_hip_ordfilt_rrrf *q);
+int yagi_hip_ordfilt_rrrf_destroy(yagi_hip_ordfilt_rrrf q);
+int yagi_hip_ordfilt_rrrf_clone(yagi_hip_ordfilt_rrrf q, yagi_hip_ordfilt_rrrf *out);
+int yagi_hip_ordfilt_rrrf_set_stream(yagi_hip_ordfilt_rrrf q, yagi_stream_t s);
+int yagi_hip_ordfilt_rrrf_reset(yagi_hip_ordfilt_rrrf q);
+int yagi_hip_ordfilt_rrrf_set_kernel(yagi_hip_ordfilt_rrrf q, int choice);
+int yagi_hip_ordfilt_rrrf_get_n(yagi_hip_ordfilt_rrrf q, size_t *n);
+int yagi_hip_ordfilt_rrrf_get_k(yagi_hip_ordfilt_rrrf q, size_t *k);
+int yagi_hip_ordfilt_rrrf_push(yagi_hip_ordfilt_rrrf q, float x);
+int yagi_hip_ordfilt_rrrf_write(yagi_hip_ordfilt_rrrf q, const float *x, size_t n);
+int yagi_hip_ordfilt_rrrf_execute(yagi_hip_ordfilt_rrrf q, float *y);
+int yagi_hip_ordfilt_rrrf_execute_one(yagi_hip_ordfilt_rrrf q, float x, float *y);
+int yagi_hip_ordfilt_rrrf_execute_block(yagi_hip_ordfilt_rrrf q, const float *x, size_t n, float *y);
+int yagi_hip_ordfilt_rrrf_execute_block_dev(yagi_hip_ordfilt_rrrf q, const float *x_dev, size_t n, float *y_dev);
+
 /* ---- design helper exposed for hosts that want the taps (kaiser.rs:16-51) ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);
 

@@ -33,7 +33,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "Fdelay", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -1410,6 +1410,86 @@ class Fdelay(_FirBase):
     def execute_track_dev(self, delay_dev, x_dev, n, y_dev):
         """delay_dev: n float32 on the device, each clamped into [0, nmax] (what is not >= 0 counts as 0)"""
         _check(self._fn("execute_track_dev")(self._h, _devptr(delay_dev), _devptr(x_dev), n, _devptr(y_dev)))
+
+
+ORDFILT_NMAX = 1025      # YAGI_ORDFILT_NMAX: the longest window of OrdFilt
+ORDFILT_TILE = 4096      # YAGI_ORDFILT_TILE: outputs per workgroup of ordfilt_kernels.hip
+ORDFILT_REG_NMAX = 9     # YAGI_ORDFILT_REG_NMAX: the longest window of the register-resident kernel form
+
+
+class OrdFilt(_Handle):
+    """OrdFilt<f32> (src/filter/ordfilt.rs): the sample of rank k (0-based, ascending) among the last n, the median for
+    OrdFilt.medfilt(m).  The per-sample calls run on the host; execute_block runs ordfilt_kernels.hip, and every output
+    word equals the reference's sequential loop (stable sort, so the older of -0.0 / +0.0 comes first).  NaN, which the
+    reference leaves unspecified, sorts beyond the infinity of its sign (yagi_hip.h).  n <= ORDFILT_NMAX."""
+    _prefix = "yagi_hip_ordfilt_rrrf_"
+
+    def __init__(self, n, k):                                 # new() :16-30
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_ordfilt_rrrf_create(n, k, C.byref(hd)))
+        self._h = hd
+
+    @classmethod
+    def medfilt(cls, m):                                      # new_medfilt() :32-34
+        new = object.__new__(cls)
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_ordfilt_rrrf_create_medfilt(m, C.byref(hd)))
+        new._h = hd
+        return new
+
+    def clone(self):                                          # derive(Clone)
+        new = object.__new__(type(self))
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_ordfilt_rrrf_clone(self._h, C.byref(hd)))
+        new._h = hd
+        return new
+
+    def reset(self):                                          # :36-38
+        _check(lib.yagi_hip_ordfilt_rrrf_reset(self._h))
+
+    def set_kernel(self, choice):
+        """0 auto, 1 the LDS form, 2 the register-resident form (2 <= n <= ORDFILT_REG_NMAX); the same bits either way"""
+        _check(lib.yagi_hip_ordfilt_rrrf_set_kernel(self._h, choice))
+
+    def _get(self, name):
+        v = C.c_size_t()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return v.value
+
+    @property
+    def n(self):
+        return self._get("get_n")
+
+    @property
+    def k(self):
+        return self._get("get_k")
+
+    def push(self, x):                                        # :40-42
+        _check(lib.yagi_hip_ordfilt_rrrf_push(self._h, float(np.float32(x))))
+
+    def write(self, x):                                       # :44-46
+        x = _arr(x, np.float32)
+        _check(lib.yagi_hip_ordfilt_rrrf_write(self._h, _ptr(x), x.size))
+
+    def execute(self):                                        # :48-53
+        y = C.c_float()
+        _check(lib.yagi_hip_ordfilt_rrrf_execute(self._h, C.byref(y)))
+        return np.float32(y.value)
+
+    def execute_one(self, x):                                 # :55-58
+        y = C.c_float()
+        _check(lib.yagi_hip_ordfilt_rrrf_execute_one(self._h, float(np.float32(x)), C.byref(y)))
+        return np.float32(y.value)
+
+    def execute_block(self, x, y=None):                       # :60-65
+        x = _arr(x, np.float32)
+        y = _out(y, x.size, np.float32)
+        _check(lib.yagi_hip_ordfilt_rrrf_execute_block(self._h, _ptr(x), x.size, _ptr(y)))
+        return y
+
+    def execute_block_devptr(self, x_dev, n, y_dev):
+        """x_dev, y_dev: n float32 on the device, not overlapping (ConfigError); asynchronous on the object's stream"""
+        _check(lib.yagi_hip_ordfilt_rrrf_execute_block_dev(self._h, _devptr(x_dev), n, _devptr(y_dev)))
 
 
 class ModulationScheme(enum.IntEnum):

@@ -436,6 +436,24 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
     _sig(_p + "execute_track", vp, vp, vp, sz, vp)
     _sig(_p + "execute_track_dev", vp, vp, vp, sz, vp)
 
+# ---- OrdFilt -----------------------------------------------------------------------------------
+_p = "yagi_hip_ordfilt_rrrf_"
+_sig(_p + "create", sz, sz, pvp)
+_sig(_p + "create_medfilt", sz, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "set_kernel", vp, ci)
+_sig(_p + "get_n", vp, C.POINTER(sz))
+_sig(_p + "get_k", vp, C.POINTER(sz))
+_sig(_p + "push", vp, f32)
+_sig(_p + "write", vp, vp, sz)
+_sig(_p + "execute", vp, C.POINTER(f32))
+_sig(_p + "execute_one", vp, f32, C.POINTER(f32))
+_sig(_p + "execute_block", vp, vp, sz, vp)
+_sig(_p + "execute_block_dev", vp, vp, sz, vp)
+
 # ---- Modem -------------------------------------------------------------------------------------
 _p = "yagi_hip_modem_"
 _sig(_p + "create", ci, pvp)

@@ -5609,3 +5609,180 @@ int yagi_hip_modem_demodulate_soft_block_dev(yagi_hip_modem q, const yagi_cf32 *
 } catch (...) { return ::yagi::api_exception(); }
 
 }  // extern "C"
+
+// ---- OrdFilt (src/filter/ordfilt.rs) -------------------------------------------------------------------------------
+// The state is the reference's Window: the last n samples, oldest first.  The per-sample calls run on a host mirror
+// (ordfilt_host_select: a stable sort of a copy under the key order); block calls run ordfilt_kernels.hip on the device
+// copy, whose launch writes the window it leaves into the other of two buffers.  The two copies are synchronised lazily
+// (Mirror).  The kernel needs only the newest n - 1 samples; the device keeps all n so that an execute() right after a
+// block call sees the reference's window.
+struct yagi_hip_ordfilt_rrrf_s {
+    hipStream_t st = nullptr;
+    int n = 0, k = 0;
+    int form = yagi::ORDFILT_AUTO;                        // set_kernel
+    yagi::FdHist<float> win;                              // host mirror
+    yagi::PingPong<> hist;                                // device copy, n floats
+    yagi::Staging ws;
+    yagi::Mirror mirror;
+    std::vector<std::pair<unsigned, unsigned>> tmp;       // execute()'s sorted copy
+
+    size_t bytes() const { return (size_t)n * sizeof(float); }
+    int init(size_t n_, size_t k_) {                                         // new() :16-30
+        if (n_ == 0) return yagi::fail(YAGI_ERR_CONFIG, "filter length must be greater than zero");
+        if (k_ >= n_) return yagi::fail(YAGI_ERR_CONFIG, "filter index must be in [0,n-1]");
+        if (n_ > (size_t)YAGI_ORDFILT_NMAX)
+            return yagi::fail(YAGI_ERR_CONFIG, "filter length %zu exceeds YAGI_ORDFILT_NMAX = %d", n_, YAGI_ORDFILT_NMAX);
+        YG_TRY(yagi::require_device());
+        n = (int)n_;
+        k = (int)k_;
+        YG_TRY(hist.alloc(bytes()));
+        win.init((size_t)n);
+        return reset();
+    }
+    int reset() {                                                            // :36-38
+        win.zero();
+        YG_HIP(hipMemsetAsync(hist.cur(), 0, bytes(), st));
+        mirror.in_sync();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] {
+            std::vector<float> t((size_t)n);
+            YG_TRY(yagi::download(t.data(), hist.cur(), bytes(), st));
+            win.load(t.data());
+            return (int)YAGI_OK;
+        });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] { return yagi::upload(hist.cur(), win.data(), bytes(), st); });
+    }
+    int enter_host() {
+        YG_TRY(ensure_host());
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    float execute() { return yagi::ordfilt_host_select(win.data(), n, k, tmp); }        // :48-53 (after ensure_host)
+    int block_dev(const float *x, size_t nb, float *y) {
+        if (nb == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        YG_TRY(yagi::launch_ordfilt(n, k, form, hist.cur<float>(), hist.next<float>(), x, nb, y, st));
+        hist.flip();
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+};
+
+extern "C" {
+
+int yagi_hip_ordfilt_rrrf_create(size_t n, size_t k, yagi_hip_ordfilt_rrrf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    auto o = std::make_unique<yagi_hip_ordfilt_rrrf_s>();
+    YG_TRY(o->init(n, k));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_create_medfilt(size_t m, yagi_hip_ordfilt_rrrf *q) try {    // new_medfilt() :32-34
+    if (m > (size_t)YAGI_ORDFILT_NMAX) return yagi_hip_ordfilt_rrrf_create((size_t)YAGI_ORDFILT_NMAX + 1, 0, q);
+    return yagi_hip_ordfilt_rrrf_create(2 * m + 1, m, q);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_destroy(yagi_hip_ordfilt_rrrf q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_clone(yagi_hip_ordfilt_rrrf q, yagi_hip_ordfilt_rrrf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_ordfilt_rrrf_s>();
+    o->st = q->st;
+    o->n = q->n;
+    o->k = q->k;
+    o->form = q->form;
+    YG_TRY(o->hist.alloc(o->bytes()));
+    o->win.init((size_t)o->n);
+    o->win.load(q->win.data());
+    o->mirror.host_written();
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_set_stream(yagi_hip_ordfilt_rrrf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+// which kernel the block calls run: 0 auto, 1 the LDS form, 2 the register form (2 <= n <= YAGI_ORDFILT_REG_NMAX)
+int yagi_hip_ordfilt_rrrf_set_kernel(yagi_hip_ordfilt_rrrf q, int choice) try {
+    CHECK_Q(q);
+    if (choice < yagi::ORDFILT_AUTO || choice > yagi::ORDFILT_REG) return fail(YAGI_ERR_CONFIG, "unknown kernel choice %d", choice);
+    if (choice == yagi::ORDFILT_REG && (q->n < 2 || q->n > YAGI_ORDFILT_REG_NMAX))
+        return fail(YAGI_ERR_CONFIG, "the register form needs 2 <= n <= %d", YAGI_ORDFILT_REG_NMAX);
+    q->form = choice;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_reset(yagi_hip_ordfilt_rrrf q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_get_n(yagi_hip_ordfilt_rrrf q, size_t *n) try {
+    CHECK_Q(q);
+    CHECK_PTR(n);
+    *n = (size_t)q->n;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_get_k(yagi_hip_ordfilt_rrrf q, size_t *k) try {
+    CHECK_Q(q);
+    CHECK_PTR(k);
+    *k = (size_t)q->k;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_push(yagi_hip_ordfilt_rrrf q, float x) try {               // :40-42
+    CHECK_Q(q);
+    YG_TRY(q->enter_host());
+    q->win.push(x);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_write(yagi_hip_ordfilt_rrrf q, const float *x, size_t n) try {   // :44-46
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    YG_TRY(q->enter_host());
+    for (size_t i = 0; i < n; ++i) q->win.push(x[i]);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_execute(yagi_hip_ordfilt_rrrf q, float *y) try {            // :48-53
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    YG_TRY(q->ensure_host());
+    *y = q->execute();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_execute_one(yagi_hip_ordfilt_rrrf q, float x, float *y) try {    // :55-58
+    CHECK_Q(q);
+    CHECK_PTR(y);
+    YG_TRY(q->enter_host());
+    q->win.push(x);
+    *y = q->execute();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_execute_block(yagi_hip_ordfilt_rrrf q, const float *x, size_t n, float *y) try {   // :60-65
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    return q->ws.run(q->st, x, n, y, n, [&](const float *xd, float *yd) { return q->block_dev(xd, n, yd); });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_ordfilt_rrrf_execute_block_dev(yagi_hip_ordfilt_rrrf q, const float *x_dev, size_t n, float *y_dev) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x_dev);
+    CHECK_PTR(y_dev);
+    CHECK_NOALIAS(x_dev, n, y_dev, n);
+    return q->block_dev(x_dev, n, y_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"

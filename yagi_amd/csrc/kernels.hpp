@@ -3,6 +3,7 @@
 // (so a caller may capture it into a hipGraph), and returns a yagi_status.
 #pragma once
 #include <cstdint>
+#include <utility>
 
 #include "common.hpp"
 
@@ -360,5 +361,29 @@ int launch_modem_demod(const ModemParams &P, const cf32 *map, const uint8_t *nbr
 // *flag is left non-zero when a symbol >= M was found; then y and state_next are not written.
 int launch_modem_modulate(const ModemParams &P, const cf32 *map, const ModemState *state, ModemState *state_next,
                           const uint8_t *sym, size_t n, cf32 *y, unsigned *partials, int *flag, hipStream_t st);
+
+// ---- ordfilt_kernels.hip -------------------------------------------------------------------
+// OrdFilt (src/filter/ordfilt.rs) block calls on device buffers: nb samples in, nb out, y[i] = the sample of rank k
+// (0-based, ascending, ties by age) among the n samples that end at x[i].  hist = the n samples before x[0], oldest
+// first (the reference's Window); hist_next receives the window the call leaves and must not alias hist.  x and y must
+// not overlap.  The order is ordfilt_key's (yagi_hip.h: partial_cmp where that is defined, NaN by sign beyond +-inf).
+constexpr int kOrdfiltWg = 256;                        // threads per workgroup
+constexpr int kOrdfiltTile = YAGI_ORDFILT_TILE;        // outputs per workgroup
+constexpr int kOrdfiltNmax = YAGI_ORDFILT_NMAX;        // longest window the LDS tile is sized for
+// LDS of the kernel: keys of a tile and its halo, the tile's outputs, one "-0.0" bit per staged sample
+constexpr size_t kOrdfiltLdsBytes = (size_t)(kOrdfiltTile + kOrdfiltNmax - 1) * 4 + (size_t)kOrdfiltTile * 4 +
+                                    (size_t)(kOrdfiltTile + kOrdfiltNmax - 1) / 8;
+static_assert(kOrdfiltLdsBytes <= 64 * 1024, "the tile must fit a workgroup's LDS");
+// The register-resident form exists for 2 <= n <= kOrdfiltRegNmax; form AUTO takes it up to kOrdfiltRegCrossover.
+enum { ORDFILT_AUTO = 0, ORDFILT_LDS = 1, ORDFILT_REG = 2 };
+constexpr int kOrdfiltRegNmax = YAGI_ORDFILT_REG_NMAX;
+constexpr int kOrdfiltRegCrossover = 9;                // DESIGN.md section 4, profiles/r10_kbench_ordfilt.txt
+static_assert(kOrdfiltRegCrossover <= kOrdfiltRegNmax, "AUTO may only pick a form that exists");
+// LDS of the register form: the tile's rows of 16 samples padded to 20 words, and one row more for the last halo
+constexpr size_t kOrdfiltRegLdsBytes = (size_t)(kOrdfiltWg + 1) * (kOrdfiltTile / kOrdfiltWg + 4) * 4;
+int launch_ordfilt(int n, int k, int form, const float *hist, float *hist_next, const float *x, size_t nb, float *y,
+                   hipStream_t st);
+// element k of the window (n samples, oldest first) after a stable sort under the same order; tmp is scratch
+float ordfilt_host_select(const float *win, int n, int k, std::vector<std::pair<unsigned, unsigned>> &tmp);
 
 }  // namespace yagi
