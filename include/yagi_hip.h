@@ -519,9 +519,22 @@ YAGI_IIRFILT_API(cccf, yagi_cf32, yagi_cf32)
  * (fir_kernels.hip: register-window kernel for blocks >= 512 samples, interleaved-output kernel below; both add
  * the taps in the reference's order and never touch a tap past h_len, so a NaN poisons exactly h_len outputs),
  * 4 = overlap-save fast convolution (<= 2049 taps; stream_kernels.hip).
- * crcf also: 2 = hand-scheduled register-sliding direct form (<= 1024 taps; the crcf auto choice), 3 = MFMA
- * Toeplitz direct form (<= 256 taps); these two multiply zero-padded taps (a NaN's footprint is rounded up to
- * 32 taps).
+ * crcf also: 2 = hand-scheduled register-sliding direct form (<= 1024 taps; the crcf auto choice from 1024 samples
+ * on), 3 = MFMA Toeplitz direct form (<= 256 taps; the crcf auto choice from 2^16 samples on).
+ * Non-finite input (NaN, +-Inf at sample s; every set below is asserted exactly by tests/test_gpu_nonfinite.py, the
+ * table is in DESIGN.md section 6):
+ *   1 (and auto for rrrf / cccf, crcf below 1024 samples): outputs s .. s + h_len - 1, the reference's window.
+ *   2: s .. s + Lp - 1, Lp = h_len rounded up to a multiple of 32 -- the kernel multiplies the zero-padded taps.
+ *   3: the same with Lp = 64, 128 or 256 (the tap class of h_len).  No output before s: the Toeplitz operand holds
+ *      zeros, not gaps, where a row's window does not reach, so a wave that finds a non-finite sample in its span
+ *      runs the products with it zeroed and adds its terms to the outputs whose window holds it (stream_kernels.hip).
+ *   2 and 3 within one call only: the state carried to the next call is the reference's h_len samples, and a call the
+ *      auto choice sends to another kernel (e.g. a short call after a long one) has that kernel's footprint.
+ *   4: whole overlap-save blocks.  Block k of a call makes outputs [kV, kV + V) of the call from the samples
+ *      [kV - P0, kV + V), V = 4096 - (h_len - 1) rounded down to a multiple of 16 (rrrf: 32), P0 = 4096 - V; every
+ *      block whose samples hold s is non-finite throughout; rrrf transforms blocks 2w and 2w + 1 together, so they are
+ *      poisoned together.  FftFilt with h_len <= 2049 is this kernel over the nblocks * n samples of the call.
+ * Outside these sets every output equals the clean stream's bit for bit, and reset() clears the window.
  * The direct forms evaluate the reference's sums (exact on integer-valued data); the fast convolution agrees
  * with them to f32 rounding (rel. L2 <= 2e-6 against the f64 truth), like the reference's own FftFilt, and is
  * 2.5x (rrrf, crcf; 256 taps) to 5x (cccf, 256 taps) faster on long blocks, a tie for short filters (63 taps). */
@@ -595,6 +608,10 @@ int yagi_hip_fft_describe(yagi_hip_fft plan, yagi_hip_fft_info *info);
  *   push / write    one transform every `delay` samples    :237-259  (write = the batched device form)
  *   get_psd_mag / get_psd   fft-shifted linear / dB        :292-316  (like the reference, the linear scale
  *                                                                   factor is 0 unless alpha == -1)
+ *   Non-finite input: a sample inside a transform's window (the window_len samples that end at a multiple of
+ *   `delay`) poisons every bin of the PSD until clear() / reset(); one that no window covers (delay > window_len)
+ *   changes nothing.  As in the reference, max(psd, 1e-12) drops a NaN operand: a NaN bin reads as the floor
+ *   1e-12 * scale, an infinite one as +Inf (tests/test_gpu_nonfinite.py).
  *   estimate_psd    one-shot                               :319-330
  * wtype uses the reference's WindowType discriminants (math/windows.rs:7-18). */
 #define YAGI_WINDOW_HAMMING 1
@@ -651,7 +668,11 @@ int yagi_hip_firfft_crcf_reset(yagi_hip_firfft_crcf q);
  *   3 = fast convolution (overlap-save kernel, then batched FFT; <= 2049 taps),
  *   4 = frequency-domain filter, one launch: FFT{h}.FFT{frame} + FFT{frame-boundary correction} (<= 257 taps).
  * All variants carry the same filter state and agree to f32 rounding (rel. L2 <= 1e-5 per frame against the
- * f64 truth); only 1 and 2 evaluate the FIR sums themselves. */
+ * f64 truth); only 1 and 2 evaluate the FIR sums themselves.
+ * Non-finite input at sample s: a frame is non-finite throughout or untouched.  0 and 4: the frame holding s, and the
+ * next one if s is among its last h_len - 1 samples (the reference's frames).  1, 2, 3 and nfft != 4096: the frames
+ * holding an output of the footprint of FirFilter kernel 2, 3, 4 (set_kernel above); never a frame before the one
+ * holding s.  tests/test_gpu_nonfinite.py::test_firfftstream_4096_which_frames, DESIGN.md section 6. */
 int yagi_hip_firfft_crcf_set_variant(yagi_hip_firfft_crcf q, int variant);
 int yagi_hip_firfft_crcf_execute(yagi_hip_firfft_crcf q, const yagi_cf32 *x, size_t nframes,
                                  yagi_cf32 *spectra);
@@ -685,6 +706,12 @@ int yagi_hip_firfft_crcf_join(yagi_hip_firfft_crcf q);
  *   firpfbch2 analyzer (2x oversampled): M even, branch length 2*m, h[0 .. 2*M*m); one step =
  *             M/2 inputs -> M outputs, alternating half rotation, y = IDFT_M(X)/M.
  *             create_kaiser(M, m, as_): h = kaiser(2*M*m+1, 1/M, as_) * M / sum(h).
+ * Non-finite input in frame / step f: the reference window is frames f .. f+p-1 (firpfbch2: steps f .. f+4m-1), every
+ * channel of them.  Calls of >= 64 frames / steps with M a power of two in 8 .. 256 (analyzers also M 512, 1024 with
+ * p <= 8) run kernels built for P = 4 / 8 / 16 taps per branch (firpfbch2 analyzer: 2 / 4 / 8 / 16) with zero taps behind
+ * the p real ones: f .. f+P-1, steps f .. f+2P-1; the firpfbch2 synthesizer a ring of 8 (m <= 2) or 16 lags:
+ * f .. f+7 / f+15.  Within the call; the carried history is the reference's.  Other shapes keep the reference window.
+ * tests/test_gpu_nonfinite.py::test_firpfbch, test_firpfbch2; DESIGN.md section 6.
  * Output layout [frame][channel].  The `_shard_dev` form computes only the sub-bands
  * k = rank + nranks*q (q < M/nranks) into yshard[step][q] so an 8-GPU node can all-gather them
  * (RCCL) -- see INTEGRATION.md; `assemble_dev` permutes the gathered [rank][step][q] slabs into

@@ -771,7 +771,8 @@ class Spgram:
     def get_psd_mag(self):
         scale = np.float32(1.0 / max(1, self.num_transforms)) if self.accumulate else np.float32(0.0)
         k = (np.arange(self.nfft) + self.nfft // 2) % self.nfft
-        return (np.maximum(self.psd[k], self.PSD_MIN) * scale).astype(np.float32)
+        # f32::max (spgram.rs:302) returns the other operand when one is NaN: np.fmax, not np.maximum
+        return (np.fmax(self.psd[k], self.PSD_MIN) * scale).astype(np.float32)
 
     def get_psd(self):
         with np.errstate(divide="ignore"):

@@ -214,8 +214,62 @@ __device__ __forceinline__ void load_apack(float (&a)[NS], const float *__restri
     for (int s = 0; s < NS; ++s) a[s] = apack[s * 64 + lane];
 }
 
+// ---- non-finite samples ------------------------------------------------------------------------------------------
+// The Toeplitz operand holds zeros, not gaps, where a row's window does not reach: the 16 outputs of a row tile share
+// the Lp + 16 columns R - (Lp-1) .. R + 16, so a NaN / Inf sample would reach outputs BEFORE it through 0 * NaN.  A wave
+// therefore looks through the span of its task first (one pass over LDS, a wave vote, no barrier).  With only finite
+// samples -- every tile of ordinary data -- the task runs exactly as before.  Otherwise the products run with the
+// non-finite B operands replaced by zero, which leaves every output whose own Lp-tap window is finite with the bits it
+// has on a finite stream (a zero tap times a finite sample adds nothing either way), and mfma_repair adds the terms
+// tap x sample of the non-finite samples to the outputs whose window s-(Lp-1) .. s holds them: NaN or +-Inf as the
+// plain sum gives.  The footprint of a sample at s is then s .. s + Lp - 1, as in the sliding kernel with Lp = Lm.
+// PAD2: the span layout of the persistent kernel (pad2) instead of the 17/16 rows (padded).
+__device__ __forceinline__ bool mfma_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+template <bool PAD2> __device__ __forceinline__ int mfma_slot(int i) { return PAD2 ? i + 2 * (i >> 6) : i + (i >> 4); }
+
+// does the task at T0 (512 outputs: span entries T0 .. T0 + 512 + Lp - 1) read a non-finite sample?  wave-uniform
+template <bool PAD2>
+__device__ __forceinline__ bool mfma_task_poisoned(const float2 *__restrict__ xs, int T0, int Lp) {
+    const int lane = threadIdx.x & 63;
+    bool bad = false;
+#pragma unroll 4
+    for (int i = lane; i < 512 + Lp; i += 64) {
+        const float2 v = xs[mfma_slot<PAD2>(T0 + i)];
+        bad = bad || mfma_nonfinite(v.x) || mfma_nonfinite(v.y);
+    }
+    return __any(bad) != 0;
+}
+
+// after the sanitised products: acc[tt][r] += sum over the non-finite samples of the output's window of tap * sample.
+// Output o (tile-relative) reads span entries o .. o + Lp - 1, entry o + d with tap h[Lp-1-d] = T[15][15 + d] of apack.
+template <bool PAD2>
+__device__ __forceinline__ void mfma_repair(f32x4 (&acc)[4], const float *__restrict__ xsf,
+                                            const float *__restrict__ apack, int T0, int Lp) {
+    const int lane = threadIdx.x & 63;
+    const int k = lane >> 4, j = lane & 15, seg = j >> 1, c = j & 1;
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int o = T0 + 64 * seg + 16 * tt + 4 * k + r;
+            asm volatile("" ::: "memory");                     // one output at a time: nothing hoisted across the 16
+            float pv = 0.f;
+            bool any = false;
+#pragma nounroll
+            for (int d = 0; d < Lp; ++d) {
+                const float v = xsf[2 * mfma_slot<PAD2>(o + d) + c];
+                if (mfma_nonfinite(v)) {
+                    const int u = 15 + d;
+                    pv = fmaf(apack[(u >> 2) * 64 + 15 + 16 * (u & 3)], v, pv);
+                    any = true;
+                }
+            }
+            if (any) acc[tt][r] += pv;
+        }
+}
+
 // acc[tt][r] = sum_k h[k] X[T0 + 64*seg + 16*tt + 4*(lane>>4) + r - k].c   (seg = (lane&15)>>1, c = lane&1)
-template <int NS>
+template <int NS, bool SAN = false>
 __device__ __forceinline__ void fir_task_mfma(f32x4 (&acc)[4], const float (&a)[NS],
                                               const float *__restrict__ xsf, int T0) {
     const int lane = threadIdx.x & 63;
@@ -233,7 +287,8 @@ __device__ __forceinline__ void fir_task_mfma(f32x4 (&acc)[4], const float (&a)[
     for (int i = 0; i < PF; ++i) bq[i] = p[2 * (4 * i + (i >> 2))];
 #pragma unroll
     for (int sp = 0; sp < NS + 12; ++sp) {
-        const float b = bq[sp % PF];
+        float b = bq[sp % PF];
+        if (SAN && mfma_nonfinite(b)) b = 0.f;
         if (sp + PF < NS + 12) {
             bq[sp % PF] = p[2 * (4 * (sp + PF) + ((sp + PF) >> 2))];
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);       // 1 DS read
@@ -322,8 +377,15 @@ fir_crcf_mfma_kernel(const float2 *__restrict__ win, const float2 *__restrict__ 
         __syncthreads();
         f32x4 acc[NT][4];
 #pragma unroll
-        for (int t = 0; t < NT; ++t)
-            fir_task_mfma<NS>(acc[t], a, reinterpret_cast<const float *>(xs), 512 * (wave + NW * t));
+        for (int t = 0; t < NT; ++t) {
+            const int T0 = 512 * (wave + NW * t);
+            if (!mfma_task_poisoned<false>(xs, T0, Lp)) {
+                fir_task_mfma<NS>(acc[t], a, reinterpret_cast<const float *>(xs), T0);
+            } else {                             // rare: a NaN / Inf sample in the task's span (see mfma_repair)
+                fir_task_mfma<NS, true>(acc[t], a, reinterpret_cast<const float *>(xs), T0);
+                mfma_repair<false>(acc[t], reinterpret_cast<const float *>(xs), apack, T0, Lp);
+            }
+        }
         if (!FUSED && direct) {                  // plain filter, 16-byte aligned output: registers -> HBM
             const long long nvalid = (long long)(n_units - o0);
 #pragma unroll
@@ -396,7 +458,7 @@ static int launch_mfma_t(const cf32 *win, const cf32 *x, const float *apack, int
 constexpr int kMTile = 2048;
 __host__ __device__ __forceinline__ constexpr int pad2(int i) { return i + 2 * (i >> 6); }
 
-template <int NS>
+template <int NS, bool SAN = false>
 __device__ __forceinline__ void fir_task_mfma2(f32x4 (&acc)[4], const float (&a)[NS],
                                                const float *__restrict__ xsf, int T0) {
     const int lane = threadIdx.x & 63;
@@ -411,7 +473,8 @@ __device__ __forceinline__ void fir_task_mfma2(f32x4 (&acc)[4], const float (&a)
     for (int i = 0; i < PF; ++i) bq[i] = p[2 * (4 * i + 2 * (i >> 4))];
 #pragma unroll
     for (int sp = 0; sp < NS + 12; ++sp) {
-        const float b = bq[sp % PF];
+        float b = bq[sp % PF];
+        if (SAN && mfma_nonfinite(b)) b = 0.f;
         if (sp + PF < NS + 12) {
             bq[sp % PF] = p[2 * (4 * (sp + PF) + 2 * ((sp + PF) >> 4))];
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);       // 1 DS read
@@ -484,7 +547,12 @@ fir_crcf_mfma_stream_kernel(const float2 *__restrict__ win, const float2 *__rest
             }
         }
         f32x4 acc[4];
-        fir_task_mfma2<NS>(acc, a, reinterpret_cast<const float *>(xs + cur * BUF), 512 * wave);
+        if (!mfma_task_poisoned<true>(xs + cur * BUF, 512 * wave, Lp)) {
+            fir_task_mfma2<NS>(acc, a, reinterpret_cast<const float *>(xs + cur * BUF), 512 * wave);
+        } else {                                       // rare: a NaN / Inf sample in the task's span (see mfma_repair)
+            fir_task_mfma2<NS, true>(acc, a, reinterpret_cast<const float *>(xs + cur * BUF), 512 * wave);
+            mfma_repair<true>(acc, reinterpret_cast<const float *>(xs + cur * BUF), apack, 512 * wave, Lp);
+        }
         __syncthreads();                               // the DMA has landed (vmcnt) and every wave is done with `cur`
         store_task_direct(acc, out, (size_t)tile * kMTile, (long long)(n - (size_t)tile * kMTile), 512 * wave, scale);
         if (!has_next) break;
