@@ -1206,6 +1206,102 @@ int yagi_hip_ordfilt_rrrf_execute_one(yagi_hip_ordfilt_rrrf q, float x, float *y
 int yagi_hip_ordfilt_rrrf_execute_block(yagi_hip_ordfilt_rrrf q, const float *x, size_t n, float *y);
 int yagi_hip_ordfilt_rrrf_execute_block_dev(yagi_hip_ordfilt_rrrf q, const float *x_dev, size_t n, float *y_dev);
 
+/* ---- MSequence: src/sequence/msequence.rs:41-164 (maximal-length shift-register sequence) --------------------------
+ * The state is one 32-bit word on the host; no call reads anything back from the device.
+ *   create(m, g, a)           new() :55-67  m outside 2..31 is YAGI_ERR_CONFIG; n = 2^m - 1.  The state starts as a,
+ *                             NOT masked: like the reference, the first advance() forms its bit from the whole of the
+ *                             state and the whole of g and only then masks with n.  set_state does not mask either.
+ *   create_genpoly(g)         :69-77  m = the bit length of g (below 2, or 32: YAGI_ERR_CONFIG), a = 1
+ *   create_default(m)         LEFT OUT: its table of generator polynomials exists only as constants of the reference's
+ *                             source, which this library does not copy.  Callers pass g.
+ *   clone / reset             derive(Clone) / :133-135 (the state becomes a again)
+ *   advance / generate_symbol :116-131 on the host.  generate_symbol(bps), MSB first; bps > 32 is YAGI_ERR_CONFIG
+ *   set_state / get_state / get_genpoly / get_genpoly_length / get_length      :138-145
+ *   measure_period            :147-158, a plain host loop (the state advances by the period it returns)
+ *   skip(k)                   NOT IN THE REFERENCE: the state becomes what k calls of advance() would leave, in
+ *                             O(log k) on the host.  advance() is linear over GF(2) on the state word, so the object
+ *                             keeps T^(2^b), b = 0 .. 63, as 32 column words each and applies those of k's set bits.
+ *   generate_bits_block       n calls of advance(), one bit per byte, on a host slice (staged through the device)
+ *   generate_symbols_block    sym[i] = generate_symbol(bps), bps in 1..8 (else YAGI_ERR_CONFIG): one symbol per byte,
+ *                             the layout yagi_hip_modem_modulate_block_dev reads
+ *   *_block_dev               the same into device buffers, asynchronous on the object's stream.  n = 0 is a no-op.
+ * After a block the host state is advanced by n * bps with the same matrices, so scalar and block calls interleave
+ * freely and stay on the reference's stream of bits.
+ * Device form: sequence_kernels.hip; a workgroup generates YAGI_MSEQUENCE_TILE symbols. */
+#define YAGI_MSEQUENCE_TILE 8192
+typedef struct yagi_hip_msequence_s *yagi_hip_msequence;
+int yagi_hip_msequence_create(unsigned m, unsigned g, unsigned a, yagi_hip_msequence *q);
+int yagi_hip_msequence_create_genpoly(unsigned g, yagi_hip_msequence *q);
+int yagi_hip_msequence_destroy(yagi_hip_msequence q);
+int yagi_hip_msequence_clone(yagi_hip_msequence q, yagi_hip_msequence *out);
+int yagi_hip_msequence_set_stream(yagi_hip_msequence q, yagi_stream_t s);
+int yagi_hip_msequence_reset(yagi_hip_msequence q);
+int yagi_hip_msequence_advance(yagi_hip_msequence q, unsigned *bit);
+int yagi_hip_msequence_generate_symbol(yagi_hip_msequence q, unsigned bps, unsigned *sym);
+int yagi_hip_msequence_set_state(yagi_hip_msequence q, unsigned a);
+int yagi_hip_msequence_get_state(yagi_hip_msequence q, unsigned *state);
+int yagi_hip_msequence_get_genpoly(yagi_hip_msequence q, unsigned *g);
+int yagi_hip_msequence_get_genpoly_length(yagi_hip_msequence q, unsigned *m);
+int yagi_hip_msequence_get_length(yagi_hip_msequence q, unsigned *n);
+int yagi_hip_msequence_measure_period(yagi_hip_msequence q, unsigned *period);
+int yagi_hip_msequence_skip(yagi_hip_msequence q, uint64_t k);
+int yagi_hip_msequence_generate_bits_block(yagi_hip_msequence q, size_t n, uint8_t *bits);
+int yagi_hip_msequence_generate_bits_block_dev(yagi_hip_msequence q, size_t n, uint8_t *bits_dev);
+int yagi_hip_msequence_generate_symbols_block(yagi_hip_msequence q, unsigned bps, size_t n, uint8_t *sym);
+int yagi_hip_msequence_generate_symbols_block_dev(yagi_hip_msequence q, unsigned bps, size_t n, uint8_t *sym_dev);
+
+/* ---- BSequence: src/sequence/bsequence.rs:8-195 (binary sequence, sliding bit correlator) --------------------------
+ * The state is the reference's word array: (num_bits + 31) / 32 words, word 0 the oldest bits and masked to the
+ * num_bits_msb bits it holds, the newest bit at bit 0 of the last word.  Scalar calls run on a host mirror, the block
+ * call on a device copy; the two are synchronised lazily.
+ *   create(num_bits)          new() :16-30  0 is YAGI_ERR_CONFIG (the reference would index an empty vector), and so
+ *                             is more than YAGI_BSEQUENCE_NMAX = 8192 bits: a limit of this library (the device
+ *                             form's LDS tile), which covers the 8191 bits of m = 13
+ *   create_from_msequence(ms) :81-88  ms.get_length() bits, ms advanced by as many
+ *   create_ccodes(qa, qb)     :34-79  complementary codes by doubling; unequal lengths, fewer than 8 bits and a
+ *                             length that is no multiple of 8 are YAGI_ERR_CONFIG
+ *   clone / reset             derive(Clone) / :90-92
+ *   init(v, nbytes)           :95-108  pushes num_bits bits of v, MSB first; nbytes < (num_bits + 7) / 8 is
+ *                             YAGI_ERR_CONFIG (the reference would index past the slice)
+ *   push / circshift          :115-134
+ *   correlate(a, b, rxy)      :137-150  a is the receiver: unequal WORD counts (not bit counts) are YAGI_ERR_CONFIG, and
+ *                             the correction term 32 - num_bits_msb is a's
+ *   add / mul (a, b, out)     :153-176  word-wise xor / and into out; unequal word counts are YAGI_ERR_CONFIG
+ *   accumulate / index / get_length    :179-194  index(i >= num_bits) is YAGI_ERR_CONFIG
+ *   push_correlate_block(q, ref, sym, n, bps, rxy)   means exactly
+ *                                 for i in 0..n:
+ *                                     for j in bps-1 down to 0:  q.push((sym[i] >> j) & 1)
+ *                                     rxy[i] = ref.correlate(q)
+ *                             bps in 1..8 (else YAGI_ERR_CONFIG); bits of sym[i] above bps are ignored; ref is read as it
+ *                             stands when the call is made; ref and q must have equal word counts and ref == q is
+ *                             rejected (both YAGI_ERR_CONFIG).  rxy may be NULL: the call then only pushes.
+ *   push_correlate_block_dev  the same on device buffers (sym_dev: n bytes, rxy_dev: n int32, not overlapping),
+ *                             asynchronous on q's stream.  n = 0 is a no-op.
+ * Device form: sequence_kernels.hip; a workgroup computes YAGI_BSEQUENCE_TILE outputs. */
+#define YAGI_BSEQUENCE_TILE 4096
+#define YAGI_BSEQUENCE_NMAX 8192
+typedef struct yagi_hip_bsequence_s *yagi_hip_bsequence;
+int yagi_hip_bsequence_create(size_t num_bits, yagi_hip_bsequence *q);
+int yagi_hip_bsequence_create_from_msequence(yagi_hip_msequence ms, yagi_hip_bsequence *q);
+int yagi_hip_bsequence_create_ccodes(yagi_hip_bsequence qa, yagi_hip_bsequence qb);
+int yagi_hip_bsequence_destroy(yagi_hip_bsequence q);
+int yagi_hip_bsequence_clone(yagi_hip_bsequence q, yagi_hip_bsequence *out);
+int yagi_hip_bsequence_set_stream(yagi_hip_bsequence q, yagi_stream_t s);
+int yagi_hip_bsequence_reset(yagi_hip_bsequence q);
+int yagi_hip_bsequence_init(yagi_hip_bsequence q, const uint8_t *v, size_t nbytes);
+int yagi_hip_bsequence_push(yagi_hip_bsequence q, unsigned bit);
+int yagi_hip_bsequence_circshift(yagi_hip_bsequence q);
+int yagi_hip_bsequence_correlate(yagi_hip_bsequence a, yagi_hip_bsequence b, int32_t *rxy);
+int yagi_hip_bsequence_add(yagi_hip_bsequence a, yagi_hip_bsequence b, yagi_hip_bsequence out);
+int yagi_hip_bsequence_mul(yagi_hip_bsequence a, yagi_hip_bsequence b, yagi_hip_bsequence out);
+int yagi_hip_bsequence_accumulate(yagi_hip_bsequence q, unsigned *count);
+int yagi_hip_bsequence_index(yagi_hip_bsequence q, size_t i, unsigned *bit);
+int yagi_hip_bsequence_get_length(yagi_hip_bsequence q, size_t *num_bits);
+int yagi_hip_bsequence_push_correlate_block(yagi_hip_bsequence q, yagi_hip_bsequence ref, const uint8_t *sym, size_t n,
+                                            unsigned bps, int32_t *rxy);
+int yagi_hip_bsequence_push_correlate_block_dev(yagi_hip_bsequence q, yagi_hip_bsequence ref, const uint8_t *sym_dev,
+                                                size_t n, unsigned bps, int32_t *rxy_dev);
+
 /* ---- design helper exposed for hosts that want the taps (kaiser.rs:16-51) ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);
 

@@ -86,6 +86,9 @@ int main() {
     run<16, 14, true>("read 8 : write 7, nt stores (bps 6)", x, y, units);
     run<8, 9, false>("read 8 : write 9 (bps 8)", x, y, units);
     run<8, 9, true>("read 8 : write 9, nt stores (bps 8)", x, y, units);
+    // BSequence's correlator (tools/kb_sequence.py): one symbol byte in, one int32 out; MSequence's generator is write only
+    run<4, 16, false>("read 1 : write 4 (bsequence correlator)", x, y, units);
+    run<4, 16, true>("read 1 : write 4, nt stores", x, y, units);
     run<16, 0, false>("read only", x, y, units);
     run<0, 16, false>("write only", x, y, units);
     run<0, 16, true>("write only, nt stores", x, y, units);

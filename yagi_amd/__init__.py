@@ -15,6 +15,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     Resamp / MsResamp          src/filter/resampler/resamp.rs:8-165, msresamp.rs:10-176
     Osc, OscScheme             src/nco/osc.rs:13-201 (nco.rs, vco.rs)
     Modem, ModulationScheme    src/modem/modem.rs:27-575 (the linear schemes and from_table)
+    MSequence / BSequence      src/sequence/msequence.rs:41-164, bsequence.rs:8-195
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -33,7 +34,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -1490,6 +1491,179 @@ class OrdFilt(_Handle):
     def execute_block_devptr(self, x_dev, n, y_dev):
         """x_dev, y_dev: n float32 on the device, not overlapping (ConfigError); asynchronous on the object's stream"""
         _check(lib.yagi_hip_ordfilt_rrrf_execute_block_dev(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+
+MSEQUENCE_TILE = 8192    # YAGI_MSEQUENCE_TILE: symbols per workgroup of the generator kernel
+BSEQUENCE_TILE = 4096    # YAGI_BSEQUENCE_TILE: outputs per workgroup of the correlator kernel
+BSEQUENCE_NMAX = 8192    # YAGI_BSEQUENCE_NMAX: the longest BSequence, in bits
+
+
+class MSequence(_Handle):
+    """MSequence (src/sequence/msequence.rs:41-164): a shift-register sequence of period 2^m - 1 for a primitive g.  The
+    per-bit calls run on the host; the block forms run sequence_kernels.hip and give the same bits, because advance() is
+    linear over GF(2) and every lane jumps to its own start.  create_default is left out (yagi_hip.h): pass g."""
+    _prefix = "yagi_hip_msequence_"
+
+    def __init__(self, m, g, a=1):                            # new() :55-67; the state starts as a, not masked
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_msequence_create(m, g, a, C.byref(hd)))
+        self._h = hd
+
+    @classmethod
+    def from_genpoly(cls, g):                                 # create_genpoly() :69-77
+        new = object.__new__(cls)
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_msequence_create_genpoly(g, C.byref(hd)))
+        new._h = hd
+        return new
+
+    def clone(self):                                          # derive(Clone)
+        new = object.__new__(type(self))
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_msequence_clone(self._h, C.byref(hd)))
+        new._h = hd
+        return new
+
+    def _get(self, name):
+        v = C.c_uint()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return v.value
+
+    def advance(self):                                        # :116-122
+        return self._get("advance")
+
+    def generate_symbol(self, bps):                           # :124-131, MSB first, bps <= 32
+        v = C.c_uint()
+        _check(lib.yagi_hip_msequence_generate_symbol(self._h, bps, C.byref(v)))
+        return v.value
+
+    def set_state(self, a):                                   # :143-145, not masked
+        _check(lib.yagi_hip_msequence_set_state(self._h, a))
+
+    def get_state(self):
+        return self._get("get_state")
+
+    def get_genpoly(self):
+        return self._get("get_genpoly")
+
+    def get_genpoly_length(self):
+        return self._get("get_genpoly_length")
+
+    def get_length(self):
+        return self._get("get_length")
+
+    def measure_period(self):                                 # :147-158
+        return self._get("measure_period")
+
+    def skip(self, k):
+        """extension: the state becomes what k calls of advance() would leave, in O(log k)"""
+        _check(lib.yagi_hip_msequence_skip(self._h, k))
+
+    def generate_bits_block(self, n, y=None):
+        """n calls of advance(), one bit per byte"""
+        y = _out(y, n, np.uint8)
+        _check(lib.yagi_hip_msequence_generate_bits_block(self._h, n, _ptr(y)))
+        return y
+
+    def generate_symbols_block(self, bps, n, y=None):
+        """y[i] = generate_symbol(bps), 1 <= bps <= 8: the layout Modem.modulate_block reads"""
+        y = _out(y, n, np.uint8)
+        _check(lib.yagi_hip_msequence_generate_symbols_block(self._h, bps, n, _ptr(y)))
+        return y
+
+    def generate_bits_block_devptr(self, n, y_dev):
+        """y_dev: n bytes on the device; asynchronous on the object's stream"""
+        _check(lib.yagi_hip_msequence_generate_bits_block_dev(self._h, n, _devptr(y_dev)))
+
+    def generate_symbols_block_devptr(self, bps, n, y_dev):
+        """y_dev: n bytes on the device; asynchronous on the object's stream"""
+        _check(lib.yagi_hip_msequence_generate_symbols_block_dev(self._h, bps, n, _devptr(y_dev)))
+
+
+class BSequence(_Handle):
+    """BSequence (src/sequence/bsequence.rs:8-195): num_bits <= BSEQUENCE_NMAX bits, the newest at index 0.  The per-bit
+    calls run on the host; push_correlate_block runs the sliding correlator of sequence_kernels.hip and equals the loop
+    `for s in sym: push the bps bits of s, MSB first; rxy = ref.correlate(self)` bit for bit."""
+    _prefix = "yagi_hip_bsequence_"
+
+    def __init__(self, num_bits):                             # new() :16-30
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_bsequence_create(num_bits, C.byref(hd)))
+        self._h = hd
+
+    @classmethod
+    def from_msequence(cls, ms):                              # :81-88; ms advances by its length
+        new = object.__new__(cls)
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_bsequence_create_from_msequence(ms._h, C.byref(hd)))
+        new._h = hd
+        return new
+
+    @classmethod
+    def ccodes(cls, n):                                       # create_ccodes() :34-79 on two new sequences of n bits
+        a, b = cls(n), cls(n)
+        _check(lib.yagi_hip_bsequence_create_ccodes(a._h, b._h))
+        return a, b
+
+    def clone(self):                                          # derive(Clone)
+        new = object.__new__(type(self))
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_bsequence_clone(self._h, C.byref(hd)))
+        new._h = hd
+        return new
+
+    def init(self, v):                                        # :95-108
+        v = _arr(v, np.uint8)
+        _check(lib.yagi_hip_bsequence_init(self._h, _ptr(v), v.size))
+
+    def push(self, bit):                                      # :115-127
+        _check(lib.yagi_hip_bsequence_push(self._h, int(bit) & 0xffffffff))
+
+    def circshift(self):                                      # :130-134
+        _check(lib.yagi_hip_bsequence_circshift(self._h))
+
+    def correlate(self, other):                               # :137-150; self is the receiver
+        r = C.c_int32()
+        _check(lib.yagi_hip_bsequence_correlate(self._h, other._h, C.byref(r)))
+        return r.value
+
+    def add(self, other, out):                                # :153-163
+        _check(lib.yagi_hip_bsequence_add(self._h, other._h, out._h))
+
+    def mul(self, other, out):                                # :166-176
+        _check(lib.yagi_hip_bsequence_mul(self._h, other._h, out._h))
+
+    def accumulate(self):                                     # :179-181
+        v = C.c_uint()
+        _check(lib.yagi_hip_bsequence_accumulate(self._h, C.byref(v)))
+        return v.value
+
+    def index(self, i):                                       # :188-194
+        v = C.c_uint()
+        _check(lib.yagi_hip_bsequence_index(self._h, i, C.byref(v)))
+        return v.value
+
+    def get_length(self):
+        v = C.c_size_t()
+        _check(lib.yagi_hip_bsequence_get_length(self._h, C.byref(v)))
+        return v.value
+
+    def push_correlate_block(self, ref, sym, bps, rxy=True):
+        """pushes the bps bits of every symbol (uint8, MSB first) and returns ref.correlate(self) after each as int32;
+        rxy=None only pushes, rxy=<int32 array of len(sym)> is filled and returned"""
+        sym = _arr(sym, np.uint8)
+        if rxy is None:
+            _check(lib.yagi_hip_bsequence_push_correlate_block(self._h, ref._h, _ptr(sym), sym.size, bps, None))
+            return None
+        y = _out(None if rxy is True else rxy, sym.size, np.int32)
+        _check(lib.yagi_hip_bsequence_push_correlate_block(self._h, ref._h, _ptr(sym), sym.size, bps, _ptr(y)))
+        return y
+
+    def push_correlate_block_devptr(self, ref, sym_dev, n, bps, rxy_dev):
+        """sym_dev: n bytes, rxy_dev: n int32 on the device (or None: only push), not overlapping (ConfigError);
+        asynchronous on the object's stream"""
+        _check(lib.yagi_hip_bsequence_push_correlate_block_dev(self._h, ref._h, _devptr(sym_dev), n, bps,
+                                                               None if rxy_dev is None else _devptr(rxy_dev)))
 
 
 class ModulationScheme(enum.IntEnum):

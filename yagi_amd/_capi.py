@@ -477,3 +477,43 @@ for _n in ("modulate_block", "modulate_block_dev"):
     _sig(_p + _n, vp, vp, sz, vp)
 for _n in ("demodulate_block", "demodulate_block_dev", "demodulate_soft_block", "demodulate_soft_block_dev"):
     _sig(_p + _n, vp, vp, sz, vp, vp)
+
+# ---- MSequence / BSequence ---------------------------------------------------------------------
+cu = C.c_uint
+pcu = C.POINTER(cu)
+_p = "yagi_hip_msequence_"
+_sig(_p + "create", cu, cu, cu, pvp)
+_sig(_p + "create_genpoly", cu, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "advance", vp, pcu)
+_sig(_p + "generate_symbol", vp, cu, pcu)
+_sig(_p + "set_state", vp, cu)
+for _n in ("get_state", "get_genpoly", "get_genpoly_length", "get_length", "measure_period"):
+    _sig(_p + _n, vp, pcu)
+_sig(_p + "skip", vp, u64)
+for _n in ("generate_bits_block", "generate_bits_block_dev"):
+    _sig(_p + _n, vp, sz, vp)
+for _n in ("generate_symbols_block", "generate_symbols_block_dev"):
+    _sig(_p + _n, vp, cu, sz, vp)
+_p = "yagi_hip_bsequence_"
+_sig(_p + "create", sz, pvp)
+_sig(_p + "create_from_msequence", vp, pvp)
+_sig(_p + "create_ccodes", vp, vp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "init", vp, vp, sz)
+_sig(_p + "push", vp, cu)
+_sig(_p + "circshift", vp)
+_sig(_p + "correlate", vp, vp, C.POINTER(C.c_int32))
+_sig(_p + "add", vp, vp, vp)
+_sig(_p + "mul", vp, vp, vp)
+_sig(_p + "accumulate", vp, pcu)
+_sig(_p + "index", vp, sz, pcu)
+_sig(_p + "get_length", vp, C.POINTER(sz))
+for _n in ("push_correlate_block", "push_correlate_block_dev"):
+    _sig(_p + _n, vp, vp, vp, sz, cu, vp)

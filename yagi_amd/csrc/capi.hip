@@ -16,6 +16,7 @@
 #include <memory>
 
 #include <algorithm>
+#include <atomic>
 
 #include "kernels.hpp"
 #include "objstate.hpp"
@@ -5783,6 +5784,453 @@ int yagi_hip_ordfilt_rrrf_execute_block_dev(yagi_hip_ordfilt_rrrf q, const float
     CHECK_PTR(y_dev);
     CHECK_NOALIAS(x_dev, n, y_dev, n);
     return q->block_dev(x_dev, n, y_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
+// ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
+// The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
+// (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the
+// same matrices, so nothing is ever read back.
+struct yagi_hip_msequence_s {
+    hipStream_t st = nullptr;
+    unsigned m = 0, g = 0, a = 0, n = 0, state = 0;
+    std::vector<unsigned> pow, stride;                    // T^(2^b); the block kernel's lane strides per bps
+    yagi::DevBuf dpow, dstride;
+    yagi::Staging ws;
+
+    int init(unsigned m_, unsigned g_, unsigned a_) {                        // new() :55-67
+        if (m_ > 31 || m_ < 2) return yagi::fail(YAGI_ERR_CONFIG, "m (%u) not in range", m_);
+        YG_TRY(yagi::require_device());
+        m = m_;
+        g = g_;
+        a = a_;
+        n = (1u << m) - 1u;
+        state = a;
+        pow.resize(yagi::kMseqPowWords);
+        stride.resize(yagi::kMseqStrideWords);
+        yagi::msequence_tables(g, n, pow.data(), stride.data());
+        return upload_tables();
+    }
+    int upload_tables() {
+        YG_TRY(yagi::fill(dpow, pow.data(), pow.size() * sizeof(unsigned), st));
+        return yagi::fill(dstride, stride.data(), stride.size() * sizeof(unsigned), st);
+    }
+    unsigned advance() {                                                     // :116-122
+        const unsigned b = (unsigned)__builtin_popcount(state & g) & 1u;
+        state = ((state << 1) | b) & n;
+        return b;
+    }
+    unsigned generate_symbol(unsigned bps) {                                 // :124-131
+        unsigned s = 0;
+        for (unsigned i = 0; i < bps; ++i) s = (s << 1) | advance();
+        return s;
+    }
+    int block_dev(unsigned bps, size_t nb, uint8_t *y) {
+        if (bps < 1 || bps > 8) return yagi::fail(YAGI_ERR_CONFIG, "bits per symbol (%u) must be in 1..8", bps);
+        if (nb == 0) return YAGI_OK;
+        YG_TRY(yagi::launch_msequence_gen(dpow.as<unsigned>(), dstride.as<unsigned>(), state, g, n, (int)m, (int)bps, nb, y, st));
+        state = yagi::msequence_skip(pow.data(), state, (uint64_t)nb * bps);
+        return YAGI_OK;
+    }
+    int block_host(unsigned bps, size_t nb, uint8_t *y) {
+        if (bps < 1 || bps > 8) return yagi::fail(YAGI_ERR_CONFIG, "bits per symbol (%u) must be in 1..8", bps);
+        if (nb == 0) return YAGI_OK;
+        YG_TRY(ws.y.ensure(nb));
+        YG_TRY(block_dev(bps, nb, ws.y.as<uint8_t>()));
+        return yagi::download(y, ws.y.p, nb, st);
+    }
+};
+
+#define MSEQ_GET(name, field)                                                                       \
+    int yagi_hip_msequence_##name(yagi_hip_msequence q, unsigned *v) try {                          \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(v);                                                                               \
+        *v = q->field;                                                                              \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }
+
+extern "C" {
+
+int yagi_hip_msequence_create(unsigned m, unsigned g, unsigned a, yagi_hip_msequence *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    auto o = std::make_unique<yagi_hip_msequence_s>();
+    YG_TRY(o->init(m, g, a));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_create_genpoly(unsigned g, yagi_hip_msequence *q) try {       // :69-77
+    CHECK_PTR(q);
+    *q = nullptr;
+    unsigned t = 0;
+    while (t < 32 && (g >> t) != 0u) ++t;                 // msb_index: the bit length
+    if (t < 2) return fail(YAGI_ERR_CONFIG, "invalid generator polynomial: 0x%x", g);
+    return yagi_hip_msequence_create(t, g, 1u, q);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_destroy(yagi_hip_msequence q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_clone(yagi_hip_msequence q, yagi_hip_msequence *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    auto o = std::make_unique<yagi_hip_msequence_s>();
+    o->st = q->st;
+    o->m = q->m;
+    o->g = q->g;
+    o->a = q->a;
+    o->n = q->n;
+    o->state = q->state;
+    o->pow = q->pow;
+    o->stride = q->stride;
+    YG_TRY(o->upload_tables());
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_set_stream(yagi_hip_msequence q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_reset(yagi_hip_msequence q) try {                              // :133-135
+    CHECK_Q(q);
+    q->state = q->a;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_advance(yagi_hip_msequence q, unsigned *bit) try {
+    CHECK_Q(q);
+    CHECK_PTR(bit);
+    *bit = q->advance();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_generate_symbol(yagi_hip_msequence q, unsigned bps, unsigned *sym) try {
+    CHECK_Q(q);
+    CHECK_PTR(sym);
+    if (bps > 32) return fail(YAGI_ERR_CONFIG, "bits per symbol (%u) must be at most 32", bps);
+    *sym = q->generate_symbol(bps);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_set_state(yagi_hip_msequence q, unsigned a) try {              // :143-145, not masked
+    CHECK_Q(q);
+    q->state = a;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+MSEQ_GET(get_state, state)
+MSEQ_GET(get_genpoly, g)
+MSEQ_GET(get_genpoly_length, m)
+MSEQ_GET(get_length, n)
+int yagi_hip_msequence_measure_period(yagi_hip_msequence q, unsigned *period) try {   // :147-158
+    CHECK_Q(q);
+    CHECK_PTR(period);
+    const unsigned s = q->state;
+    unsigned p = 0;
+    for (unsigned i = 0; i <= q->n; ++i) {
+        q->advance();
+        ++p;
+        if (q->state == s) break;
+    }
+    *period = p;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_skip(yagi_hip_msequence q, uint64_t k) try {
+    CHECK_Q(q);
+    q->state = yagi::msequence_skip(q->pow.data(), q->state, k);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_generate_bits_block(yagi_hip_msequence q, size_t n, uint8_t *bits) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(bits);
+    return q->block_host(1, n, bits);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_generate_bits_block_dev(yagi_hip_msequence q, size_t n, uint8_t *bits_dev) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(bits_dev);
+    return q->block_dev(1, n, bits_dev);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_generate_symbols_block(yagi_hip_msequence q, unsigned bps, size_t n, uint8_t *sym) try {
+    CHECK_Q(q);
+    if (n != 0) CHECK_PTR(sym);
+    return q->block_host(bps, n, sym);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_msequence_generate_symbols_block_dev(yagi_hip_msequence q, unsigned bps, size_t n, uint8_t *sym_dev) try {
+    CHECK_Q(q);
+    if (n != 0) CHECK_PTR(sym_dev);
+    return q->block_dev(bps, n, sym_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
+// ---- BSequence (src/sequence/bsequence.rs) -------------------------------------------------------------------------
+// The state is the reference's word array, word 0 oldest and masked.  Scalar calls run on the host mirror; the block
+// call runs sequence_kernels.hip on the device copy, whose launch writes the window it leaves into the other of two
+// buffers.  The two copies are synchronised lazily (Mirror).  The kernel reads ref's words from a buffer of q's own,
+// refreshed when ref (identified by uid) or its content (counted by ver) differs from what that buffer holds.
+struct yagi_hip_bsequence_s {
+    hipStream_t st = nullptr;
+    size_t num_bits = 0, num_bits_msb = 0;
+    unsigned bit_mask_msb = 0;
+    std::vector<unsigned> s;                              // host mirror
+    yagi::PingPong<> dev;                                 // device copy
+    yagi::DevBuf dref;                                    // ref's words as the block kernel reads them
+    unsigned long long uid = 0, ver = 0, ref_uid = 0, ref_ver = 0;
+    yagi::Staging ws;
+    yagi::Mirror mirror;
+
+    static unsigned long long next_uid() {
+        static std::atomic<unsigned long long> c{0};
+        return ++c;
+    }
+    size_t bytes() const { return s.size() * sizeof(unsigned); }
+    static int check_bits(size_t nbits) {
+        if (nbits == 0) return yagi::fail(YAGI_ERR_CONFIG, "sequence length must be greater than zero");
+        if (nbits > (size_t)YAGI_BSEQUENCE_NMAX)
+            return yagi::fail(YAGI_ERR_CONFIG, "sequence length %zu exceeds YAGI_BSEQUENCE_NMAX = %d", nbits, YAGI_BSEQUENCE_NMAX);
+        return YAGI_OK;
+    }
+    int init(size_t nbits) {                                                 // new() :16-30
+        YG_TRY(check_bits(nbits));
+        YG_TRY(yagi::require_device());
+        num_bits = nbits;
+        num_bits_msb = nbits % 32 == 0 ? 32 : nbits % 32;
+        bit_mask_msb = num_bits_msb == 32 ? 0xffffffffu : (1u << num_bits_msb) - 1u;
+        s.assign((nbits + 31) / 32, 0u);
+        uid = next_uid();
+        YG_TRY(dev.alloc(bytes()));
+        YG_TRY(dref.alloc(bytes()));
+        return reset();
+    }
+    int reset() {                                                            // :90-92
+        std::fill(s.begin(), s.end(), 0u);
+        YG_HIP(hipMemsetAsync(dev.cur(), 0, bytes(), st));
+        mirror.in_sync();
+        ++ver;
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] { return yagi::download(s.data(), dev.cur(), bytes(), st); });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] { return yagi::upload(dev.cur(), s.data(), bytes(), st); });
+    }
+    int enter_host() {
+        YG_TRY(ensure_host());
+        mirror.host_written();
+        ++ver;
+        return YAGI_OK;
+    }
+    void push(unsigned bit) {                                                // :115-127 (after enter_host)
+        s[0] = (s[0] << 1) & bit_mask_msb;
+        for (size_t i = 1; i < s.size(); ++i) {
+            s[i - 1] |= s[i] >> 31;
+            s[i] <<= 1;
+        }
+        s.back() |= bit & 1u;
+    }
+    void load_bytes(const uint8_t *v) {                                      // init() :95-108
+        for (size_t i = 0; i < num_bits; ++i) push((v[i / 8] >> (7 - i % 8)) & 1u);
+    }
+    int block_dev(yagi_hip_bsequence_s *ref, const uint8_t *sym, size_t nb, unsigned bps, int32_t *rxy) {
+        if (nb == 0) return YAGI_OK;
+        if (ref->uid != ref_uid || ref->ver != ref_ver) {                    // ref as it stands now
+            YG_TRY(ref->ensure_host());
+            YG_TRY(yagi::upload(dref.p, ref->s.data(), bytes(), st));
+            ref_uid = ref->uid;
+            ref_ver = ref->ver;
+        }
+        YG_TRY(ensure_dev());
+        YG_TRY(yagi::launch_bsequence_corr(dev.cur<unsigned>(), dev.next<unsigned>(), dref.as<unsigned>(), (int)s.size(),
+                                           bit_mask_msb, (int)ref->num_bits_msb, sym, nb, (int)bps, rxy, st));
+        dev.flip();
+        mirror.dev_written();
+        ++ver;
+        return YAGI_OK;
+    }
+};
+
+static int bseq_block_args(yagi_hip_bsequence q, yagi_hip_bsequence ref, unsigned bps) {
+    CHECK_Q(q);
+    CHECK_Q(ref);
+    if (bps < 1 || bps > 8) return fail(YAGI_ERR_CONFIG, "bits per symbol (%u) must be in 1..8", bps);
+    if (ref == q) return fail(YAGI_ERR_CONFIG, "the reference sequence must be another object than the one pushed into");
+    if (ref->s.size() != q->s.size()) return fail(YAGI_ERR_CONFIG, "binary sequences must be the same length");
+    return YAGI_OK;
+}
+// out = a (op) b word by word (:153-176)
+template <class F>
+static int bseq_combine(yagi_hip_bsequence a, yagi_hip_bsequence b, yagi_hip_bsequence out, F &&op) {
+    CHECK_Q(a);
+    CHECK_Q(b);
+    CHECK_Q(out);
+    if (a->s.size() != b->s.size() || a->s.size() != out->s.size())
+        return fail(YAGI_ERR_CONFIG, "binary sequences must be same length");
+    YG_TRY(a->ensure_host());
+    YG_TRY(b->ensure_host());
+    YG_TRY(out->enter_host());
+    for (size_t i = 0; i < a->s.size(); ++i) out->s[i] = op(a->s[i], b->s[i]);
+    return YAGI_OK;
+}
+
+extern "C" {
+
+int yagi_hip_bsequence_create(size_t num_bits, yagi_hip_bsequence *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    auto o = std::make_unique<yagi_hip_bsequence_s>();
+    YG_TRY(o->init(num_bits));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_create_from_msequence(yagi_hip_msequence ms, yagi_hip_bsequence *q) try {    // :81-88
+    CHECK_PTR(q);
+    *q = nullptr;
+    CHECK_Q(ms);
+    auto o = std::make_unique<yagi_hip_bsequence_s>();
+    YG_TRY(o->init((size_t)ms->n));
+    YG_TRY(o->enter_host());
+    for (unsigned i = 0; i < ms->n; ++i) o->push(ms->advance());
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_create_ccodes(yagi_hip_bsequence qa, yagi_hip_bsequence qb) try {            // :34-79
+    CHECK_Q(qa);
+    CHECK_Q(qb);
+    if (qa->num_bits != qb->num_bits) return fail(YAGI_ERR_CONFIG, "sequence lengths must match");
+    if (qa->num_bits < 8) return fail(YAGI_ERR_CONFIG, "sequence too short");
+    if (qa->num_bits % 8 != 0) return fail(YAGI_ERR_CONFIG, "sequence must be multiple of 8");
+    const size_t nby = qa->num_bits / 8;
+    std::vector<uint8_t> a(nby, 0), b(nby, 0);
+    a[nby - 1] = 0xb8;
+    b[nby - 1] = 0xb7;
+    for (size_t n = 1; n < nby; n *= 2) {
+        const size_t i1 = nby - n, i0 = nby - 2 * n;
+        for (size_t i = 0; i < n; ++i) {                  // a -> [a b], b -> [a ~b]
+            a[i0 + i] = a[i1 + i];
+            b[i0 + i] = a[i1 + i];
+        }
+        for (size_t i = 0; i < n; ++i) a[i1 + i] = b[i1 + i];
+        for (size_t i = 0; i < n; ++i) b[nby - i - 1] ^= 0xff;
+    }
+    YG_TRY(qa->enter_host());
+    YG_TRY(qb->enter_host());
+    qa->load_bytes(a.data());
+    qb->load_bytes(b.data());
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_destroy(yagi_hip_bsequence q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_clone(yagi_hip_bsequence q, yagi_hip_bsequence *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_bsequence_s>();
+    o->st = q->st;
+    YG_TRY(o->init(q->num_bits));
+    o->s = q->s;
+    o->mirror.host_written();
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_set_stream(yagi_hip_bsequence q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_reset(yagi_hip_bsequence q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_init(yagi_hip_bsequence q, const uint8_t *v, size_t nbytes) try {
+    CHECK_Q(q);
+    CHECK_PTR(v);
+    if (nbytes < (q->num_bits + 7) / 8) return fail(YAGI_ERR_CONFIG, "init needs %zu bytes", (q->num_bits + 7) / 8);
+    YG_TRY(q->enter_host());
+    q->load_bytes(v);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_push(yagi_hip_bsequence q, unsigned bit) try {
+    CHECK_Q(q);
+    YG_TRY(q->enter_host());
+    q->push(bit);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_circshift(yagi_hip_bsequence q) try {                                        // :130-134
+    CHECK_Q(q);
+    YG_TRY(q->enter_host());
+    q->push((q->s[0] >> (q->num_bits_msb - 1)) & 1u);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_correlate(yagi_hip_bsequence a, yagi_hip_bsequence b, int32_t *rxy) try {    // :137-150
+    CHECK_Q(a);
+    CHECK_Q(b);
+    CHECK_PTR(rxy);
+    if (a->s.size() != b->s.size()) return fail(YAGI_ERR_CONFIG, "binary sequences must be the same length");
+    YG_TRY(a->ensure_host());
+    YG_TRY(b->ensure_host());
+    int32_t r = 0;
+    for (size_t i = 0; i < a->s.size(); ++i) r += __builtin_popcount(~(a->s[i] ^ b->s[i]));
+    *rxy = r - (32 - (int32_t)a->num_bits_msb);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_add(yagi_hip_bsequence a, yagi_hip_bsequence b, yagi_hip_bsequence out) try {
+    return bseq_combine(a, b, out, [](unsigned x, unsigned y) { return x ^ y; });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_mul(yagi_hip_bsequence a, yagi_hip_bsequence b, yagi_hip_bsequence out) try {
+    return bseq_combine(a, b, out, [](unsigned x, unsigned y) { return x & y; });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_accumulate(yagi_hip_bsequence q, unsigned *count) try {                      // :179-181
+    CHECK_Q(q);
+    CHECK_PTR(count);
+    YG_TRY(q->ensure_host());
+    unsigned c = 0;
+    for (unsigned w : q->s) c += (unsigned)__builtin_popcount(w);
+    *count = c;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_index(yagi_hip_bsequence q, size_t i, unsigned *bit) try {                   // :188-194
+    CHECK_Q(q);
+    CHECK_PTR(bit);
+    if (i >= q->num_bits) return fail(YAGI_ERR_CONFIG, "invalid index %zu", i);
+    YG_TRY(q->ensure_host());
+    *bit = (q->s[q->s.size() - 1 - i / 32] >> (i % 32)) & 1u;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_get_length(yagi_hip_bsequence q, size_t *num_bits) try {
+    CHECK_Q(q);
+    CHECK_PTR(num_bits);
+    *num_bits = q->num_bits;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_push_correlate_block(yagi_hip_bsequence q, yagi_hip_bsequence ref, const uint8_t *sym, size_t n,
+                                            unsigned bps, int32_t *rxy) try {
+    YG_TRY(bseq_block_args(q, ref, bps));
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(sym);
+    YG_TRY(q->ws.put(q->st, sym, n));
+    if (rxy) YG_TRY(q->ws.y.ensure(n * sizeof(int32_t)));
+    YG_TRY(q->block_dev(ref, q->ws.x.as<uint8_t>(), n, bps, rxy ? q->ws.y.as<int32_t>() : nullptr));
+    if (rxy) return download(rxy, q->ws.y.p, n * sizeof(int32_t), q->st);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_bsequence_push_correlate_block_dev(yagi_hip_bsequence q, yagi_hip_bsequence ref, const uint8_t *sym_dev,
+                                                size_t n, unsigned bps, int32_t *rxy_dev) try {
+    YG_TRY(bseq_block_args(q, ref, bps));
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(sym_dev);
+    if (rxy_dev) CHECK_NOALIAS(sym_dev, n, rxy_dev, n);
+    return q->block_dev(ref, sym_dev, n, bps, rxy_dev);
 } catch (...) { return ::yagi::api_exception(); }
 
 }  // extern "C"

@@ -386,4 +386,36 @@ int launch_ordfilt(int n, int k, int form, const float *hist, float *hist_next, 
 // element k of the window (n samples, oldest first) after a stable sort under the same order; tmp is scratch
 float ordfilt_host_select(const float *win, int n, int k, std::vector<std::pair<unsigned, unsigned>> &tmp);
 
+// ---- sequence_kernels.hip ------------------------------------------------------------------
+// MSequence (src/sequence/msequence.rs): advance() is linear over GF(2) on the 32-bit state word; a matrix is 32 column
+// words.  pow = T^(2^b), b = 0 .. kMseqPowers-1; stride = for bps = 1 .. 8 the kMseqStrides lane-stride matrices
+// T^(kMseqRun * bps * 2^b) of the block kernel.  Both tables are built once per object and uploaded as they are.
+constexpr int kMseqWg = 256;                           // threads per workgroup
+constexpr int kMseqTile = YAGI_MSEQUENCE_TILE;         // symbols per workgroup
+constexpr int kMseqRun = kMseqTile / kMseqWg;          // consecutive symbols per lane
+constexpr int kMseqPowers = 64;
+constexpr int kMseqStrides = 6;                        // one per bit of the lane number within a wave
+constexpr size_t kMseqPowWords = (size_t)kMseqPowers * 32, kMseqStrideWords = (size_t)8 * kMseqStrides * 32;
+constexpr size_t kMseqLdsBytes = (size_t)kMseqTile;    // the tile's bytes
+void msequence_tables(unsigned g, unsigned nmask, unsigned *pow, unsigned *stride);
+unsigned msequence_skip(const unsigned *pow, unsigned s, uint64_t k);     // the state k steps after s, O(log k)
+// y[i] = generate_symbol(bps) for i < n from the state s0 (bps = 1: one bit per byte); the caller advances its state
+int launch_msequence_gen(const unsigned *pow, const unsigned *stride, unsigned s0, unsigned g, unsigned nmask, int m,
+                         int bps, size_t n, uint8_t *y, hipStream_t st);
+
+// BSequence (src/sequence/bsequence.rs) push_correlate_block on device buffers: for each of n symbols, push its bps
+// bits (MSB first) into the window cur (W words, word 0 oldest and masked by qmask), then rxy[i] = ref.correlate(q).
+// next receives the window the call leaves and must not alias cur.  rxy may be null (the call then only pushes).
+constexpr int kBseqWg = 256;                           // threads per workgroup
+constexpr int kBseqTile = YAGI_BSEQUENCE_TILE;         // outputs per workgroup
+constexpr int kBseqNmax = YAGI_BSEQUENCE_NMAX;         // longest window, in bits
+// LDS of the kernel: the packed words a tile's windows span (8 bits per symbol at most, the window, one word of slack
+// at either end) and the symbol bytes under them (one bit per symbol at least, 16 bytes of alignment slack)
+constexpr int kBseqPackedWords = kBseqTile * 8 / 32 + kBseqNmax / 32 + 2;
+constexpr int kBseqSymBytes = kBseqTile + (kBseqNmax / 32 + 2) * 32 + 16;
+constexpr size_t kBseqLdsBytes = (size_t)kBseqPackedWords * 4 + (size_t)kBseqSymBytes;
+static_assert(kBseqLdsBytes <= 64 * 1024 && kBseqNmax % 32 == 0 && kBseqNmax / 32 <= kBseqWg, "the tile must fit a workgroup's LDS");
+int launch_bsequence_corr(const unsigned *cur, unsigned *next, const unsigned *ref, int W, unsigned qmask,
+                          int ref_bits_msb, const uint8_t *sym, size_t n, int bps, int *rxy, hipStream_t st);
+
 }  // namespace yagi
