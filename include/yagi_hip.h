@@ -827,6 +827,62 @@ int yagi_hip_osc_mix_block_down(yagi_hip_osc q, const yagi_cf32 *x, size_t nx, y
 int yagi_hip_osc_mix_block_up_dev(yagi_hip_osc q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
 int yagi_hip_osc_mix_block_down_dev(yagi_hip_osc q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev);
 
+/* ---- Ddc / Duc: digital down- and up-converter (the reference's src/filter/dds.rs is an empty file) -------------------
+ * Defined as compositions of two objects of this library, kinds crcf and cccf:
+ *   Ddc  = Osc::mix_block_down, then FirDecimationFilter::execute_block: n M samples in, n out.  Input j of a call at
+ *          oscillator state (theta, d_theta) is mixed with the phase word theta + (u32)j d_theta; the decimator's window
+ *          holds MIXED samples of earlier calls; the call leaves theta + (u32)(n M) d_theta.
+ *   Duc  = FirInterpolationFilter::execute_block, then Osc::mix_block_up: n samples in, n I out.  Output j is mixed with
+ *          theta + (u32)j d_theta; the interpolator's window holds the unmixed inputs; theta advances by n I steps.
+ * Every output word equals what separate yagi_hip_osc and yagi_hip_firdecim / yagi_hip_firinterp objects give for the
+ * same taps, scale, frequency, phase and call lengths.
+ *   create(scheme, rate, h, h_len)   scheme as for yagi_hip_osc_create, rate / h / h_len as for yagi_hip_firdecim_*_create
+ *                             (Ddc) or yagi_hip_firinterp_*_create (Duc); the parts' own YAGI_ERR_CONFIG messages
+ *   create_kaiser(scheme, rate, m, as_)   the parts' Kaiser prototype and its errors
+ *   clone / set_stream / reset       reset clears the filter window and leaves the oscillator alone
+ *   set/adjust_frequency, set/adjust_phase, get_frequency, get_phase   Osc's, through the same constrain()
+ *   get_state / set_state            EXTENSION: the raw u32 words theta and d_theta
+ *   set_scale / get_scale / get_decim_rate / get_interp_rate          the filter's
+ *   execute                          Ddc: x[M] -> *y, Duc: *x -> y[I], on the host mirror with Osc's per-sample mix;
+ *                                    may be interleaved with block calls
+ *   execute_block(x, n, y)           host slices: n outputs from n M inputs (Ddc), n I outputs from n inputs (Duc)
+ *   execute_block_dev                device buffers, asynchronous on the object's stream; x and y must not overlap and
+ *                                    need 8-byte alignment only; n = 0 returns at once and changes nothing
+ *   set_kernel(choice)               0 auto, 1 two launches through a scratch buffer the object owns, 2 the fused kernel
+ *                                    where one serves the shape (else two launches); auto = fused where served
+ *   get_last_kernel                  1 or 2: what the last block call ran (0 before the first)
+ * Device form: ddc_kernels.hip (which lists the shapes that take two launches). */
+#define YAGI_DECLARE_DDC(OBJ, RATE, K, C)                                                                           \
+    typedef struct yagi_hip_##OBJ##_##K##_s *yagi_hip_##OBJ##_##K;                                                  \
+    int yagi_hip_##OBJ##_##K##_create(int scheme, size_t rate, const C *h, size_t h_len, yagi_hip_##OBJ##_##K *q);  \
+    int yagi_hip_##OBJ##_##K##_create_kaiser(int scheme, size_t rate, size_t m, float as_, yagi_hip_##OBJ##_##K *q); \
+    int yagi_hip_##OBJ##_##K##_destroy(yagi_hip_##OBJ##_##K q);                                                     \
+    int yagi_hip_##OBJ##_##K##_clone(yagi_hip_##OBJ##_##K q, yagi_hip_##OBJ##_##K *out);                            \
+    int yagi_hip_##OBJ##_##K##_set_stream(yagi_hip_##OBJ##_##K q, yagi_stream_t s);                                 \
+    int yagi_hip_##OBJ##_##K##_reset(yagi_hip_##OBJ##_##K q);                                                       \
+    int yagi_hip_##OBJ##_##K##_set_frequency(yagi_hip_##OBJ##_##K q, float dtheta);                                 \
+    int yagi_hip_##OBJ##_##K##_adjust_frequency(yagi_hip_##OBJ##_##K q, float df);                                  \
+    int yagi_hip_##OBJ##_##K##_set_phase(yagi_hip_##OBJ##_##K q, float phi);                                        \
+    int yagi_hip_##OBJ##_##K##_adjust_phase(yagi_hip_##OBJ##_##K q, float dphi);                                    \
+    int yagi_hip_##OBJ##_##K##_get_frequency(yagi_hip_##OBJ##_##K q, float *f);                                     \
+    int yagi_hip_##OBJ##_##K##_get_phase(yagi_hip_##OBJ##_##K q, float *phi);                                       \
+    int yagi_hip_##OBJ##_##K##_get_state(yagi_hip_##OBJ##_##K q, uint32_t *theta, uint32_t *d_theta);               \
+    int yagi_hip_##OBJ##_##K##_set_state(yagi_hip_##OBJ##_##K q, uint32_t theta, uint32_t d_theta);                 \
+    int yagi_hip_##OBJ##_##K##_set_scale(yagi_hip_##OBJ##_##K q, C scale);                                          \
+    int yagi_hip_##OBJ##_##K##_get_scale(yagi_hip_##OBJ##_##K q, C *scale);                                         \
+    int yagi_hip_##OBJ##_##K##_##RATE(yagi_hip_##OBJ##_##K q, size_t *rate);                                        \
+    int yagi_hip_##OBJ##_##K##_set_kernel(yagi_hip_##OBJ##_##K q, int choice);                                      \
+    int yagi_hip_##OBJ##_##K##_get_last_kernel(yagi_hip_##OBJ##_##K q, int *k);                                     \
+    int yagi_hip_##OBJ##_##K##_execute(yagi_hip_##OBJ##_##K q, const yagi_cf32 *x, yagi_cf32 *y);                   \
+    int yagi_hip_##OBJ##_##K##_execute_block(yagi_hip_##OBJ##_##K q, const yagi_cf32 *x, size_t n, yagi_cf32 *y);   \
+    int yagi_hip_##OBJ##_##K##_execute_block_dev(yagi_hip_##OBJ##_##K q, const yagi_cf32 *x_dev, size_t n,          \
+                                                 yagi_cf32 *y_dev);
+YAGI_DECLARE_DDC(ddc, get_decim_rate, crcf, float)
+YAGI_DECLARE_DDC(ddc, get_decim_rate, cccf, yagi_cf32)
+YAGI_DECLARE_DDC(duc, get_interp_rate, crcf, float)
+YAGI_DECLARE_DDC(duc, get_interp_rate, cccf, yagi_cf32)
+#undef YAGI_DECLARE_DDC
+
 /* ---- FirHilbertFilter: src/filter/fir/firhilb.rs:1-263 (FIR Hilbert transform) -------------------------------------
  *   create(m, as_)            new() :38-84  m < 2 is YAGI_ERR_CONFIG; |as_| is used; hq = 2m taps of the Kaiser
  *                             half-band filter (4m + 1 taps, fc 0.25) times sin(pi/2 t), every other one reversed

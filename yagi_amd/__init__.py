@@ -34,7 +34,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -1245,6 +1245,141 @@ class Osc(_Handle):
 
     def mix_block_down_dev(self, x_dev, n, y_dev):
         _check(lib.yagi_hip_osc_mix_block_down_dev(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+
+class _DdcBase(_FirBase):
+    """what Ddc and Duc share: the oscillator words, the filter's scale and rate, the kernel choice"""
+    _obj = None
+    _rate_fn = None
+
+    def __init__(self, kind, scheme, rate, h, h_len=None):
+        self._init_ddc(kind, scheme)
+        h = _arr(h, self.Cdt)
+        hd = C.c_void_p()
+        _check(self._fn("create")(self.scheme.value, rate, _ptr(h), h.size if h_len is None else h_len, C.byref(hd)))
+        self._h = hd
+
+    def _init_ddc(self, kind, scheme):
+        if kind not in ("crcf", "cccf"):
+            raise ConfigError(f"{type(self).__name__} mixes complex samples: kind must be 'crcf' or 'cccf', not {kind!r}")
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_{self._obj}_{kind}_"
+        self.scheme = OscScheme(scheme)
+
+    @classmethod
+    def new_kaiser(cls, kind, scheme, rate, m, as_):
+        self = object.__new__(cls)
+        self._init_ddc(kind, scheme)
+        hd = C.c_void_p()
+        _check(self._fn("create_kaiser")(self.scheme.value, rate, m, as_, C.byref(hd)))
+        self._h = hd
+        return self
+
+    def set_frequency(self, dtheta):
+        _check(self._fn("set_frequency")(self._h, dtheta))
+
+    def adjust_frequency(self, df):
+        _check(self._fn("adjust_frequency")(self._h, df))
+
+    def set_phase(self, phi):
+        _check(self._fn("set_phase")(self._h, phi))
+
+    def adjust_phase(self, dphi):
+        _check(self._fn("adjust_phase")(self._h, dphi))
+
+    def _f32(self, name):
+        v = C.c_float()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return np.float32(v.value)
+
+    def get_frequency(self):
+        return self._f32("get_frequency")
+
+    def get_phase(self):
+        return self._f32("get_phase")
+
+    def get_state(self):
+        """extension: the raw u32 words (theta, d_theta)"""
+        t, d = C.c_uint32(), C.c_uint32()
+        _check(self._fn("get_state")(self._h, C.byref(t), C.byref(d)))
+        return t.value, d.value
+
+    def set_state(self, theta, d_theta):
+        """extension: set the raw u32 words"""
+        _check(self._fn("set_state")(self._h, theta & 0xFFFFFFFF, d_theta & 0xFFFFFFFF))
+
+    def _rate(self):
+        n = C.c_size_t()
+        _check(self._fn(self._rate_fn)(self._h, C.byref(n)))
+        return n.value
+
+    def set_kernel(self, choice):
+        """0 auto (fused where a fused kernel serves the shape), 1 two launches, 2 fused where served"""
+        _check(self._fn("set_kernel")(self._h, choice))
+
+    def get_last_kernel(self):
+        """1 (two launches) or 2 (fused): what the last block call ran; 0 before the first"""
+        k = C.c_int()
+        _check(self._fn("get_last_kernel")(self._h, C.byref(k)))
+        return k.value
+
+    def execute_block_devptr(self, x_dev, n, y_dev):
+        """x_dev, y_dev: complex64 on the device, not overlapping (ConfigError), 8-byte aligned; Ddc reads n*M samples
+        and writes n, Duc reads n and writes n*I; asynchronous on the object's stream"""
+        _check(self._fn("execute_block_dev")(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+
+class Ddc(_DdcBase):
+    """Digital down-converter: Osc.mix_block_down followed by FirDecimationFilter.execute_block in one launch
+    (ddc_kernels.hip), kinds crcf and cccf.  Every output word equals the two objects' composition; the decimator's
+    window holds mixed samples."""
+    _obj = "ddc"
+    _rate_fn = "get_decim_rate"
+
+    def get_decim_rate(self):
+        return self._rate()
+
+    def execute(self, x):
+        """M samples -> one output, on the host"""
+        x = _arr(x, np.complex64)
+        if x.size < self._rate():
+            raise ConfigError(f"input block too short: need {self._rate()} samples, got {x.size}")
+        y = np.zeros(1, np.complex64)
+        _check(self._fn("execute")(self._h, _ptr(x), _ptr(y)))
+        return y[0]
+
+    def execute_block(self, x, n):
+        """n outputs from the first n*M samples of x"""
+        x = _arr(x, np.complex64)
+        if x.size < n * self._rate():
+            raise ConfigError(f"input block too short: need {n * self._rate()} samples, got {x.size}")
+        y = np.empty(n, np.complex64)
+        _check(self._fn("execute_block")(self._h, _ptr(x), n, _ptr(y)))
+        return y
+
+
+class Duc(_DdcBase):
+    """Digital up-converter: FirInterpolationFilter.execute_block followed by Osc.mix_block_up in one launch
+    (ddc_kernels.hip), kinds crcf and cccf.  Every output word equals the two objects' composition."""
+    _obj = "duc"
+    _rate_fn = "get_interp_rate"
+
+    def get_interp_rate(self):
+        return self._rate()
+
+    def execute(self, x):
+        """one sample -> I outputs, on the host"""
+        xv = np.array([x], np.complex64)
+        y = np.empty(self._rate(), np.complex64)
+        _check(self._fn("execute")(self._h, _ptr(xv), _ptr(y)))
+        return y
+
+    def execute_block(self, x):
+        """n samples -> n*I outputs"""
+        x = _arr(x, np.complex64)
+        y = np.empty(x.size * self._rate(), np.complex64)
+        _check(self._fn("execute_block")(self._h, _ptr(x), x.size, _ptr(y)))
+        return y
 
 
 class FirHilbertFilter(_Handle):

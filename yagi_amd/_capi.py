@@ -397,6 +397,32 @@ _sig(_p + "mix_block_down", vp, vp, sz, vp, sz)
 _sig(_p + "mix_block_up_dev", vp, vp, sz, vp)
 _sig(_p + "mix_block_down_dev", vp, vp, sz, vp)
 
+# ---- Ddc / Duc ---------------------------------------------------------------------------------
+for _o, _rate in (("ddc", "get_decim_rate"), ("duc", "get_interp_rate")):
+    for _k in ("crcf", "cccf"):
+        _Cc = KIND_TYPES[_k][1]
+        _p = f"yagi_hip_{_o}_{_k}_"
+        _sig(_p + "create", ci, sz, vp, sz, pvp)
+        _sig(_p + "create_kaiser", ci, sz, sz, f32, pvp)
+        _sig(_p + "destroy", vp)
+        _sig(_p + "clone", vp, pvp)
+        _sig(_p + "set_stream", vp, vp)
+        _sig(_p + "reset", vp)
+        for _n in ("set_frequency", "adjust_frequency", "set_phase", "adjust_phase"):
+            _sig(_p + _n, vp, f32)
+        for _n in ("get_frequency", "get_phase"):
+            _sig(_p + _n, vp, C.POINTER(f32))
+        _sig(_p + "get_state", vp, C.POINTER(u32), C.POINTER(u32))
+        _sig(_p + "set_state", vp, u32, u32)
+        _sig(_p + "set_scale", vp, _Cc)
+        _sig(_p + "get_scale", vp, vp)
+        _sig(_p + _rate, vp, C.POINTER(sz))
+        _sig(_p + "set_kernel", vp, ci)
+        _sig(_p + "get_last_kernel", vp, C.POINTER(ci))
+        _sig(_p + "execute", vp, vp, vp)
+        _sig(_p + "execute_block", vp, vp, sz, vp)
+        _sig(_p + "execute_block_dev", vp, vp, sz, vp)
+
 # ---- FirHilbertFilter --------------------------------------------------------------------------
 _p = "yagi_hip_firhilb_"
 _sig(_p + "create", sz, f32, pvp)

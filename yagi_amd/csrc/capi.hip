@@ -6234,3 +6234,334 @@ int yagi_hip_bsequence_push_correlate_block_dev(yagi_hip_bsequence q, yagi_hip_b
 } catch (...) { return ::yagi::api_exception(); }
 
 }  // extern "C"
+
+// ---- Ddc / Duc (the reference's src/filter/dds.rs is an empty file: defined here as compositions) -----------------------
+// Ddc = Osc::mix_block_down, then FirDecimationFilter::execute_block; Duc = FirInterpolationFilter::execute_block, then
+// Osc::mix_block_up.  The objects compose the parts' own structs, so the window mirror, the staging of host slices, the
+// oscillator words and their constrain routine are the shared ones.  A block call runs one fused launch
+// (ddc_kernels.hip) where a fused kernel serves the shape, else the two launches of the parts through a scratch buffer
+// the object owns (kernel choice 1 forces that route); the words are the same either way.
+namespace yagi {
+
+static int ddc_check_scheme(int scheme) {
+    if (scheme != YAGI_OSC_NCO && scheme != YAGI_OSC_VCO) return fail(YAGI_ERR_CONFIG, "osc: unknown scheme %d", scheme);
+    return YAGI_OK;
+}
+
+struct DdcCommon {
+    OscObj osc;
+    DevBuf scratch;            // two-launch route: the full-rate stream between the launches
+    int choice = 0, last = 0;  // set_kernel / get_last_kernel
+    int set_kernel(int c) {
+        if (c < 0 || c > 2) return fail(YAGI_ERR_CONFIG, "unknown kernel choice %d (0 auto, 1 two launches, 2 fused)", c);
+        choice = c;
+        return YAGI_OK;
+    }
+    void copy_osc(const DdcCommon &o) {
+        osc.theta = o.osc.theta;
+        osc.d_theta = o.osc.d_theta;
+        osc.alpha = o.osc.alpha;
+        osc.beta = o.osc.beta;
+        choice = o.choice;
+    }
+};
+
+template <class K>
+struct DdcObj : DdcCommon {
+    using C = typename K::C;
+    FirDecim<K> fir;
+
+    hipStream_t &stream() { return fir.st; }
+    DevWindow<cf32> &window() { return fir.w; }
+    C &scale() { return fir.scale; }
+    size_t rate() const { return (size_t)fir.M; }
+    size_t n_in(size_t n) const { return n * (size_t)fir.M; }
+    size_t n_out(size_t n) const { return n; }
+    int init(int scheme, size_t M, const C *h, size_t n) {
+        YG_TRY(ddc_check_scheme(scheme));
+        YG_TRY(fir.init(M, h, n));
+        osc.st = fir.st;
+        return osc.init(scheme);
+    }
+    int clone_from(DdcObj &q) {
+        YG_TRY(q.fir.w.ensure_dev(q.fir.st));
+        fir.st = q.fir.st;
+        YG_TRY(init(q.osc.vco ? YAGI_OSC_VCO : YAGI_OSC_NCO, (size_t)q.fir.M, q.fir.h.data(), q.fir.h.size()));
+        fir.scale = q.fir.scale;
+        copy_osc(q);
+        return fir.w.clone_from(q.fir.w, q.fir.st);
+    }
+    // n outputs from n*M device samples
+    int block_dev(const cf32 *x, size_t n, cf32 *y) {
+        if (n == 0) return YAGI_OK;
+        const size_t nin = n_in(n);
+        if (choice != 1 && ddc_fused_serves<K>(fir.L, fir.M, n, osc.vco)) {
+            YG_TRY(fir.w.ensure_dev(fir.st));
+            YG_TRY((launch_ddc_block<K>(fir.w.dev(), x, fir.taps.template as<C>(), fir.L, fir.M, fir.scale, y, n, fir.st,
+                                        fir.w.next(), osc.vco, osc.tab.p, osc.theta, osc.d_theta)));
+            fir.w.flip();                           // the kernel's last workgroup wrote the next window, mixed
+            osc.theta += (uint32_t)nin * osc.d_theta;
+            last = 2;
+            return YAGI_OK;
+        }
+        YG_TRY(scratch.ensure(nin * sizeof(cf32)));
+        YG_TRY(osc.block_dev(x, nin, scratch.as<cf32>(), true));
+        YG_TRY(fir.block_dev(scratch.as<cf32>(), n, y));
+        last = 1;
+        return YAGI_OK;
+    }
+    // x[M] -> y on the host mirror: mix, step, push; the output follows the FIRST of the M pushes (firdecim.rs:179-191)
+    int execute(const cf32 *x, cf32 *y) {
+        YG_TRY(fir.w.ensure_host(fir.st));
+        for (int i = 0; i < fir.M; ++i) {
+            fir.w.push(osc_mix(osc.vco, osc.theta, true, x[i]));
+            osc.theta += osc.d_theta;
+            if (i == 0) *y = host_fir_window_dot<cf32, C>(fir.w.host(), (size_t)fir.L, fir.h.data(), fir.scale);
+        }
+        return YAGI_OK;
+    }
+    Staging &staging() { return fir.ws; }
+};
+
+template <class K>
+struct DucObj : DdcCommon {
+    using C = typename K::C;
+    FirInterp<K> fir;
+
+    hipStream_t &stream() { return fir.bank.st; }
+    DevWindow<cf32> &window() { return fir.bank.w; }
+    C &scale() { return fir.bank.scale; }
+    size_t rate() const { return (size_t)fir.interp; }
+    size_t n_in(size_t n) const { return n; }
+    size_t n_out(size_t n) const { return n * (size_t)fir.interp; }
+    int init(int scheme, size_t I, const C *h, size_t n) {
+        YG_TRY(ddc_check_scheme(scheme));
+        YG_TRY(fir.init(I, h, n));
+        osc.st = fir.bank.st;
+        return osc.init(scheme);
+    }
+    int clone_from(DucObj &q) {
+        FirPfb<K> &b = fir.bank, &qb = q.fir.bank;
+        YG_TRY(qb.w.ensure_dev(qb.st));
+        fir.interp = q.fir.interp;
+        fir.hs = q.fir.hs;
+        b.st = qb.st;
+        b.nf = qb.nf;
+        b.Ls = qb.Ls;
+        b.hb = qb.hb;
+        b.scale = qb.scale;
+        YG_TRY(fill(b.taps, b.hb.data(), b.hb.size() * sizeof(C), b.st));
+        YG_TRY(b.w.clone_from(qb.w, qb.st));
+        osc.st = b.st;
+        YG_TRY(osc.init(q.osc.vco ? YAGI_OSC_VCO : YAGI_OSC_NCO));
+        copy_osc(q);
+        return YAGI_OK;
+    }
+    // n inputs -> n*I device outputs
+    int block_dev(const cf32 *x, size_t n, cf32 *y) {
+        if (n == 0) return YAGI_OK;
+        FirPfb<K> &b = fir.bank;
+        const size_t nout = n_out(n);
+        if (choice != 1 && duc_fused_serves<K>(b.nf, b.Ls, osc.vco)) {
+            YG_TRY(b.w.ensure_dev(b.st));
+            YG_TRY((launch_duc_all<K>(b.w.dev(), x, b.taps.template as<C>(), b.nf, b.Ls, b.scale, y, n, b.st, b.w.next(),
+                                      osc.vco, osc.tab.p, osc.theta, osc.d_theta)));
+            b.w.flip();                             // the kernel's last workgroup wrote the next window
+            osc.theta += (uint32_t)nout * osc.d_theta;
+            last = 2;
+            return YAGI_OK;
+        }
+        YG_TRY(scratch.ensure(nout * sizeof(cf32)));
+        YG_TRY(fir.block_dev(x, n, scratch.as<cf32>()));
+        YG_TRY(osc.block_dev(scratch.as<cf32>(), nout, y, false));
+        last = 1;
+        return YAGI_OK;
+    }
+    // x -> y[I] on the host mirror: push, then every branch's sum (firinterp.rs:224-231) mixed up and stepped
+    int execute(const cf32 *x, cf32 *y) {
+        FirPfb<K> &b = fir.bank;
+        YG_TRY(b.w.ensure_host(b.st));
+        b.w.push(*x);
+        for (int i = 0; i < b.nf; ++i) {
+            const cf32 v = host_fir_window_dot<cf32, C>(b.w.host(), (size_t)b.Ls, b.hb.data() + (size_t)i * b.Ls, b.scale);
+            y[i] = osc_mix(osc.vco, osc.theta, false, v);
+            osc.theta += osc.d_theta;
+        }
+        return YAGI_OK;
+    }
+    Staging &staging() { return fir.bank.ws; }
+};
+
+template <class Q>
+static int ddc_block_host(Q *q, const cf32 *x, size_t n, cf32 *y) {
+    return q->staging().run(q->stream(), x, q->n_in(n), y, q->n_out(n),
+                            [&](const cf32 *xd, cf32 *yd) { return q->block_dev(xd, n, yd); });
+}
+
+// the Kaiser prototypes of the parts (firdecim.rs:70-87, firinterp.rs:73-90): same checks, same messages
+template <class C>
+static int ddc_kaiser_taps(bool interp, size_t M, size_t m, float as_, std::vector<C> &hc) {
+    if (M < 2) return fail(YAGI_ERR_CONFIG, interp ? "interp factor must be greater than 1" : "decim factor must be greater than 1");
+    if (m == 0) return fail(YAGI_ERR_CONFIG, "filter delay must be greater than 0");
+    if (as_ < 0.0f) return fail(YAGI_ERR_CONFIG, "stop-band attenuation must be positive");
+    std::vector<float> hf;
+    YG_TRY(design_kaiser(2 * M * m + 1, 0.5f / (float)M, as_, 0.0f, hf));
+    hc.resize(hf.size() - (interp ? 1 : 0));               // the interpolator drops the last tap (firinterp.rs:89)
+    for (size_t i = 0; i < hc.size(); ++i) hc[i] = to_c(hf[i], (C *)nullptr);
+    return YAGI_OK;
+}
+
+}  // namespace yagi
+
+// OBJ: ddc | duc; INTERP: 0 | 1; RATE: the name of the rate accessor
+#define YAGI_DDC_IMPL(OBJ, TMPL, INTERP, RATE, K, KT, C)                                                            \
+    struct yagi_hip_##OBJ##_##K##_s : TMPL<KT> {};                                                                  \
+    extern "C" {                                                                                                    \
+    int yagi_hip_##OBJ##_##K##_create(int scheme, size_t rate, const C *h, size_t h_len, yagi_hip_##OBJ##_##K *q) try { \
+        CHECK_PTR(q);                                                                                               \
+        *q = nullptr;                                                                                               \
+        if (h_len && !h) return fail(YAGI_ERR_CONFIG, "null pointer argument");                                     \
+        auto o = std::make_unique<yagi_hip_##OBJ##_##K##_s>();                                                      \
+        YG_TRY(o->init(scheme, rate, h, h_len));                                                                    \
+        *q = o.release();                                                                                           \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_create_kaiser(int scheme, size_t rate, size_t m, float as_,                          \
+                                             yagi_hip_##OBJ##_##K *q) try {                                         \
+        CHECK_PTR(q);                                                                                               \
+        *q = nullptr;                                                                                               \
+        YG_TRY(ddc_check_scheme(scheme));                                                                           \
+        std::vector<C> hc;                                                                                          \
+        YG_TRY(ddc_kaiser_taps<C>(INTERP, rate, m, as_, hc));                                                       \
+        return yagi_hip_##OBJ##_##K##_create(scheme, rate, hc.data(), hc.size(), q);                                \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_destroy(yagi_hip_##OBJ##_##K q) try {                                                \
+        if (q) (void)hipStreamSynchronize(q->stream());                                                             \
+        delete q;                                                                                                   \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_clone(yagi_hip_##OBJ##_##K q, yagi_hip_##OBJ##_##K *out) try {                       \
+        CHECK_Q(q);                                                                                                 \
+        CHECK_PTR(out);                                                                                             \
+        *out = nullptr;                                                                                             \
+        auto o = std::make_unique<yagi_hip_##OBJ##_##K##_s>();                                                      \
+        YG_TRY(o->clone_from(*q));                                                                                  \
+        *out = o.release();                                                                                         \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_set_stream(yagi_hip_##OBJ##_##K q, yagi_stream_t s) try {                            \
+        CHECK_Q(q);                                                                                                 \
+        if (q->stream() == to_stream(s)) return YAGI_OK;                                                            \
+        YG_HIP(hipStreamSynchronize(q->stream()));                                                                  \
+        q->stream() = to_stream(s);                                                                                 \
+        q->osc.st = to_stream(s);                                                                                   \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_reset(yagi_hip_##OBJ##_##K q) try {      /* the filter window; the oscillator stays */ \
+        CHECK_Q(q);                                                                                                 \
+        return q->window().reset(q->stream());                                                                      \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_set_frequency(yagi_hip_##OBJ##_##K q, float dtheta) try {                            \
+        CHECK_Q(q);                                                                                                 \
+        return osc_constrain(dtheta, &q->osc.d_theta);                                                              \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_adjust_frequency(yagi_hip_##OBJ##_##K q, float df) try {                             \
+        CHECK_Q(q);                                                                                                 \
+        uint32_t w = 0;                                                                                             \
+        YG_TRY(osc_constrain(df, &w));                                                                              \
+        q->osc.d_theta += w;                                                                                        \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_set_phase(yagi_hip_##OBJ##_##K q, float phi) try {                                   \
+        CHECK_Q(q);                                                                                                 \
+        return osc_constrain(phi, &q->osc.theta);                                                                   \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_adjust_phase(yagi_hip_##OBJ##_##K q, float dphi) try {                               \
+        CHECK_Q(q);                                                                                                 \
+        uint32_t w = 0;                                                                                             \
+        YG_TRY(osc_constrain(dphi, &w));                                                                            \
+        q->osc.theta += w;                                                                                          \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_get_frequency(yagi_hip_##OBJ##_##K q, float *f) try {                                \
+        CHECK_Q(q);                                                                                                 \
+        CHECK_PTR(f);                                                                                               \
+        *f = osc_frequency(q->osc.d_theta);                                                                         \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_get_phase(yagi_hip_##OBJ##_##K q, float *phi) try {                                  \
+        CHECK_Q(q);                                                                                                 \
+        CHECK_PTR(phi);                                                                                             \
+        *phi = osc_phase(q->osc.theta);                                                                             \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_get_state(yagi_hip_##OBJ##_##K q, uint32_t *theta, uint32_t *d_theta) try {          \
+        CHECK_Q(q);                                                                                                 \
+        CHECK_PTR(theta);                                                                                           \
+        CHECK_PTR(d_theta);                                                                                         \
+        *theta = q->osc.theta;                                                                                      \
+        *d_theta = q->osc.d_theta;                                                                                  \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_set_state(yagi_hip_##OBJ##_##K q, uint32_t theta, uint32_t d_theta) try {            \
+        CHECK_Q(q);                                                                                                 \
+        q->osc.theta = theta;                                                                                       \
+        q->osc.d_theta = d_theta;                                                                                   \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_set_scale(yagi_hip_##OBJ##_##K q, C scale) try {                                     \
+        CHECK_Q(q);                                                                                                 \
+        q->scale() = scale;                                                                                         \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_get_scale(yagi_hip_##OBJ##_##K q, C *scale) try {                                    \
+        CHECK_Q(q);                                                                                                 \
+        CHECK_PTR(scale);                                                                                           \
+        *scale = q->scale();                                                                                        \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_##RATE(yagi_hip_##OBJ##_##K q, size_t *rate) try {                                   \
+        CHECK_Q(q);                                                                                                 \
+        CHECK_PTR(rate);                                                                                            \
+        *rate = q->rate();                                                                                          \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_set_kernel(yagi_hip_##OBJ##_##K q, int choice) try {                                 \
+        CHECK_Q(q);                                                                                                 \
+        return q->set_kernel(choice);                                                                               \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_get_last_kernel(yagi_hip_##OBJ##_##K q, int *k) try {                                \
+        CHECK_Q(q);                                                                                                 \
+        CHECK_PTR(k);                                                                                               \
+        *k = q->last;                                                                                               \
+        return YAGI_OK;                                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_execute(yagi_hip_##OBJ##_##K q, const yagi_cf32 *x, yagi_cf32 *y) try {              \
+        CHECK_Q(q);                                                                                                 \
+        CHECK_PTR(x);                                                                                               \
+        CHECK_PTR(y);                                                                                               \
+        return q->execute(x, y);                                                                                    \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_execute_block(yagi_hip_##OBJ##_##K q, const yagi_cf32 *x, size_t n,                  \
+                                             yagi_cf32 *y) try {                                                    \
+        CHECK_Q(q);                                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                                 \
+        CHECK_PTR(x);                                                                                               \
+        CHECK_PTR(y);                                                                                               \
+        return ddc_block_host(q, x, n, y);                                                                          \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    int yagi_hip_##OBJ##_##K##_execute_block_dev(yagi_hip_##OBJ##_##K q, const yagi_cf32 *x, size_t n,              \
+                                                 yagi_cf32 *y) try {                                                \
+        CHECK_Q(q);                                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                                 \
+        CHECK_PTR(x);                                                                                               \
+        CHECK_PTR(y);                                                                                               \
+        CHECK_NOALIAS(x, q->n_in(n), y, q->n_out(n));                                                               \
+        return q->block_dev(x, n, y);                                                                               \
+    } catch (...) { return ::yagi::api_exception(); }                                                               \
+    }
+
+YAGI_DDC_IMPL(ddc, DdcObj, false, get_decim_rate, crcf, CRCF, float)
+YAGI_DDC_IMPL(ddc, DdcObj, false, get_decim_rate, cccf, CCCF, yagi_cf32)
+YAGI_DDC_IMPL(duc, DucObj, true, get_interp_rate, crcf, CRCF, float)
+YAGI_DDC_IMPL(duc, DucObj, true, get_interp_rate, cccf, CCCF, yagi_cf32)

@@ -14,124 +14,26 @@
 // ds_read) and one broadcast tap.  Algorithmic HBM traffic: sizeof(T)*(M + 1) bytes per output
 // (+ the (L-1)-sample halo per tile, which is L2-resident).  This is the general kernel (any
 // L, M, type); the crcf M=1 hot case has an MFMA version in fir_mfma.hip.
+//
+// The bodies of fir_block_kernel, fir_decim_consec_kernel and the two bank kernels, and the choice among them, live in
+// fir_bodies.hpp: ddc_kernels.hip runs the same bodies with an oscillator mix fused in.
 #include <type_traits>
 
 #include "devmath.hpp"
 #include <cstdlib>
 
+#include "fir_bodies.hpp"
 #include "kernels.hpp"
 
 namespace yagi {
 
-constexpr int kFirBlock = 256;
-constexpr int kFirR = 4;                         // outputs per lane
-constexpr size_t kFirLdsBudget = 48 * 1024;
-
-template <class T>
-__device__ __forceinline__ T load_stream(const T *__restrict__ win, const T *__restrict__ x,
-                                         long long idx, int L) {
-    return (idx < 0) ? win[L + idx] : x[idx];
-}
-
-// The state a Window<T> holds after the block (window.rs:77-85): new_win = last L samples of (win ++ x[0..n)).
-// Written by the LAST workgroup of the block's own kernel (reads only; `win_next` is the object's other window
-// buffer), which saves the separate 4-5 us window-update launch after every execute_block.
-template <class T>
-__device__ __forceinline__ void write_next_window(const T *__restrict__ win, const T *__restrict__ x, size_t n, int L,
-                                                  T *__restrict__ win_next) {
-    if (win_next == nullptr || blockIdx.x != gridDim.x - 1) return;
-    for (int j = threadIdx.x; j < L; j += blockDim.x) {
-        const size_t c = n + (size_t)j;            // index into win ++ x
-        win_next[j] = (c < (size_t)L) ? win[c] : x[c - (size_t)L];
-    }
-}
-
-// STAGE = span in LDS.  The span is stored de-interleaved by decimation phase, xs[phase][j] = X[base + j*M + phase]
-// (pitch P = ceil(span/M) + pad), so at tap k the 64 lanes of a wave -- 64 consecutive outputs, M samples
-// apart in the stream -- read 64 CONSECUTIVE LDS words of one phase row (with the plain layout a decimator
-// reads with a lane stride of M samples: 2M-way bank conflicts on ds_read_b64).  Taps come through the scalar
-// cache (k is wave-uniform): one LDS read and one FMA group per MAC.
 template <class K, bool STAGE>
 __global__ void __launch_bounds__(kFirBlock)
 fir_block_kernel(const typename K::T *__restrict__ win, const typename K::T *__restrict__ x,
                  const typename K::C *__restrict__ taps, int L, int M, typename K::C scale,
                  typename K::T *__restrict__ y, size_t ny, int tile, long long x_len,
                  typename K::T *__restrict__ win_next) {
-    using T = typename K::T;
-    using C = typename K::C;
-    extern __shared__ __align__(16) unsigned char smem[];
-    write_next_window(win, x, ny * (size_t)M, L, win_next);
-    const size_t o0 = (size_t)blockIdx.x * (size_t)tile;
-    const int nt = (int)((ny - o0) < (size_t)tile ? (ny - o0) : (size_t)tile);
-    const long long base = (long long)o0 * M - (L - 1);
-    const int span = (nt - 1) * M + L;
-    const int pitch = (((tile - 1) * M + L + M - 1) / M) | 1;          // odd: phase rows start on different banks
-
-    T *xs = reinterpret_cast<T *>(smem);
-    if (STAGE) {
-        // loads issued in batches before the LDS writes (devmath.hpp: batched_for)
-        if (base >= 0 && base + span <= x_len) {       // block-uniform: the whole span lies inside x
-            const T *src = x + base;
-            if (M == 1) {
-                batched_for<kFirBlock>(span, [&](int i) { return src[i]; }, [&](int i, T v) { xs[i] = v; });
-            } else {
-                batched_for<kFirBlock>(span, [&](int i) { return src[i]; }, [&](int i, T v) {
-                    const int j = i / M, ph = i - j * M;
-                    xs[ph * pitch + j] = v;
-                });
-            }
-        } else {
-            batched_for<kFirBlock>(span, [&](int i) { return load_stream(win, x, base + i, L); }, [&](int i, T v) {
-                const int j = i / M, ph = i - j * M;
-                xs[ph * pitch + j] = v;
-            });
-        }
-        __syncthreads();
-    }
-
-    T acc[kFirR];
-#pragma unroll
-    for (int r = 0; r < kFirR; ++r) acc[r] = zero_of<T>();
-
-    // newest sample of output o sits at span offset o*M + (L-1); tap k reads offset o*M + (L-1-k):
-    // phase (L-1-k) mod M, row index o + (L-1-k) div M.  Taps are fetched 8 at a time (one scalar load),
-    // a full tile (all 4 x 256 outputs exist) runs without per-output guards.
-    auto run = [&](auto full_tag) {
-        constexpr bool FULL = decltype(full_tag)::value;
-        int ph = (L - 1) % M, jq = (L - 1) / M;
-        auto tap = [&](C hk, int k) {
-            if (STAGE) {
-                const T *row = xs + ph * pitch + jq + threadIdx.x;
-#pragma unroll
-                for (int r = 0; r < kFirR; ++r)
-                    if (FULL || (int)threadIdx.x + r * kFirBlock < nt) acc[r] = mac(acc[r], row[r * kFirBlock], hk);
-                if (--ph < 0) { ph = M - 1; --jq; }
-            } else {
-#pragma unroll
-                for (int r = 0; r < kFirR; ++r) {
-                    const int o = threadIdx.x + r * kFirBlock;
-                    if (FULL || o < nt)
-                        acc[r] = mac(acc[r], load_stream(win, x, base + (long long)o * M + (L - 1) - k, L), hk);
-                }
-            }
-        };
-        int k = 0;
-        for (; k + 8 <= L; k += 8) {
-            C hk[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) hk[u] = taps[k + u];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) tap(hk[u], k + u);
-        }
-        for (; k < L; ++k) tap(taps[k], k);
-    };
-    if (nt == kFirR * kFirBlock) run(std::true_type{});
-    else run(std::false_type{});
-#pragma unroll
-    for (int r = 0; r < kFirR; ++r) {
-        const int o = threadIdx.x + r * kFirBlock;
-        if (o < nt) y[o0 + o] = mul(acc[r], scale);
-    }
+    fir_block_body<K, STAGE>(win, x, taps, L, M, scale, y, ny, tile, x_len, win_next, FirNoMix{});
 }
 
 // one chunk of eight samples of the rrrf body below (FULL: all eight inside d <= L-8; else wave-uniform guards)
@@ -221,7 +123,6 @@ __device__ __forceinline__ void fir_consec_rrrf_body(const float *xl, const floa
 // (the span reaches up to 7 samples further back); the taps past L are skipped, never multiplied, so a NaN in the
 // stream poisons exactly the outputs it poisons in the reference.  Taps come through the scalar cache 8 at a time.  Same sums in the same tap order as fir_block_kernel (bit-identical results).
 // ---------------------------------------------------------------------------------------------
-constexpr int kConsecR = 8, kConsecTile = 256 * kConsecR;
 __device__ __forceinline__ int consec_pad(int i) { return i + (i >> 3); }
 
 template <class K>
@@ -342,148 +243,13 @@ static int launch_fir_consec(const typename K::T *win, const typename K::T *x, c
     return YAGI_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Decimator (M >= 2) with the same register window, one decimation phase at a time: the taps of phase p are
-// h[L-1-p-M*i], i = 0.., and at step i output o reads row p of the phase-split span at index o + i -- so a lane
-// that owns 8 consecutive outputs slides an 8-sample window along the row, one LDS read per 8 MACs.  Rows carry
-// the 9/8 padding of fir_consec_kernel.  The sum runs phase by phase instead of in tap order (same products,
-// f32 rounding may differ from fir_block_kernel in the last bit; exact on integer data).  NT lanes per
-// workgroup (tile = 8*NT outputs) so that the M rows fit the LDS budget.
-// ---------------------------------------------------------------------------------------------
+// Decimator (M >= 2) with the same register window, one decimation phase at a time (fir_bodies.hpp)
 template <class K, int NT, int R>
 __global__ void __launch_bounds__(NT)
 fir_decim_consec_kernel(const typename K::T *__restrict__ win, const typename K::T *__restrict__ x,
                         const typename K::C *__restrict__ taps, int L, int M, typename K::C scale,
                         typename K::T *__restrict__ y, size_t ny, int pitch, typename K::T *__restrict__ win_next) {
-    using T = typename K::T;
-    using C = typename K::C;
-    constexpr int TILE = NT * R, LG = R == 8 ? 3 : 2;
-    static_assert(R == 8 || R == 4, "window of 4 or 8 samples");
-    extern __shared__ __align__(16) unsigned char smem[];
-    T *xs = reinterpret_cast<T *>(smem);
-    write_next_window(win, x, ny * (size_t)M, L, win_next);
-    const size_t o0 = (size_t)blockIdx.x * TILE;
-    const int nt = (int)((ny - o0) < (size_t)TILE ? (ny - o0) : (size_t)TILE);
-    const long long base = (long long)o0 * M - (L - 1);         // stream index of row 0, entry 0
-    const long long xlen = (long long)ny * M;
-    const int ni = (L + M - 1) / M;                              // steps of the longest row
-    const int total = (TILE + ni - 1) * M;                       // entries any (o, i) of a full tile can reach
-    // entry e = jj*M + ph; (jj, ph) advance by NT entries per trip without a division
-    const int djj = NT / M, dph = NT - djj * M;
-    int jj = (int)threadIdx.x / M, ph = (int)threadIdx.x - jj * M;
-    // eight loads per lane in flight before the LDS writes; (jj, ph) advance with the stores, in order
-    const bool inside = base >= 0 && base + total <= xlen;       // block-uniform: every entry lies inside x
-    // Interior tile, M a power of two with NT / M a multiple of R: the lane's decimation phase is fixed
-    // (ph = tid mod M) and its row index advances by NT / M per trip, so the LDS slot advances by a constant and the
-    // samples come through a buffer descriptor of exactly `total` entries (entries past it are range-checked away, never read):
-    // no address arithmetic per entry -- the generic staging below spent as many vector instructions as the taps.
-    const int lgM = 31 - __builtin_clz((unsigned)M);
-    const bool desc = inside && (unsigned long long)total * sizeof(T) < 0xffffffffull;
-    const bool fast = desc && (M & (M - 1)) == 0 && M <= NT && ((NT >> lgM) & (R - 1)) == 0;
-    if (desc && !fast) {
-        // any other M: the same descriptor loads, the (row, phase) of an entry advanced incrementally per trip
-        const __amdgpu_buffer_rsrc_t rx = make_rsrc(x + base, (unsigned)((size_t)total * sizeof(T)));
-        const unsigned vo = (unsigned)sizeof(T) * threadIdx.x;
-        for (int t0 = 0; t0 * NT < total; t0 += 8) {
-            T r[8];
-#pragma unroll
-            for (int it = 0; it < 8; ++it)
-                r[it] = buf_ld_t<T>(rx, vo + (unsigned)sizeof(T) * NT * (unsigned)(t0 + it), 0u);
-#pragma unroll
-            for (int it = 0; it < 8; ++it) {
-                if ((int)threadIdx.x + NT * (t0 + it) < total) xs[ph * pitch + jj + (jj >> LG)] = r[it];
-                jj += djj; ph += dph;
-                if (ph >= M) { ph -= M; ++jj; }
-            }
-        }
-    } else if (fast) {
-        const __amdgpu_buffer_rsrc_t rx = make_rsrc(x + base, (unsigned)((size_t)total * sizeof(T)));
-        const unsigned vo = (unsigned)sizeof(T) * threadIdx.x;
-        const int rows = NT >> lgM;                              // row entries per trip
-        const int sstride = rows + (rows >> LG);
-        const int jj0 = (int)threadIdx.x >> lgM;
-        T *dst = xs + ((int)threadIdx.x & (M - 1)) * pitch + jj0 + (jj0 >> LG);
-        for (int t0 = 0; t0 * NT < total; t0 += 8) {
-            T r[8];
-#pragma unroll
-            for (int it = 0; it < 8; ++it)       // the trip goes into the VGPR offset: that is the part the range check covers
-                r[it] = buf_ld_t<T>(rx, vo + (unsigned)sizeof(T) * NT * (unsigned)(t0 + it), 0u);
-            if ((t0 + 8) * NT <= total) {
-#pragma unroll
-                for (int it = 0; it < 8; ++it) dst[sstride * (t0 + it)] = r[it];
-            } else {
-#pragma unroll
-                for (int it = 0; it < 8; ++it)
-                    if ((int)threadIdx.x + NT * (t0 + it) < total) dst[sstride * (t0 + it)] = r[it];
-            }
-        }
-    } else
-    for (int e0 = threadIdx.x; e0 < total; e0 += 8 * NT) {
-        T r[8];
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int e = e0 + NT * it;
-            const long long idx = base + (e < total ? e : total - 1);
-            T v = zero_of<T>();
-            if (inside) v = x[idx];
-            else if (idx < 0) v = win[L + idx];
-            else if (idx < xlen) v = x[idx];
-            r[it] = v;
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            if (e0 + NT * it < total) xs[ph * pitch + jj + (jj >> LG)] = r[it];
-            jj += djj; ph += dph;
-            if (ph >= M) { ph -= M; ++jj; }
-        }
-    }
-    __syncthreads();
-    const int l = threadIdx.x;
-    T acc[R], w[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = zero_of<T>();
-    const int np_phases = M < L ? M : L;
-#pragma unroll 1
-    for (int ph = 0; ph < np_phases; ++ph) {
-        const int n_p = (L - 1 - ph) / M + 1;
-        const T *row = xs + ph * pitch + (R + 1) * l;            // slot of row index R l + q: (R+1) l + q + (q >> LG)
-        const C *tp = taps + (L - 1 - ph);                       // step i multiplies by tp[-M*i]
-#pragma unroll
-        for (int r = 0; r < R - 1; ++r) w[r] = row[r];           // w[(r + i) & (R-1)] = row entry R l + r + i
-        auto eight_steps = [&](int i0, auto full_tag) {
-            constexpr bool FULL = decltype(full_tag)::value;
-            C hk[R];
-#pragma unroll
-            for (int u = 0; u < R; ++u) {
-                const int i = (FULL || i0 + u < n_p) ? i0 + u : n_p - 1;
-                hk[u] = tp[-(long long)M * i];
-            }
-            const T *rb = row + i0 + (i0 >> LG);                 // i0 is a multiple of R
-#pragma unroll
-            for (int u = 0; u < R; ++u) {
-                w[(R - 1 + u) & (R - 1)] = rb[(R - 1 + u) + ((R - 1 + u) >> LG)];   // the window's new highest sample
-                if (FULL || i0 + u < n_p) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r) acc[r] = mac(acc[r], w[(r + u) & (R - 1)], hk[u]);
-                }
-            }
-        };
-        int i0 = 0;
-        for (; i0 + R <= n_p; i0 += R) eight_steps(i0, std::true_type{});
-        if (i0 < n_p) eight_steps(i0, std::false_type{});
-    }
-    const int o = R * l;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-        if (o + r < nt) y[o0 + o + r] = mul(acc[r], scale);
-}
-
-// row pitch of the decimator kernel: entries any step can touch (tile + steps rounded up to 8, + the 8 of the
-// last window refill), padded 9/8, odd so that the M rows start on different banks
-static inline int decim_consec_pitch(int tile, int L, int M, int R) {
-    const int ni = (L + M - 1) / M;
-    const int n = tile + ((ni + R - 1) & ~(R - 1)) + R;
-    return (n + n / R + 1) | 1;
+    fir_decim_consec_body<K, NT, R>(win, x, taps, L, M, scale, y, ny, pitch, win_next, FirNoMix{});
 }
 
 template <class K, int NT, int R>
@@ -508,55 +274,23 @@ int launch_fir_block(const typename K::T *win, const typename K::T *x, const typ
     using T = typename K::T;
     if (ny == 0) return YAGI_OK;
     if (L <= 0 || M <= 0) return fail(YAGI_ERR_INTERNAL, "fir_block: bad L/M");
-    // M = 1 with a block long enough to fill tiles, span within 48 KiB: the register-window kernel
-    if (M == 1 && ny >= 512 && ((size_t)(kConsecTile + L + 8) * 9 / 8 + 1) * sizeof(T) <= kFirLdsBudget && x_len == 0)
-        return launch_fir_consec<K>(win, x, taps, L, scale, y, ny, st, win_next);
-    // decimators: the same register window per decimation phase, with the widest workgroup whose M rows fit
-    // (pays once a phase has enough taps to amortise its window fill: 8-sample window from 32 taps per phase,
-    // 4-sample window with full 256-lane workgroups from 8; YAGI_HIP_DECIM_WINDOW_MIN_STEPS overrides the 8)
-    static const int min_steps = [] {
-        const char *e = getenv("YAGI_HIP_DECIM_WINDOW_MIN_STEPS");
-        return e ? atoi(e) : 8;
-    }();
-    if (M >= 2 && L >= M && L / M >= min_steps && ny >= 512 && x_len == 0) {
-        auto fits = [&](int nt, int r) {
-            return (size_t)M * decim_consec_pitch(nt * r, L, M, r) * sizeof(T) <= kFirLdsBudget;
-        };
-        const bool long_phase = L / M >= 32;
-        // short phases: measured wins for complex samples and for M <= 4 (rrrf M = 8, 16 taps per phase: the general
-        // kernel's 4-byte LDS reads are cheaper than eight window fills)
-        const bool short_ok = sizeof(T) == 8 || M <= 4;
-        if (long_phase && fits(256, 8)) return launch_fir_decim_consec<K, 256, 8>(win, x, taps, L, M, scale, y, ny, st, win_next);
-        if (long_phase || short_ok) {
-            if (fits(256, 4)) return launch_fir_decim_consec<K, 256, 4>(win, x, taps, L, M, scale, y, ny, st, win_next);
-            if (fits(128, 4)) return launch_fir_decim_consec<K, 128, 4>(win, x, taps, L, M, scale, y, ny, st, win_next);
-        }
-        if (long_phase && fits(64, 8)) return launch_fir_decim_consec<K, 64, 8>(win, x, taps, L, M, scale, y, ny, st, win_next);
-        if (long_phase && fits(64, 4)) return launch_fir_decim_consec<K, 64, 4>(win, x, taps, L, M, scale, y, ny, st, win_next);
+    const FirBlockPlan p = fir_block_plan(sizeof(T), L, M, ny, x_len);      // fir_bodies.hpp: thresholds and budgets
+    if (p.kind == kFirPlanConsec) return launch_fir_consec<K>(win, x, taps, L, scale, y, ny, st, win_next);
+    if (p.kind == kFirPlanDecim) {
+        if (p.nt == 256 && p.r == 8) return launch_fir_decim_consec<K, 256, 8>(win, x, taps, L, M, scale, y, ny, st, win_next);
+        if (p.nt == 256 && p.r == 4) return launch_fir_decim_consec<K, 256, 4>(win, x, taps, L, M, scale, y, ny, st, win_next);
+        if (p.nt == 128 && p.r == 4) return launch_fir_decim_consec<K, 128, 4>(win, x, taps, L, M, scale, y, ny, st, win_next);
+        if (p.nt == 64 && p.r == 8) return launch_fir_decim_consec<K, 64, 8>(win, x, taps, L, M, scale, y, ny, st, win_next);
+        return launch_fir_decim_consec<K, 64, 4>(win, x, taps, L, M, scale, y, ny, st, win_next);
     }
-    // largest tile (<= R*256 outputs) whose phase-split span fits the LDS budget
-    auto need = [&](int t) {
-        const size_t pitch = (size_t)((((long long)(t - 1) * M + L + M - 1) / M) | 1);
-        return (size_t)M * pitch * sizeof(T);
-    };
-    int tile = kFirR * kFirBlock;
-    bool stage = true;
-    while (tile >= 64 && need(tile) > kFirLdsBudget) tile /= 2;
-    size_t lds = 0;
-    if (tile < 64) {           // span too large for LDS staging: stream from L2/HBM
-        stage = false;
-        tile = kFirR * kFirBlock;
-    } else {
-        lds = need(tile);
-    }
-    const size_t nblk = (ny + tile - 1) / tile;
+    const size_t nblk = (ny + p.tile - 1) / p.tile;
     if (nblk > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "block too large");
     // x_len = samples readable at x (0 = unknown: the outputs' own span, ny*M)
     const long long xl = (long long)(x_len ? x_len : ny * (size_t)M);
-    if (stage)
-        fir_block_kernel<K, true><<<(unsigned)nblk, kFirBlock, lds, st>>>(win, x, taps, L, M, scale, y, ny, tile, xl, win_next);
+    if (p.kind == kFirPlanStaged)
+        fir_block_kernel<K, true><<<(unsigned)nblk, kFirBlock, p.lds, st>>>(win, x, taps, L, M, scale, y, ny, p.tile, xl, win_next);
     else
-        fir_block_kernel<K, false><<<(unsigned)nblk, kFirBlock, lds, st>>>(win, x, taps, L, M, scale, y, ny, tile, xl, win_next);
+        fir_block_kernel<K, false><<<(unsigned)nblk, kFirBlock, 0, st>>>(win, x, taps, L, M, scale, y, ny, p.tile, xl, win_next);
     YG_LAUNCH_CHECK();
     return YAGI_OK;
 }
@@ -565,94 +299,21 @@ template int launch_fir_block<RRRF>(const float *, const float *, const float *,
 template int launch_fir_block<CRCF>(const cf32 *, const cf32 *, const float *, int, int, float, cf32 *, size_t, hipStream_t, size_t, cf32 *);
 template int launch_fir_block<CCCF>(const cf32 *, const cf32 *, const cf32 *, int, int, cf32, cf32 *, size_t, hipStream_t, size_t, cf32 *);
 
-// ---------------------------------------------------------------------------------------------
-// polyphase bank, all branches per pushed sample (interpolator form):
-//   y[n*nf + i] = scale * sum_{k<Ls} hb[i][k] * X[n-k]
-// A workgroup owns TN consecutive input samples x all nf branches.  Samples + halo are staged
-// in LDS; branch taps are staged TRANSPOSED (hsT[k][i]) so the 64 lanes of a wave, which hold
-// 64 consecutive branches i, read consecutive LDS words; stores are coalesced along i.
-// Traffic: sizeof(T) read + nf*sizeof(T) written per input sample (write-bound).
-// ---------------------------------------------------------------------------------------------
-constexpr int kPfbTN = 64;
-
+// polyphase bank, all branches per pushed sample (interpolator form); the bodies are in fir_bodies.hpp
 template <class K, bool TAPS_LDS>
 __global__ void __launch_bounds__(256)
 firpfb_all_kernel(const typename K::T *__restrict__ win, const typename K::T *__restrict__ x,
                   const typename K::C *__restrict__ hb, int nf, int Ls, typename K::C scale,
                   typename K::T *__restrict__ y, size_t n, typename K::T *__restrict__ win_next) {
-    using T = typename K::T;
-    using C = typename K::C;
-    extern __shared__ __align__(16) unsigned char smem[];
-    T *xs = reinterpret_cast<T *>(smem);                       // kPfbTN + Ls - 1 samples
-    write_next_window(win, x, n, Ls, win_next);
-    C *hsT = reinterpret_cast<C *>(smem + ((size_t)(kPfbTN + Ls - 1) * sizeof(T) + 15) / 16 * 16);
-    const size_t n0 = (size_t)blockIdx.x * kPfbTN;
-    const int nt = (int)((n - n0) < (size_t)kPfbTN ? (n - n0) : (size_t)kPfbTN);
-    const long long base = (long long)n0 - (Ls - 1);
-    batched_for<256>(nt + Ls - 1, [&](int i) { return load_stream(win, x, base + i, Ls); }, [&](int i, T v) { xs[i] = v; });
-    if (TAPS_LDS)
-        for (int e = threadIdx.x; e < nf * Ls; e += 256) {
-            const int i = e / Ls, k = e - i * Ls;
-            hsT[k * nf + i] = hb[e];
-        }
-    __syncthreads();
-    const int total = nt * nf;
-    for (int e = threadIdx.x; e < total; e += 256) {
-        const int nl = e / nf, i = e - nl * nf;
-        T acc = zero_of<T>();
-        for (int k = 0; k < Ls; ++k) {
-            const C hk = TAPS_LDS ? hsT[k * nf + i] : hb[i * Ls + k];
-            acc = mac(acc, xs[nl + (Ls - 1) - k], hk);
-        }
-        y[(n0 + nl) * (size_t)nf + i] = mul(acc, scale);
-    }
+    firpfb_all_body<K, TAPS_LDS>(win, x, hb, nf, Ls, scale, y, n, win_next, FirNoMix{});
 }
 
-// Few branches (interpolators: nf = 2 .. 16): with a lane per (sample, branch) the 64 lanes of a wave share 64/nf
-// samples and nf taps -- two LDS reads per MAC and a tile of only 64 samples.  Here a lane owns ONE input sample
-// and walks the branches four at a time: one LDS read (consecutive across lanes) per 4 MACs, the taps through
-// the scalar cache (branch and tap index are wave-uniform), 256 samples per workgroup, and each lane stores 4
-// consecutive outputs.  Same tap order as firpfb_all_kernel.
 template <class K>
 __global__ void __launch_bounds__(256)
 firpfb_fewbranch_kernel(const typename K::T *__restrict__ win, const typename K::T *__restrict__ x,
                         const typename K::C *__restrict__ hb, int nf, int Ls, typename K::C scale,
                         typename K::T *__restrict__ y, size_t n, typename K::T *__restrict__ win_next) {
-    using T = typename K::T;
-    using C = typename K::C;
-    extern __shared__ __align__(16) unsigned char smem[];
-    T *xs = reinterpret_cast<T *>(smem);                       // 256 + Ls - 1 samples
-    write_next_window(win, x, n, Ls, win_next);
-    const size_t n0 = (size_t)blockIdx.x * 256;
-    const int nt = (int)((n - n0) < (size_t)256 ? (n - n0) : (size_t)256);
-    const long long base = (long long)n0 - (Ls - 1);
-    batched_for<256>(nt + Ls - 1, [&](int i) { return load_stream(win, x, base + i, Ls); }, [&](int i, T v) { xs[i] = v; });
-    __syncthreads();
-    const int nl = threadIdx.x;
-    if (nl >= nt) return;
-    const T *xr = xs + nl + (Ls - 1);                          // tap k reads xr[-k]
-    T *yo = y + (n0 + nl) * (size_t)nf;
-    int g0 = 0;
-    for (; g0 + 4 <= nf; g0 += 4) {
-        const C *h0 = hb + (size_t)g0 * Ls;
-        T acc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = zero_of<T>();
-#pragma unroll 4
-        for (int k = 0; k < Ls; ++k) {
-            const T sk = xr[-k];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = mac(acc[j], sk, h0[(size_t)j * Ls + k]);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) yo[g0 + j] = mul(acc[j], scale);
-    }
-    for (; g0 < nf; ++g0) {                                    // the last nf % 4 branches
-        const C *h0 = hb + (size_t)g0 * Ls;
-        T acc = zero_of<T>();
-        for (int k = 0; k < Ls; ++k) acc = mac(acc, xr[-k], h0[k]);
-        yo[g0] = mul(acc, scale);
-    }
+    firpfb_fewbranch_body<K>(win, x, hb, nf, Ls, scale, y, n, win_next, FirNoMix{});
 }
 
 template <class K>
@@ -662,24 +323,16 @@ int launch_firpfb_all(const typename K::T *win, const typename K::T *x, const ty
     using T = typename K::T;
     using C = typename K::C;
     if (n == 0) return YAGI_OK;
-    if (nf <= 16 && (size_t)(256 + Ls - 1) * sizeof(T) <= kFirLdsBudget) {
-        const size_t nblk = (n + 255) / 256;
-        if (nblk > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "block too large");
-        firpfb_fewbranch_kernel<K><<<(unsigned)nblk, 256, (size_t)(256 + Ls - 1) * sizeof(T), st>>>(win, x, hb, nf, Ls,
-                                                                                                   scale, y, n, win_next);
-        YG_LAUNCH_CHECK();
-        return YAGI_OK;
-    }
-    const size_t xs_bytes = ((size_t)(kPfbTN + Ls - 1) * sizeof(T) + 15) / 16 * 16;
-    if (xs_bytes > kFirLdsBudget) return fail(YAGI_ERR_CONFIG, "branch filters too long (%d taps)", Ls);
-    const size_t tap_bytes = (size_t)nf * Ls * sizeof(C);
-    const bool taps_lds = xs_bytes + tap_bytes <= kFirLdsBudget;
-    const size_t nblk = (n + kPfbTN - 1) / kPfbTN;
+    const FirPfbPlan p = firpfb_all_plan(sizeof(T), sizeof(C), nf, Ls);     // fir_bodies.hpp
+    if (p.kind == kPfbPlanNone) return fail(YAGI_ERR_CONFIG, "branch filters too long (%d taps)", Ls);
+    const size_t nblk = p.kind == kPfbPlanFew ? (n + 255) / 256 : (n + kPfbTN - 1) / kPfbTN;
     if (nblk > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "block too large");
-    if (taps_lds)
-        firpfb_all_kernel<K, true><<<(unsigned)nblk, 256, xs_bytes + tap_bytes, st>>>(win, x, hb, nf, Ls, scale, y, n, win_next);
+    if (p.kind == kPfbPlanFew)
+        firpfb_fewbranch_kernel<K><<<(unsigned)nblk, 256, p.lds, st>>>(win, x, hb, nf, Ls, scale, y, n, win_next);
+    else if (p.kind == kPfbPlanTapsLds)
+        firpfb_all_kernel<K, true><<<(unsigned)nblk, 256, p.lds, st>>>(win, x, hb, nf, Ls, scale, y, n, win_next);
     else
-        firpfb_all_kernel<K, false><<<(unsigned)nblk, 256, xs_bytes, st>>>(win, x, hb, nf, Ls, scale, y, n, win_next);
+        firpfb_all_kernel<K, false><<<(unsigned)nblk, 256, p.lds, st>>>(win, x, hb, nf, Ls, scale, y, n, win_next);
     YG_LAUNCH_CHECK();
     return YAGI_OK;
 }

@@ -300,6 +300,26 @@ constexpr int kOscWgPerCu = 2;     // persistent grid: 2 workgroups per CU
 int launch_osc_mix(int vco, bool down, const void *tab, uint32_t theta0, uint32_t dtheta, const cf32 *x, cf32 *y,
                    size_t n, hipStream_t st);
 
+// ---- ddc_kernels.hip -----------------------------------------------------------------------
+// Ddc: launch_fir_block (M >= 2) over x mixed down with theta0 + (u32)j dtheta at sample j, in one launch; win holds
+// mixed samples and win_next receives the mixed tail.  Duc: launch_firpfb_all with output j mixed up with
+// theta0 + (u32)j dtheta at its store.  K is CRCF or CCCF; vco / tab as for launch_osc_mix.  The *_serves predicates say
+// whether a fused kernel exists for the shape (same kernel choice as the plain launcher, span + table within 64 KiB
+// of LDS); the launchers fail where it does not, and the caller runs launch_osc_mix and the plain launcher instead.
+// Every output word equals that composition's.  x and y must not overlap and need 8-byte alignment only.
+template <class K>
+bool ddc_fused_serves(int L, int M, size_t ny, int vco);
+template <class K>
+int launch_ddc_block(const cf32 *win, const cf32 *x, const typename K::C *taps, int L, int M, typename K::C scale,
+                     cf32 *y, size_t ny, hipStream_t st, cf32 *win_next, int vco, const void *tab, uint32_t theta0,
+                     uint32_t dtheta);
+template <class K>
+bool duc_fused_serves(int nf, int Ls, int vco);
+template <class K>
+int launch_duc_all(const cf32 *win, const cf32 *x, const typename K::C *hb, int nf, int Ls, typename K::C scale,
+                   cf32 *y, size_t n, hipStream_t st, cf32 *win_next, int vco, const void *tab, uint32_t theta0,
+                   uint32_t dtheta);
+
 // ---- firhilb_kernels.hip -------------------------------------------------------------------
 // FirHilbertFilter (src/filter/fir/firhilb.rs) block calls on device buffers, n units (r2c: n real -> n complex; c2r:
 // n complex -> 2n real; decim: 2n real -> n complex; interp: n complex -> 2n real).  win: the four windows w0..w3 of

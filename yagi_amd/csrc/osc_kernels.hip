@@ -19,32 +19,13 @@
 #pragma clang fp contract(off)
 
 #include "kernels.hpp"
+#include "osc_mix.hpp"      // OscEntry, osc_one: shared with the fused kernels of ddc_kernels.hip
 
 namespace yagi {
 namespace {
 
 typedef float osc_v2f __attribute__((ext_vector_type(2)));
 typedef float osc_v4f __attribute__((ext_vector_type(4)));
-
-template <int VCO> struct OscEntry { using E = float2; };    // NCO {sin, cos}
-template <> struct OscEntry<1> { using E = float4; };          // VCO {v_sin, s_sin, v_cos, s_cos}
-
-template <int VCO, bool DOWN>
-__device__ __forceinline__ float2 osc_one(const typename OscEntry<VCO>::E *tab, uint32_t theta, float xr, float xi) {
-    float s, c;
-    if constexpr (!VCO) {
-        const float2 e = tab[(theta + (1u << 21)) >> 22];
-        s = e.x;
-        c = e.y;
-    } else {
-        const float4 e = tab[theta >> 22];
-        const float acc = (float)(theta & 0x3FFFFFu);
-        s = e.x + acc * e.y;
-        c = e.z + acc * e.w;
-    }
-    if (DOWN) s = -s;
-    return make_float2(xr * c - xi * s, xr * s + xi * c);
-}
 
 // SPL samples per load: 2 (16-byte loads and stores, x and y 16-byte aligned) or 1
 template <int VCO, bool DOWN, int SPL>
