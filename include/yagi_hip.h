@@ -755,6 +755,48 @@ int yagi_hip_firpfbch2_crcf_analyzer_execute_shard_dev(yagi_hip_firpfbch2_crcf q
 int yagi_hip_firpfbch2_crcf_assemble_dev(const yagi_cf32 *gathered_dev, size_t nsteps, size_t M,
                                          int nranks, yagi_cf32 *y_dev, yagi_stream_t s);
 
+/* ---- multichannel::firpfbchr: M channels spaced 1/M, one output per channel every P inputs --------------
+ * Absent from the reference like the two above (firpfbch is P = M, firpfbch2 is P = M/2); defined by closed forms
+ * ("FirPfbChr").  Real prototype h[0 .. 2*M*m), stream index t from 0, zero history, steps s = 0, 1, ...
+ * counted from the start of the stream and carried across calls (reset() clears histories and both counters):
+ *   analyzer:    one step = P inputs -> M outputs,
+ *                y_s[k] = (1/M) sum_{l < 2Mm} h[l] x[(s+1)P - 1 - l] exp(+j 2 pi k (l - sP) / M)
+ *   synthesizer: one step = M channel values -> P outputs,
+ *                y[t] = (P/M) sum_{r >= 0, (t mod P) + rP < 2Mm} h[(t mod P) + rP] V_{floor(t/P) - r}[t mod M],
+ *                V_s[b] = sum_k X_s[k] exp(+j 2 pi k b / M)
+ *   create_kaiser: h = kaiser(2Mm+1, 0.5/P, as_) * M / sum(h); create_kaiser_synthesizer: kaiser(2Mm+1, 0.5/M, as_)
+ *   * M / sum(h).  Analyzer then synthesizer returns the input delayed by 2Mm - P + 1 samples (-63 dB at M 16, P 12, m 8,
+ *   As 60).
+ * M >= 2, 1 <= P <= M, m >= 1, M <= 8192, m <= 2048, and a shape no launch can hold (M*m beyond the LDS) are
+ * YAGI_ERR_CONFIG at create, decided before a device is required.  The synthesizer's history (ceil(2Mm/P) - 1 steps of
+ * M values) is allocated by the first synthesizer call, which returns YAGI_ERR_CONFIG if it exceeds 2^23 values
+ * (M 4096, P 1: 8191 steps); the analyzer of such an object works.
+ * set_kernel: 0 auto, 1 the general analyzer kernel, 2 the column kernel (M in {64, 128, 256}, P a multiple of M/8,
+ * 2m <= 16; YAGI_ERR_CONFIG elsewhere); get_last_kernel: 1 or 2, what the last analyzer call ran (0 before the first).
+ * Non-finite input sample t: the general kernel poisons exactly the steps with 0 <= (s+1)P - 1 - t < 2Mm, every channel;
+ * the column kernel, built for 4 / 8 / 16 taps per branch with zero taps behind the 2m real ones, the steps with
+ * 0 <= (s+1)P - 1 - t < Pb*M within the call (the carried history is 2Mm - P samples).  A non-finite X_s[k] poisons
+ * exactly the synthesizer outputs sP .. sP + 2Mm - 1.  tests/test_gpu_chanr_nonfinite.py.
+ * The _dev forms take device pointers that must not overlap (YAGI_ERR_CONFIG) and run on the object's stream. */
+typedef struct yagi_hip_firpfbchr_crcf_s *yagi_hip_firpfbchr_crcf;
+int yagi_hip_firpfbchr_crcf_create(size_t M, size_t P, size_t m, const float *h, yagi_hip_firpfbchr_crcf *q);
+int yagi_hip_firpfbchr_crcf_create_kaiser(size_t M, size_t P, size_t m, float as_, yagi_hip_firpfbchr_crcf *q);
+int yagi_hip_firpfbchr_crcf_create_kaiser_synthesizer(size_t M, size_t P, size_t m, float as_,
+                                                      yagi_hip_firpfbchr_crcf *q);
+int yagi_hip_firpfbchr_crcf_destroy(yagi_hip_firpfbchr_crcf q);
+int yagi_hip_firpfbchr_crcf_set_stream(yagi_hip_firpfbchr_crcf q, yagi_stream_t s);
+int yagi_hip_firpfbchr_crcf_reset(yagi_hip_firpfbchr_crcf q);
+int yagi_hip_firpfbchr_crcf_set_kernel(yagi_hip_firpfbchr_crcf q, int choice);
+int yagi_hip_firpfbchr_crcf_get_last_kernel(yagi_hip_firpfbchr_crcf q, int *kernel);
+int yagi_hip_firpfbchr_crcf_analyzer_execute(yagi_hip_firpfbchr_crcf q, const yagi_cf32 *x,
+                                             size_t nsteps, yagi_cf32 *y);
+int yagi_hip_firpfbchr_crcf_analyzer_execute_dev(yagi_hip_firpfbchr_crcf q, const yagi_cf32 *x_dev,
+                                                 size_t nsteps, yagi_cf32 *y_dev);
+int yagi_hip_firpfbchr_crcf_synthesizer_execute(yagi_hip_firpfbchr_crcf q, const yagi_cf32 *x,
+                                                size_t nsteps, yagi_cf32 *y);
+int yagi_hip_firpfbchr_crcf_synthesizer_execute_dev(yagi_hip_firpfbchr_crcf q, const yagi_cf32 *x_dev,
+                                                    size_t nsteps, yagi_cf32 *y_dev);
+
 /* ---- multi-GPU: RCCL over xGMI (one process per GPU) ------------------------------------------
  * The reference has no distributed layer; the one exchange step of the hot path is the
  * firpfbch2 analyzer with its output sub-bands sharded over the GPUs of a node.

@@ -34,7 +34,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -2460,3 +2460,76 @@ class FirPfbCh2(_Handle):
     @staticmethod
     def assemble_dev(gathered_dev, nsteps, M, nranks, y_dev, stream=None):
         _check(lib.yagi_hip_firpfbch2_crcf_assemble_dev(_devptr(gathered_dev), nsteps, M, nranks, _devptr(y_dev), stream))
+
+
+class FirPfbChr(_Handle):
+    """Rational-oversampling channelizer: M channels spaced 1/M, each output once per P input samples (1 <= P <= M,
+    oversampling M/P), prototype h[0 : 2*M*m].  FirPfbCh is P = M, FirPfbCh2 is P = M/2 (include/yagi_hip.h has the
+    closed forms).  The analyzer takes P samples per step and gives M channel values; the synthesizer takes M channel
+    values per step and gives P samples.  Steps are counted from the start of the stream and carried across calls."""
+    _prefix = "yagi_hip_firpfbchr_crcf_"
+
+    def __init__(self, M, P, m, h):
+        h = _arr(h, np.float32)
+        if M >= 1 and m >= 1 and h.size < 2 * M * m:
+            raise ConfigError("prototype shorter than 2*M*m")
+        hd = C.c_void_p()
+        _check(lib.yagi_hip_firpfbchr_crcf_create(M, P, m, _ptr(h), C.byref(hd)))
+        self._h, self.M, self.P, self.m = hd, M, P, m
+
+    @classmethod
+    def _designed(cls, fn, M, P, m, as_):
+        self = object.__new__(cls)
+        hd = C.c_void_p()
+        _check(fn(M, P, m, as_, C.byref(hd)))
+        self._h, self.M, self.P, self.m = hd, M, P, m
+        return self
+
+    @classmethod
+    def new_kaiser(cls, M, P, m, as_):
+        """analyzer prototype kaiser(2Mm+1, 0.5/P, as_) scaled to sum M"""
+        return cls._designed(lib.yagi_hip_firpfbchr_crcf_create_kaiser, M, P, m, as_)
+
+    @classmethod
+    def new_kaiser_synthesizer(cls, M, P, m, as_):
+        """prototype of the matching synthesizer: kaiser(2Mm+1, 0.5/M, as_) scaled to sum M; new_kaiser's analyzer followed
+        by this synthesizer returns the input delayed by 2Mm - P + 1 samples"""
+        return cls._designed(lib.yagi_hip_firpfbchr_crcf_create_kaiser_synthesizer, M, P, m, as_)
+
+    def set_kernel(self, choice):
+        """analyzer: 0 auto, 1 the general kernel, 2 the column kernel (M in {64, 128, 256}, P a multiple of M/8,
+        2m <= 16; a ConfigError elsewhere)"""
+        _check(lib.yagi_hip_firpfbchr_crcf_set_kernel(self._h, choice))
+
+    def get_last_kernel(self):
+        """1 (general) or 2 (column): what the last analyzer call ran; 0 before the first"""
+        k = C.c_int()
+        _check(lib.yagi_hip_firpfbchr_crcf_get_last_kernel(self._h, C.byref(k)))
+        return k.value
+
+    def analyzer_execute(self, x):
+        x = _arr(x, np.complex64)
+        if x.size % self.P:
+            raise ConfigError("input must hold a whole number of P-sample steps")
+        ns = x.size // self.P
+        y = np.empty(ns * self.M, np.complex64)
+        _check(lib.yagi_hip_firpfbchr_crcf_analyzer_execute(self._h, _ptr(x), ns, _ptr(y)))
+        return y.reshape(ns, self.M)
+
+    def analyzer_execute_devptr(self, x_dev, nsteps, y_dev):
+        """x_dev: nsteps*P complex64 on the device, y_dev: nsteps*M, not overlapping (ConfigError), 8-byte aligned;
+        asynchronous on the object's stream (the C ABI's analyzer_execute_dev; named as Ddc.execute_block_devptr is)"""
+        _check(lib.yagi_hip_firpfbchr_crcf_analyzer_execute_dev(self._h, _devptr(x_dev), nsteps, _devptr(y_dev)))
+
+    def synthesizer_execute(self, X):
+        """X: steps of M channel samples ([nsteps, M] or flat) -> nsteps*P output samples"""
+        X = _arr(X, np.complex64)
+        if X.size % self.M:
+            raise ConfigError("input must hold a whole number of M-channel steps")
+        ns = X.size // self.M
+        y = np.empty(ns * self.P, np.complex64)
+        _check(lib.yagi_hip_firpfbchr_crcf_synthesizer_execute(self._h, _ptr(X), ns, _ptr(y)))
+        return y
+
+    def synthesizer_execute_devptr(self, x_dev, nsteps, y_dev):
+        _check(lib.yagi_hip_firpfbchr_crcf_synthesizer_execute_dev(self._h, _devptr(x_dev), nsteps, _devptr(y_dev)))

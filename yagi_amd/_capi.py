@@ -247,6 +247,19 @@ _sig("yagi_hip_firpfbch2_crcf_analyzer_execute_dev", vp, vp, sz, vp)
 _sig("yagi_hip_firpfbch2_crcf_analyzer_execute_shard_dev", vp, vp, sz, ci, ci, vp)
 _sig("yagi_hip_firpfbch2_crcf_assemble_dev", vp, sz, sz, ci, vp, vp)
 
+_sig("yagi_hip_firpfbchr_crcf_create", sz, sz, sz, vp, pvp)
+_sig("yagi_hip_firpfbchr_crcf_create_kaiser", sz, sz, sz, f32, pvp)
+_sig("yagi_hip_firpfbchr_crcf_create_kaiser_synthesizer", sz, sz, sz, f32, pvp)
+_sig("yagi_hip_firpfbchr_crcf_destroy", vp)
+_sig("yagi_hip_firpfbchr_crcf_set_stream", vp, vp)
+_sig("yagi_hip_firpfbchr_crcf_reset", vp)
+_sig("yagi_hip_firpfbchr_crcf_set_kernel", vp, ci)
+_sig("yagi_hip_firpfbchr_crcf_get_last_kernel", vp, C.POINTER(ci))
+_sig("yagi_hip_firpfbchr_crcf_analyzer_execute", vp, vp, sz, vp)
+_sig("yagi_hip_firpfbchr_crcf_analyzer_execute_dev", vp, vp, sz, vp)
+_sig("yagi_hip_firpfbchr_crcf_synthesizer_execute", vp, vp, sz, vp)
+_sig("yagi_hip_firpfbchr_crcf_synthesizer_execute_dev", vp, vp, sz, vp)
+
 # ---- multi-GPU (RCCL through the C ABI) ---------------------------------------------------------
 _sig("yagi_hip_comm_unique_id", vp)
 _sig("yagi_hip_comm_create", vp, ci, ci, pvp)

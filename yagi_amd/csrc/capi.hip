@@ -697,6 +697,29 @@ struct PfbCh2 {
     Staging ws;
     DevBuf shard, gathered;    // sharded analyzer: this rank's sub-bands, and every rank's ([rank][step][M/R] per chunk)
 };
+struct PfbChr {
+    hipStream_t st = nullptr;
+    int M = 0, P = 0, m = 0;
+    DevBuf h, tw;
+    DevWindow<cf32> hist;      // 2Mm - P samples
+    uint64_t step = 0;         // analyzer steps since the start of the stream: the commutator's rotation
+    DevWindow<cf32> syn_hist;  // synthesizer: the last ceil(2Mm/P) - 1 steps, inverse-transformed ([step][M]); allocated by
+    bool syn_ready = false;    // the first synthesizer call, so an analyzer-only object pays nothing for it
+    int syn_rows = 0;
+    // the synthesizer's state is limited here and not at create: its size says nothing about what the analyzer can hold
+    int prepare_synthesizer() {
+        if (syn_ready) return YAGI_OK;
+        if ((size_t)syn_rows * (size_t)M > ((size_t)1 << 23))
+            return fail(YAGI_ERR_CONFIG, "firpfbchr: synthesizer history of %d steps of %d channels is too large", syn_rows, M);
+        YG_TRY(syn_hist.init((int)((size_t)syn_rows * (size_t)M), st));
+        syn_ready = true;
+        return YAGI_OK;
+    }
+    uint64_t syn_step = 0;
+    DevBuf syn_v;              // the call's inverse transforms (chanr_kernels.hip: two launches)
+    int choice = 0, last = 0;  // set_kernel / get_last_kernel
+    Staging ws;
+};
 
 }  // namespace yagi
 
@@ -2627,6 +2650,136 @@ int yagi_hip_firpfbch2_crcf_assemble_dev(const yagi_cf32 *gathered, size_t nstep
     CHECK_PTR(gathered);
     CHECK_PTR(y);
     return launch_firpfbch2_assemble(gathered, nsteps, (int)M, nranks, y, to_stream(s));
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
+// ---- firpfbchr: M channels, P inputs per analyzer step (chanr_kernels.hip) -----------------------------
+struct yagi_hip_firpfbchr_crcf_s : PfbChr {};
+
+// argument errors first, before the device is required
+static int firpfbchr_check_args(size_t M, size_t P, size_t m) {
+    if (M < 2) return fail(YAGI_ERR_CONFIG, "number of channels must be at least 2");
+    if (P < 1 || P > M) return fail(YAGI_ERR_CONFIG, "decimation rate must be in [1, M]");
+    if (m < 1) return fail(YAGI_ERR_CONFIG, "filter semi-length must be at least 1");
+    if (M > 8192 || m > 2048) return fail(YAGI_ERR_CONFIG, "channelizer too large");
+    return firpfbchr_check_shape((int)M, (int)P, (int)m);
+}
+
+extern "C" {
+
+int yagi_hip_firpfbchr_crcf_create(size_t M, size_t P, size_t m, const float *h, yagi_hip_firpfbchr_crcf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    YG_TRY(firpfbchr_check_args(M, P, m));
+    CHECK_PTR(h);
+    YG_TRY(require_device());
+    auto o = std::make_unique<yagi_hip_firpfbchr_crcf_s>();
+    o->M = (int)M;
+    o->P = (int)P;
+    o->m = (int)m;
+    const size_t hl = 2 * M * m;
+    YG_TRY(fill(o->h, h, hl * sizeof(float), nullptr));
+    YG_TRY(make_twiddles((int)M, YAGI_FFT_FORWARD, o->tw));
+    YG_TRY(o->hist.init((int)(hl - P), nullptr));
+    o->syn_rows = (int)((hl + P - 1) / P - 1);                 // the history itself: prepare_synthesizer()
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+static int firpfbchr_create_designed(size_t M, size_t P, size_t m, float fc, float as_, yagi_hip_firpfbchr_crcf *q) {
+    CHECK_PTR(q);
+    *q = nullptr;
+    YG_TRY(firpfbchr_check_args(M, P, m));
+    std::vector<float> hf;
+    YG_TRY(design_kaiser(2 * M * m + 1, fc, std::fabs(as_), 0.0f, hf));
+    float hsum = 0.0f;                          // unit channel gain: sum(h) = M
+    for (float v : hf) hsum += v;
+    for (float &v : hf) v = v * (float)M / hsum;
+    return yagi_hip_firpfbchr_crcf_create(M, P, m, hf.data(), q);
+}
+// analyzer prototype kaiser(2Mm+1, 0.5/P, as): the channel keeps the whole band its output rate can carry
+int yagi_hip_firpfbchr_crcf_create_kaiser(size_t M, size_t P, size_t m, float as_, yagi_hip_firpfbchr_crcf *q) try {
+    return firpfbchr_create_designed(M, P, m, 0.5f / (float)(P ? P : 1), as_, q);
+} catch (...) { return ::yagi::api_exception(); }
+// prototype of the matching synthesizer: kaiser(2Mm+1, 0.5/M, as)
+int yagi_hip_firpfbchr_crcf_create_kaiser_synthesizer(size_t M, size_t P, size_t m, float as_, yagi_hip_firpfbchr_crcf *q) try {
+    return firpfbchr_create_designed(M, P, m, 0.5f / (float)(M ? M : 1), as_, q);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firpfbchr_crcf_destroy(yagi_hip_firpfbchr_crcf q) try { delete q; return YAGI_OK; } catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firpfbchr_crcf_set_stream(yagi_hip_firpfbchr_crcf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;      // unchanged: no host synchronisation
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firpfbchr_crcf_reset(yagi_hip_firpfbchr_crcf q) try {
+    CHECK_Q(q);
+    q->step = 0;
+    q->syn_step = 0;
+    YG_TRY(q->hist.reset(q->st));
+    return q->syn_ready ? q->syn_hist.reset(q->st) : YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firpfbchr_crcf_set_kernel(yagi_hip_firpfbchr_crcf q, int choice) try {
+    CHECK_Q(q);
+    if (choice < 0 || choice > 2) return fail(YAGI_ERR_CONFIG, "kernel choice must be 0 (auto), 1 (general) or 2 (column)");
+    if (choice == 2 && !firpfbchr_col_served(q->M, q->P, q->m))
+        return fail(YAGI_ERR_CONFIG, "firpfbchr: the column kernel serves M in {64,128,256}, P a multiple of M/8, 2m <= 16");
+    q->choice = choice;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firpfbchr_crcf_get_last_kernel(yagi_hip_firpfbchr_crcf q, int *k) try {
+    CHECK_Q(q);
+    CHECK_PTR(k);
+    *k = q->last;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firpfbchr_crcf_analyzer_execute_dev(yagi_hip_firpfbchr_crcf q, const yagi_cf32 *x, size_t nsteps, yagi_cf32 *y) try {
+    CHECK_Q(q);
+    if (nsteps == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    CHECK_NOALIAS(x, nsteps * (size_t)q->P, y, nsteps * (size_t)q->M);
+    int ran = 0;
+    YG_TRY(launch_firpfbchr(q->hist.dev(), q->hist.len, x, q->h.as<float>(), q->M, q->P, q->m, q->tw.as<cf32>(), q->step, y,
+                            nsteps, q->st, q->choice, &ran));
+    q->last = ran;
+    q->step += nsteps;
+    return q->hist.advance(x, nsteps * (size_t)q->P, q->st);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firpfbchr_crcf_analyzer_execute(yagi_hip_firpfbchr_crcf q, const yagi_cf32 *x, size_t nsteps, yagi_cf32 *y) try {
+    CHECK_Q(q);
+    if (nsteps == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    return q->ws.run(q->st, x, nsteps * (size_t)q->P, y, nsteps * (size_t)q->M, [&](const cf32 *xd, cf32 *yd) {
+        return yagi_hip_firpfbchr_crcf_analyzer_execute_dev(q, xd, nsteps, yd);
+    });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firpfbchr_crcf_synthesizer_execute_dev(yagi_hip_firpfbchr_crcf q, const yagi_cf32 *x, size_t nsteps, yagi_cf32 *y) try {
+    CHECK_Q(q);
+    if (nsteps == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    CHECK_NOALIAS(x, nsteps * (size_t)q->M, y, nsteps * (size_t)q->P);
+    YG_TRY(q->prepare_synthesizer());
+    const size_t nv = nsteps * (size_t)q->M;
+    YG_TRY(q->syn_v.ensure(nv * sizeof(cf32)));
+    cf32 *v = q->syn_v.as<cf32>();
+    YG_TRY(launch_firpfbchr_syn_transform(x, q->M, q->tw.as<cf32>(), v, nsteps, q->st));
+    YG_TRY(launch_firpfbchr_syn_combine(q->syn_hist.dev(), q->syn_rows, v, q->h.as<float>(), q->M, q->P, q->m, q->syn_step, y,
+                                        nsteps, q->st));
+    q->syn_step += nsteps;
+    return q->syn_hist.advance(v, nv, q->st);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_firpfbchr_crcf_synthesizer_execute(yagi_hip_firpfbchr_crcf q, const yagi_cf32 *x, size_t nsteps, yagi_cf32 *y) try {
+    CHECK_Q(q);
+    if (nsteps == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(y);
+    return q->ws.run(q->st, x, nsteps * (size_t)q->M, y, nsteps * (size_t)q->P, [&](const cf32 *xd, cf32 *yd) {
+        return yagi_hip_firpfbchr_crcf_synthesizer_execute_dev(q, xd, nsteps, yd);
+    });
 } catch (...) { return ::yagi::api_exception(); }
 
 }  // extern "C"

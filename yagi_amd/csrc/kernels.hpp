@@ -227,6 +227,22 @@ int launch_firpfbch2(const cf32 *hist, int hist_len, const cf32 *x, const float 
 int launch_firpfbch2_assemble(const cf32 *gathered, size_t nsteps, int M, int nranks, cf32 *y,
                               hipStream_t st);
 
+// ---- chanr_kernels.hip ---------------------------------------------------------------------
+// firpfbchr (M channels, P inputs per analyzer step, prototype h[0 : 2Mm]); closed forms at the top of the file.
+// YAGI_OK when the general kernels can hold (M, m) in LDS, YAGI_ERR_CONFIG otherwise (host arithmetic only).
+int firpfbchr_check_shape(int M, int P, int m);
+bool firpfbchr_col_served(int M, int P, int m);
+// analyzer: hist = the 2Mm - P samples before x[0], step0 = index of the first step in the stream (its rotation);
+// y = nsteps*M.  choice: 1 general, 2 column (an error where firpfbchr_col_served() is false); *ran = the kernel taken.
+int launch_firpfbchr(const cf32 *hist, int hist_len, const cf32 *x, const float *h, int M, int P, int m,
+                     const cf32 *twM, uint64_t step0, cf32 *y, size_t nsteps, hipStream_t st, int choice, int *ran);
+// synthesizer, first launch: v[s][b] = sum_k x[s][k] e^{+j 2 pi k b / M} for the nsteps steps of the call
+int launch_firpfbchr_syn_transform(const cf32 *x, int M, const cf32 *twM, cf32 *v, size_t nsteps, hipStream_t st);
+// second launch: y[t] = (P/M) sum_r h[t mod P + rP] v[floor(t/P) - r][(step0 P + t) mod M], t < nsteps*P; vhist = the
+// hist_rows = ceil(2Mm/P) - 1 transformed steps before the call
+int launch_firpfbchr_syn_combine(const cf32 *vhist, int hist_rows, const cf32 *v, const float *h, int M, int P, int m,
+                                 uint64_t step0, cf32 *y, size_t nsteps, hipStream_t st);
+
 // ---- iir_kernels.hip -----------------------------------------------------------------------
 // IirFilter (src/filter/iir/iirfilt.rs) as a chunked state scan.  The block is cut into chunks of T samples, one per
 // lane, 64 chunks per workgroup.  The state of S entries after a chunk is A^T s0 + z, z = the chunk's final state from
