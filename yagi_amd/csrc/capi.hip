@@ -20,6 +20,7 @@
 
 #include "kernels.hpp"
 #include "objstate.hpp"
+#include "stream_tables.hpp"
 
 namespace yagi {
 
@@ -213,8 +214,8 @@ struct FirFilt {
     DevBuf apack;              // crcf only, L <= 256: Toeplitz A-operand table of the MFMA kernel
     int Lm = 0;                // padded length of the MFMA form (0 = not available)
     DevBuf hfreq, twf, twb;    // crcf only, L <= 2049: FFT_4096{[h;0]} and both twiddle tables (fast convolution)
-    DevBuf gfft, gfft_s;       // crcf only, L <= 257: conj(DFT_512{reversed taps}) / 512 and its scaled copy (fast correction sum)
-    DevBuf hfreq_s;            // scale * hfreq for the frequency-domain stream kernel, rebuilt when the scale changes
+    DevBuf gfft, gfft_s;       // crcf only, L <= 257: conj(DFT_512{reversed taps}) / 512 and its scaled copy in the pair layout (fast correction sum)
+    DevBuf hfreq_s;            // scale * hfreq in the pair layout (stream_tables.hpp) for the frequency-domain stream kernel, rebuilt when the scale changes
     bool hfreq_s_valid = false;
     float hfreq_s_scale = 0.f;
     bool conv_ready = false;
@@ -445,19 +446,12 @@ static int make_twiddles(int n, int dir, DevBuf &buf, bool half_too = false) {
 
 // twiddle table of the 4096-point stream kernels: W_4096^m (m < 4096, forward) followed by six 256-entry rows the
 // frequency-domain kernels read with the lane index (coalesced, no gathers): rows 0-3 W^{t 2^k}, row 4 W^{(t&15)(t>>4)},
-// row 5 W_256^{(t&15)(t>>4)}
+// row 5 W_256^{(t&15)(t>>4)}.  Behind the rows the headline kernel's two paired tables (stream_tables.hpp): the six
+// row entries of lane t and wave 0's six transform twiddles of lane l, two by two for 16-byte loads -- copies of
+// entries above, so a kernel that reads them computes what it computed from the rows and the W_4096 gathers, bit for bit
 static int make_stream_twiddles(DevBuf &buf) {
-    std::vector<cf32> tab(4096 + 6 * 256);
-    auto W = [](unsigned m) {
-        const double a = -2.0 * M_PI * (double)(m & 4095u) / 4096.0;
-        return cf32{(float)std::cos(a), (float)std::sin(a)};
-    };
-    for (unsigned m = 0; m < 4096; ++m) tab[m] = W(m);
-    for (unsigned t = 0; t < 256; ++t) {
-        for (unsigned k = 0; k < 4; ++k) tab[4096 + 256 * k + t] = W(t << k);
-        tab[4096 + 1024 + t] = W((t & 15u) * (t >> 4));
-        tab[4096 + 1280 + t] = W(16u * (((t & 15u) * (t >> 4)) & 255u));
-    }
+    std::vector<cf32> tab(kStreamTabFloat2);
+    build_stream_twiddles(tab.data());      // stream_tables.hpp
     return fill(buf, tab.data(), tab.size() * sizeof(cf32), nullptr);
 }
 
@@ -2347,9 +2341,9 @@ int yagi_hip_firfft_crcf_execute_dev(yagi_hip_firfft_crcf q, const yagi_cf32 *x,
         YG_TRY(f.prepare_conv());
         if (!f.hfreq_s_valid || f.hfreq_s_scale != f.scale) {
             YG_TRY(f.hfreq_s.ensure(4096 * sizeof(cf32)));
-            YG_TRY(launch_scale_cf32(f.hfreq.as<cf32>(), f.scale, f.hfreq_s.as<cf32>(), 4096, f.st));
+            YG_TRY(launch_scale_cf32_pairs(f.hfreq.as<cf32>(), f.scale, f.hfreq_s.as<cf32>(), 256, 4096, f.st));
             YG_TRY(f.gfft_s.ensure(512 * sizeof(cf32)));
-            YG_TRY(launch_scale_cf32(f.gfft.as<cf32>(), f.scale, f.gfft_s.as<cf32>(), 512, f.st));
+            YG_TRY(launch_scale_cf32_pairs(f.gfft.as<cf32>(), f.scale, f.gfft_s.as<cf32>(), 64, 512, f.st));
             f.hfreq_s_valid = true;
             f.hfreq_s_scale = f.scale;
         }

@@ -203,6 +203,13 @@ __device__ __forceinline__ float2 buf_ld_aux(__amdgpu_buffer_rsrc_t r, unsigned 
     const v2u_t q = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, AUX);
     return make_float2(__uint_as_float(q.x), __uint_as_float(q.y));
 }
+// 16-byte load of two adjacent float2 table entries (cached like any table: no policy bits)
+typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void buf_ld_tab2(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float2 &a, float2 &b) {
+    const v4u_t q = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
+    a = make_float2(__uint_as_float(q.x), __uint_as_float(q.y));
+    b = make_float2(__uint_as_float(q.z), __uint_as_float(q.w));
+}
 template <int AUX>
 __device__ __forceinline__ void buf_st_aux(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float2 v) {
     v2u_t q;

@@ -3,6 +3,7 @@
 // src/fft/mod.rs:45-48).  One launch per block, 16 B of HBM traffic per input sample.
 #include "fft_core.hpp"
 #include "kernels.hpp"
+#include "stream_tables.hpp"
 
 namespace yagi {
 
@@ -28,12 +29,21 @@ namespace yagi {
 // the 16 rows a wave instruction touches sit on 16 distinct bank pairs), as immediate-offset ds_reads -- no address
 // arithmetic, no global gathers (15 gathers per pass had been the L1/TA bottleneck, 4 gathers + 11 products cost
 // 22 packed instructions per set).  The pass-1 set W_4096^{tc} keeps "four exact entries + products"; its four
-// entries W^{t 2^k} and the correction transform's W^{b'c} are rows of an auxiliary table indexed by the lane:
-// coalesced loads.
+// entries W^{t 2^k}, the correction transform's W^{b'c} and the lane's T entry are the lane's six constants.
+//
+// TABLES IN PAIRS (stream_tables.hpp).  Every per-lane constant of a frame -- those six, wave 0's six transform
+// twiddles W_512^{l,2l,4l}, W_64^{b',2b',4b'}, its eight entries of conj(DFT_512{g}), the lane's sixteen of FFT{h} --
+// is laid out so that lane t's entries 2p and 2p+1 sit side by side and the 16-byte loads of a wave are contiguous:
+// 18 sixteen-byte loads per frame and main lane + 7 on wave 0, each wave instruction 1 KiB = 8 lines, where there were
+// 22 + 14 eight-byte loads and, on wave 0, six GATHERS from W_4096 (tw[8l], tw[16l], tw[32l]: 64 to 256 bytes apart
+// per lane, ~180 lines a frame for 3 KiB of constants, on the serial section ahead of wave 0's frame loads).  The
+// entries are copies of what was read before: not a bit of the output changes.  In the bench context (alternating
+// processes, profiles/r14_notes.md): wave 0's and the lanes' six constants +2.3 % as 48/64-byte lane records, +4.2 %
+// as pairs together with the single LDS reads below (+0.8 %), FFT{h} in pairs a further +2.5 %: +6.8 % in all.
 //
 // LOADS AND STORES.  The frame's 32 eight-byte accesses per lane are buffer accesses: one VGPR byte offset, 2 KiB
 // steps in SGPR offsets (the flat form spent ~3 VALU + a carry-hazard nop on each).  Everything the head needs -- the
-// table row, wave 0's correction operands, the 16 frame loads -- is requested in one go before the first LDS write:
+// lane's T entry, wave 0's correction operands, the 16 frame loads -- is requested in one go before the first LDS write:
 // one memory round trip; wave 0's operands go out AHEAD of its frame loads (vmcnt retires in order), all of them plain
 // loads whose waits the compiler counts itself (no hand-counted s_waitcnt is left in this kernel).  The frame is read
 // once and the spectra are written once, so the frame loads bypass the CU's L1 (sc1: the tables the four resident
@@ -51,12 +61,26 @@ namespace yagi {
 // under the pipelined block calls that hide its uneven finish), the corrections of a block as a launch of their own,
 // FFT{h} / twiddle loads hoisted to the kernel head, the correction transform's two output factors as one gathered
 // table entry, a two-wave workgroup per frame, the triangle on the matrix pipe, barriers sunk below register-only
-// work, an L2 prefetch of a later frame, s_setprio over the head.
+// work, an L2 prefetch of a later frame, s_setprio over the head; and (profiles/r14_notes.md) the output as
+// v.FFT{h} + u in two packed FMAs after the correction transform -- 16 packed instructions and 10 VGPRs fewer, but the
+// FFT{h} loads then complete between the stores: -1.4 % alone, nothing beside the single LDS reads, and it changes the
+// rounding -- and the per-lane constants as 48- and 64-byte lane records (a wave's 16-byte load then touches 24 to 32
+// lines, not 8: 1.2 % behind the pairs).
 // ---------------------------------------------------------------------------------------------
 constexpr int kFreqMaxTaps = 257;
 constexpr unsigned kOffCvs = kFft4096LdsFloat2;          // c_f, 256 float2 (behind the exchange buffer)
 constexpr unsigned kOffT256 = kOffCvs + 256;             // T[b][c] = W_256^{bc}, 16 rows of 17 float2
 constexpr unsigned kFreqLdsFloat2 = kOffT256 + 16 * kTRow;   // 39 040 B -> 4 workgroups per CU
+
+// One 8-byte LDS read that stays ONE instruction.  Left as plain loads, the compiler pairs 78 of this kernel's 141
+// reads into 39 ds_read2_b64, which the LDS serves at half the rate of two ds_read_b64 (8 array cycles against 2 + 2,
+// 32-bank addressing against 64): the headline runs 0.8 % slower with them (profiles/r14_notes.md).  A relaxed,
+// workgroup-scope atomic load is the same ds_read_b64 -- no fence, no extra wait -- and is never merged.
+__device__ __forceinline__ float2 lds_rd(const float2 *p) {
+    const unsigned long long q = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+    return make_float2(__uint_as_float((unsigned)q), __uint_as_float((unsigned)(q >> 32)));
+}
 
 // passes 2 and 3 of the frame transform (exchange-1 data stored, a barrier ago), pass-2 twiddles W_256^{b'c'} = T[b'][c']
 __device__ __forceinline__ void freq_pass23(float2 (&v)[16], float2 *__restrict__ lds, const float2 *__restrict__ T) {
@@ -64,20 +88,20 @@ __device__ __forceinline__ void freq_pass23(float2 (&v)[16], float2 *__restrict_
     {
         const unsigned c = t >> 4, bp = t & 15;
 #pragma unroll
-        for (int a = 0; a < 16; ++a) v[a] = lds[c * kEx1Stride + 16 * a + bp];
+        for (int a = 0; a < 16; ++a) v[a] = lds_rd(&lds[c * kEx1Stride + 16 * a + bp]);
         __syncthreads();
         dft16<-1>(v);
 #pragma unroll
         for (int cp = 0; cp < 16; ++cp) {
             float2 u = v[dft16_pos(cp)];
-            if (cp) u = cmul(u, T[bp * kTRow + cp]);
+            if (cp) u = cmul(u, lds_rd(&T[bp * kTRow + cp]));
             lds[bp * kEx2Stride + cp * 16 + c] = u;
         }
     }
     __syncthreads();
     float2 w[16];
 #pragma unroll
-    for (int bp = 0; bp < 16; ++bp) w[bp] = lds[bp * kEx2Stride + t];
+    for (int bp = 0; bp < 16; ++bp) w[bp] = lds_rd(&lds[bp * kEx2Stride + t]);
     dft16<-1>(w);
 #pragma unroll
     for (int d = 0; d < 16; ++d) v[d] = w[dft16_pos(d)];
@@ -94,20 +118,20 @@ __device__ __forceinline__ void freq_head256(const float2 *__restrict__ xs, floa
                                              const float2 *__restrict__ T, float2 wbc) {
     const unsigned t = threadIdx.x;
     const unsigned c = t >> 4, bp = t & 15;
-    v[0] = xs[bp];
+    v[0] = lds_rd(&xs[bp]);
 #pragma unroll
-    for (int a = 1; a < 16; ++a) v[a] = cmul(xs[16 * a + bp], T[c * kTRow + a]);
+    for (int a = 1; a < 16; ++a) v[a] = cmul(lds_rd(&xs[16 * a + bp]), lds_rd(&T[c * kTRow + a]));
     dft16<-1>(v);
 #pragma unroll
     for (int cp = 0; cp < 16; ++cp) {
         float2 u = cmul(v[dft16_pos(cp)], wbc);
-        if (cp) u = cmul(u, T[bp * kTRow + cp]);
+        if (cp) u = cmul(u, lds_rd(&T[bp * kTRow + cp]));
         lds[bp * kEx2Stride + cp * 16 + c] = u;
     }
     __syncthreads();
     float2 w[16];
 #pragma unroll
-    for (int b = 0; b < 16; ++b) w[b] = lds[b * kEx2Stride + t];
+    for (int b = 0; b < 16; ++b) w[b] = lds_rd(&lds[b * kEx2Stride + t]);
     dft16<-1>(w);
 #pragma unroll
     for (int d = 0; d < 16; ++d) v[d] = w[dft16_pos(d)];
@@ -180,7 +204,7 @@ __device__ __forceinline__ void wave_fft512(const float2 (&v)[8], float2 (&X)[8]
     __builtin_amdgcn_wave_barrier();
     const unsigned c = l >> 3, bp = l & 7u;
 #pragma unroll
-    for (int a = 0; a < 8; ++a) r[a] = scr[c * kW512S1 + 8 * a + bp];
+    for (int a = 0; a < 8; ++a) r[a] = lds_rd(&scr[c * kW512S1 + 8 * a + bp]);
     dft8<SIGN, 8, 8>(r, z);
     {
         const float2 u3 = cmul(u1, u2), u5 = cmul(u4, u1), u6 = cmul(u4, u2), u7 = cmul(u4, u3);
@@ -191,7 +215,7 @@ __device__ __forceinline__ void wave_fft512(const float2 (&v)[8], float2 (&X)[8]
     }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int b = 0; b < 8; ++b) r[b] = scr[kW512Ex2 + b * kW512S2 + l];
+    for (int b = 0; b < 8; ++b) r[b] = lds_rd(&scr[kW512Ex2 + b * kW512S2 + l]);
     __builtin_amdgcn_wave_barrier();                 // the next transform's writes stay behind these reads
     dft8<SIGN, 8, NOUT>(r, X);
 }
@@ -216,11 +240,14 @@ __device__ __forceinline__ void freq_load_corr_fft(CorrOperands &o, const float2
         o.dp[a] = prev[mi];
         o.dq[a] = own[mi];
     }
-    o.w1 = tw[8u * l]; o.w2 = tw[16u * l]; o.w4 = tw[32u * l];
-    const unsigned bp = l & 7u;
-    o.u1 = tw[64u * bp]; o.u2 = tw[128u * bp]; o.u4 = tw[256u * bp];
+    // the lane's six twiddles and eight table entries, in pairs: seven 16-byte loads, 8 lines each
+    const __amdgpu_buffer_rsrc_t rc = make_rsrc(tw + kStreamTabCorr, 64u * 48u);
+    const __amdgpu_buffer_rsrc_t rg = make_rsrc(gfft, 64u * 64u);
+    buf_ld_tab2(rc, 16u * l, 0u, o.w1, o.w2);
+    buf_ld_tab2(rc, 16u * l, 1024u, o.w4, o.u1);
+    buf_ld_tab2(rc, 16u * l, 2048u, o.u2, o.u4);
 #pragma unroll
-    for (int d = 0; d < 8; ++d) o.gc[d] = gfft[l + 64u * d];
+    for (unsigned d = 0; d < 8; d += 2) buf_ld_tab2(rg, 16u * l, 512u * d, o.gc[d], o.gc[d + 1]);
 }
 // c_f[0 .. 256) -> cvs, by wave 0 (l = threadIdx.x < 64); scr = 1120 float2 of LDS nobody else touches meanwhile
 __device__ __forceinline__ void freq_correction_fft(const CorrOperands &o, int L, float2 *__restrict__ scr,
@@ -240,8 +267,9 @@ __device__ __forceinline__ void freq_correction_fft(const CorrOperands &o, int L
     for (int d = 0; d < 4; ++d) cvs[l + 64u * d] = (int)(64u * d + l) < Lc ? D[d] : make_float2(0.f, 0.f);
 }
 
-// The headline kernel.  hs = scale * FFT_4096{[h; 0]}; gfft = scale * conj(DFT_512{g}) / 512; tw = the stream twiddle
-// table (capi.hip make_stream_twiddles: W_4096^m, then rows W^{t 2^k} (k < 4), W^{(t&15)(t>>4)}, W_256^{(t&15)(t>>4)});
+// The headline kernel.  hs = scale * FFT_4096{[h; 0]} and gfft = scale * conj(DFT_512{g}) / 512, both in the pair layout
+// (launch_scale_cf32_pairs, 256 and 64 lanes); tw = the stream twiddle table (stream_tables.hpp: W_4096^m, the six
+// lane-indexed rows, then the rows in pairs at kStreamTabMain and wave 0's twiddles in pairs at kStreamTabCorr);
 // win = the L-sample filter window before the call, win_next receives the one after it (last L samples of x; null =
 // the caller produces it).
 __global__ void __launch_bounds__(256, 4)
@@ -252,11 +280,14 @@ firfft_crcf_4096_freq_kernel(const float2 *__restrict__ win, const float2 *__res
     __shared__ __attribute__((aligned(16))) float2 lds[kFreqLdsFloat2];
     float2 *cvs = lds + kOffCvs;
     const float2 *T = lds + kOffT256;
-    const float2 *ax = tw + 4096;
     const unsigned t = threadIdx.x, f = blockIdx.x;
     const bool wave0 = __builtin_amdgcn_readfirstlane(t >> 6) == 0;
     // ---- head: every load the frame needs, wave 0's correction operands first ----
-    const float2 tw_t = ax[1280 + t];
+    // the lane's six constants, three pairs 4 KiB apart: the correction transform's factor and the T entry now, the
+    // four pass-1 powers behind the head's barrier
+    const __amdgpu_buffer_rsrc_t rt = make_rsrc(tw + kStreamTabMain, 256u * 48u);
+    float2 wbc, tw_t;
+    buf_ld_tab2(rt, 16u * t, 8192u, wbc, tw_t);
     float2 v[16];
     CorrOperands co;
     if (wave0) freq_load_corr_fft(co, win, x, L, f, tw, gfft);
@@ -275,10 +306,13 @@ firfft_crcf_4096_freq_kernel(const float2 *__restrict__ win, const float2 *__res
     if (wave0) freq_correction_fft(co, L, lds, cvs);
     __syncthreads();                                  // c_f and T published; the exchange buffer is free
     // ---- frame transform ----
+    float2 p1, p2, p4, p8;
+    buf_ld_tab2(rt, 16u * t, 0u, p1, p2);
+    buf_ld_tab2(rt, 16u * t, 4096u, p4, p8);
     dft16<-1>(v);
     {
         float2 w[16];
-        twiddle_powers_from(w, ax[t], ax[256 + t], ax[512 + t], ax[768 + t]);
+        twiddle_powers_from(w, p1, p2, p4, p8);
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
             float2 z = v[dft16_pos(c)];
@@ -292,28 +326,30 @@ firfft_crcf_4096_freq_kernel(const float2 *__restrict__ win, const float2 *__res
         const __amdgpu_buffer_rsrc_t rh = make_rsrc(hs, 32768u);
         float2 hv[16];
 #pragma unroll
-        for (unsigned d = 0; d < 16; ++d) hv[d] = buf_ld_aux<0>(rh, 8u * t, 2048u * d);      // a table: cached
+        for (unsigned d = 0; d < 16; d += 2) buf_ld_tab2(rh, 16u * t, 2048u * d, hv[d], hv[d + 1]);   // a table: cached
 #pragma unroll
         for (unsigned d = 0; d < 16; ++d) v[d] = cmul(v[d], hv[d]);
     }
     // ---- correction transform, sum, store ----
     float2 u[16];
-    freq_head256(cvs, u, lds, T, ax[1024 + t]);
+    freq_head256(cvs, u, lds, T, wbc);
     const __amdgpu_buffer_rsrc_t ro = make_rsrc(out + (size_t)f * 4096, 32768u);
 #pragma unroll
     for (unsigned d = 0; d < 16; ++d)
         buf_st(ro, 8u * t, 2048u * d, make_float2(v[d].x + u[d].x, v[d].y + u[d].y));
 }
 
-__global__ void scale_cf32_kernel(const float2 *__restrict__ src, float s, float2 *__restrict__ dst, unsigned n) {
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = make_float2(src[i].x * s, src[i].y * s);
+// dst = s * src with entry l + lanes d in the slot lane l's 16-byte load d / 2 reads it from (stream_tables.hpp): the
+// scaled copies of FFT{h} (256 lanes) and of the correction sum's table (64 lanes) the stream kernel multiplies by
+__global__ void scale_cf32_pairs_kernel(const float2 *__restrict__ src, float s, float2 *__restrict__ dst, unsigned lanes,
+                                        unsigned n) {
+    const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) dst[stream_pair_slot(k % lanes, k / lanes, lanes)] = make_float2(src[k].x * s, src[k].y * s);
 }
-// dst[i] = s * src[i] (the scaled copy of FFT{h} the stream kernel multiplies by)
-int launch_scale_cf32(const cf32 *src, float s, cf32 *dst, size_t n, hipStream_t st) {
+int launch_scale_cf32_pairs(const cf32 *src, float s, cf32 *dst, unsigned lanes, size_t n, hipStream_t st) {
     if (n == 0) return YAGI_OK;
-    scale_cf32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const float2 *>(src), s,
-                                                                    reinterpret_cast<float2 *>(dst), (unsigned)n);
+    scale_cf32_pairs_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(reinterpret_cast<const float2 *>(src), s,
+                                                                          reinterpret_cast<float2 *>(dst), lanes, (unsigned)n);
     YG_LAUNCH_CHECK();
     return YAGI_OK;
 }
