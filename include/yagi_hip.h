@@ -542,6 +542,52 @@ int yagi_hip_firfilt_rrrf_set_kernel(yagi_hip_firfilt_rrrf q, int choice);
 int yagi_hip_firfilt_crcf_set_kernel(yagi_hip_firfilt_crcf q, int choice);
 int yagi_hip_firfilt_cccf_set_kernel(yagi_hip_firfilt_cccf q, int choice);
 
+/* ---- plan queries (diagnostics, like get_last_kernel: no reference counterpart) -----------------------------------
+ * What a block call of the FIR family would launch for a shape, answered by the very planner the launch calls.  Read-
+ * only host arithmetic: no device is needed or initialised, and YAGI_HIP_DECIM_WINDOW_MIN_STEPS is honoured as by the
+ * launch.  elem / coeff_elem = bytes per sample / per tap: 4 (real) or 8 (complex), so rrrf = (4, 4), crcf = (8, 4),
+ * cccf = (8, 8).  A bad argument is YAGI_ERR_CONFIG.  These describe the present kernels and may change with them.
+ *
+ *   plan_fir_block(elem, L, M, ny)        FirFilter kernel 1 (M = 1), FirDecimationFilter and Ddc's fused kernel: a
+ *                                         call of ny outputs, L taps, decimation M.  kind = YAGI_PLAN_FIR_*; DECIM
+ *                                         also sets nt (lanes per workgroup), r (outputs per lane) and staging
+ *                                         (YAGI_PLAN_STAGE_*, how a tile that lies wholly inside the call's input is
+ *                                         staged; tiles that touch the carried window or the end of the call stage
+ *                                         entry by entry).  tile = outputs per workgroup.
+ *   plan_firpfb_all(elem, coeff_elem, nf, Ls)   FirPfbFilter execute_all_dev, FirInterpolationFilter and Duc: nf
+ *                                         branches of Ls taps.  kind = YAGI_PLAN_PFB_*; tile = inputs per workgroup,
+ *                                         0 with YAGI_PLAN_PFB_NONE (the call itself returns YAGI_ERR_CONFIG).
+ *   plan_rresamp(elem, P, Q, Ls)          Rresamp: tile = primitive blocks (Q in, P out) per workgroup; YAGI_ERR_CONFIG
+ *                                         where the block call returns it (one block's span does not fit the LDS).
+ *   plan_resamp(elem, Ls, step)           Resamp: tile = outputs per workgroup for the 8.24 fixed-point step
+ *                                         round(2^24 / rate); YAGI_ERR_CONFIG where Ls + 1 samples do not fit.
+ *   lds = the launch's dynamic LDS in bytes (Ddc / Duc add the oscillator table behind it).
+ *   *_range: the same for `count` consecutive tap counts from L0 / Ls0 on into out[0 .. count); a shape that does not
+ *   fit is reported as tile = 0, never as an error. */
+#define YAGI_PLAN_FIR_CONSEC 0    /* M = 1 register-window kernel */
+#define YAGI_PLAN_FIR_DECIM 1     /* per-phase register-window decimator <nt, r> */
+#define YAGI_PLAN_FIR_STAGED 2    /* general kernel, span of `tile` outputs staged in LDS */
+#define YAGI_PLAN_FIR_UNSTAGED 3  /* general kernel reading the stream from L2 / HBM */
+#define YAGI_PLAN_PFB_FEW 0          /* <= 16 branches: a lane per input sample */
+#define YAGI_PLAN_PFB_TAPS_LDS 1     /* a lane per (sample, branch), taps transposed in LDS */
+#define YAGI_PLAN_PFB_TAPS_GLOBAL 2  /* the same, taps read from L1 / L2 */
+#define YAGI_PLAN_PFB_NONE 3
+#define YAGI_PLAN_STAGE_ELEMENT 0
+#define YAGI_PLAN_STAGE_DESCRIPTOR 1
+#define YAGI_PLAN_STAGE_POW2 2
+typedef struct {
+    int kind, nt, r, tile, staging;
+    size_t lds;
+} yagi_hip_plan;
+int yagi_hip_plan_fir_block(size_t elem, size_t L, size_t M, size_t ny, yagi_hip_plan *out);
+int yagi_hip_plan_firpfb_all(size_t elem, size_t coeff_elem, size_t nf, size_t Ls, yagi_hip_plan *out);
+int yagi_hip_plan_rresamp(size_t elem, size_t P, size_t Q, size_t Ls, yagi_hip_plan *out);
+int yagi_hip_plan_resamp(size_t elem, size_t Ls, uint32_t step, yagi_hip_plan *out);
+int yagi_hip_plan_fir_block_range(size_t elem, size_t L0, size_t count, size_t M, size_t ny, yagi_hip_plan *out);
+int yagi_hip_plan_firpfb_all_range(size_t elem, size_t coeff_elem, size_t nf, size_t Ls0, size_t count, yagi_hip_plan *out);
+int yagi_hip_plan_rresamp_range(size_t elem, size_t P, size_t Q, size_t Ls0, size_t count, yagi_hip_plan *out);
+int yagi_hip_plan_resamp_range(size_t elem, size_t Ls0, size_t count, uint32_t step, yagi_hip_plan *out);
+
 /* ---- Fft<f32>: src/fft/mod.rs:33-69 (arithmetic = rustfft 6.2 in the reference) ------------
  *   create       Fft::new(n, direction)        :39-43   any n >= 1 the engine supports
  *   run          run(input, output)            :45-48   out of place, unnormalised,

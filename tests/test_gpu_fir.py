@@ -334,7 +334,10 @@ def test_firdecim_random_vs_f64(ya, oracle, kind, M, L, n):
 def test_firdecim_register_window_kernel(ya, oracle, kind, M, L):
     """Blocks of >= 512 outputs with >= 8 taps per decimation phase take the per-phase register-window kernel
     (8- or 4-sample window, workgroups of 256 / 128 / 64 lanes by phase length and what fits the LDS;
-    YAGI_HIP_DECIM_WINDOW_MIN_STEPS=0 sends every shape here through it), the rest the general kernel; the
+    YAGI_HIP_DECIM_WINDOW_MIN_STEPS=0 sends every shape here through it), the rest the general kernel.  By the library's
+    plan query this list reaches <256, 8>, <256, 4> and <128, 4> with real samples (no 64-lane workgroup), and with
+    complex samples <256, 8>, <256, 4>, <128, 4> (power-of-two staging only) and <64, 4>, never <64, 8>;
+    tests/test_gpu_fir_plans.py runs every (lanes, window, staging) for every sample type.  The
     stream is cut at ragged places, a NaN placed in
     the input must poison exactly the outputs whose window holds it, and integers stay exact."""
     rng = np.random.default_rng(9000 + 37 * M + L)

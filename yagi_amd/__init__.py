@@ -35,6 +35,8 @@ __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
     "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "Plan", "plan_fir_block", "plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
+    "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
@@ -195,6 +197,67 @@ def firhilb_design(m, as_):
     hq = np.zeros(2 * max(int(m), 1), np.float32)
     _check(lib.yagi_hip_firhilb_design(m, as_, _ptr(hq)))
     return hq
+
+
+# ---- plan queries (diagnostics: what a FIR-family block call would launch; no device needed) ----
+Plan = collections.namedtuple("Plan", "kind nt r tile staging lds")
+PLAN_FIR_CONSEC, PLAN_FIR_DECIM, PLAN_FIR_STAGED, PLAN_FIR_UNSTAGED = range(4)
+PLAN_PFB_FEW, PLAN_PFB_TAPS_LDS, PLAN_PFB_TAPS_GLOBAL, PLAN_PFB_NONE = range(4)
+PLAN_STAGE_ELEMENT, PLAN_STAGE_DESCRIPTOR, PLAN_STAGE_POW2 = range(3)
+PLAN_DTYPE = np.dtype([("kind", "i4"), ("nt", "i4"), ("r", "i4"), ("tile", "i4"), ("staging", "i4"), ("lds", "u8")],
+                      align=True)
+assert PLAN_DTYPE.itemsize == C.sizeof(_capi.plan)
+
+
+def _plan(fn, *args):
+    p = _capi.plan()
+    _check(fn(*args, C.byref(p)))
+    return Plan(p.kind, p.nt, p.r, p.tile, p.staging, p.lds)
+
+
+def _plan_range(fn, count, *args):
+    out = np.zeros(int(count), PLAN_DTYPE)
+    _check(fn(*args, _ptr(out)))
+    return out
+
+
+def plan_fir_block(elem, L, M, ny):
+    """yagi_hip_plan_fir_block: FirFilter kernel 1 (M = 1), FirDecimationFilter, Ddc's fused kernel"""
+    return _plan(lib.yagi_hip_plan_fir_block, elem, L, M, ny)
+
+
+def plan_firpfb_all(elem, coeff_elem, nf, Ls):
+    """yagi_hip_plan_firpfb_all: FirPfbFilter.execute_all, FirInterpolationFilter, Duc"""
+    return _plan(lib.yagi_hip_plan_firpfb_all, elem, coeff_elem, nf, Ls)
+
+
+def plan_rresamp(elem, P, Q, Ls):
+    """yagi_hip_plan_rresamp: tile = primitive blocks per workgroup; ConfigError where the block call raises it"""
+    return _plan(lib.yagi_hip_plan_rresamp, elem, P, Q, Ls)
+
+
+def plan_resamp(elem, Ls, step):
+    """yagi_hip_plan_resamp: tile = outputs per workgroup; ConfigError where the branch length does not fit"""
+    return _plan(lib.yagi_hip_plan_resamp, elem, Ls, step)
+
+
+def plan_fir_block_range(elem, L0, count, M, ny):
+    """plans of L = L0 .. L0 + count - 1 as a PLAN_DTYPE array"""
+    return _plan_range(lib.yagi_hip_plan_fir_block_range, count, elem, L0, count, M, ny)
+
+
+def plan_firpfb_all_range(elem, coeff_elem, nf, Ls0, count):
+    return _plan_range(lib.yagi_hip_plan_firpfb_all_range, count, elem, coeff_elem, nf, Ls0, count)
+
+
+def plan_rresamp_range(elem, P, Q, Ls0, count):
+    """tile = 0 where the shape does not fit"""
+    return _plan_range(lib.yagi_hip_plan_rresamp_range, count, elem, P, Q, Ls0, count)
+
+
+def plan_resamp_range(elem, Ls0, count, step):
+    """tile = 0 where the shape does not fit"""
+    return _plan_range(lib.yagi_hip_plan_resamp_range, count, elem, Ls0, count, step)
 
 
 # ---- dotprod (trait DotProd, src/dotprod/mod.rs:13-73) ----------------------------------------

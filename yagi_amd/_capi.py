@@ -175,6 +175,21 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
 for _k in ("rrrf", "crcf", "cccf"):
     _sig(f"yagi_hip_firfilt_{_k}_set_kernel", vp, ci)
 
+class plan(C.Structure):
+    """yagi_hip_plan"""
+    _fields_ = [("kind", ci), ("nt", ci), ("r", ci), ("tile", ci), ("staging", ci), ("lds", sz)]
+
+
+_pplan = C.POINTER(plan)
+_sig("yagi_hip_plan_fir_block", sz, sz, sz, sz, _pplan)
+_sig("yagi_hip_plan_firpfb_all", sz, sz, sz, sz, _pplan)
+_sig("yagi_hip_plan_rresamp", sz, sz, sz, sz, _pplan)
+_sig("yagi_hip_plan_resamp", sz, sz, C.c_uint32, _pplan)
+_sig("yagi_hip_plan_fir_block_range", sz, sz, sz, sz, sz, vp)
+_sig("yagi_hip_plan_firpfb_all_range", sz, sz, sz, sz, sz, vp)
+_sig("yagi_hip_plan_rresamp_range", sz, sz, sz, sz, sz, vp)
+_sig("yagi_hip_plan_resamp_range", sz, sz, sz, C.c_uint32, vp)
+
 for _k, _T in (("cf", cf32), ("f", f32)):
     p = f"yagi_hip_spgram{_k}_"
     _sig(p + "create", sz, ci, sz, sz, pvp)

@@ -170,6 +170,7 @@ __device__ __forceinline__ void fir_decim_consec_body(const typename K::T *win,
     // (ph = tid mod M) and its row index advances by NT / M per trip, so the LDS slot advances by a constant and the
     // samples come through a buffer descriptor of exactly `total` entries (entries past it are range-checked away, never read):
     // no address arithmetic per entry -- the generic staging below spent as many vector instructions as the taps.
+    // (decim_interior_staging below repeats `desc` and `fast` for the plan queries: change the two together)
     const int lgM = 31 - __builtin_clz((unsigned)M);
     const bool desc = inside && (unsigned long long)total * sizeof(T) < 0xffffffffull;
     const bool fast = desc && (M & (M - 1)) == 0 && M <= NT && ((NT >> lgM) & (R - 1)) == 0;
@@ -303,6 +304,11 @@ inline int decim_window_min_steps() {
 
 // size of the M = 1 register-window kernel's span (fir_kernels.hip: kConsecTile outputs)
 constexpr int kConsecR = 8, kConsecTile = 256 * kConsecR;
+// its dynamic LDS: the tile + the taps rounded up to 8, padded 9/8
+inline size_t fir_consec_lds(size_t elem, int L) {
+    const int span = kConsecTile + ((L + 7) & ~7);
+    return (size_t)(span + (span >> 3) + 1) * elem;
+}
 
 inline FirBlockPlan fir_block_plan(size_t elem, int L, int M, size_t ny, size_t x_len) {
     FirBlockPlan p;
@@ -470,6 +476,62 @@ inline FirPfbPlan firpfb_all_plan(size_t elem, size_t celem, int nf, int Ls) {
         p.kind = kPfbPlanTapsGlobal;
         p.lds = xs_bytes;
     }
+    return p;
+}
+
+// How fir_decim_consec_body<K, nt, r> stages a tile whose whole span lies inside x (`inside` there; a tile that touches
+// the carried window or the end of the block always stages entry by entry): the body's `desc` and `fast`, repeated
+// here for the plan queries because the body's instruction stream is pinned -- change the two together.
+enum { kDecimStageElement = 0, kDecimStageDescriptor = 1, kDecimStagePow2 = 2 };
+inline int decim_interior_staging(size_t elem, int L, int M, int nt, int r) {
+    const int ni = (L + M - 1) / M;
+    const long long total = (long long)(nt * r + ni - 1) * M;
+    if (!((unsigned long long)total * elem < 0xffffffffull)) return kDecimStageElement;
+    const int lgM = 31 - __builtin_clz((unsigned)M);
+    const bool fast = (M & (M - 1)) == 0 && M <= nt && ((nt >> lgM) & (r - 1)) == 0;
+    return fast ? kDecimStagePow2 : kDecimStageDescriptor;
+}
+
+// blocks per tile of rresamp_kernel: ~1024 outputs or inputs, whichever is larger, inside the LDS budget;
+// tb = 0: even one block's span (Q + Ls - 1 samples) does not fit
+struct RresampPlan {
+    int tb = 0;
+    size_t lds = 0;
+};
+inline RresampPlan rresamp_plan(size_t elem, int P, int Q, int Ls) {
+    RresampPlan p;
+    const int big = P > Q ? P : Q;
+    int tb = 1024 / big;
+    if (tb < 1) tb = 1;
+    auto bytes = [&](int t) { return ((size_t)t * Q + Ls - 1) * elem; };
+    while (tb > 1 && bytes(tb) > kFirLdsBudget) tb /= 2;
+    if (bytes(tb) > kFirLdsBudget) return p;
+    p.tb = tb;
+    p.lds = bytes(tb);
+    return p;
+}
+
+// input span of `t` consecutive outputs of resamp_kernel, an upper bound over every starting phase
+inline uint64_t resamp_span(uint64_t t, uint32_t step, int Ls) {
+    return (((t - 1) * (uint64_t)step) >> 24) + 1 + (uint64_t)Ls;
+}
+// outputs per tile of resamp_kernel: up to 1024 (four per lane), fewer where 1/rate makes the input span outgrow the
+// LDS; tile = 0: one output's span (Ls + 1 samples) does not fit.  step > 0.
+struct ResampPlan {
+    int tile = 0;
+    size_t lds = 0;
+};
+inline ResampPlan resamp_plan(size_t elem, int Ls, uint32_t step) {
+    ResampPlan p;
+    const uint64_t cap = kFirLdsBudget / elem;
+    if (resamp_span(1, step, Ls) > cap) return p;
+    uint64_t tile = 1024;
+    const uint64_t room = cap - (uint64_t)Ls - 1;                       // >= 0 after the check above
+    const uint64_t fit = (((room + 1) << 24) - 1) / step + 1;           // largest t with ((t-1) step) >> 24 <= room
+    if (fit < tile) tile = fit;
+    while (tile > 1 && resamp_span(tile, step, Ls) > cap) --tile;
+    p.tile = (int)tile;
+    p.lds = (size_t)resamp_span(tile, step, Ls) * elem;
     return p;
 }
 

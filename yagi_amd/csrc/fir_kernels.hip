@@ -233,9 +233,7 @@ static int launch_fir_consec(const typename K::T *win, const typename K::T *x, c
                              typename K::C scale, typename K::T *y, size_t ny, hipStream_t st,
                              typename K::T *win_next) {
     using T = typename K::T;
-    const int Lp = (L + 7) & ~7;
-    const int span = kConsecTile + Lp;
-    const size_t lds = (size_t)(span + (span >> 3) + 1) * sizeof(T);
+    const size_t lds = fir_consec_lds(sizeof(T), L);
     const size_t nblk = (ny + kConsecTile - 1) / kConsecTile;
     if (nblk > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "block too large");
     fir_consec_kernel<K><<<(unsigned)nblk, 256, lds, st>>>(win, x, taps, L, scale, y, ny, win_next);
@@ -440,16 +438,11 @@ int launch_rresamp(const typename K::T *win, const typename K::T *x, const typen
                    typename K::T *win_next) {
     using T = typename K::T;
     if (nblocks == 0) return YAGI_OK;
-    // blocks per tile: ~1024 outputs or inputs, whichever is larger, inside the LDS budget
-    const int big = P > Q ? P : Q;
-    int tb = 1024 / big;
-    if (tb < 1) tb = 1;
-    auto bytes = [&](int t) { return ((size_t)t * Q + Ls - 1) * sizeof(T); };
-    while (tb > 1 && bytes(tb) > kFirLdsBudget) tb /= 2;
-    if (bytes(tb) > kFirLdsBudget) return fail(YAGI_ERR_CONFIG, "rresamp: Q and the branch length do not fit the LDS (%d, %d)", Q, Ls);
-    const size_t nblk = (nblocks + tb - 1) / tb;
+    const RresampPlan p = rresamp_plan(sizeof(T), P, Q, Ls);                // fir_bodies.hpp: blocks per tile
+    if (p.tb == 0) return fail(YAGI_ERR_CONFIG, "rresamp: Q and the branch length do not fit the LDS (%d, %d)", Q, Ls);
+    const size_t nblk = (nblocks + p.tb - 1) / p.tb;
     if (nblk > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "block too large");
-    rresamp_kernel<K><<<(unsigned)nblk, 256, bytes(tb), st>>>(win, x, hb, P, Q, Ls, scale, y, nblocks, tb, win_next);
+    rresamp_kernel<K><<<(unsigned)nblk, 256, p.lds, st>>>(win, x, hb, P, Q, Ls, scale, y, nblocks, p.tb, win_next);
     YG_LAUNCH_CHECK();
     return YAGI_OK;
 }
@@ -525,11 +518,6 @@ resamp_kernel(const typename K::T *__restrict__ win, const typename K::T *__rest
     }
 }
 
-// input span of `t` consecutive outputs, an upper bound over every starting phase
-static inline uint64_t resamp_span(uint64_t t, uint32_t step, int Ls) {
-    return (((t - 1) * (uint64_t)step) >> 24) + 1 + (uint64_t)Ls;
-}
-
 template <class K>
 int launch_resamp(const typename K::T *win, const typename K::T *x, const typename K::C *hb, int Ls, int bits,
                   uint32_t step, uint32_t p0, typename K::T *y, size_t ny, size_t nx, hipStream_t st,
@@ -537,18 +525,11 @@ int launch_resamp(const typename K::T *win, const typename K::T *x, const typena
     using T = typename K::T;
     if (ny == 0) return YAGI_OK;
     if (bits < 1 || bits > 16 || step == 0) return fail(YAGI_ERR_CONFIG, "resamp: bad schedule (bits %d, step %u)", bits, step);
-    // outputs per tile: up to 1024 (four per lane), fewer where 1/rate makes the input span outgrow the LDS
-    const uint64_t cap = kFirLdsBudget / sizeof(T);
-    if (resamp_span(1, step, Ls) > cap) return fail(YAGI_ERR_CONFIG, "resamp: branch length %d does not fit the LDS", Ls);
-    uint64_t tile = 1024;
-    const uint64_t room = cap - (uint64_t)Ls - 1;                       // >= 0 after the check above
-    const uint64_t fit = (((room + 1) << 24) - 1) / step + 1;           // largest t with ((t-1) step) >> 24 <= room
-    if (fit < tile) tile = fit;
-    while (tile > 1 && resamp_span(tile, step, Ls) > cap) --tile;
-    const size_t nblk = (ny + tile - 1) / tile;
+    const ResampPlan p = resamp_plan(sizeof(T), Ls, step);                  // fir_bodies.hpp: outputs per tile
+    if (p.tile == 0) return fail(YAGI_ERR_CONFIG, "resamp: branch length %d does not fit the LDS", Ls);
+    const size_t nblk = (ny + p.tile - 1) / p.tile;
     if (nblk > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "block too large");
-    const size_t lds = (size_t)resamp_span(tile, step, Ls) * sizeof(T);
-    resamp_kernel<K><<<(unsigned)nblk, 256, lds, st>>>(win, x, hb, Ls, bits, step, p0, y, ny, nx, (int)tile, win_next);
+    resamp_kernel<K><<<(unsigned)nblk, 256, p.lds, st>>>(win, x, hb, Ls, bits, step, p0, y, ny, nx, p.tile, win_next);
     YG_LAUNCH_CHECK();
     return YAGI_OK;
 }
@@ -556,4 +537,115 @@ template int launch_resamp<RRRF>(const float *, const float *, const float *, in
 template int launch_resamp<CRCF>(const cf32 *, const cf32 *, const float *, int, int, uint32_t, uint32_t, cf32 *, size_t, size_t, hipStream_t, cf32 *);
 template int launch_resamp<CCCF>(const cf32 *, const cf32 *, const cf32 *, int, int, uint32_t, uint32_t, cf32 *, size_t, size_t, hipStream_t, cf32 *);
 
+// ---------------------------------------------------------------------------------------------
+// Plan queries (include/yagi_hip.h, diagnostics): what the launchers above would run for a shape, from the planners
+// they call themselves.  Host arithmetic only, no device needed.  A shape that does not fit leaves tile = 0.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(kFirPlanConsec == YAGI_PLAN_FIR_CONSEC && kFirPlanDecim == YAGI_PLAN_FIR_DECIM &&
+                  kFirPlanStaged == YAGI_PLAN_FIR_STAGED && kFirPlanUnstaged == YAGI_PLAN_FIR_UNSTAGED &&
+                  kPfbPlanFew == YAGI_PLAN_PFB_FEW && kPfbPlanTapsLds == YAGI_PLAN_PFB_TAPS_LDS &&
+                  kPfbPlanTapsGlobal == YAGI_PLAN_PFB_TAPS_GLOBAL && kPfbPlanNone == YAGI_PLAN_PFB_NONE &&
+                  kDecimStageElement == YAGI_PLAN_STAGE_ELEMENT && kDecimStageDescriptor == YAGI_PLAN_STAGE_DESCRIPTOR &&
+                  kDecimStagePow2 == YAGI_PLAN_STAGE_POW2,
+              "the header's plan codes are the planners' enums");
+
+bool plan_elem_ok(size_t elem) { return elem == sizeof(float) || elem == sizeof(cf32); }
+
+yagi_hip_plan fir_block_plan_of(size_t elem, int L, int M, size_t ny) {
+    const FirBlockPlan p = fir_block_plan(elem, L, M, ny, 0);
+    yagi_hip_plan o{};
+    o.kind = p.kind;
+    o.nt = p.nt;
+    o.r = p.r;
+    o.tile = p.kind == kFirPlanConsec ? kConsecTile : p.kind == kFirPlanDecim ? p.nt * p.r : p.tile;
+    o.lds = p.lds;
+    if (p.kind == kFirPlanConsec) o.lds = fir_consec_lds(elem, L);
+    if (p.kind == kFirPlanDecim) o.staging = decim_interior_staging(elem, L, M, p.nt, p.r);
+    return o;
+}
+yagi_hip_plan firpfb_all_plan_of(size_t elem, size_t celem, int nf, int Ls) {
+    const FirPfbPlan p = firpfb_all_plan(elem, celem, nf, Ls);
+    yagi_hip_plan o{};
+    o.kind = p.kind;
+    o.tile = p.kind == kPfbPlanNone ? 0 : p.kind == kPfbPlanFew ? 256 : kPfbTN;
+    o.lds = p.lds;
+    return o;
+}
+yagi_hip_plan rresamp_plan_of(size_t elem, int P, int Q, int Ls) {
+    const RresampPlan p = rresamp_plan(elem, P, Q, Ls);
+    yagi_hip_plan o{};
+    o.tile = p.tb;
+    o.lds = p.lds;
+    return o;
+}
+yagi_hip_plan resamp_plan_of(size_t elem, int Ls, uint32_t step) {
+    const ResampPlan p = resamp_plan(elem, Ls, step);
+    yagi_hip_plan o{};
+    o.tile = p.tile;
+    o.lds = p.lds;
+    return o;
+}
+
+}  // namespace
 }  // namespace yagi
+
+using namespace yagi;
+
+#define PLAN_CHECK(cond, what)                                                                   \
+    do {                                                                                         \
+        if (!out) return fail(YAGI_ERR_CONFIG, "null pointer argument");                         \
+        if (!(cond)) return fail(YAGI_ERR_CONFIG, "plan query: bad " what);                      \
+    } while (0)
+
+extern "C" {
+
+int yagi_hip_plan_fir_block(size_t elem, size_t L, size_t M, size_t ny, yagi_hip_plan *out) try {
+    return yagi_hip_plan_fir_block_range(elem, L, 1, M, ny, out);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_plan_fir_block_range(size_t elem, size_t L0, size_t count, size_t M, size_t ny, yagi_hip_plan *out) try {
+    PLAN_CHECK(plan_elem_ok(elem) && L0 >= 1 && count <= (size_t)1 << 24 && L0 + count <= ((size_t)1 << 24) + 1 && M >= 1 && M <= (size_t)1 << 20 && ny >= 1,
+               "shape (elem 4 or 8, 1 <= L <= 2^24, 1 <= M <= 2^20, ny >= 1)");
+    for (size_t i = 0; i < count; ++i) out[i] = fir_block_plan_of(elem, (int)(L0 + i), (int)M, ny);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_plan_firpfb_all(size_t elem, size_t coeff_elem, size_t nf, size_t Ls, yagi_hip_plan *out) try {
+    return yagi_hip_plan_firpfb_all_range(elem, coeff_elem, nf, Ls, 1, out);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_plan_firpfb_all_range(size_t elem, size_t coeff_elem, size_t nf, size_t Ls0, size_t count,
+                                   yagi_hip_plan *out) try {
+    PLAN_CHECK(plan_elem_ok(elem) && plan_elem_ok(coeff_elem) && coeff_elem <= elem && nf >= 1 && nf <= (size_t)1 << 20 &&
+                   Ls0 >= 1 && count <= (size_t)1 << 24 && Ls0 + count <= ((size_t)1 << 20) + 1,
+               "shape (elem, coeff_elem 4 or 8, 1 <= nf, Ls <= 2^20)");
+    for (size_t i = 0; i < count; ++i) out[i] = firpfb_all_plan_of(elem, coeff_elem, (int)nf, (int)(Ls0 + i));
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_plan_rresamp(size_t elem, size_t P, size_t Q, size_t Ls, yagi_hip_plan *out) try {
+    YG_TRY(yagi_hip_plan_rresamp_range(elem, P, Q, Ls, 1, out));
+    if (out->tile == 0) return fail(YAGI_ERR_CONFIG, "rresamp: Q and the branch length do not fit the LDS (%zu, %zu)", Q, Ls);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_plan_rresamp_range(size_t elem, size_t P, size_t Q, size_t Ls0, size_t count, yagi_hip_plan *out) try {
+    PLAN_CHECK(plan_elem_ok(elem) && P >= 1 && P <= (size_t)1 << 15 && Q >= 1 && Q <= (size_t)1 << 15 && Ls0 >= 1 &&
+                   count <= (size_t)1 << 24 && Ls0 + count <= ((size_t)1 << 20) + 1,
+               "shape (elem 4 or 8, 1 <= P, Q <= 2^15, 1 <= Ls <= 2^20)");
+    for (size_t i = 0; i < count; ++i) out[i] = rresamp_plan_of(elem, (int)P, (int)Q, (int)(Ls0 + i));
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_plan_resamp(size_t elem, size_t Ls, uint32_t step, yagi_hip_plan *out) try {
+    YG_TRY(yagi_hip_plan_resamp_range(elem, Ls, 1, step, out));
+    if (out->tile == 0) return fail(YAGI_ERR_CONFIG, "resamp: branch length %zu does not fit the LDS", Ls);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_plan_resamp_range(size_t elem, size_t Ls0, size_t count, uint32_t step, yagi_hip_plan *out) try {
+    PLAN_CHECK(plan_elem_ok(elem) && Ls0 >= 1 && count <= (size_t)1 << 24 && Ls0 + count <= ((size_t)1 << 21) + 1 && step > 0,
+               "shape (elem 4 or 8, 1 <= Ls <= 2^21, step > 0)");
+    for (size_t i = 0; i < count; ++i) out[i] = resamp_plan_of(elem, (int)(Ls0 + i), step);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
