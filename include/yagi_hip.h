@@ -1446,6 +1446,52 @@ int yagi_hip_bsequence_push_correlate_block(yagi_hip_bsequence q, yagi_hip_bsequ
 int yagi_hip_bsequence_push_correlate_block_dev(yagi_hip_bsequence q, yagi_hip_bsequence ref, const uint8_t *sym_dev,
                                                 size_t n, unsigned bps, int32_t *rxy_dev);
 
+/* ---- Autocorr: sliding delay-conjugate correlator and window energy (src/filter/autocorr.rs is an empty file) ---------
+ * The reference declares the object and leaves it empty; this library defines it as a composition of the reference's
+ * buffer::Window and dotprod.  With X the stream since reset() and X[k] = 0 for k < 0, after
+ * sample n was pushed
+ *     w[i] = X[n - W + 1 + i],   v[i] = conj(X[n - W + 1 + i - d]),   i = 0 .. W-1
+ *     rxx[n]    = dotprod(w, v): the sequential sum over i from +0.0, every product and every add rounded on its own
+ *                 (no FMA), the complex product num-complex's (a.re b.re - a.im b.im, a.re b.im + a.im b.re)
+ *     energy[n] = sum over i, in the same order from +0.0, of fl(fl(w[i].re^2) + fl(w[i].im^2))   (rrrf: fl(w[i]^2))
+ * and every output word equals that composition bit for bit.  cccf = Complex<f32>, rrrf = f32 (conj is the identity).
+ *   create(window_size, delay)  1 <= window_size <= YAGI_AUTOCORR_WMAX and delay <= YAGI_AUTOCORR_DMAX, else
+ *                             YAGI_ERR_CONFIG (limits of this build: the device form's LDS tile, the carried history)
+ *   clone / reset             a copy of the state / the stream starts again (all history +0.0)
+ *   get_window_size / get_delay
+ *   push / write              on the host mirror, no launch
+ *   execute / get_energy      rxx and energy of the window as it stands, on the host mirror, no launch
+ *   execute_block(x, n, rxx, energy)      pushes n samples and writes rxx[i], energy[i] after each; host slices, staged
+ *                             through the device.  energy may be NULL.
+ *   execute_block_dev         the same on device buffers (x_dev, rxx_dev: n elements; energy_dev: n float or NULL),
+ *                             asynchronous on the object's stream.  The buffers MUST NOT OVERLAP (YAGI_ERR_CONFIG):
+ *                             a workgroup reads samples in front of its tile while another stores.  n = 0 is a no-op.
+ * The state is the last window_size + delay samples, carried on the device between block calls.
+ * Device form: autocorr_kernels.hip; a workgroup computes YAGI_AUTOCORR_TILE outputs. */
+#define YAGI_AUTOCORR_WMAX 1024
+#define YAGI_AUTOCORR_DMAX 65536
+#define YAGI_AUTOCORR_TILE 2048
+typedef struct yagi_hip_autocorr_cccf_s *yagi_hip_autocorr_cccf;
+typedef struct yagi_hip_autocorr_rrrf_s *yagi_hip_autocorr_rrrf;
+#define YAGI_AUTOCORR_API(K, T)                                                                                       \
+    int yagi_hip_autocorr_##K##_create(size_t window_size, size_t delay, yagi_hip_autocorr_##K *q);                    \
+    int yagi_hip_autocorr_##K##_destroy(yagi_hip_autocorr_##K q);                                                      \
+    int yagi_hip_autocorr_##K##_clone(yagi_hip_autocorr_##K q, yagi_hip_autocorr_##K *out);                            \
+    int yagi_hip_autocorr_##K##_set_stream(yagi_hip_autocorr_##K q, yagi_stream_t s);                                  \
+    int yagi_hip_autocorr_##K##_reset(yagi_hip_autocorr_##K q);                                                        \
+    int yagi_hip_autocorr_##K##_get_window_size(yagi_hip_autocorr_##K q, size_t *window_size);                         \
+    int yagi_hip_autocorr_##K##_get_delay(yagi_hip_autocorr_##K q, size_t *delay);                                     \
+    int yagi_hip_autocorr_##K##_push(yagi_hip_autocorr_##K q, T x);                                                    \
+    int yagi_hip_autocorr_##K##_write(yagi_hip_autocorr_##K q, const T *x, size_t n);                                  \
+    int yagi_hip_autocorr_##K##_execute(yagi_hip_autocorr_##K q, T *rxx);                                              \
+    int yagi_hip_autocorr_##K##_get_energy(yagi_hip_autocorr_##K q, float *energy);                                    \
+    int yagi_hip_autocorr_##K##_execute_block(yagi_hip_autocorr_##K q, const T *x, size_t n, T *rxx, float *energy);   \
+    int yagi_hip_autocorr_##K##_execute_block_dev(yagi_hip_autocorr_##K q, const T *x_dev, size_t n, T *rxx_dev,       \
+                                                  float *energy_dev);
+YAGI_AUTOCORR_API(cccf, yagi_cf32)
+YAGI_AUTOCORR_API(rrrf, float)
+#undef YAGI_AUTOCORR_API
+
 /* ---- design helper exposed for hosts that want the taps (kaiser.rs:16-51) ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);
 

@@ -16,6 +16,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     Osc, OscScheme             src/nco/osc.rs:13-201 (nco.rs, vco.rs)
     Modem, ModulationScheme    src/modem/modem.rs:27-575 (the linear schemes and from_table)
     MSequence / BSequence      src/sequence/msequence.rs:41-164, bsequence.rs:8-195
+    Autocorr                   (absent from the reference: src/filter/autocorr.rs is empty)
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -34,7 +35,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "plan_fir_block", "plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
@@ -1689,6 +1690,84 @@ class OrdFilt(_Handle):
     def execute_block_devptr(self, x_dev, n, y_dev):
         """x_dev, y_dev: n float32 on the device, not overlapping (ConfigError); asynchronous on the object's stream"""
         _check(lib.yagi_hip_ordfilt_rrrf_execute_block_dev(self._h, _devptr(x_dev), n, _devptr(y_dev)))
+
+
+AUTOCORR_WMAX = 1024     # YAGI_AUTOCORR_WMAX: the longest window of Autocorr
+AUTOCORR_DMAX = 65536    # YAGI_AUTOCORR_DMAX: the longest delay of Autocorr
+AUTOCORR_TILE = 2048     # YAGI_AUTOCORR_TILE: outputs per workgroup of autocorr_kernels.hip
+
+
+class Autocorr(_Handle):
+    """Autocorr<T>(window_size W, delay d), T = Complex<f32> ("cccf") or f32 ("rrrf"): after each sample n,
+    rxx[n] = sum_i X[n-W+1+i] conj(X[n-W+1+i-d]) and energy[n] = sum_i |X[n-W+1+i]|^2 over i = 0 .. W-1, X = 0 before the
+    stream starts.  The reference leaves the object empty (src/filter/autocorr.rs); it is defined here as its Window and
+    dotprod composed (yagi_hip.h): sequential f32 sums from +0.0, products and adds unfused, and
+    every output word equals that composition.  The per-sample calls run on the host; execute_block runs
+    autocorr_kernels.hip.  W <= AUTOCORR_WMAX, d <= AUTOCORR_DMAX."""
+
+    def __init__(self, kind, window_size, delay):
+        if kind not in ("cccf", "rrrf"):
+            raise ConfigError(f"unknown type combination {kind!r}")
+        self.kind = kind
+        self.T = KINDS[kind][0]
+        self._prefix = f"yagi_hip_autocorr_{kind}_"
+        hd = C.c_void_p()
+        _check(self._fn("create")(window_size, delay, C.byref(hd)))
+        self._h = hd
+
+    def clone(self):
+        new = object.__new__(type(self))
+        new.kind, new.T, new._prefix = self.kind, self.T, self._prefix
+        hd = C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._h = hd
+        return new
+
+    def _get(self, name):
+        v = C.c_size_t()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return v.value
+
+    @property
+    def window_size(self):
+        return self._get("get_window_size")
+
+    @property
+    def delay(self):
+        return self._get("get_delay")
+
+    def push(self, x):
+        _check(self._fn("push")(self._h, _byval(x, cf32 if self.kind == "cccf" else C.c_float)))
+
+    def write(self, x):
+        x = _arr(x, self.T)
+        _check(self._fn("write")(self._h, _ptr(x), x.size))
+
+    def execute(self):
+        """rxx of the window as it stands"""
+        y = np.zeros(1, self.T)
+        _check(self._fn("execute")(self._h, _ptr(y)))
+        return y[0]
+
+    def get_energy(self):
+        """the energy of the last window_size samples"""
+        e = C.c_float()
+        _check(self._fn("get_energy")(self._h, C.byref(e)))
+        return np.float32(e.value)
+
+    def execute_block(self, x, rxx=None, energy=False):
+        """pushes x and returns rxx after each sample, or (rxx, energy) where energy is True"""
+        x = _arr(x, self.T)
+        rxx = _out(rxx, x.size, self.T)
+        e = np.empty(x.size, np.float32) if energy else None
+        _check(self._fn("execute_block")(self._h, _ptr(x), x.size, _ptr(rxx), _ptr(e) if energy else None))
+        return (rxx, e) if energy else rxx
+
+    def execute_block_devptr(self, x_dev, n, rxx_dev, energy_dev=None):
+        """x_dev, rxx_dev: n samples on the device; energy_dev: n float32 or None.  The buffers must not overlap
+        (ConfigError); asynchronous on the object's stream"""
+        _check(self._fn("execute_block_dev")(self._h, _devptr(x_dev), n, _devptr(rxx_dev),
+                                             None if energy_dev is None else _devptr(energy_dev)))
 
 
 MSEQUENCE_TILE = 8192    # YAGI_MSEQUENCE_TILE: symbols per workgroup of the generator kernel

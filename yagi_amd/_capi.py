@@ -571,3 +571,20 @@ _sig(_p + "index", vp, sz, pcu)
 _sig(_p + "get_length", vp, C.POINTER(sz))
 for _n in ("push_correlate_block", "push_correlate_block_dev"):
     _sig(_p + _n, vp, vp, vp, sz, cu, vp)
+
+# ---- Autocorr ----------------------------------------------------------------------------------
+for _k, _T in (("cccf", cf32), ("rrrf", f32)):
+    _p = f"yagi_hip_autocorr_{_k}_"
+    _sig(_p + "create", sz, sz, pvp)
+    _sig(_p + "destroy", vp)
+    _sig(_p + "clone", vp, pvp)
+    _sig(_p + "set_stream", vp, vp)
+    _sig(_p + "reset", vp)
+    _sig(_p + "get_window_size", vp, C.POINTER(sz))
+    _sig(_p + "get_delay", vp, C.POINTER(sz))
+    _sig(_p + "push", vp, _T)
+    _sig(_p + "write", vp, vp, sz)
+    _sig(_p + "execute", vp, vp)
+    _sig(_p + "get_energy", vp, C.POINTER(f32))
+    _sig(_p + "execute_block", vp, vp, sz, vp, vp)
+    _sig(_p + "execute_block_dev", vp, vp, sz, vp, vp)

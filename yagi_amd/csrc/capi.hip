@@ -5935,6 +5935,189 @@ int yagi_hip_ordfilt_rrrf_execute_block_dev(yagi_hip_ordfilt_rrrf q, const float
 
 }  // extern "C"
 
+// ---- Autocorr (yagi_hip.h; src/filter/autocorr.rs is empty) ---------------------------------------------------------
+// The state is the last W + d samples, oldest first: the window w is its newest W, and conj of its oldest W is v.  The
+// per-sample calls run on a host mirror (autocorr_host, the kernel's arithmetic); block calls run autocorr_kernels.hip on
+// the device copy, whose launch writes the history it leaves into the other of two buffers.  The two copies are
+// synchronised lazily (Mirror).
+namespace yagi {
+
+template <class T>
+struct AutocorrObj {
+    hipStream_t st = nullptr;
+    int W = 0, d = 0;
+    FdHist<T> win;                                        // host mirror
+    PingPong<> hist;                                      // device copy, W + d samples
+    Staging ws;
+    DevBuf we;                                            // host block form: the energies on the device
+    Mirror mirror;
+
+    size_t len() const { return (size_t)W + (size_t)d; }
+    size_t bytes() const { return len() * sizeof(T); }
+    int init(size_t W_, size_t d_) {
+        if (W_ == 0) return fail(YAGI_ERR_CONFIG, "window size must be greater than zero");
+        if (W_ > (size_t)YAGI_AUTOCORR_WMAX)
+            return fail(YAGI_ERR_CONFIG, "window size %zu exceeds YAGI_AUTOCORR_WMAX = %d", W_, YAGI_AUTOCORR_WMAX);
+        if (d_ > (size_t)YAGI_AUTOCORR_DMAX)
+            return fail(YAGI_ERR_CONFIG, "delay %zu exceeds YAGI_AUTOCORR_DMAX = %d", d_, YAGI_AUTOCORR_DMAX);
+        YG_TRY(require_device());
+        W = (int)W_;
+        d = (int)d_;
+        YG_TRY(hist.alloc(bytes()));
+        win.init(len());
+        return reset();
+    }
+    int reset() {
+        win.zero();
+        YG_HIP(hipMemsetAsync(hist.cur(), 0, bytes(), st));
+        mirror.in_sync();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] {
+            std::vector<T> t(len());
+            YG_TRY(download(t.data(), hist.cur(), bytes(), st));
+            win.load(t.data());
+            return (int)YAGI_OK;
+        });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] { return upload(hist.cur(), win.data(), bytes(), st); });
+    }
+    int enter_host() {
+        YG_TRY(ensure_host());
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    void execute(T *rxx, float *energy) { autocorr_host<T>(win.data(), W, d, rxx, energy); }   // after ensure_host
+    int block_dev(const T *x, size_t nb, T *rxx, float *energy) {
+        if (nb == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        YG_TRY(launch_autocorr<T>(W, d, hist.cur<T>(), hist.next<T>(), x, nb, rxx, energy, st));
+        hist.flip();
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+};
+
+}  // namespace yagi
+
+#define YAGI_AUTOCORR_IMPL(K, T)                                                                    \
+    struct yagi_hip_autocorr_##K##_s : AutocorrObj<T> {};                                           \
+    extern "C" {                                                                                    \
+    int yagi_hip_autocorr_##K##_create(size_t window_size, size_t delay, yagi_hip_autocorr_##K *q) try { \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        auto o = std::make_unique<yagi_hip_autocorr_##K##_s>();                                     \
+        YG_TRY(o->init(window_size, delay));                                                        \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_destroy(yagi_hip_autocorr_##K q) try {                              \
+        if (q) (void)hipStreamSynchronize(q->st);                                                   \
+        delete q;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_clone(yagi_hip_autocorr_##K q, yagi_hip_autocorr_##K *out) try {    \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = nullptr;                                                                             \
+        YG_TRY(q->ensure_host());                                                                   \
+        auto o = std::make_unique<yagi_hip_autocorr_##K##_s>();                                     \
+        o->st = q->st;                                                                              \
+        o->W = q->W;                                                                                \
+        o->d = q->d;                                                                                \
+        YG_TRY(o->hist.alloc(o->bytes()));                                                          \
+        o->win.init(o->len());                                                                      \
+        o->win.load(q->win.data());                                                                 \
+        o->mirror.host_written();                                                                   \
+        *out = o.release();                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_set_stream(yagi_hip_autocorr_##K q, yagi_stream_t s) try {          \
+        CHECK_Q(q);                                                                                 \
+        if (q->st == to_stream(s)) return YAGI_OK;                                                  \
+        YG_HIP(hipStreamSynchronize(q->st));                                                        \
+        q->st = to_stream(s);                                                                       \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_reset(yagi_hip_autocorr_##K q) try {                                \
+        CHECK_Q(q);                                                                                 \
+        return q->reset();                                                                          \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_get_window_size(yagi_hip_autocorr_##K q, size_t *window_size) try { \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(window_size);                                                                     \
+        *window_size = (size_t)q->W;                                                                \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_get_delay(yagi_hip_autocorr_##K q, size_t *delay) try {             \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(delay);                                                                           \
+        *delay = (size_t)q->d;                                                                      \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_push(yagi_hip_autocorr_##K q, T x) try {                            \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(q->enter_host());                                                                    \
+        q->win.push(x);                                                                             \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_write(yagi_hip_autocorr_##K q, const T *x, size_t n) try {          \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x);                                                                               \
+        YG_TRY(q->enter_host());                                                                    \
+        for (size_t i = 0; i < n; ++i) q->win.push(x[i]);                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_execute(yagi_hip_autocorr_##K q, T *rxx) try {                      \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(rxx);                                                                             \
+        YG_TRY(q->ensure_host());                                                                   \
+        float e;                                                                                    \
+        q->execute(rxx, &e);                                                                        \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_get_energy(yagi_hip_autocorr_##K q, float *energy) try {            \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(energy);                                                                          \
+        YG_TRY(q->ensure_host());                                                                   \
+        T r;                                                                                        \
+        q->execute(&r, energy);                                                                     \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_execute_block(yagi_hip_autocorr_##K q, const T *x, size_t n, T *rxx, \
+                                              float *energy) try {                                  \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x);                                                                               \
+        CHECK_PTR(rxx);                                                                             \
+        if (energy) YG_TRY(q->we.ensure(n * sizeof(float)));                                        \
+        float *ed = energy ? q->we.as<float>() : nullptr;                                           \
+        YG_TRY(q->ws.run(q->st, x, n, rxx, n, [&](const T *xd, T *yd) { return q->block_dev(xd, n, yd, ed); })); \
+        if (energy) YG_TRY(download(energy, ed, n * sizeof(float), q->st));                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_autocorr_##K##_execute_block_dev(yagi_hip_autocorr_##K q, const T *x_dev, size_t n, T *rxx_dev, \
+                                                  float *energy_dev) try {                          \
+        CHECK_Q(q);                                                                                 \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x_dev);                                                                           \
+        CHECK_PTR(rxx_dev);                                                                         \
+        CHECK_NOALIAS(x_dev, n, rxx_dev, n);                                                        \
+        if (energy_dev) {                                                                           \
+            CHECK_NOALIAS(x_dev, n, energy_dev, n);                                                 \
+            CHECK_NOALIAS(rxx_dev, n, energy_dev, n);                                               \
+        }                                                                                           \
+        return q->block_dev(x_dev, n, rxx_dev, energy_dev);                                         \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    }
+
+YAGI_AUTOCORR_IMPL(cccf, cf32)
+YAGI_AUTOCORR_IMPL(rrrf, float)
+#undef YAGI_AUTOCORR_IMPL
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

@@ -457,4 +457,29 @@ static_assert(kBseqLdsBytes <= 64 * 1024 && kBseqNmax % 32 == 0 && kBseqNmax / 3
 int launch_bsequence_corr(const unsigned *cur, unsigned *next, const unsigned *ref, int W, unsigned qmask,
                           int ref_bits_msb, const uint8_t *sym, size_t n, int bps, int *rxy, hipStream_t st);
 
+// ---- autocorr_kernels.hip ------------------------------------------------------------------
+// Autocorr (yagi_hip.h) block calls on device buffers: nb samples in; rxx[i] and, where energy is not null, energy[i]
+// after each (W = window_size, d = delay).  hist = the W + d samples before x[0], oldest first (the kernel reads the
+// newest W - 1 + d; the oldest is there for an execute() right after the call); hist_next receives the history the call
+// leaves and must not alias hist.  x, rxx and energy must not overlap.
+constexpr int kAutocorrWg = 256;                       // threads per workgroup
+constexpr int kAutocorrTile = YAGI_AUTOCORR_TILE;      // outputs per workgroup
+constexpr int kAutocorrWmax = YAGI_AUTOCORR_WMAX;      // longest window the LDS tile is sized for
+constexpr int kAutocorrDmax = YAGI_AUTOCORR_DMAX;      // longest delay (the carried history is W + d samples)
+constexpr int kAutocorrR = kAutocorrTile / kAutocorrWg;   // consecutive outputs per lane
+// LDS of the kernel: per staged sample (Tile + Wmax of them, in rows of R padded by 16 bytes) its term of rxx, two floats
+// for cccf, one for rrrf, and with energy its term of that: for cccf in rows of its own, for rrrf beside the first
+constexpr size_t autocorr_lds_bytes(size_t elem_bytes, bool with_energy) {
+    const size_t rows = (size_t)(kAutocorrTile + kAutocorrWmax) / kAutocorrR, r = (size_t)kAutocorrR;
+    return elem_bytes == 8 ? rows * (r * 8 + 16) + (with_energy ? rows * (r * 4 + 16) : 0)
+                           : rows * (r * (with_energy ? 8 : 4) + 16);
+}
+static_assert(autocorr_lds_bytes(8, true) <= 64 * 1024, "the tile must fit a workgroup's LDS");
+template <class T>
+int launch_autocorr(int W, int d, const T *hist, T *hist_next, const T *x, size_t nb, T *rxx, float *energy,
+                    hipStream_t st);
+// rxx and energy of the window as it stands: h = the last W + d samples, oldest first; the kernel's arithmetic
+template <class T>
+void autocorr_host(const T *h, int W, int d, T *rxx, float *energy);
+
 }  // namespace yagi
