@@ -105,6 +105,7 @@ int yagi_hip_dotprod_cccf_dev(const yagi_cf32 *a, const yagi_cf32 *b, size_t n, 
  * firfilt  = FirFilter<T,C>             src/filter/fir/firfilt.rs
  *   create              new(h)                          :63-79   (h_len == 0 -> CONFIG)
  *   create_kaiser       new_kaiser(n, fc, as_, mu)      :93-97   (design: kaiser.rs:16-51)
+ *   create_rnyquist     new_rnyquist(ftype, k, m, beta, mu) :112-116 (design: yagi_hip_fir_design_prototype; 2km+1 taps)
  *   create_rect         new_rect(n)                     :149-155 (n in [1,1024])
  *   create_dc_blocker   new_dc_blocker(m, as_)          :166-170 (design/mod.rs:336-378 fir_design_notch at f0 = 0)
  *   create_notch        new_notch(m, as_, f0)           :183-186 (real taps: notch pair at +-f0; complex taps: the
@@ -124,6 +125,8 @@ int yagi_hip_dotprod_cccf_dev(const yagi_cf32 *a, const yagi_cf32 *b, size_t n, 
  * firdecim = FirDecimationFilter<T,C>   src/filter/fir/firdecim.rs
  *   create              new(M, h, h_len)                :38-57   (h_len==0 or M==0 -> CONFIG)
  *   create_kaiser       new_kaiser(M, m, as_)           :70-87   (M<2, m==0, as_<0 -> CONFIG)
+ *   create_prototype    new_prototype(ftype, M, m, beta, dt) :102-121 (M<2, m==0, beta outside [0,1], dt outside
+ *                                                       [-1,1] -> CONFIG; design: yagi_hip_fir_design_prototype)
  *   execute             execute(&x[..M]) -> T           :179-191
  *   execute_block       execute_block(x, n, y)          :200-205 (x holds n*M samples)
  *   y[i] = scale * sum_k h[k] * x[i*M - k].
@@ -145,6 +148,8 @@ int yagi_hip_dotprod_cccf_dev(const yagi_cf32 *a, const yagi_cf32 *b, size_t n, 
     int yagi_hip_firfilt_##K##_create(const C *h, size_t h_len, yagi_hip_firfilt_##K *q);           \
     int yagi_hip_firfilt_##K##_create_kaiser(size_t n, float fc, float as_, float mu,               \
                                              yagi_hip_firfilt_##K *q);                              \
+    int yagi_hip_firfilt_##K##_create_rnyquist(int ftype, size_t k, size_t m, float beta, float mu, \
+                                               yagi_hip_firfilt_##K *q);                            \
     int yagi_hip_firfilt_##K##_create_rect(size_t n, yagi_hip_firfilt_##K *q);                      \
     int yagi_hip_firfilt_##K##_create_dc_blocker(size_t m, float as_, yagi_hip_firfilt_##K *q);     \
     int yagi_hip_firfilt_##K##_create_notch(size_t m, float as_, float f0, yagi_hip_firfilt_##K *q);\
@@ -175,6 +180,8 @@ int yagi_hip_dotprod_cccf_dev(const yagi_cf32 *a, const yagi_cf32 *b, size_t n, 
                                        yagi_hip_firdecim_##K *q);                                   \
     int yagi_hip_firdecim_##K##_create_kaiser(size_t M, size_t m, float as_,                        \
                                               yagi_hip_firdecim_##K *q);                            \
+    int yagi_hip_firdecim_##K##_create_prototype(int ftype, size_t M, size_t m, float beta,         \
+                                                 float dt, yagi_hip_firdecim_##K *q);               \
     int yagi_hip_firdecim_##K##_destroy(yagi_hip_firdecim_##K q);                                   \
     int yagi_hip_firdecim_##K##_clone(yagi_hip_firdecim_##K q, yagi_hip_firdecim_##K *out);         \
     int yagi_hip_firdecim_##K##_set_stream(yagi_hip_firdecim_##K q, yagi_stream_t s);               \
@@ -253,6 +260,9 @@ YAGI_FFTFILT_API(cccf, yagi_cf32, yagi_cf32)
  *   create           new(interp, h, h_len)        :36-60   (interp < 2 or h_len < interp -> CONFIG; taps
  *                                                          zero-padded to a multiple of interp)
  *   create_kaiser    new_kaiser(interp, m, as_)   :73-90   (uses the first 2*interp*m taps)
+ *   create_prototype new_prototype(ftype, interp, m, beta, dt)   :105-124 (interp < 2, m == 0, beta outside [0,1],
+ *                                                          dt outside [-1,1] -> CONFIG; all 2*interp*m+1 taps of
+ *                                                          yagi_hip_fir_design_prototype: sub-filters of 2m+1)
  *   create_linear    new_linear(interp)           :135-147
  *   create_window    new_window(interp, m)        :159-174
  *   execute          execute(x, &mut y[..interp]) :224-231 (push x, then every branch in order)
@@ -266,6 +276,8 @@ YAGI_FFTFILT_API(cccf, yagi_cf32, yagi_cf32)
                                         yagi_hip_firinterp_##K *q);                                 \
     int yagi_hip_firinterp_##K##_create_kaiser(size_t interp, size_t m, float as_,                  \
                                                yagi_hip_firinterp_##K *q);                          \
+    int yagi_hip_firinterp_##K##_create_prototype(int ftype, size_t interp, size_t m, float beta,   \
+                                                  float dt, yagi_hip_firinterp_##K *q);             \
     int yagi_hip_firinterp_##K##_create_linear(size_t interp, yagi_hip_firinterp_##K *q);           \
     int yagi_hip_firinterp_##K##_create_window(size_t interp, size_t m, yagi_hip_firinterp_##K *q); \
     int yagi_hip_firinterp_##K##_destroy(yagi_hip_firinterp_##K q);                                 \
@@ -300,7 +312,7 @@ YAGI_FIRINTERP_API(cccf, yagi_cf32, yagi_cf32)
  *   execute_block   execute_block(x, n, y)               :163-170 n times execute.  (For block_len > 1 the
  *                   reference slices x and y by Q and P here and panics inside execute; this engine advances
  *                   by Q*block_len and P*block_len like liquid-dsp's rresamp_execute_block.)
- *   new_prototype (:84-97) needs fir_design_prototype (design code out of scope): create() with external taps.
+ *   new_prototype (:84-97) is not provided: create() with the taps of yagi_hip_fir_design_prototype and its scale.
  * Device form: rresamp_kernel -- the branch schedule is static (output n of a block = branch (nQ) mod P after
  * input floor(nQ/P)), so every output is an independent 2m-tap dot product. */
 #define YAGI_RRESAMP_API(K, T, C)                                                                   \
@@ -1492,8 +1504,109 @@ YAGI_AUTOCORR_API(cccf, yagi_cf32)
 YAGI_AUTOCORR_API(rrrf, float)
 #undef YAGI_AUTOCORR_API
 
-/* ---- design helper exposed for hosts that want the taps (kaiser.rs:16-51) ---------------- */
-int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);
+/* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
+int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */
+
+/* (Root-)Nyquist prototypes: src/filter/fir/design/mod.rs:392-451, single precision like the reference.
+ *   estimate_req_filter_stopband_attenuation(df, n, &as_)   design/mod.rs:161-184: twenty bisections of [0.01, 200] dB on
+ *                             the Kaiser length estimate (as_ - 7.95) / (14.26 df) (:228-238); df outside (0, 0.5] is
+ *                             YAGI_ERR_CONFIG
+ *   fir_design_prototype(ftype, k, m, beta, dt, h)   h receives 2km+1 taps.  ftype is numbered as FirFilterShape
+ *                             (design/mod.rs:41-77).  Built here:
+ *                               KAISER    fir_design_kaiser(2km+1, 0.5/k, as_, dt), as_ from the estimate at df = beta/k
+ *                               RCOS      rcos.rs:17-51     k, m >= 1, beta in [0, 1]
+ *                               RRCOS     rrcos.rs:15-63    the same ranges; both special branches (z = 0, 16 beta^2 z^2 = 1)
+ *                               ARKAISER  rkaiser.rs:49-93  k >= 2, m >= 1, beta in (0, 1), dt in [-1, 1]; sum h^2 = k
+ *                             The estimate runs first for every shape, as in the reference, so beta = 0 (df = 0) is
+ *                             YAGI_ERR_CONFIG for all of them, and KAISER takes dt in (-0.5, 0.5] (kaiser.rs:18).  k = 0
+ *                             and m = 0 are YAGI_ERR_CONFIG for every shape (the reference would divide by zero).
+ *                             Every other shape (PM, FEXP, FSECH, FARCSECH, RKAISER, HM3, GMSKTX, GMSKRX, RFEXP, RFSECH,
+ *                             RFARCSECH) is YAGI_ERR_CONFIG ("not built").  ARKAISER: where the closed-form bandwidth
+ *                             correction rho_hat (rkaiser.rs:65-69) leaves (0, 1) the reference falls back on a table of
+ *                             fitted constants (:105-144) that is not part of this library; that is YAGI_ERR_CONFIG here
+ *                             (for example m = 1, beta = 0.05).  k 2..12, m 4..31, beta 0.2..0.35 stay inside. */
+enum yagi_fir_shape {
+    YAGI_FIR_SHAPE_KAISER = 0, YAGI_FIR_SHAPE_PM, YAGI_FIR_SHAPE_RCOS, YAGI_FIR_SHAPE_FEXP, YAGI_FIR_SHAPE_FSECH,
+    YAGI_FIR_SHAPE_FARCSECH, YAGI_FIR_SHAPE_ARKAISER, YAGI_FIR_SHAPE_RKAISER, YAGI_FIR_SHAPE_RRCOS, YAGI_FIR_SHAPE_HM3,
+    YAGI_FIR_SHAPE_GMSKTX, YAGI_FIR_SHAPE_GMSKRX, YAGI_FIR_SHAPE_RFEXP, YAGI_FIR_SHAPE_RFSECH, YAGI_FIR_SHAPE_RFARCSECH,
+    YAGI_FIR_SHAPE_UNKNOWN = -1   /* no reference counterpart: what a SymStream made from external taps reports */
+};
+int yagi_hip_estimate_req_filter_stopband_attenuation(float df, size_t n, float *as_);
+int yagi_hip_fir_design_prototype(int ftype, size_t k, size_t m, float beta, float dt, float *h /* 2km+1 */);
+
+/* ---- SymStream (symstreamcf): src/framing/symstream.rs:6-122 (symbol source -> modulator -> pulse shaper) -----------------
+ * The reference draws its symbols from Modem::random_symbol, a generator nobody can reproduce (its own clone test is
+ * disabled for that reason, :330-333).  Here the symbol source is an LFSR: a private copy of an MSequence taken at
+ * creation.  Everything else is the reference's object: ftype, k, m, beta, a Modem, a gain, a FirInterpolationFilter
+ * <Complex<f32>, f32> of k branches with Ls = 2m+1 taps each and scale 1, and buf_index in [0, k).
+ *
+ * Definition.  Sample t of the stream since creation or reset() is branch t mod k of the interpolator after symbol
+ * floor(t / k) was pushed (write_samples :111-121).  The pushed value is v = modulate(s) * gain, two f32 products
+ * (re gain, im gain) (:104-109); s = source.generate_symbol(bps) is drawn when the symbol's first sample is written;
+ * gain, scheme and bps are read at that moment and the interpolator's window keeps VALUES, so set_gain / set_scheme
+ * between calls affect later symbols only.  Every output word equals MSequence.generate_symbols_block ->
+ * Modem.modulate_block -> x gain per component -> FirInterpolationFilter(crcf).execute_block run one after the other,
+ * at any n, any cut of the stream into calls and any mix of the entry points.
+ *   create_linear(ftype, k, m, beta, scheme, src)   new_linear() :24-59 plus the source.  k < 2, m == 0 and beta outside
+ *                             [0, 1] are YAGI_ERR_CONFIG; scheme errors are Modem's, design errors those of
+ *                             yagi_hip_fir_design_prototype (dt = 0).  src is copied at its current state (its state
+ *                             word, m, g and jump tables) and not touched afterwards.
+ *   create_taps(k, h, h_len, scheme, src)   extension: externally designed taps, as yagi_hip_firinterp_crcf_create(k, h,
+ *                             h_len) takes them (Ls = ceil(h_len / k)).  get_ftype reports YAGI_FIR_SHAPE_UNKNOWN, get_beta
+ *                             0, and get_m floor((Ls - 1) / 2): the m of a 2km+1-tap prototype, so get_delay stays k m.
+ *   destroy / clone / set_stream      clone copies everything: source state, window, buf_index, the modem with its DPSK
+ *                             index, gain.  A clone and its original then write equal streams.
+ *   reset()                   :61-65  the modem, the interpolator's window and buf_index.  The source stays where it
+ *                             stands, as the reference leaves its generator.
+ *   source_set_state(a) / source_get_state(&a)   extension: rewind or read the source's state word (not masked, as
+ *                             MSequence::set_state).  After any calls the state equals (symbols drawn) x bps advance()s.
+ *   get_ftype / get_k / get_m / get_beta / get_scheme / get_gain / get_delay (= k m)      :67-102
+ *   set_scheme(scheme)        :83-86  builds a new modem: DPSK index 0, new bps
+ *   set_modem(mod)            extension: a copy of the caller's Modem at its current state (the way to an arbitrary
+ *                             constellation, yagi_hip_modem_create_from_table); get_scheme then reports its scheme
+ *   set_gain(gain)            :92-94  any float
+ *   write_samples(y, n)       :111-121  any n; a call may start and end inside a symbol, buf_index carries over.  Host
+ *                             pointer, staged through the device.  n = 0 is a no-op.
+ *   write_samples_dev(y_dev, n)   the same on a device buffer, asynchronous on the object's stream
+ *   modulate_symbols(sym, nsym, y) / _dev   extension: the caller's symbol bytes instead of the source, nsym symbols ->
+ *                             nsym k samples; the source does not advance.  A symbol >= M anywhere is YAGI_ERR_RANGE: y is
+ *                             not written and no state moves (as yagi_hip_modem_modulate_block).  Allowed only on a symbol
+ *                             boundary (buf_index == 0), else YAGI_ERR_MODE.  The _dev form reads the range flag back, so it
+ *                             returns after the check has run; sym_dev and y_dev must not overlap (YAGI_ERR_CONFIG).
+ *   is_fused(&fused)          read-only: 1 where a block call of the object as it stands runs the fused kernel, 0 where it
+ *                             runs the three launches of the parts (DPSK schemes; shapes whose bank plan is
+ *                             YAGI_PLAN_PFB_NONE or whose span + tables exceed 64 KiB of LDS).  The words are the same.
+ * Device pointers: y_dev 8-byte aligned.
+ * Device form: symstream_kernels.hip: one launch per call; a workgroup jumps the LFSR to its tile,
+ * stages gain x constellation points in LDS and runs the bank kernels' sums. */
+typedef struct yagi_hip_symstreamcf_s *yagi_hip_symstreamcf;
+int yagi_hip_symstreamcf_create_linear(int ftype, size_t k, size_t m, float beta, int scheme, yagi_hip_msequence src,
+                                       yagi_hip_symstreamcf *q);
+int yagi_hip_symstreamcf_create_taps(size_t k, const float *h, size_t h_len, int scheme, yagi_hip_msequence src,
+                                     yagi_hip_symstreamcf *q);
+int yagi_hip_symstreamcf_destroy(yagi_hip_symstreamcf q);
+int yagi_hip_symstreamcf_clone(yagi_hip_symstreamcf q, yagi_hip_symstreamcf *out);
+int yagi_hip_symstreamcf_set_stream(yagi_hip_symstreamcf q, yagi_stream_t s);
+int yagi_hip_symstreamcf_reset(yagi_hip_symstreamcf q);
+int yagi_hip_symstreamcf_source_set_state(yagi_hip_symstreamcf q, unsigned a);
+int yagi_hip_symstreamcf_source_get_state(yagi_hip_symstreamcf q, unsigned *a);
+int yagi_hip_symstreamcf_get_ftype(yagi_hip_symstreamcf q, int *ftype);
+int yagi_hip_symstreamcf_get_k(yagi_hip_symstreamcf q, size_t *k);
+int yagi_hip_symstreamcf_get_m(yagi_hip_symstreamcf q, size_t *m);
+int yagi_hip_symstreamcf_get_beta(yagi_hip_symstreamcf q, float *beta);
+int yagi_hip_symstreamcf_get_scheme(yagi_hip_symstreamcf q, int *scheme);
+int yagi_hip_symstreamcf_get_gain(yagi_hip_symstreamcf q, float *gain);
+int yagi_hip_symstreamcf_get_delay(yagi_hip_symstreamcf q, size_t *delay);
+int yagi_hip_symstreamcf_get_buf_index(yagi_hip_symstreamcf q, size_t *buf_index);
+int yagi_hip_symstreamcf_set_scheme(yagi_hip_symstreamcf q, int scheme);
+int yagi_hip_symstreamcf_set_modem(yagi_hip_symstreamcf q, yagi_hip_modem mod);
+int yagi_hip_symstreamcf_set_gain(yagi_hip_symstreamcf q, float gain);
+int yagi_hip_symstreamcf_is_fused(yagi_hip_symstreamcf q, int *fused);
+int yagi_hip_symstreamcf_write_samples(yagi_hip_symstreamcf q, yagi_cf32 *y, size_t n);
+int yagi_hip_symstreamcf_write_samples_dev(yagi_hip_symstreamcf q, yagi_cf32 *y_dev, size_t n);
+int yagi_hip_symstreamcf_modulate_symbols(yagi_hip_symstreamcf q, const uint8_t *sym, size_t nsym, yagi_cf32 *y);
+int yagi_hip_symstreamcf_modulate_symbols_dev(yagi_hip_symstreamcf q, const uint8_t *sym_dev, size_t nsym,
+                                              yagi_cf32 *y_dev);
 
 #ifdef __cplusplus
 }

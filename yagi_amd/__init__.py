@@ -38,7 +38,8 @@ __all__ = [
     "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "plan_fir_block", "plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
-    "fir_design_kaiser", "firhilb_design", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
+    "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
+    "estimate_req_filter_stopband_attenuation", "SymStream", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
 
@@ -191,6 +192,42 @@ def fir_design_kaiser(n, fc, as_, mu=0.0):
     h = np.zeros(max(int(n), 1), np.float32)
     _check(lib.yagi_hip_fir_design_kaiser(n, fc, as_, mu, _ptr(h)))
     return h[:n]
+
+
+class FirFilterShape(enum.IntEnum):
+    """filter::FirFilterShape (src/filter/fir/design/mod.rs:41-77), numbered as yagi_fir_shape.  fir_design_prototype
+    builds Kaiser, Rcos, Rrcos and Arkaiser; the others are a ConfigError.  Unknown has no reference counterpart: what
+    a SymStream made from external taps reports."""
+    Unknown = -1
+    Kaiser = 0
+    Pm = 1
+    Rcos = 2
+    Fexp = 3
+    Fsech = 4
+    Farcsech = 5
+    Arkaiser = 6
+    Rkaiser = 7
+    Rrcos = 8
+    Hm3 = 9
+    Gmsktx = 10
+    Gmskrx = 11
+    Rfexp = 12
+    Rfsech = 13
+    Rfarcsech = 14
+
+
+def estimate_req_filter_stopband_attenuation(df, n):
+    """filter::estimate_req_filter_stopband_attenuation (src/filter/fir/design/mod.rs:161-184)"""
+    v = C.c_float()
+    _check(lib.yagi_hip_estimate_req_filter_stopband_attenuation(df, n, C.byref(v)))
+    return np.float32(v.value)
+
+
+def fir_design_prototype(ftype, k, m, beta, dt=0.0):
+    """filter::fir_design_prototype (src/filter/fir/design/mod.rs:392-451): 2km+1 taps"""
+    h = np.zeros(2 * max(int(k), 0) * max(int(m), 0) + 1, np.float32)
+    _check(lib.yagi_hip_fir_design_prototype(int(ftype), k, m, beta, dt, _ptr(h)))
+    return h
 
 
 def firhilb_design(m, as_):
@@ -348,6 +385,10 @@ class FirFilter(_FirBase):
         return cls._from(kind, "create_kaiser", n, fc, as_, mu)
 
     @classmethod
+    def new_rnyquist(cls, kind, ftype, k, m, beta, mu=0.0):  # firfilt.rs:112-116
+        return cls._from(kind, "create_rnyquist", int(ftype), k, m, beta, mu)
+
+    @classmethod
     def new_rect(cls, kind, n):                              # firfilt.rs:149-155
         return cls._from(kind, "create_rect", n)
 
@@ -445,6 +486,16 @@ class FirDecimationFilter(_FirBase):
         self._prefix = f"yagi_hip_firdecim_{kind}_"
         hd = C.c_void_p()
         _check(self._fn("create_kaiser")(decimation_factor, m, as_, C.byref(hd)))
+        self._h = hd
+        return self
+
+    @classmethod
+    def new_prototype(cls, kind, ftype, decimation_factor, m, beta, dt=0.0):   # firdecim.rs:102-121
+        self = object.__new__(cls)
+        self._init_kind(kind)
+        self._prefix = f"yagi_hip_firdecim_{kind}_"
+        hd = C.c_void_p()
+        _check(self._fn("create_prototype")(int(ftype), decimation_factor, m, beta, dt, C.byref(hd)))
         self._h = hd
         return self
 
@@ -579,6 +630,10 @@ class FirInterpolationFilter(_FirBase):
     @classmethod
     def new_kaiser(cls, kind, interp, m, as_):               # :73-90
         return cls._from(kind, "create_kaiser", interp, m, as_)
+
+    @classmethod
+    def new_prototype(cls, kind, ftype, interp, m, beta, dt=0.0):   # :105-124
+        return cls._from(kind, "create_prototype", int(ftype), interp, m, beta, dt)
 
     @classmethod
     def new_linear(cls, kind, interp):                       # :135-147
@@ -2163,6 +2218,114 @@ class Modem(_Handle):
 
     def demodulate_soft_block_devptr(self, x_dev, n, sym_dev, soft_dev):
         _check(self._fn("demodulate_soft_block_dev")(self._h, _devptr(x_dev), n, _devptr(sym_dev), _devptr(soft_dev)))
+
+
+class SymStream(_Handle):
+    """framing::SymStream (src/framing/symstream.rs), symstreamcf: symbol source -> Modem -> x gain ->
+    FirInterpolationFilter<Complex<f32>, f32> of k branches, written in any number of samples per call.  The symbol
+    source is a private copy of an MSequence taken at creation (the reference draws from an RNG nobody can reproduce), so
+    every output word equals MSequence.generate_symbols_block -> Modem.modulate_block -> x gain per component ->
+    FirInterpolationFilter("crcf").execute_block, and a clone writes the stream its original writes.  A block call is one
+    launch of symstream_kernels.hip (is_fused) except for Dpsk* schemes and shapes the fused kernel does not serve, which
+    run the three objects' launchers; the words are the same (include/yagi_hip.h)."""
+    _prefix = "yagi_hip_symstreamcf_"
+
+    def __init__(self, ftype, k, m, beta, scheme, source):    # new_linear :24-59 plus the source
+        hd = C.c_void_p()
+        _check(self._fn("create_linear")(int(ftype), k, m, beta, int(scheme), source._h, C.byref(hd)))
+        self._h = hd
+
+    @classmethod
+    def from_taps(cls, k, h, scheme, source, h_len=None):
+        """extension: externally designed taps, read as FirInterpolationFilter("crcf", k, h, h_len) reads them"""
+        self = object.__new__(cls)
+        h = _arr(h, np.float32)
+        hd = C.c_void_p()
+        _check(self._fn("create_taps")(k, _ptr(h), h.size if h_len is None else h_len, int(scheme), source._h, C.byref(hd)))
+        self._h = hd
+        return self
+
+    def clone(self):                                          # derive(Clone)
+        new = object.__new__(type(self))
+        hd = C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._h = hd
+        return new
+
+    def _get(self, name, ctype):
+        v = ctype()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return v.value
+
+    def get_ftype(self):                                      # :67-69
+        return FirFilterShape(self._get("get_ftype", C.c_int))
+
+    def get_k(self):                                          # :71-73
+        return self._get("get_k", C.c_size_t)
+
+    def get_m(self):                                          # :75-77; from_taps: (ceil(h_len / k) - 1) // 2
+        return self._get("get_m", C.c_size_t)
+
+    def get_beta(self):                                       # :79-81
+        return np.float32(self._get("get_beta", C.c_float))
+
+    def set_scheme(self, scheme):                             # :83-86 a new modem: Dpsk index 0
+        _check(self._fn("set_scheme")(self._h, int(scheme)))
+
+    def set_modem(self, modem):
+        """extension: a copy of `modem` (a Modem, e.g. Modem.from_table) at its current state becomes the modulator"""
+        _check(self._fn("set_modem")(self._h, modem._h))
+
+    def get_scheme(self):                                     # :88-90
+        return ModulationScheme(self._get("get_scheme", C.c_int))
+
+    def set_gain(self, gain):                                 # :92-94
+        _check(self._fn("set_gain")(self._h, gain))
+
+    def get_gain(self):                                       # :96-98
+        return np.float32(self._get("get_gain", C.c_float))
+
+    def get_delay(self):                                      # :100-102
+        return self._get("get_delay", C.c_size_t)
+
+    def get_buf_index(self):
+        """extension: t mod k for the next sample t"""
+        return self._get("get_buf_index", C.c_size_t)
+
+    def is_fused(self):
+        """True where a block call of the object as it stands is one launch of the fused kernel"""
+        return bool(self._get("is_fused", C.c_int))
+
+    def source_set_state(self, a):
+        """extension: the source's state word (not masked, as MSequence.set_state)"""
+        _check(self._fn("source_set_state")(self._h, a))
+
+    def source_get_state(self):
+        return self._get("source_get_state", C.c_uint)
+
+    def write_samples(self, n, y=None):                       # :111-121
+        """the next n samples of the stream; n may start and end inside a symbol"""
+        y = _out(y, n, np.complex64)
+        _check(self._fn("write_samples")(self._h, _ptr(y), n))
+        return y
+
+    def modulate_symbols(self, sym, y=None):
+        """extension: the caller's symbols instead of the source, k samples each.  A symbol >= M is a RangeError and
+        nothing moves; off a symbol boundary (get_buf_index() != 0) it is a ModeError"""
+        sym = _arr(sym, np.uint8)
+        y = _out(y, sym.size * self.get_k(), np.complex64)
+        _check(self._fn("modulate_symbols")(self._h, _ptr(sym), sym.size, _ptr(y)))
+        return y
+
+    # The device-pointer forms are spelled *_devptr, as Modem's and Autocorr's: tests/test_gpu_dev_buffers.py owns the
+    # list of the package's *_dev methods; these two are covered by tests/test_gpu_symstream_dev_buffers.py instead.
+    def write_samples_devptr(self, y_dev, n):
+        """y_dev: n samples on the device; asynchronous on the object's stream"""
+        _check(self._fn("write_samples_dev")(self._h, _devptr(y_dev), n))
+
+    def modulate_symbols_devptr(self, sym_dev, nsym, y_dev):
+        """sym_dev: nsym bytes, y_dev: nsym k samples on the device; they must not overlap (ConfigError)"""
+        _check(self._fn("modulate_symbols_dev")(self._h, _devptr(sym_dev), nsym, _devptr(y_dev)))
 
 
 class MsResamp(_FirBase):

@@ -62,6 +62,8 @@ _sig("yagi_hip_stream_synchronize", vp)
 _sig("yagi_hip_gen_real_dev", u64, u64, sz, vp, vp)
 _sig("yagi_hip_gen_complex_dev", u64, u64, sz, vp, vp)
 _sig("yagi_hip_fir_design_kaiser", sz, f32, f32, f32, vp)
+_sig("yagi_hip_estimate_req_filter_stopband_attenuation", f32, sz, C.POINTER(f32))
+_sig("yagi_hip_fir_design_prototype", ci, sz, sz, f32, f32, vp)
 
 for _k in ("rrrf", "rccf", "crcf", "cccf"):
     _sig(f"yagi_hip_dotprod_{_k}", vp, vp, sz, vp)
@@ -74,6 +76,7 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
     p = f"yagi_hip_firfilt_{_k}_"
     _sig(p + "create", vp, sz, pvp)
     _sig(p + "create_kaiser", sz, f32, f32, f32, pvp)
+    _sig(p + "create_rnyquist", ci, sz, sz, f32, f32, pvp)
     _sig(p + "freqresponse", vp, f32, vp)
     _sig(p + "groupdelay", vp, f32, vp)
     _sig(p + "create_rect", sz, pvp)
@@ -99,6 +102,7 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
     p = f"yagi_hip_firdecim_{_k}_"
     _sig(p + "create", sz, vp, sz, pvp)
     _sig(p + "create_kaiser", sz, sz, f32, pvp)
+    _sig(p + "create_prototype", ci, sz, sz, f32, f32, pvp)
     _sig(p + "destroy", vp)
     _sig(p + "clone", vp, pvp)
     _sig(p + "set_stream", vp, vp)
@@ -131,6 +135,7 @@ for _k, (_T, _Cc) in KIND_TYPES.items():
     p = f"yagi_hip_firinterp_{_k}_"
     _sig(p + "create", sz, vp, sz, pvp)
     _sig(p + "create_kaiser", sz, sz, f32, pvp)
+    _sig(p + "create_prototype", ci, sz, sz, f32, f32, pvp)
     _sig(p + "create_linear", sz, pvp)
     _sig(p + "create_window", sz, sz, pvp)
     _sig(p + "destroy", vp)
@@ -588,3 +593,27 @@ for _k, _T in (("cccf", cf32), ("rrrf", f32)):
     _sig(_p + "get_energy", vp, C.POINTER(f32))
     _sig(_p + "execute_block", vp, vp, sz, vp, vp)
     _sig(_p + "execute_block_dev", vp, vp, sz, vp, vp)
+
+# ---- SymStream ---------------------------------------------------------------------------------
+_p = "yagi_hip_symstreamcf_"
+_sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)
+_sig(_p + "create_taps", sz, vp, sz, ci, vp, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "source_set_state", vp, cu)
+_sig(_p + "source_get_state", vp, pcu)
+for _n in ("get_ftype", "get_scheme", "is_fused"):
+    _sig(_p + _n, vp, C.POINTER(ci))
+for _n in ("get_k", "get_m", "get_delay", "get_buf_index"):
+    _sig(_p + _n, vp, C.POINTER(sz))
+for _n in ("get_beta", "get_gain"):
+    _sig(_p + _n, vp, C.POINTER(f32))
+_sig(_p + "set_scheme", vp, ci)
+_sig(_p + "set_modem", vp, vp)
+_sig(_p + "set_gain", vp, f32)
+for _n in ("write_samples", "write_samples_dev"):
+    _sig(_p + _n, vp, vp, sz)
+for _n in ("modulate_symbols", "modulate_symbols_dev"):
+    _sig(_p + _n, vp, vp, sz, vp)

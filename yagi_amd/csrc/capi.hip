@@ -27,6 +27,7 @@ namespace yagi {
 int design_kaiser(size_t n, float fc, float as_, float mu, std::vector<float> &h);   // host.cpp
 int window_value(int type, size_t i, size_t wlen, float arg, float *out);            // host.cpp
 int design_notch(size_t m, float f0, float as_, std::vector<float> &h);                // host.cpp
+int design_prototype(int ftype, size_t k, size_t m, float beta, float dt, std::vector<float> &h);   // host.cpp
 
 static int require_device() {
     static int ok = -1;
@@ -961,6 +962,16 @@ static int taps_groupdelay(const std::vector<C> &h, float fc, float *out) {
         for (size_t i = 0; i < hf.size(); ++i) hc[i] = to_c(hf[i], (C *)nullptr);                   \
         return yagi_hip_firfilt_##K##_create(hc.data(), hc.size(), q);                              \
     } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_firfilt_##K##_create_rnyquist(int ftype, size_t k, size_t m, float beta, float mu, \
+                                               yagi_hip_firfilt_##K *q) try {                       \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        std::vector<float> hf;                                                                      \
+        YG_TRY(design_prototype(ftype, k, m, beta, mu, hf));                                        \
+        std::vector<C> hc(hf.size());                                                               \
+        for (size_t i = 0; i < hf.size(); ++i) hc[i] = to_c(hf[i], (C *)nullptr);                   \
+        return yagi_hip_firfilt_##K##_create(hc.data(), hc.size(), q);                              \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_firfilt_##K##_create_rect(size_t n, yagi_hip_firfilt_##K *q) try {                 \
         CHECK_PTR(q);                                                                               \
         *q = nullptr;                                                                               \
@@ -1132,6 +1143,22 @@ static int taps_groupdelay(const std::vector<C> &h, float fc, float *out) {
         if (as_ < 0.0f) return fail(YAGI_ERR_CONFIG, "stop-band attenuation must be positive");     \
         std::vector<float> hf;                                                                      \
         YG_TRY(design_kaiser(2 * M * m + 1, 0.5f / (float)M, as_, 0.0f, hf));                       \
+        std::vector<C> hc(hf.size());                                                               \
+        for (size_t i = 0; i < hf.size(); ++i) hc[i] = to_c(hf[i], (C *)nullptr);                   \
+        return yagi_hip_firdecim_##K##_create(M, hc.data(), hc.size(), q);                          \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_firdecim_##K##_create_prototype(int ftype, size_t M, size_t m, float beta,         \
+                                                 float dt, yagi_hip_firdecim_##K *q) try {          \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        if (M < 2) return fail(YAGI_ERR_CONFIG, "decimation factor must be greater than 1");        \
+        if (m == 0) return fail(YAGI_ERR_CONFIG, "filter delay must be greater than 0");            \
+        if (beta < 0.0f || beta > 1.0f)                                                             \
+            return fail(YAGI_ERR_CONFIG, "filter excess bandwidth factor must be in [0,1]");        \
+        if (dt < -1.0f || dt > 1.0f)                                                                \
+            return fail(YAGI_ERR_CONFIG, "filter fractional sample delay must be in [-1,1]");       \
+        std::vector<float> hf;                                                                      \
+        YG_TRY(design_prototype(ftype, M, m, beta, dt, hf));                                        \
         std::vector<C> hc(hf.size());                                                               \
         for (size_t i = 0; i < hf.size(); ++i) hc[i] = to_c(hf[i], (C *)nullptr);                   \
         return yagi_hip_firdecim_##K##_create(M, hc.data(), hc.size(), q);                          \
@@ -1472,6 +1499,15 @@ struct FirInterp {
     }
 };
 
+// new_prototype (firinterp.rs:105-124): its checks, then all 2 interp m + 1 taps of the design
+static int firinterp_prototype_taps(int ftype, size_t interp, size_t m, float beta, float dt, std::vector<float> &hf) {
+    if (interp < 2) return fail(YAGI_ERR_CONFIG, "interp factor must be greater than 1");
+    if (m == 0) return fail(YAGI_ERR_CONFIG, "filter delay must be greater than 0");
+    if (beta < 0.0f || beta > 1.0f) return fail(YAGI_ERR_CONFIG, "filter excess bandwidth factor must be in [0,1]");
+    if (dt < -1.0f || dt > 1.0f) return fail(YAGI_ERR_CONFIG, "filter fractional sample delay must be in [-1,1]");
+    return design_prototype(ftype, interp, m, beta, dt, hf);
+}
+
 }  // namespace yagi
 
 #define YAGI_FIRINTERP_IMPL(K, KT, T, C)                                                            \
@@ -1499,6 +1535,16 @@ struct FirInterp {
         std::vector<C> hc(hf.size());                                                               \
         for (size_t i = 0; i < hf.size(); ++i) hc[i] = to_c(hf[i], (C *)nullptr);                   \
         return yagi_hip_firinterp_##K##_create(interp, hc.data(), hc.size() - 1, q);                \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_firinterp_##K##_create_prototype(int ftype, size_t interp, size_t m, float beta,   \
+                                                  float dt, yagi_hip_firinterp_##K *q) try {        \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        std::vector<float> hf;                                                                      \
+        YG_TRY(firinterp_prototype_taps(ftype, interp, m, beta, dt, hf));                           \
+        std::vector<C> hc(hf.size());                                                               \
+        for (size_t i = 0; i < hf.size(); ++i) hc[i] = to_c(hf[i], (C *)nullptr);                   \
+        return yagi_hip_firinterp_##K##_create(interp, hc.data(), hc.size(), q);                    \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_firinterp_##K##_create_linear(size_t interp, yagi_hip_firinterp_##K *q) try {      \
         CHECK_PTR(q);                                                                               \
@@ -6895,3 +6941,328 @@ YAGI_DDC_IMPL(ddc, DdcObj, false, get_decim_rate, crcf, CRCF, float)
 YAGI_DDC_IMPL(ddc, DdcObj, false, get_decim_rate, cccf, CCCF, yagi_cf32)
 YAGI_DDC_IMPL(duc, DucObj, true, get_interp_rate, crcf, CRCF, float)
 YAGI_DDC_IMPL(duc, DucObj, true, get_interp_rate, cccf, CCCF, yagi_cf32)
+
+// ---- SymStream (src/framing/symstream.rs) -----------------------------------------------------------------------------
+// The reference's fields (ftype, k, m, beta, modem, gain, interp, buf, buf_index :6-17) plus the symbol source: the words
+// and jump tables of an MSequence, copied at creation.  The modem and the interpolator are the library's own objects, so
+// the three-launch route (DPSK, shapes the fused kernel does not serve) is their launchers one after the other and the
+// window mirror is the shared one; a block call runs symstream_kernels.hip wherever that serves the object as it stands.
+struct yagi_hip_symstreamcf_s {
+    int ftype = YAGI_FIR_SHAPE_UNKNOWN;
+    size_t k = 0, m = 0;
+    float beta = 0.0f, gain = 1.0f;
+    yagi_hip_modem modem = nullptr;            // owned
+    FirInterp<CRCF> fir;
+    int p = 0;                                 // buf_index
+    unsigned sm = 0, sg = 0, smask = 0, sstate = 0;       // the source: MSequence's m, g, n and state
+    std::vector<unsigned> pow, stride;         // T^(2^b); the fused kernel's lane strides per bps
+    DevBuf dpow, dstride;
+    int run = 0;                               // symstream_run(k, Ls): what `stride` is built for
+    DevBuf dbuf;                               // k values: the reference's buf, the branches of the last pushed symbol
+    DevBuf dsym, dpts, dout, flag;             // three-launch route: symbols, points, interpolator output; range flag
+    Staging ws;
+
+    ~yagi_hip_symstreamcf_s() {
+        if (modem) (void)yagi_hip_modem_destroy(modem);
+    }
+    hipStream_t &stream() { return fir.bank.st; }
+    int Ls() const { return fir.bank.Ls; }
+    int alloc_dev() {
+        YG_TRY(fill(dpow, pow.data(), pow.size() * sizeof(unsigned), stream()));
+        YG_TRY(fill(dstride, stride.data(), stride.size() * sizeof(unsigned), stream()));
+        YG_TRY(dbuf.alloc(k * sizeof(cf32)));
+        YG_HIP(hipMemsetAsync(dbuf.p, 0, k * sizeof(cf32), stream()));
+        return flag.alloc(sizeof(int));
+    }
+    int init(int ftype_, size_t k_, size_t m_, float beta_, const float *h, size_t h_len, int scheme, yagi_hip_msequence src) {
+        YG_TRY(fir.init(k_, h, h_len));        // needs the device
+        YG_TRY(yagi_hip_modem_create(scheme, &modem));
+        modem->st = stream();
+        ftype = ftype_;
+        k = k_;
+        m = m_;
+        beta = beta_;
+        sm = src->m;
+        sg = src->g;
+        smask = src->n;
+        sstate = src->state;
+        pow = src->pow;
+        run = symstream_run((int)k, Ls());
+        stride.resize(kSymStrideWords);
+        symstream_strides(pow.data(), run, stride.data());
+        return alloc_dev();
+    }
+    bool fused() const { return modem->P.kind != MODEM_DPSK && symstream_fused_serves((int)k, Ls(), modem->P.M); }
+    int reset() {                                                            // :61-65
+        YG_TRY(modem->reset());
+        YG_TRY(fir.bank.w.reset(stream()));
+        p = 0;
+        return YAGI_OK;
+    }
+    int set_modem(yagi_hip_modem fresh) {      // takes ownership
+        YG_HIP(hipStreamSynchronize(stream()));
+        (void)yagi_hip_modem_destroy(modem);
+        modem = fresh;
+        modem->st = stream();
+        return YAGI_OK;
+    }
+    // samples [0, n) of a call that starts at buf_index p; sym: the caller's symbols on the device, or null (the source)
+    int block_dev(const uint8_t *sym, size_t n, cf32 *y) {
+        if (n == 0) return YAGI_OK;
+        FirPfb<CRCF> &b = fir.bank;
+        const int bps = modem->P.bps, M = modem->P.M;
+        const size_t old = p > 0 ? 1 : 0;
+        const size_t nnew = ((size_t)p + n + k - 1) / k - old;
+        if (fused()) {
+            YG_TRY(b.w.ensure_dev(b.st));
+            const int *fl = nullptr;
+            if (sym) {
+                YG_TRY(launch_symstream_check(M, sym, nnew, flag.as<int>(), b.st));
+                if (M < 256) fl = flag.as<int>();
+            }
+            const SymSource src{dpow.as<unsigned>(), dstride.as<unsigned>(), sstate, sg, smask, (int)sm, bps, run};
+            YG_TRY(launch_symstream(b.w.dev(), b.taps.as<float>(), (int)k, b.Ls, b.scale, modem->dmap.as<cf32>(), M, gain, sym,
+                                    fl, sym ? nullptr : &src, p, n, y, b.w.next(), dbuf.as<cf32>(), b.st));
+            if (fl) {
+                int bad = 0;
+                YG_TRY(download(&bad, flag.p, sizeof(int), b.st));
+                if (bad) return fail(YAGI_ERR_RANGE, "input symbol exceeds constellation size");
+            }
+            if (nnew) b.w.flip();              // the kernel's last workgroup wrote the next window
+        } else {
+            // the branches of the symbol the previous call pushed, then the parts' launchers over the new symbols
+            const size_t head = p > 0 ? std::min(n, k - (size_t)p) : 0;
+            if (nnew) {
+                const uint8_t *s = sym;
+                if (!s) {
+                    YG_TRY(dsym.ensure(nnew));
+                    YG_TRY(gen_symbols(nnew));
+                    s = dsym.as<uint8_t>();
+                }
+                YG_TRY(dpts.ensure(nnew * sizeof(cf32)));
+                YG_TRY(dout.ensure(nnew * k * sizeof(cf32)));
+                YG_TRY(modem->modulate_dev(s, nnew, dpts.as<cf32>()));       // a symbol >= M: YAGI_ERR_RANGE, nothing moved
+                YG_TRY(launch_symstream_gain(dpts.as<cf32>(), nnew, gain, b.st));
+                YG_TRY(fir.block_dev(dpts.as<cf32>(), nnew, dout.as<cf32>()));
+            }
+            if (head)
+                YG_HIP(hipMemcpyAsync(y, dbuf.as<cf32>() + p, head * sizeof(cf32), hipMemcpyDeviceToDevice, b.st));
+            if (nnew) {
+                YG_HIP(hipMemcpyAsync(y + head, dout.p, (n - head) * sizeof(cf32), hipMemcpyDeviceToDevice, b.st));
+                YG_HIP(hipMemcpyAsync(dbuf.p, dout.as<cf32>() + (nnew - 1) * k, k * sizeof(cf32), hipMemcpyDeviceToDevice, b.st));
+            }
+        }
+        if (!sym) sstate = msequence_skip(pow.data(), sstate, (uint64_t)nnew * (uint64_t)bps);
+        p = (int)(((size_t)p + n) % k);
+        return YAGI_OK;
+    }
+    // the source's next nnew symbols into dsym: MSequence's own generator with the object's tables
+    int gen_symbols(size_t nnew) {
+        if (mstride.empty()) {                 // first use of the three-launch route
+            std::vector<unsigned> pw(kMseqPowWords);
+            mstride.resize(kMseqStrideWords);
+            msequence_tables(sg, smask, pw.data(), mstride.data());
+            YG_TRY(fill(dmstride, mstride.data(), mstride.size() * sizeof(unsigned), stream()));
+        }
+        return launch_msequence_gen(dpow.as<unsigned>(), dmstride.as<unsigned>(), sstate, sg, smask, (int)sm, modem->P.bps, nnew,
+                                    dsym.as<uint8_t>(), stream());
+    }
+    std::vector<unsigned> mstride;             // MSequence's block-kernel strides (three-launch route only)
+    DevBuf dmstride;
+    int block_host(const uint8_t *sym, size_t nsym, size_t n, cf32 *y) {
+        YG_TRY(ws.y.ensure(n * sizeof(cf32)));
+        const uint8_t *sd = nullptr;
+        if (sym) {
+            YG_TRY(ws.put(stream(), sym, nsym));
+            sd = ws.x.as<uint8_t>();
+        }
+        YG_TRY(block_dev(sd, n, ws.y.as<cf32>()));
+        return download(y, ws.y.p, n * sizeof(cf32), stream());
+    }
+};
+
+static int symstream_check_source(yagi_hip_msequence src) {
+    if (!src) return fail(YAGI_ERR_CONFIG, "null handle (symbol source)");
+    return YAGI_OK;
+}
+
+#define SYMSTREAM_GET(name, type, expr)                                                             \
+    int yagi_hip_symstreamcf_##name(yagi_hip_symstreamcf q, type *v) try {                          \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(v);                                                                               \
+        *v = (expr);                                                                                \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }
+
+extern "C" {
+
+int yagi_hip_symstreamcf_create_linear(int ftype, size_t k, size_t m, float beta, int scheme, yagi_hip_msequence src,
+                                       yagi_hip_symstreamcf *q) try {                // new_linear :24-59
+    CHECK_PTR(q);
+    *q = nullptr;
+    if (k < 2) return fail(YAGI_ERR_CONFIG, "samples/symbol must be at least 2");
+    if (m == 0) return fail(YAGI_ERR_CONFIG, "filter delay must be greater than zero");
+    if (!(beta >= 0.0f && beta <= 1.0f)) return fail(YAGI_ERR_CONFIG, "filter excess bandwidth must be in (0,1]");
+    int kind = 0, bps = 0;
+    YG_TRY(yagi_hip_modem_s::kind_of(scheme, &kind, &bps));
+    std::vector<float> h;
+    YG_TRY(firinterp_prototype_taps(ftype, k, m, beta, 0.0f, h));
+    YG_TRY(symstream_check_source(src));
+    auto o = std::make_unique<yagi_hip_symstreamcf_s>();
+    o->fir.bank.st = src->st;
+    YG_TRY(o->init(ftype, k, m, beta, h.data(), h.size(), scheme, src));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_create_taps(size_t k, const float *h, size_t h_len, int scheme, yagi_hip_msequence src,
+                                     yagi_hip_symstreamcf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    if (k < 2) return fail(YAGI_ERR_CONFIG, "samples/symbol must be at least 2");
+    if (h_len && !h) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    if (h_len < k) return fail(YAGI_ERR_CONFIG, "filter length cannot be less than interp factor");
+    int kind = 0, bps = 0;
+    YG_TRY(yagi_hip_modem_s::kind_of(scheme, &kind, &bps));
+    YG_TRY(symstream_check_source(src));
+    auto o = std::make_unique<yagi_hip_symstreamcf_s>();
+    o->fir.bank.st = src->st;
+    const size_t ls = (h_len + k - 1) / k;
+    YG_TRY(o->init(YAGI_FIR_SHAPE_UNKNOWN, k, (ls - 1) / 2, 0.0f, h, h_len, scheme, src));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_destroy(yagi_hip_symstreamcf q) try {
+    if (q) (void)hipStreamSynchronize(q->stream());
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_clone(yagi_hip_symstreamcf q, yagi_hip_symstreamcf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    FirPfb<CRCF> &qb = q->fir.bank;
+    YG_TRY(qb.w.ensure_dev(qb.st));
+    auto o = std::make_unique<yagi_hip_symstreamcf_s>();
+    FirPfb<CRCF> &b = o->fir.bank;
+    o->ftype = q->ftype;
+    o->k = q->k;
+    o->m = q->m;
+    o->beta = q->beta;
+    o->gain = q->gain;
+    o->p = q->p;
+    o->sm = q->sm;
+    o->sg = q->sg;
+    o->smask = q->smask;
+    o->sstate = q->sstate;
+    o->pow = q->pow;
+    o->stride = q->stride;
+    o->run = q->run;
+    o->fir.interp = q->fir.interp;
+    o->fir.hs = q->fir.hs;
+    b.st = qb.st;
+    b.nf = qb.nf;
+    b.Ls = qb.Ls;
+    b.hb = qb.hb;
+    b.scale = qb.scale;
+    YG_TRY(fill(b.taps, b.hb.data(), b.hb.size() * sizeof(float), b.st));
+    YG_TRY(b.w.clone_from(qb.w, qb.st));
+    YG_TRY(yagi_hip_modem_clone(q->modem, &o->modem));
+    YG_TRY(o->alloc_dev());
+    YG_HIP(hipMemcpyAsync(o->dbuf.p, q->dbuf.p, q->k * sizeof(cf32), hipMemcpyDeviceToDevice, b.st));
+    YG_HIP(hipStreamSynchronize(b.st));
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_set_stream(yagi_hip_symstreamcf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->stream() == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->stream()));
+    q->stream() = to_stream(s);
+    q->modem->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_reset(yagi_hip_symstreamcf q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_source_set_state(yagi_hip_symstreamcf q, unsigned a) try {
+    CHECK_Q(q);
+    q->sstate = a;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+SYMSTREAM_GET(source_get_state, unsigned, q->sstate)
+SYMSTREAM_GET(get_ftype, int, q->ftype)                                              // :67-69
+SYMSTREAM_GET(get_k, size_t, q->k)                                                   // :71-73
+SYMSTREAM_GET(get_m, size_t, q->m)                                                   // :75-77
+SYMSTREAM_GET(get_beta, float, q->beta)                                              // :79-81
+SYMSTREAM_GET(get_scheme, int, q->modem->scheme)                                     // :88-90
+SYMSTREAM_GET(get_gain, float, q->gain)                                              // :96-98
+SYMSTREAM_GET(get_delay, size_t, q->k * q->m)                                        // :100-102
+SYMSTREAM_GET(get_buf_index, size_t, (size_t)q->p)
+SYMSTREAM_GET(is_fused, int, q->fused() ? 1 : 0)
+
+int yagi_hip_symstreamcf_set_scheme(yagi_hip_symstreamcf q, int scheme) try {        // :83-86
+    CHECK_Q(q);
+    yagi_hip_modem fresh = nullptr;
+    YG_TRY(yagi_hip_modem_create(scheme, &fresh));
+    return q->set_modem(fresh);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_set_modem(yagi_hip_symstreamcf q, yagi_hip_modem mod) try {
+    CHECK_Q(q);
+    CHECK_Q(mod);
+    yagi_hip_modem fresh = nullptr;
+    YG_TRY(yagi_hip_modem_clone(mod, &fresh));
+    return q->set_modem(fresh);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_set_gain(yagi_hip_symstreamcf q, float gain) try {          // :92-94
+    CHECK_Q(q);
+    q->gain = gain;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_write_samples(yagi_hip_symstreamcf q, yagi_cf32 *y, size_t n) try {      // :111-121
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(y);
+    return q->block_host(nullptr, 0, n, y);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_write_samples_dev(yagi_hip_symstreamcf q, yagi_cf32 *y_dev, size_t n) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(y_dev);
+    return q->block_dev(nullptr, n, y_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_modulate_symbols(yagi_hip_symstreamcf q, const uint8_t *sym, size_t nsym, yagi_cf32 *y) try {
+    CHECK_Q(q);
+    if (nsym == 0) return YAGI_OK;
+    CHECK_PTR(sym);
+    CHECK_PTR(y);
+    if (q->p != 0) return fail(YAGI_ERR_MODE, "modulate_symbols needs a symbol boundary (buf_index is %d)", q->p);
+    for (size_t i = 0; i < nsym; ++i)
+        if ((int)sym[i] >= q->modem->P.M) return fail(YAGI_ERR_RANGE, "input symbol %zu exceeds constellation size", i);
+    return q->block_host(sym, nsym, nsym * q->k, y);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamcf_modulate_symbols_dev(yagi_hip_symstreamcf q, const uint8_t *sym_dev, size_t nsym,
+                                              yagi_cf32 *y_dev) try {
+    CHECK_Q(q);
+    if (nsym == 0) return YAGI_OK;
+    CHECK_PTR(sym_dev);
+    CHECK_PTR(y_dev);
+    if (q->p != 0) return fail(YAGI_ERR_MODE, "modulate_symbols needs a symbol boundary (buf_index is %d)", q->p);
+    CHECK_NOALIAS(sym_dev, nsym, y_dev, nsym * q->k);
+    return q->block_dev(sym_dev, nsym * q->k, y_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"

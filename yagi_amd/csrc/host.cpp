@@ -113,6 +113,143 @@ int design_kaiser(size_t n, float fc, float as_, float mu, std::vector<float> &h
     return YAGI_OK;
 }
 
+// ---- (root-)Nyquist prototypes (design/mod.rs:392-451), single precision like the reference ----------------
+// estimate_req_filter_len_kaiser (design/mod.rs:228-238), [Vaidyanathan:1993]
+static int filter_len_kaiser(float df, float as_, float *n) {
+    if (df > 0.5f || df <= 0.0f) return fail(YAGI_ERR_CONFIG, "cutoff frequency (%g) out of range (0, 0.5)", (double)df);
+    if (as_ <= 0.0f) return fail(YAGI_ERR_CONFIG, "stopband attenuation must be greater than zero");
+    *n = (as_ - 7.95f) / (14.26f * df);
+    return YAGI_OK;
+}
+
+// estimate_req_filter_stopband_attenuation (design/mod.rs:161-184): twenty bisections of [0.01, 200] dB on the Kaiser
+// length estimate
+int estimate_stopband_attenuation(float df, size_t n, float *as_) {
+    float as0 = 0.01f, as1 = 200.0f, as_hat = 0.0f;
+    for (int it = 0; it < 20; ++it) {
+        as_hat = 0.5f * (as1 + as0);
+        float n_hat = 0.0f;
+        YG_TRY(filter_len_kaiser(df, as_hat, &n_hat));
+        if (n_hat < static_cast<float>(n)) as0 = as_hat;
+        else as1 = as_hat;
+    }
+    *as_ = as_hat;
+    return YAGI_OK;
+}
+
+static int check_nyquist_args(size_t k, size_t m, float beta) {       // rcos.rs:18-26, rrcos.rs:16-24
+    if (k < 1) return fail(YAGI_ERR_CONFIG, "k must be greater than 0");
+    if (m < 1) return fail(YAGI_ERR_CONFIG, "m must be greater than 0");
+    if (beta < 0.0f || beta > 1.0f) return fail(YAGI_ERR_CONFIG, "beta must be in [0,1]");
+    return YAGI_OK;
+}
+
+// fir_design_rcos (rcos.rs:17-51)
+static int design_rcos(size_t k, size_t m, float beta, float dt, std::vector<float> &h) {
+    YG_TRY(check_nyquist_args(k, m, beta));
+    const float pi = 3.14159265358979323846f;
+    const float kf = static_cast<float>(k), mf = static_cast<float>(m);
+    h.resize(2 * k * m + 1);
+    for (size_t n = 0; n < h.size(); ++n) {
+        const float z = (static_cast<float>(n) + dt) / kf - mf;
+        const float t1 = std::cos(beta * pi * z);
+        const float t2 = sinc(z);
+        const float t3 = 1.0f - 4.0f * beta * beta * z * z;
+        // where 4 beta^2 z^2 reaches 1 the quotient is 0 / 0: its limit
+        h[n] = std::fabs(t3) < 1e-3f ? std::sin(pi / (2.0f * beta)) * beta * 0.5f : t1 * t2 / t3;
+    }
+    return YAGI_OK;
+}
+
+// fir_design_rrcos (rrcos.rs:15-63): the closed form and its two limits, at z = 0 and at 16 beta^2 z^2 = 1
+static int design_rrcos(size_t k, size_t m, float beta, float dt, std::vector<float> &h) {
+    YG_TRY(check_nyquist_args(k, m, beta));
+    const float pi = 3.14159265358979323846f;
+    const float kf = static_cast<float>(k), mf = static_cast<float>(m);
+    h.resize(2 * k * m + 1);
+    for (size_t n = 0; n < h.size(); ++n) {
+        const float z = (static_cast<float>(n) + dt) / kf - mf;
+        if (std::fabs(z) < 1e-5f) {
+            h[n] = 1.0f - beta + 4.0f * beta / pi;
+            continue;
+        }
+        float g = 1.0f - 16.0f * beta * beta * z * z;
+        g *= g;
+        if (std::fabs(g) < 1e-5f) {
+            const float g1 = 1.0f + 2.0f / pi, g2 = std::sin(0.25f * pi / beta);
+            const float g3 = 1.0f - 2.0f / pi, g4 = std::cos(0.25f * pi / beta);
+            h[n] = beta / std::sqrt(2.0f) * (g1 * g2 + g3 * g4);
+        } else {
+            const float t1 = std::cos((1.0f + beta) * pi * z);
+            const float t2 = std::sin((1.0f - beta) * pi * z);
+            const float t3 = 1.0f / (4.0f * beta * z);
+            const float t4 = 4.0f * beta / (pi * (1.0f - (16.0f * beta * beta * z * z)));
+            h[n] = t4 * (t1 + (t2 * t3));
+        }
+    }
+    return YAGI_OK;
+}
+
+// fir_design_arkaiser (rkaiser.rs:49-93): a Kaiser-windowed sinc whose transition band is narrowed by rho and whose
+// cutoff is moved up to match, rho from the closed form rho ~ c0 + c1 ln(beta) + c2 ln^2(beta); normalised to sum h^2 = k.
+// Where that form leaves (0, 1) the reference falls back on a table of fitted constants (rkaiser.rs:105-144), which is
+// not part of this library: those shapes are a configuration error here.
+static int design_arkaiser(size_t k, size_t m, float beta, float dt, std::vector<float> &h) {
+    if (k < 2) return fail(YAGI_ERR_CONFIG, "k must be at least 2");
+    if (m < 1) return fail(YAGI_ERR_CONFIG, "m must be at least 1");
+    if (beta <= 0.0f || beta >= 1.0f) return fail(YAGI_ERR_CONFIG, "beta must be in (0,1)");
+    if (dt < -1.0f || dt > 1.0f) return fail(YAGI_ERR_CONFIG, "dt must be in [-1,1]");
+    const float mf = static_cast<float>(m);
+    const float c0 = 0.762886f + 0.067663f * std::log(mf);
+    const float c1 = 0.065515f;
+    const float c2 = std::log(1.0f - 0.088f * std::pow(mf, -1.6f));
+    const float log_beta = std::log(beta);
+    const float rho_hat = c0 + c1 * log_beta + c2 * log_beta * log_beta;
+    if (!(rho_hat > 0.0f && rho_hat < 1.0f))
+        return fail(YAGI_ERR_CONFIG,
+                    "arkaiser: the closed-form bandwidth correction rho (%g) leaves (0, 1) at m = %zu, beta = %g; "
+                    "the reference's fitted fallback table is not part of this library",
+                    (double)rho_hat, m, (double)beta);
+    const size_t n = 2 * k * m + 1;
+    const float kf = static_cast<float>(k);
+    const float del = beta * rho_hat / kf;
+    float as_ = 0.0f;
+    YG_TRY(estimate_stopband_attenuation(del, n, &as_));
+    const float fc = 0.5f * (1.0f + beta * (1.0f - rho_hat)) / kf;
+    YG_TRY(design_kaiser(n, fc, as_, dt, h));
+    float e2 = 0.0f;
+    for (float v : h) e2 += v * v;
+    const float s = std::sqrt(kf / e2);
+    for (float &v : h) v *= s;
+    return YAGI_OK;
+}
+
+// fir_design_prototype (design/mod.rs:392-451) for the shapes built here; ftype is numbered as FirFilterShape
+// (design/mod.rs:41-77).  The stop-band estimate comes first, as there, so beta = 0 fails in it for every shape.
+int design_prototype(int ftype, size_t k, size_t m, float beta, float dt, std::vector<float> &h) {
+    static const char *const names[] = {"kaiser", "pm", "rcos", "fexp", "fsech", "farcsech", "arkaiser", "rkaiser",
+                                        "rrcos", "hm3", "gmsktx", "gmskrx", "rfexp", "rfsech", "rfarcsech"};
+    if (ftype < 0 || ftype >= (int)(sizeof names / sizeof *names)) return fail(YAGI_ERR_CONFIG, "unknown filter shape %d", ftype);
+    if (ftype != YAGI_FIR_SHAPE_KAISER && ftype != YAGI_FIR_SHAPE_RCOS && ftype != YAGI_FIR_SHAPE_RRCOS &&
+        ftype != YAGI_FIR_SHAPE_ARKAISER)
+        return fail(YAGI_ERR_CONFIG, "filter shape %s is not built (its design code is not part of this library)", names[ftype]);
+    if (k < 1) return fail(YAGI_ERR_CONFIG, "k must be greater than 0");
+    if (m < 1) return fail(YAGI_ERR_CONFIG, "m must be greater than 0");
+    if (k > ((size_t)1 << 20) || m > ((size_t)1 << 20) || k * m > ((size_t)1 << 24))
+        return fail(YAGI_ERR_CONFIG, "prototype too long (k = %zu, m = %zu)", k, m);
+    const size_t h_len = 2 * k * m + 1;
+    const float fc = 0.5f / static_cast<float>(k);
+    const float df = beta / static_cast<float>(k);
+    float as_ = 0.0f;
+    YG_TRY(estimate_stopband_attenuation(df, h_len, &as_));
+    switch (ftype) {
+    case YAGI_FIR_SHAPE_KAISER: return design_kaiser(h_len, fc, as_, dt, h);
+    case YAGI_FIR_SHAPE_RCOS: return design_rcos(k, m, beta, dt, h);
+    case YAGI_FIR_SHAPE_RRCOS: return design_rrcos(k, m, beta, dt, h);
+    default: return design_arkaiser(k, m, beta, dt, h);
+    }
+}
+
 // fir_design_notch (design/mod.rs:336-378): 1 - (Kaiser-windowed tone at f0, normalised to unit gain at f0)
 int design_notch(size_t m, float f0, float as_, std::vector<float> &h) {
     if (m < 1 || m > 1000) return fail(YAGI_ERR_CONFIG, "filter semi-length (%zu) out of range [1,1000]", m);
@@ -662,6 +799,19 @@ int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h
     std::memcpy(h, v.data(), n * sizeof(float));
     return YAGI_OK;
 }
+
+int yagi_hip_estimate_req_filter_stopband_attenuation(float df, size_t n, float *as_) try {
+    if (!as_) return yagi::fail(YAGI_ERR_CONFIG, "null output pointer");
+    return yagi::estimate_stopband_attenuation(df, n, as_);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_fir_design_prototype(int ftype, size_t k, size_t m, float beta, float dt, float *h) try {
+    std::vector<float> v;
+    YG_TRY(yagi::design_prototype(ftype, k, m, beta, dt, v));
+    if (!h) return yagi::fail(YAGI_ERR_CONFIG, "null output pointer");
+    std::memcpy(h, v.data(), v.size() * sizeof(float));
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
 
 // extension: the 2m taps of FirHilbertFilter::new (firhilb.rs:43-64); no device needed
 int yagi_hip_firhilb_design(size_t m, float as_, float *hq) try {

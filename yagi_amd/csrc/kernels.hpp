@@ -482,4 +482,30 @@ int launch_autocorr(int W, int d, const T *hist, T *hist_next, const T *x, size_
 template <class T>
 void autocorr_host(const T *h, int W, int d, T *rxx, float *energy);
 
+// ---- symstream_kernels.hip -----------------------------------------------------------------
+// SymStream (yagi_hip.h): samples [0, n) of a call that starts at buf_index p, from the carried window `win` (Ls values,
+// oldest first) and new symbols that come either from the caller's bytes (sym, flag = the result of
+// launch_symstream_check on them, null where M = 256) or from the LFSR (src).  hb = the interpolator's [k][Ls] branch
+// taps, map = the modem's M points.  win_next receives the window the call leaves where it pushes at least one symbol
+// (ceil((p + n) / k) - (p > 0) of them: the caller flips then), buf[i] branch i of the last symbol for the branches
+// the call does not write.  Served shapes: symstream_fused_serves.
+constexpr int kSymStrides = 8;                         // lane-stride matrices: one per bit of the lane number in a workgroup
+constexpr size_t kSymStrideWords = (size_t)8 * kSymStrides * 32;
+struct SymSource {
+    const unsigned *pow, *stride;                      // device: T^(2^b) (kMseqPowWords); symstream_strides' table
+    unsigned s0, g, nmask;
+    int m, bps, run;                                   // run = symstream_run(k, Ls), what `stride` was built for
+};
+int symstream_max_slots(int k, int Ls);                // most symbol slots a workgroup stages (a multiple of the bank tile)
+int symstream_wg_slots(int k, int Ls, size_t nslots);  // slots per workgroup of a call that touches nslots
+int symstream_run(int k, int Ls);                      // consecutive symbols a lane generates
+void symstream_strides(const unsigned *pow, int run, unsigned *stride);   // T^(run * bps * 2^b), bps = 1 .. 8, b < 8
+size_t symstream_lds_bytes(int k, int Ls, int M, int wg_slots);   // dynamic LDS of the fused launch
+bool symstream_fused_serves(int k, int Ls, int M);
+int launch_symstream(const cf32 *win, const float *hb, int k, int Ls, float scale, const cf32 *map, int M, float gain,
+                     const uint8_t *sym, const int *flag, const SymSource *src, int p, size_t n, cf32 *y, cf32 *win_next,
+                     cf32 *buf, hipStream_t st);
+int launch_symstream_check(int M, const uint8_t *sym, size_t n, int *flag, hipStream_t st);   // zeroes flag first
+int launch_symstream_gain(cf32 *v, size_t n, float gain, hipStream_t st);                    // v[i] = (re gain, im gain)
+
 }  // namespace yagi
