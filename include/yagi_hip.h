@@ -600,6 +600,22 @@ int yagi_hip_plan_firpfb_all_range(size_t elem, size_t coeff_elem, size_t nf, si
 int yagi_hip_plan_rresamp_range(size_t elem, size_t P, size_t Q, size_t Ls0, size_t count, yagi_hip_plan *out);
 int yagi_hip_plan_resamp_range(size_t elem, size_t Ls0, size_t count, uint32_t step, yagi_hip_plan *out);
 
+/* What a Spgram write of `nframes` transforms (2 <= nfft <= 2^20, 1 <= nframes < 2^31) would launch, answered by the
+ * functions the launch itself calls; no device is needed.  A call is cut into launches of at most launch_frames
+ * transforms; the other fields describe the first launch, of min(nframes, launch_frames) transforms.
+ *   fused = 1 (nfft in {256, 512, 1024, 2048, 4096}): one kernel tapers, transforms and accumulates.  group = frames
+ *           transformed together (4096 / nfft), slab = consecutive transforms per workgroup (a multiple of group),
+ *           rows = workgroups * group partial rows of nfft floats; folded = 1 when the rows are first summed 32 to 1
+ *           into fold_rows rows (rows > 64).  launch_frames = 2^20, accum_slab = 0.
+ *   fused = 0: frame builder, batched FFT, two-stage accumulation.  workgroups = the frame builder's grid (it strides
+ *           beyond 8192 workgroups), accum_slab = frames per Horner slab (32), rows = slabs, group = 1, slab = 0,
+ *           launch_frames = 2^25 / nfft clamped to [1, 8192]. */
+typedef struct {
+    int fused, group, slab, workgroups, rows, folded, fold_rows, accum_slab;
+    size_t launch_frames;
+} yagi_hip_spgram_plan;
+int yagi_hip_plan_spgram(size_t nfft, size_t nframes, yagi_hip_spgram_plan *out);
+
 /* ---- Fft<f32>: src/fft/mod.rs:33-69 (arithmetic = rustfft 6.2 in the reference) ------------
  *   create       Fft::new(n, direction)        :39-43   any n >= 1 the engine supports
  *   run          run(input, output)            :45-48   out of place, unnormalised,

@@ -36,7 +36,7 @@ __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
     "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
-    "Plan", "plan_fir_block", "plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
+    "Plan", "SpgramPlan", "plan_spgram", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
     "estimate_req_filter_stopband_attenuation", "SymStream", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
@@ -262,6 +262,19 @@ def _plan_range(fn, count, *args):
 def plan_fir_block(elem, L, M, ny):
     """yagi_hip_plan_fir_block: FirFilter kernel 1 (M = 1), FirDecimationFilter, Ddc's fused kernel"""
     return _plan(lib.yagi_hip_plan_fir_block, elem, L, M, ny)
+
+
+SpgramPlan = collections.namedtuple("SpgramPlan",
+                                    "fused group slab workgroups rows folded fold_rows launch_frames accum_slab")
+
+
+def plan_spgram(nfft, nframes):
+    """yagi_hip_plan_spgram: what a Spgram write of nframes transforms launches (its first launch; a call is cut every
+    launch_frames transforms)"""
+    p = _capi.spgram_plan()
+    _check(lib.yagi_hip_plan_spgram(nfft, nframes, C.byref(p)))
+    return SpgramPlan(p.fused, p.group, p.slab, p.workgroups, p.rows, p.folded, p.fold_rows, p.launch_frames,
+                      p.accum_slab)
 
 
 def plan_firpfb_all(elem, coeff_elem, nf, Ls):

@@ -195,6 +195,15 @@ _sig("yagi_hip_plan_firpfb_all_range", sz, sz, sz, sz, sz, vp)
 _sig("yagi_hip_plan_rresamp_range", sz, sz, sz, sz, sz, vp)
 _sig("yagi_hip_plan_resamp_range", sz, sz, sz, C.c_uint32, vp)
 
+
+class spgram_plan(C.Structure):
+    """yagi_hip_spgram_plan"""
+    _fields_ = [("fused", ci), ("group", ci), ("slab", ci), ("workgroups", ci), ("rows", ci), ("folded", ci),
+                ("fold_rows", ci), ("accum_slab", ci), ("launch_frames", sz)]
+
+
+_sig("yagi_hip_plan_spgram", sz, sz, C.POINTER(spgram_plan))
+
 for _k, _T in (("cf", cf32), ("f", f32)):
     p = f"yagi_hip_spgram{_k}_"
     _sig(p + "create", sz, ci, sz, sz, pvp)

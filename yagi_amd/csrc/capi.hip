@@ -1915,7 +1915,7 @@ struct SpgramObj {
     // x_len = samples readable at x (the write() block)
     int run_frames(const T *x, long long first, size_t nframes, size_t x_len = 0) {
         if (spgram_fused_supported(nfft)) {       // fused taper -> FFT -> |X|^2 -> accumulate (spgram_kernels.hip)
-            const size_t big = (size_t)1 << 20;   // transforms per launch
+            const size_t big = spgram_launch_frames(nfft);      // transforms per launch
             for (size_t f0 = 0; f0 < nframes; f0 += big) {
                 const size_t nf = (nframes - f0) < big ? (nframes - f0) : big;
                 YG_TRY(part.ensure(spgram_fused_scratch_floats(nfft, nf) * sizeof(float)));
@@ -1927,8 +1927,7 @@ struct SpgramObj {
             }
             return YAGI_OK;
         }
-        size_t chunk = ((size_t)1 << 25) / (size_t)nfft;          // transforms per batch: 2 x 256 MiB of frames at most
-        chunk = chunk < 1 ? 1 : (chunk > 8192 ? 8192 : chunk);
+        const size_t chunk = spgram_launch_frames(nfft);        // transforms per batch: 2 x 256 MiB of frames at most
         for (size_t f0 = 0; f0 < nframes; f0 += chunk) {
             const size_t nf = (nframes - f0) < chunk ? (nframes - f0) : chunk;
             YG_TRY(tbuf.ensure(nf * (size_t)nfft * sizeof(cf32)));

@@ -206,6 +206,20 @@ int launch_spgram_fused(int nfft, const T *win, const T *x, size_t x_len, const 
                         int delay, size_t nframes, float alpha, float gamma, bool first_ever, const cf32 *twn,
                         float *psd, float *part, hipStream_t st);
 int launch_spgram_psd(const float *psd, int nfft, float scale, bool in_db, float *out, hipStream_t st);
+// the launch arithmetic, shared by the launchers, SpgramObj::run_frames and yagi_hip_plan_spgram:
+//   spgram_launch_frames  transforms per launch of run_frames (the cut of a longer call)
+//   spgram_fused_slab     consecutive transforms per workgroup of a fused launch of nframes (a multiple of the group)
+//   spgram_fused_rows     workgroups, partial rows and the 32-to-1 fold of that launch
+//   spgram_frames_grid    workgroups of the unfused frame builder (grid-stride beyond the cap)
+struct SpgramFusedRows {
+    unsigned group, slab, workgroups, rows, fold_rows;           // fold_rows = 0 unless folded
+    bool folded;
+};
+size_t spgram_launch_frames(int nfft);
+unsigned spgram_fused_slab(int nfft, size_t nframes);
+SpgramFusedRows spgram_fused_rows(int nfft, size_t nframes);
+unsigned spgram_frames_grid(int nfft, size_t nframes);
+int spgram_accum_slab();
 
 // ---- chan_kernels.hip ----------------------------------------------------------------------
 // firpfbch analyzer: hist = the (p-1)*M samples preceding x[0] (oldest first).

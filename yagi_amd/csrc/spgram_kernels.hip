@@ -252,11 +252,13 @@ static unsigned sp_grid(size_t total) {
     size_t g = (total + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
+unsigned spgram_frames_grid(int nfft, size_t nframes) { return sp_grid(nframes * (size_t)nfft); }
+int spgram_accum_slab() { return kSpSlab; }
 
 template <class T>
 int launch_spgram_frames(const T *win, const T *x, const float *w, int wlen, int nfft, long long first,
                          int delay, size_t nframes, cf32 *time, hipStream_t st) {
-    spgram_frames_kernel<T><<<sp_grid(nframes * (size_t)nfft), 256, 0, st>>>(
+    spgram_frames_kernel<T><<<spgram_frames_grid(nfft, nframes), 256, 0, st>>>(
         win, x, w, wlen, nfft, first, delay, nframes, reinterpret_cast<float2 *>(time));
     YG_LAUNCH_CHECK();
     return YAGI_OK;
@@ -283,15 +285,30 @@ int launch_spgram_accum(const cf32 *freq, int nfft, size_t nframes, float alpha,
 }
 // fused paths: nfft = 4096 and nfft = 256 M (M in {1,2,4,8}); part: spgram_fused_scratch_floats(nfft, nframes) floats
 bool spgram_fused_supported(int nfft) { return nfft == 256 || nfft == 512 || nfft == 1024 || nfft == 2048 || nfft == 4096; }
-static unsigned spgram_fused_slab(int nfft, size_t nframes) {
+unsigned spgram_fused_slab(int nfft, size_t nframes) {
     const unsigned B = (unsigned)(4096 / nfft);                  // frames transformed together
     size_t sl = nframes / 1024;
     sl = sl < 4 ? 4 : (sl > 32 ? 32 : sl);
     return (unsigned)((sl + B - 1) / B * B);
 }
+SpgramFusedRows spgram_fused_rows(int nfft, size_t nframes) {
+    SpgramFusedRows r{};
+    r.group = (unsigned)(4096 / nfft);
+    r.slab = spgram_fused_slab(nfft, nframes);
+    r.workgroups = (unsigned)((nframes + r.slab - 1) / r.slab);
+    r.rows = r.workgroups * r.group;                             // B rows of nfft floats per workgroup
+    r.folded = r.rows > 2 * kSpFold;                             // many rows: fold them 32 to 1 across the whole chip first
+    r.fold_rows = r.folded ? (r.rows + kSpFold - 1) / kSpFold : 0;
+    return r;
+}
+// transforms per launch of SpgramObj::run_frames.  Fused: 2^20.  Unfused: 2 x 256 MiB of frames at most
+size_t spgram_launch_frames(int nfft) {
+    if (spgram_fused_supported(nfft)) return (size_t)1 << 20;
+    const size_t chunk = ((size_t)1 << 25) / (size_t)nfft;
+    return chunk < 1 ? 1 : (chunk > 8192 ? 8192 : chunk);
+}
 size_t spgram_fused_scratch_floats(int nfft, size_t nframes) {
-    const unsigned slab = spgram_fused_slab(nfft, nframes);
-    const size_t rows_floats = ((nframes + slab - 1) / slab) * (size_t)4096;      // B rows of nfft floats per workgroup
+    const size_t rows_floats = (size_t)spgram_fused_rows(nfft, nframes).workgroups * 4096;
     return rows_floats + rows_floats / kSpFold + 4096;           // + the folded rows of the two-level sum
 }
 template <class T>
@@ -300,8 +317,8 @@ int launch_spgram_fused(int nfft, const T *win, const T *x, size_t x_len, const 
                         float *psd, float *part, hipStream_t st) {
     if (nframes == 0) return YAGI_OK;
     if (nframes > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "too many transforms in one call");
-    const unsigned slab = spgram_fused_slab(nfft, nframes);
-    const unsigned nwg = (unsigned)((nframes + slab - 1) / slab);
+    const SpgramFusedRows pr = spgram_fused_rows(nfft, nframes);
+    const unsigned slab = pr.slab, nwg = pr.workgroups;
     const float l2g = (float)std::log2((double)gamma);
     const float2 *tw = reinterpret_cast<const float2 *>(twn);
 #define YG_SP_ARGS win, x, w, wlen, first, (long long)x_len, delay, (unsigned)nframes, slab, alpha, l2g, first_ever ? 1 : 0, tw, part
@@ -315,11 +332,11 @@ int launch_spgram_fused(int nfft, const T *win, const T *x, size_t x_len, const 
     }
 #undef YG_SP_ARGS
     YG_LAUNCH_CHECK();
-    unsigned nrows = nwg * (unsigned)(4096 / nfft);
+    unsigned nrows = pr.rows;
     const float *rows = part;
-    if (nrows > 2 * kSpFold) {                                   // many rows: fold them 32 to 1 across the whole chip first
+    if (pr.folded) {
         float *folded = part + (size_t)nrows * nfft;
-        const unsigned nf = (nrows + kSpFold - 1) / kSpFold;
+        const unsigned nf = pr.fold_rows;
         spgram_fold_kernel<<<dim3((unsigned)((nfft + 255) / 256), nf), 256, 0, st>>>(part, nfft, nrows, folded);
         YG_LAUNCH_CHECK();
         rows = folded;
@@ -340,3 +357,30 @@ int launch_spgram_psd(const float *psd, int nfft, float scale, bool in_db, float
 }
 
 }  // namespace yagi
+
+extern "C" int yagi_hip_plan_spgram(size_t nfft, size_t nframes, yagi_hip_spgram_plan *out) try {
+    using namespace yagi;
+    if (!out) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    if (nfft < 2 || nfft > ((size_t)1 << 20) || nframes < 1 || nframes > 0x7fffffffull)
+        return fail(YAGI_ERR_CONFIG, "plan query: bad shape (2 <= nfft <= 2^20, 1 <= nframes < 2^31)");
+    yagi_hip_spgram_plan o{};
+    o.launch_frames = spgram_launch_frames((int)nfft);
+    const size_t nf = nframes < o.launch_frames ? nframes : o.launch_frames;      // the first launch of the call
+    if (spgram_fused_supported((int)nfft)) {
+        const SpgramFusedRows r = spgram_fused_rows((int)nfft, nf);
+        o.fused = 1;
+        o.group = (int)r.group;
+        o.slab = (int)r.slab;
+        o.workgroups = (int)r.workgroups;
+        o.rows = (int)r.rows;
+        o.folded = r.folded ? 1 : 0;
+        o.fold_rows = (int)r.fold_rows;
+    } else {
+        o.group = 1;
+        o.accum_slab = spgram_accum_slab();
+        o.workgroups = (int)spgram_frames_grid((int)nfft, nf);
+        o.rows = (int)(spgram_accum_scratch_floats((int)nfft, nf) / nfft);
+    }
+    *out = o;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
