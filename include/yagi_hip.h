@@ -1520,6 +1520,77 @@ YAGI_AUTOCORR_API(cccf, yagi_cf32)
 YAGI_AUTOCORR_API(rrrf, float)
 #undef YAGI_AUTOCORR_API
 
+/* ---- BurstDetector: Autocorr, a normalised threshold and run / peak extraction in one object ------------------------
+ * Absent from the reference; defined by composition of what this library already pins.
+ * BurstDetector<T>(W, d, threshold, energy_floor, min_length), T = Complex<f32> (cccf) or f32 (rrrf).  Let rxx[n] and
+ * energy[n] be Autocorr(W, d)'s outputs on the stream since reset(), n the absolute sample index (the first sample is
+ * 0), and thr2 = fl(threshold * threshold), formed once on the host.  All arithmetic is f32; every product, add and
+ * quotient is rounded on its own (no FMA):
+ *     m[n]   = fl(fl(re^2) + fl(im^2)) of rxx[n]                 (rrrf: fl(rxx^2))
+ *     q[n]   = fl(energy[n]^2)
+ *     hit[n] = energy[n] > energy_floor && m[n] > fl(thr2 * q[n])  strict, so a NaN anywhere gives no hit; at W = 1,
+ *                                                                d = 0, where m = q, a threshold >= 1 never fires
+ *     r[n]   = m[n] / q[n]                                       IEEE division, looked at only where hit[n]
+ * A run is a maximal set of consecutive hits; its peak is the index of its largest r, the earliest on ties (+Inf
+ * included).  The first non-hit after a run closes it; a run whose last hit is the last sample seen so far is pending,
+ * and a later call extends or closes it.  An event is a closed run with length >= min_length.  A block call returns the
+ * events its samples close, ordered by start.  However a stream is cut into calls, the concatenated list is the same,
+ * but for:
+ * Capacity.  Inside a call the device sees runs cut at its tiles (YAGI_AUTOCORR_TILE consecutive samples counted from
+ * the call's first); call those pieces segments.  A call may hold tiles + YAGI_BURSTDET_SEGMAX segments: a burst of any
+ * length costs one per tile, and SEGMAX more are free.  A call with more still pushes its samples, reports
+ * overflow = 1, writes no events and drops the pending run; a run that continues into the next call starts there.
+ * Events buffer.  The call reports the number of events and writes the first cap of them, as snprintf does.
+ *   create(W, d, threshold, energy_floor, min_length)   W and d as for Autocorr; threshold finite and > 0, energy_floor
+ *                             finite and >= 0, min_length >= 1; anything else is YAGI_ERR_CONFIG
+ *   clone / reset             a copy of history, pending run and sample counter / all three cleared
+ *   get_window_size / get_delay / get_threshold / get_energy_floor / get_min_length / get_position
+ *   get_pending(&has, &ev)    the pending run so far (length and peak up to the last sample seen); synchronises
+ *   detect_block(x, n, events, cap, &count, &overflow)   host slices, staged through the device
+ *   detect_block_dev(x_dev, n, events_dev, cap, status_dev)   status_dev = uint32_t[2] {count, overflow}; asynchronous on
+ *                             the object's stream, no host synchronisation.  n = 0 writes {0, 0}.  events_dev may be
+ *                             NULL where cap = 0.
+ *   flush(events, cap, &count)   closes the pending run, an event if it is long enough; the sample counter stays
+ *   detect_host(...)          the definition on the host alone (no device needed), one call on a stream from reset():
+ *                             the sequential state machine over Autocorr's host arithmetic, the capacity rule included
+ * Not built: merging runs across gaps, a per-sample push, a known-preamble cross-correlation front
+ * end, soft outputs, sharding.
+ * Device form: burstdet_kernels.hip: a tile kernel and a one-workgroup stitch kernel per call; the stitch walks a
+ * call's segments one by one, about 0.3 us each on an MI355X, so a block that is all burst costs milliseconds. */
+#define YAGI_BURSTDET_SEGMAX 8192
+typedef struct yagi_burst_event {
+    uint64_t start, length, peak;            /* absolute sample indices */
+    float ratio, energy, rxx_re, rxx_im;     /* r, energy and rxx at the peak; rrrf: rxx_im = +0.0 */
+} yagi_burst_event;
+typedef struct yagi_hip_burstdet_cccf_s *yagi_hip_burstdet_cccf;
+typedef struct yagi_hip_burstdet_rrrf_s *yagi_hip_burstdet_rrrf;
+#define YAGI_BURSTDET_API(K, T)                                                                                       \
+    int yagi_hip_burstdet_##K##_create(size_t window_size, size_t delay, float threshold, float energy_floor,         \
+                                       uint64_t min_length, yagi_hip_burstdet_##K *q);                                \
+    int yagi_hip_burstdet_##K##_destroy(yagi_hip_burstdet_##K q);                                                      \
+    int yagi_hip_burstdet_##K##_clone(yagi_hip_burstdet_##K q, yagi_hip_burstdet_##K *out);                            \
+    int yagi_hip_burstdet_##K##_set_stream(yagi_hip_burstdet_##K q, yagi_stream_t s);                                  \
+    int yagi_hip_burstdet_##K##_reset(yagi_hip_burstdet_##K q);                                                        \
+    int yagi_hip_burstdet_##K##_get_window_size(yagi_hip_burstdet_##K q, size_t *window_size);                         \
+    int yagi_hip_burstdet_##K##_get_delay(yagi_hip_burstdet_##K q, size_t *delay);                                     \
+    int yagi_hip_burstdet_##K##_get_threshold(yagi_hip_burstdet_##K q, float *threshold);                              \
+    int yagi_hip_burstdet_##K##_get_energy_floor(yagi_hip_burstdet_##K q, float *energy_floor);                        \
+    int yagi_hip_burstdet_##K##_get_min_length(yagi_hip_burstdet_##K q, uint64_t *min_length);                         \
+    int yagi_hip_burstdet_##K##_get_position(yagi_hip_burstdet_##K q, uint64_t *position);                             \
+    int yagi_hip_burstdet_##K##_get_pending(yagi_hip_burstdet_##K q, int *has_pending, yagi_burst_event *ev);          \
+    int yagi_hip_burstdet_##K##_detect_block(yagi_hip_burstdet_##K q, const T *x, size_t n, yagi_burst_event *events,  \
+                                             size_t cap, size_t *count, int *overflow);                               \
+    int yagi_hip_burstdet_##K##_detect_block_dev(yagi_hip_burstdet_##K q, const T *x_dev, size_t n,                    \
+                                                 yagi_burst_event *events_dev, size_t cap, uint32_t *status_dev);     \
+    int yagi_hip_burstdet_##K##_flush(yagi_hip_burstdet_##K q, yagi_burst_event *events, size_t cap, size_t *count);   \
+    int yagi_hip_burstdet_##K##_detect_host(size_t window_size, size_t delay, float threshold, float energy_floor,    \
+                                            uint64_t min_length, const T *x, size_t n, yagi_burst_event *events,      \
+                                            size_t cap, size_t *count, int *overflow, int *has_pending,               \
+                                            yagi_burst_event *pending);
+YAGI_BURSTDET_API(cccf, yagi_cf32)
+YAGI_BURSTDET_API(rrrf, float)
+#undef YAGI_BURSTDET_API
+
 /* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */
 

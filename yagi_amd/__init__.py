@@ -17,6 +17,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     Modem, ModulationScheme    src/modem/modem.rs:27-575 (the linear schemes and from_table)
     MSequence / BSequence      src/sequence/msequence.rs:41-164, bsequence.rs:8-195
     Autocorr                   (absent from the reference: src/filter/autocorr.rs is empty)
+    BurstDetector              (absent from the reference: Autocorr, threshold and run / peak extraction fused)
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -35,7 +36,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "SpgramPlan", "plan_spgram", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
@@ -1836,6 +1837,105 @@ class Autocorr(_Handle):
         (ConfigError); asynchronous on the object's stream"""
         _check(self._fn("execute_block_dev")(self._h, _devptr(x_dev), n, _devptr(rxx_dev),
                                              None if energy_dev is None else _devptr(energy_dev)))
+
+
+BURSTDET_SEGMAX = 8192   # YAGI_BURSTDET_SEGMAX: segments a BurstDetector call may hold beyond one per tile
+# yagi_burst_event: start, length and peak are absolute sample indices; ratio, energy and rxx are taken at the peak
+BURST_EVENT = np.dtype([("start", np.uint64), ("length", np.uint64), ("peak", np.uint64), ("ratio", np.float32),
+                        ("energy", np.float32), ("rxx_re", np.float32), ("rxx_im", np.float32)])
+
+
+class BurstDetector(_Handle):
+    """BurstDetector<T>(W, d, threshold, energy_floor=0, min_length=1), T = Complex<f32> ("cccf") or f32 ("rrrf"):
+    Autocorr(W, d), the test hit[n] = energy[n] > energy_floor and |rxx[n]|^2 > threshold^2 energy[n]^2, and the runs
+    of consecutive hits with their peaks (the largest |rxx|^2 / energy^2, the earliest on ties), all in f32 and rounded
+    as yagi_hip.h and DESIGN.md section 6 say.  A block call reads the samples and returns only the events they close
+    (BURST_EVENT records, ordered by start); a run that reaches the call's last sample stays pending for the next call
+    or flush().  A call whose runs fall into more than tiles + BURSTDET_SEGMAX per-tile segments reports overflow and no
+    events.  The block calls run burstdet_kernels.hip."""
+
+    def __init__(self, kind, window_size, delay, threshold, energy_floor=0.0, min_length=1):
+        if kind not in ("cccf", "rrrf"):
+            raise ConfigError(f"unknown type combination {kind!r}")
+        if not (isinstance(min_length, (int, np.integer)) and 0 <= min_length < 2 ** 64):
+            raise ConfigError("min_length must be an integer of at least one")
+        self.kind = kind
+        self.T = KINDS[kind][0]
+        self._prefix = f"yagi_hip_burstdet_{kind}_"
+        hd = C.c_void_p()
+        _check(self._fn("create")(window_size, delay, threshold, energy_floor, min_length, C.byref(hd)))
+        self._h = hd
+
+    def clone(self):
+        new = object.__new__(type(self))
+        new.kind, new.T, new._prefix = self.kind, self.T, self._prefix
+        hd = C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._h = hd
+        return new
+
+    def _get(self, name, ctype):
+        v = ctype()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return v.value
+
+    window_size = property(lambda self: self._get("get_window_size", C.c_size_t))
+    delay = property(lambda self: self._get("get_delay", C.c_size_t))
+    threshold = property(lambda self: np.float32(self._get("get_threshold", C.c_float)))
+    energy_floor = property(lambda self: np.float32(self._get("get_energy_floor", C.c_float)))
+    min_length = property(lambda self: self._get("get_min_length", C.c_uint64))
+
+    @property
+    def position(self):
+        """samples seen since reset(); synchronises"""
+        return self._get("get_position", C.c_uint64)
+
+    @property
+    def pending(self):
+        """the run that reaches the last sample seen, as a BURST_EVENT record so far, or None; synchronises"""
+        has, ev = C.c_int(), np.zeros(1, BURST_EVENT)
+        _check(self._fn("get_pending")(self._h, C.byref(has), _ptr(ev)))
+        return ev[0] if has.value else None
+
+    def detect_block(self, x, cap=None):
+        """pushes x and returns (events, overflow): the BURST_EVENT records the block closes, at most cap of them where
+        cap is given (events.size is then min(count, cap); the count is the third item of the tuple in that case)"""
+        x = _arr(x, self.T)
+        room = (x.size + AUTOCORR_TILE - 1) // AUTOCORR_TILE + BURSTDET_SEGMAX + 1 if cap is None else int(cap)
+        ev = np.zeros(room, BURST_EVENT)
+        count, over = C.c_size_t(), C.c_int()
+        _check(self._fn("detect_block")(self._h, _ptr(x), x.size, _ptr(ev), room, C.byref(count), C.byref(over)))
+        ev = ev[:min(count.value, room)].copy()
+        return (ev, bool(over.value)) if cap is None else (ev, bool(over.value), count.value)
+
+    def detect_block_devptr(self, x_dev, n, events_dev, cap, status_dev):
+        """x_dev: n samples; events_dev: room for cap BURST_EVENT records (None where cap is 0); status_dev: two uint32
+        that receive (count, overflow).  min(count, cap) records are written.  The buffers must not overlap
+        (ConfigError); asynchronous on the object's stream, no host synchronisation"""
+        x_dev, events_dev, status_dev = (None if p is None else _devptr(p) for p in (x_dev, events_dev, status_dev))
+        _check(self._fn("detect_block_dev")(self._h, x_dev, n, events_dev, cap, status_dev))
+
+    def flush(self):
+        """closes the pending run: one event if it is long enough, else none; position is unchanged"""
+        ev, count = np.zeros(1, BURST_EVENT), C.c_size_t()
+        _check(self._fn("flush")(self._h, _ptr(ev), 1, C.byref(count)))
+        return ev[:count.value].copy()
+
+
+def burst_detect_host(kind, x, window_size, delay, threshold, energy_floor=0.0, min_length=1):
+    """BurstDetector's definition on the host alone, no device needed: one call on a stream from reset().  Returns
+    (events, overflow, pending), pending a BURST_EVENT record or None.  It is the library's own sequential form (the
+    state machine over Autocorr's host arithmetic), slow and meant for checks."""
+    if kind not in ("cccf", "rrrf"):
+        raise ConfigError(f"unknown type combination {kind!r}")
+    x = _arr(x, KINDS[kind][0])
+    room = (x.size + AUTOCORR_TILE - 1) // AUTOCORR_TILE + BURSTDET_SEGMAX + 1
+    ev, pend = np.zeros(room, BURST_EVENT), np.zeros(1, BURST_EVENT)
+    count, over, has = C.c_size_t(), C.c_int(), C.c_int()
+    _check(getattr(lib, f"yagi_hip_burstdet_{kind}_detect_host")(
+        window_size, delay, threshold, energy_floor, min_length, _ptr(x), x.size, _ptr(ev), room, C.byref(count),
+        C.byref(over), C.byref(has), _ptr(pend)))
+    return ev[:min(count.value, room)].copy(), bool(over.value), (pend[0] if has.value else None)
 
 
 MSEQUENCE_TILE = 8192    # YAGI_MSEQUENCE_TILE: symbols per workgroup of the generator kernel

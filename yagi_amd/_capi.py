@@ -603,6 +603,26 @@ for _k, _T in (("cccf", cf32), ("rrrf", f32)):
     _sig(_p + "execute_block", vp, vp, sz, vp, vp)
     _sig(_p + "execute_block_dev", vp, vp, sz, vp, vp)
 
+# ---- BurstDetector -----------------------------------------------------------------------------
+for _k in ("cccf", "rrrf"):
+    _p = f"yagi_hip_burstdet_{_k}_"
+    _sig(_p + "create", sz, sz, f32, f32, u64, pvp)
+    _sig(_p + "destroy", vp)
+    _sig(_p + "clone", vp, pvp)
+    _sig(_p + "set_stream", vp, vp)
+    _sig(_p + "reset", vp)
+    _sig(_p + "get_window_size", vp, C.POINTER(sz))
+    _sig(_p + "get_delay", vp, C.POINTER(sz))
+    _sig(_p + "get_threshold", vp, C.POINTER(f32))
+    _sig(_p + "get_energy_floor", vp, C.POINTER(f32))
+    _sig(_p + "get_min_length", vp, C.POINTER(u64))
+    _sig(_p + "get_position", vp, C.POINTER(u64))
+    _sig(_p + "get_pending", vp, C.POINTER(ci), vp)
+    _sig(_p + "detect_block", vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(ci))
+    _sig(_p + "detect_block_dev", vp, vp, sz, vp, sz, vp)
+    _sig(_p + "flush", vp, vp, sz, C.POINTER(sz))
+    _sig(_p + "detect_host", sz, sz, f32, f32, u64, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(ci), C.POINTER(ci), vp)
+
 # ---- SymStream ---------------------------------------------------------------------------------
 _p = "yagi_hip_symstreamcf_"
 _sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)

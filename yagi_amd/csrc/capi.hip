@@ -6163,6 +6163,260 @@ YAGI_AUTOCORR_IMPL(cccf, cf32)
 YAGI_AUTOCORR_IMPL(rrrf, float)
 #undef YAGI_AUTOCORR_IMPL
 
+// ---- BurstDetector (yagi_hip.h; absent from the reference) ----------------------------------------------------------
+// The state is Autocorr's history (the last W + d samples) plus a BurstState: the sample counter and the pending run.
+// Block calls run burstdet_kernels.hip on the device copy: the tile kernel writes the history the call leaves into the
+// other of two buffers, the stitch kernel updates the BurstState in place.  Getters, flush and clone work on a host
+// mirror; the two copies are synchronised lazily (Mirror).
+namespace yagi {
+
+static int burstdet_check(float threshold, float energy_floor, uint64_t min_length) {
+    if (!std::isfinite(threshold) || !(threshold > 0.0f))
+        return fail(YAGI_ERR_CONFIG, "threshold must be finite and greater than zero");
+    if (!std::isfinite(energy_floor) || !(energy_floor >= 0.0f))
+        return fail(YAGI_ERR_CONFIG, "energy floor must be finite and not negative");
+    if (min_length < 1) return fail(YAGI_ERR_CONFIG, "minimum length must be at least one");
+    return YAGI_OK;
+}
+static int burstdet_check_window(size_t W, size_t d) {
+    if (W == 0) return fail(YAGI_ERR_CONFIG, "window size must be greater than zero");
+    if (W > (size_t)YAGI_AUTOCORR_WMAX)
+        return fail(YAGI_ERR_CONFIG, "window size %zu exceeds YAGI_AUTOCORR_WMAX = %d", W, YAGI_AUTOCORR_WMAX);
+    if (d > (size_t)YAGI_AUTOCORR_DMAX)
+        return fail(YAGI_ERR_CONFIG, "delay %zu exceeds YAGI_AUTOCORR_DMAX = %d", d, YAGI_AUTOCORR_DMAX);
+    return YAGI_OK;
+}
+
+template <class T>
+struct BurstDetObj {
+    hipStream_t st = nullptr;
+    int W = 0, d = 0;
+    float threshold = 0.0f, thr2 = 0.0f, floor_ = 0.0f;
+    uint64_t min_length = 1;
+    FdHist<T> win;                                        // host mirror: the history
+    BurstState hs{};                                      //              counter and pending run
+    PingPong<> hist;                                      // device copy, W + d samples
+    DevBuf state;                                         //              one BurstState
+    DevBuf scratch;                                       // tile table and segment pool, grown with the block length
+    Staging ws;                                           // host block form: x; y holds {status, events}
+    Mirror mirror;
+
+    size_t len() const { return (size_t)W + (size_t)d; }
+    size_t bytes() const { return len() * sizeof(T); }
+    int configure(size_t W_, size_t d_, float threshold_, float floor__, uint64_t min_length_) {
+        YG_TRY(burstdet_check_window(W_, d_));
+        YG_TRY(burstdet_check(threshold_, floor__, min_length_));
+        W = (int)W_;
+        d = (int)d_;
+        threshold = threshold_;
+        thr2 = threshold_ * threshold_;
+        floor_ = floor__;
+        min_length = min_length_;
+        return YAGI_OK;
+    }
+    int alloc() {
+        YG_TRY(require_device());
+        YG_TRY(hist.alloc(bytes()));
+        YG_TRY(state.alloc(sizeof(BurstState)));
+        win.init(len());
+        return YAGI_OK;
+    }
+    int reset() {
+        win.zero();
+        hs = BurstState{};
+        YG_HIP(hipMemsetAsync(hist.cur(), 0, bytes(), st));
+        YG_HIP(hipMemsetAsync(state.p, 0, sizeof(BurstState), st));
+        mirror.in_sync();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] {
+            std::vector<T> t(len());
+            YG_TRY(download(t.data(), hist.cur(), bytes(), st));
+            win.load(t.data());
+            return download(&hs, state.p, sizeof(BurstState), st);
+        });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] {
+            YG_TRY(upload(hist.cur(), win.data(), bytes(), st));
+            return upload(state.p, &hs, sizeof(BurstState), st);
+        });
+    }
+    // events a call of nb samples can report: a run per segment, and the pending run of the call before
+    static size_t most_events(size_t nb) {
+        return (nb + kAutocorrTile - 1) / kAutocorrTile + (size_t)kBurstSegmax + 1;
+    }
+    int block_dev(const T *x, size_t nb, yagi_burst_event *events, size_t cap, unsigned *status) {
+        YG_TRY(ensure_dev());
+        YG_TRY(scratch.ensure(burstdet_scratch_bytes(nb)));
+        YG_TRY(launch_burstdet<T>(W, d, thr2, floor_, min_length, hist.cur<T>(), hist.next<T>(), x, nb, scratch.p,
+                                  state.as<BurstState>(), events, cap, status, st));
+        if (nb != 0) hist.flip();
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+    int block(const T *x, size_t nb, yagi_burst_event *events, size_t cap, size_t *count, int *overflow) {
+        const size_t room = std::min(cap, most_events(nb));
+        YG_TRY(ws.put(st, x, nb));
+        YG_TRY(ws.y.ensure(16 + room * sizeof(yagi_burst_event)));
+        unsigned *sd = ws.y.as<unsigned>();
+        yagi_burst_event *ed = reinterpret_cast<yagi_burst_event *>(ws.y.as<char>() + 16);
+        YG_TRY(block_dev(ws.x.as<T>(), nb, ed, room, sd));
+        unsigned status[2];
+        YG_TRY(download(status, sd, sizeof status, st));
+        *count = status[0];
+        *overflow = (int)status[1];
+        return download(events, ed, std::min((size_t)status[0], room) * sizeof(yagi_burst_event), st);
+    }
+    int flush(yagi_burst_event *events, size_t cap, size_t *count) {
+        YG_TRY(ensure_host());
+        *count = 0;
+        if (!hs.has_pending) return YAGI_OK;
+        if (hs.pending.length >= min_length) {
+            if (cap > 0) events[0] = hs.pending;
+            *count = 1;
+        }
+        hs.has_pending = 0;
+        mirror.host_written();
+        return YAGI_OK;
+    }
+};
+
+}  // namespace yagi
+
+#define YAGI_BURSTDET_GET(K, name, type, expr)                                                      \
+    int yagi_hip_burstdet_##K##_get_##name(yagi_hip_burstdet_##K q, type *out) try {                \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = (expr);                                                                              \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }
+
+#define YAGI_BURSTDET_IMPL(K, T)                                                                    \
+    struct yagi_hip_burstdet_##K##_s : BurstDetObj<T> {};                                           \
+    extern "C" {                                                                                    \
+    int yagi_hip_burstdet_##K##_create(size_t window_size, size_t delay, float threshold, float energy_floor, \
+                                       uint64_t min_length, yagi_hip_burstdet_##K *q) try {         \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        auto o = std::make_unique<yagi_hip_burstdet_##K##_s>();                                     \
+        YG_TRY(o->configure(window_size, delay, threshold, energy_floor, min_length));              \
+        YG_TRY(o->alloc());                                                                         \
+        YG_TRY(o->reset());                                                                         \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_burstdet_##K##_destroy(yagi_hip_burstdet_##K q) try {                              \
+        if (q) (void)hipStreamSynchronize(q->st);                                                   \
+        delete q;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_burstdet_##K##_clone(yagi_hip_burstdet_##K q, yagi_hip_burstdet_##K *out) try {    \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = nullptr;                                                                             \
+        YG_TRY(q->ensure_host());                                                                   \
+        auto o = std::make_unique<yagi_hip_burstdet_##K##_s>();                                     \
+        o->st = q->st;                                                                              \
+        YG_TRY(o->configure((size_t)q->W, (size_t)q->d, q->threshold, q->floor_, q->min_length));   \
+        YG_TRY(o->alloc());                                                                         \
+        o->win.load(q->win.data());                                                                 \
+        o->hs = q->hs;                                                                              \
+        o->mirror.host_written();                                                                   \
+        *out = o.release();                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_burstdet_##K##_set_stream(yagi_hip_burstdet_##K q, yagi_stream_t s) try {          \
+        CHECK_Q(q);                                                                                 \
+        if (q->st == to_stream(s)) return YAGI_OK;                                                  \
+        YG_HIP(hipStreamSynchronize(q->st));                                                        \
+        q->st = to_stream(s);                                                                       \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_burstdet_##K##_reset(yagi_hip_burstdet_##K q) try {                                \
+        CHECK_Q(q);                                                                                 \
+        return q->reset();                                                                          \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    YAGI_BURSTDET_GET(K, window_size, size_t, (size_t)q->W)                                         \
+    YAGI_BURSTDET_GET(K, delay, size_t, (size_t)q->d)                                               \
+    YAGI_BURSTDET_GET(K, threshold, float, q->threshold)                                            \
+    YAGI_BURSTDET_GET(K, energy_floor, float, q->floor_)                                            \
+    YAGI_BURSTDET_GET(K, min_length, uint64_t, q->min_length)                                       \
+    int yagi_hip_burstdet_##K##_get_position(yagi_hip_burstdet_##K q, uint64_t *position) try {     \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(position);                                                                        \
+        YG_TRY(q->ensure_host());                                                                   \
+        *position = q->hs.position;                                                                 \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_burstdet_##K##_get_pending(yagi_hip_burstdet_##K q, int *has_pending, yagi_burst_event *ev) try { \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(has_pending);                                                                     \
+        CHECK_PTR(ev);                                                                              \
+        YG_TRY(q->ensure_host());                                                                   \
+        *has_pending = q->hs.has_pending != 0;                                                      \
+        *ev = *has_pending ? q->hs.pending : yagi_burst_event{};                                    \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_burstdet_##K##_detect_block(yagi_hip_burstdet_##K q, const T *x, size_t n, yagi_burst_event *events, \
+                                             size_t cap, size_t *count, int *overflow) try {        \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(count);                                                                           \
+        CHECK_PTR(overflow);                                                                        \
+        *count = 0;                                                                                 \
+        *overflow = 0;                                                                              \
+        if (n == 0) return YAGI_OK;                                                                 \
+        CHECK_PTR(x);                                                                               \
+        if (cap != 0) CHECK_PTR(events);                                                            \
+        return q->block(x, n, events, cap, count, overflow);                                        \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_burstdet_##K##_detect_block_dev(yagi_hip_burstdet_##K q, const T *x_dev, size_t n, \
+                                                 yagi_burst_event *events_dev, size_t cap, uint32_t *status_dev) try { \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(status_dev);                                                                      \
+        if (n != 0) CHECK_PTR(x_dev);                                                               \
+        if (cap != 0) CHECK_PTR(events_dev);                                                        \
+        if (n != 0) {                                                                               \
+            if (cap != 0) CHECK_NOALIAS(x_dev, n, events_dev, cap);                                 \
+            CHECK_NOALIAS(x_dev, n, status_dev, 2);                                                 \
+        }                                                                                           \
+        if (cap != 0) CHECK_NOALIAS(events_dev, cap, status_dev, 2);                                \
+        return q->block_dev(x_dev, n, events_dev, cap, status_dev);                                 \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_burstdet_##K##_flush(yagi_hip_burstdet_##K q, yagi_burst_event *events, size_t cap, size_t *count) try { \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(count);                                                                           \
+        if (cap != 0) CHECK_PTR(events);                                                            \
+        return q->flush(events, cap, count);                                                        \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_burstdet_##K##_detect_host(size_t window_size, size_t delay, float threshold, float energy_floor, \
+                                            uint64_t min_length, const T *x, size_t n, yagi_burst_event *events, \
+                                            size_t cap, size_t *count, int *overflow, int *has_pending, \
+                                            yagi_burst_event *pending) try {                        \
+        CHECK_PTR(count);                                                                           \
+        CHECK_PTR(overflow);                                                                        \
+        CHECK_PTR(has_pending);                                                                     \
+        CHECK_PTR(pending);                                                                         \
+        if (n != 0) CHECK_PTR(x);                                                                   \
+        if (cap != 0) CHECK_PTR(events);                                                            \
+        YG_TRY(burstdet_check_window(window_size, delay));                                          \
+        YG_TRY(burstdet_check(threshold, energy_floor, min_length));                                \
+        std::vector<T> win(window_size + delay, T{});                                               \
+        BurstState s{};                                                                             \
+        YG_TRY(burstdet_host<T>((int)window_size, (int)delay, threshold * threshold, energy_floor, min_length, \
+                                win.data(), &s, x, n, events, cap, count, overflow));               \
+        *has_pending = s.has_pending != 0;                                                          \
+        *pending = s.has_pending ? s.pending : yagi_burst_event{};                                  \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    }
+
+YAGI_BURSTDET_IMPL(cccf, cf32)
+YAGI_BURSTDET_IMPL(rrrf, float)
+#undef YAGI_BURSTDET_IMPL
+#undef YAGI_BURSTDET_GET
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

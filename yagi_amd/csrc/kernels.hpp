@@ -496,6 +496,35 @@ int launch_autocorr(int W, int d, const T *hist, T *hist_next, const T *x, size_
 template <class T>
 void autocorr_host(const T *h, int W, int d, T *rxx, float *energy);
 
+// ---- burstdet_kernels.hip ------------------------------------------------------------------
+// BurstDetector (yagi_hip.h) block calls on device buffers: nb samples in, the events they close out.  hist / hist_next
+// as for launch_autocorr.  scratch holds burstdet_scratch_bytes(nb): the tile table, then the segment pool.  state is the
+// object's device state; its pool_used is zero between calls.  events has room for cap; status receives {count, overflow}.
+constexpr int kBurstSegmax = YAGI_BURSTDET_SEGMAX;     // segments a call may hold beyond one per tile
+struct BurstSeg {                                      // a run of hits inside a tile; offsets from the tile's first sample
+    unsigned start, length, peak;
+    float ratio, energy, re, im;                       // r, energy and rxx at the peak
+    unsigned pad;
+};
+struct BurstState {
+    unsigned long long position, pool_used;            // samples since reset(); segments the running call has taken
+    unsigned has_pending, pad;
+    yagi_burst_event pending;                          // the run that ends on the last sample seen
+};
+static_assert(sizeof(BurstSeg) == 32 && sizeof(BurstState) == 64 && sizeof(yagi_burst_event) == 40, "device layouts");
+constexpr size_t burstdet_scratch_bytes(size_t nb) {
+    const size_t tiles = (nb + kAutocorrTile - 1) / kAutocorrTile;
+    return tiles * 16 + (tiles + (size_t)kBurstSegmax) * sizeof(BurstSeg);
+}
+template <class T>
+int launch_burstdet(int W, int d, float thr2, float floor_, unsigned long long min_length, const T *hist, T *hist_next,
+                    const T *x, size_t nb, void *scratch, BurstState *state, yagi_burst_event *events, size_t cap,
+                    unsigned *status, hipStream_t st);
+// the same call on the host, sample by sample over autocorr_host: win = the last W + d samples (updated), state as above
+template <class T>
+int burstdet_host(int W, int d, float thr2, float floor_, unsigned long long min_length, T *win, BurstState *state,
+                  const T *x, size_t n, yagi_burst_event *events, size_t cap, size_t *count, int *overflow);
+
 // ---- symstream_kernels.hip -----------------------------------------------------------------
 // SymStream (yagi_hip.h): samples [0, n) of a call that starts at buf_index p, from the carried window `win` (Ls values,
 // oldest first) and new symbols that come either from the caller's bytes (sym, flag = the result of
