@@ -1695,6 +1695,84 @@ int yagi_hip_symstreamcf_modulate_symbols(yagi_hip_symstreamcf q, const uint8_t 
 int yagi_hip_symstreamcf_modulate_symbols_dev(yagi_hip_symstreamcf q, const uint8_t *sym_dev, size_t nsym,
                                               yagi_cf32 *y_dev);
 
+/* ---- SymStreamR (symstreamrcf): src/framing/symstreamr.rs:9-129 (SymStream at any bandwidth) ---------------------------
+ * Definition: S = symstreamcf_create_linear(ftype, k = 2, m, beta, scheme, src) pushed one sample at a time through
+ * R = msresamp_crcf_create(rate = 0.5f / bw, as = 60): the arbitrary Resamp(rate_arb, 7, min(0.515 rate_arb, 0.49), 60,
+ * 256) first, then S half-band interpolator stages (0 .. 8; bw >= 0.25 has none, and the decimator chain never occurs).
+ * With s[] the samples of S since reset() and y[] the concatenation of what R.execute returns for them, write_samples(n)
+ * returns y[P .. P + n) and advances P.  A sample is pushed only when every output so far has been taken (fill_buffer
+ * :101-116), so after any call the number pushed is the smallest N with outputs(N) >= P; the outputs of the last pushed
+ * sample beyond P (at most 2 * 2^S) stay on the device and are served first by the next call.  The schedule is a closed
+ * form on the Resamp's integer phase p0: q = ceil(missing / 2^S) arbitrary-stage outputs need
+ * ((p0 + (q - 1) step) >> 24) + 1 samples (0 for q = 0), so no call reads anything back.  Consequences, bit for bit: the
+ * stream does not depend on how it is cut into calls; source_get_state stands where an MSequence stands after the bits
+ * of ceil(N / 2) symbols; set_gain / set_scheme reach only symbols drawn later.
+ *   create_linear(ftype, bw, m, beta, scheme, src)   :23-53 plus the source.  bw outside [0.001, 1] or not finite, a null
+ *                             source and whatever symstreamcf_create_linear refuses are YAGI_ERR_CONFIG.
+ *   destroy / clone / set_stream      clone copies everything, the outputs not yet taken included
+ *   reset()                   :55-60  S, R, P and the outputs not yet taken; the source stays where it stands
+ *   get_bw                    :66-68  1 / (rate k) in f32 -- not the argument echoed back
+ *   get_delay                 :94-99  (k m + R.get_delay()) rate in f32
+ *   get_ftype / get_m / get_beta / get_scheme / get_gain / set_scheme / set_gain      :62-92, S's
+ *   set_modem / source_set_state / source_get_state      extensions, as symstreamcf's
+ *   get_params(&interp, &stages, &rate_arbitrary)   R's; any pointer may be null
+ *   get_pending(&n)           outputs pushed and not yet taken
+ *   write_samples(y, n) / write_samples_dev(y_dev, n)    :118-128  any n.  The _dev form is asynchronous on the object's
+ *                             stream; a call the pending outputs cover launches no kernel.
+ *   is_fused(&fused)          1 where a call runs symstreamr_kernels.hip (S and the arbitrary Resamp in one launch that
+ *                             reads no sample, then R's half-band chain), 0 where it runs S.write_samples_dev into
+ *                             scratch and R's two parts (DPSK schemes, modems S does not run fused, shapes whose LDS
+ *                             does not fit).  The words are the same.
+ * Device pointers: y_dev 8-byte aligned.
+ * plan_symstreamr(bw, m, n, p0): what a call that misses n outputs with the Resamp at phase p0 does, without a device:
+ * the split of the rate, the Resamp's step, the fused kernel's tile (arbitrary-stage outputs per tile), the most tiles
+ * a workgroup stages and the tiles per workgroup of this call (0: the shape is not served fused for any constellation),
+ * its dynamic LDS with a 256-point constellation, q, need, the outputs of the arbitrary stage and of the chain, the
+ * leftover and the phase after the call. */
+typedef struct yagi_hip_symstreamrcf_s *yagi_hip_symstreamrcf;
+int yagi_hip_symstreamrcf_create_linear(int ftype, float bw, size_t m, float beta, int scheme, yagi_hip_msequence src,
+                                        yagi_hip_symstreamrcf *q);
+int yagi_hip_symstreamrcf_destroy(yagi_hip_symstreamrcf q);
+int yagi_hip_symstreamrcf_clone(yagi_hip_symstreamrcf q, yagi_hip_symstreamrcf *out);
+int yagi_hip_symstreamrcf_set_stream(yagi_hip_symstreamrcf q, yagi_stream_t s);
+int yagi_hip_symstreamrcf_reset(yagi_hip_symstreamrcf q);
+int yagi_hip_symstreamrcf_source_set_state(yagi_hip_symstreamrcf q, unsigned a);
+int yagi_hip_symstreamrcf_source_get_state(yagi_hip_symstreamrcf q, unsigned *a);
+int yagi_hip_symstreamrcf_get_ftype(yagi_hip_symstreamrcf q, int *ftype);
+int yagi_hip_symstreamrcf_get_bw(yagi_hip_symstreamrcf q, float *bw);
+int yagi_hip_symstreamrcf_get_m(yagi_hip_symstreamrcf q, size_t *m);
+int yagi_hip_symstreamrcf_get_beta(yagi_hip_symstreamrcf q, float *beta);
+int yagi_hip_symstreamrcf_get_scheme(yagi_hip_symstreamrcf q, int *scheme);
+int yagi_hip_symstreamrcf_get_gain(yagi_hip_symstreamrcf q, float *gain);
+int yagi_hip_symstreamrcf_get_delay(yagi_hip_symstreamrcf q, float *delay);
+int yagi_hip_symstreamrcf_get_pending(yagi_hip_symstreamrcf q, size_t *n);
+int yagi_hip_symstreamrcf_get_params(yagi_hip_symstreamrcf q, int *interp, size_t *num_halfband_stages,
+                                     float *rate_arbitrary);
+int yagi_hip_symstreamrcf_set_scheme(yagi_hip_symstreamrcf q, int scheme);
+int yagi_hip_symstreamrcf_set_modem(yagi_hip_symstreamrcf q, yagi_hip_modem mod);
+int yagi_hip_symstreamrcf_set_gain(yagi_hip_symstreamrcf q, float gain);
+int yagi_hip_symstreamrcf_is_fused(yagi_hip_symstreamrcf q, int *fused);
+int yagi_hip_symstreamrcf_write_samples(yagi_hip_symstreamrcf q, yagi_cf32 *y, size_t n);
+int yagi_hip_symstreamrcf_write_samples_dev(yagi_hip_symstreamrcf q, yagi_cf32 *y_dev, size_t n);
+
+typedef struct {
+    int interp;            /* R's type: 1 where rate > 1 */
+    int tile;              /* arbitrary-stage outputs per tile (plan_resamp's) */
+    int max_wg_tiles;      /* most tiles a workgroup stages; 0: not served fused */
+    int wg_tiles;          /* tiles per workgroup of this call */
+    uint32_t step;         /* round(2^24 / rate_arb) */
+    uint32_t phase_next;   /* the Resamp's phase after the call */
+    float rate, rate_arb;
+    size_t stages;         /* half-band interpolator stages S */
+    size_t lds;            /* dynamic LDS of the fused launch, M = 256 */
+    size_t q;              /* ceil(n / 2^S) */
+    size_t need;           /* samples of the SymStream the call pushes */
+    size_t outputs_arb;    /* outputs of the arbitrary stage for them */
+    size_t outputs;        /* outputs_arb * 2^S */
+    size_t leftover;       /* outputs - n */
+} yagi_hip_symstreamr_plan;
+int yagi_hip_plan_symstreamr(float bw, size_t m, size_t n, uint32_t p0, yagi_hip_symstreamr_plan *out);
+
 #ifdef __cplusplus
 }
 #endif

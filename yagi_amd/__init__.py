@@ -40,7 +40,7 @@ __all__ = [
     "Plan", "SpgramPlan", "plan_spgram", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
-    "estimate_req_filter_stopband_attenuation", "SymStream", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
+    "estimate_req_filter_stopband_attenuation", "SymStream", "SymStreamR", "SymStreamRPlan", "plan_symstreamr", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
 
@@ -2439,6 +2439,69 @@ class SymStream(_Handle):
     def modulate_symbols_devptr(self, sym_dev, nsym, y_dev):
         """sym_dev: nsym bytes, y_dev: nsym k samples on the device; they must not overlap (ConfigError)"""
         _check(self._fn("modulate_symbols_dev")(self._h, _devptr(sym_dev), nsym, _devptr(y_dev)))
+
+
+SymStreamRPlan = collections.namedtuple(
+    "SymStreamRPlan", "interp tile max_wg_tiles wg_tiles step phase_next rate rate_arb stages lds q need outputs_arb "
+                      "outputs leftover")
+
+
+def plan_symstreamr(bw, m, n, p0=0):
+    """yagi_hip_plan_symstreamr: what a SymStreamR(bw, m) call that misses n outputs does with its Resamp at phase p0
+    (no device needed): tile = arbitrary-stage outputs per tile of the fused kernel, wg_tiles of them per workgroup,
+    need = samples of the SymStream pushed, leftover = outputs the call leaves for the next one"""
+    p = _capi.symstreamr_plan()
+    _check(lib.yagi_hip_plan_symstreamr(bw, m, n, p0, C.byref(p)))
+    return SymStreamRPlan(p.interp, p.tile, p.max_wg_tiles, p.wg_tiles, p.step, p.phase_next, np.float32(p.rate),
+                          np.float32(p.rate_arb), p.stages, p.lds, p.q, p.need, p.outputs_arb, p.outputs, p.leftover)
+
+
+class SymStreamR(_Handle):
+    """framing::SymStreamR (src/framing/symstreamr.rs), symstreamrcf: a SymStream at two samples per symbol pushed one
+    sample at a time through MsResamp("crcf", 0.5 / bw, 60), written in any number of samples per call; bw in
+    [0.001, 1] is the occupied bandwidth.  Every output word equals SymStream.write_samples -> MsResamp.execute fed
+    exactly the samples the reference would have pushed, at any cut of the stream into calls.  A call is one launch of
+    symstreamr_kernels.hip (SymStream and the arbitrary Resamp, no sample read) plus the half-band chain's launch where
+    bw < 0.25 (is_fused); Dpsk* schemes and shapes the fused kernel does not serve run the two objects' device forms.
+    The words are the same (include/yagi_hip.h)."""
+    _prefix = "yagi_hip_symstreamrcf_"
+
+    def __init__(self, ftype, bw, m, beta, scheme, source):   # new_linear :23-53 plus the source
+        hd = C.c_void_p()
+        _check(self._fn("create_linear")(int(ftype), bw, m, beta, int(scheme), source._h, C.byref(hd)))
+        self._h = hd
+
+    clone = SymStream.clone
+    _get = SymStream._get
+    get_ftype = SymStream.get_ftype                           # :62-64
+    get_m = SymStream.get_m                                   # :70-72
+    get_beta = SymStream.get_beta                             # :74-76
+    set_scheme = SymStream.set_scheme                         # :78-80
+    set_modem = SymStream.set_modem
+    get_scheme = SymStream.get_scheme                         # :82-84
+    set_gain = SymStream.set_gain                             # :86-88
+    get_gain = SymStream.get_gain                             # :90-92
+    is_fused = SymStream.is_fused
+    source_set_state = SymStream.source_set_state
+    source_get_state = SymStream.source_get_state
+    write_samples = SymStream.write_samples                   # :118-128
+    write_samples_devptr = SymStream.write_samples_devptr
+
+    def get_bw(self):                                         # :66-68: 1 / (rate k), not the argument echoed back
+        return np.float32(self._get("get_bw", C.c_float))
+
+    def get_delay(self):                                      # :94-99
+        return np.float32(self._get("get_delay", C.c_float))
+
+    def get_pending(self):
+        """extension: outputs of the last pushed sample that no call has taken yet"""
+        return self._get("get_pending", C.c_size_t)
+
+    def get_params(self):
+        """(type, half-band stages, rate of the arbitrary resampler) of the MsResamp, as MsResamp.get_params"""
+        interp, ns, ra = C.c_int(), C.c_size_t(), C.c_float()
+        _check(self._fn("get_params")(self._h, C.byref(interp), C.byref(ns), C.byref(ra)))
+        return interp.value, ns.value, np.float32(ra.value)
 
 
 class MsResamp(_FirBase):

@@ -646,3 +646,35 @@ for _n in ("write_samples", "write_samples_dev"):
     _sig(_p + _n, vp, vp, sz)
 for _n in ("modulate_symbols", "modulate_symbols_dev"):
     _sig(_p + _n, vp, vp, sz, vp)
+
+# ---- SymStreamR --------------------------------------------------------------------------------
+_p = "yagi_hip_symstreamrcf_"
+_sig(_p + "create_linear", ci, f32, sz, f32, ci, vp, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "source_set_state", vp, cu)
+_sig(_p + "source_get_state", vp, pcu)
+for _n in ("get_ftype", "get_scheme", "is_fused"):
+    _sig(_p + _n, vp, C.POINTER(ci))
+for _n in ("get_m", "get_pending"):
+    _sig(_p + _n, vp, C.POINTER(sz))
+for _n in ("get_bw", "get_beta", "get_gain", "get_delay"):
+    _sig(_p + _n, vp, C.POINTER(f32))
+_sig(_p + "get_params", vp, C.POINTER(ci), C.POINTER(sz), C.POINTER(f32))
+_sig(_p + "set_scheme", vp, ci)
+_sig(_p + "set_modem", vp, vp)
+_sig(_p + "set_gain", vp, f32)
+for _n in ("write_samples", "write_samples_dev"):
+    _sig(_p + _n, vp, vp, sz)
+
+
+class symstreamr_plan(C.Structure):
+    """yagi_hip_symstreamr_plan"""
+    _fields_ = [("interp", ci), ("tile", ci), ("max_wg_tiles", ci), ("wg_tiles", ci), ("step", C.c_uint32),
+                ("phase_next", C.c_uint32), ("rate", f32), ("rate_arb", f32), ("stages", sz), ("lds", sz), ("q", sz),
+                ("need", sz), ("outputs_arb", sz), ("outputs", sz), ("leftover", sz)]
+
+
+_sig("yagi_hip_plan_symstreamr", f32, sz, sz, C.c_uint32, C.POINTER(symstreamr_plan))

@@ -7519,3 +7519,281 @@ int yagi_hip_symstreamcf_modulate_symbols_dev(yagi_hip_symstreamcf q, const uint
 } catch (...) { return ::yagi::api_exception(); }
 
 }  // extern "C"
+
+// ---- SymStreamR (src/framing/symstreamr.rs) ---------------------------------------------------------------------------
+// The reference's fields: a SymStream at k = 2, an MsResamp of rate 0.5 / bw and buf (the outputs of the last pushed
+// sample that no call has taken yet).  Both parts are the library's own objects, so the composition route is their
+// device forms one after the other; the fused route (symstreamr_kernels.hip) forms the SymStream's samples and the
+// MsResamp's arbitrary stage in one launch on the same state, and the MsResamp's half-band chain follows unchanged.
+// The schedule is host arithmetic on the Resamp's integer phase: no call reads anything back.
+namespace yagi {
+
+// MsResamp::new's split of the rate (msresamp.rs:33-51) and the Resamp's step for what remains
+static void symstreamr_split(float rate, int *interp, size_t *stages, float *rate_arb, uint32_t *step) {
+    *interp = rate > 1.0f ? 1 : 0;
+    *stages = 0;
+    float ra = rate;
+    if (*interp) {
+        while (ra > 2.0f) { ++*stages; ra *= 0.5f; }
+    } else {
+        while (ra < 0.5f) { ++*stages; ra *= 2.0f; }
+    }
+    *rate_arb = ra;
+    *step = (uint32_t)std::round(16777216.0f / ra);
+}
+
+// inputs the arbitrary stage needs from phase p0 for q outputs, and all the outputs they give
+static size_t symstreamr_need(uint32_t p0, uint32_t step, size_t q, size_t *outputs, uint32_t *next) {
+    if (q == 0) {
+        if (outputs) *outputs = 0;
+        if (next) *next = p0;
+        return 0;
+    }
+    const unsigned __int128 a = (unsigned __int128)p0 + (unsigned __int128)(q - 1) * step;
+    const size_t need = (size_t)(a >> 24) + 1;
+    const unsigned __int128 end = (unsigned __int128)need << 24;
+    const size_t n = (size_t)((end - p0 + step - 1) / step);
+    if (outputs) *outputs = n;
+    if (next) *next = (uint32_t)((unsigned __int128)p0 + (unsigned __int128)n * step - end);
+    return need;
+}
+
+static int symstreamr_check_bw(float bw) {
+    if (!std::isfinite(bw) || !(bw >= 0.001f && bw <= 1.0f))
+        return fail(YAGI_ERR_CONFIG, "symbol bandwidth (%g) must be in [0.001,1]", (double)bw);
+    return YAGI_OK;
+}
+
+}  // namespace yagi
+
+struct yagi_hip_symstreamrcf_s {
+    yagi_hip_symstreamcf S = nullptr;          // owned, k = 2
+    yagi_hip_msresamp_crcf R = nullptr;        // owned
+    DevBuf left;                               // 2 * 2^stages values: outputs pushed but not taken
+    size_t left_off = 0, left_len = 0;
+    DevBuf ds, dy;                             // composition route: the SymStream's samples, the MsResamp's outputs
+    Staging ws;
+
+    ~yagi_hip_symstreamrcf_s() {
+        if (S) (void)yagi_hip_symstreamcf_destroy(S);
+        if (R) (void)yagi_hip_msresamp_crcf_destroy(R);
+    }
+    hipStream_t stream() { return S->stream(); }
+    size_t left_cap() const { return (size_t)2 << R->num_stages; }
+    bool fused() const {
+        return S->fused() && symstreamr_fused_serves(R->arb->step, R->arb->bank.Ls, S->Ls(), S->modem->P.M, S->run);
+    }
+    int copy_dev(cf32 *dst, const cf32 *src, size_t n) {
+        if (n) YG_HIP(hipMemcpyAsync(dst, src, n * sizeof(cf32), hipMemcpyDeviceToDevice, stream()));
+        return YAGI_OK;
+    }
+    int reset() {
+        YG_TRY(yagi_hip_symstreamcf_reset(S));
+        YG_TRY(yagi_hip_msresamp_crcf_reset(R));
+        left_off = left_len = 0;
+        return YAGI_OK;
+    }
+    // the next n samples of the stream to y (device)
+    int write_dev(cf32 *y, size_t n) {
+        cf32 *lb = left.as<cf32>();
+        const size_t c = std::min(n, left_len);
+        YG_TRY(copy_dev(y, lb + left_off, c));
+        left_off += c;
+        left_len -= c;
+        const size_t miss = n - c;
+        if (miss == 0) return YAGI_OK;
+        y += c;
+        auto &A = *R->arb;
+        const size_t ns = R->num_stages;
+        const size_t q = (miss + R->group() - 1) >> ns;
+        size_t n1 = 0;
+        uint32_t next = 0;
+        const size_t need = symstreamr_need(A.phase, A.step, q, &n1, &next);
+        if (ns) YG_TRY(R->mid.ensure(n1 * sizeof(cf32)));
+        if (!fused()) {
+            // the composition: S's samples into scratch, then R's arbitrary stage -- into the stream between R's two parts
+            // where half-band stages follow, else into scratch from where the two parts of the call are copied out
+            YG_TRY(ds.ensure(need * sizeof(cf32)));
+            YG_TRY(S->block_dev(nullptr, need, ds.as<cf32>()));
+            if (ns == 0) {
+                YG_TRY(dy.ensure(n1 * sizeof(cf32)));
+                YG_TRY(A.block_dev(ds.as<cf32>(), need, dy.as<cf32>(), n1));
+                YG_TRY(copy_dev(y, dy.as<cf32>(), miss));
+                YG_TRY(copy_dev(lb, dy.as<cf32>() + miss, n1 - miss));
+            } else {
+                YG_TRY(A.block_dev(ds.as<cf32>(), need, R->mid.as<cf32>(), n1));
+            }
+        } else {
+            FirPfb<CRCF> &sb = S->fir.bank, &rb = A.bank;
+            YG_TRY(sb.w.ensure_dev(sb.st));
+            YG_TRY(rb.w.ensure_dev(rb.st));
+            const int bps = S->modem->P.bps, M = S->modem->P.M, p = S->p;
+            const SymSource src{S->dpow.as<unsigned>(), S->dstride.as<unsigned>(), S->sstate, S->sg, S->smask, (int)S->sm, bps,
+                                S->run};
+            cf32 *ya = ns ? R->mid.as<cf32>() : y, *yb = ns ? ya : lb;
+            YG_TRY(launch_symstreamr(sb.w.dev(), sb.taps.as<float>(), sb.Ls, sb.scale, S->modem->dmap.as<cf32>(), M, S->gain,
+                                     src, p, rb.w.dev(), rb.taps.as<float>(), rb.Ls, A.bits, A.step, A.phase, need, n1, ya,
+                                     ns ? n1 : miss, yb, sb.w.next(), rb.w.next(), S->dbuf.as<cf32>(), sb.st));
+            const size_t nnew = ((size_t)p + need + 1) / 2 - (p > 0 ? 1 : 0);
+            if (nnew) {
+                sb.w.flip();
+                S->sstate = msequence_skip(S->pow.data(), S->sstate, (uint64_t)nnew * (uint64_t)bps);
+            }
+            S->p = (int)(((size_t)p + need) % 2);
+            rb.w.flip();
+            A.phase = next;
+        }
+        if (ns == 0) {
+            left_off = 0;
+            left_len = n1 - miss;
+            return YAGI_OK;
+        }
+        // the half-band chain: whole groups straight to y, the last ones to the leftover and their requested part copied out
+        const cf32 *mid = R->mid.as<cf32>();
+        const size_t gfull = miss >> ns, rem = n1 - gfull, tail = miss - (gfull << ns);
+        YG_TRY(R->half->block_dev(mid, gfull, y));
+        YG_TRY(R->half->block_dev(mid + gfull, rem, lb));
+        YG_TRY(copy_dev(y + (gfull << ns), lb, tail));
+        left_off = tail;
+        left_len = (rem << ns) - tail;
+        return YAGI_OK;
+    }
+    int write_host(cf32 *y, size_t n) {
+        YG_TRY(ws.y.ensure(n * sizeof(cf32)));
+        YG_TRY(write_dev(ws.y.as<cf32>(), n));
+        return download(y, ws.y.p, n * sizeof(cf32), stream());
+    }
+};
+
+#define SYMSTREAMR_GET(name, type, expr)                                                            \
+    int yagi_hip_symstreamrcf_##name(yagi_hip_symstreamrcf q, type *v) try {                        \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(v);                                                                               \
+        *v = (expr);                                                                                \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }
+
+extern "C" {
+
+int yagi_hip_symstreamrcf_create_linear(int ftype, float bw, size_t m, float beta, int scheme, yagi_hip_msequence src,
+                                        yagi_hip_symstreamrcf *q) try {              // new_linear :23-53
+    CHECK_PTR(q);
+    *q = nullptr;
+    YG_TRY(symstreamr_check_bw(bw));
+    auto o = std::make_unique<yagi_hip_symstreamrcf_s>();
+    YG_TRY(yagi_hip_symstreamcf_create_linear(ftype, 2, m, beta, scheme, src, &o->S));
+    YG_TRY(yagi_hip_msresamp_crcf_create(0.5f / bw, 60.0f, &o->R));
+    YG_TRY(yagi_hip_msresamp_crcf_set_stream(o->R, (yagi_stream_t)o->S->stream()));
+    YG_TRY(o->left.alloc(o->left_cap() * sizeof(cf32)));
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_destroy(yagi_hip_symstreamrcf q) try {
+    if (q && q->S) (void)hipStreamSynchronize(q->stream());
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_clone(yagi_hip_symstreamrcf q, yagi_hip_symstreamrcf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    auto o = std::make_unique<yagi_hip_symstreamrcf_s>();
+    YG_TRY(yagi_hip_symstreamcf_clone(q->S, &o->S));
+    YG_TRY(yagi_hip_msresamp_crcf_clone(q->R, &o->R));
+    YG_TRY(o->left.alloc(o->left_cap() * sizeof(cf32)));
+    o->left_off = q->left_off;
+    o->left_len = q->left_len;
+    YG_TRY(o->copy_dev(o->left.as<cf32>(), q->left.as<cf32>(), q->left_cap()));
+    YG_HIP(hipStreamSynchronize(o->stream()));
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_set_stream(yagi_hip_symstreamrcf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    YG_TRY(yagi_hip_symstreamcf_set_stream(q->S, s));
+    return yagi_hip_msresamp_crcf_set_stream(q->R, s);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_reset(yagi_hip_symstreamrcf q) try {                        // :55-60
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_source_set_state(yagi_hip_symstreamrcf q, unsigned a) try {
+    CHECK_Q(q);
+    return yagi_hip_symstreamcf_source_set_state(q->S, a);
+} catch (...) { return ::yagi::api_exception(); }
+
+SYMSTREAMR_GET(source_get_state, unsigned, q->S->sstate)
+SYMSTREAMR_GET(get_ftype, int, q->S->ftype)                                           // :62-64
+SYMSTREAMR_GET(get_bw, float, 1.0f / (q->R->rate * (float)q->S->k))                   // :66-68
+SYMSTREAMR_GET(get_m, size_t, q->S->m)                                                // :70-72
+SYMSTREAMR_GET(get_beta, float, q->S->beta)                                           // :74-76
+SYMSTREAMR_GET(get_scheme, int, q->S->modem->scheme)                                  // :82-84
+SYMSTREAMR_GET(get_gain, float, q->S->gain)                                           // :90-92
+SYMSTREAMR_GET(get_delay, float, ((float)(q->S->k * q->S->m) + q->R->delay()) * q->R->rate)   // :94-99
+SYMSTREAMR_GET(get_pending, size_t, q->left_len)
+SYMSTREAMR_GET(is_fused, int, q->fused() ? 1 : 0)
+
+int yagi_hip_symstreamrcf_get_params(yagi_hip_symstreamrcf q, int *interp, size_t *num_halfband_stages,
+                                     float *rate_arbitrary) try {
+    CHECK_Q(q);
+    return yagi_hip_msresamp_crcf_get_params(q->R, interp, num_halfband_stages, rate_arbitrary);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_set_scheme(yagi_hip_symstreamrcf q, int scheme) try {       // :78-80
+    CHECK_Q(q);
+    return yagi_hip_symstreamcf_set_scheme(q->S, scheme);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_set_modem(yagi_hip_symstreamrcf q, yagi_hip_modem mod) try {
+    CHECK_Q(q);
+    return yagi_hip_symstreamcf_set_modem(q->S, mod);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_set_gain(yagi_hip_symstreamrcf q, float gain) try {         // :86-88
+    CHECK_Q(q);
+    return yagi_hip_symstreamcf_set_gain(q->S, gain);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_write_samples(yagi_hip_symstreamrcf q, yagi_cf32 *y, size_t n) try {    // :118-128
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(y);
+    return q->write_host(y, n);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symstreamrcf_write_samples_dev(yagi_hip_symstreamrcf q, yagi_cf32 *y_dev, size_t n) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(y_dev);
+    if ((uintptr_t)y_dev & 7) return fail(YAGI_ERR_CONFIG, "symstreamr: sample buffers must be 8-byte aligned");
+    return q->write_dev(y_dev, n);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_plan_symstreamr(float bw, size_t m, size_t n, uint32_t p0, yagi_hip_symstreamr_plan *out) try {
+    CHECK_PTR(out);
+    *out = yagi_hip_symstreamr_plan{};
+    YG_TRY(symstreamr_check_bw(bw));
+    if (m == 0 || m > ((size_t)1 << 20)) return fail(YAGI_ERR_CONFIG, "filter delay must be in [1, 2^20]");
+    const float rate = 0.5f / bw;
+    symstreamr_split(rate, &out->interp, &out->stages, &out->rate_arb, &out->step);
+    out->rate = rate;
+    const int Lr = 14, Ls = (int)(2 * m + 1), run = symstream_run(2, Ls);     // MsResamp's Resamp has m = 7
+    out->tile = symstreamr_tile(out->step, Lr);
+    out->max_wg_tiles = symstreamr_fused_serves(out->step, Lr, Ls, 256, run) ? symstreamr_max_tiles(out->step, Lr, Ls, run) : 0;
+    out->q = (n + ((size_t)1 << out->stages) - 1) >> out->stages;
+    out->need = symstreamr_need(p0, out->step, out->q, &out->outputs_arb, &out->phase_next);
+    out->outputs = out->outputs_arb << out->stages;
+    out->leftover = out->outputs - n;
+    if (out->max_wg_tiles && out->outputs_arb) {
+        out->wg_tiles = symstreamr_wg_tiles(out->step, Lr, Ls, run, out->outputs_arb);
+        out->lds = symstreamr_lds_bytes(out->step, Lr, Ls, 256, out->wg_tiles);
+    }
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"

@@ -5,6 +5,8 @@
 //                are), also applied to the tail of x that write_next_window leaves as the next window
 //   bank kernels mix(v, idx): the value stored to y[idx]
 // FirNoMix returns v, and the plain kernels compile to what they were before the bodies moved here.
+// At the end: the per-output sums of resamp_kernel and of the bank kernels' single-branch loop, and the LFSR symbol
+// source of symstream_kernel, each shared with symstreamr_kernels.hip (SymStreamR), which runs them back to back.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
@@ -533,6 +535,94 @@ inline ResampPlan resamp_plan(size_t elem, int Ls, uint32_t step) {
     p.tile = (int)tile;
     p.lds = (size_t)resamp_span(tile, step, Ls) * elem;
     return p;
+}
+
+// One output of resamp_kernel: the branch's FMA chain in tap order (bit-identical to the per-sample loop on exact data),
+// four taps' reads together.  xp = the newest sample of the output's window (tap k reads xp[-k]), hrow = the branch's Ls
+// taps.  Shared with symstreamr_kernel, which runs it from samples it has just formed in LDS.
+template <class T, class C>
+__device__ __forceinline__ T resamp_branch_dot(const T *xp, const C *__restrict__ hrow, int Ls) {
+    T acc = zero_of<T>();
+    int k = 0;
+    if constexpr (std::is_same<C, float>::value) {
+        if ((Ls & 1) == 0) {                    // even rows (Ls = 2m) start 8-byte aligned: the taps in pairs
+            const float2 *h2 = reinterpret_cast<const float2 *>(hrow);
+            for (; k + 4 <= Ls; k += 4) {
+                const T x0 = xp[-k], x1 = xp[-k - 1], x2 = xp[-k - 2], x3 = xp[-k - 3];
+                const float2 ha = h2[k >> 1], hc = h2[(k >> 1) + 1];
+                acc = mac(acc, x0, ha.x);
+                acc = mac(acc, x1, ha.y);
+                acc = mac(acc, x2, hc.x);
+                acc = mac(acc, x3, hc.y);
+            }
+            if (k < Ls) {
+                const float2 ha = h2[k >> 1];
+                acc = mac(acc, xp[-k], ha.x);
+                acc = mac(acc, xp[-k - 1], ha.y);
+                k += 2;
+            }
+        }
+    }
+    for (; k + 4 <= Ls; k += 4) {
+        const T x0 = xp[-k], x1 = xp[-k - 1], x2 = xp[-k - 2], x3 = xp[-k - 3];
+        const C h0 = hrow[k], h1 = hrow[k + 1], h2 = hrow[k + 2], h3 = hrow[k + 3];
+        acc = mac(acc, x0, h0);
+        acc = mac(acc, x1, h1);
+        acc = mac(acc, x2, h2);
+        acc = mac(acc, x3, h3);
+    }
+    for (; k < Ls; ++k) acc = mac(acc, xp[-k], hrow[k]);
+    return acc;
+}
+
+// One branch of a polyphase bank at one input sample, as the last nf % 4 branches of firpfb_fewbranch_body form it: the
+// chain over the taps in order, then the scale.  xr = the newest sample (tap k reads xr[-k]), h0 = the branch's Ls taps.
+template <class T, class C>
+__device__ __forceinline__ T pfb_branch_dot(const T *xr, const C *__restrict__ h0, int Ls, C scale) {
+    T acc = zero_of<T>();
+    for (int k = 0; k < Ls; ++k) acc = mac(acc, xr[-k], h0[k]);
+    return mul(acc, scale);
+}
+
+// ---- the LFSR symbol source of symstream_kernel and symstreamr_kernel ------------------------------------------------
+// the matrix (32 column words) applied to s.  All 32 columns, unrolled: the matrix then comes in two wide scalar loads
+// and one wait; a loop over the m columns a state can have set waits for a scalar load per column, and that latency
+// (a few hundred cycles, 20 matrices deep) was most of a workgroup's time.
+__device__ __forceinline__ unsigned sym_apply(const unsigned *__restrict__ M, unsigned s) {
+    unsigned acc = 0u;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) acc ^= (0u - ((s >> j) & 1u)) & M[j];
+    return acc;
+}
+
+// s0 advanced by `off` bits with the T^(2^b) matrices; wave-uniform where the arguments are
+__device__ __forceinline__ unsigned sym_jump(const unsigned *__restrict__ pow, unsigned s0, unsigned long long off) {
+    unsigned s = s0;
+    for (int b = 0; off != 0; ++b, off >>= 1)
+        if (off & 1u) s = sym_apply(pow + 32 * b, s);
+    return s;
+}
+
+// Lane `tid` of a workgroup: from the state `s` at the first of `ngen` consecutive symbols, add tid * run symbols with
+// the eight lane-stride matrices T^(run * bps * 2^b), step its `run` symbols and leave tab[symbol] in dst[tid * run ..].
+template <class T>
+__device__ __forceinline__ void sym_lane_fill(const unsigned *__restrict__ stride, unsigned s, int tid, int run, int bps,
+                                              unsigned g, unsigned nmask, const T *tab, T *dst, int ngen) {
+#pragma unroll
+    for (int b = 0; b < kSymStrides; ++b) {
+        const unsigned t = sym_apply(stride + 32 * b, s);
+        s = ((tid >> b) & 1) ? t : s;
+    }
+    int e = tid * run;
+    for (int r = 0; r < run; ++r, ++e) {
+        unsigned v = 0u;
+        for (int c = 0; c < bps; ++c) {
+            const unsigned bit = (unsigned)__popc(s & g) & 1u;
+            s = ((s << 1) | bit) & nmask;
+            v = (v << 1) | bit;
+        }
+        if (e < ngen) dst[e] = tab[v];
+    }
 }
 
 }  // namespace yagi

@@ -483,38 +483,7 @@ resamp_kernel(const typename K::T *__restrict__ win, const typename K::T *__rest
         const uint32_t br = ((uint32_t)a & 0xFFFFFFu) >> shift;
         const C *hrow = hb + (size_t)br * Ls;
         const T *xp = xs + (Ls - 1) + li;
-        // one FMA chain in tap order (bit-identical to the per-sample loop on exact data), four taps' reads together
-        T acc = zero_of<T>();
-        int k = 0;
-        if constexpr (std::is_same<C, float>::value) {
-            if ((Ls & 1) == 0) {                    // even rows (Ls = 2m) start 8-byte aligned: the taps in pairs
-                const float2 *h2 = reinterpret_cast<const float2 *>(hrow);
-                for (; k + 4 <= Ls; k += 4) {
-                    const T x0 = xp[-k], x1 = xp[-k - 1], x2 = xp[-k - 2], x3 = xp[-k - 3];
-                    const float2 ha = h2[k >> 1], hc = h2[(k >> 1) + 1];
-                    acc = mac(acc, x0, ha.x);
-                    acc = mac(acc, x1, ha.y);
-                    acc = mac(acc, x2, hc.x);
-                    acc = mac(acc, x3, hc.y);
-                }
-                if (k < Ls) {
-                    const float2 ha = h2[k >> 1];
-                    acc = mac(acc, xp[-k], ha.x);
-                    acc = mac(acc, xp[-k - 1], ha.y);
-                    k += 2;
-                }
-            }
-        }
-        for (; k + 4 <= Ls; k += 4) {
-            const T x0 = xp[-k], x1 = xp[-k - 1], x2 = xp[-k - 2], x3 = xp[-k - 3];
-            const C h0 = hrow[k], h1 = hrow[k + 1], h2 = hrow[k + 2], h3 = hrow[k + 3];
-            acc = mac(acc, x0, h0);
-            acc = mac(acc, x1, h1);
-            acc = mac(acc, x2, h2);
-            acc = mac(acc, x3, h3);
-        }
-        for (; k < Ls; ++k) acc = mac(acc, xp[-k], hrow[k]);
-        y[j0 + o] = acc;
+        y[j0 + o] = resamp_branch_dot<T, C>(xp, hrow, Ls);     // fir_bodies.hpp
     }
 }
 

@@ -551,4 +551,21 @@ int launch_symstream(const cf32 *win, const float *hb, int k, int Ls, float scal
 int launch_symstream_check(int M, const uint8_t *sym, size_t n, int *flag, hipStream_t st);   // zeroes flag first
 int launch_symstream_gain(cf32 *v, size_t n, float gain, hipStream_t st);                    // v[i] = (re gain, im gain)
 
+// ---- symstreamr_kernels.hip ----------------------------------------------------------------
+// SymStreamR (yagi_hip.h): `need` samples of a k = 2 SymStream (symbol window swin, branch taps shb [2][Ls], buf_index p,
+// LFSR source src with the strides of symstream_run(2, Ls)) pushed through a Resamp (window rwin of Lr samples, bank
+// rhb [2^bits][Lr], phase p0) in one launch: all ny = num_output(need) outputs, output j to ya[j] for j < split and to
+// yb[j - split] behind it.  swin_next (where the call pushes a symbol: ceil((p + need) / 2) - p > 0), rwin_next and
+// buf[1] (where p + need is odd) receive what the call leaves; the caller flips and advances as after the two
+// launchers.  Served shapes: symstreamr_fused_serves.
+int symstreamr_tile(uint32_t step, int Lr);                                    // resamp_plan's tile: outputs per tile
+int symstreamr_max_tiles(uint32_t step, int Lr, int Ls, int run);              // most tiles a workgroup stages
+int symstreamr_wg_tiles(uint32_t step, int Lr, int Ls, int run, size_t ny);    // tiles per workgroup of a call of ny outputs
+size_t symstreamr_lds_bytes(uint32_t step, int Lr, int Ls, int M, int wg_tiles);
+bool symstreamr_fused_serves(uint32_t step, int Lr, int Ls, int M, int run);
+int launch_symstreamr(const cf32 *swin, const float *shb, int Ls, float scale, const cf32 *map, int M, float gain,
+                      const SymSource &src, int p, const cf32 *rwin, const float *rhb, int Lr, int bits, uint32_t step,
+                      uint32_t p0, size_t need, size_t ny, cf32 *ya, size_t split, cf32 *yb, cf32 *swin_next,
+                      cf32 *rwin_next, cf32 *buf, hipStream_t st);
+
 }  // namespace yagi

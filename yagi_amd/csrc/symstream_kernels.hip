@@ -48,16 +48,6 @@ namespace {
 constexpr size_t kSymLdsLimit = 64 * 1024;
 inline size_t round16(size_t b) { return (b + 15) / 16 * 16; }
 
-// the matrix (32 column words) applied to s.  All 32 columns, unrolled: the matrix then comes in two wide scalar loads
-// and one wait; a loop over the m columns a state can have set waits for a scalar load per column, and that latency
-// (a few hundred cycles, 20 matrices deep) was most of a workgroup's time.
-__device__ __forceinline__ unsigned sym_apply(const unsigned *__restrict__ M, unsigned s) {
-    unsigned acc = 0u;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) acc ^= (0u - ((s >> j) & 1u)) & M[j];
-    return acc;
-}
-
 struct SymArgs {
     const cf32 *win;            // Ls entries, oldest first
     const float *hb;            // [k][Ls]
@@ -93,10 +83,8 @@ __global__ void __launch_bounds__(256) symstream_kernel(const SymArgs a) {
     const int span = nt + Ls - 1;
     const int nwin = base < 0 ? (int)std::min((long long)span, -base) : 0;
     if (LFSR && tid < 64) {                                               // the state at symbol max(base, 0): wave-uniform
-        unsigned long long off = (base < 0 ? 0ull : (unsigned long long)base) * (unsigned)a.bps;
-        unsigned s = a.s0;
-        for (int b = 0; off != 0; ++b, off >>= 1)
-            if (off & 1u) s = sym_apply(a.pow + 32 * b, s);
+        const unsigned long long off = (base < 0 ? 0ull : (unsigned long long)base) * (unsigned)a.bps;
+        const unsigned s = sym_jump(a.pow, a.s0, off);                    // fir_bodies.hpp
         if (tid == 0) *jumped = s;
     }
     for (int i = tid; i < a.M; i += 256) tab[i] = mul(a.map[i], a.gain);
@@ -111,24 +99,8 @@ __global__ void __launch_bounds__(256) symstream_kernel(const SymArgs a) {
     if (LFSR) {
         const int ngen = span - nwin;                                     // symbols max(base, 0) .. + ngen - 1
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        if (wave * 64 * a.run < ngen) {                                   // wave-uniform
-            unsigned s = *jumped;
-#pragma unroll
-            for (int b = 0; b < kSymStrides; ++b) {                       // + tid * run symbols
-                const unsigned t = sym_apply(a.stride + 32 * b, s);
-                s = ((tid >> b) & 1) ? t : s;
-            }
-            int e = nwin + tid * a.run;
-            for (int r = 0; r < a.run; ++r, ++e) {
-                unsigned v = 0u;
-                for (int c = 0; c < a.bps; ++c) {
-                    const unsigned bit = (unsigned)__popc(s & a.g) & 1u;
-                    s = ((s << 1) | bit) & a.nmask;
-                    v = (v << 1) | bit;
-                }
-                if (e < span) xs[e] = tab[v];
-            }
-        }
+        if (wave * 64 * a.run < ngen)                                     // wave-uniform
+            sym_lane_fill(a.stride, *jumped, tid, a.run, a.bps, a.g, a.nmask, tab, xs + nwin, ngen);
     } else {
         for (int i = nwin + tid; i < span; i += 256) xs[i] = tab[a.sym[base + i]];
     }
@@ -172,10 +144,9 @@ __global__ void __launch_bounds__(256) symstream_kernel(const SymArgs a) {
             }
             for (; g0 < k; ++g0) {                                        // the last k % 4 branches
                 const float *h0 = a.hb + (size_t)g0 * Ls;
-                cf32 acc = zero_of<cf32>();
-                for (int t = 0; t < Ls; ++t) acc = mac(acc, xr[-t], h0[t]);
-                if (whole) yo[g0] = mul(acc, a.scale);
-                else store(ob + g0, g0, last_slot, mul(acc, a.scale));
+                const cf32 v = pfb_branch_dot(xr, h0, Ls, a.scale);       // fir_bodies.hpp
+                if (whole) yo[g0] = v;
+                else store(ob + g0, g0, last_slot, v);
             }
         }
     } else {
