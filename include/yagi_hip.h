@@ -616,6 +616,49 @@ typedef struct {
 } yagi_hip_spgram_plan;
 int yagi_hip_plan_spgram(size_t nfft, size_t nframes, yagi_hip_spgram_plan *out);
 
+/* What a block call of the half-band family would launch, answered by the very planners the launches call
+ * (resamp2_kernels.hip).  Read-only host arithmetic: no device is needed or initialised.  elem = bytes per sample, 4
+ * (rrrf) or 8 (crcf, cccf); a bad argument is YAGI_ERR_CONFIG.  These describe the present kernels and may change with
+ * them.
+ *
+ *   plan_msresamp2(elem, interp, ns, m, n)   MsResamp2 execute_block of n execute() calls (decimator: n outputs,
+ *       interpolator: n inputs).  m[0 .. ns) in the OBJECT's stage order, as get_stage_lengths returns it: the
+ *       interpolator runs stage 0 first, the decimator runs stage ns - 1 first, so stage g of the object is processing
+ *       stage ns - 1 - g of the decimator kernels; n[], walk[] and walk_q[] below are in processing order (0 = the
+ *       stage at the full rate).
+ *       fused = 1: the chain in one launch (at most four stages whose streams fit lds <= 64 KiB); fused = 0: one
+ *       Resamp2 block call per stage (plan_resamp2 answers for each), every other field but lds is 0, and lds too
+ *       beyond four stages.
+ *       Interpolator: tiles workgroups of 256 inputs, tpw = 1.
+ *       Decimator: the general kernel runs `tiles` tiles of 256 outputs, tpw consecutive ones per workgroup, over the
+ *       outputs [0, 256 head_tiles) and [tail_first, n); with fast_tiles > 0 the fast kernel runs fast_tiles tiles of F
+ *       outputs from 256 head_tiles on, fast_tpw per workgroup, with fast_lds bytes.  F, n[k] (outputs of stage k per
+ *       fast tile), cnt0 (input pairs per tile) and U (a tile's first input pair = 2^(ns-1) first output - U) describe
+ *       the geometry whenever one with F >= 64 exists (ns <= 3), else F = 0.  walk[k] = YAGI_PLAN_WALK_*: how the
+ *       fast kernel walks stage k's taps -- R outputs per lane with 2 m_k = R Q + RHO -- and walk_q[k] = Q (Q = 1:
+ *       the walk has no full group).  long_halo = 1: a general tile's full-rate streams, 256 * 2^(ns-1) pairs and a
+ *       halo, outgrow the 256 (2^(ns-1) + 1) entries a workgroup loads through registers (a halo of more than 256
+ *       pairs), and the kernel instance that stages the rest from memory runs.
+ *   plan_resamp2(elem, mode, m, nx)          Resamp2 execute_block of nx samples in form `mode` (0 filter .. 4 interp).
+ *       chain = 0: resamp2_kernel, tiles workgroups of 1024 units with lds bytes; chain = 1: a long decimator block
+ *       as the one-stage case of the chain kernels, what plan_msresamp2(elem, 0, 1, &m, nx / 2) describes (tiles and
+ *       lds are its general kernel's). */
+#define YAGI_PLAN_WALK_GENERAL 0  /* general kernel only: one tap chain per output */
+#define YAGI_PLAN_WALK_R1 1       /* fast kernel, one output per lane */
+#define YAGI_PLAN_WALK_R2 2       /* two outputs per lane, RHO = 0 */
+#define YAGI_PLAN_WALK_R4_RHO0 3  /* four outputs per lane, m even */
+#define YAGI_PLAN_WALK_R4_RHO2 4  /* four outputs per lane, m odd */
+typedef struct {
+    int fused, tpw, fast_tpw, F, n[3], cnt0, U, walk[4], walk_q[4], long_halo;
+    size_t lds, fast_lds, head_tiles, fast_tiles, tail_first, tiles;
+} yagi_hip_msresamp2_plan;
+typedef struct {
+    int chain;
+    size_t tiles, lds;
+} yagi_hip_resamp2_plan;
+int yagi_hip_plan_msresamp2(size_t elem, int interp, size_t ns, const size_t *m, size_t n, yagi_hip_msresamp2_plan *out);
+int yagi_hip_plan_resamp2(size_t elem, int mode, size_t m, size_t nx, yagi_hip_resamp2_plan *out);
+
 /* ---- Fft<f32>: src/fft/mod.rs:33-69 (arithmetic = rustfft 6.2 in the reference) ------------
  *   create       Fft::new(n, direction)        :39-43   any n >= 1 the engine supports
  *   run          run(input, output)            :45-48   out of place, unnormalised,

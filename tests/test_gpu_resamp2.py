@@ -208,7 +208,9 @@ def test_msresamp2_fused_decimator_equals_the_chain_on_a_large_block(ya, oracle,
     """the decimator chain in one launch (<= 4 stages, LDS-resident intermediates, several tiles per workgroup from
     8192 tiles on; up to three stages: the middle of the block through msresamp2_decim_fast_kernel, its two ends through
     the general kernel) against the same stages run one after the other as Resamp2 objects: identical bits, over two
-    calls (the windows of every stage written by the fused kernel's last workgroup carry into the second call)"""
+    calls (the windows of every stage written by the fused kernel's last workgroup carry into the second call).  Both
+    sides are GPU kernels that share the tap walk; the comparison against an independent reference -- the oracle's
+    sequential stages, bit for bit on integer data at every launch plan -- lives in tests/test_gpu_halfband_plans.py"""
     ns = len(ms)
     rate = 1 << ns
     hfs = [oracle.halfband_kaiser(m, 60.0) for m in ms]

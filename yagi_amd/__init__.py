@@ -37,7 +37,7 @@ __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
     "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
-    "Plan", "SpgramPlan", "plan_spgram", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
+    "Plan", "SpgramPlan", "plan_spgram", "MsResamp2Plan", "Resamp2Plan", "plan_msresamp2", "plan_resamp2", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
     "estimate_req_filter_stopband_attenuation", "SymStream", "SymStreamR", "SymStreamRPlan", "plan_symstreamr", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
@@ -276,6 +276,31 @@ def plan_spgram(nfft, nframes):
     _check(lib.yagi_hip_plan_spgram(nfft, nframes, C.byref(p)))
     return SpgramPlan(p.fused, p.group, p.slab, p.workgroups, p.rows, p.folded, p.fold_rows, p.launch_frames,
                       p.accum_slab)
+
+
+MsResamp2Plan = collections.namedtuple(
+    "MsResamp2Plan", "fused lds tiles tpw head_tiles fast_tiles tail_first fast_tpw fast_lds F n cnt0 U walk walk_q long_halo")
+Resamp2Plan = collections.namedtuple("Resamp2Plan", "chain tiles lds")
+PLAN_WALK_GENERAL, PLAN_WALK_R1, PLAN_WALK_R2, PLAN_WALK_R4_RHO0, PLAN_WALK_R4_RHO2 = range(5)
+
+
+def plan_msresamp2(elem, interp, m_stage, n):
+    """yagi_hip_plan_msresamp2: what MsResamp2.execute_block of n execute() calls launches.  m_stage in the object's
+    stage order (get_stage_lengths); n, walk and walk_q of the answer in the decimator kernels' processing order,
+    where stage g of the object is processing stage len(m_stage) - 1 - g"""
+    ms = np.array(list(m_stage) or [0], np.uint64)
+    p = _capi.msresamp2_plan()
+    _check(lib.yagi_hip_plan_msresamp2(elem, int(bool(interp)), len(m_stage), _ptr(ms), n, C.byref(p)))
+    return MsResamp2Plan(p.fused, p.lds, p.tiles, p.tpw, p.head_tiles, p.fast_tiles, p.tail_first, p.fast_tpw,
+                         p.fast_lds, p.F, tuple(p.n), p.cnt0, p.U, tuple(p.walk), tuple(p.walk_q), p.long_halo)
+
+
+def plan_resamp2(elem, mode, m, nx):
+    """yagi_hip_plan_resamp2: resamp2_kernel (chain = 0) or, for a long decimator block, the one-stage case of the
+    MsResamp2 chain kernels (chain = 1: plan_msresamp2(elem, False, [m], nx // 2) has the details)"""
+    p = _capi.resamp2_plan()
+    _check(lib.yagi_hip_plan_resamp2(elem, mode, m, nx, C.byref(p)))
+    return Resamp2Plan(p.chain, p.tiles, p.lds)
 
 
 def plan_firpfb_all(elem, coeff_elem, nf, Ls):

@@ -204,6 +204,21 @@ class spgram_plan(C.Structure):
 
 _sig("yagi_hip_plan_spgram", sz, sz, C.POINTER(spgram_plan))
 
+class msresamp2_plan(C.Structure):
+    """yagi_hip_msresamp2_plan"""
+    _fields_ = [("fused", ci), ("tpw", ci), ("fast_tpw", ci), ("F", ci), ("n", ci * 3), ("cnt0", ci), ("U", ci),
+                ("walk", ci * 4), ("walk_q", ci * 4), ("long_halo", ci), ("lds", sz), ("fast_lds", sz), ("head_tiles", sz),
+                ("fast_tiles", sz), ("tail_first", sz), ("tiles", sz)]
+
+
+class resamp2_plan(C.Structure):
+    """yagi_hip_resamp2_plan"""
+    _fields_ = [("chain", ci), ("tiles", sz), ("lds", sz)]
+
+
+_sig("yagi_hip_plan_msresamp2", sz, ci, sz, vp, sz, C.POINTER(msresamp2_plan))
+_sig("yagi_hip_plan_resamp2", sz, ci, sz, sz, C.POINTER(resamp2_plan))
+
 for _k, _T in (("cf", cf32), ("f", f32)):
     p = f"yagi_hip_spgram{_k}_"
     _sig(p + "create", sz, ci, sz, sz, pvp)

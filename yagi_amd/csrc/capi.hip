@@ -2895,7 +2895,7 @@ struct Resamp2Obj {
     int block_dev(int mode, const T *x, size_t nx, T *y) {
         YG_TRY(check_form(mode, nx));
         if (nx == 0) return YAGI_OK;
-        if (mode == kR2Decim && nx >= ((size_t)1 << 19) && m <= 64) {
+        if (resamp2_takes_chain(mode, m, nx)) {
             // a long decimator block: the one-stage case of the MsResamp2 chain kernels (the same sums in the same order;
             // the middle of the block four outputs per lane through msresamp2_decim_fast_kernel)
             const int mk = m;
@@ -3006,7 +3006,7 @@ struct MsResamp2Obj {
         }
         const T *src = x;
         int pp = 0;
-        if (interp && num_stages <= 4 && fused_interp_fits()) {      // the whole chain in one launch (LDS-resident levels)
+        if (interp && fused_interp_fits()) {                         // the whole chain in one launch (LDS-resident levels)
             const int ns = (int)num_stages;
             int mk[4];
             C sc[4];
@@ -3033,7 +3033,7 @@ struct MsResamp2Obj {
                 cnt *= 2;
                 pp ^= 1;
             }
-        } else if (num_stages <= 4 && fused_decim_fits()) {          // the whole chain in one launch (LDS-resident intermediates)
+        } else if (!interp && fused_decim_fits()) {                  // the whole chain in one launch (LDS-resident intermediates)
             const int ns = (int)num_stages;
             int mk[4];
             C sc[4];
@@ -3064,15 +3064,18 @@ struct MsResamp2Obj {
         }
         return YAGI_OK;
     }
+    // the planners' answer (kernels.hpp): at most four stages whose streams fit 64 KiB of LDS
     bool fused_interp_fits() const {
+        if (num_stages > 4) return false;
         int mk[4];
         for (size_t k = 0; k < num_stages && k < 4; ++k) mk[k] = stage[k]->m;
-        return msresamp2_interp_lds((int)num_stages, mk, sizeof(T)) <= 64 * 1024;
+        return msresamp2_interp_plan((int)num_stages, mk, sizeof(T), 1).fused;
     }
     bool fused_decim_fits() const {
+        if (num_stages > 4) return false;
         int mk[4];
         for (size_t k = 0; k < num_stages && k < 4; ++k) mk[k] = stage[num_stages - 1 - k]->m;
-        return msresamp2_decim_lds((int)num_stages, mk, sizeof(T)) <= 64 * 1024;
+        return msresamp2_decim_plan((int)num_stages, mk, sizeof(T), 1).fused;
     }
     int block_host(const T *x, size_t n, T *y) {
         if (n == 0) return YAGI_OK;

@@ -133,12 +133,42 @@ constexpr int kR2MaxSemiLen = 1024;
 template <class T, class C>
 int launch_msresamp2_decim(int ns, const int *m, const C *scale, const C *const *h1, const T *const *state,
                            T *const *state_next, const T *x, T *y, size_t nout, hipStream_t st);
-size_t msresamp2_decim_lds(int ns, const int *m, size_t elem);
 // MsResamp2 interpolator chain in one launch: stages in processing order (input rate first)
 template <class T, class C>
 int launch_msresamp2_interp(int ns, const int *m, const C *scale, const C *const *h1, const T *const *state,
                             T *const *state_next, const T *x, T *y, size_t nin, hipStream_t st);
-size_t msresamp2_interp_lds(int ns, const int *m, size_t elem);
+// What the two launchers above do for a shape: host arithmetic, shared by the launchers, MsResamp2Obj's fused-or-chain
+// choice, Resamp2Obj's decimator route and the plan queries (yagi_hip_plan_msresamp2 / _resamp2).  elem = bytes per sample.
+struct MsFastGeom {
+    int F;                      // final outputs per tile of msresamp2_decim_fast_kernel
+    int n[3];                   // outputs of stage k per tile
+    int cnt0;                   // input pairs per tile
+    int U;                      // first input pair of a tile = 2^(S-1) * (its first output) - U
+};
+enum { kMsWalkGeneral = 0, kMsWalkR1 = 1, kMsWalkR2 = 2, kMsWalkR4Rho0 = 3, kMsWalkR4Rho2 = 4 };
+struct MsDecimPlan {
+    bool fused;                 // false: more than four stages or more than 64 KiB of LDS -- one launch per stage
+    size_t lds, fast_lds;       // dynamic LDS of the general / the fast kernel
+    long long head_tiles;       // general kernel: the outputs [0, 256 head_tiles) and [tail_first, nout)
+    long long fast_tiles;       // fast kernel: fast_tiles tiles of geo.F outputs from 256 head_tiles on (0: not launched)
+    long long tail_first;
+    long long tiles;            // tiles of the general kernel, tpw consecutive ones per workgroup
+    bool long_halo;             // a tile's stage-0 streams outgrow the per-lane registers: the instance that stages the rest from memory
+    int tpw, fast_tpw;
+    MsFastGeom geo;             // F = 0: no geometry with F >= 64 exists (or more than three stages)
+    int walk[4], walk_q[4];     // fast kernel: tap walk of stage k (kMsWalk*) and its group count Q
+};
+MsDecimPlan msresamp2_decim_plan(int ns, const int *m, size_t elem, size_t nout);
+struct MsInterpPlan {
+    bool fused;
+    size_t lds;
+    size_t tiles;               // workgroups of 256 inputs
+};
+MsInterpPlan msresamp2_interp_plan(int ns, const int *m, size_t elem, size_t nin);
+// a Resamp2 decimator block of nx samples runs as the one-stage case of the chain kernels (else resamp2_kernel)
+inline bool resamp2_takes_chain(int mode, int m, size_t nx) {
+    return mode == kR2Decim && nx >= ((size_t)1 << 19) && m <= 64;
+}
 // one block of nx input samples; state = [w0 (2m, oldest first)][w1 (2m)]; state_next receives the windows after the
 // block (must not alias state).  Outputs: filter 2 nx ((y0,y1) pairs), analyzer / synthesizer nx, decim nx/2, interp 2 nx.
 template <class T, class C>

@@ -129,6 +129,8 @@ __global__ void resamp2_state_kernel(const T *__restrict__ state, const T *__res
     state_next[j] = u < 0 ? state[s * m2 + (int)(m2 + u)] : r2_stream<T, MODE>(x, nx, s, u, c0);
 }
 
+static size_t resamp2_kernel_lds(int m, size_t elem) { return 2 * (size_t)(kR2Tile + 2 * m) * elem; }
+
 template <class T, class C, int MODE>
 static int launch_resamp2_mode(const T *state, const T *x, size_t nx, const C *h1, int m, C scale, int c0, T *y,
                                T *state_next, hipStream_t st) {
@@ -146,7 +148,7 @@ static int launch_resamp2_mode(const T *state, const T *x, size_t nx, const C *h
     if (nunits == 0) return YAGI_OK;
     const size_t tiles = (nunits + kR2Tile - 1) / kR2Tile;
     if (tiles > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "block too large");
-    const size_t lds = 2 * (size_t)(kR2Tile + 2 * m) * sizeof(T);
+    const size_t lds = resamp2_kernel_lds(m, sizeof(T));
     resamp2_kernel<T, C, MODE><<<(unsigned)tiles, kR2Lanes, lds, st>>>(state, x, nx, h1, m, scale, c0, y, nunits);
     YG_LAUNCH_CHECK();
     resamp2_state_kernel<T, MODE><<<(4 * m + 255) / 256, 256, 0, st>>>(state, x, nx, m, c0, (long long)n0, (long long)n1,
@@ -191,7 +193,7 @@ struct MsDecimArgs {
     T *state_next[kMsMaxStages];
 };
 
-template <class T, class C, int S>
+template <class T, class C, int S, bool LONG_HALO>
 __global__ void __launch_bounds__(256)
 msresamp2_decim_kernel(MsDecimArgs<T, C> a, const T *__restrict__ x, T *__restrict__ y, size_t nout, int tpw,
                        long long head_tiles, long long tail_first) {
@@ -275,6 +277,27 @@ msresamp2_decim_kernel(MsDecimArgs<T, C> a, const T *__restrict__ x, T *__restri
                     S1[0][j] = e;
                 }
             }
+            // the registers hold 256 NP entries: the tile's own pairs and a halo of up to 256.  A longer halo (2 m_0 - 1
+            // plus twice the later stages' reach: one stage from m = 129, two equal ones from m = 44, three from m = 19)
+            // runs the LONG_HALO instance, which stages the rest from memory; these entries were left unwritten before
+            // (a designed four-stage decimator at fc = 0.45, m = 20 / 4 / 3 / 3, has a halo of 355).  The other instance is
+            // the kernel as it was, instruction for instruction
+            if constexpr (LONG_HALO)
+                for (int j = (int)threadIdx.x + 256 * NP; j < cnt; j += 256) {
+                    const long long u = u0 + j;
+                    T e, o;
+                    if (u < 0) {
+                        const bool held = soff + j >= 0;
+                        o = held ? a.state[0][soff + j] : zero_of<T>();
+                        e = held ? a.state[0][m20 + soff + j] : zero_of<T>();
+                    } else {
+                        const long long uc = u < npairs ? u : npairs - 1;   // pairs past the block's end are never used
+                        e = x[2 * uc];
+                        o = x[2 * uc + 1];
+                    }
+                    S0[0][j] = o;
+                    S1[0][j] = e;
+                }
         }
         if (tile + 1 < tend) issue(tile + 1);
 #pragma unroll
@@ -346,14 +369,7 @@ msresamp2_decim_kernel(MsDecimArgs<T, C> a, const T *__restrict__ x, T *__restri
 // A tile makes F final outputs, F the largest count whose stage-0 streams fit 256 R_0 pairs (231 for m = 3 / 5 / 10).
 // Each output is the same FMA chain in tap order as in resamp2_kernel: bit-identical to the chain of launches.
 // ---------------------------------------------------------------------------------------------
-struct MsFastGeom {
-    int F;                      // final outputs per tile
-    int n[3];                   // outputs of stage k per tile
-    int cnt0;                   // input pairs per tile
-    int U;                      // first input pair of a tile = 2^(S-1) * (its first output) - U
-};
-
-template <class T> struct MsPair { T e, o; };
+template <class T> struct MsPair { T e, o; };                       // (MsFastGeom, the tile's geometry: kernels.hpp)
 
 // The walk over the entries of a lane's R outputs (R = 2, 4): entry t = R g + c feeds output r with tap t - r, so every
 // output sees its taps in rising order.  With 2m = R Q + RHO (RHO = 0, or 2 at R = 4) the set of (c, r) pairs that are taps
@@ -402,10 +418,11 @@ __device__ __forceinline__ void ms_fast_stage(const T *__restrict__ S1l, const T
     }
 }
 
-template <class T> __host__ __device__ constexpr int ms_plane_stride(int R) {
+__host__ __device__ constexpr int ms_plane_stride_of(size_t elem, int R) {
     // >= 256 positions; the stage-0 fill (lane -> plane lane mod R, position lane div R) spreads over the banks
-    return 256 + (R > 1 ? (sizeof(T) == 4 ? 64 : 32) / R : 0);
+    return 256 + (R > 1 ? (elem == 4 ? 64 : 32) / R : 0);
 }
+template <class T> __host__ __device__ constexpr int ms_plane_stride(int R) { return ms_plane_stride_of(sizeof(T), R); }
 
 template <class T, class C, int S>
 __global__ void __launch_bounds__(256)
@@ -509,51 +526,42 @@ msresamp2_decim_fast_kernel(MsDecimArgs<T, C> a, MsFastGeom geo, const T *__rest
 }
 
 template <class T, class C, int S>
-static void launch_ms_fast(const MsDecimArgs<T, C> &a, const MsFastGeom &geo, const T *x, T *y, long long o_first,
-                           long long ntiles, hipStream_t st) {
-    size_t lds = 0;
-    constexpr int RL = S == 1 ? 4 : 1;
-    for (int k = 0; k < (S == 3 ? 2 : S); ++k)                       // three stages: the last one's streams lie over stage 0's
-        lds += 2 * (size_t)(RL << (S - 1 - k)) * ms_plane_stride<T>(RL << (S - 1 - k)) * sizeof(T);
-    if (S == 1) lds += 4 * (size_t)ms_plane_stride<T>(4) * sizeof(T);   // the output planes
-    lds += 64 * sizeof(T);                                           // a lane past the last output may read past its plane
-    // two consecutive tiles per workgroup (the second tile's input in flight during the first): 1 / 2 / 4 / 8 / 16 tiles
-    // measure 115.6 / 112.7 / 118.5 / 123.4 / 129.4 us at 2^26 inputs -- many short workgroups interleave better than
-    // a few long ones prefetch
-    const int tpw = S == 1 ? 1 : 2;                                  // one stage: tiles of ~1000 outputs, 1 / 2 / 4 per workgroup: 153.7 / 161.6 / 166.6 us
-    const long long nblk = (ntiles + tpw - 1) / tpw;
-    msresamp2_decim_fast_kernel<T, C, S><<<(unsigned)nblk, 256, lds, st>>>(a, geo, x, y, o_first, (int)ntiles, tpw);
+static void launch_ms_fast(const MsDecimArgs<T, C> &a, const MsDecimPlan &p, const T *x, T *y, hipStream_t st) {
+    const long long nblk = (p.fast_tiles + p.fast_tpw - 1) / p.fast_tpw;
+    msresamp2_decim_fast_kernel<T, C, S><<<(unsigned)nblk, 256, p.fast_lds, st>>>(a, p.geo, x, y, p.head_tiles * kMsTile,
+                                                                                   (int)p.fast_tiles, p.fast_tpw);
 }
 
-template <class T, class C>
-int launch_msresamp2_decim(int ns, const int *m, const C *scale, const C *const *h1, const T *const *state,
-                           T *const *state_next, const T *x, T *y, size_t nout, hipStream_t st) {
-    if (ns < 1 || ns > kMsMaxStages) return fail(YAGI_ERR_INTERNAL, "msresamp2: %d stages in one launch", ns);
-    if (nout == 0) return YAGI_OK;
-    MsDecimArgs<T, C> a;
-    a.ns = ns;
+// dynamic LDS of msresamp2_decim_fast_kernel<T, C, S>
+static size_t ms_fast_lds(int S, size_t elem) {
     size_t lds = 0;
-    for (int k = 0; k < ns; ++k) {
-        a.m[k] = m[k];
-        a.scale[k] = scale[k];
-        a.h1[k] = h1[k];
-        a.state[k] = state[k];
-        a.state_next[k] = state_next[k];
-    }
+    const int RL = S == 1 ? 4 : 1;
+    for (int k = 0; k < (S == 3 ? 2 : S); ++k)                       // three stages: the last one's streams lie over stage 0's
+        lds += 2 * (size_t)(RL << (S - 1 - k)) * ms_plane_stride_of(elem, RL << (S - 1 - k)) * elem;
+    if (S == 1) lds += 4 * (size_t)ms_plane_stride_of(elem, 4) * elem;   // the output planes
+    return lds + 64 * elem;                                          // a lane past the last output may read past its plane
+}
+
+// What a decimator call of nout outputs launches (m in processing order, full rate first).
+MsDecimPlan msresamp2_decim_plan(int ns, const int *m, size_t elem, size_t nout) {
+    MsDecimPlan p{};
+    if (ns < 1 || ns > kMsMaxStages) return p;
     {   // the widest tile: ranges of an interior workgroup
         long long lo = 0, hi = kMsTile;
         for (int k = ns - 1; k >= 0; --k) {
-            lds += 2 * (size_t)((hi - lo) + 2 * m[k] - 1) * sizeof(T);
+            p.lds += 2 * (size_t)((hi - lo) + 2 * m[k] - 1) * elem;
+            if (k == 0) p.long_halo = (hi - lo) + 2 * m[0] - 1 > 256 * ((1 << (ns - 1)) + 1);   // more stage-0 entries than a lane's registers hold
             lo = 2 * (lo - (2 * m[k] - 1));
             hi = 2 * hi;
         }
     }
-    if (lds > 64 * 1024) return fail(YAGI_ERR_INTERNAL, "msresamp2: the fused chain needs %zu bytes of LDS", lds);
+    p.fused = p.lds <= 64 * 1024;
+    if (!p.fused) return p;
     // the middle of a long block goes to the fast kernel: tiles of F outputs from the first multiple of 256 whose halo
     // lies inside the block, the general kernel keeps that head and a tail of at least one output (it writes the windows)
-    long long head_tiles = ((long long)nout + kMsTile - 1) / kMsTile, tail_first = head_tiles * kMsTile;
-    MsFastGeom geo{};
-    long long fast_tiles = 0;
+    p.head_tiles = ((long long)nout + kMsTile - 1) / kMsTile;
+    p.tail_first = p.head_tiles * kMsTile;
+    MsFastGeom &geo = p.geo;
     if (ns <= 3) {
         const int P2 = 1 << (ns - 1);                                 // input pairs per final output
         const int R0 = ns == 1 ? 4 : P2;                              // pairs per lane and tile
@@ -580,32 +588,66 @@ int launch_msresamp2_decim(int ns, const int *m, const C *scale, const C *const 
             const long long head = (o_min + kMsTile - 1) / kMsTile;
             const long long room = (long long)nout - 1 - head * kMsTile;
             if (room >= 1024LL * 231) {                               // from ~2^18 outputs on
-                fast_tiles = room / geo.F;
-                head_tiles = head;
-                tail_first = head * kMsTile + fast_tiles * geo.F;
+                p.fast_tiles = room / geo.F;
+                p.head_tiles = head;
+                p.tail_first = head * kMsTile + p.fast_tiles * geo.F;
             }
+            // the tap walk of every stage (ms_fast_stage): R_k outputs per lane, 2 m_k = R_k Q + RHO
+            for (int k = 0; k < ns; ++k) {
+                const int R = (ns == 1 ? 4 : 1) << (ns - 1 - k), m2 = 2 * m[k];
+                p.walk[k] = R == 1 ? kMsWalkR1 : R == 2 ? kMsWalkR2 : (m2 & 2) ? kMsWalkR4Rho2 : kMsWalkR4Rho0;
+                p.walk_q[k] = R == 1 ? m2 : (m2 - (R == 4 ? (m2 & 2) : 0)) / R;
+            }
+            p.fast_lds = ms_fast_lds(ns, elem);
+            // two consecutive tiles per workgroup (the second tile's input in flight during the first): 1 / 2 / 4 / 8 / 16 tiles
+            // measure 115.6 / 112.7 / 118.5 / 123.4 / 129.4 us at 2^26 inputs -- many short workgroups interleave better than
+            // a few long ones prefetch
+            p.fast_tpw = ns == 1 ? 1 : 2;                             // one stage: tiles of ~1000 outputs, 1 / 2 / 4 per workgroup: 153.7 / 161.6 / 166.6 us
         }
     }
-    const long long tiles = head_tiles + (((long long)nout - tail_first) + kMsTile - 1) / kMsTile;
+    p.tiles = p.head_tiles + (((long long)nout - p.tail_first) + kMsTile - 1) / kMsTile;
     // consecutive tiles per workgroup (input prefetch across tiles) while >= ~4096 workgroups remain
-    int tpw = 1;
-    while (tpw < 8 && tiles / (2 * tpw) >= 4096) tpw *= 2;
-    const long long nblk = (tiles + tpw - 1) / tpw;
-    if (nblk > 0x7fffffffLL || fast_tiles > 0x7fffffffLL) return fail(YAGI_ERR_CONFIG, "block too large");
-    if (fast_tiles) {
-        const long long o_first = head_tiles * kMsTile;
+    p.tpw = 1;
+    while (p.tpw < 8 && p.tiles / (2 * p.tpw) >= 4096) p.tpw *= 2;
+    return p;
+}
+
+template <class T, class C>
+int launch_msresamp2_decim(int ns, const int *m, const C *scale, const C *const *h1, const T *const *state,
+                           T *const *state_next, const T *x, T *y, size_t nout, hipStream_t st) {
+    if (ns < 1 || ns > kMsMaxStages) return fail(YAGI_ERR_INTERNAL, "msresamp2: %d stages in one launch", ns);
+    if (nout == 0) return YAGI_OK;
+    MsDecimArgs<T, C> a;
+    a.ns = ns;
+    for (int k = 0; k < ns; ++k) {
+        a.m[k] = m[k];
+        a.scale[k] = scale[k];
+        a.h1[k] = h1[k];
+        a.state[k] = state[k];
+        a.state_next[k] = state_next[k];
+    }
+    const MsDecimPlan p = msresamp2_decim_plan(ns, m, sizeof(T), nout);
+    if (!p.fused) return fail(YAGI_ERR_INTERNAL, "msresamp2: the fused chain needs %zu bytes of LDS", p.lds);
+    const long long nblk = (p.tiles + p.tpw - 1) / p.tpw;
+    if (nblk > 0x7fffffffLL || p.fast_tiles > 0x7fffffffLL) return fail(YAGI_ERR_CONFIG, "block too large");
+    if (p.fast_tiles) {
         switch (ns) {
-        case 1: launch_ms_fast<T, C, 1>(a, geo, x, y, o_first, fast_tiles, st); break;
-        case 2: launch_ms_fast<T, C, 2>(a, geo, x, y, o_first, fast_tiles, st); break;
-        default: launch_ms_fast<T, C, 3>(a, geo, x, y, o_first, fast_tiles, st); break;
+        case 1: launch_ms_fast<T, C, 1>(a, p, x, y, st); break;
+        case 2: launch_ms_fast<T, C, 2>(a, p, x, y, st); break;
+        default: launch_ms_fast<T, C, 3>(a, p, x, y, st); break;
         }
         YG_LAUNCH_CHECK();
     }
-    switch (ns) {
-    case 1: msresamp2_decim_kernel<T, C, 1><<<(unsigned)nblk, 256, lds, st>>>(a, x, y, nout, tpw, head_tiles, tail_first); break;
-    case 2: msresamp2_decim_kernel<T, C, 2><<<(unsigned)nblk, 256, lds, st>>>(a, x, y, nout, tpw, head_tiles, tail_first); break;
-    case 3: msresamp2_decim_kernel<T, C, 3><<<(unsigned)nblk, 256, lds, st>>>(a, x, y, nout, tpw, head_tiles, tail_first); break;
-    default: msresamp2_decim_kernel<T, C, 4><<<(unsigned)nblk, 256, lds, st>>>(a, x, y, nout, tpw, head_tiles, tail_first); break;
+    auto general = [&](auto kernel) { kernel<<<(unsigned)nblk, 256, p.lds, st>>>(a, x, y, nout, p.tpw, p.head_tiles, p.tail_first); };
+    switch (ns + (p.long_halo ? kMsMaxStages : 0)) {                 // the long-halo instances last: the others keep their place in the code object
+    case 1: general(msresamp2_decim_kernel<T, C, 1, false>); break;
+    case 2: general(msresamp2_decim_kernel<T, C, 2, false>); break;
+    case 3: general(msresamp2_decim_kernel<T, C, 3, false>); break;
+    case 4: general(msresamp2_decim_kernel<T, C, 4, false>); break;
+    case 5: general(msresamp2_decim_kernel<T, C, 1, true>); break;
+    case 6: general(msresamp2_decim_kernel<T, C, 2, true>); break;
+    case 7: general(msresamp2_decim_kernel<T, C, 3, true>); break;
+    default: general(msresamp2_decim_kernel<T, C, 4, true>); break;
     }
     YG_LAUNCH_CHECK();
     return YAGI_OK;
@@ -723,19 +765,22 @@ msresamp2_interp_kernel(MsDecimArgs<T, C> a, const T *__restrict__ x, T *__restr
     }
 }
 
-static size_t msresamp2_interp_lds_impl(int ns, const int *m, size_t elem) {
-    long long lo = 0, hi = (long long)kMsTile << ns;
-    size_t lds = 0;
+// What an interpolator call of nin inputs launches (m in processing order, input rate first).
+MsInterpPlan msresamp2_interp_plan(int ns, const int *m, size_t elem, size_t nin) {
+    MsInterpPlan p{};
+    if (ns < 1 || ns > kMsMaxStages) return p;
+    long long lo = 0, hi = (long long)kMsTile << ns;                 // the ranges of an interior workgroup's levels
     for (int k = ns - 1; k >= 0; --k) {
         long long l = (lo >> 1) - (2 * m[k] - 1), h = hi >> 1;
         if (k > 0) { l &= ~1ll; h = (h + 1) & ~1ll; }
-        lds += 2 * (size_t)(h - l) * elem;
+        p.lds += 2 * (size_t)(h - l) * elem;
         lo = l;
         hi = h;
     }
-    return lds;
+    p.fused = p.lds <= 64 * 1024;
+    if (p.fused) p.tiles = (nin + kMsTile - 1) / kMsTile;
+    return p;
 }
-size_t msresamp2_interp_lds(int ns, const int *m, size_t elem) { return msresamp2_interp_lds_impl(ns, m, elem); }
 
 template <class T, class C>
 int launch_msresamp2_interp(int ns, const int *m, const C *scale, const C *const *h1, const T *const *state,
@@ -751,9 +796,9 @@ int launch_msresamp2_interp(int ns, const int *m, const C *scale, const C *const
         a.state[k] = state[k];
         a.state_next[k] = state_next[k];
     }
-    const size_t lds = msresamp2_interp_lds_impl(ns, m, sizeof(T));
-    if (lds > 64 * 1024) return fail(YAGI_ERR_INTERNAL, "msresamp2: the fused chain needs %zu bytes of LDS", lds);
-    const size_t tiles = (nin + kMsTile - 1) / kMsTile;
+    const MsInterpPlan p = msresamp2_interp_plan(ns, m, sizeof(T), nin);
+    if (!p.fused) return fail(YAGI_ERR_INTERNAL, "msresamp2: the fused chain needs %zu bytes of LDS", p.lds);
+    const size_t lds = p.lds, tiles = p.tiles;
     if (tiles > 0x7fffffffull) return fail(YAGI_ERR_CONFIG, "block too large");
     switch (ns) {
     case 1: msresamp2_interp_kernel<T, C, 1><<<(unsigned)tiles, 256, lds, st>>>(a, x, y, nin); break;
@@ -771,18 +816,6 @@ template int launch_msresamp2_interp<cf32, float>(int, const int *, const float 
 template int launch_msresamp2_interp<cf32, cf32>(int, const int *, const cf32 *, const cf32 *const *, const cf32 *const *,
                                                  cf32 *const *, const cf32 *, cf32 *, size_t, hipStream_t);
 
-// LDS the fused chain would need (host-side dispatch test)
-size_t msresamp2_decim_lds(int ns, const int *m, size_t elem) {
-    size_t lds = 0;
-    long long lo = 0, hi = kMsTile;
-    for (int k = ns - 1; k >= 0; --k) {
-        lds += 2 * (size_t)((hi - lo) + 2 * m[k] - 1) * elem;
-        lo = 2 * (lo - (2 * m[k] - 1));
-        hi = 2 * hi;
-    }
-    return lds;
-}
-
 template int launch_msresamp2_decim<float, float>(int, const int *, const float *, const float *const *, const float *const *,
                                                   float *const *, const float *, float *, size_t, hipStream_t);
 template int launch_msresamp2_decim<cf32, float>(int, const int *, const float *, const float *const *, const cf32 *const *,
@@ -798,3 +831,73 @@ template int launch_resamp2<cf32, cf32>(int, const cf32 *, const cf32 *, size_t,
                                         cf32 *, hipStream_t);
 
 }  // namespace yagi
+
+extern "C" int yagi_hip_plan_msresamp2(size_t elem, int interp, size_t ns, const size_t *m, size_t n,
+                                       yagi_hip_msresamp2_plan *out) try {
+    using namespace yagi;
+    if (!out || !m) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    if ((elem != 4 && elem != 8) || ns < 1 || ns > 16 || n < 1 || n > ((size_t)1 << 40))
+        return fail(YAGI_ERR_CONFIG, "plan query: bad shape (elem 4 or 8, 1 <= ns <= 16, 1 <= n <= 2^40)");
+    for (size_t g = 0; g < ns; ++g)
+        if (m[g] < 2 || m[g] > (size_t)kR2MaxSemiLen)
+            return fail(YAGI_ERR_CONFIG, "plan query: filter semi-length %zu out of range [2, %d]", m[g], kR2MaxSemiLen);
+    yagi_hip_msresamp2_plan o{};
+    if (ns <= (size_t)kMsMaxStages) {
+        int mk[kMsMaxStages];                                        // processing order: the decimator runs stage ns - 1 first
+        for (size_t k = 0; k < ns; ++k) mk[k] = (int)m[interp ? k : ns - 1 - k];
+        if (interp) {
+            const MsInterpPlan p = msresamp2_interp_plan((int)ns, mk, elem, n);
+            o.fused = p.fused ? 1 : 0;
+            o.lds = p.lds;
+            o.tiles = p.tiles;
+            o.tpw = p.fused ? 1 : 0;
+        } else {
+            const MsDecimPlan p = msresamp2_decim_plan((int)ns, mk, elem, n);
+            o.fused = p.fused ? 1 : 0;
+            o.lds = p.lds;
+            if (p.fused) {
+                o.tpw = p.tpw;
+                o.head_tiles = (size_t)p.head_tiles;
+                o.fast_tiles = (size_t)p.fast_tiles;
+                o.tail_first = (size_t)p.tail_first;
+                o.tiles = (size_t)p.tiles;
+                o.F = p.geo.F;
+                for (int k = 0; k < 3; ++k) o.n[k] = p.geo.n[k];
+                o.cnt0 = p.geo.cnt0;
+                o.U = p.geo.U;
+                o.fast_tpw = p.fast_tpw;
+                o.fast_lds = p.fast_lds;
+                o.long_halo = p.long_halo ? 1 : 0;
+                for (int k = 0; k < 4; ++k) {
+                    o.walk[k] = p.walk[k];
+                    o.walk_q[k] = p.walk_q[k];
+                }
+            }
+        }
+    }
+    *out = o;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+extern "C" int yagi_hip_plan_resamp2(size_t elem, int mode, size_t m, size_t nx, yagi_hip_resamp2_plan *out) try {
+    using namespace yagi;
+    if (!out) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    if ((elem != 4 && elem != 8) || mode < kR2Filter || mode > kR2Interp || m < 2 || m > (size_t)kR2MaxSemiLen || nx < 1 ||
+        nx > ((size_t)1 << 40) || (mode != kR2Filter && mode != kR2Interp && (nx & 1)))
+        return fail(YAGI_ERR_CONFIG, "plan query: bad shape (elem 4 or 8, a form of Resamp2, 2 <= m <= %d, 1 <= nx <= 2^40, "
+                                     "pairs of samples for the forms that consume pairs)", kR2MaxSemiLen);
+    yagi_hip_resamp2_plan o{};
+    if (resamp2_takes_chain(mode, (int)m, nx)) {
+        const int mk = (int)m;
+        const MsDecimPlan p = msresamp2_decim_plan(1, &mk, elem, nx / 2);
+        o.chain = 1;
+        o.tiles = (size_t)p.tiles;
+        o.lds = p.lds;
+    } else {
+        const size_t nunits = mode == kR2Interp ? nx : (nx + 1) / 2;
+        o.tiles = (nunits + kR2Tile - 1) / kR2Tile;
+        o.lds = resamp2_kernel_lds((int)m, elem);
+    }
+    *out = o;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
