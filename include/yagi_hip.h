@@ -1596,8 +1596,8 @@ YAGI_AUTOCORR_API(rrrf, float)
  *   flush(events, cap, &count)   closes the pending run, an event if it is long enough; the sample counter stays
  *   detect_host(...)          the definition on the host alone (no device needed), one call on a stream from reset():
  *                             the sequential state machine over Autocorr's host arithmetic, the capacity rule included
- * Not built: merging runs across gaps, a per-sample push, a known-preamble cross-correlation front
- * end, soft outputs, sharding.
+ * Not built: merging runs across gaps, a per-sample push, soft outputs, sharding.  A known-preamble
+ * cross-correlation front end is another object: PreambleDetector, below.
  * Device form: burstdet_kernels.hip: a tile kernel and a one-workgroup stitch kernel per call; the stitch walks a
  * call's segments one by one, about 0.3 us each on an MI355X, so a block that is all burst costs milliseconds. */
 #define YAGI_BURSTDET_SEGMAX 8192
@@ -1633,6 +1633,91 @@ typedef struct yagi_hip_burstdet_rrrf_s *yagi_hip_burstdet_rrrf;
 YAGI_BURSTDET_API(cccf, yagi_cf32)
 YAGI_BURSTDET_API(rrrf, float)
 #undef YAGI_BURSTDET_API
+
+/* ---- PreambleDetector: a bank of known-preamble correlators, a normalised threshold and run / peak extraction ---------
+ * Absent from the reference; defined by composition of what this library already pins.
+ * PreambleDetector(p[L], dphi[K], threshold, energy_floor, min_length), Complex<f32> only (cccf).  It correlates the
+ * stream with the preamble p under K carrier-offset hypotheses dphi_k (radians per sample, used in the caller's order,
+ * duplicates allowed) and returns events, not samples.
+ * Templates, built once on the host: theta = (double)dphi_k (double)i and v_k[i] = conj(p[i]) e^{-j theta}, the four
+ * products and two sums in f64 from the f32 parts of p and cos / sin of theta, each component rounded once to f32
+ * (dphi_k = 0 gives conj(p) exactly).  yagi_hip_pdet_templates builds the same words without a device.
+ *     thr2 = fl(threshold * threshold), formed once on the host
+ *     ep   = sum over i = 0 .. L-1, from +0.0, of fl(fl(p.re^2) + fl(p.im^2)); it must be finite and > 0
+ * With X the stream since reset(), X[j] = 0 for j < 0, n the absolute sample index and w[i] = X[n - L + 1 + i], all in
+ * f32 and every product, add and quotient rounded on its own (no FMA):
+ *     rxy_k[n]  = dotprod(w, v_k): the sequential sum over i from +0.0 of num-complex's product,
+ *                 re += fl(w.re v.re) - fl(w.im v.im),  im += fl(w.re v.im) + fl(w.im v.re)
+ *     energy[n] = sum over i, in the same order from +0.0, of fl(fl(w[i].re^2) + fl(w[i].im^2))   (Autocorr(L, 0)'s)
+ *     m_k[n]    = fl(fl(re^2) + fl(im^2)) of rxy_k[n]
+ *     kb        = 0; for k = 1 .. K-1 in order kb = k where m_k > m_kb (strict: ties keep the lowest k, a NaN m_0 stays)
+ *     q[n]      = fl(energy[n] * ep)
+ *     hit[n]    = energy[n] > energy_floor && m_kb > fl(thr2 * q[n])   strict, so a NaN gives no hit
+ *     r[n]      = m_kb / q[n]                                         IEEE division, looked at only where hit[n]
+ * r <= 1 up to rounding (Cauchy-Schwarz), so sensible thresholds lie in (0, 1).  Runs, peaks, pending run, events, the
+ * chunking property, the capacity rule (tiles of YAGI_PDET_TILE samples, YAGI_PDET_SEGMAX segments beyond one per tile)
+ * and the events buffer are BurstDetector's, word for word.  An event's ratio, energy, rxy and hypothesis (kb) are taken
+ * at its peak: peak - (L - 1) is where the preamble starts, dphi[hypothesis] the coarse carrier offset, arg(rxy) the
+ * carrier phase.
+ *   create(p, L, dphi, K, threshold, energy_floor, min_length)   1 <= L <= YAGI_PDET_LMAX, 1 <= K <= YAGI_PDET_KMAX, dphi
+ *                             finite, ep finite and > 0, threshold finite and > 0, energy_floor finite and >= 0,
+ *                             min_length >= 1; anything else is YAGI_ERR_CONFIG, decided before any device is asked for
+ *   clone / reset             a copy of history, pending run and sample counter / all three cleared
+ *   get_length / get_hypotheses / get_threshold / get_energy_floor / get_min_length / get_preamble_energy (ep)
+ *   get_dphi(out[K]) / get_templates(out[K L])   the hypotheses and the templates, row k = v_k
+ *   get_position / get_pending(&has, &ev)   as BurstDetector's; they synchronise
+ *   detect_block(x, n, events, cap, &count, &overflow)   host slices, staged through the device
+ *   detect_block_dev(x_dev, n, events_dev, cap, status_dev)   status_dev = uint32_t[2] {count, overflow}; asynchronous on
+ *                             the object's stream, no host synchronisation.  n = 0 writes {0, 0}.  events_dev may be
+ *                             NULL where cap = 0.  The buffers MUST NOT OVERLAP (YAGI_ERR_CONFIG).
+ *   correlate_block(x, n, rxy, energy)   the bank's raw output: pushes n samples like any block call (the sample counter
+ *                             advances, a pending run is dropped: it could not be continued) and writes
+ *                             rxy[k n + i] = rxy_k and energy[i] after sample i; energy may be NULL
+ *   correlate_block_dev       the same on device buffers, which MUST NOT OVERLAP (YAGI_ERR_CONFIG); n = 0 is a no-op
+ *   flush(events, cap, &count)   closes the pending run, an event if it is long enough; the sample counter stays
+ *   detect_host(...)          the definition on the host alone (no device needed), one call on a stream from reset()
+ * Not built: an rrrf kind, fine interpolation of timing and frequency, an FFT / overlap-save or
+ * MFMA correlator, L beyond LMAX, a per-sample push, hysteresis, sharding.
+ * Device form: pdet_kernels.hip: a tile kernel and a one-workgroup stitch kernel per call. */
+#define YAGI_PDET_LMAX 1024
+#define YAGI_PDET_KMAX 32
+#define YAGI_PDET_TILE 2048
+#define YAGI_PDET_SEGMAX 8192
+typedef struct yagi_preamble_event {
+    uint64_t start, length, peak;            /* absolute sample indices */
+    float ratio, energy, rxy_re, rxy_im;     /* r, energy and rxy of the best hypothesis at the peak */
+    uint32_t hypothesis, pad;                /* kb at the peak; pad = 0 */
+} yagi_preamble_event;
+typedef struct yagi_hip_pdet_cccf_s *yagi_hip_pdet_cccf;
+int yagi_hip_pdet_templates(const yagi_cf32 *p, size_t L, const float *dphi, size_t K, yagi_cf32 *out);
+int yagi_hip_pdet_cccf_create(const yagi_cf32 *p, size_t L, const float *dphi, size_t K, float threshold,
+                              float energy_floor, uint64_t min_length, yagi_hip_pdet_cccf *q);
+int yagi_hip_pdet_cccf_destroy(yagi_hip_pdet_cccf q);
+int yagi_hip_pdet_cccf_clone(yagi_hip_pdet_cccf q, yagi_hip_pdet_cccf *out);
+int yagi_hip_pdet_cccf_set_stream(yagi_hip_pdet_cccf q, yagi_stream_t s);
+int yagi_hip_pdet_cccf_reset(yagi_hip_pdet_cccf q);
+int yagi_hip_pdet_cccf_get_length(yagi_hip_pdet_cccf q, size_t *length);
+int yagi_hip_pdet_cccf_get_hypotheses(yagi_hip_pdet_cccf q, size_t *hypotheses);
+int yagi_hip_pdet_cccf_get_threshold(yagi_hip_pdet_cccf q, float *threshold);
+int yagi_hip_pdet_cccf_get_energy_floor(yagi_hip_pdet_cccf q, float *energy_floor);
+int yagi_hip_pdet_cccf_get_min_length(yagi_hip_pdet_cccf q, uint64_t *min_length);
+int yagi_hip_pdet_cccf_get_preamble_energy(yagi_hip_pdet_cccf q, float *ep);
+int yagi_hip_pdet_cccf_get_dphi(yagi_hip_pdet_cccf q, float *dphi);
+int yagi_hip_pdet_cccf_get_templates(yagi_hip_pdet_cccf q, yagi_cf32 *templates);
+int yagi_hip_pdet_cccf_get_position(yagi_hip_pdet_cccf q, uint64_t *position);
+int yagi_hip_pdet_cccf_get_pending(yagi_hip_pdet_cccf q, int *has_pending, yagi_preamble_event *ev);
+int yagi_hip_pdet_cccf_detect_block(yagi_hip_pdet_cccf q, const yagi_cf32 *x, size_t n, yagi_preamble_event *events,
+                                    size_t cap, size_t *count, int *overflow);
+int yagi_hip_pdet_cccf_detect_block_dev(yagi_hip_pdet_cccf q, const yagi_cf32 *x_dev, size_t n,
+                                        yagi_preamble_event *events_dev, size_t cap, uint32_t *status_dev);
+int yagi_hip_pdet_cccf_correlate_block(yagi_hip_pdet_cccf q, const yagi_cf32 *x, size_t n, yagi_cf32 *rxy, float *energy);
+int yagi_hip_pdet_cccf_correlate_block_dev(yagi_hip_pdet_cccf q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *rxy_dev,
+                                           float *energy_dev);
+int yagi_hip_pdet_cccf_flush(yagi_hip_pdet_cccf q, yagi_preamble_event *events, size_t cap, size_t *count);
+int yagi_hip_pdet_cccf_detect_host(const yagi_cf32 *p, size_t L, const float *dphi, size_t K, float threshold,
+                                   float energy_floor, uint64_t min_length, const yagi_cf32 *x, size_t n,
+                                   yagi_preamble_event *events, size_t cap, size_t *count, int *overflow,
+                                   int *has_pending, yagi_preamble_event *pending);
 
 /* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */

@@ -18,6 +18,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     MSequence / BSequence      src/sequence/msequence.rs:41-164, bsequence.rs:8-195
     Autocorr                   (absent from the reference: src/filter/autocorr.rs is empty)
     BurstDetector              (absent from the reference: Autocorr, threshold and run / peak extraction fused)
+    PreambleDetector           (absent from the reference: a bank of known-preamble correlators, threshold and events)
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -36,7 +37,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "SpgramPlan", "plan_spgram", "MsResamp2Plan", "Resamp2Plan", "plan_msresamp2", "plan_resamp2", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
@@ -1960,6 +1961,158 @@ def burst_detect_host(kind, x, window_size, delay, threshold, energy_floor=0.0, 
     _check(getattr(lib, f"yagi_hip_burstdet_{kind}_detect_host")(
         window_size, delay, threshold, energy_floor, min_length, _ptr(x), x.size, _ptr(ev), room, C.byref(count),
         C.byref(over), C.byref(has), _ptr(pend)))
+    return ev[:min(count.value, room)].copy(), bool(over.value), (pend[0] if has.value else None)
+
+
+PDET_LMAX = 1024         # YAGI_PDET_LMAX: the longest preamble of PreambleDetector
+PDET_KMAX = 32           # YAGI_PDET_KMAX: the most carrier-offset hypotheses
+PDET_TILE = 2048         # YAGI_PDET_TILE: outputs per workgroup of pdet_kernels.hip
+PDET_SEGMAX = 8192       # YAGI_PDET_SEGMAX: segments a PreambleDetector call may hold beyond one per tile
+# yagi_preamble_event: start, length and peak are absolute sample indices; ratio, energy, rxy and hypothesis are taken
+# at the peak
+PREAMBLE_EVENT = np.dtype([("start", np.uint64), ("length", np.uint64), ("peak", np.uint64), ("ratio", np.float32),
+                           ("energy", np.float32), ("rxy_re", np.float32), ("rxy_im", np.float32),
+                           ("hypothesis", np.uint32), ("pad", np.uint32)])
+
+
+def _pdet_args(p, dphi, min_length, kind):
+    if kind != "cccf":
+        raise ConfigError(f"unknown type combination {kind!r}")
+    if not (isinstance(min_length, (int, np.integer)) and 0 <= min_length < 2 ** 64):
+        raise ConfigError("min_length must be an integer of at least one")
+    p, dphi = _arr(p, np.complex64), _arr(dphi, np.float32)
+    if p.ndim != 1 or dphi.ndim != 1:
+        raise ConfigError("the preamble and the hypotheses are one-dimensional")
+    return p, dphi
+
+
+def preamble_templates(p, dphi):
+    """PreambleDetector's templates, no device needed: row k is v_k[i] = conj(p[i]) e^{-j dphi_k i}, evaluated in f64 and
+    rounded once per component (yagi_hip.h)"""
+    p, dphi = _pdet_args(p, dphi, 1, "cccf")
+    out = np.zeros((dphi.size, p.size), np.complex64)
+    _check(lib.yagi_hip_pdet_templates(_ptr(p), p.size, _ptr(dphi), dphi.size, _ptr(out)))
+    return out
+
+
+class PreambleDetector(_Handle):
+    """PreambleDetector(p, dphi, threshold, energy_floor=0, min_length=1), Complex<f32> only: the stream is correlated
+    with the preamble p (L samples) under the K carrier-offset hypotheses dphi (radians per sample), rxy_k[n] =
+    dotprod(last L samples, conj(p) e^{-j dphi_k i}); with m the largest |rxy_k[n]|^2 (the lowest k on ties), hit[n] =
+    energy[n] > energy_floor and m > threshold^2 energy[n] ep, ep the preamble's energy, and the runs of consecutive
+    hits with their peaks (the largest m / (energy ep), the earliest on ties), all in f32 and rounded as yagi_hip.h and
+    DESIGN.md section 6 say.  A block call reads the samples and returns only the events they close (PREAMBLE_EVENT
+    records, ordered by start); a run that reaches the call's last sample stays pending for the next call or flush().
+    peak - (L - 1) is where the preamble starts, dphi[hypothesis] the coarse carrier offset, arg(rxy) the carrier phase.
+    A call whose runs fall into more than tiles + PDET_SEGMAX per-tile segments reports overflow and no events.  The
+    block calls run pdet_kernels.hip.  L <= PDET_LMAX, K <= PDET_KMAX."""
+    _prefix = "yagi_hip_pdet_cccf_"
+
+    def __init__(self, p, dphi, threshold, energy_floor=0.0, min_length=1, kind="cccf"):
+        p, dphi = _pdet_args(p, dphi, min_length, kind)
+        self.kind, self.T = kind, np.complex64
+        hd = C.c_void_p()
+        _check(self._fn("create")(_ptr(p), p.size, _ptr(dphi), dphi.size, threshold, energy_floor, min_length,
+                                  C.byref(hd)))
+        self._h = hd
+
+    def clone(self):
+        new = object.__new__(type(self))
+        new.kind, new.T = self.kind, self.T
+        hd = C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._h = hd
+        return new
+
+    def _get(self, name, ctype):
+        v = ctype()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return v.value
+
+    length = property(lambda self: self._get("get_length", C.c_size_t))
+    hypotheses = property(lambda self: self._get("get_hypotheses", C.c_size_t))
+    threshold = property(lambda self: np.float32(self._get("get_threshold", C.c_float)))
+    energy_floor = property(lambda self: np.float32(self._get("get_energy_floor", C.c_float)))
+    min_length = property(lambda self: self._get("get_min_length", C.c_uint64))
+    preamble_energy = property(lambda self: np.float32(self._get("get_preamble_energy", C.c_float)))
+
+    @property
+    def dphi(self):
+        out = np.zeros(self.hypotheses, np.float32)
+        _check(self._fn("get_dphi")(self._h, _ptr(out)))
+        return out
+
+    def get_templates(self):
+        """the K x L templates the object correlates with"""
+        out = np.zeros((self.hypotheses, self.length), np.complex64)
+        _check(self._fn("get_templates")(self._h, _ptr(out)))
+        return out
+
+    @property
+    def position(self):
+        """samples seen since reset(); synchronises"""
+        return self._get("get_position", C.c_uint64)
+
+    @property
+    def pending(self):
+        """the run that reaches the last sample seen, as a PREAMBLE_EVENT record so far, or None; synchronises"""
+        has, ev = C.c_int(), np.zeros(1, PREAMBLE_EVENT)
+        _check(self._fn("get_pending")(self._h, C.byref(has), _ptr(ev)))
+        return ev[0] if has.value else None
+
+    def detect_block(self, x, cap=None):
+        """pushes x and returns (events, overflow): the PREAMBLE_EVENT records the block closes, at most cap of them
+        where cap is given (events.size is then min(count, cap); the count is the third item of the tuple in that case)"""
+        x = _arr(x, self.T)
+        room = (x.size + PDET_TILE - 1) // PDET_TILE + PDET_SEGMAX + 1 if cap is None else int(cap)
+        ev = np.zeros(room, PREAMBLE_EVENT)
+        count, over = C.c_size_t(), C.c_int()
+        _check(self._fn("detect_block")(self._h, _ptr(x), x.size, _ptr(ev), room, C.byref(count), C.byref(over)))
+        ev = ev[:min(count.value, room)].copy()
+        return (ev, bool(over.value)) if cap is None else (ev, bool(over.value), count.value)
+
+    def detect_block_devptr(self, x_dev, n, events_dev, cap, status_dev):
+        """x_dev: n samples; events_dev: room for cap PREAMBLE_EVENT records (None where cap is 0); status_dev: two
+        uint32 that receive (count, overflow).  min(count, cap) records are written.  The buffers must not overlap
+        (ConfigError); asynchronous on the object's stream, no host synchronisation"""
+        x_dev, events_dev, status_dev = (None if p is None else _devptr(p) for p in (x_dev, events_dev, status_dev))
+        _check(self._fn("detect_block_dev")(self._h, x_dev, n, events_dev, cap, status_dev))
+
+    def correlate_block(self, x, rxy=None):
+        """the bank's raw output: pushes x and returns (rxy, energy), rxy[k, i] = rxy_k and energy[i] after sample i.  The
+        sample counter advances; a pending run is dropped"""
+        x = _arr(x, self.T)
+        k = self.hypotheses
+        rxy = _out(rxy, k * x.size, self.T)
+        e = np.empty(x.size, np.float32)
+        _check(self._fn("correlate_block")(self._h, _ptr(x), x.size, _ptr(rxy), _ptr(e)))
+        return rxy.reshape(k, x.size), e
+
+    def correlate_block_devptr(self, x_dev, n, rxy_dev, energy_dev=None):
+        """x_dev: n samples; rxy_dev: K n samples, row k at k n; energy_dev: n float32 or None.  The buffers must not
+        overlap (ConfigError); asynchronous on the object's stream"""
+        x_dev, rxy_dev, energy_dev = (None if p is None else _devptr(p) for p in (x_dev, rxy_dev, energy_dev))
+        _check(self._fn("correlate_block_dev")(self._h, x_dev, n, rxy_dev, energy_dev))
+
+    def flush(self):
+        """closes the pending run: one event if it is long enough, else none; position is unchanged"""
+        ev, count = np.zeros(1, PREAMBLE_EVENT), C.c_size_t()
+        _check(self._fn("flush")(self._h, _ptr(ev), 1, C.byref(count)))
+        return ev[:count.value].copy()
+
+
+def preamble_detect_host(x, p, dphi, threshold, energy_floor=0.0, min_length=1, kind="cccf"):
+    """PreambleDetector's definition on the host alone, no device needed: one call on a stream from reset().  Returns
+    (events, overflow, pending), pending a PREAMBLE_EVENT record or None.  It is the library's own sequential form,
+    slow and meant for checks."""
+    p, dphi = _pdet_args(p, dphi, min_length, kind)
+    x = _arr(x, np.complex64)
+    room = (x.size + PDET_TILE - 1) // PDET_TILE + PDET_SEGMAX + 1
+    ev, pend = np.zeros(room, PREAMBLE_EVENT), np.zeros(1, PREAMBLE_EVENT)
+    count, over, has = C.c_size_t(), C.c_int(), C.c_int()
+    _check(lib.yagi_hip_pdet_cccf_detect_host(
+        _ptr(p), p.size, _ptr(dphi), dphi.size, threshold, energy_floor, min_length, _ptr(x), x.size, _ptr(ev), room,
+        C.byref(count), C.byref(over), C.byref(has), _ptr(pend)))
     return ev[:min(count.value, room)].copy(), bool(over.value), (pend[0] if has.value else None)
 
 

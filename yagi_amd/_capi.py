@@ -638,6 +638,31 @@ for _k in ("cccf", "rrrf"):
     _sig(_p + "flush", vp, vp, sz, C.POINTER(sz))
     _sig(_p + "detect_host", sz, sz, f32, f32, u64, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(ci), C.POINTER(ci), vp)
 
+# ---- PreambleDetector --------------------------------------------------------------------------
+_sig("yagi_hip_pdet_templates", vp, sz, vp, sz, vp)
+_p = "yagi_hip_pdet_cccf_"
+_sig(_p + "create", vp, sz, vp, sz, f32, f32, u64, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "get_length", vp, C.POINTER(sz))
+_sig(_p + "get_hypotheses", vp, C.POINTER(sz))
+_sig(_p + "get_threshold", vp, C.POINTER(f32))
+_sig(_p + "get_energy_floor", vp, C.POINTER(f32))
+_sig(_p + "get_min_length", vp, C.POINTER(u64))
+_sig(_p + "get_preamble_energy", vp, C.POINTER(f32))
+_sig(_p + "get_dphi", vp, vp)
+_sig(_p + "get_templates", vp, vp)
+_sig(_p + "get_position", vp, C.POINTER(u64))
+_sig(_p + "get_pending", vp, C.POINTER(ci), vp)
+_sig(_p + "detect_block", vp, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(ci))
+_sig(_p + "detect_block_dev", vp, vp, sz, vp, sz, vp)
+_sig(_p + "correlate_block", vp, vp, sz, vp, vp)
+_sig(_p + "correlate_block_dev", vp, vp, sz, vp, vp)
+_sig(_p + "flush", vp, vp, sz, C.POINTER(sz))
+_sig(_p + "detect_host", vp, sz, vp, sz, f32, f32, u64, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(ci), C.POINTER(ci), vp)
+
 # ---- SymStream ---------------------------------------------------------------------------------
 _p = "yagi_hip_symstreamcf_"
 _sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)

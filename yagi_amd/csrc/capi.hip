@@ -6420,6 +6420,344 @@ YAGI_BURSTDET_IMPL(rrrf, float)
 #undef YAGI_BURSTDET_IMPL
 #undef YAGI_BURSTDET_GET
 
+// ---- PreambleDetector (yagi_hip.h; absent from the reference) -------------------------------------------------------
+// The state is the history (the last L samples) plus a PdetState: the sample counter and the pending run.  Block calls
+// run pdet_kernels.hip on the device copy: the tile kernel writes the history the call leaves into the other of two
+// buffers, the stitch kernel updates the PdetState in place.  Getters, flush and clone work on a host mirror; the two
+// copies are synchronised lazily (Mirror).  The templates are built once on the host and never change.
+namespace yagi {
+
+struct PdetObj {
+    hipStream_t st = nullptr;
+    int L = 0, K = 0;
+    float threshold = 0.0f, thr2 = 0.0f, floor_ = 0.0f, ep = 0.0f;
+    uint64_t min_length = 1;
+    std::vector<float> dphi;                              // K
+    std::vector<cf32> tmpl;                               // [K][L]
+    DevBuf tmpl_dev;                                      // [K][pdet_pitch(L)]
+    FdHist<cf32> win;                                     // host mirror: the history
+    PdetState hs{};                                       //              counter and pending run
+    PingPong<> hist;                                      // device copy, L samples
+    DevBuf state;                                         //              one PdetState
+    DevBuf scratch;                                       // tile table and segment pool, grown with the block length
+    Staging ws;                                           // host block form: x; y holds {status, events} or rxy
+    DevBuf we;                                            // host correlate form: the energies on the device
+    Mirror mirror;
+
+    size_t bytes() const { return (size_t)L * sizeof(cf32); }
+    // everything that needs no device
+    int configure(const cf32 *p, size_t L_, const float *dphi_, size_t K_, float threshold_, float floor__,
+                  uint64_t min_length_) {
+        if (L_ == 0 || L_ > (size_t)YAGI_PDET_LMAX)
+            return fail(YAGI_ERR_CONFIG, "preamble length %zu is outside 1 .. YAGI_PDET_LMAX = %d", L_, YAGI_PDET_LMAX);
+        if (K_ == 0 || K_ > (size_t)YAGI_PDET_KMAX)
+            return fail(YAGI_ERR_CONFIG, "%zu hypotheses are outside 1 .. YAGI_PDET_KMAX = %d", K_, YAGI_PDET_KMAX);
+        if (!p || !dphi_) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        for (size_t k = 0; k < K_; ++k)
+            if (!std::isfinite(dphi_[k])) return fail(YAGI_ERR_CONFIG, "hypothesis %zu is not finite", k);
+        YG_TRY(burstdet_check(threshold_, floor__, min_length_));
+        const float e = pdet_preamble_energy(p, L_);
+        if (!std::isfinite(e) || !(e > 0.0f))
+            return fail(YAGI_ERR_CONFIG, "the preamble's energy must be finite and greater than zero");
+        L = (int)L_;
+        K = (int)K_;
+        threshold = threshold_;
+        thr2 = threshold_ * threshold_;
+        floor_ = floor__;
+        min_length = min_length_;
+        ep = e;
+        dphi.assign(dphi_, dphi_ + K_);
+        tmpl.resize(K_ * L_);
+        pdet_templates(p, L_, dphi_, K_, tmpl.data());
+        return YAGI_OK;
+    }
+    int copy_config(const PdetObj &o) {
+        L = o.L, K = o.K, threshold = o.threshold, thr2 = o.thr2, floor_ = o.floor_, ep = o.ep, min_length = o.min_length;
+        dphi = o.dphi;
+        tmpl = o.tmpl;
+        return YAGI_OK;
+    }
+    int alloc() {
+        YG_TRY(require_device());
+        const size_t pitch = pdet_pitch((size_t)L);
+        std::vector<cf32> rows((size_t)K * pitch, cf32{});
+        for (int k = 0; k < K; ++k) {
+            const cf32 *row = tmpl.data() + (size_t)k * (size_t)L;
+            std::copy(row, row + L, rows.begin() + (size_t)k * pitch);
+        }
+        YG_TRY(fill(tmpl_dev, rows.data(), rows.size() * sizeof(cf32), st));
+        YG_TRY(hist.alloc(bytes()));
+        YG_TRY(state.alloc(sizeof(PdetState)));
+        win.init((size_t)L);
+        return YAGI_OK;
+    }
+    int reset() {
+        win.zero();
+        hs = PdetState{};
+        YG_HIP(hipMemsetAsync(hist.cur(), 0, bytes(), st));
+        YG_HIP(hipMemsetAsync(state.p, 0, sizeof(PdetState), st));
+        mirror.in_sync();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] {
+            std::vector<cf32> t((size_t)L);
+            YG_TRY(download(t.data(), hist.cur(), bytes(), st));
+            win.load(t.data());
+            return download(&hs, state.p, sizeof(PdetState), st);
+        });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] {
+            YG_TRY(upload(hist.cur(), win.data(), bytes(), st));
+            return upload(state.p, &hs, sizeof(PdetState), st);
+        });
+    }
+    // events a call of nb samples can report: a run per segment, and the pending run of the call before
+    static size_t most_events(size_t nb) { return (nb + kPdetTile - 1) / kPdetTile + (size_t)kPdetSegmax + 1; }
+    int block_dev(const cf32 *x, size_t nb, yagi_preamble_event *events, size_t cap, unsigned *status) {
+        YG_TRY(ensure_dev());
+        YG_TRY(scratch.ensure(pdet_scratch_bytes(nb)));
+        YG_TRY(launch_pdet(L, K, tmpl_dev.as<cf32>(), ep, thr2, floor_, min_length, hist.cur<cf32>(), hist.next<cf32>(), x,
+                           nb, scratch.p, state.as<PdetState>(), events, cap, status, st));
+        if (nb != 0) hist.flip();
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+    int block(const cf32 *x, size_t nb, yagi_preamble_event *events, size_t cap, size_t *count, int *overflow) {
+        const size_t room = std::min(cap, most_events(nb));
+        YG_TRY(ws.put(st, x, nb));
+        YG_TRY(ws.y.ensure(16 + room * sizeof(yagi_preamble_event)));
+        unsigned *sd = ws.y.as<unsigned>();
+        yagi_preamble_event *ed = reinterpret_cast<yagi_preamble_event *>(ws.y.as<char>() + 16);
+        YG_TRY(block_dev(ws.x.as<cf32>(), nb, ed, room, sd));
+        unsigned status[2];
+        YG_TRY(download(status, sd, sizeof status, st));
+        *count = status[0];
+        *overflow = (int)status[1];
+        return download(events, ed, std::min((size_t)status[0], room) * sizeof(yagi_preamble_event), st);
+    }
+    int correlate_dev(const cf32 *x, size_t nb, cf32 *rxy, float *energy) {
+        if (nb == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        YG_TRY(launch_pdet_correlate(L, K, tmpl_dev.as<cf32>(), hist.cur<cf32>(), hist.next<cf32>(), x, nb, rxy, energy,
+                                     state.as<PdetState>(), st));
+        hist.flip();
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+    int flush(yagi_preamble_event *events, size_t cap, size_t *count) {
+        YG_TRY(ensure_host());
+        *count = 0;
+        if (!hs.has_pending) return YAGI_OK;
+        if (hs.pending.length >= min_length) {
+            if (cap > 0) events[0] = hs.pending;
+            *count = 1;
+        }
+        hs.has_pending = 0;
+        mirror.host_written();
+        return YAGI_OK;
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_pdet_cccf_s : PdetObj {};
+
+#define YAGI_PDET_GET(name, type, expr)                                                             \
+    int yagi_hip_pdet_cccf_get_##name(yagi_hip_pdet_cccf q, type *out) try {                        \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = (expr);                                                                              \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }
+
+extern "C" {
+
+int yagi_hip_pdet_templates(const cf32 *p, size_t L, const float *dphi, size_t K, cf32 *out) try {
+    if (L == 0 || L > (size_t)YAGI_PDET_LMAX || K == 0 || K > (size_t)YAGI_PDET_KMAX)
+        return fail(YAGI_ERR_CONFIG, "(length, hypotheses) = (%zu, %zu) out of range", L, K);
+    CHECK_PTR(p);
+    CHECK_PTR(dphi);
+    CHECK_PTR(out);
+    for (size_t k = 0; k < K; ++k)
+        if (!std::isfinite(dphi[k])) return fail(YAGI_ERR_CONFIG, "hypothesis %zu is not finite", k);
+    pdet_templates(p, L, dphi, K, out);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_create(const cf32 *p, size_t L, const float *dphi, size_t K, float threshold, float energy_floor,
+                              uint64_t min_length, yagi_hip_pdet_cccf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    auto o = std::make_unique<yagi_hip_pdet_cccf_s>();
+    YG_TRY(o->configure(p, L, dphi, K, threshold, energy_floor, min_length));
+    YG_TRY(o->alloc());
+    YG_TRY(o->reset());
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_destroy(yagi_hip_pdet_cccf q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_clone(yagi_hip_pdet_cccf q, yagi_hip_pdet_cccf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_pdet_cccf_s>();
+    o->st = q->st;
+    YG_TRY(o->copy_config(*q));
+    YG_TRY(o->alloc());
+    o->win.load(q->win.data());
+    o->hs = q->hs;
+    o->mirror.host_written();
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_set_stream(yagi_hip_pdet_cccf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_reset(yagi_hip_pdet_cccf q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+
+YAGI_PDET_GET(length, size_t, (size_t)q->L)
+YAGI_PDET_GET(hypotheses, size_t, (size_t)q->K)
+YAGI_PDET_GET(threshold, float, q->threshold)
+YAGI_PDET_GET(energy_floor, float, q->floor_)
+YAGI_PDET_GET(min_length, uint64_t, q->min_length)
+YAGI_PDET_GET(preamble_energy, float, q->ep)
+
+int yagi_hip_pdet_cccf_get_dphi(yagi_hip_pdet_cccf q, float *dphi) try {
+    CHECK_Q(q);
+    CHECK_PTR(dphi);
+    std::copy(q->dphi.begin(), q->dphi.end(), dphi);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_get_templates(yagi_hip_pdet_cccf q, cf32 *templates) try {
+    CHECK_Q(q);
+    CHECK_PTR(templates);
+    std::copy(q->tmpl.begin(), q->tmpl.end(), templates);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_get_position(yagi_hip_pdet_cccf q, uint64_t *position) try {
+    CHECK_Q(q);
+    CHECK_PTR(position);
+    YG_TRY(q->ensure_host());
+    *position = q->hs.position;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_get_pending(yagi_hip_pdet_cccf q, int *has_pending, yagi_preamble_event *ev) try {
+    CHECK_Q(q);
+    CHECK_PTR(has_pending);
+    CHECK_PTR(ev);
+    YG_TRY(q->ensure_host());
+    *has_pending = q->hs.has_pending != 0;
+    *ev = *has_pending ? q->hs.pending : yagi_preamble_event{};
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_detect_block(yagi_hip_pdet_cccf q, const cf32 *x, size_t n, yagi_preamble_event *events, size_t cap,
+                                    size_t *count, int *overflow) try {
+    CHECK_Q(q);
+    CHECK_PTR(count);
+    CHECK_PTR(overflow);
+    *count = 0;
+    *overflow = 0;
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    if (cap != 0) CHECK_PTR(events);
+    return q->block(x, n, events, cap, count, overflow);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_detect_block_dev(yagi_hip_pdet_cccf q, const cf32 *x_dev, size_t n, yagi_preamble_event *events_dev,
+                                        size_t cap, uint32_t *status_dev) try {
+    CHECK_Q(q);
+    CHECK_PTR(status_dev);
+    if (n != 0) CHECK_PTR(x_dev);
+    if (cap != 0) CHECK_PTR(events_dev);
+    if (n != 0) {
+        if (cap != 0) CHECK_NOALIAS(x_dev, n, events_dev, cap);
+        CHECK_NOALIAS(x_dev, n, status_dev, 2);
+    }
+    if (cap != 0) CHECK_NOALIAS(events_dev, cap, status_dev, 2);
+    return q->block_dev(x_dev, n, events_dev, cap, status_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_correlate_block(yagi_hip_pdet_cccf q, const cf32 *x, size_t n, cf32 *rxy, float *energy) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    CHECK_PTR(rxy);
+    const size_t kn = (size_t)q->K * n;
+    if (energy) YG_TRY(q->we.ensure(n * sizeof(float)));
+    float *ed = energy ? q->we.as<float>() : nullptr;
+    YG_TRY(q->ws.run(q->st, x, n, rxy, kn, [&](const cf32 *xd, cf32 *yd) { return q->correlate_dev(xd, n, yd, ed); }));
+    if (energy) YG_TRY(download(energy, ed, n * sizeof(float), q->st));
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_correlate_block_dev(yagi_hip_pdet_cccf q, const cf32 *x_dev, size_t n, cf32 *rxy_dev,
+                                           float *energy_dev) try {
+    CHECK_Q(q);
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x_dev);
+    CHECK_PTR(rxy_dev);
+    const size_t kn = (size_t)q->K * n;
+    CHECK_NOALIAS(x_dev, n, rxy_dev, kn);
+    if (energy_dev) {
+        CHECK_NOALIAS(x_dev, n, energy_dev, n);
+        CHECK_NOALIAS(rxy_dev, kn, energy_dev, n);
+    }
+    return q->correlate_dev(x_dev, n, rxy_dev, energy_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_flush(yagi_hip_pdet_cccf q, yagi_preamble_event *events, size_t cap, size_t *count) try {
+    CHECK_Q(q);
+    CHECK_PTR(count);
+    if (cap != 0) CHECK_PTR(events);
+    return q->flush(events, cap, count);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_pdet_cccf_detect_host(const cf32 *p, size_t L, const float *dphi, size_t K, float threshold,
+                                   float energy_floor, uint64_t min_length, const cf32 *x, size_t n,
+                                   yagi_preamble_event *events, size_t cap, size_t *count, int *overflow, int *has_pending,
+                                   yagi_preamble_event *pending) try {
+    CHECK_PTR(count);
+    CHECK_PTR(overflow);
+    CHECK_PTR(has_pending);
+    CHECK_PTR(pending);
+    if (n != 0) CHECK_PTR(x);
+    if (cap != 0) CHECK_PTR(events);
+    PdetObj o;
+    YG_TRY(o.configure(p, L, dphi, K, threshold, energy_floor, min_length));
+    std::vector<cf32> win(L, cf32{});
+    PdetState s{};
+    YG_TRY(pdet_host(o.L, o.K, o.tmpl.data(), o.ep, o.thr2, energy_floor, min_length, win.data(), &s, x, n, events, cap,
+                     count, overflow));
+    *has_pending = s.has_pending != 0;
+    *pending = s.has_pending ? s.pending : yagi_preamble_event{};
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+#undef YAGI_PDET_GET
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

@@ -555,6 +555,54 @@ template <class T>
 int burstdet_host(int W, int d, float thr2, float floor_, unsigned long long min_length, T *win, BurstState *state,
                   const T *x, size_t n, yagi_burst_event *events, size_t cap, size_t *count, int *overflow);
 
+// ---- pdet_kernels.hip ----------------------------------------------------------------------
+// PreambleDetector (yagi_hip.h) block calls on device buffers.  tmpl holds the K templates as rows of pdet_pitch(L)
+// elements (the taps behind L are never added; they are there so that a four-tap read stays inside the row).  hist =
+// the L samples before x[0], oldest first; hist_next receives the history the call leaves and must not alias hist.
+// launch_pdet: nb samples in, the events they close out; scratch holds pdet_scratch_bytes(nb): the tile table, then the
+// segment pool (BurstSeg, the hypothesis in its spare word); state's pool_used is zero between calls; events has room
+// for cap; status receives {count, overflow}.  launch_pdet_correlate: rxy[k nb + i] and energy[i] (or null) of sample i;
+// state's counter advances by nb and its pending run is dropped.
+constexpr int kPdetWg = 256;                           // threads per workgroup
+constexpr int kPdetTile = YAGI_PDET_TILE;              // outputs per workgroup
+constexpr int kPdetLmax = YAGI_PDET_LMAX;              // longest preamble the LDS tile is sized for
+constexpr int kPdetKmax = YAGI_PDET_KMAX;
+constexpr int kPdetSegmax = YAGI_PDET_SEGMAX;          // segments a call may hold beyond one per tile
+constexpr int kPdetR = kPdetTile / kPdetWg;            // consecutive outputs per lane
+constexpr size_t pdet_pitch(size_t L) { return (L + 3) / 4 * 4; }
+// LDS of the kernels: per staged sample (Tile + Lmax of them, in rows of R padded by 16 bytes) the sample, two floats,
+// and in rows of its own its energy term
+constexpr size_t pdet_lds_bytes() {
+    const size_t rows = (size_t)(kPdetTile + kPdetLmax) / kPdetR, r = (size_t)kPdetR;
+    return rows * (r * 8 + 16) + rows * (r * 4 + 16);
+}
+static_assert(pdet_lds_bytes() <= 64 * 1024, "the tile must fit a workgroup's LDS");
+struct PdetState {
+    unsigned long long position, pool_used;            // samples since reset(); segments the running call has taken
+    unsigned has_pending, pad;
+    yagi_preamble_event pending;                       // the run that ends on the last sample seen
+};
+static_assert(sizeof(PdetState) == 72 && sizeof(yagi_preamble_event) == 48, "device layouts");
+constexpr size_t pdet_scratch_bytes(size_t nb) {
+    const size_t tiles = (nb + kPdetTile - 1) / kPdetTile;
+    return tiles * 16 + (tiles + (size_t)kPdetSegmax) * sizeof(BurstSeg);
+}
+int launch_pdet(int L, int K, const cf32 *tmpl, float ep, float thr2, float floor_, unsigned long long min_length,
+                const cf32 *hist, cf32 *hist_next, const cf32 *x, size_t nb, void *scratch, PdetState *state,
+                yagi_preamble_event *events, size_t cap, unsigned *status, hipStream_t st);
+int launch_pdet_correlate(int L, int K, const cf32 *tmpl, const cf32 *hist, cf32 *hist_next, const cf32 *x, size_t nb,
+                          cf32 *rxy, float *energy, PdetState *state, hipStream_t st);
+// v_k[i] = conj(p[i]) e^{-j dphi_k i}, evaluated in f64 and rounded once per component: out[k L + i]
+void pdet_templates(const cf32 *p, size_t L, const float *dphi, size_t K, cf32 *out);
+// ep = the f32 sum over i, from +0.0, of fl(fl(p.re^2) + fl(p.im^2))
+float pdet_preamble_energy(const cf32 *p, size_t L);
+// rxy_k (k = 0 .. K-1) and the energy of the window h[0 .. L) against tmpl[k L + i]
+void pdet_host_sums(const cf32 *h, int L, int K, const cf32 *tmpl, cf32 *rxy, float *energy);
+// launch_pdet on the host, sample by sample: win = the last L samples (updated), tmpl = K rows of L, state as above
+int pdet_host(int L, int K, const cf32 *tmpl, float ep, float thr2, float floor_, unsigned long long min_length,
+              cf32 *win, PdetState *state, const cf32 *x, size_t n, yagi_preamble_event *events, size_t cap,
+              size_t *count, int *overflow);
+
 // ---- symstream_kernels.hip -----------------------------------------------------------------
 // SymStream (yagi_hip.h): samples [0, n) of a call that starts at buf_index p, from the carried window `win` (Ls values,
 // oldest first) and new symbols that come either from the caller's bytes (sym, flag = the result of
