@@ -1719,6 +1719,82 @@ int yagi_hip_pdet_cccf_detect_host(const yagi_cf32 *p, size_t L, const float *dp
                                    yagi_preamble_event *events, size_t cap, size_t *count, int *overflow,
                                    int *has_pending, yagi_preamble_event *pending);
 
+/* ---- SymSync: symbol timing recovery for a bank of channels (src/filter/symsync.rs) ---------------------------------
+ * SymSync(channels, k, npfb, h[h_len]): `channels` independent Symsync<Complex32> objects of one design (crcf only).
+ * A block is x[s x_pitch + c], step s < n, channel c < channels; per channel the call writes the outputs the reference's
+ * execute would write for that channel's samples, y[j y_pitch + c] for j < ny[c], bit for bit its sequential loop:
+ *     new (:37-110)        dh = central differences of h with the wrap at both ends, hdh_max by the `|| i == 0` rule,
+ *                          dh *= fl(0.06 / hdh_max); two FirPfbFilter::new(npfb, ., h_len) banks over one window, Ls =
+ *                          h_len div npfb taps per branch; then reset(), set_lf_bw(0.01), unlock()
+ *     step (:230-266)      push; while b < npfb { mf = row b . window; y = mf / Complex(k, 0) (num-complex's division);
+ *                          where decim_counter == k_out: decim_counter = 0 and, unless locked, dmf = derivative row b .
+ *                          window, q = clamp(Re(conj(mf) dmf), -1, 1), q_hat = the loop filter's execute_df2(q), rate +=
+ *                          rate_adjustment q_hat, del = rate + q_hat, tau_decim = tau; then decim_counter += 1, tau +=
+ *                          del, bf = tau npfb, b = round(bf) as usize }; tau -= 1, bf -= npfb, b -= npfb
+ * all in f32, every product, add and quotient rounded on its own; the sums run oldest first from +0.0 (the sum
+ * FirPfbFilter::execute forms).  reset() clears the matched filter's window and NOT the derivative filter's, as the
+ * reference does (:160-172).
+ * Capacity (absent from the reference, which panics where y is too short or a NaN reaches the loop): a channel writes at
+ * most ycap outputs per call.  An inner-loop iteration about to store output number ycap does not run: the channel is
+ * stalled (its first ycap outputs of that call are the sequential loop's).  A stalled channel ignores the rest of the
+ * call's input and all later input, writes nothing, reports ny = 0, keeps get_tau, and stays so until reset() or
+ * reset_channel(c).  A call returns YAGI_OK whether or not channels stalled.
+ * Deviation: where hdh_max is 0 or not finite, create returns YAGI_ERR_CONFIG (the reference would build NaN taps).
+ *   create(channels, k, npfb, h, h_len)   k >= 2, npfb >= 1, h_len >= 2, (h_len - 1) mod npfb = 0; limits below;
+ *                             anything else is YAGI_ERR_CONFIG, decided before any device is asked for
+ *   create_rnyquist(channels, ftype, k, m, beta, npfb)   (:112-131) the shapes yagi_hip_fir_design_prototype builds
+ *   create_kaiser(channels, k, m, beta, npfb)            (:133-158) fc = 0.75, 40 dB, taps x fl(2 fc)
+ *   rnyquist_taps / kaiser_taps   the prototypes those two design, 2 npfb k m + 1 taps; no device needed
+ *   destroy / clone / set_stream / reset / reset_channel(c)
+ *   lock / unlock / is_locked
+ *   set_output_rate(k_out)    sets rate and del at once, for every channel
+ *   set_lf_bw(bw)             (:196-213) in f32, the coefficients normalised by a0
+ *   get_channels / get_branch_length (Ls)
+ *   get_tau(tau[channels]) / get_stalled(stalled[channels])   they synchronise
+ *   execute(x, x_pitch, n, y, y_pitch, ycap, ny[channels], stalled[channels])   host slices, staged through the device
+ *   execute_dev(x_dev, x_pitch, n, y_dev, y_pitch, ycap, status_dev)   status_dev = uint32_t[2 channels]: ny, then
+ *                             stalled; asynchronous on the object's stream; n = 0 writes zeros for ny
+ *   execute_host(channels, k, npfb, h, h_len, k_out, bw, locked, x, x_pitch, n, y, y_pitch, ycap, ny, stalled, tau)
+ *                             the definition on the host alone, one call from reset(), no device needed; tau may be NULL
+ * Rows >= ny[c] of a channel are not touched.  The pitches are in samples and >= channels, so a sub-band c0 .. c0 + C of
+ * an analyzer's output runs in place with pointer + c0 and pitch M.  n and ycap are below 2^31.  x and y must not overlap.
+ * Not built: rrrf, per-channel designs or bandwidths, a per-channel lock mask, four lanes per
+ * channel, a time-parallel form for locked objects, sharding.
+ * Device form: symsync_kernels.hip: one lane per channel, one wave per workgroup. */
+#define YAGI_SYMSYNC_NPFB_MAX 128
+#define YAGI_SYMSYNC_LS_MAX 128
+#define YAGI_SYMSYNC_CHANNELS_MAX 1048576
+typedef struct yagi_hip_symsync_crcf_s *yagi_hip_symsync_crcf;
+int yagi_hip_symsync_crcf_create(size_t channels, size_t k, size_t npfb, const float *h, size_t h_len,
+                                 yagi_hip_symsync_crcf *q);
+int yagi_hip_symsync_crcf_create_rnyquist(size_t channels, int ftype, size_t k, size_t m, float beta, size_t npfb,
+                                          yagi_hip_symsync_crcf *q);
+int yagi_hip_symsync_crcf_create_kaiser(size_t channels, size_t k, size_t m, float beta, size_t npfb,
+                                        yagi_hip_symsync_crcf *q);
+int yagi_hip_symsync_crcf_rnyquist_taps(int ftype, size_t k, size_t m, float beta, size_t npfb, float *h);
+int yagi_hip_symsync_crcf_kaiser_taps(size_t k, size_t m, float beta, size_t npfb, float *h);
+int yagi_hip_symsync_crcf_destroy(yagi_hip_symsync_crcf q);
+int yagi_hip_symsync_crcf_clone(yagi_hip_symsync_crcf q, yagi_hip_symsync_crcf *out);
+int yagi_hip_symsync_crcf_set_stream(yagi_hip_symsync_crcf q, yagi_stream_t s);
+int yagi_hip_symsync_crcf_reset(yagi_hip_symsync_crcf q);
+int yagi_hip_symsync_crcf_reset_channel(yagi_hip_symsync_crcf q, size_t c);
+int yagi_hip_symsync_crcf_lock(yagi_hip_symsync_crcf q);
+int yagi_hip_symsync_crcf_unlock(yagi_hip_symsync_crcf q);
+int yagi_hip_symsync_crcf_is_locked(yagi_hip_symsync_crcf q, int *locked);
+int yagi_hip_symsync_crcf_set_output_rate(yagi_hip_symsync_crcf q, size_t k_out);
+int yagi_hip_symsync_crcf_set_lf_bw(yagi_hip_symsync_crcf q, float bw);
+int yagi_hip_symsync_crcf_get_channels(yagi_hip_symsync_crcf q, size_t *channels);
+int yagi_hip_symsync_crcf_get_branch_length(yagi_hip_symsync_crcf q, size_t *Ls);
+int yagi_hip_symsync_crcf_get_tau(yagi_hip_symsync_crcf q, float *tau);
+int yagi_hip_symsync_crcf_get_stalled(yagi_hip_symsync_crcf q, uint32_t *stalled);
+int yagi_hip_symsync_crcf_execute(yagi_hip_symsync_crcf q, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
+                                  size_t y_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled);
+int yagi_hip_symsync_crcf_execute_dev(yagi_hip_symsync_crcf q, const yagi_cf32 *x_dev, size_t x_pitch, size_t n,
+                                      yagi_cf32 *y_dev, size_t y_pitch, size_t ycap, uint32_t *status_dev);
+int yagi_hip_symsync_crcf_execute_host(size_t channels, size_t k, size_t npfb, const float *h, size_t h_len, size_t k_out,
+                                       float bw, int locked, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
+                                       size_t y_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled, float *tau);
+
 /* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */
 

@@ -19,6 +19,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     Autocorr                   (absent from the reference: src/filter/autocorr.rs is empty)
     BurstDetector              (absent from the reference: Autocorr, threshold and run / peak extraction fused)
     PreambleDetector           (absent from the reference: a bank of known-preamble correlators, threshold and events)
+    SymSync                    src/filter/symsync.rs:37-276, one object per channel of a bank
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -37,7 +38,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "SpgramPlan", "plan_spgram", "MsResamp2Plan", "Resamp2Plan", "plan_msresamp2", "plan_resamp2", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
@@ -2114,6 +2115,173 @@ def preamble_detect_host(x, p, dphi, threshold, energy_floor=0.0, min_length=1, 
         _ptr(p), p.size, _ptr(dphi), dphi.size, threshold, energy_floor, min_length, _ptr(x), x.size, _ptr(ev), room,
         C.byref(count), C.byref(over), C.byref(has), _ptr(pend)))
     return ev[:min(count.value, room)].copy(), bool(over.value), (pend[0] if has.value else None)
+
+
+SYMSYNC_NPFB_MAX = 128             # YAGI_SYMSYNC_NPFB_MAX: the most branches of SymSync's two banks
+SYMSYNC_LS_MAX = 128               # YAGI_SYMSYNC_LS_MAX: the most taps per branch (h_len div npfb)
+SYMSYNC_CHANNELS_MAX = 1 << 20     # YAGI_SYMSYNC_CHANNELS_MAX
+
+
+def _symsync_size(v, what):
+    if not (isinstance(v, (int, np.integer)) and 0 <= v < 2 ** 63):
+        raise ConfigError(f"{what} must be a non-negative integer")
+    return int(v)
+
+
+class SymSync(_Handle):
+    """SymSync(channels, k, npfb, h): `channels` independent filter::symsync::Symsync<Complex32> objects of one design
+    (src/filter/symsync.rs), Complex<f32> only.  execute takes a block x[n, channels] (step, channel) and returns, per
+    channel, the outputs the reference's execute would write for that channel's samples, bit for bit its sequential loop:
+    a polyphase matched filter and derivative matched filter over one window, the timing error Re(conj(mf) dmf), the
+    second-order loop filter and the fractional index tau that picks the branch of the next output (yagi_hip.h).  reset()
+    clears the matched filter's window and not the derivative filter's, as the reference does.
+    Capacity: a channel writes at most ycap outputs per call; a channel that would write more (or that a NaN reached)
+    is stalled: it ignores all further input and reports ny = 0 until reset() or reset_channel(c).
+    The block calls run symsync_kernels.hip, one lane per channel.  npfb <= SYMSYNC_NPFB_MAX, h.size div npfb <=
+    SYMSYNC_LS_MAX, channels <= SYMSYNC_CHANNELS_MAX."""
+    _prefix = "yagi_hip_symsync_crcf_"
+
+    def __init__(self, channels, k, npfb, h, kind="crcf"):
+        if kind != "crcf":
+            raise ConfigError(f"unknown type combination {kind!r}")
+        channels, k, npfb = (_symsync_size(v, w) for v, w in ((channels, "channels"), (k, "k"), (npfb, "npfb")))
+        h = _arr(h, np.float32)
+        if h.ndim != 1:
+            raise ConfigError("the taps are one-dimensional")
+        hd = C.c_void_p()
+        _check(self._fn("create")(channels, k, npfb, _ptr(h), h.size, C.byref(hd)))
+        self._set(hd, channels, k)
+
+    def _set(self, hd, channels, k):
+        self._h, self.kind, self.T, self.channels, self.k, self.k_out = hd, "crcf", np.complex64, channels, k, 1
+
+    @classmethod
+    def rnyquist(cls, channels, ftype, k, m, beta, npfb):
+        """Symsync::new_rnyquist (:112-131)"""
+        channels, k, m, npfb = (_symsync_size(v, "argument") for v in (channels, k, m, npfb))
+        new, hd = object.__new__(cls), C.c_void_p()
+        _check(new._fn("create_rnyquist")(channels, int(ftype), k, m, beta, npfb, C.byref(hd)))
+        new._set(hd, channels, k)
+        return new
+
+    @classmethod
+    def kaiser(cls, channels, k, m, beta, npfb):
+        """Symsync::new_kaiser (:133-158)"""
+        channels, k, m, npfb = (_symsync_size(v, "argument") for v in (channels, k, m, npfb))
+        new, hd = object.__new__(cls), C.c_void_p()
+        _check(new._fn("create_kaiser")(channels, k, m, beta, npfb, C.byref(hd)))
+        new._set(hd, channels, k)
+        return new
+
+    @staticmethod
+    def rnyquist_taps(ftype, k, m, beta, npfb):
+        """the prototype rnyquist designs: 2 npfb k m + 1 taps, no device needed"""
+        k, m, npfb = (_symsync_size(v, "argument") for v in (k, m, npfb))
+        h = np.zeros(2 * npfb * k * m + 1, np.float32)
+        _check(lib.yagi_hip_symsync_crcf_rnyquist_taps(int(ftype), k, m, beta, npfb, _ptr(h)))
+        return h
+
+    @staticmethod
+    def kaiser_taps(k, m, beta, npfb):
+        """the prototype kaiser designs: 2 npfb k m + 1 taps, no device needed"""
+        k, m, npfb = (_symsync_size(v, "argument") for v in (k, m, npfb))
+        h = np.zeros(2 * npfb * k * m + 1, np.float32)
+        _check(lib.yagi_hip_symsync_crcf_kaiser_taps(k, m, beta, npfb, _ptr(h)))
+        return h
+
+    def clone(self):
+        new, hd = object.__new__(type(self)), C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._set(hd, self.channels, self.k)
+        new.k_out = self.k_out
+        return new
+
+    def reset_channel(self, c):
+        _check(self._fn("reset_channel")(self._h, _symsync_size(c, "channel")))
+
+    def lock(self):
+        _check(self._fn("lock")(self._h))
+
+    def unlock(self):
+        _check(self._fn("unlock")(self._h))
+
+    def is_locked(self):
+        v = C.c_int()
+        _check(self._fn("is_locked")(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def set_output_rate(self, k_out):
+        """sets rate and del at once, for every channel"""
+        _check(self._fn("set_output_rate")(self._h, _symsync_size(k_out, "k_out")))
+        self.k_out = int(k_out)
+
+    def set_lf_bw(self, bw):
+        _check(self._fn("set_lf_bw")(self._h, bw))
+
+    @property
+    def branch_length(self):
+        v = C.c_size_t()
+        _check(self._fn("get_branch_length")(self._h, C.byref(v)))
+        return v.value
+
+    def get_tau(self):
+        """tau_decim of every channel; synchronises"""
+        out = np.zeros(self.channels, np.float32)
+        _check(self._fn("get_tau")(self._h, _ptr(out)))
+        return out
+
+    def get_stalled(self):
+        """the stalled word of every channel; synchronises"""
+        out = np.zeros(self.channels, np.uint32)
+        _check(self._fn("get_stalled")(self._h, _ptr(out)))
+        return out
+
+    def default_ycap(self, n):
+        """2 ceil(n k_out / k) + 8: a default, not a bound (a loop far from lock can write more)"""
+        return 2 * -(-int(n) * self.k_out // self.k) + 8
+
+    def execute(self, x, ycap=None):
+        """x[n, channels] -> (y[ycap, channels], ny[channels], stalled[channels]); y[j, c] is an output for j < ny[c]
+        and zero below.  ycap defaults to default_ycap(n)"""
+        x = _arr(x, self.T)
+        if x.ndim != 2 or x.shape[1] != self.channels:
+            raise ConfigError(f"the block is [steps, {self.channels}]")
+        n = x.shape[0]
+        ycap = self.default_ycap(n) if ycap is None else _symsync_size(ycap, "ycap")
+        y = np.zeros((ycap, self.channels), self.T)
+        ny, st = np.zeros(self.channels, np.uint32), np.zeros(self.channels, np.uint32)
+        _check(self._fn("execute")(self._h, _ptr(x), self.channels, n, _ptr(y), self.channels, ycap, _ptr(ny), _ptr(st)))
+        return y, ny, st
+
+    def execute_devptr(self, x_dev, x_pitch, n, y_dev, y_pitch, ycap, status_dev):
+        """x_dev: n rows of pitch x_pitch samples; y_dev: ycap rows of pitch y_pitch; status_dev: 2 channels uint32 that
+        receive ny, then stalled.  Rows >= ny[c] of a channel are not touched.  Asynchronous on the object's stream (the
+        C ABI's execute_dev; named as Ddc.execute_block_devptr is)"""
+        x_dev, y_dev, status_dev = (None if p is None else _devptr(p) for p in (x_dev, y_dev, status_dev))
+        _check(self._fn("execute_dev")(self._h, x_dev, x_pitch, n, y_dev, y_pitch, ycap, status_dev))
+
+    @staticmethod
+    def execute_host(channels, k, npfb, h, x, ycap=None, k_out=1, bw=0.01, locked=False, x_pitch=None, y_pitch=None):
+        """the definition on the host alone, no device needed: one call from reset().  x is [n, x_pitch] (x_pitch
+        defaults to channels); returns (y[ycap, y_pitch], ny, stalled, tau).  The library's own sequential form, slow and
+        meant for checks"""
+        channels, k, npfb, k_out = (_symsync_size(v, "argument") for v in (channels, k, npfb, k_out))
+        if not 1 <= channels <= SYMSYNC_CHANNELS_MAX:
+            raise ConfigError("channels must be in 1 .. SYMSYNC_CHANNELS_MAX")
+        h = _arr(h, np.float32)
+        x_pitch = channels if x_pitch is None else _symsync_size(x_pitch, "x_pitch")
+        y_pitch = channels if y_pitch is None else _symsync_size(y_pitch, "y_pitch")
+        x = _arr(x, np.complex64)
+        if h.ndim != 1 or x.ndim != 2 or x.shape[1] != x_pitch:
+            raise ConfigError("the taps are one-dimensional and the block is [steps, x_pitch]")
+        n = x.shape[0]
+        ycap = 2 * -(-n * k_out // max(k, 1)) + 8 if ycap is None else _symsync_size(ycap, "ycap")
+        y = np.zeros((ycap, y_pitch), np.complex64)
+        ny, st, tau = np.zeros(channels, np.uint32), np.zeros(channels, np.uint32), np.zeros(channels, np.float32)
+        _check(lib.yagi_hip_symsync_crcf_execute_host(channels, k, npfb, _ptr(h), h.size, k_out, bw, int(bool(locked)),
+                                                      _ptr(x), x_pitch, n, _ptr(y), y_pitch, ycap, _ptr(ny), _ptr(st),
+                                                      _ptr(tau)))
+        return y, ny, st, tau
 
 
 MSEQUENCE_TILE = 8192    # YAGI_MSEQUENCE_TILE: symbols per workgroup of the generator kernel

@@ -663,6 +663,31 @@ _sig(_p + "correlate_block_dev", vp, vp, sz, vp, vp)
 _sig(_p + "flush", vp, vp, sz, C.POINTER(sz))
 _sig(_p + "detect_host", vp, sz, vp, sz, f32, f32, u64, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(ci), C.POINTER(ci), vp)
 
+# ---- SymSync -----------------------------------------------------------------------------------
+_p = "yagi_hip_symsync_crcf_"
+_sig(_p + "create", sz, sz, sz, vp, sz, pvp)
+_sig(_p + "create_rnyquist", sz, ci, sz, sz, f32, sz, pvp)
+_sig(_p + "create_kaiser", sz, sz, sz, f32, sz, pvp)
+_sig(_p + "rnyquist_taps", ci, sz, sz, f32, sz, vp)
+_sig(_p + "kaiser_taps", sz, sz, f32, sz, vp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "reset_channel", vp, sz)
+_sig(_p + "lock", vp)
+_sig(_p + "unlock", vp)
+_sig(_p + "is_locked", vp, C.POINTER(ci))
+_sig(_p + "set_output_rate", vp, sz)
+_sig(_p + "set_lf_bw", vp, f32)
+_sig(_p + "get_channels", vp, C.POINTER(sz))
+_sig(_p + "get_branch_length", vp, C.POINTER(sz))
+_sig(_p + "get_tau", vp, vp)
+_sig(_p + "get_stalled", vp, vp)
+_sig(_p + "execute", vp, vp, sz, sz, vp, sz, sz, vp, vp)
+_sig(_p + "execute_dev", vp, vp, sz, sz, vp, sz, sz, vp)
+_sig(_p + "execute_host", sz, sz, sz, vp, sz, sz, f32, ci, vp, sz, sz, vp, sz, sz, vp, vp, vp)
+
 # ---- SymStream ---------------------------------------------------------------------------------
 _p = "yagi_hip_symstreamcf_"
 _sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)

@@ -6758,6 +6758,346 @@ int yagi_hip_pdet_cccf_detect_host(const cf32 *p, size_t L, const float *dphi, s
 }  // extern "C"
 #undef YAGI_PDET_GET
 
+// ---- SymSync (src/filter/symsync.rs, one object per channel) --------------------------------------------------------
+// The state is the [Ls][channels] history plus one SymsyncChan per channel; symsync_kernels.hip updates both in place on
+// the device.  Setters that touch per-channel state (set_output_rate, reset_channel), the getters and clone work on a
+// host mirror; the two copies are synchronised lazily (Mirror).  The loop filter, the lock flag and k_out travel to the
+// kernel by value with every call.
+namespace yagi {
+
+struct SymsyncObj {
+    hipStream_t st = nullptr;
+    size_t C = 0, k = 0, npfb = 0, Ls = 0, k_out = 1;
+    SymsyncLoop p{};
+    std::vector<float> taps;                              // [npfb][Ls] entries (H, D)
+    DevBuf taps_dev, state_dev, hist_dev;
+    std::vector<SymsyncChan> hs;                          // host mirror
+    std::vector<cf32> hh;
+    Mirror mirror;
+    Staging ws;                                           // host block form: x as given; y compact [ycap][C]
+    DevBuf wstatus;
+
+    // everything that needs no device
+    int configure(size_t channels, size_t k_, size_t npfb_, const float *h, size_t h_len) {
+        if (channels == 0 || channels > (size_t)YAGI_SYMSYNC_CHANNELS_MAX)
+            return fail(YAGI_ERR_CONFIG, "symsync: %zu channels are outside 1 .. YAGI_SYMSYNC_CHANNELS_MAX", channels);
+        YG_TRY(symsync_design(k_, npfb_, h, h_len, taps, &Ls));
+        C = channels, k = k_, npfb = npfb_, k_out = 1;
+        p = SymsyncLoop{};
+        p.kf = (float)k;
+        p.knorm = p.kf * p.kf + 0.0f * 0.0f;
+        p.npfbf = (float)npfb;
+        p.npfb = (unsigned)npfb, p.Ls = (unsigned)Ls, p.locked = 0, p.k_out = 1;
+        YG_TRY(symsync_set_bw(0.01f, &p));
+        hs.assign(C, SymsyncChan{});
+        hh.assign(Ls * C, cf32{});
+        for (auto &s : hs) symsync_reset_chan(&s, k, k_out);
+        return YAGI_OK;
+    }
+    int alloc() {
+        YG_TRY(require_device());
+        YG_TRY(fill(taps_dev, taps.data(), taps.size() * sizeof(float), st));
+        YG_TRY(state_dev.alloc(C * sizeof(SymsyncChan)));
+        YG_TRY(hist_dev.alloc(Ls * C * sizeof(cf32)));
+        YG_TRY(wstatus.alloc(2 * C * sizeof(unsigned)));
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] {
+            YG_TRY(download(hs.data(), state_dev.p, C * sizeof(SymsyncChan), st));
+            return download(hh.data(), hist_dev.p, Ls * C * sizeof(cf32), st);
+        });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] {
+            YG_TRY(upload(state_dev.p, hs.data(), C * sizeof(SymsyncChan), st));
+            return upload(hist_dev.p, hh.data(), Ls * C * sizeof(cf32), st);
+        });
+    }
+    int set_output_rate(size_t k_out_) {
+        if (k_out_ == 0) return fail(YAGI_ERR_CONFIG, "output rate must be greater than 0");
+        YG_TRY(ensure_host());
+        k_out = k_out_;
+        p.k_out = k_out_;
+        for (auto &s : hs) {
+            s.rate = (float)k / (float)k_out;
+            s.del = s.rate;
+        }
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int reset_channel(size_t c) {
+        if (c >= C) return fail(YAGI_ERR_CONFIG, "symsync: channel %zu of %zu", c, C);
+        YG_TRY(ensure_host());
+        symsync_reset_chan(&hs[c], k, k_out);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int reset() {
+        YG_TRY(ensure_host());
+        for (auto &s : hs) symsync_reset_chan(&s, k, k_out);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    static int check_block(size_t C, size_t x_pitch, size_t n, size_t y_pitch, size_t ycap) {
+        if (n >= ((size_t)1 << 31) || ycap >= ((size_t)1 << 31))
+            return fail(YAGI_ERR_CONFIG, "symsync: n and ycap must be below 2^31");
+        if (x_pitch < C || y_pitch < C || x_pitch >= ((size_t)1 << 31) || y_pitch >= ((size_t)1 << 31))
+            return fail(YAGI_ERR_CONFIG, "symsync: the pitches are in samples, at least the channel count and below 2^31");
+        return YAGI_OK;
+    }
+    int block_dev(const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, size_t ycap, unsigned *status) {
+        YG_TRY(ensure_dev());
+        YG_TRY(launch_symsync(p, taps_dev.as<float>(), state_dev.as<SymsyncChan>(), hist_dev.as<cf32>(), C, x, x_pitch, n,
+                              y, y_pitch, ycap, status, st));
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_symsync_crcf_s : SymsyncObj {};
+
+namespace {
+
+int symsync_make(yagi_hip_symsync_crcf *q, size_t channels, size_t k, size_t npfb, const float *h, size_t h_len) {
+    *q = nullptr;
+    auto o = std::make_unique<yagi_hip_symsync_crcf_s>();
+    YG_TRY(o->configure(channels, k, npfb, h, h_len));
+    YG_TRY(o->alloc());
+    *q = o.release();
+    return YAGI_OK;
+}
+
+// create_rnyquist (:112-131) and create_kaiser (:133-158): the prototype
+int symsync_rnyquist_taps(int ftype, size_t k, size_t m, float beta, size_t npfb, std::vector<float> &h) {
+    if (k < 2) return fail(YAGI_ERR_CONFIG, "samples/symbol must be at least 2");
+    if (m == 0) return fail(YAGI_ERR_CONFIG, "filter delay must be greater than 0");
+    if (!(beta >= 0.0f && beta <= 1.0f)) return fail(YAGI_ERR_CONFIG, "excess bandwidth factor must be in [0,1]");
+    if (npfb == 0) return fail(YAGI_ERR_CONFIG, "number of filters must be greater than 0");
+    if (npfb > (size_t)YAGI_SYMSYNC_NPFB_MAX || 2 * k * m > (size_t)YAGI_SYMSYNC_LS_MAX)
+        return fail(YAGI_ERR_CONFIG, "symsync: (npfb, 2 k m) = (%zu, %zu) out of range", npfb, 2 * k * m);
+    return design_prototype(ftype, k * npfb, m, beta, 0.0f, h);
+}
+int symsync_kaiser_taps(size_t k, size_t m, float beta, size_t npfb, std::vector<float> &h) {
+    if (k < 2) return fail(YAGI_ERR_CONFIG, "samples/symbol must be at least 2");
+    if (m == 0) return fail(YAGI_ERR_CONFIG, "filter delay must be greater than 0");
+    if (!(beta > 0.0f && beta <= 1.0f)) return fail(YAGI_ERR_CONFIG, "excess bandwidth factor must be in [0,1]");
+    if (npfb == 0) return fail(YAGI_ERR_CONFIG, "number of filters must be greater than 0");
+    if (npfb > (size_t)YAGI_SYMSYNC_NPFB_MAX || 2 * k * m > (size_t)YAGI_SYMSYNC_LS_MAX)
+        return fail(YAGI_ERR_CONFIG, "symsync: (npfb, 2 k m) = (%zu, %zu) out of range", npfb, 2 * k * m);
+    const float fc = 0.75f;
+    YG_TRY(design_kaiser(2 * npfb * k * m + 1, fc / ((float)k * (float)npfb), 40.0f, 0.0f, h));
+    for (float &c : h) c *= 2.0f * fc;
+    return YAGI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int yagi_hip_symsync_crcf_create(size_t channels, size_t k, size_t npfb, const float *h, size_t h_len,
+                                 yagi_hip_symsync_crcf *q) try {
+    CHECK_PTR(q);
+    return symsync_make(q, channels, k, npfb, h, h_len);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_create_rnyquist(size_t channels, int ftype, size_t k, size_t m, float beta, size_t npfb,
+                                          yagi_hip_symsync_crcf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    std::vector<float> h;
+    YG_TRY(symsync_rnyquist_taps(ftype, k, m, beta, npfb, h));
+    return symsync_make(q, channels, k, npfb, h.data(), h.size());
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_create_kaiser(size_t channels, size_t k, size_t m, float beta, size_t npfb,
+                                        yagi_hip_symsync_crcf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    std::vector<float> h;
+    YG_TRY(symsync_kaiser_taps(k, m, beta, npfb, h));
+    return symsync_make(q, channels, k, npfb, h.data(), h.size());
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_rnyquist_taps(int ftype, size_t k, size_t m, float beta, size_t npfb, float *h) try {
+    CHECK_PTR(h);
+    std::vector<float> v;
+    YG_TRY(symsync_rnyquist_taps(ftype, k, m, beta, npfb, v));
+    std::copy(v.begin(), v.end(), h);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_kaiser_taps(size_t k, size_t m, float beta, size_t npfb, float *h) try {
+    CHECK_PTR(h);
+    std::vector<float> v;
+    YG_TRY(symsync_kaiser_taps(k, m, beta, npfb, v));
+    std::copy(v.begin(), v.end(), h);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_destroy(yagi_hip_symsync_crcf q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_clone(yagi_hip_symsync_crcf q, yagi_hip_symsync_crcf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_symsync_crcf_s>();
+    o->st = q->st;
+    o->C = q->C, o->k = q->k, o->npfb = q->npfb, o->Ls = q->Ls, o->k_out = q->k_out, o->p = q->p;
+    o->taps = q->taps, o->hs = q->hs, o->hh = q->hh;
+    YG_TRY(o->alloc());
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_set_stream(yagi_hip_symsync_crcf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_reset(yagi_hip_symsync_crcf q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_reset_channel(yagi_hip_symsync_crcf q, size_t c) try {
+    CHECK_Q(q);
+    return q->reset_channel(c);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_lock(yagi_hip_symsync_crcf q) try {
+    CHECK_Q(q);
+    q->p.locked = 1;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_unlock(yagi_hip_symsync_crcf q) try {
+    CHECK_Q(q);
+    q->p.locked = 0;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_is_locked(yagi_hip_symsync_crcf q, int *locked) try {
+    CHECK_Q(q);
+    CHECK_PTR(locked);
+    *locked = q->p.locked != 0;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_set_output_rate(yagi_hip_symsync_crcf q, size_t k_out) try {
+    CHECK_Q(q);
+    return q->set_output_rate(k_out);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_set_lf_bw(yagi_hip_symsync_crcf q, float bw) try {
+    CHECK_Q(q);
+    return symsync_set_bw(bw, &q->p);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_get_channels(yagi_hip_symsync_crcf q, size_t *channels) try {
+    CHECK_Q(q);
+    CHECK_PTR(channels);
+    *channels = q->C;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_get_branch_length(yagi_hip_symsync_crcf q, size_t *Ls) try {
+    CHECK_Q(q);
+    CHECK_PTR(Ls);
+    *Ls = q->Ls;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_get_tau(yagi_hip_symsync_crcf q, float *tau) try {
+    CHECK_Q(q);
+    CHECK_PTR(tau);
+    YG_TRY(q->ensure_host());
+    for (size_t c = 0; c < q->C; ++c) tau[c] = q->hs[c].tau_decim;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_get_stalled(yagi_hip_symsync_crcf q, uint32_t *stalled) try {
+    CHECK_Q(q);
+    CHECK_PTR(stalled);
+    YG_TRY(q->ensure_host());
+    for (size_t c = 0; c < q->C; ++c) stalled[c] = q->hs[c].stalled;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_execute_dev(yagi_hip_symsync_crcf q, const cf32 *x_dev, size_t x_pitch, size_t n, cf32 *y_dev,
+                                      size_t y_pitch, size_t ycap, uint32_t *status_dev) try {
+    CHECK_Q(q);
+    CHECK_PTR(status_dev);
+    YG_TRY(SymsyncObj::check_block(q->C, x_pitch, n, y_pitch, ycap));
+    if (n != 0) CHECK_PTR(x_dev);
+    if (ycap != 0) CHECK_PTR(y_dev);
+    return q->block_dev(x_dev, x_pitch, n, y_dev, y_pitch, ycap, status_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_execute(yagi_hip_symsync_crcf q, const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch,
+                                  size_t ycap, uint32_t *ny, uint32_t *stalled) try {
+    CHECK_Q(q);
+    CHECK_PTR(ny);
+    CHECK_PTR(stalled);
+    const size_t C = q->C;
+    YG_TRY(SymsyncObj::check_block(C, x_pitch, n, y_pitch, ycap));
+    if (n != 0) CHECK_PTR(x);
+    if (ycap != 0) CHECK_PTR(y);
+    const size_t nx = n ? (n - 1) * x_pitch + C : 0;
+    YG_TRY(q->ws.put(q->st, x, nx));
+    YG_TRY(q->ws.y.ensure(ycap * C * sizeof(cf32)));
+    YG_TRY(q->block_dev(q->ws.x.as<cf32>(), x_pitch, n, q->ws.y.as<cf32>(), C, ycap, q->wstatus.as<unsigned>()));
+    std::vector<unsigned> status(2 * C);
+    YG_TRY(download(status.data(), q->wstatus.p, 2 * C * sizeof(unsigned), q->st));
+    size_t rows = 0;
+    for (size_t c = 0; c < C; ++c) {
+        ny[c] = status[c];
+        stalled[c] = status[C + c];
+        rows = std::max(rows, (size_t)status[c]);
+    }
+    std::vector<cf32> t(rows * C);
+    YG_TRY(download(t.data(), q->ws.y.p, rows * C * sizeof(cf32), q->st));
+    for (size_t j = 0; j < rows; ++j)
+        for (size_t c = 0; c < C; ++c)
+            if (j < ny[c]) y[j * y_pitch + c] = t[j * C + c];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symsync_crcf_execute_host(size_t channels, size_t k, size_t npfb, const float *h, size_t h_len, size_t k_out,
+                                       float bw, int locked, const cf32 *x, size_t x_pitch, size_t n, cf32 *y,
+                                       size_t y_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled, float *tau) try {
+    CHECK_PTR(ny);
+    CHECK_PTR(stalled);
+    SymsyncObj o;
+    YG_TRY(o.configure(channels, k, npfb, h, h_len));
+    if (k_out == 0) return fail(YAGI_ERR_CONFIG, "output rate must be greater than 0");
+    o.k_out = k_out;
+    o.p.k_out = k_out;
+    for (auto &s : o.hs) symsync_reset_chan(&s, k, k_out);
+    YG_TRY(symsync_set_bw(bw, &o.p));
+    o.p.locked = locked != 0;
+    YG_TRY(SymsyncObj::check_block(channels, x_pitch, n, y_pitch, ycap));
+    if (n != 0) CHECK_PTR(x);
+    if (ycap != 0) CHECK_PTR(y);
+    symsync_host(o.p, o.taps.data(), o.hs.data(), o.hh.data(), channels, x, x_pitch, n, y, y_pitch, ycap, ny, stalled);
+    if (tau)
+        for (size_t c = 0; c < channels; ++c) tau[c] = o.hs[c].tau_decim;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

@@ -603,6 +603,41 @@ int pdet_host(int L, int K, const cf32 *tmpl, float ep, float thr2, float floor_
               cf32 *win, PdetState *state, const cf32 *x, size_t n, yagi_preamble_event *events, size_t cap,
               size_t *count, int *overflow);
 
+// ---- symsync_kernels.hip -------------------------------------------------------------------
+// SymSync (yagi_hip.h): C independent Symsync<Complex32> loops of one design, one lane per channel.  taps holds both
+// banks interleaved: entry [b Ls + j] = (H[b][j], D[b][j]), rows against the window oldest first.  hist is the last Ls
+// rows of input, [Ls][C], oldest first; state one SymsyncChan per channel.  Both are updated in place (a workgroup
+// touches its own channels only).  status receives ny[C], then stalled[C].
+constexpr int kSymsyncWg = 64;                         // channels per workgroup: one wave
+constexpr int kSymsyncAhead = 16;                      // input rows per chunk: requested one chunk ahead, staged in LDS
+constexpr size_t kSymsyncLdsMax = 160 * 1024;          // ring, tap table and stage where all fit; else the table stays global
+struct SymsyncChan {
+    float tau, tau_decim, bf, rate, del, q, q_hat, v0, v1, v2;
+    unsigned since, stalled;                           // samples since reset (saturates at Ls): the matched filter reads
+    unsigned long long b, decim;                       // +0.0 for older slots; b and decim_counter in 64 bits, as usize
+};
+static_assert(sizeof(SymsyncChan) == 64, "device layout");
+struct SymsyncLoop {
+    float b0, b1, b2, a1, a2, rate_adj;                // the loop filter, normalised by a0, and rate_adjustment
+    float kf, knorm, npfbf;                            // k as f32, fl(fl(kf kf) + fl(0 0)), npfb as f32
+    unsigned npfb, Ls, locked;
+    unsigned long long k_out;
+};
+constexpr size_t symsync_ring_bytes(size_t Ls) { return Ls * kSymsyncWg * sizeof(cf32); }
+constexpr size_t symsync_table_bytes(size_t npfb, size_t Ls) { return npfb * Ls * 2 * sizeof(float); }
+constexpr size_t symsync_stage_bytes() { return (size_t)kSymsyncAhead * kSymsyncWg * sizeof(cf32); }
+// symsync.rs:37-79: both banks from the prototype, interleaved as above; YAGI_ERR_CONFIG as yagi_hip.h says
+int symsync_design(size_t k, size_t npfb, const float *h, size_t h_len, std::vector<float> &taps, size_t *Ls);
+// set_lf_bw (:196-213) in f32
+int symsync_set_bw(float bw, SymsyncLoop *p);
+// reset() of one channel (:160-172); the history is not touched
+void symsync_reset_chan(SymsyncChan *s, size_t k, size_t k_out);
+int launch_symsync(const SymsyncLoop &p, const float *taps, SymsyncChan *state, cf32 *hist, size_t C, const cf32 *x,
+                   size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, size_t ycap, unsigned *status, hipStream_t st);
+// the same on the host, channel after channel; ny and stalled have C entries each
+void symsync_host(const SymsyncLoop &p, const float *taps, SymsyncChan *state, cf32 *hist, size_t C, const cf32 *x,
+                  size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, size_t ycap, unsigned *ny, unsigned *stalled);
+
 // ---- symstream_kernels.hip -----------------------------------------------------------------
 // SymStream (yagi_hip.h): samples [0, n) of a call that starts at buf_index p, from the carried window `win` (Ls values,
 // oldest first) and new symbols that come either from the caller's bytes (sym, flag = the result of
