@@ -1795,6 +1795,85 @@ int yagi_hip_symsync_crcf_execute_host(size_t channels, size_t k, size_t npfb, c
                                        float bw, int locked, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
                                        size_t y_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled, float *tau);
 
+/* ---- EqLms: LMS equalizer for a bank of channels (src/equalization/eqlms.rs) -----------------------------------------
+ * EqLms(channels, h[h_len] or NULL): `channels` independent Eqlms<Complex32> objects of one design (cccf only).  A block
+ * is x[s x_pitch + c], step s, channel c < channels; per channel every output word and every weight equals the
+ * reference's sequential loop, in f32 with every product, sum and quotient rounded on its own:
+ *     execute (:137-140)   y = sum_i conj(w0[i]) r[i] over the window oldest first, num-complex's product (re = a.re b.re
+ *                          - a.im b.im, im = a.re b.im + a.im b.re with a = (w.re, -w.im)), folded from Complex(0, 0)
+ *     push(x) (:125-129)   the window takes x; x2_n = x.re x.re - x.im (-x.im); x2_sum += x2_n - x2_0, x2_0 the value
+ *                          pushed h_len pushes earlier (the same expression on the sample that leaves the window, which
+ *                          is how the device forms it); x2_sum is a running f32 sum and part of the state, never
+ *                          recomputed from the window; count += 1
+ *     step(d, d_hat) (:170-187)   nothing while count < h_len; else alpha = d - d_hat and, for every tap, w0[i] = w0[i] +
+ *                          ((mu conj(alpha)) r[i]) / x2_sum: an f32-times-complex scaling, the full complex product, a
+ *                          true IEEE division per component.  x2_sum = 0 or NaN gives that channel Inf / NaN weights
+ *     step_blind(d_hat) (:189-192)   d = d_hat / |d_hat| componentwise, then step(d, d_hat); d_hat = 0 gives NaN
+ * Deviation 1, |z|: the reference calls the platform's hypotf, which is not one fixed word.  The library defines
+ * |z| = (float)sqrt((double)re (double)re + (double)im (double)im), on the device and on the host (DESIGN.md section 4
+ * records how often that differs from this platform's hypotf).
+ * Deviation 2, DECISION: the desired symbol is table[j], j the FIRST index that minimises (y.re - t.re)^2 + (y.im -
+ * t.im)^2 with unfused terms, only a strictly smaller value replacing the best.  It is the library's own rule, the one
+ * Modem's Arb hard decision uses, NOT the reference's Modem::get_demodulator_sample.
+ *   create(channels, h, h_len)   h0[i] = conj(h[h_len - 1 - i]); h = NULL: h0[h_len / 2] = 1.  h_len = 0 is
+ *                             YAGI_ERR_CONFIG as in the reference; limits below; decided before any device is asked for
+ *   create_rnyquist(channels, ftype, k, m, beta, dt)   (:51-76) k >= 2, m >= 1, beta in [0, 1], dt in [-1, 1];
+ *                             h = fir_design_prototype(ftype, k, m, beta, dt) / fl(k), h_len = 2 k m + 1
+ *   create_lowpass(channels, h_len, fc)   (:78-90) h_len >= 1, fc in [0, 0.5]; h = fir_design_kaiser(h_len, fc, 40, 0)
+ *                             x 2 x fc, the imaginary part the reference's (h 0) fc
+ *   destroy / clone / set_stream / reset / reset_channel(c)
+ *   set_bw(mu) / get_bw       mu < 0 is YAGI_ERR_CONFIG; one value for the bank, 0.5 after create
+ *   get_length / get_channels
+ *   get_coefficients(out[channels][h_len])   w0;   get_weights: w0 reversed and conjugated.  They synchronise
+ *   set_constellation(table, M)   DECISION's table, 1 <= M <= YAGI_EQLMS_TABLE_MAX, copied
+ *   execute_block(k, x, x_pitch, n, y, y_pitch)   (:153-168) per row: push, y[s] = execute(), and step_blind(y[s]) where
+ *                             (count + k - 1) mod k = 0; count carries across calls.  k >= 1
+ *   decim_block(k, mode, x, x_pitch, n, d, d_pitch, y, y_pitch)   n rows in, a multiple of k; per symbol i < n / k:
+ *                             decim_execute (:142-151: push x[i k], y[i] = execute(), push the other k - 1 rows), THEN one
+ *                             update, so the gradient uses the shifted window and the later x2_sum (the order of the
+ *                             reference's testbench).  mode: YAGI_EQLMS_NONE no update; TRAIN step(d[i d_pitch + c], y);
+ *                             BLIND step_blind(y); DECISION step(table[j], y).  d is read by TRAIN only
+ *   execute_block_dev / decim_block_dev   the same on device pointers, asynchronous on the object's stream
+ *   execute_host(channels, h, h_len, mu, call, k, x, x_pitch, n, d, d_pitch, table, M, y, y_pitch, w0)   the definition on
+ *                             the host alone, one call from reset(), no device needed; call = a mode for decim_block or
+ *                             YAGI_EQLMS_EXECUTE for execute_block; w0[channels][h_len] may be NULL
+ * Every result is independent of how the stream is cut into calls.  The pitches are in samples and >= channels; n is below
+ * 2^31.  x, d and y must not overlap.
+ * Not built: Eqrls, rrrf, per-channel designs or step sizes, sharding.
+ * Device form: eqlms_kernels.hip: one lane per channel, one wave per workgroup. */
+#define YAGI_EQLMS_LEN_MAX 128
+#define YAGI_EQLMS_CHANNELS_MAX 1048576
+#define YAGI_EQLMS_TABLE_MAX 256
+enum { YAGI_EQLMS_NONE = 0, YAGI_EQLMS_TRAIN = 1, YAGI_EQLMS_BLIND = 2, YAGI_EQLMS_DECISION = 3, YAGI_EQLMS_EXECUTE = 4 };
+typedef struct yagi_hip_eqlms_cccf_s *yagi_hip_eqlms_cccf;
+int yagi_hip_eqlms_cccf_create(size_t channels, const yagi_cf32 *h, size_t h_len, yagi_hip_eqlms_cccf *q);
+int yagi_hip_eqlms_cccf_create_rnyquist(size_t channels, int ftype, size_t k, size_t m, float beta, float dt,
+                                        yagi_hip_eqlms_cccf *q);
+int yagi_hip_eqlms_cccf_create_lowpass(size_t channels, size_t h_len, float fc, yagi_hip_eqlms_cccf *q);
+int yagi_hip_eqlms_cccf_destroy(yagi_hip_eqlms_cccf q);
+int yagi_hip_eqlms_cccf_clone(yagi_hip_eqlms_cccf q, yagi_hip_eqlms_cccf *out);
+int yagi_hip_eqlms_cccf_set_stream(yagi_hip_eqlms_cccf q, yagi_stream_t s);
+int yagi_hip_eqlms_cccf_reset(yagi_hip_eqlms_cccf q);
+int yagi_hip_eqlms_cccf_reset_channel(yagi_hip_eqlms_cccf q, size_t c);
+int yagi_hip_eqlms_cccf_set_bw(yagi_hip_eqlms_cccf q, float mu);
+int yagi_hip_eqlms_cccf_get_bw(yagi_hip_eqlms_cccf q, float *mu);
+int yagi_hip_eqlms_cccf_get_length(yagi_hip_eqlms_cccf q, size_t *h_len);
+int yagi_hip_eqlms_cccf_get_channels(yagi_hip_eqlms_cccf q, size_t *channels);
+int yagi_hip_eqlms_cccf_get_coefficients(yagi_hip_eqlms_cccf q, yagi_cf32 *w0);
+int yagi_hip_eqlms_cccf_get_weights(yagi_hip_eqlms_cccf q, yagi_cf32 *w);
+int yagi_hip_eqlms_cccf_set_constellation(yagi_hip_eqlms_cccf q, const yagi_cf32 *table, size_t M);
+int yagi_hip_eqlms_cccf_execute_block(yagi_hip_eqlms_cccf q, size_t k, const yagi_cf32 *x, size_t x_pitch, size_t n,
+                                      yagi_cf32 *y, size_t y_pitch);
+int yagi_hip_eqlms_cccf_execute_block_dev(yagi_hip_eqlms_cccf q, size_t k, const yagi_cf32 *x_dev, size_t x_pitch, size_t n,
+                                          yagi_cf32 *y_dev, size_t y_pitch);
+int yagi_hip_eqlms_cccf_decim_block(yagi_hip_eqlms_cccf q, size_t k, int mode, const yagi_cf32 *x, size_t x_pitch, size_t n,
+                                    const yagi_cf32 *d, size_t d_pitch, yagi_cf32 *y, size_t y_pitch);
+int yagi_hip_eqlms_cccf_decim_block_dev(yagi_hip_eqlms_cccf q, size_t k, int mode, const yagi_cf32 *x_dev, size_t x_pitch,
+                                        size_t n, const yagi_cf32 *d_dev, size_t d_pitch, yagi_cf32 *y_dev, size_t y_pitch);
+int yagi_hip_eqlms_cccf_execute_host(size_t channels, const yagi_cf32 *h, size_t h_len, float mu, int call, size_t k,
+                                     const yagi_cf32 *x, size_t x_pitch, size_t n, const yagi_cf32 *d, size_t d_pitch,
+                                     const yagi_cf32 *table, size_t M, yagi_cf32 *y, size_t y_pitch, yagi_cf32 *w0);
+
 /* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */
 

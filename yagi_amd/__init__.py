@@ -20,6 +20,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     BurstDetector              (absent from the reference: Autocorr, threshold and run / peak extraction fused)
     PreambleDetector           (absent from the reference: a bank of known-preamble correlators, threshold and events)
     SymSync                    src/filter/symsync.rs:37-276, one object per channel of a bank
+    EqLms, EqLmsUpdate         src/equalization/eqlms.rs:25-199, one object per channel of a bank
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -38,7 +39,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "EqLms", "EqLmsUpdate", "EQLMS_LEN_MAX", "EQLMS_CHANNELS_MAX", "EQLMS_TABLE_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "SpgramPlan", "plan_spgram", "MsResamp2Plan", "Resamp2Plan", "plan_msresamp2", "plan_resamp2", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
@@ -2282,6 +2283,181 @@ class SymSync(_Handle):
                                                       _ptr(x), x_pitch, n, _ptr(y), y_pitch, ycap, _ptr(ny), _ptr(st),
                                                       _ptr(tau)))
         return y, ny, st, tau
+
+
+EQLMS_LEN_MAX = 128                # YAGI_EQLMS_LEN_MAX: the most taps of EqLms
+EQLMS_CHANNELS_MAX = 1 << 20       # YAGI_EQLMS_CHANNELS_MAX
+EQLMS_TABLE_MAX = 256              # YAGI_EQLMS_TABLE_MAX: the most points of DECISION's constellation
+
+
+class EqLmsUpdate(enum.IntEnum):
+    """what EqLms.decim_block does after each symbol, numbered as YAGI_EQLMS_*"""
+    NONE = 0        # a fixed decimating filter
+    TRAIN = 1       # step(d, y) against known symbols
+    BLIND = 2       # step_blind(y): constant modulus
+    DECISION = 3    # step(table[j], y) against the nearest point of set_constellation's table
+_EQLMS_EXECUTE = 4  # YAGI_EQLMS_EXECUTE: execute_host's word for execute_block
+
+
+class EqLms(_Handle):
+    """EqLms(channels, h_len, h=None): `channels` independent equalization::eqlms::Eqlms<Complex32> objects of one design
+    (src/equalization/eqlms.rs), Complex<f32> only.  A block is x[n, channels] (step, channel); per channel every output
+    word and every weight is the reference's sequential loop bit for bit: y = sum conj(w0[i]) r[i] over the window oldest
+    first, x2_sum a running f32 sum, and w0[i] += ((mu conj(d - y)) r[i]) / x2_sum once count >= h_len (yagi_hip.h).
+    Two stated deviations: |z| of the blind update is (float)sqrt((double)re^2 + (double)im^2), not the platform's
+    hypotf, and DECISION picks the first table entry at the least unfused squared distance (Modem's Arb rule), not the
+    reference's get_demodulator_sample.
+    The block calls run eqlms_kernels.hip, one lane per channel.  h_len <= EQLMS_LEN_MAX, channels <= EQLMS_CHANNELS_MAX."""
+    _prefix = "yagi_hip_eqlms_cccf_"
+
+    def __init__(self, channels, h_len, h=None, kind="cccf"):
+        """Eqlms::new (:25-49): h0[i] = conj(h[h_len - 1 - i]); h = None: h0[h_len // 2] = 1"""
+        if kind != "cccf":
+            raise ConfigError(f"unknown type combination {kind!r}")
+        channels, h_len = _symsync_size(channels, "channels"), _symsync_size(h_len, "h_len")
+        if h is not None:
+            h = _arr(h, np.complex64)
+            if h.ndim != 1 or h.size != h_len:
+                raise ConfigError("the taps are one-dimensional, h_len of them")
+        hd = C.c_void_p()
+        _check(self._fn("create")(channels, None if h is None else _ptr(h), h_len, C.byref(hd)))
+        self._set(hd, channels)
+
+    def _set(self, hd, channels):
+        self._h, self.kind, self.T, self.channels = hd, "cccf", np.complex64, channels
+        v = C.c_size_t()
+        _check(self._fn("get_length")(self._h, C.byref(v)))
+        self.h_len = v.value
+
+    @classmethod
+    def rnyquist(cls, channels, ftype, k, m, beta, dt):
+        """Eqlms::new_rnyquist (:51-76)"""
+        channels, k, m = (_symsync_size(v, "argument") for v in (channels, k, m))
+        new, hd = object.__new__(cls), C.c_void_p()
+        _check(new._fn("create_rnyquist")(channels, int(ftype), k, m, beta, dt, C.byref(hd)))
+        new._set(hd, channels)
+        return new
+
+    @classmethod
+    def lowpass(cls, channels, h_len, fc):
+        """Eqlms::new_lowpass (:78-90)"""
+        channels, h_len = (_symsync_size(v, "argument") for v in (channels, h_len))
+        new, hd = object.__new__(cls), C.c_void_p()
+        _check(new._fn("create_lowpass")(channels, h_len, fc, C.byref(hd)))
+        new._set(hd, channels)
+        return new
+
+    def clone(self):
+        new, hd = object.__new__(type(self)), C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._set(hd, self.channels)
+        return new
+
+    def reset_channel(self, c):
+        _check(self._fn("reset_channel")(self._h, _symsync_size(c, "channel")))
+
+    def set_bw(self, mu):
+        """the step size mu >= 0, one value for the bank"""
+        _check(self._fn("set_bw")(self._h, mu))
+
+    def get_bw(self):
+        v = C.c_float()
+        _check(self._fn("get_bw")(self._h, C.byref(v)))
+        return v.value
+
+    def get_length(self):
+        return self.h_len
+
+    def get_coefficients(self):
+        """w0[channels, h_len]; synchronises"""
+        out = np.zeros((self.channels, self.h_len), self.T)
+        _check(self._fn("get_coefficients")(self._h, _ptr(out)))
+        return out
+
+    def get_weights(self):
+        """w0 reversed and conjugated, [channels, h_len] (:121-123); synchronises"""
+        out = np.zeros((self.channels, self.h_len), self.T)
+        _check(self._fn("get_weights")(self._h, _ptr(out)))
+        return out
+
+    def set_constellation(self, table):
+        """DECISION's table, 1 .. EQLMS_TABLE_MAX points"""
+        table = _arr(table, self.T)
+        if table.ndim != 1:
+            raise ConfigError("the constellation is one-dimensional")
+        _check(self._fn("set_constellation")(self._h, _ptr(table), table.size))
+
+    def _block(self, x):
+        x = _arr(x, self.T)
+        if x.ndim != 2 or x.shape[1] != self.channels:
+            raise ConfigError(f"the block is [steps, {self.channels}]")
+        return x
+
+    def execute_block(self, k, x):
+        """Eqlms::execute_block (:153-168): x[n, channels] -> y[n, channels], a blind update where (count + k - 1) % k == 0"""
+        x = self._block(x)
+        y = np.zeros_like(x)
+        _check(self._fn("execute_block")(self._h, _symsync_size(k, "k"), _ptr(x), self.channels, x.shape[0], _ptr(y),
+                                         self.channels))
+        return y
+
+    def decim_block(self, k, mode, x, d=None):
+        """x[n k, channels] -> y[n, channels]: per symbol decim_execute (:142-151), then one update of `mode`
+        (EqLmsUpdate); d[n, channels] are TRAIN's known symbols"""
+        x, k = self._block(x), _symsync_size(k, "k")
+        if d is not None:
+            d = self._block(d)
+            if k and d.shape[0] * k != x.shape[0]:
+                raise ConfigError("d holds one row per symbol")
+        y = np.zeros((x.shape[0] // max(k, 1), self.channels), self.T)
+        _check(self._fn("decim_block")(self._h, k, int(mode), _ptr(x), self.channels, x.shape[0],
+                                       None if d is None else _ptr(d), self.channels, _ptr(y), self.channels))
+        return y
+
+    def execute_block_devptr(self, k, x_dev, x_pitch, n, y_dev, y_pitch):
+        """x_dev: n rows of pitch x_pitch samples; y_dev: n rows of pitch y_pitch.  Asynchronous on the object's stream
+        (the C ABI's execute_block_dev; named as Ddc.execute_block_devptr is)"""
+        x_dev, y_dev = (None if p is None else _devptr(p) for p in (x_dev, y_dev))
+        _check(self._fn("execute_block_dev")(self._h, k, x_dev, x_pitch, n, y_dev, y_pitch))
+
+    def decim_block_devptr(self, k, mode, x_dev, x_pitch, n, d_dev, d_pitch, y_dev, y_pitch):
+        """x_dev: n rows (a multiple of k); d_dev: n / k rows of known symbols, None unless TRAIN; y_dev: n / k rows.
+        Asynchronous on the object's stream (the C ABI's decim_block_dev)"""
+        x_dev, d_dev, y_dev = (None if p is None else _devptr(p) for p in (x_dev, d_dev, y_dev))
+        _check(self._fn("decim_block_dev")(self._h, k, int(mode), x_dev, x_pitch, n, d_dev, d_pitch, y_dev, y_pitch))
+
+    @staticmethod
+    def execute_host(channels, h_len, h, mu, k, x, mode=None, d=None, table=None, x_pitch=None, d_pitch=None, y_pitch=None):
+        """the definition on the host alone, no device needed: one call from reset().  mode = None runs execute_block,
+        an EqLmsUpdate runs decim_block.  x is [n, x_pitch] (the pitches default to channels); returns (y[rows, y_pitch],
+        w0[channels, h_len]).  The library's own sequential form, slow and meant for checks"""
+        channels, h_len, k = (_symsync_size(v, "argument") for v in (channels, h_len, k))
+        if not 1 <= channels <= EQLMS_CHANNELS_MAX:
+            raise ConfigError("channels must be in 1 .. EQLMS_CHANNELS_MAX")
+        x_pitch, d_pitch, y_pitch = (channels if p is None else _symsync_size(p, "pitch") for p in (x_pitch, d_pitch, y_pitch))
+        x = _arr(x, np.complex64)
+        if x.ndim != 2 or x.shape[1] != x_pitch:
+            raise ConfigError("the block is [steps, x_pitch]")
+        if h is not None:
+            h = _arr(h, np.complex64)
+            if h.ndim != 1 or h.size != h_len:
+                raise ConfigError("the taps are one-dimensional, h_len of them")
+        if d is not None:
+            d = _arr(d, np.complex64)
+            if d.ndim != 2 or d.shape[1] != d_pitch or d.shape[0] * max(k, 1) != x.shape[0]:
+                raise ConfigError("d is [symbols, d_pitch]")
+        if table is not None:
+            table = _arr(table, np.complex64).reshape(-1)
+        call = _EQLMS_EXECUTE if mode is None else int(mode)
+        n = x.shape[0]
+        rows = n if mode is None else n // max(k, 1)
+        y = np.zeros((rows, y_pitch), np.complex64)
+        w0 = np.zeros((channels, min(h_len, EQLMS_LEN_MAX)), np.complex64)
+        _check(lib.yagi_hip_eqlms_cccf_execute_host(
+            channels, None if h is None else _ptr(h), h_len, mu, call, k, _ptr(x), x_pitch, n,
+            None if d is None else _ptr(d), d_pitch, None if table is None else _ptr(table),
+            0 if table is None else table.size, _ptr(y), y_pitch, _ptr(w0)))
+        return y, w0
 
 
 MSEQUENCE_TILE = 8192    # YAGI_MSEQUENCE_TILE: symbols per workgroup of the generator kernel

@@ -688,6 +688,29 @@ _sig(_p + "execute", vp, vp, sz, sz, vp, sz, sz, vp, vp)
 _sig(_p + "execute_dev", vp, vp, sz, sz, vp, sz, sz, vp)
 _sig(_p + "execute_host", sz, sz, sz, vp, sz, sz, f32, ci, vp, sz, sz, vp, sz, sz, vp, vp, vp)
 
+# ---- EqLms -------------------------------------------------------------------------------------
+_p = "yagi_hip_eqlms_cccf_"
+_sig(_p + "create", sz, vp, sz, pvp)
+_sig(_p + "create_rnyquist", sz, ci, sz, sz, f32, f32, pvp)
+_sig(_p + "create_lowpass", sz, sz, f32, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "reset_channel", vp, sz)
+_sig(_p + "set_bw", vp, f32)
+_sig(_p + "get_bw", vp, C.POINTER(f32))
+_sig(_p + "get_length", vp, C.POINTER(sz))
+_sig(_p + "get_channels", vp, C.POINTER(sz))
+_sig(_p + "get_coefficients", vp, vp)
+_sig(_p + "get_weights", vp, vp)
+_sig(_p + "set_constellation", vp, vp, sz)
+_sig(_p + "execute_block", vp, sz, vp, sz, sz, vp, sz)
+_sig(_p + "execute_block_dev", vp, sz, vp, sz, sz, vp, sz)
+_sig(_p + "decim_block", vp, sz, ci, vp, sz, sz, vp, sz, vp, sz)
+_sig(_p + "decim_block_dev", vp, sz, ci, vp, sz, sz, vp, sz, vp, sz)
+_sig(_p + "execute_host", sz, vp, sz, f32, ci, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz, vp)
+
 # ---- SymStream ---------------------------------------------------------------------------------
 _p = "yagi_hip_symstreamcf_"
 _sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)

@@ -7098,6 +7098,377 @@ int yagi_hip_symsync_crcf_execute_host(size_t channels, size_t k, size_t npfb, c
 
 }  // extern "C"
 
+// ---- EqLms (src/equalization/eqlms.rs, one object per channel) -----------------------------------------------------
+// The state is the weights and the window, [h_len][channels] each, plus one EqlmsChan per channel; eqlms_kernels.hip
+// updates all three in place on the device.  reset, reset_channel, the getters and clone work on a host mirror; the two
+// copies are synchronised lazily (Mirror).  mu, k and the mode travel to the kernel by value with every call.
+namespace yagi {
+
+struct EqlmsObj {
+    hipStream_t st = nullptr;
+    size_t C = 0, h_len = 0;
+    float mu = 0.5f;
+    std::vector<cf32> h0, table;
+    DevBuf w_dev, hist_dev, state_dev, table_dev;
+    std::vector<cf32> hw, hh;                             // host mirror: [h_len][C]
+    std::vector<EqlmsChan> hs;
+    Mirror mirror;
+    Staging ws, wsd;                                      // host block forms: x and a compact y; the rows of d
+
+    void reset_chan(size_t c) {
+        for (size_t i = 0; i < h_len; ++i) {
+            hw[i * C + c] = h0[i];
+            hh[i * C + c] = cf32{0.0f, 0.0f};
+        }
+        hs[c] = EqlmsChan{};
+    }
+    // new (:25-49); everything that needs no device
+    int configure(size_t channels, const cf32 *h, size_t h_len_) {
+        if (channels == 0 || channels > (size_t)YAGI_EQLMS_CHANNELS_MAX)
+            return fail(YAGI_ERR_CONFIG, "eqlms: %zu channels are outside 1 .. YAGI_EQLMS_CHANNELS_MAX", channels);
+        if (h_len_ == 0) return fail(YAGI_ERR_CONFIG, "filter length must be greater than 0");
+        if (h_len_ > (size_t)YAGI_EQLMS_LEN_MAX)
+            return fail(YAGI_ERR_CONFIG, "eqlms: %zu taps are more than YAGI_EQLMS_LEN_MAX", h_len_);
+        C = channels, h_len = h_len_, mu = 0.5f;
+        h0.assign(h_len, cf32{0.0f, 0.0f});
+        if (h)
+            for (size_t i = 0; i < h_len; ++i) h0[i] = cf32{h[h_len - i - 1].re, -h[h_len - i - 1].im};
+        else
+            h0[h_len / 2] = cf32{1.0f, 0.0f};
+        hw.assign(h_len * C, cf32{});
+        hh.assign(h_len * C, cf32{});
+        hs.assign(C, EqlmsChan{});
+        for (size_t c = 0; c < C; ++c) reset_chan(c);
+        return YAGI_OK;
+    }
+    int alloc() {
+        YG_TRY(require_device());
+        YG_TRY(w_dev.alloc(h_len * C * sizeof(cf32)));
+        YG_TRY(hist_dev.alloc(h_len * C * sizeof(cf32)));
+        YG_TRY(state_dev.alloc(C * sizeof(EqlmsChan)));
+        if (!table.empty()) {
+            YG_TRY(fill(table_dev, table.data(), table.size() * sizeof(cf32), st));
+        }
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] {
+            YG_TRY(download(hw.data(), w_dev.p, h_len * C * sizeof(cf32), st));
+            YG_TRY(download(hh.data(), hist_dev.p, h_len * C * sizeof(cf32), st));
+            return download(hs.data(), state_dev.p, C * sizeof(EqlmsChan), st);
+        });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] {
+            YG_TRY(upload(w_dev.p, hw.data(), h_len * C * sizeof(cf32), st));
+            YG_TRY(upload(hist_dev.p, hh.data(), h_len * C * sizeof(cf32), st));
+            return upload(state_dev.p, hs.data(), C * sizeof(EqlmsChan), st);
+        });
+    }
+    int reset_channel(size_t c) {
+        if (c >= C) return fail(YAGI_ERR_CONFIG, "eqlms: channel %zu of %zu", c, C);
+        YG_TRY(ensure_host());
+        reset_chan(c);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int reset() {
+        YG_TRY(ensure_host());
+        for (size_t c = 0; c < C; ++c) reset_chan(c);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    static int set_bw(float mu_, float *mu) {               // (:105-111)
+        if (mu_ < 0.0f) return fail(YAGI_ERR_CONFIG, "learning rate cannot be less than zero");
+        *mu = mu_;
+        return YAGI_OK;
+    }
+    static int check_table(const cf32 *t, size_t M) {
+        if (M == 0 || M > (size_t)YAGI_EQLMS_TABLE_MAX)
+            return fail(YAGI_ERR_CONFIG, "eqlms: a constellation of %zu points is outside 1 .. YAGI_EQLMS_TABLE_MAX", M);
+        if (!t) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        return YAGI_OK;
+    }
+    // call = a mode (decim_block) or YAGI_EQLMS_EXECUTE; sets the rows of y
+    static int check_block(size_t C, int call, size_t k, size_t x_pitch, size_t n, bool have_d, size_t d_pitch, size_t M,
+                           size_t y_pitch, size_t *rows) {
+        if (call < YAGI_EQLMS_NONE || call > YAGI_EQLMS_EXECUTE)
+            return fail(YAGI_ERR_CONFIG, "eqlms: unknown update mode %d", call);
+        if (k == 0) return fail(YAGI_ERR_CONFIG, "down-sampling rate 'k' must be greater than 0");
+        if (n >= ((size_t)1 << 31) || k >= ((size_t)1 << 31)) return fail(YAGI_ERR_CONFIG, "eqlms: n and k must be below 2^31");
+        if (x_pitch < C || y_pitch < C || x_pitch >= ((size_t)1 << 31) || y_pitch >= ((size_t)1 << 31))
+            return fail(YAGI_ERR_CONFIG, "eqlms: the pitches are in samples, at least the channel count and below 2^31");
+        *rows = n;
+        if (call == YAGI_EQLMS_EXECUTE) return YAGI_OK;
+        if (n % k != 0) return fail(YAGI_ERR_CONFIG, "eqlms: decim_block takes whole symbols, %zu rows at k = %zu", n, k);
+        *rows = n / k;
+        if (call == YAGI_EQLMS_TRAIN && *rows != 0) {
+            if (!have_d) return fail(YAGI_ERR_CONFIG, "eqlms: TRAIN needs the known symbols d");
+            if (d_pitch < C || d_pitch >= ((size_t)1 << 31))
+                return fail(YAGI_ERR_CONFIG, "eqlms: the pitches are in samples, at least the channel count and below 2^31");
+        }
+        if (call == YAGI_EQLMS_DECISION && M == 0)
+            return fail(YAGI_ERR_CONFIG, "eqlms: DECISION needs set_constellation first");
+        return YAGI_OK;
+    }
+    int block_dev(int call, size_t k, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, cf32 *y,
+                  size_t y_pitch) {
+        if (n == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        YG_TRY(launch_eqlms(call, h_len, mu, w_dev.as<cf32>(), hist_dev.as<cf32>(), state_dev.as<EqlmsChan>(), C, k, x,
+                            x_pitch, n, d, d_pitch, table_dev.as<cf32>(), table.size(), y, y_pitch, st));
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+    int block_host(int call, size_t k, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, cf32 *y,
+                   size_t y_pitch) {
+        size_t rows = 0;
+        YG_TRY(check_block(C, call, k, x_pitch, n, d != nullptr, d_pitch, table.size(), y_pitch, &rows));
+        if (n == 0) return YAGI_OK;
+        if (!x || !y) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        YG_TRY(ws.put(st, x, (n - 1) * x_pitch + C));
+        const bool train = call == YAGI_EQLMS_TRAIN;
+        if (train) {
+            YG_TRY(wsd.put(st, d, (rows - 1) * d_pitch + C));
+        }
+        YG_TRY(ws.y.ensure(rows * C * sizeof(cf32)));
+        YG_TRY(block_dev(call, k, ws.x.as<cf32>(), x_pitch, n, train ? wsd.x.as<cf32>() : nullptr, d_pitch, ws.y.as<cf32>(), C));
+        std::vector<cf32> t(rows * C);
+        YG_TRY(download(t.data(), ws.y.p, rows * C * sizeof(cf32), st));
+        for (size_t j = 0; j < rows; ++j) std::copy(t.begin() + j * C, t.begin() + (j + 1) * C, y + j * y_pitch);
+        return YAGI_OK;
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_eqlms_cccf_s : EqlmsObj {};
+
+namespace {
+
+int eqlms_make(yagi_hip_eqlms_cccf *q, size_t channels, const cf32 *h, size_t h_len) {
+    *q = nullptr;
+    auto o = std::make_unique<yagi_hip_eqlms_cccf_s>();
+    YG_TRY(o->configure(channels, h, h_len));
+    YG_TRY(o->alloc());
+    *q = o.release();
+    return YAGI_OK;
+}
+
+// new_rnyquist (:51-76): the prototype over fl(k), as complex taps
+int eqlms_rnyquist_taps(int ftype, size_t k, size_t m, float beta, float dt, std::vector<cf32> &hc) {
+    if (k < 2) return fail(YAGI_ERR_CONFIG, "samples/symbol must be greater than 1");
+    if (m == 0) return fail(YAGI_ERR_CONFIG, "filter delay must be greater than 0");
+    if (!(beta >= 0.0f && beta <= 1.0f)) return fail(YAGI_ERR_CONFIG, "filter excess bandwidth factor must be in [0,1]");
+    if (!(dt >= -1.0f && dt <= 1.0f)) return fail(YAGI_ERR_CONFIG, "filter fractional sample delay must be in [-1,1]");
+    if (k > (size_t)YAGI_EQLMS_LEN_MAX || m > (size_t)YAGI_EQLMS_LEN_MAX || 2 * k * m + 1 > (size_t)YAGI_EQLMS_LEN_MAX)
+        return fail(YAGI_ERR_CONFIG, "eqlms: 2 k m + 1 taps at (k, m) = (%zu, %zu) are more than YAGI_EQLMS_LEN_MAX", k, m);
+    std::vector<float> h;
+    YG_TRY(design_prototype(ftype, k, m, beta, dt, h));
+    hc.resize(h.size());
+    const float kf = (float)k;
+    for (size_t i = 0; i < h.size(); ++i) hc[i] = cf32{h[i] / kf, 0.0f};
+    return YAGI_OK;
+}
+// new_lowpass (:78-90): x * Complex(2, 0) * fc
+int eqlms_lowpass_taps(size_t h_len, float fc, std::vector<cf32> &hc) {
+    if (h_len == 0) return fail(YAGI_ERR_CONFIG, "filter length must be greater than 0");
+    if (!(fc >= 0.0f && fc <= 0.5f)) return fail(YAGI_ERR_CONFIG, "filter cutoff must be in (0,0.5]");
+    if (h_len > (size_t)YAGI_EQLMS_LEN_MAX)
+        return fail(YAGI_ERR_CONFIG, "eqlms: %zu taps are more than YAGI_EQLMS_LEN_MAX", h_len);
+    std::vector<float> h;
+    YG_TRY(design_kaiser(h_len, fc, 40.0f, 0.0f, h));
+    hc.resize(h.size());
+    for (size_t i = 0; i < h.size(); ++i) {
+        const float re = h[i] * 2.0f, im = h[i] * 0.0f;
+        hc[i] = cf32{re * fc, im * fc};
+    }
+    return YAGI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int yagi_hip_eqlms_cccf_create(size_t channels, const cf32 *h, size_t h_len, yagi_hip_eqlms_cccf *q) try {
+    CHECK_PTR(q);
+    return eqlms_make(q, channels, h, h_len);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_create_rnyquist(size_t channels, int ftype, size_t k, size_t m, float beta, float dt,
+                                        yagi_hip_eqlms_cccf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    std::vector<cf32> hc;
+    YG_TRY(eqlms_rnyquist_taps(ftype, k, m, beta, dt, hc));
+    return eqlms_make(q, channels, hc.data(), hc.size());
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_create_lowpass(size_t channels, size_t h_len, float fc, yagi_hip_eqlms_cccf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    std::vector<cf32> hc;
+    YG_TRY(eqlms_lowpass_taps(h_len, fc, hc));
+    return eqlms_make(q, channels, hc.data(), hc.size());
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_destroy(yagi_hip_eqlms_cccf q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_clone(yagi_hip_eqlms_cccf q, yagi_hip_eqlms_cccf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_eqlms_cccf_s>();
+    o->st = q->st;
+    o->C = q->C, o->h_len = q->h_len, o->mu = q->mu;
+    o->h0 = q->h0, o->table = q->table, o->hw = q->hw, o->hh = q->hh, o->hs = q->hs;
+    YG_TRY(o->alloc());
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_set_stream(yagi_hip_eqlms_cccf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_reset(yagi_hip_eqlms_cccf q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_reset_channel(yagi_hip_eqlms_cccf q, size_t c) try {
+    CHECK_Q(q);
+    return q->reset_channel(c);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_set_bw(yagi_hip_eqlms_cccf q, float mu) try {
+    CHECK_Q(q);
+    return EqlmsObj::set_bw(mu, &q->mu);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_get_bw(yagi_hip_eqlms_cccf q, float *mu) try {
+    CHECK_Q(q);
+    CHECK_PTR(mu);
+    *mu = q->mu;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_get_length(yagi_hip_eqlms_cccf q, size_t *h_len) try {
+    CHECK_Q(q);
+    CHECK_PTR(h_len);
+    *h_len = q->h_len;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_get_channels(yagi_hip_eqlms_cccf q, size_t *channels) try {
+    CHECK_Q(q);
+    CHECK_PTR(channels);
+    *channels = q->C;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_get_coefficients(yagi_hip_eqlms_cccf q, cf32 *w0) try {
+    CHECK_Q(q);
+    CHECK_PTR(w0);
+    YG_TRY(q->ensure_host());
+    for (size_t c = 0; c < q->C; ++c)
+        for (size_t i = 0; i < q->h_len; ++i) w0[c * q->h_len + i] = q->hw[i * q->C + c];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_get_weights(yagi_hip_eqlms_cccf q, cf32 *w) try {      // (:121-123)
+    CHECK_Q(q);
+    CHECK_PTR(w);
+    YG_TRY(q->ensure_host());
+    for (size_t c = 0; c < q->C; ++c)
+        for (size_t i = 0; i < q->h_len; ++i) {
+            const cf32 v = q->hw[(q->h_len - 1 - i) * q->C + c];
+            w[c * q->h_len + i] = cf32{v.re, -v.im};
+        }
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_set_constellation(yagi_hip_eqlms_cccf q, const cf32 *table, size_t M) try {
+    CHECK_Q(q);
+    YG_TRY(EqlmsObj::check_table(table, M));
+    YG_HIP(hipStreamSynchronize(q->st));                     // a launch in flight may still read the table
+    q->table.assign(table, table + M);
+    return fill(q->table_dev, q->table.data(), M * sizeof(cf32), q->st);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_execute_block(yagi_hip_eqlms_cccf q, size_t k, const cf32 *x, size_t x_pitch, size_t n, cf32 *y,
+                                      size_t y_pitch) try {
+    CHECK_Q(q);
+    return q->block_host(YAGI_EQLMS_EXECUTE, k, x, x_pitch, n, nullptr, 0, y, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_execute_block_dev(yagi_hip_eqlms_cccf q, size_t k, const cf32 *x_dev, size_t x_pitch, size_t n,
+                                          cf32 *y_dev, size_t y_pitch) try {
+    CHECK_Q(q);
+    size_t rows = 0;
+    YG_TRY(EqlmsObj::check_block(q->C, YAGI_EQLMS_EXECUTE, k, x_pitch, n, false, 0, 0, y_pitch, &rows));
+    if (n != 0) {
+        CHECK_PTR(x_dev);
+        CHECK_PTR(y_dev);
+    }
+    return q->block_dev(YAGI_EQLMS_EXECUTE, k, x_dev, x_pitch, n, nullptr, 0, y_dev, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_decim_block(yagi_hip_eqlms_cccf q, size_t k, int mode, const cf32 *x, size_t x_pitch, size_t n,
+                                    const cf32 *d, size_t d_pitch, cf32 *y, size_t y_pitch) try {
+    CHECK_Q(q);
+    if (mode == YAGI_EQLMS_EXECUTE) return fail(YAGI_ERR_CONFIG, "eqlms: unknown update mode %d", mode);
+    return q->block_host(mode, k, x, x_pitch, n, d, d_pitch, y, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_decim_block_dev(yagi_hip_eqlms_cccf q, size_t k, int mode, const cf32 *x_dev, size_t x_pitch,
+                                        size_t n, const cf32 *d_dev, size_t d_pitch, cf32 *y_dev, size_t y_pitch) try {
+    CHECK_Q(q);
+    if (mode == YAGI_EQLMS_EXECUTE) return fail(YAGI_ERR_CONFIG, "eqlms: unknown update mode %d", mode);
+    size_t rows = 0;
+    YG_TRY(EqlmsObj::check_block(q->C, mode, k, x_pitch, n, d_dev != nullptr, d_pitch, q->table.size(), y_pitch, &rows));
+    if (n != 0) {
+        CHECK_PTR(x_dev);
+        CHECK_PTR(y_dev);
+    }
+    return q->block_dev(mode, k, x_dev, x_pitch, n, d_dev, d_pitch, y_dev, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqlms_cccf_execute_host(size_t channels, const cf32 *h, size_t h_len, float mu, int call, size_t k,
+                                     const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch,
+                                     const cf32 *table, size_t M, cf32 *y, size_t y_pitch, cf32 *w0) try {
+    EqlmsObj o;
+    YG_TRY(o.configure(channels, h, h_len));
+    YG_TRY(EqlmsObj::set_bw(mu, &o.mu));
+    if (call == YAGI_EQLMS_DECISION) {
+        YG_TRY(EqlmsObj::check_table(table, M));
+    }
+    size_t rows = 0;
+    YG_TRY(EqlmsObj::check_block(channels, call, k, x_pitch, n, d != nullptr, d_pitch, M, y_pitch, &rows));
+    if (n != 0) {
+        CHECK_PTR(x);
+        CHECK_PTR(y);
+    }
+    eqlms_host(call, h_len, o.mu, o.hw.data(), o.hh.data(), o.hs.data(), channels, k, x, x_pitch, n, d, d_pitch, table, M, y,
+               y_pitch);
+    if (w0)
+        for (size_t c = 0; c < channels; ++c)
+            for (size_t i = 0; i < h_len; ++i) w0[c * h_len + i] = o.hw[i * channels + c];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

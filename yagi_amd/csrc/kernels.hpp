@@ -638,6 +638,38 @@ int launch_symsync(const SymsyncLoop &p, const float *taps, SymsyncChan *state, 
 void symsync_host(const SymsyncLoop &p, const float *taps, SymsyncChan *state, cf32 *hist, size_t C, const cf32 *x,
                   size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, size_t ycap, unsigned *ny, unsigned *stalled);
 
+// ---- eqlms_kernels.hip ---------------------------------------------------------------------
+// EqLms (yagi_hip.h): C independent Eqlms<Complex32> loops of one design, one lane per channel.  w = the weights w0,
+// [h_len][C]; hist = the window, [h_len][C], oldest first; state one EqlmsChan per channel.  All three are updated in
+// place (a workgroup touches its own channels only).  call = a YAGI_EQLMS_* mode for decim_block (n input rows, a
+// multiple of k, n / k rows of y; d = n / k rows of known symbols for TRAIN; table = M points for DECISION) or kEqlmsExec
+// for execute_block (n rows in, n rows out).
+constexpr int kEqlmsWg = 64;                           // channels per workgroup: one wave
+constexpr int kEqlmsAhead = 16;                        // input rows per chunk: requested one chunk ahead, staged in LDS
+constexpr int kEqlmsAheadD = 8;                        // the same for TRAIN's rows of known symbols
+constexpr int kEqlmsExec = 4;                          // execute_block, after the four YAGI_EQLMS_* modes
+struct EqlmsChan {
+    float x2_sum;                                      // the running f32 sum, never recomputed from the window
+    unsigned pad;
+    unsigned long long count;                          // pushes since reset, as usize
+};
+static_assert(sizeof(EqlmsChan) == 16, "device layout");
+constexpr size_t eqlms_taps_bytes(size_t h_len) { return h_len * kEqlmsWg * sizeof(cf32); }
+constexpr size_t eqlms_stage_bytes() { return (size_t)kEqlmsAhead * kEqlmsWg * sizeof(cf32); }
+constexpr size_t eqlms_dstage_bytes() { return (size_t)kEqlmsAheadD * kEqlmsWg * sizeof(cf32); }
+// ring, weights, both stages and the DECISION table: 145408 bytes at h_len = 128, under the 160 KiB of a CU
+constexpr size_t eqlms_lds_bytes(size_t h_len) {
+    return 2 * eqlms_taps_bytes(h_len) + eqlms_stage_bytes() + eqlms_dstage_bytes() + YAGI_EQLMS_TABLE_MAX * sizeof(cf32);
+}
+static_assert(eqlms_lds_bytes(YAGI_EQLMS_LEN_MAX) <= 160 * 1024, "the LDS of a CU");
+int launch_eqlms(int call, size_t h_len, float mu, cf32 *w, cf32 *hist, EqlmsChan *state, size_t C, size_t k, const cf32 *x,
+                 size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, const cf32 *table, size_t M, cf32 *y,
+                 size_t y_pitch, hipStream_t st);
+// the same on the host, channel after channel
+void eqlms_host(int call, size_t h_len, float mu, cf32 *w, cf32 *hist, EqlmsChan *state, size_t C, size_t k, const cf32 *x,
+                size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, const cf32 *table, size_t M, cf32 *y,
+                size_t y_pitch);
+
 // ---- symstream_kernels.hip -----------------------------------------------------------------
 // SymStream (yagi_hip.h): samples [0, n) of a call that starts at buf_index p, from the carried window `win` (Ls values,
 // oldest first) and new symbols that come either from the caller's bytes (sym, flag = the result of
