@@ -1874,6 +1874,124 @@ int yagi_hip_eqlms_cccf_execute_host(size_t channels, const yagi_cf32 *h, size_t
                                      const yagi_cf32 *x, size_t x_pitch, size_t n, const yagi_cf32 *d, size_t d_pitch,
                                      const yagi_cf32 *table, size_t M, yagi_cf32 *y, size_t y_pitch, yagi_cf32 *w0);
 
+/* ---- Agc: automatic gain control for a bank of channels (src/agc/agc.rs) ---------------------------------------------
+ * Agc(channels): `channels` independent Agc<T> objects of one set of settings, T = Complex<f32> (crcf) or f32 (rrrf).  A
+ * block is x[s x_pitch + c], step s < n, channel c < channels; per channel every output word, gain and squelch mode
+ * equals the reference's sequential loop, in f32 with every product and sum rounded on its own:
+ *     execute (:71-89)     y = x g (both components); y2 = (y conj y).re = re re - im (-im) (rrrf: y y);
+ *                          y2' = (1 - alpha) y2' + alpha y2;
+ *                          locked: the output is y, NOT scaled (the reference returns before `* scale`), nothing else
+ *                          changes; else where y2' > 1e-6: g = g yg_expf(-0.5 alpha yg_lnf(y2')), the argument formed
+ *                          left to right in f32; g = minNum(g, 1e6) (Rust's f32::min: a NaN g would become 1e6);
+ *                          squelch_update_mode; the output is y scale
+ *     squelch_update_mode (:212-248)   hi = (-20 yg_log10f(g) > threshold); Enabled -> hi ? Rise : Enabled; Rise -> hi ?
+ *                          SignalHi : Fall; SignalHi -> hi ? SignalHi : Fall; Fall -> timer = timeout, hi ? SignalHi :
+ *                          SignalLo; SignalLo -> timer -= 1, timer = 0 ? Timeout : hi ? SignalHi : SignalLo; Timeout ->
+ *                          Enabled; Disabled stays
+ *     reset (:60-69)       g = 1, y2' = 1, unlocked, mode -> Enabled unless Disabled
+ *     init(x) (:171-178)   per channel the f32 sum of |x|^2 (the expression of y2) in row order from +0; then
+ *                          g = 1 / (sqrt(sum / fl(n)) + 1e-16) in f32, y2' = 1
+ * The three words.  The reference calls the platform's ln, exp and log10, which are not fixed words.  The library
+ * defines each as the f32 rounding of an f64 evaluation made of IEEE f64 + - * / only, each rounded on its own and none
+ * fused, integer and bit operations on the exponent, and the f64 literals below (agc_words.hpp; the same source runs on
+ * the host and on the device, and tests/agc_ref.py restates it in Python floats):
+ *     ln64(x), x a positive finite f32 as f64:  x = 2^e m with m in [1, 2) from the bits; where m >= fl(sqrt 2): m = m / 2,
+ *         e = e + 1.  s = (m - 1) / (m + 1); z = s s; p = 1/23; then for k = 21, 19, .. 3, 1: p = p z + fl(1 / k).
+ *         ln64 = fl(e) LN2 + (2 s) p, LN2 = 0x1.62e42fefa39efp-1
+ *     yg_lnf(x) = (float)ln64(x); yg_log10f(x) = (float)(ln64(x) 0x1.bcb7b1526e50ep-2).  Special arguments of both: a
+ *         NaN or x < 0 gives NaN; either zero gives -inf; +inf gives +inf; subnormal f32 are normal f64
+ *     exp64(x), x not a NaN:  x = min(max(x, -110), 95) (beyond the clamp the f32 word is 0 or inf anyway, and 2^k stays
+ *         a normal f64); t = x 0x1.71547652b82fep+0 + 0.5; k = floor(t); r = (x - k HI) - k LO with HI =
+ *         0x1.62e42feep-1, LO = 0x1.a39ef35793c76p-33; p = fl(1 / 14!); then for j = 13, 12, .. 1, 0: p = p r + fl(1 / j!).
+ *         exp64 = p 2^k (exact)
+ *     yg_expf(x) = (float)exp64(x); NaN gives NaN, -inf gives +0, +inf gives +inf; subnormal results come from the one
+ *         f64 -> f32 rounding
+ *     set_rssi's 10^(-rssi / 20) = (float)exp64((double)fl32(-rssi / 20) 0x1.26bb1bbb55516p+1), host only
+ * yagi_hip_lnf / expf / log10f(x, n, y) run the words over arrays on the host.
+ * Deviations: squelch_set_timeout(0) is YAGI_ERR_CONFIG (the reference's usize timer would underflow in SignalLo) and
+ * timeouts are below 2^32.  set_gain, set_gains, set_signal_level and set_scale accept v > 0 only, so a NaN is
+ * YAGI_ERR_CONFIG too (the reference tests `v <= 0.0`, which lets a NaN through); set_bandwidth rejects a NaN as the
+ * reference does.  Otherwise non-finite samples follow the loop as written: a NaN in y2' stays there and
+ * freezes g; such samples change only their own channel.
+ *   create(channels)          bandwidth 0.01, scale 1, squelch disabled, threshold 0, timeout 100 (:37-58);
+ *                             1 <= channels <= YAGI_AGC_CHANNELS_MAX, decided before any device is asked for
+ *   destroy / clone / set_stream / reset / reset_channel(c)
+ *   lock / unlock             every channel;  is_locked: 1 where every channel is locked
+ *   set_locked(locked[channels]) / get_locked(locked[channels])   per channel, nonzero = locked
+ *   set_bandwidth(bt) / get_bandwidth   bt in [0, 1], alpha = bt;  set_scale / get_scale   scale > 0
+ *   set_gain(g) (g > 0; y2' stays) / set_signal_level(x2) (x2 > 0: g = 1 / x2, y2' = 1) / set_rssi(rssi) (g =
+ *                             maxNum(10^(-rssi / 20), 1e-16), y2' = 1): every channel
+ *   set_gains(g[channels])    per channel, all > 0
+ *   get_gain(g[channels]) / get_signal_level (1 / g) / get_rssi (-20 yg_log10f(g))   they synchronise
+ *   squelch_enable (every mode = Enabled) / squelch_disable / squelch_is_enabled
+ *   squelch_set_threshold / squelch_get_threshold, squelch_set_timeout / squelch_get_timeout
+ *   squelch_get_status(mode[channels])   YAGI_AGC_SQUELCH_*; synchronises
+ *   init(x, x_pitch, n) / init_dev   n = 0 is YAGI_ERR_CONFIG; they synchronise
+ *   execute_block(x, x_pitch, n, y, y_pitch, status, status_pitch)   host slices, staged through the device
+ *   execute_block_dev(...)    device pointers, asynchronous on the object's stream.  status = uint8_t [n][status_pitch],
+ *                             the squelch mode after each sample, or NULL
+ *   execute_host(channels, bandwidth, scale, g0, locked, squelch, threshold, timeout, x, x_pitch, n, y, y_pitch, status,
+ *                status_pitch, g_out, mode_out)   the definition on the host alone, one call from reset() followed by
+ *                             set_gain(g0); no device needed; status, g_out[channels], mode_out[channels] may be NULL
+ * The pitches are in elements and >= channels; n is below 2^31; n = 0 touches nothing.  y == x with y_pitch == x_pitch
+ * runs in place; any other overlap of x and y, and any overlap of the status plane with x or y, is YAGI_ERR_CONFIG.
+ * Not built: per-channel bandwidths or thresholds, a time-parallel form, SymTrack.
+ * Device form: agc_kernels.hip: one lane per channel, one wave per workgroup. */
+#define YAGI_AGC_CHANNELS_MAX 1048576
+enum {
+    YAGI_AGC_SQUELCH_DISABLED = 0, YAGI_AGC_SQUELCH_ENABLED, YAGI_AGC_SQUELCH_RISE, YAGI_AGC_SQUELCH_SIGNALHI,
+    YAGI_AGC_SQUELCH_FALL, YAGI_AGC_SQUELCH_SIGNALLO, YAGI_AGC_SQUELCH_TIMEOUT
+};
+int yagi_hip_lnf(const float *x, size_t n, float *y);
+int yagi_hip_expf(const float *x, size_t n, float *y);
+int yagi_hip_log10f(const float *x, size_t n, float *y);
+#define YAGI_HIP_AGC_DECL(K, T)                                                                                          \
+    typedef struct yagi_hip_agc_##K##_s *yagi_hip_agc_##K;                                                               \
+    int yagi_hip_agc_##K##_create(size_t channels, yagi_hip_agc_##K *q);                                                 \
+    int yagi_hip_agc_##K##_destroy(yagi_hip_agc_##K q);                                                                  \
+    int yagi_hip_agc_##K##_clone(yagi_hip_agc_##K q, yagi_hip_agc_##K *out);                                             \
+    int yagi_hip_agc_##K##_set_stream(yagi_hip_agc_##K q, yagi_stream_t s);                                              \
+    int yagi_hip_agc_##K##_reset(yagi_hip_agc_##K q);                                                                    \
+    int yagi_hip_agc_##K##_reset_channel(yagi_hip_agc_##K q, size_t c);                                                  \
+    int yagi_hip_agc_##K##_lock(yagi_hip_agc_##K q);                                                                     \
+    int yagi_hip_agc_##K##_unlock(yagi_hip_agc_##K q);                                                                   \
+    int yagi_hip_agc_##K##_is_locked(yagi_hip_agc_##K q, int *locked);                                                   \
+    int yagi_hip_agc_##K##_set_locked(yagi_hip_agc_##K q, const uint8_t *locked);                                        \
+    int yagi_hip_agc_##K##_get_locked(yagi_hip_agc_##K q, uint8_t *locked);                                              \
+    int yagi_hip_agc_##K##_set_bandwidth(yagi_hip_agc_##K q, float bt);                                                  \
+    int yagi_hip_agc_##K##_get_bandwidth(yagi_hip_agc_##K q, float *bt);                                                 \
+    int yagi_hip_agc_##K##_set_scale(yagi_hip_agc_##K q, float scale);                                                   \
+    int yagi_hip_agc_##K##_get_scale(yagi_hip_agc_##K q, float *scale);                                                  \
+    int yagi_hip_agc_##K##_set_gain(yagi_hip_agc_##K q, float gain);                                                     \
+    int yagi_hip_agc_##K##_set_signal_level(yagi_hip_agc_##K q, float x2);                                               \
+    int yagi_hip_agc_##K##_set_rssi(yagi_hip_agc_##K q, float rssi);                                                     \
+    int yagi_hip_agc_##K##_set_gains(yagi_hip_agc_##K q, const float *gain);                                             \
+    int yagi_hip_agc_##K##_get_gain(yagi_hip_agc_##K q, float *gain);                                                    \
+    int yagi_hip_agc_##K##_get_signal_level(yagi_hip_agc_##K q, float *level);                                           \
+    int yagi_hip_agc_##K##_get_rssi(yagi_hip_agc_##K q, float *rssi);                                                    \
+    int yagi_hip_agc_##K##_get_channels(yagi_hip_agc_##K q, size_t *channels);                                           \
+    int yagi_hip_agc_##K##_squelch_enable(yagi_hip_agc_##K q);                                                           \
+    int yagi_hip_agc_##K##_squelch_disable(yagi_hip_agc_##K q);                                                          \
+    int yagi_hip_agc_##K##_squelch_is_enabled(yagi_hip_agc_##K q, int *enabled);                                         \
+    int yagi_hip_agc_##K##_squelch_set_threshold(yagi_hip_agc_##K q, float threshold);                                   \
+    int yagi_hip_agc_##K##_squelch_get_threshold(yagi_hip_agc_##K q, float *threshold);                                  \
+    int yagi_hip_agc_##K##_squelch_set_timeout(yagi_hip_agc_##K q, uint64_t timeout);                                    \
+    int yagi_hip_agc_##K##_squelch_get_timeout(yagi_hip_agc_##K q, uint64_t *timeout);                                   \
+    int yagi_hip_agc_##K##_squelch_get_status(yagi_hip_agc_##K q, uint8_t *mode);                                        \
+    int yagi_hip_agc_##K##_init(yagi_hip_agc_##K q, const T *x, size_t x_pitch, size_t n);                               \
+    int yagi_hip_agc_##K##_init_dev(yagi_hip_agc_##K q, const T *x_dev, size_t x_pitch, size_t n);                       \
+    int yagi_hip_agc_##K##_execute_block(yagi_hip_agc_##K q, const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch, \
+                                         uint8_t *status, size_t status_pitch);                                          \
+    int yagi_hip_agc_##K##_execute_block_dev(yagi_hip_agc_##K q, const T *x_dev, size_t x_pitch, size_t n, T *y_dev,     \
+                                             size_t y_pitch, uint8_t *status_dev, size_t status_pitch);                  \
+    int yagi_hip_agc_##K##_execute_host(size_t channels, float bandwidth, float scale, float g0, int locked, int squelch, \
+                                        float threshold, uint64_t timeout, const T *x, size_t x_pitch, size_t n, T *y,   \
+                                        size_t y_pitch, uint8_t *status, size_t status_pitch, float *g_out,              \
+                                        uint8_t *mode_out);
+YAGI_HIP_AGC_DECL(crcf, yagi_cf32)
+YAGI_HIP_AGC_DECL(rrrf, float)
+#undef YAGI_HIP_AGC_DECL
+
 /* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */
 

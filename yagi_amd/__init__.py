@@ -43,7 +43,7 @@ __all__ = [
     "Plan", "SpgramPlan", "plan_spgram", "MsResamp2Plan", "Resamp2Plan", "plan_msresamp2", "plan_resamp2", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
-    "estimate_req_filter_stopband_attenuation", "SymStream", "SymStreamR", "SymStreamRPlan", "plan_symstreamr", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
+    "estimate_req_filter_stopband_attenuation", "Agc", "AgcSquelchMode", "AGC_CHANNELS_MAX", "lnf", "expf", "log10f", "SymStream", "SymStreamR", "SymStreamRPlan", "plan_symstreamr", "device_count", "synchronize", "gen_complex_dev", "gen_real_dev",
 ]
 
 
@@ -2458,6 +2458,227 @@ class EqLms(_Handle):
             None if d is None else _ptr(d), d_pitch, None if table is None else _ptr(table),
             0 if table is None else table.size, _ptr(y), y_pitch, _ptr(w0)))
         return y, w0
+
+
+AGC_CHANNELS_MAX = 1 << 20         # YAGI_AGC_CHANNELS_MAX
+
+
+class AgcSquelchMode(enum.IntEnum):
+    """agc::AgcSquelchMode (src/agc/agc.rs:22-31), numbered as YAGI_AGC_SQUELCH_*"""
+    DISABLED = 0
+    ENABLED = 1
+    RISE = 2
+    SIGNALHI = 3
+    FALL = 4
+    SIGNALLO = 5
+    TIMEOUT = 6
+
+
+def _word(name, x):
+    x = _arr(x, np.float32)
+    y = np.empty_like(x)
+    _check(getattr(lib, "yagi_hip_" + name)(_ptr(x), x.size, _ptr(y)))
+    return y
+
+
+def lnf(x):
+    """the library's ln in f32 (yagi_hip.h, the Agc block), elementwise on the host"""
+    return _word("lnf", x)
+
+
+def expf(x):
+    """the library's exp in f32, elementwise on the host"""
+    return _word("expf", x)
+
+
+def log10f(x):
+    """the library's log10 in f32, elementwise on the host"""
+    return _word("log10f", x)
+
+
+class Agc(_Handle):
+    """Agc(channels, kind="crcf"): `channels` independent agc::Agc<T> objects of one set of settings (src/agc/agc.rs), T =
+    Complex<f32> ("crcf") or f32 ("rrrf").  A block is x[n, channels] (step, channel); per channel every output word, gain
+    and squelch mode is the reference's sequential loop bit for bit, with the library's own ln, exp and log10 (lnf, expf,
+    log10f) where the reference calls the platform's (yagi_hip.h).  A locked channel's output is not scaled, as in the
+    reference.  The block calls run agc_kernels.hip, one lane per channel.  channels <= AGC_CHANNELS_MAX."""
+
+    def __init__(self, channels, kind="crcf"):
+        if kind not in ("crcf", "rrrf"):
+            raise ConfigError(f"unknown type combination {kind!r}")
+        channels = _symsync_size(channels, "channels")
+        self._prefix = f"yagi_hip_agc_{kind}_"
+        hd = C.c_void_p()
+        _check(self._fn("create")(channels, C.byref(hd)))
+        self._set(hd, kind, channels)
+
+    def _set(self, hd, kind, channels):
+        self._prefix = f"yagi_hip_agc_{kind}_"
+        self._h, self.kind, self.T, self.channels = hd, kind, KINDS[kind][0], channels
+
+    def clone(self):
+        new, hd = object.__new__(type(self)), C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._set(hd, self.kind, self.channels)
+        return new
+
+    def reset_channel(self, c):
+        _check(self._fn("reset_channel")(self._h, _symsync_size(c, "channel")))
+
+    def _call(self, name, *args):
+        _check(self._fn(name)(self._h, *args))
+
+    def _get(self, name, ctype):
+        v = ctype()
+        _check(self._fn(name)(self._h, C.byref(v)))
+        return v.value
+
+    def _per_channel(self, name, dt):
+        out = np.zeros(self.channels, dt)
+        _check(self._fn(name)(self._h, _ptr(out)))
+        return out
+
+    def _vector(self, v, dt, what):
+        v = _arr(v, dt)
+        if v.shape != (self.channels,):
+            raise ConfigError(f"{what} holds one value per channel")
+        return v
+
+    def lock(self):
+        self._call("lock")
+
+    def unlock(self):
+        self._call("unlock")
+
+    def is_locked(self):
+        """True where every channel is locked"""
+        return bool(self._get("is_locked", C.c_int))
+
+    def set_locked(self, locked):
+        """locked[channels], nonzero = locked"""
+        self._call("set_locked", _ptr(self._vector(np.asarray(locked) != 0, np.uint8, "locked")))
+
+    def get_locked(self):
+        return self._per_channel("get_locked", np.uint8)
+
+    def set_bandwidth(self, bt):
+        self._call("set_bandwidth", bt)
+
+    def get_bandwidth(self):
+        return self._get("get_bandwidth", C.c_float)
+
+    def set_scale(self, scale):
+        self._call("set_scale", scale)
+
+    def get_scale(self):
+        return self._get("get_scale", C.c_float)
+
+    def set_gain(self, gain):
+        self._call("set_gain", gain)
+
+    def set_gains(self, gain):
+        self._call("set_gains", _ptr(self._vector(gain, np.float32, "gain")))
+
+    def set_signal_level(self, x2):
+        self._call("set_signal_level", x2)
+
+    def set_rssi(self, rssi):
+        self._call("set_rssi", rssi)
+
+    def get_gain(self):
+        """g[channels]; synchronises"""
+        return self._per_channel("get_gain", np.float32)
+
+    def get_signal_level(self):
+        return self._per_channel("get_signal_level", np.float32)
+
+    def get_rssi(self):
+        return self._per_channel("get_rssi", np.float32)
+
+    def squelch_enable(self):
+        self._call("squelch_enable")
+
+    def squelch_disable(self):
+        self._call("squelch_disable")
+
+    def squelch_is_enabled(self):
+        return bool(self._get("squelch_is_enabled", C.c_int))
+
+    def squelch_set_threshold(self, threshold):
+        self._call("squelch_set_threshold", threshold)
+
+    def squelch_get_threshold(self):
+        return self._get("squelch_get_threshold", C.c_float)
+
+    def squelch_set_timeout(self, timeout):
+        self._call("squelch_set_timeout", _symsync_size(timeout, "timeout"))
+
+    def squelch_get_timeout(self):
+        return self._get("squelch_get_timeout", C.c_uint64)
+
+    def squelch_get_status(self):
+        """AgcSquelchMode numbers, [channels]; synchronises"""
+        return self._per_channel("squelch_get_status", np.uint8)
+
+    def _block(self, x):
+        x = _arr(x, self.T)
+        if x.ndim != 2 or x.shape[1] != self.channels:
+            raise ConfigError(f"the block is [steps, {self.channels}]")
+        return x
+
+    def init(self, x):
+        """Agc::init (:171-178) per channel on x[n, channels]"""
+        x = self._block(x)
+        self._call("init", _ptr(x), self.channels, x.shape[0])
+
+    def init_devptr(self, x_dev, x_pitch, n):
+        self._call("init_dev", None if x_dev is None else _devptr(x_dev), x_pitch, n)
+
+    def execute_block(self, x, status=False):
+        """x[n, channels] -> y[n, channels], or (y, mode[n, channels]) with status: the squelch mode after each sample"""
+        x = self._block(x)
+        y = np.zeros_like(x)
+        st = np.zeros(x.shape, np.uint8) if status else None
+        self._call("execute_block", _ptr(x), self.channels, x.shape[0], _ptr(y), self.channels,
+                   None if st is None else _ptr(st), self.channels)
+        return (y, st) if status else y
+
+    def execute_block_devptr(self, x_dev, x_pitch, n, y_dev, y_pitch, status_dev=None, status_pitch=0):
+        """x_dev, y_dev: n rows of pitch x_pitch, y_pitch elements (y_dev may be x_dev at the same pitch); status_dev: n
+        rows of status_pitch bytes or None.  Asynchronous on the object's stream (the C ABI's execute_block_dev)"""
+        x_dev, y_dev, status_dev = (None if p is None else _devptr(p) for p in (x_dev, y_dev, status_dev))
+        self._call("execute_block_dev", x_dev, x_pitch, n, y_dev, y_pitch, status_dev, status_pitch)
+
+    @staticmethod
+    def execute_host(channels, bandwidth, scale, g0, locked, squelch, threshold, timeout, x, kind="crcf", status=False,
+                     x_pitch=None, y_pitch=None, status_pitch=None, y=None):
+        """the definition on the host alone, no device needed: one call from reset() followed by set_gain(g0).  x is
+        [n, x_pitch] (the pitches default to channels); y, where given, is the [n, y_pitch] array that is written
+        (y = x runs in place).  Returns (y, mode[n, status_pitch] or None, g[channels], mode[channels]).  The
+        library's own sequential form, slow and meant for checks"""
+        if kind not in ("crcf", "rrrf"):
+            raise ConfigError(f"unknown type combination {kind!r}")
+        T = KINDS[kind][0]
+        channels, timeout = _symsync_size(channels, "channels"), _symsync_size(timeout, "timeout")
+        if not 1 <= channels <= AGC_CHANNELS_MAX:
+            raise ConfigError("channels must be in 1 .. AGC_CHANNELS_MAX")
+        x_pitch, y_pitch, status_pitch = (channels if p is None else _symsync_size(p, "pitch")
+                                          for p in (x_pitch, y_pitch, status_pitch))
+        if not (isinstance(x, np.ndarray) and x.dtype == np.dtype(T) and x.flags.c_contiguous):
+            x = _arr(x, T)
+        if x.ndim != 2 or x.shape[1] != x_pitch:
+            raise ConfigError("the block is [steps, x_pitch]")
+        n = x.shape[0]
+        if y is None:
+            y = np.zeros((n, y_pitch), T)
+        elif not (isinstance(y, np.ndarray) and y.dtype == np.dtype(T) and y.flags.c_contiguous and y.shape == (n, y_pitch)):
+            raise ConfigError("y is a C-contiguous [steps, y_pitch] array of the block's type")
+        st = np.zeros((n, status_pitch), np.uint8) if status else None
+        g, mode = np.zeros(channels, np.float32), np.zeros(channels, np.uint8)
+        fn = getattr(lib, f"yagi_hip_agc_{kind}_execute_host")
+        _check(fn(channels, bandwidth, scale, g0, int(bool(locked)), int(bool(squelch)), threshold, timeout, _ptr(x),
+                  x_pitch, n, _ptr(y), y_pitch, None if st is None else _ptr(st), status_pitch, _ptr(g), _ptr(mode)))
+        return y, st, g, mode
 
 
 MSEQUENCE_TILE = 8192    # YAGI_MSEQUENCE_TILE: symbols per workgroup of the generator kernel

@@ -711,6 +711,35 @@ _sig(_p + "decim_block", vp, sz, ci, vp, sz, sz, vp, sz, vp, sz)
 _sig(_p + "decim_block_dev", vp, sz, ci, vp, sz, sz, vp, sz, vp, sz)
 _sig(_p + "execute_host", sz, vp, sz, f32, ci, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz, vp)
 
+# ---- Agc ---------------------------------------------------------------------------------------
+u8p = C.POINTER(C.c_uint8)
+for _n in ("lnf", "expf", "log10f"):
+    _sig("yagi_hip_" + _n, vp, sz, vp)
+for _k in ("crcf", "rrrf"):
+    _p = f"yagi_hip_agc_{_k}_"
+    _sig(_p + "create", sz, pvp)
+    _sig(_p + "clone", vp, pvp)
+    _sig(_p + "set_stream", vp, vp)
+    _sig(_p + "reset_channel", vp, sz)
+    for _n in ("destroy", "reset", "lock", "unlock", "squelch_enable", "squelch_disable"):
+        _sig(_p + _n, vp)
+    for _n in ("is_locked", "squelch_is_enabled"):
+        _sig(_p + _n, vp, C.POINTER(ci))
+    for _n in ("set_locked", "get_locked", "set_gains", "get_gain", "get_signal_level", "get_rssi", "squelch_get_status"):
+        _sig(_p + _n, vp, vp)
+    for _n in ("set_bandwidth", "set_scale", "set_gain", "set_signal_level", "set_rssi", "squelch_set_threshold"):
+        _sig(_p + _n, vp, f32)
+    for _n in ("get_bandwidth", "get_scale", "squelch_get_threshold"):
+        _sig(_p + _n, vp, C.POINTER(f32))
+    _sig(_p + "get_channels", vp, C.POINTER(sz))
+    _sig(_p + "squelch_set_timeout", vp, u64)
+    _sig(_p + "squelch_get_timeout", vp, C.POINTER(u64))
+    for _n in ("init", "init_dev"):
+        _sig(_p + _n, vp, vp, sz, sz)
+    for _n in ("execute_block", "execute_block_dev"):
+        _sig(_p + _n, vp, vp, sz, sz, vp, sz, vp, sz)
+    _sig(_p + "execute_host", sz, f32, f32, f32, ci, ci, f32, u64, vp, sz, sz, vp, sz, vp, sz, vp, vp)
+
 # ---- SymStream ---------------------------------------------------------------------------------
 _p = "yagi_hip_symstreamcf_"
 _sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)

@@ -7469,6 +7469,407 @@ int yagi_hip_eqlms_cccf_execute_host(size_t channels, const cf32 *h, size_t h_le
 
 }  // extern "C"
 
+// ---- Agc (src/agc/agc.rs, one object per channel) ------------------------------------------------------------------
+// The state is one AgcChan per channel; agc_kernels.hip updates it in place on the device.  reset, the setters and getters
+// that touch g, the locks and the squelch modes work on a host mirror; the two copies are synchronised lazily (Mirror).
+// alpha, scale, threshold and timeout travel to the kernel by value with every call.
+namespace yagi {
+
+template <class T>
+struct AgcObj {
+    hipStream_t st = nullptr;
+    size_t C = 0;
+    AgcSettings g;
+    DevBuf state_dev, sum_dev, stat_dev;
+    std::vector<AgcChan> hs;                              // host mirror
+    Mirror mirror;
+    Staging ws;                                           // host block forms: x and a compact y (stat_dev: the status)
+
+    static void reset_chan(AgcChan &s) {                  // reset (:60-69)
+        s.g = 1.0f, s.y2p = 1.0f, s.locked = 0;
+        s.mode = s.mode == YAGI_AGC_SQUELCH_DISABLED ? YAGI_AGC_SQUELCH_DISABLED : YAGI_AGC_SQUELCH_ENABLED;
+    }
+    // new (:37-58); everything that needs no device
+    int configure(size_t channels) {
+        if (channels == 0 || channels > (size_t)YAGI_AGC_CHANNELS_MAX)
+            return fail(YAGI_ERR_CONFIG, "agc: %zu channels are outside 1 .. YAGI_AGC_CHANNELS_MAX", channels);
+        C = channels;
+        g = AgcSettings{};
+        AgcChan s{};
+        s.mode = YAGI_AGC_SQUELCH_DISABLED;
+        reset_chan(s);
+        hs.assign(C, s);
+        return YAGI_OK;
+    }
+    int alloc() {
+        YG_TRY(require_device());
+        YG_TRY(state_dev.alloc(C * sizeof(AgcChan)));
+        YG_TRY(sum_dev.alloc(C * sizeof(float)));
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] { return download(hs.data(), state_dev.p, C * sizeof(AgcChan), st); });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] { return upload(state_dev.p, hs.data(), C * sizeof(AgcChan), st); });
+    }
+    template <class F>
+    int edit(F &&f) {                                       // f(AgcChan &, channel) on the host mirror
+        YG_TRY(ensure_host());
+        for (size_t c = 0; c < C; ++c) f(hs[c], c);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    static int check_bandwidth(float bt) {
+        if (!(bt >= 0.0f && bt <= 1.0f)) return fail(YAGI_ERR_CONFIG, "bandwidth must be in [0, 1]");
+        return YAGI_OK;
+    }
+    static int check_positive(float v, const char *what) {
+        if (!(v > 0.0f)) return fail(YAGI_ERR_CONFIG, "%s must be greater than zero", what);
+        return YAGI_OK;
+    }
+    static int check_timeout(uint64_t t) {
+        if (t == 0 || t >= ((uint64_t)1 << 32)) return fail(YAGI_ERR_CONFIG, "agc: the squelch timeout is in 1 .. 2^32 - 1");
+        return YAGI_OK;
+    }
+    static int check_rows(size_t C, size_t x_pitch, size_t n) {
+        if (n >= ((size_t)1 << 31)) return fail(YAGI_ERR_CONFIG, "agc: n must be below 2^31");
+        if (x_pitch < C) return fail(YAGI_ERR_CONFIG, "agc: the pitches are in elements, at least the channel count");
+        return YAGI_OK;
+    }
+    static int check_block(size_t C, const T *x, size_t x_pitch, size_t n, const T *y, size_t y_pitch, const uint8_t *status,
+                           size_t status_pitch) {
+        YG_TRY(check_rows(C, x_pitch, n));
+        if (y_pitch < C || (status && status_pitch < C))
+            return fail(YAGI_ERR_CONFIG, "agc: the pitches are in elements, at least the channel count");
+        if (n == 0) return YAGI_OK;
+        if (!x || !y) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y, sa = (uintptr_t)status;
+        const uintptr_t xe = xa + ((n - 1) * x_pitch + C) * sizeof(T), ye = ya + ((n - 1) * y_pitch + C) * sizeof(T);
+        const uintptr_t se = sa + (n - 1) * status_pitch + C;
+        if (status && ((sa < xe && xa < se) || (sa < ye && ya < se)))
+            return fail(YAGI_ERR_CONFIG, "agc: the status plane overlaps x or y");
+        if (x == y && x_pitch == y_pitch) return YAGI_OK;   // in place
+        if (xa < ye && ya < xe) return fail(YAGI_ERR_CONFIG, "agc: x and y overlap and are not the same block");
+        return YAGI_OK;
+    }
+    int block_dev(const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch, uint8_t *status, size_t status_pitch) {
+        if (n == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        YG_TRY(launch_agc<T>(g, state_dev.as<AgcChan>(), C, x, x_pitch, n, y, y_pitch, status, status_pitch, st));
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+    int block_host(const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch, uint8_t *status, size_t status_pitch) {
+        YG_TRY(check_block(C, x, x_pitch, n, y, y_pitch, status, status_pitch));
+        if (n == 0) return YAGI_OK;
+        YG_TRY(ws.put(st, x, (n - 1) * x_pitch + C));
+        YG_TRY(ws.y.ensure(n * C * sizeof(T)));
+        if (status) {
+            YG_TRY(stat_dev.ensure(n * C));
+        }
+        YG_TRY(block_dev(ws.x.template as<T>(), x_pitch, n, ws.y.template as<T>(), C, status ? stat_dev.as<uint8_t>() : nullptr, C));
+        std::vector<T> t(n * C);
+        YG_TRY(download(t.data(), ws.y.p, n * C * sizeof(T), st));
+        for (size_t j = 0; j < n; ++j) std::copy(t.begin() + j * C, t.begin() + (j + 1) * C, y + j * y_pitch);
+        if (status) {
+            std::vector<uint8_t> sb(n * C);
+            YG_TRY(download(sb.data(), stat_dev.p, n * C, st));
+            for (size_t j = 0; j < n; ++j) std::copy(sb.begin() + j * C, sb.begin() + (j + 1) * C, status + j * status_pitch);
+        }
+        return YAGI_OK;
+    }
+    static int check_init(size_t C, const T *x, size_t x_pitch, size_t n) {
+        if (n == 0) return fail(YAGI_ERR_CONFIG, "number of samples must be greater than zero");
+        YG_TRY(check_rows(C, x_pitch, n));
+        if (!x) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        return YAGI_OK;
+    }
+    int init_dev(const T *x, size_t x_pitch, size_t n) {    // init (:171-178)
+        YG_TRY(launch_agc_init<T>(x, x_pitch, n, C, sum_dev.as<float>(), st));
+        std::vector<float> sum(C);
+        YG_TRY(download(sum.data(), sum_dev.p, C * sizeof(float), st));
+        return edit([&](AgcChan &s, size_t c) { s.g = agc_level_gain(sum[c], n), s.y2p = 1.0f; });
+    }
+};
+
+}  // namespace yagi
+
+#define YAGI_AGC_API(K, T)                                                                          \
+    struct yagi_hip_agc_##K##_s : AgcObj<T> {};                                                     \
+    extern "C" {                                                                                    \
+    int yagi_hip_agc_##K##_create(size_t channels, yagi_hip_agc_##K *q) try {                       \
+        CHECK_PTR(q);                                                                               \
+        *q = nullptr;                                                                               \
+        auto o = std::make_unique<yagi_hip_agc_##K##_s>();                                          \
+        YG_TRY(o->configure(channels));                                                             \
+        YG_TRY(o->alloc());                                                                         \
+        *q = o.release();                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_destroy(yagi_hip_agc_##K q) try {                                        \
+        if (q) (void)hipStreamSynchronize(q->st);                                                   \
+        delete q;                                                                                   \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_clone(yagi_hip_agc_##K q, yagi_hip_agc_##K *out) try {                   \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        *out = nullptr;                                                                             \
+        YG_TRY(q->ensure_host());                                                                   \
+        auto o = std::make_unique<yagi_hip_agc_##K##_s>();                                          \
+        o->st = q->st, o->C = q->C, o->g = q->g, o->hs = q->hs;                                     \
+        YG_TRY(o->alloc());                                                                         \
+        *out = o.release();                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_set_stream(yagi_hip_agc_##K q, yagi_stream_t s) try {                    \
+        CHECK_Q(q);                                                                                 \
+        if (q->st == to_stream(s)) return YAGI_OK;                                                  \
+        YG_HIP(hipStreamSynchronize(q->st));                                                        \
+        q->st = to_stream(s);                                                                       \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_reset(yagi_hip_agc_##K q) try {                                          \
+        CHECK_Q(q);                                                                                 \
+        return q->edit([](AgcChan &s, size_t) { AgcObj<T>::reset_chan(s); });                       \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_reset_channel(yagi_hip_agc_##K q, size_t c) try {                        \
+        CHECK_Q(q);                                                                                 \
+        if (c >= q->C) return fail(YAGI_ERR_CONFIG, "agc: channel %zu of %zu", c, q->C);            \
+        return q->edit([c](AgcChan &s, size_t i) { if (i == c) AgcObj<T>::reset_chan(s); });        \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_lock(yagi_hip_agc_##K q) try {                                           \
+        CHECK_Q(q);                                                                                 \
+        return q->edit([](AgcChan &s, size_t) { s.locked = 1; });                                   \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_unlock(yagi_hip_agc_##K q) try {                                         \
+        CHECK_Q(q);                                                                                 \
+        return q->edit([](AgcChan &s, size_t) { s.locked = 0; });                                   \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_is_locked(yagi_hip_agc_##K q, int *locked) try {                         \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(locked);                                                                          \
+        YG_TRY(q->ensure_host());                                                                   \
+        *locked = 1;                                                                                \
+        for (const AgcChan &s : q->hs) *locked &= s.locked ? 1 : 0;                                 \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_set_locked(yagi_hip_agc_##K q, const uint8_t *locked) try {              \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(locked);                                                                          \
+        return q->edit([locked](AgcChan &s, size_t c) { s.locked = locked[c] ? 1 : 0; });           \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_get_locked(yagi_hip_agc_##K q, uint8_t *locked) try {                    \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(locked);                                                                          \
+        YG_TRY(q->ensure_host());                                                                   \
+        for (size_t c = 0; c < q->C; ++c) locked[c] = q->hs[c].locked;                              \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_set_bandwidth(yagi_hip_agc_##K q, float bt) try {                        \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(AgcObj<T>::check_bandwidth(bt));                                                     \
+        q->g.alpha = bt;                                                                            \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_get_bandwidth(yagi_hip_agc_##K q, float *bt) try {                       \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(bt);                                                                              \
+        *bt = q->g.alpha;                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_set_scale(yagi_hip_agc_##K q, float scale) try {                         \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(AgcObj<T>::check_positive(scale, "scale"));                                          \
+        q->g.scale = scale;                                                                         \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_get_scale(yagi_hip_agc_##K q, float *scale) try {                        \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(scale);                                                                           \
+        *scale = q->g.scale;                                                                        \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_set_gain(yagi_hip_agc_##K q, float gain) try {                           \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(AgcObj<T>::check_positive(gain, "gain"));                                            \
+        return q->edit([gain](AgcChan &s, size_t) { s.g = gain; });                                 \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_set_signal_level(yagi_hip_agc_##K q, float x2) try {                     \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(AgcObj<T>::check_positive(x2, "signal level"));                                      \
+        const float gain = 1.0f / x2;                                                               \
+        return q->edit([gain](AgcChan &s, size_t) { s.g = gain, s.y2p = 1.0f; });                   \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_set_rssi(yagi_hip_agc_##K q, float rssi) try {                           \
+        CHECK_Q(q);                                                                                 \
+        const float gain = agc_rssi_gain(rssi);                                                     \
+        return q->edit([gain](AgcChan &s, size_t) { s.g = gain, s.y2p = 1.0f; });                   \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_set_gains(yagi_hip_agc_##K q, const float *gain) try {                   \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(gain);                                                                            \
+        for (size_t c = 0; c < q->C; ++c) YG_TRY(AgcObj<T>::check_positive(gain[c], "gain"));       \
+        return q->edit([gain](AgcChan &s, size_t c) { s.g = gain[c]; });                            \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_get_gain(yagi_hip_agc_##K q, float *gain) try {                          \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(gain);                                                                            \
+        YG_TRY(q->ensure_host());                                                                   \
+        for (size_t c = 0; c < q->C; ++c) gain[c] = q->hs[c].g;                                     \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_get_signal_level(yagi_hip_agc_##K q, float *level) try {                 \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(level);                                                                           \
+        YG_TRY(q->ensure_host());                                                                   \
+        for (size_t c = 0; c < q->C; ++c) level[c] = 1.0f / q->hs[c].g;                             \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_get_rssi(yagi_hip_agc_##K q, float *rssi) try {                          \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(rssi);                                                                            \
+        YG_TRY(q->ensure_host());                                                                   \
+        for (size_t c = 0; c < q->C; ++c) rssi[c] = agc_rssi(q->hs[c].g);                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_get_channels(yagi_hip_agc_##K q, size_t *channels) try {                 \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(channels);                                                                        \
+        *channels = q->C;                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_squelch_enable(yagi_hip_agc_##K q) try {                                 \
+        CHECK_Q(q);                                                                                 \
+        q->g.squelch = true;                                                                        \
+        return q->edit([](AgcChan &s, size_t) { s.mode = YAGI_AGC_SQUELCH_ENABLED; });              \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_squelch_disable(yagi_hip_agc_##K q) try {                                \
+        CHECK_Q(q);                                                                                 \
+        q->g.squelch = false;                                                                       \
+        return q->edit([](AgcChan &s, size_t) { s.mode = YAGI_AGC_SQUELCH_DISABLED; });             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_squelch_is_enabled(yagi_hip_agc_##K q, int *enabled) try {               \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(enabled);                                                                         \
+        *enabled = q->g.squelch ? 1 : 0;                                                            \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_squelch_set_threshold(yagi_hip_agc_##K q, float threshold) try {         \
+        CHECK_Q(q);                                                                                 \
+        q->g.threshold = threshold;                                                                 \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_squelch_get_threshold(yagi_hip_agc_##K q, float *threshold) try {        \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(threshold);                                                                       \
+        *threshold = q->g.threshold;                                                                \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_squelch_set_timeout(yagi_hip_agc_##K q, uint64_t timeout) try {          \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(AgcObj<T>::check_timeout(timeout));                                                  \
+        q->g.timeout = (unsigned)timeout;                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_squelch_get_timeout(yagi_hip_agc_##K q, uint64_t *timeout) try {         \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(timeout);                                                                         \
+        *timeout = q->g.timeout;                                                                    \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_squelch_get_status(yagi_hip_agc_##K q, uint8_t *mode) try {              \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(mode);                                                                            \
+        YG_TRY(q->ensure_host());                                                                   \
+        for (size_t c = 0; c < q->C; ++c) mode[c] = q->hs[c].mode;                                  \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_init(yagi_hip_agc_##K q, const T *x, size_t x_pitch, size_t n) try {     \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(AgcObj<T>::check_init(q->C, x, x_pitch, n));                                         \
+        YG_TRY(q->ws.put(q->st, x, (n - 1) * x_pitch + q->C));                                      \
+        return q->init_dev(q->ws.x.as<T>(), x_pitch, n);                                            \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_init_dev(yagi_hip_agc_##K q, const T *x_dev, size_t x_pitch, size_t n) try { \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(AgcObj<T>::check_init(q->C, x_dev, x_pitch, n));                                     \
+        return q->init_dev(x_dev, x_pitch, n);                                                      \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_execute_block(yagi_hip_agc_##K q, const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch, \
+                                         uint8_t *status, size_t status_pitch) try {                \
+        CHECK_Q(q);                                                                                 \
+        return q->block_host(x, x_pitch, n, y, y_pitch, status, status_pitch);                      \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_execute_block_dev(yagi_hip_agc_##K q, const T *x_dev, size_t x_pitch, size_t n, T *y_dev, \
+                                             size_t y_pitch, uint8_t *status_dev, size_t status_pitch) try { \
+        CHECK_Q(q);                                                                                 \
+        YG_TRY(AgcObj<T>::check_block(q->C, x_dev, x_pitch, n, y_dev, y_pitch, status_dev, status_pitch)); \
+        return q->block_dev(x_dev, x_pitch, n, y_dev, y_pitch, status_dev, status_pitch);           \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    int yagi_hip_agc_##K##_execute_host(size_t channels, float bandwidth, float scale, float g0, int locked, int squelch, \
+                                        float threshold, uint64_t timeout, const T *x, size_t x_pitch, size_t n, T *y, \
+                                        size_t y_pitch, uint8_t *status, size_t status_pitch, float *g_out, \
+                                        uint8_t *mode_out) try {                                    \
+        AgcObj<T> o;                                                                                \
+        YG_TRY(o.configure(channels));                                                              \
+        YG_TRY(AgcObj<T>::check_bandwidth(bandwidth));                                              \
+        YG_TRY(AgcObj<T>::check_positive(scale, "scale"));                                          \
+        YG_TRY(AgcObj<T>::check_positive(g0, "gain"));                                              \
+        YG_TRY(AgcObj<T>::check_timeout(timeout));                                                  \
+        YG_TRY(AgcObj<T>::check_block(channels, x, x_pitch, n, y, y_pitch, status, status_pitch));  \
+        o.g.alpha = bandwidth, o.g.scale = scale, o.g.threshold = threshold, o.g.timeout = (unsigned)timeout; \
+        o.g.squelch = squelch != 0;                                                                 \
+        for (AgcChan &s : o.hs) {                                                                   \
+            s.g = g0, s.locked = locked ? 1 : 0;                                                    \
+            s.mode = squelch ? YAGI_AGC_SQUELCH_ENABLED : YAGI_AGC_SQUELCH_DISABLED;                \
+        }                                                                                           \
+        agc_host<T>(o.g, o.hs.data(), channels, x, x_pitch, n, y, y_pitch, status, status_pitch);   \
+        for (size_t c = 0; c < channels; ++c) {                                                     \
+            if (g_out) g_out[c] = o.hs[c].g;                                                        \
+            if (mode_out) mode_out[c] = o.hs[c].mode;                                               \
+        }                                                                                           \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }                                               \
+    }
+
+YAGI_AGC_API(crcf, cf32)
+YAGI_AGC_API(rrrf, float)
+#undef YAGI_AGC_API
+
+extern "C" {
+
+int yagi_hip_lnf(const float *x, size_t n, float *y) try {
+    if (n != 0) {
+        CHECK_PTR(x);
+        CHECK_PTR(y);
+    }
+    yagi::agc_words_host(0, x, n, y);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_expf(const float *x, size_t n, float *y) try {
+    if (n != 0) {
+        CHECK_PTR(x);
+        CHECK_PTR(y);
+    }
+    yagi::agc_words_host(1, x, n, y);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_log10f(const float *x, size_t n, float *y) try {
+    if (n != 0) {
+        CHECK_PTR(x);
+        CHECK_PTR(y);
+    }
+    yagi::agc_words_host(2, x, n, y);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

@@ -670,6 +670,40 @@ void eqlms_host(int call, size_t h_len, float mu, cf32 *w, cf32 *hist, EqlmsChan
                 size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, const cf32 *table, size_t M, cf32 *y,
                 size_t y_pitch);
 
+// ---- agc_kernels.hip -----------------------------------------------------------------------
+// Agc (yagi_hip.h): C independent Agc<T> loops of one set of settings, one lane per channel, T = cf32 or float.  state is
+// one AgcChan per channel, updated in place.  n rows in, n rows out; status (may be null) receives the squelch mode after
+// every sample, one byte each.  y may be x at the same pitch.
+constexpr int kAgcWg = 64;                             // channels per workgroup: one wave
+constexpr int kAgcAhead = 8;                           // input rows per chunk: requested one chunk ahead, in registers
+struct AgcChan {
+    float g, y2p;                                      // the gain and the smoothed output energy y2'
+    unsigned timer;                                    // squelch_timer
+    uint8_t mode, locked, pad[2];                      // YAGI_AGC_SQUELCH_*; is_locked
+};
+static_assert(sizeof(AgcChan) == 16, "device layout");
+struct AgcSettings {
+    float alpha = 1e-2f, scale = 1.0f, threshold = 0.0f;
+    unsigned timeout = 100;
+    bool squelch = false;                              // every channel's mode is Disabled exactly when this is false
+};
+template <class T>
+int launch_agc(const AgcSettings &g, AgcChan *state, size_t C, const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch,
+               uint8_t *status, size_t status_pitch, hipStream_t st);
+// sum[c] = the f32 sum of |x[i x_pitch + c]|^2 over i < n, in row order
+template <class T>
+int launch_agc_init(const T *x, size_t x_pitch, size_t n, size_t C, float *sum, hipStream_t st);
+// the same on the host, channel after channel
+template <class T>
+void agc_host(const AgcSettings &g, AgcChan *state, size_t C, const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch,
+              uint8_t *status, size_t status_pitch);
+template <class T>
+void agc_init_host(const T *x, size_t x_pitch, size_t n, size_t C, float *sum);
+float agc_level_gain(float sum, size_t n);             // init: 1 / (sqrt(sum / n) + 1e-16)
+float agc_rssi_gain(float rssi);                       // set_rssi: max(10^(-rssi / 20), 1e-16)
+float agc_rssi(float g);                               // get_rssi: -20 yg_log10f(g)
+void agc_words_host(int word, const float *x, size_t n, float *y);   // word 0 yg_lnf, 1 yg_expf, 2 yg_log10f
+
 // ---- symstream_kernels.hip -----------------------------------------------------------------
 // SymStream (yagi_hip.h): samples [0, n) of a call that starts at buf_index p, from the carried window `win` (Ls values,
 // oldest first) and new symbols that come either from the caller's bytes (sym, flag = the result of
