@@ -6190,89 +6190,74 @@ static int burstdet_check_window(size_t W, size_t d) {
     return YAGI_OK;
 }
 
-template <class T>
-struct BurstDetObj {
+// What the event detectors share: the threshold settings, the history and the State {position, pool_used, has_pending,
+// pending} on the host and on the device, and the calls that move them.  D, the object itself, supplies the history
+// length (to alloc_state), most_events(nb) and block_dev(x, nb, events, cap, status).
+template <class D, class T, class State, class Ev>
+struct EventDetObj {
     hipStream_t st = nullptr;
-    int W = 0, d = 0;
     float threshold = 0.0f, thr2 = 0.0f, floor_ = 0.0f;
     uint64_t min_length = 1;
     FdHist<T> win;                                        // host mirror: the history
-    BurstState hs{};                                      //              counter and pending run
-    PingPong<> hist;                                      // device copy, W + d samples
-    DevBuf state;                                         //              one BurstState
+    State hs{};                                           //              counter and pending run
+    PingPong<> hist;                                      // device copy of the history
+    DevBuf state;                                         //              one State
     DevBuf scratch;                                       // tile table and segment pool, grown with the block length
     Staging ws;                                           // host block form: x; y holds {status, events}
     Mirror mirror;
 
-    size_t len() const { return (size_t)W + (size_t)d; }
-    size_t bytes() const { return len() * sizeof(T); }
-    int configure(size_t W_, size_t d_, float threshold_, float floor__, uint64_t min_length_) {
-        YG_TRY(burstdet_check_window(W_, d_));
+    size_t bytes() const { return win.len * sizeof(T); }
+    int set_threshold(float threshold_, float floor__, uint64_t min_length_) {
         YG_TRY(burstdet_check(threshold_, floor__, min_length_));
-        W = (int)W_;
-        d = (int)d_;
         threshold = threshold_;
         thr2 = threshold_ * threshold_;
         floor_ = floor__;
         min_length = min_length_;
         return YAGI_OK;
     }
-    int alloc() {
+    int alloc_state(size_t len) {
         YG_TRY(require_device());
-        YG_TRY(hist.alloc(bytes()));
-        YG_TRY(state.alloc(sizeof(BurstState)));
-        win.init(len());
+        YG_TRY(hist.alloc(len * sizeof(T)));
+        YG_TRY(state.alloc(sizeof(State)));
+        win.init(len);
         return YAGI_OK;
     }
     int reset() {
         win.zero();
-        hs = BurstState{};
+        hs = State{};
         YG_HIP(hipMemsetAsync(hist.cur(), 0, bytes(), st));
-        YG_HIP(hipMemsetAsync(state.p, 0, sizeof(BurstState), st));
+        YG_HIP(hipMemsetAsync(state.p, 0, sizeof(State), st));
         mirror.in_sync();
         return YAGI_OK;
     }
     int ensure_host() {
         return mirror.need_host([&] {
-            std::vector<T> t(len());
+            std::vector<T> t(win.len);
             YG_TRY(download(t.data(), hist.cur(), bytes(), st));
             win.load(t.data());
-            return download(&hs, state.p, sizeof(BurstState), st);
+            return download(&hs, state.p, sizeof(State), st);
         });
     }
     int ensure_dev() {
         return mirror.need_dev([&] {
             YG_TRY(upload(hist.cur(), win.data(), bytes(), st));
-            return upload(state.p, &hs, sizeof(BurstState), st);
+            return upload(state.p, &hs, sizeof(State), st);
         });
     }
-    // events a call of nb samples can report: a run per segment, and the pending run of the call before
-    static size_t most_events(size_t nb) {
-        return (nb + kAutocorrTile - 1) / kAutocorrTile + (size_t)kBurstSegmax + 1;
-    }
-    int block_dev(const T *x, size_t nb, yagi_burst_event *events, size_t cap, unsigned *status) {
-        YG_TRY(ensure_dev());
-        YG_TRY(scratch.ensure(burstdet_scratch_bytes(nb)));
-        YG_TRY(launch_burstdet<T>(W, d, thr2, floor_, min_length, hist.cur<T>(), hist.next<T>(), x, nb, scratch.p,
-                                  state.as<BurstState>(), events, cap, status, st));
-        if (nb != 0) hist.flip();
-        mirror.dev_written();
-        return YAGI_OK;
-    }
-    int block(const T *x, size_t nb, yagi_burst_event *events, size_t cap, size_t *count, int *overflow) {
-        const size_t room = std::min(cap, most_events(nb));
+    int block(const T *x, size_t nb, Ev *events, size_t cap, size_t *count, int *overflow) {
+        const size_t room = std::min(cap, D::most_events(nb));
         YG_TRY(ws.put(st, x, nb));
-        YG_TRY(ws.y.ensure(16 + room * sizeof(yagi_burst_event)));
-        unsigned *sd = ws.y.as<unsigned>();
-        yagi_burst_event *ed = reinterpret_cast<yagi_burst_event *>(ws.y.as<char>() + 16);
-        YG_TRY(block_dev(ws.x.as<T>(), nb, ed, room, sd));
+        YG_TRY(ws.y.ensure(16 + room * sizeof(Ev)));
+        unsigned *sd = ws.y.template as<unsigned>();
+        Ev *ed = reinterpret_cast<Ev *>(ws.y.template as<char>() + 16);
+        YG_TRY(static_cast<D *>(this)->block_dev(ws.x.template as<T>(), nb, ed, room, sd));
         unsigned status[2];
         YG_TRY(download(status, sd, sizeof status, st));
         *count = status[0];
         *overflow = (int)status[1];
-        return download(events, ed, std::min((size_t)status[0], room) * sizeof(yagi_burst_event), st);
+        return download(events, ed, std::min((size_t)status[0], room) * sizeof(Ev), st);
     }
-    int flush(yagi_burst_event *events, size_t cap, size_t *count) {
+    int flush(Ev *events, size_t cap, size_t *count) {
         YG_TRY(ensure_host());
         *count = 0;
         if (!hs.has_pending) return YAGI_OK;
@@ -6282,6 +6267,34 @@ struct BurstDetObj {
         }
         hs.has_pending = 0;
         mirror.host_written();
+        return YAGI_OK;
+    }
+};
+
+template <class T>
+struct BurstDetObj : EventDetObj<BurstDetObj<T>, T, BurstState, yagi_burst_event> {
+    int W = 0, d = 0;                                     // the history is W + d samples
+
+    int configure(size_t W_, size_t d_, float threshold_, float floor__, uint64_t min_length_) {
+        YG_TRY(burstdet_check_window(W_, d_));
+        YG_TRY(this->set_threshold(threshold_, floor__, min_length_));
+        W = (int)W_;
+        d = (int)d_;
+        return YAGI_OK;
+    }
+    int alloc() { return this->alloc_state((size_t)W + (size_t)d); }
+    // events a call of nb samples can report: a run per segment, and the pending run of the call before
+    static size_t most_events(size_t nb) {
+        return (nb + kAutocorrTile - 1) / kAutocorrTile + (size_t)kBurstSegmax + 1;
+    }
+    int block_dev(const T *x, size_t nb, yagi_burst_event *events, size_t cap, unsigned *status) {
+        YG_TRY(this->ensure_dev());
+        YG_TRY(this->scratch.ensure(burstdet_scratch_bytes(nb)));
+        YG_TRY(launch_burstdet<T>(W, d, this->thr2, this->floor_, this->min_length, this->hist.template cur<T>(),
+                                  this->hist.template next<T>(), x, nb, this->scratch.p,
+                                  this->state.template as<BurstState>(), events, cap, status, this->st));
+        if (nb != 0) this->hist.flip();
+        this->mirror.dev_written();
         return YAGI_OK;
     }
 };
@@ -6427,24 +6440,14 @@ YAGI_BURSTDET_IMPL(rrrf, float)
 // copies are synchronised lazily (Mirror).  The templates are built once on the host and never change.
 namespace yagi {
 
-struct PdetObj {
-    hipStream_t st = nullptr;
-    int L = 0, K = 0;
-    float threshold = 0.0f, thr2 = 0.0f, floor_ = 0.0f, ep = 0.0f;
-    uint64_t min_length = 1;
+struct PdetObj : EventDetObj<PdetObj, cf32, PdetState, yagi_preamble_event> {
+    int L = 0, K = 0;                                     // the history is L samples
+    float ep = 0.0f;
     std::vector<float> dphi;                              // K
     std::vector<cf32> tmpl;                               // [K][L]
     DevBuf tmpl_dev;                                      // [K][pdet_pitch(L)]
-    FdHist<cf32> win;                                     // host mirror: the history
-    PdetState hs{};                                       //              counter and pending run
-    PingPong<> hist;                                      // device copy, L samples
-    DevBuf state;                                         //              one PdetState
-    DevBuf scratch;                                       // tile table and segment pool, grown with the block length
-    Staging ws;                                           // host block form: x; y holds {status, events} or rxy
-    DevBuf we;                                            // host correlate form: the energies on the device
-    Mirror mirror;
+    DevBuf we;                                            // host correlate form: the energies on the device (ws.y: rxy)
 
-    size_t bytes() const { return (size_t)L * sizeof(cf32); }
     // everything that needs no device
     int configure(const cf32 *p, size_t L_, const float *dphi_, size_t K_, float threshold_, float floor__,
                   uint64_t min_length_) {
@@ -6455,16 +6458,12 @@ struct PdetObj {
         if (!p || !dphi_) return fail(YAGI_ERR_CONFIG, "null pointer argument");
         for (size_t k = 0; k < K_; ++k)
             if (!std::isfinite(dphi_[k])) return fail(YAGI_ERR_CONFIG, "hypothesis %zu is not finite", k);
-        YG_TRY(burstdet_check(threshold_, floor__, min_length_));
+        YG_TRY(set_threshold(threshold_, floor__, min_length_));
         const float e = pdet_preamble_energy(p, L_);
         if (!std::isfinite(e) || !(e > 0.0f))
             return fail(YAGI_ERR_CONFIG, "the preamble's energy must be finite and greater than zero");
         L = (int)L_;
         K = (int)K_;
-        threshold = threshold_;
-        thr2 = threshold_ * threshold_;
-        floor_ = floor__;
-        min_length = min_length_;
         ep = e;
         dphi.assign(dphi_, dphi_ + K_);
         tmpl.resize(K_ * L_);
@@ -6478,40 +6477,14 @@ struct PdetObj {
         return YAGI_OK;
     }
     int alloc() {
-        YG_TRY(require_device());
+        YG_TRY(alloc_state((size_t)L));
         const size_t pitch = pdet_pitch((size_t)L);
         std::vector<cf32> rows((size_t)K * pitch, cf32{});
         for (int k = 0; k < K; ++k) {
             const cf32 *row = tmpl.data() + (size_t)k * (size_t)L;
             std::copy(row, row + L, rows.begin() + (size_t)k * pitch);
         }
-        YG_TRY(fill(tmpl_dev, rows.data(), rows.size() * sizeof(cf32), st));
-        YG_TRY(hist.alloc(bytes()));
-        YG_TRY(state.alloc(sizeof(PdetState)));
-        win.init((size_t)L);
-        return YAGI_OK;
-    }
-    int reset() {
-        win.zero();
-        hs = PdetState{};
-        YG_HIP(hipMemsetAsync(hist.cur(), 0, bytes(), st));
-        YG_HIP(hipMemsetAsync(state.p, 0, sizeof(PdetState), st));
-        mirror.in_sync();
-        return YAGI_OK;
-    }
-    int ensure_host() {
-        return mirror.need_host([&] {
-            std::vector<cf32> t((size_t)L);
-            YG_TRY(download(t.data(), hist.cur(), bytes(), st));
-            win.load(t.data());
-            return download(&hs, state.p, sizeof(PdetState), st);
-        });
-    }
-    int ensure_dev() {
-        return mirror.need_dev([&] {
-            YG_TRY(upload(hist.cur(), win.data(), bytes(), st));
-            return upload(state.p, &hs, sizeof(PdetState), st);
-        });
+        return fill(tmpl_dev, rows.data(), rows.size() * sizeof(cf32), st);
     }
     // events a call of nb samples can report: a run per segment, and the pending run of the call before
     static size_t most_events(size_t nb) { return (nb + kPdetTile - 1) / kPdetTile + (size_t)kPdetSegmax + 1; }
@@ -6524,19 +6497,6 @@ struct PdetObj {
         mirror.dev_written();
         return YAGI_OK;
     }
-    int block(const cf32 *x, size_t nb, yagi_preamble_event *events, size_t cap, size_t *count, int *overflow) {
-        const size_t room = std::min(cap, most_events(nb));
-        YG_TRY(ws.put(st, x, nb));
-        YG_TRY(ws.y.ensure(16 + room * sizeof(yagi_preamble_event)));
-        unsigned *sd = ws.y.as<unsigned>();
-        yagi_preamble_event *ed = reinterpret_cast<yagi_preamble_event *>(ws.y.as<char>() + 16);
-        YG_TRY(block_dev(ws.x.as<cf32>(), nb, ed, room, sd));
-        unsigned status[2];
-        YG_TRY(download(status, sd, sizeof status, st));
-        *count = status[0];
-        *overflow = (int)status[1];
-        return download(events, ed, std::min((size_t)status[0], room) * sizeof(yagi_preamble_event), st);
-    }
     int correlate_dev(const cf32 *x, size_t nb, cf32 *rxy, float *energy) {
         if (nb == 0) return YAGI_OK;
         YG_TRY(ensure_dev());
@@ -6544,18 +6504,6 @@ struct PdetObj {
                                      state.as<PdetState>(), st));
         hist.flip();
         mirror.dev_written();
-        return YAGI_OK;
-    }
-    int flush(yagi_preamble_event *events, size_t cap, size_t *count) {
-        YG_TRY(ensure_host());
-        *count = 0;
-        if (!hs.has_pending) return YAGI_OK;
-        if (hs.pending.length >= min_length) {
-            if (cap > 0) events[0] = hs.pending;
-            *count = 1;
-        }
-        hs.has_pending = 0;
-        mirror.host_written();
         return YAGI_OK;
     }
 };

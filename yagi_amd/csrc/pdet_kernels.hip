@@ -21,12 +21,12 @@
 // also copies its share of the history the call leaves (the last L samples of history ++ x) into the other of the
 // object's two buffers.
 //
-// pdet_tile_kernel: the bank, then hit and r per output, and from there the segment extraction of runs_common.hpp (the
-// steps of burstdet_tile_kernel): a tile without a hit writes {0, 0} to its slot of the tile table and ends; otherwise
+// pdet_tile_kernel: the bank, then hit and r per output, and from there the segment extraction of runs_common.hpp, as
+// in burstdet_tile_kernel: a tile without a hit writes {0, 0} to its slot of the tile table and ends; otherwise
 // the lanes' sums go to LDS, where the staged values were, and runs::tile_segments scans the lanes' runs and writes the
 // tile's segments to the call's pool.  The hypothesis at a segment's peak rides in the segment's spare word.
 //
-// pdet_stitch_kernel: runs::stitch over the 48-byte event (the steps of burstdet_stitch_kernel): one workgroup walks the
+// pdet_stitch_kernel: runs::stitch over the 48-byte event, as in burstdet_stitch_kernel: one workgroup walks the
 // tile table in tile order, joins segments that meet at a tile seam (the pending run of the call before is the first
 // run), reports closed runs of min_length or more, and stores position, pending run and a zeroed pool counter.  No
 // workgroup waits on another: the second launch is the only ordering.

@@ -1,7 +1,7 @@
 // runs_common.hpp -- from per-sample hits to events, for detectors whose front end leaves every lane with hit and r of its
-// R consecutive outputs (pdet_kernels.hip; burstdet_kernels.hip keeps its own text of the same steps, so that its code
-// objects stay the ones its table in DESIGN.md was measured on).  Three pieces, each over an event type Ev that has
-// {uint64 start, length, peak; float ratio, energy} and whatever else PeakOf<Ev> stores at a peak:
+// R consecutive outputs (burstdet_kernels.hip behind autocorr_tile.hpp's sums, pdet_kernels.hip behind its own bank).
+// Three pieces, each over an event type Ev that has {uint64 start, length, peak; float ratio, energy} and whatever else
+// PeakOf<Ev> stores at a peak:
 //
 // tile_segments: the back end of a tile kernel of WG lanes with R outputs each.  The tile's hits fall into segments
 // (maximal runs of hits inside the tile).  Each lane reduces its own R outputs to one scan element
