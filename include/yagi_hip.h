@@ -1935,7 +1935,7 @@ int yagi_hip_eqlms_cccf_execute_host(size_t channels, const yagi_cf32 *h, size_t
  *                             set_gain(g0); no device needed; status, g_out[channels], mode_out[channels] may be NULL
  * The pitches are in elements and >= channels; n is below 2^31; n = 0 touches nothing.  y == x with y_pitch == x_pitch
  * runs in place; any other overlap of x and y, and any overlap of the status plane with x or y, is YAGI_ERR_CONFIG.
- * Not built: per-channel bandwidths or thresholds, a time-parallel form, SymTrack.
+ * Not built: per-channel bandwidths or thresholds, a time-parallel form.
  * Device form: agc_kernels.hip: one lane per channel, one wave per workgroup. */
 #define YAGI_AGC_CHANNELS_MAX 1048576
 enum {
@@ -1991,6 +1991,122 @@ int yagi_hip_log10f(const float *x, size_t n, float *y);
 YAGI_HIP_AGC_DECL(crcf, yagi_cf32)
 YAGI_HIP_AGC_DECL(rrrf, float)
 #undef YAGI_HIP_AGC_DECL
+
+/* ---- SymTrack: agc, timing, carrier and equalizer loops for a bank of channels (src/framing/symtrack.rs is an empty file)
+ * SymTrack(channels, ftype, k, m, beta, scheme, osc_scheme, npfb, eq_len): `channels` independent receivers of one design
+ * (cccf only).  The reference file is empty, so the object is defined by composition of objects this library pins to the
+ * reference.  It follows liquid-dsp's symtrack as recalled; that is a note, not a parity claim.
+ * SymTrack: the definition.  Per channel the object owns
+ *     agc    Agc<Complex32> as after new() (crcf), squelch disabled
+ *     sync   Symsync<Complex32>::new_rnyquist(ftype, k, m, beta, npfb), then set_output_rate(2)
+ *     nco    Osc::new(osc_scheme), YAGI_OSC_NCO or YAGI_OSC_VCO, phase and frequency 0
+ *     eq     Eqlms<Complex32>::new_lowpass(eq_len, 0.45)
+ *     demod  Modem of `scheme` (or of a table)
+ * set_bandwidth(bw), bw >= 0, 0.9 at creation: agc.set_bandwidth(0.02 bw), sync.set_lf_bw(0.001 bw), eq.set_bw(0.02 bw),
+ * nco.pll_set_bandwidth(0.001 bw), the products formed in f32; a value one of the four setters refuses is YAGI_ERR_CONFIG.
+ * execute over one input sample x of a channel:
+ *     v = agc.execute(x)
+ *     for each output s the synchroniser's step(v) produces, in order (0, 1 or more):
+ *         u = nco.mix_down(s); nco.step()
+ *         eq.push(u)
+ *         j = sync_index; sync_index += 1
+ *         if j is odd: continue                      (outputs 0, 2, 4, .. since reset are the symbol instants)
+ *         d_hat = eq.execute()
+ *         sym = demod.demodulate(d_hat); x_hat = demod.get_demodulator_sample()
+ *         e = demod.get_demodulator_phase_error()    ((d_hat conj(x_hat)).im, num-complex's product, unfused)
+ *         nco.pll_step(e)                            (adjust_frequency(e alpha); adjust_phase(e beta), through constrain())
+ *         if num_syms > eq_holdoff and strategy != OFF:
+ *             d = d_hat / |d_hat| (CM: EqLms's own |.| word and quotients) or x_hat (DD)
+ *             eq.step(d, d_hat)                      (behind eq's own count >= h_len gate)
+ *         num_syms += 1
+ *         emit (d_hat, sym)
+ * eq_holdoff is 200 and the strategy CM at creation.  All in f32 with the words of the parts: Agc's own ln and exp, SymSync's
+ * sums and quotients, Osc's table lookup, EqLms's sums, |.| and quotients, Modem's hard decision.
+ * Schemes: BPSK, QPSK, OOK, ASK2 .. ASK256, QAM4 .. QAM256 and tables of 2 .. 256 points (a power of two).  PSK and DPSK
+ * decide through the device library's atan2f / sincosf, which are not fixed words: create returns YAGI_ERR_CONFIG for them.
+ * Hard decisions only.
+ * Deviations:
+ *   capacity   a channel writes at most ycap symbols per call.  An iteration about to emit symbol number ycap does not run:
+ *              the channel is stalled, reason YAGI_SYMTRACK_STALL_CAPACITY (SymSync's rule; the sample's agc step and the
+ *              synchroniser's push have run).  The inner loop is counted, so it ends whatever the state holds.
+ *   constrain  the reference never returns for an infinity or a magnitude at which +- 2 pi makes no progress.  A pll_step
+ *              whose argument e alpha or e beta has magnitude >= YAGI_SYMTRACK_PLL_ARG_MAX does not run, nor anything
+ *              behind it in that iteration (no eq.step, no count, no output): the channel is stalled, reason
+ *              YAGI_SYMTRACK_STALL_PLL.  Below the bound constrain is the reference's loops, NaN -> 0 as Rust's cast.
+ *   stalled    a stalled channel ignores all further input, reports ny = 0, keeps its getters and revives on reset() or
+ *              reset_channel(c).  A call returns YAGI_OK either way.  Non-finite samples otherwise follow the loops as
+ *              written and touch only their own channel.
+ *   create(channels, ftype, k, m, beta, scheme, osc_scheme, npfb, eq_len)   channels <= YAGI_SYMTRACK_CHANNELS_MAX, k >= 2,
+ *                             npfb and 2 k m within SymSync's limits, 1 <= eq_len <= YAGI_EQLMS_LEN_MAX, and the LDS of the
+ *                             lane-strided tiles (the synchroniser's window, the equalizer's window and weights, the staged
+ *                             rows) plus the oscillator table and the constellation within 160 KiB; anything else is
+ *                             YAGI_ERR_CONFIG, decided before any device is asked for
+ *   create_from_table(channels, ftype, k, m, beta, table, M, osc_scheme, npfb, eq_len)
+ *   destroy / clone / set_stream / reset / reset_channel(c)
+ *   set_bandwidth(bw) / get_bandwidth
+ *   set_bandwidths(agc, sync, eq, pll)   the four setters one by one (get_bandwidth then reports NaN)
+ *   set_eq_strategy(YAGI_SYMTRACK_EQ_OFF | _CM | _DD) / set_eq_holdoff(nsyms)
+ *   set_nco(c, frequency, phase) / set_nco_all(frequency[channels], phase[channels])   through constrain(): YAGI_ERR_CONFIG
+ *                             where the reference's loops would not end
+ *   get_channels; and, synchronising, [channels] each: get_tau, get_gain, get_rssi, get_nco_frequency, get_nco_phase
+ *                             (Osc's f32 formulas), get_nco_state(theta, d_theta) (the raw words), get_num_syms (uint64_t),
+ *                             get_stalled (the reason, 0 = running); get_weights(w[channels][eq_len]) as EqLms's
+ *   execute(x, x_pitch, n, y, y_pitch, sym, sym_pitch, ycap, ny[channels], stalled[channels])   host slices; sym may be NULL
+ *   execute_dev(x_dev, x_pitch, n, y_dev, y_pitch, sym_dev, sym_pitch, ycap, status_dev)   status_dev = uint32_t[3 channels]:
+ *                             ny, then the stall reason, then the low word of num_syms; asynchronous on the object's
+ *                             stream; n = 0 writes zeros for ny; sym_dev may be NULL
+ *   execute_host(channels, ftype, k, m, beta, scheme, table, M, osc_scheme, npfb, eq_len, bw, strategy, holdoff,
+ *                nco_frequency, nco_phase, x, x_pitch, n, y, y_pitch, sym, sym_pitch, ycap, ny, stalled)
+ *                             the definition on the host alone, one call from reset(), no device needed; table = NULL takes
+ *                             `scheme`; nco_frequency / nco_phase [channels] may be NULL (zeros)
+ * y[j y_pitch + c] = d_hat and sym[j sym_pitch + c] = the symbol as one byte, j < ny[c]; rows >= ny[c] of a channel are not
+ * touched.  The pitches are in elements and >= channels.  n and ycap are below 2^31.  x and y must not overlap.
+ * Not built: PSK / DPSK and soft bits, rrrf, per-channel designs or bandwidths, squelch, several
+ * lanes per channel, a fused channelizer -> SymTrack, sharding, Eqrls.
+ * Device form: symtrack_kernels.hip: one lane per channel, one wave per workgroup. */
+#define YAGI_SYMTRACK_CHANNELS_MAX 1048576
+#define YAGI_SYMTRACK_PLL_ARG_MAX 256.0f
+enum { YAGI_SYMTRACK_EQ_OFF = 0, YAGI_SYMTRACK_EQ_CM = 1, YAGI_SYMTRACK_EQ_DD = 2 };
+enum { YAGI_SYMTRACK_STALL_NONE = 0, YAGI_SYMTRACK_STALL_CAPACITY = 1, YAGI_SYMTRACK_STALL_PLL = 2 };
+typedef struct yagi_hip_symtrack_cccf_s *yagi_hip_symtrack_cccf;
+int yagi_hip_symtrack_cccf_create(size_t channels, int ftype, size_t k, size_t m, float beta, int scheme, int osc_scheme,
+                                  size_t npfb, size_t eq_len, yagi_hip_symtrack_cccf *q);
+int yagi_hip_symtrack_cccf_create_from_table(size_t channels, int ftype, size_t k, size_t m, float beta,
+                                             const yagi_cf32 *table, size_t M, int osc_scheme, size_t npfb, size_t eq_len,
+                                             yagi_hip_symtrack_cccf *q);
+int yagi_hip_symtrack_cccf_destroy(yagi_hip_symtrack_cccf q);
+int yagi_hip_symtrack_cccf_clone(yagi_hip_symtrack_cccf q, yagi_hip_symtrack_cccf *out);
+int yagi_hip_symtrack_cccf_set_stream(yagi_hip_symtrack_cccf q, yagi_stream_t s);
+int yagi_hip_symtrack_cccf_reset(yagi_hip_symtrack_cccf q);
+int yagi_hip_symtrack_cccf_reset_channel(yagi_hip_symtrack_cccf q, size_t c);
+int yagi_hip_symtrack_cccf_set_bandwidth(yagi_hip_symtrack_cccf q, float bw);
+int yagi_hip_symtrack_cccf_get_bandwidth(yagi_hip_symtrack_cccf q, float *bw);
+int yagi_hip_symtrack_cccf_set_bandwidths(yagi_hip_symtrack_cccf q, float agc, float sync, float eq, float pll);
+int yagi_hip_symtrack_cccf_set_eq_strategy(yagi_hip_symtrack_cccf q, int strategy);
+int yagi_hip_symtrack_cccf_set_eq_holdoff(yagi_hip_symtrack_cccf q, uint64_t nsyms);
+int yagi_hip_symtrack_cccf_set_nco(yagi_hip_symtrack_cccf q, size_t c, float frequency, float phase);
+int yagi_hip_symtrack_cccf_set_nco_all(yagi_hip_symtrack_cccf q, const float *frequency, const float *phase);
+int yagi_hip_symtrack_cccf_get_channels(yagi_hip_symtrack_cccf q, size_t *channels);
+int yagi_hip_symtrack_cccf_get_tau(yagi_hip_symtrack_cccf q, float *tau);
+int yagi_hip_symtrack_cccf_get_gain(yagi_hip_symtrack_cccf q, float *gain);
+int yagi_hip_symtrack_cccf_get_rssi(yagi_hip_symtrack_cccf q, float *rssi);
+int yagi_hip_symtrack_cccf_get_nco_frequency(yagi_hip_symtrack_cccf q, float *frequency);
+int yagi_hip_symtrack_cccf_get_nco_phase(yagi_hip_symtrack_cccf q, float *phase);
+int yagi_hip_symtrack_cccf_get_nco_state(yagi_hip_symtrack_cccf q, uint32_t *theta, uint32_t *d_theta);
+int yagi_hip_symtrack_cccf_get_weights(yagi_hip_symtrack_cccf q, yagi_cf32 *w);
+int yagi_hip_symtrack_cccf_get_num_syms(yagi_hip_symtrack_cccf q, uint64_t *num_syms);
+int yagi_hip_symtrack_cccf_get_stalled(yagi_hip_symtrack_cccf q, uint32_t *stalled);
+int yagi_hip_symtrack_cccf_execute(yagi_hip_symtrack_cccf q, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
+                                   size_t y_pitch, uint8_t *sym, size_t sym_pitch, size_t ycap, uint32_t *ny,
+                                   uint32_t *stalled);
+int yagi_hip_symtrack_cccf_execute_dev(yagi_hip_symtrack_cccf q, const yagi_cf32 *x_dev, size_t x_pitch, size_t n,
+                                       yagi_cf32 *y_dev, size_t y_pitch, uint8_t *sym_dev, size_t sym_pitch, size_t ycap,
+                                       uint32_t *status_dev);
+int yagi_hip_symtrack_cccf_execute_host(size_t channels, int ftype, size_t k, size_t m, float beta, int scheme,
+                                        const yagi_cf32 *table, size_t M, int osc_scheme, size_t npfb, size_t eq_len, float bw,
+                                        int strategy, uint64_t holdoff, const float *nco_frequency, const float *nco_phase,
+                                        const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y, size_t y_pitch,
+                                        uint8_t *sym, size_t sym_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled);
 
 /* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */

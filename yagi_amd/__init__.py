@@ -21,6 +21,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     PreambleDetector           (absent from the reference: a bank of known-preamble correlators, threshold and events)
     SymSync                    src/filter/symsync.rs:37-276, one object per channel of a bank
     EqLms, EqLmsUpdate         src/equalization/eqlms.rs:25-199, one object per channel of a bank
+    SymTrack, SymTrackEq       (src/framing/symtrack.rs is empty: Agc -> SymSync -> Osc -> EqLms -> Modem, loops closed)
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -39,7 +40,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "EqLms", "EqLmsUpdate", "EQLMS_LEN_MAX", "EQLMS_CHANNELS_MAX", "EQLMS_TABLE_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "EqLms", "EqLmsUpdate", "SymTrack", "SymTrackEq", "symtrack_host", "SYMTRACK_CHANNELS_MAX", "SYMTRACK_PLL_ARG_MAX", "SYMTRACK_STALL_CAPACITY", "SYMTRACK_STALL_PLL", "EQLMS_LEN_MAX", "EQLMS_CHANNELS_MAX", "EQLMS_TABLE_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "SpgramPlan", "plan_spgram", "MsResamp2Plan", "Resamp2Plan", "plan_msresamp2", "plan_resamp2", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
@@ -2679,6 +2680,189 @@ class Agc(_Handle):
         _check(fn(channels, bandwidth, scale, g0, int(bool(locked)), int(bool(squelch)), threshold, timeout, _ptr(x),
                   x_pitch, n, _ptr(y), y_pitch, None if st is None else _ptr(st), status_pitch, _ptr(g), _ptr(mode)))
         return y, st, g, mode
+
+
+SYMTRACK_CHANNELS_MAX = 1 << 20    # YAGI_SYMTRACK_CHANNELS_MAX
+SYMTRACK_PLL_ARG_MAX = 256.0       # YAGI_SYMTRACK_PLL_ARG_MAX: a pll_step argument of this magnitude stalls the channel
+SYMTRACK_STALL_CAPACITY = 1        # YAGI_SYMTRACK_STALL_CAPACITY: the channel would have written symbol number ycap
+SYMTRACK_STALL_PLL = 2             # YAGI_SYMTRACK_STALL_PLL
+
+
+class SymTrackEq(enum.IntEnum):
+    """what SymTrack's equalizer does after each symbol past the hold-off, numbered as YAGI_SYMTRACK_EQ_*"""
+    OFF = 0         # the weights stay
+    CM = 1          # constant modulus: step(d_hat / |d_hat|, d_hat)
+    DD = 2          # decision directed: step(x_hat, d_hat), x_hat from the de-rotated sample
+
+
+def _symtrack_scheme(scheme):
+    """(scheme number, table or None) of a ModulationScheme or a table of points"""
+    if isinstance(scheme, (int, np.integer, enum.IntEnum)):
+        return int(scheme), None
+    t = _arr(scheme, np.complex64)
+    if t.ndim != 1:
+        raise ConfigError("a constellation table is one-dimensional")
+    return int(ModulationScheme.Arb), t
+
+
+class SymTrack(_Handle):
+    """SymTrack(channels, ftype, k, m, beta, scheme, osc_scheme, npfb=16, eq_len=9): `channels` independent receivers of
+    one design: Agc -> SymSync (k_out = 2) -> Osc.mix_down -> EqLms -> Modem, with the carrier loop closed from the
+    demodulator's phase error per symbol and the equalizer updated from the de-rotated sample (yagi_hip.h, "SymTrack: the
+    definition"; the reference's src/framing/symtrack.rs is empty).  scheme is a ModulationScheme (Bpsk, Qpsk, Ook, Ask*,
+    Qam*; Psk* and Dpsk* are a ConfigError) or a table of 2 .. 256 points.  execute takes a block x[n, channels] (step,
+    channel) and returns per channel the equalized symbols d_hat and the decisions, bit for bit the composition of the
+    parts' sequential loops.
+    A channel that would write more than ycap symbols in a call, or whose pll_step argument reaches SYMTRACK_PLL_ARG_MAX,
+    is stalled: it ignores all further input and reports ny = 0 until reset() or reset_channel(c).
+    The block calls run symtrack_kernels.hip, one lane per channel."""
+    _prefix = "yagi_hip_symtrack_cccf_"
+
+    def __init__(self, channels, ftype, k, m, beta, scheme, osc_scheme=OscScheme.Nco, npfb=16, eq_len=9):
+        channels, k, m, npfb, eq_len = (_symsync_size(v, "argument") for v in (channels, k, m, npfb, eq_len))
+        scheme, table = _symtrack_scheme(scheme)
+        osc = OscScheme(osc_scheme).value
+        hd = C.c_void_p()
+        if table is None:
+            _check(self._fn("create")(channels, int(ftype), k, m, beta, scheme, osc, npfb, eq_len, C.byref(hd)))
+        else:
+            _check(self._fn("create_from_table")(channels, int(ftype), k, m, beta, _ptr(table), table.size, osc, npfb,
+                                                 eq_len, C.byref(hd)))
+        self._set(hd, channels, k, eq_len)
+
+    def _set(self, hd, channels, k, eq_len):
+        self._h, self.kind, self.T, self.channels, self.k, self.eq_len = hd, "cccf", np.complex64, channels, k, eq_len
+
+    def clone(self):
+        new, hd = object.__new__(type(self)), C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._set(hd, self.channels, self.k, self.eq_len)
+        return new
+
+    def reset_channel(self, c):
+        _check(self._fn("reset_channel")(self._h, _symsync_size(c, "channel")))
+
+    def set_bandwidth(self, bw):
+        """agc 0.02 bw, timing loop 0.001 bw, equalizer 0.02 bw, PLL 0.001 bw, the products in f32"""
+        _check(self._fn("set_bandwidth")(self._h, bw))
+
+    def get_bandwidth(self):
+        v = C.c_float()
+        _check(self._fn("get_bandwidth")(self._h, C.byref(v)))
+        return v.value
+
+    def set_bandwidths(self, agc, sync, eq, pll):
+        """the four setters one by one; get_bandwidth reports NaN afterwards"""
+        _check(self._fn("set_bandwidths")(self._h, agc, sync, eq, pll))
+
+    def set_eq_strategy(self, strategy):
+        _check(self._fn("set_eq_strategy")(self._h, int(SymTrackEq(strategy))))
+
+    def set_eq_holdoff(self, nsyms):
+        _check(self._fn("set_eq_holdoff")(self._h, _symsync_size(nsyms, "nsyms")))
+
+    def set_nco(self, c, frequency, phase=0.0):
+        """set_frequency and set_phase of channel c's oscillator, radians per synchroniser output sample and radians"""
+        _check(self._fn("set_nco")(self._h, _symsync_size(c, "channel"), frequency, phase))
+
+    def set_nco_all(self, frequency, phase=None):
+        f = _arr(frequency, np.float32)
+        p = np.zeros(self.channels, np.float32) if phase is None else _arr(phase, np.float32)
+        if f.shape != (self.channels,) or p.shape != (self.channels,):
+            raise ConfigError("one frequency and one phase per channel")
+        _check(self._fn("set_nco_all")(self._h, _ptr(f), _ptr(p)))
+
+    def _get(self, name, dt, shape=None):
+        out = np.zeros(self.channels if shape is None else shape, dt)
+        _check(self._fn(name)(self._h, _ptr(out)))
+        return out
+
+    def get_tau(self):
+        """tau_decim of every channel; synchronises, as every getter below does"""
+        return self._get("get_tau", np.float32)
+
+    def get_gain(self):
+        return self._get("get_gain", np.float32)
+
+    def get_rssi(self):
+        return self._get("get_rssi", np.float32)
+
+    def get_nco_frequency(self):
+        return self._get("get_nco_frequency", np.float32)
+
+    def get_nco_phase(self):
+        return self._get("get_nco_phase", np.float32)
+
+    def get_nco_state(self):
+        """(theta, d_theta): the oscillators' raw u32 words"""
+        th, dth = np.zeros(self.channels, np.uint32), np.zeros(self.channels, np.uint32)
+        _check(self._fn("get_nco_state")(self._h, _ptr(th), _ptr(dth)))
+        return th, dth
+
+    def get_weights(self):
+        """[channels, eq_len], as EqLms.get_weights"""
+        return self._get("get_weights", np.complex64, (self.channels, self.eq_len))
+
+    def get_num_syms(self):
+        return self._get("get_num_syms", np.uint64)
+
+    def get_stalled(self):
+        """the stall reason of every channel, 0 = running"""
+        return self._get("get_stalled", np.uint32)
+
+    def default_ycap(self, n):
+        """ceil(n / k) + 8: a default, not a bound (a loop far from lock can write more)"""
+        return -(-int(n) // self.k) + 8
+
+    def execute(self, x, ycap=None, symbols=True):
+        """x[n, channels] -> (y[ycap, channels], sym[ycap, channels] or None, ny[channels], stalled[channels]); y[j, c] and
+        sym[j, c] are symbol j of channel c for j < ny[c] and zero below.  ycap defaults to default_ycap(n)"""
+        x = _arr(x, self.T)
+        if x.ndim != 2 or x.shape[1] != self.channels:
+            raise ConfigError(f"the block is [steps, {self.channels}]")
+        n = x.shape[0]
+        ycap = self.default_ycap(n) if ycap is None else _symsync_size(ycap, "ycap")
+        y = np.zeros((ycap, self.channels), self.T)
+        sym = np.zeros((ycap, self.channels), np.uint8) if symbols else None
+        ny, st = np.zeros(self.channels, np.uint32), np.zeros(self.channels, np.uint32)
+        _check(self._fn("execute")(self._h, _ptr(x), self.channels, n, _ptr(y), self.channels,
+                                   None if sym is None else _ptr(sym), self.channels, ycap, _ptr(ny), _ptr(st)))
+        return y, sym, ny, st
+
+    def execute_devptr(self, x_dev, x_pitch, n, y_dev, y_pitch, sym_dev, sym_pitch, ycap, status_dev):
+        """x_dev: n rows of pitch x_pitch samples; y_dev: ycap rows of pitch y_pitch; sym_dev: ycap rows of sym_pitch bytes
+        or None; status_dev: 3 channels uint32 that receive ny, the stall reason and the low word of num_syms.  Rows >=
+        ny[c] of a channel are not touched.  Asynchronous on the object's stream (the C ABI's execute_dev)"""
+        x_dev, y_dev, sym_dev, status_dev = (None if p is None else _devptr(p) for p in (x_dev, y_dev, sym_dev, status_dev))
+        _check(self._fn("execute_dev")(self._h, x_dev, x_pitch, n, y_dev, y_pitch, sym_dev, sym_pitch, ycap, status_dev))
+
+
+def symtrack_host(channels, ftype, k, m, beta, scheme, osc_scheme, x, npfb=16, eq_len=9, bw=0.9, strategy=SymTrackEq.CM,
+                  holdoff=200, nco_frequency=None, nco_phase=None, ycap=None, x_pitch=None, y_pitch=None, sym_pitch=None):
+    """SymTrack's definition on the host alone, no device needed: one call from reset().  x is [n, x_pitch] (the pitches
+    default to channels); returns (y[ycap, y_pitch], sym[ycap, sym_pitch], ny, stalled).  The library's own sequential
+    form, slow and meant for checks"""
+    channels, k, m, npfb, eq_len, holdoff = (_symsync_size(v, "argument") for v in (channels, k, m, npfb, eq_len, holdoff))
+    if not 1 <= channels <= SYMTRACK_CHANNELS_MAX:
+        raise ConfigError("channels must be in 1 .. SYMTRACK_CHANNELS_MAX")
+    scheme, table = _symtrack_scheme(scheme)
+    x_pitch, y_pitch, sym_pitch = (channels if p is None else _symsync_size(p, "pitch") for p in (x_pitch, y_pitch, sym_pitch))
+    x = _arr(x, np.complex64)
+    if x.ndim != 2 or x.shape[1] != x_pitch:
+        raise ConfigError("the block is [steps, x_pitch]")
+    n = x.shape[0]
+    ycap = -(-n // max(k, 1)) + 8 if ycap is None else _symsync_size(ycap, "ycap")
+    f = None if nco_frequency is None else _arr(nco_frequency, np.float32)
+    p = None if nco_phase is None else _arr(nco_phase, np.float32)
+    if any(a is not None and a.shape != (channels,) for a in (f, p)):
+        raise ConfigError("one frequency and one phase per channel")
+    y, sym = np.zeros((ycap, y_pitch), np.complex64), np.zeros((ycap, sym_pitch), np.uint8)
+    ny, st = np.zeros(channels, np.uint32), np.zeros(channels, np.uint32)
+    _check(lib.yagi_hip_symtrack_cccf_execute_host(
+        channels, int(ftype), k, m, beta, scheme, None if table is None else _ptr(table), 0 if table is None else table.size,
+        OscScheme(osc_scheme).value, npfb, eq_len, bw, int(SymTrackEq(strategy)), holdoff, None if f is None else _ptr(f),
+        None if p is None else _ptr(p), _ptr(x), x_pitch, n, _ptr(y), y_pitch, _ptr(sym), sym_pitch, ycap, _ptr(ny), _ptr(st)))
+    return y, sym, ny, st
 
 
 MSEQUENCE_TILE = 8192    # YAGI_MSEQUENCE_TILE: symbols per workgroup of the generator kernel

@@ -740,6 +740,32 @@ for _k in ("crcf", "rrrf"):
         _sig(_p + _n, vp, vp, sz, sz, vp, sz, vp, sz)
     _sig(_p + "execute_host", sz, f32, f32, f32, ci, ci, f32, u64, vp, sz, sz, vp, sz, vp, sz, vp, vp)
 
+# ---- SymTrack ----------------------------------------------------------------------------------
+_p = "yagi_hip_symtrack_cccf_"
+_sig(_p + "create", sz, ci, sz, sz, f32, ci, ci, sz, sz, pvp)
+_sig(_p + "create_from_table", sz, ci, sz, sz, f32, vp, sz, ci, sz, sz, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "reset_channel", vp, sz)
+_sig(_p + "set_bandwidth", vp, f32)
+_sig(_p + "get_bandwidth", vp, C.POINTER(f32))
+_sig(_p + "set_bandwidths", vp, f32, f32, f32, f32)
+_sig(_p + "set_eq_strategy", vp, ci)
+_sig(_p + "set_eq_holdoff", vp, u64)
+_sig(_p + "set_nco", vp, sz, f32, f32)
+_sig(_p + "set_nco_all", vp, vp, vp)
+_sig(_p + "get_channels", vp, C.POINTER(sz))
+for _n in ("get_tau", "get_gain", "get_rssi", "get_nco_frequency", "get_nco_phase", "get_weights", "get_num_syms",
+           "get_stalled"):
+    _sig(_p + _n, vp, vp)
+_sig(_p + "get_nco_state", vp, vp, vp)
+_sig(_p + "execute", vp, vp, sz, sz, vp, sz, vp, sz, sz, vp, vp)
+_sig(_p + "execute_dev", vp, vp, sz, sz, vp, sz, vp, sz, sz, vp)
+_sig(_p + "execute_host", sz, ci, sz, sz, f32, ci, vp, sz, ci, sz, sz, f32, ci, u64, vp, vp, vp, sz, sz, vp, sz, vp, sz, sz,
+     vp, vp)
+
 # ---- SymStream ---------------------------------------------------------------------------------
 _p = "yagi_hip_symstreamcf_"
 _sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)

@@ -7818,6 +7818,441 @@ int yagi_hip_log10f(const float *x, size_t n, float *y) try {
 
 }  // extern "C"
 
+// ---- SymTrack (src/framing/symtrack.rs is empty: the composition of yagi_hip.h) ------------------------------------------
+// The state is the parts' own records and arrays plus one SymtrackChan per channel; symtrack_kernels.hip updates all of
+// them in place on the device.  The host side of the parts (their configure(), reset and mirrors) is reused as it is;
+// their device buffers are never allocated.  Setters that touch per-channel state, the getters and clone work on the
+// host mirror; the two copies are synchronised lazily (Mirror).  The loop settings travel to the kernel by value.
+namespace yagi {
+
+struct SymtrackObj {
+    hipStream_t st = nullptr;
+    size_t C = 0, k = 0;
+    SymsyncObj sy;                                        // host parts only: taps, p, hs, hh
+    EqlmsObj eq;                                          // h0, mu, hw, hh, hs
+    AgcObj<cf32> ag;                                      // g, hs
+    ModemParams P{};
+    std::vector<cf32> map;
+    std::vector<uint8_t> nbr;
+    int vco = 0, strategy = YAGI_SYMTRACK_EQ_CM;
+    std::vector<float> osc;                               // the oscillator's device table, on the host
+    float pll_alpha = 0.0f, pll_beta = 0.0f, bw = 0.0f;
+    uint64_t holdoff = 200;
+    std::vector<SymtrackChan> hst;
+    DevBuf taps_dev, osc_dev, map_dev, agc_dev, ss_dev, eq_dev, st_dev, sshist_dev, eqw_dev, eqhist_dev, wstatus, wsym;
+    Mirror mirror;
+    Staging ws;                                           // host block form: x as given; y compact [ycap][C]
+
+    // everything that needs no device; table = nullptr takes `scheme`
+    int configure(size_t channels, int ftype, size_t k_, size_t m, float beta, int scheme, const cf32 *table, size_t M,
+                  int osc_scheme, size_t npfb, size_t eq_len) {
+        if (channels == 0 || channels > (size_t)YAGI_SYMTRACK_CHANNELS_MAX)
+            return fail(YAGI_ERR_CONFIG, "symtrack: %zu channels are outside 1 .. YAGI_SYMTRACK_CHANNELS_MAX", channels);
+        int kind = 0, bps = 0;
+        if (table) {
+            while (bps < 8 && ((size_t)1 << bps) < M) ++bps;
+            if (M < 2 || ((size_t)1 << bps) != M) return fail(YAGI_ERR_CONFIG, "table size must be a power of 2 in 2..256");
+            kind = MODEM_ARB;
+        } else {
+            YG_TRY(yagi_hip_modem_s::kind_of(scheme, &kind, &bps));
+            if (kind == MODEM_PSK || kind == MODEM_DPSK)
+                return fail(YAGI_ERR_CONFIG, "symtrack: PSK and DPSK decide through atan2f / sincosf of the device library, "
+                                             "which are not fixed words; they are not built");
+        }
+        if (osc_scheme != YAGI_OSC_NCO && osc_scheme != YAGI_OSC_VCO)
+            return fail(YAGI_ERR_CONFIG, "osc: unknown scheme %d", osc_scheme);
+        std::vector<float> h;
+        YG_TRY(symsync_rnyquist_taps(ftype, k_, m, beta, npfb, h));
+        YG_TRY(sy.configure(channels, k_, npfb, h.data(), h.size()));
+        sy.k_out = 2;
+        sy.p.k_out = 2;
+        for (auto &s : sy.hs) symsync_reset_chan(&s, k_, 2);
+        std::vector<cf32> hc;
+        YG_TRY(eqlms_lowpass_taps(eq_len, 0.45f, hc));
+        YG_TRY(eq.configure(channels, hc.data(), hc.size()));
+        YG_TRY(ag.configure(channels));
+        YG_TRY(modem_design(kind, bps, table, P, map, nbr));
+        vco = osc_scheme == YAGI_OSC_VCO;
+        const size_t lds = symtrack_lds_bytes(sy.Ls, eq_len, vco, map.size());
+        if (lds > kSymtrackLdsMax)
+            return fail(YAGI_ERR_CONFIG, "symtrack: 2 k m = %zu and eq_len = %zu need %zu bytes of LDS, more than 160 KiB",
+                        sy.Ls, eq_len, lds);
+        osc_device_table(vco, osc);
+        C = channels, k = k_;
+        strategy = YAGI_SYMTRACK_EQ_CM, holdoff = 200;
+        hst.assign(C, SymtrackChan{});
+        return set_bandwidth(0.9f);
+    }
+    int set_bandwidths(float a, float s, float e, float pl) {
+        SymsyncLoop t = sy.p;
+        YG_TRY(AgcObj<cf32>::check_bandwidth(a));
+        YG_TRY(symsync_set_bw(s, &t));
+        float mu = 0.0f;
+        YG_TRY(EqlmsObj::set_bw(e, &mu));
+        if (!(e >= 0.0f)) return fail(YAGI_ERR_CONFIG, "learning rate cannot be less than zero");
+        if (!(pl >= 0.0f)) return fail(YAGI_ERR_CONFIG, "Bandwidth must be positive");
+        ag.g.alpha = a;
+        sy.p = t;
+        eq.mu = mu;
+        pll_alpha = pl;
+        pll_beta = std::sqrt(pl);
+        bw = std::nanf("");
+        return YAGI_OK;
+    }
+    int set_bandwidth(float bw_) {
+        if (!(bw_ >= 0.0f)) return fail(YAGI_ERR_CONFIG, "symtrack: the bandwidth must be at least 0");
+        YG_TRY(set_bandwidths(0.02f * bw_, 0.001f * bw_, 0.02f * bw_, 0.001f * bw_));
+        bw = bw_;
+        return YAGI_OK;
+    }
+    SymtrackLoop loop() const {
+        SymtrackLoop p{};
+        p.ss = sy.p;
+        p.agc_alpha = ag.g.alpha, p.agc_scale = ag.g.scale, p.eq_mu = eq.mu, p.pll_alpha = pll_alpha, p.pll_beta = pll_beta;
+        p.h_len = (unsigned)eq.h_len, p.vco = (unsigned)vco, p.strategy = (unsigned)strategy, p.M = (unsigned)map.size();
+        p.kind = P.kind, p.bps = P.bps;
+        p.holdoff = holdoff;
+        std::copy(P.ref, P.ref + 8, p.ref);
+        return p;
+    }
+    SymtrackState host_state() {
+        return SymtrackState{ag.hs.data(), sy.hs.data(), eq.hs.data(), hst.data(), sy.hh.data(), eq.hw.data(), eq.hh.data()};
+    }
+    SymtrackState dev_state() {
+        return SymtrackState{agc_dev.as<AgcChan>(),  ss_dev.as<SymsyncChan>(), eq_dev.as<EqlmsChan>(), st_dev.as<SymtrackChan>(),
+                             sshist_dev.as<cf32>(), eqw_dev.as<cf32>(),       eqhist_dev.as<cf32>()};
+    }
+    int alloc() {
+        YG_TRY(require_device());
+        YG_TRY(fill(taps_dev, sy.taps.data(), sy.taps.size() * sizeof(float), st));
+        YG_TRY(fill(osc_dev, osc.data(), osc.size() * sizeof(float), st));
+        std::vector<float> mr(2 * map.size() + 8);
+        for (size_t i = 0; i < map.size(); ++i) mr[2 * i] = map[i].re, mr[2 * i + 1] = map[i].im;
+        std::copy(P.ref, P.ref + 8, mr.begin() + 2 * map.size());
+        YG_TRY(fill(map_dev, mr.data(), mr.size() * sizeof(float), st));
+        YG_TRY(agc_dev.alloc(C * sizeof(AgcChan)));
+        YG_TRY(ss_dev.alloc(C * sizeof(SymsyncChan)));
+        YG_TRY(eq_dev.alloc(C * sizeof(EqlmsChan)));
+        YG_TRY(st_dev.alloc(C * sizeof(SymtrackChan)));
+        YG_TRY(sshist_dev.alloc(sy.Ls * C * sizeof(cf32)));
+        YG_TRY(eqw_dev.alloc(eq.h_len * C * sizeof(cf32)));
+        YG_TRY(eqhist_dev.alloc(eq.h_len * C * sizeof(cf32)));
+        YG_TRY(wstatus.alloc(3 * C * sizeof(unsigned)));
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    template <class F>
+    int each_array(F &&f) {                                 // f(device buffer, host pointer, bytes)
+        YG_TRY(f(agc_dev, ag.hs.data(), C * sizeof(AgcChan)));
+        YG_TRY(f(ss_dev, sy.hs.data(), C * sizeof(SymsyncChan)));
+        YG_TRY(f(eq_dev, eq.hs.data(), C * sizeof(EqlmsChan)));
+        YG_TRY(f(st_dev, hst.data(), C * sizeof(SymtrackChan)));
+        YG_TRY(f(sshist_dev, sy.hh.data(), sy.Ls * C * sizeof(cf32)));
+        YG_TRY(f(eqw_dev, eq.hw.data(), eq.h_len * C * sizeof(cf32)));
+        return f(eqhist_dev, eq.hh.data(), eq.h_len * C * sizeof(cf32));
+    }
+    int ensure_host() {
+        return mirror.need_host([&] { return each_array([&](DevBuf &d, void *h, size_t b) { return download(h, d.p, b, st); }); });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] { return each_array([&](DevBuf &d, void *h, size_t b) { return upload(d.p, h, b, st); }); });
+    }
+    void reset_chan(size_t c) {
+        AgcObj<cf32>::reset_chan(ag.hs[c]);
+        symsync_reset_chan(&sy.hs[c], k, 2);
+        eq.reset_chan(c);
+        hst[c] = SymtrackChan{};
+    }
+    int reset_channel(size_t c) {
+        if (c >= C) return fail(YAGI_ERR_CONFIG, "symtrack: channel %zu of %zu", c, C);
+        YG_TRY(ensure_host());
+        reset_chan(c);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int reset() {
+        YG_TRY(ensure_host());
+        for (size_t c = 0; c < C; ++c) reset_chan(c);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    // the words of set_frequency / set_phase for channels [c0, c0 + count): nothing changes where one of them fails
+    int set_nco(size_t c0, size_t count, const float *frequency, const float *phase) {
+        std::vector<uint32_t> w(2 * count);
+        for (size_t i = 0; i < count; ++i) {
+            YG_TRY(osc_constrain(frequency[i], &w[2 * i]));
+            YG_TRY(osc_constrain(phase[i], &w[2 * i + 1]));
+        }
+        YG_TRY(ensure_host());
+        for (size_t i = 0; i < count; ++i) hst[c0 + i].d_theta = w[2 * i], hst[c0 + i].theta = w[2 * i + 1];
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    static int check_block(size_t C, size_t x_pitch, size_t n, size_t y_pitch, bool have_sym, size_t sym_pitch, size_t ycap) {
+        if (n >= ((size_t)1 << 31) || ycap >= ((size_t)1 << 31))
+            return fail(YAGI_ERR_CONFIG, "symtrack: n and ycap must be below 2^31");
+        if (x_pitch < C || y_pitch < C || x_pitch >= ((size_t)1 << 31) || y_pitch >= ((size_t)1 << 31) ||
+            (have_sym && (sym_pitch < C || sym_pitch >= ((size_t)1 << 31))))
+            return fail(YAGI_ERR_CONFIG, "symtrack: the pitches are in elements, at least the channel count and below 2^31");
+        return YAGI_OK;
+    }
+    int block_dev(const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, uint8_t *sym, size_t sym_pitch,
+                  size_t ycap, unsigned *status) {
+        YG_TRY(ensure_dev());
+        YG_TRY(launch_symtrack(loop(), taps_dev.as<float>(), osc_dev.p, map_dev.as<cf32>(), dev_state(), C, x, x_pitch, n, y,
+                               y_pitch, sym, sym_pitch, ycap, status, st));
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_symtrack_cccf_s : SymtrackObj {};
+
+namespace {
+
+int symtrack_make(yagi_hip_symtrack_cccf *q, size_t channels, int ftype, size_t k, size_t m, float beta, int scheme,
+                  const cf32 *table, size_t M, int osc_scheme, size_t npfb, size_t eq_len) {
+    *q = nullptr;
+    auto o = std::make_unique<yagi_hip_symtrack_cccf_s>();
+    YG_TRY(o->configure(channels, ftype, k, m, beta, scheme, table, M, osc_scheme, npfb, eq_len));
+    YG_TRY(o->alloc());
+    *q = o.release();
+    return YAGI_OK;
+}
+
+}  // namespace
+
+#define SYMTRACK_GET(name, T, expr)                                                                 \
+    int yagi_hip_symtrack_cccf_##name(yagi_hip_symtrack_cccf q, T *out) try {                       \
+        CHECK_Q(q);                                                                                 \
+        CHECK_PTR(out);                                                                             \
+        YG_TRY(q->ensure_host());                                                                   \
+        for (size_t c = 0; c < q->C; ++c) out[c] = (expr);                                          \
+        return YAGI_OK;                                                                             \
+    } catch (...) { return ::yagi::api_exception(); }
+
+extern "C" {
+
+int yagi_hip_symtrack_cccf_create(size_t channels, int ftype, size_t k, size_t m, float beta, int scheme, int osc_scheme,
+                                  size_t npfb, size_t eq_len, yagi_hip_symtrack_cccf *q) try {
+    CHECK_PTR(q);
+    return symtrack_make(q, channels, ftype, k, m, beta, scheme, nullptr, 0, osc_scheme, npfb, eq_len);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_create_from_table(size_t channels, int ftype, size_t k, size_t m, float beta, const cf32 *table,
+                                             size_t M, int osc_scheme, size_t npfb, size_t eq_len,
+                                             yagi_hip_symtrack_cccf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    CHECK_PTR(table);
+    return symtrack_make(q, channels, ftype, k, m, beta, YAGI_MODEM_ARB, table, M, osc_scheme, npfb, eq_len);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_destroy(yagi_hip_symtrack_cccf q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_clone(yagi_hip_symtrack_cccf q, yagi_hip_symtrack_cccf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_symtrack_cccf_s>();
+    o->st = q->st;
+    o->C = q->C, o->k = q->k;
+    o->sy.C = q->sy.C, o->sy.k = q->sy.k, o->sy.npfb = q->sy.npfb, o->sy.Ls = q->sy.Ls, o->sy.k_out = q->sy.k_out;
+    o->sy.p = q->sy.p, o->sy.taps = q->sy.taps, o->sy.hs = q->sy.hs, o->sy.hh = q->sy.hh;
+    o->eq.C = q->eq.C, o->eq.h_len = q->eq.h_len, o->eq.mu = q->eq.mu;
+    o->eq.h0 = q->eq.h0, o->eq.hw = q->eq.hw, o->eq.hh = q->eq.hh, o->eq.hs = q->eq.hs;
+    o->ag.C = q->ag.C, o->ag.g = q->ag.g, o->ag.hs = q->ag.hs;
+    o->P = q->P, o->map = q->map, o->nbr = q->nbr;
+    o->vco = q->vco, o->strategy = q->strategy, o->osc = q->osc;
+    o->pll_alpha = q->pll_alpha, o->pll_beta = q->pll_beta, o->bw = q->bw, o->holdoff = q->holdoff;
+    o->hst = q->hst;
+    YG_TRY(o->alloc());
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_set_stream(yagi_hip_symtrack_cccf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_reset(yagi_hip_symtrack_cccf q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_reset_channel(yagi_hip_symtrack_cccf q, size_t c) try {
+    CHECK_Q(q);
+    return q->reset_channel(c);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_set_bandwidth(yagi_hip_symtrack_cccf q, float bw) try {
+    CHECK_Q(q);
+    return q->set_bandwidth(bw);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_get_bandwidth(yagi_hip_symtrack_cccf q, float *bw) try {
+    CHECK_Q(q);
+    CHECK_PTR(bw);
+    *bw = q->bw;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_set_bandwidths(yagi_hip_symtrack_cccf q, float agc, float sync, float eq, float pll) try {
+    CHECK_Q(q);
+    return q->set_bandwidths(agc, sync, eq, pll);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_set_eq_strategy(yagi_hip_symtrack_cccf q, int strategy) try {
+    CHECK_Q(q);
+    if (strategy < YAGI_SYMTRACK_EQ_OFF || strategy > YAGI_SYMTRACK_EQ_DD)
+        return fail(YAGI_ERR_CONFIG, "symtrack: unknown equalizer strategy %d", strategy);
+    q->strategy = strategy;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_set_eq_holdoff(yagi_hip_symtrack_cccf q, uint64_t nsyms) try {
+    CHECK_Q(q);
+    q->holdoff = nsyms;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_set_nco(yagi_hip_symtrack_cccf q, size_t c, float frequency, float phase) try {
+    CHECK_Q(q);
+    if (c >= q->C) return fail(YAGI_ERR_CONFIG, "symtrack: channel %zu of %zu", c, q->C);
+    return q->set_nco(c, 1, &frequency, &phase);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_set_nco_all(yagi_hip_symtrack_cccf q, const float *frequency, const float *phase) try {
+    CHECK_Q(q);
+    CHECK_PTR(frequency);
+    CHECK_PTR(phase);
+    return q->set_nco(0, q->C, frequency, phase);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_get_channels(yagi_hip_symtrack_cccf q, size_t *channels) try {
+    CHECK_Q(q);
+    CHECK_PTR(channels);
+    *channels = q->C;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+SYMTRACK_GET(get_tau, float, q->sy.hs[c].tau_decim)
+SYMTRACK_GET(get_gain, float, q->ag.hs[c].g)
+SYMTRACK_GET(get_rssi, float, agc_rssi(q->ag.hs[c].g))
+SYMTRACK_GET(get_nco_frequency, float, osc_frequency(q->hst[c].d_theta))
+SYMTRACK_GET(get_nco_phase, float, osc_phase(q->hst[c].theta))
+SYMTRACK_GET(get_num_syms, uint64_t, (uint64_t)q->hst[c].num_syms)
+SYMTRACK_GET(get_stalled, uint32_t, q->hst[c].stall)
+
+int yagi_hip_symtrack_cccf_get_nco_state(yagi_hip_symtrack_cccf q, uint32_t *theta, uint32_t *d_theta) try {
+    CHECK_Q(q);
+    CHECK_PTR(theta);
+    CHECK_PTR(d_theta);
+    YG_TRY(q->ensure_host());
+    for (size_t c = 0; c < q->C; ++c) theta[c] = q->hst[c].theta, d_theta[c] = q->hst[c].d_theta;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_get_weights(yagi_hip_symtrack_cccf q, cf32 *w) try {
+    CHECK_Q(q);
+    CHECK_PTR(w);
+    YG_TRY(q->ensure_host());
+    const size_t L = q->eq.h_len;
+    for (size_t c = 0; c < q->C; ++c)
+        for (size_t i = 0; i < L; ++i) {
+            const cf32 v = q->eq.hw[(L - 1 - i) * q->C + c];
+            w[c * L + i] = cf32{v.re, -v.im};
+        }
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_execute_dev(yagi_hip_symtrack_cccf q, const cf32 *x_dev, size_t x_pitch, size_t n, cf32 *y_dev,
+                                       size_t y_pitch, uint8_t *sym_dev, size_t sym_pitch, size_t ycap,
+                                       uint32_t *status_dev) try {
+    CHECK_Q(q);
+    CHECK_PTR(status_dev);
+    YG_TRY(SymtrackObj::check_block(q->C, x_pitch, n, y_pitch, sym_dev != nullptr, sym_pitch, ycap));
+    if (n != 0) CHECK_PTR(x_dev);
+    if (ycap != 0) CHECK_PTR(y_dev);
+    return q->block_dev(x_dev, x_pitch, n, y_dev, y_pitch, sym_dev, sym_pitch, ycap, status_dev);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_execute(yagi_hip_symtrack_cccf q, const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch,
+                                   uint8_t *sym, size_t sym_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled) try {
+    CHECK_Q(q);
+    CHECK_PTR(ny);
+    CHECK_PTR(stalled);
+    const size_t C = q->C;
+    YG_TRY(SymtrackObj::check_block(C, x_pitch, n, y_pitch, sym != nullptr, sym_pitch, ycap));
+    if (n != 0) CHECK_PTR(x);
+    if (ycap != 0) CHECK_PTR(y);
+    const size_t nx = n ? (n - 1) * x_pitch + C : 0;
+    YG_TRY(q->ws.put(q->st, x, nx));
+    YG_TRY(q->ws.y.ensure(ycap * C * sizeof(cf32)));
+    if (sym) YG_TRY(q->wsym.ensure(ycap * C));
+    YG_TRY(q->block_dev(q->ws.x.as<cf32>(), x_pitch, n, q->ws.y.as<cf32>(), C, sym ? q->wsym.as<uint8_t>() : nullptr, C, ycap,
+                        q->wstatus.as<unsigned>()));
+    std::vector<unsigned> status(3 * C);
+    YG_TRY(download(status.data(), q->wstatus.p, 3 * C * sizeof(unsigned), q->st));
+    size_t rows = 0;
+    for (size_t c = 0; c < C; ++c) {
+        ny[c] = status[c];
+        stalled[c] = status[C + c];
+        rows = std::max(rows, (size_t)status[c]);
+    }
+    std::vector<cf32> t(rows * C);
+    YG_TRY(download(t.data(), q->ws.y.p, rows * C * sizeof(cf32), q->st));
+    std::vector<uint8_t> tb(sym ? rows * C : 0);
+    if (sym) YG_TRY(download(tb.data(), q->wsym.p, rows * C, q->st));
+    for (size_t j = 0; j < rows; ++j)
+        for (size_t c = 0; c < C; ++c)
+            if (j < ny[c]) {
+                y[j * y_pitch + c] = t[j * C + c];
+                if (sym) sym[j * sym_pitch + c] = tb[j * C + c];
+            }
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_execute_host(size_t channels, int ftype, size_t k, size_t m, float beta, int scheme,
+                                        const cf32 *table, size_t M, int osc_scheme, size_t npfb, size_t eq_len, float bw,
+                                        int strategy, uint64_t holdoff, const float *nco_frequency, const float *nco_phase,
+                                        const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, uint8_t *sym,
+                                        size_t sym_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled) try {
+    CHECK_PTR(ny);
+    CHECK_PTR(stalled);
+    SymtrackObj o;
+    YG_TRY(o.configure(channels, ftype, k, m, beta, scheme, table, M, osc_scheme, npfb, eq_len));
+    YG_TRY(o.set_bandwidth(bw));
+    if (strategy < YAGI_SYMTRACK_EQ_OFF || strategy > YAGI_SYMTRACK_EQ_DD)
+        return fail(YAGI_ERR_CONFIG, "symtrack: unknown equalizer strategy %d", strategy);
+    o.strategy = strategy, o.holdoff = holdoff;
+    for (size_t c = 0; c < channels; ++c) {
+        if (nco_frequency) YG_TRY(osc_constrain(nco_frequency[c], &o.hst[c].d_theta));
+        if (nco_phase) YG_TRY(osc_constrain(nco_phase[c], &o.hst[c].theta));
+    }
+    YG_TRY(SymtrackObj::check_block(channels, x_pitch, n, y_pitch, sym != nullptr, sym_pitch, ycap));
+    if (n != 0) CHECK_PTR(x);
+    if (ycap != 0) CHECK_PTR(y);
+    std::vector<unsigned> status(3 * channels);
+    symtrack_host(o.loop(), o.sy.taps.data(), o.osc.data(), o.map.data(), o.host_state(), channels, x, x_pitch, n, y, y_pitch,
+                  sym, sym_pitch, ycap, status.data());
+    for (size_t c = 0; c < channels; ++c) ny[c] = status[c], stalled[c] = status[channels + c];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

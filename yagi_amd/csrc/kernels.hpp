@@ -704,6 +704,49 @@ float agc_rssi_gain(float rssi);                       // set_rssi: max(10^(-rss
 float agc_rssi(float g);                               // get_rssi: -20 yg_log10f(g)
 void agc_words_host(int word, const float *x, size_t n, float *y);   // word 0 yg_lnf, 1 yg_expf, 2 yg_log10f
 
+// ---- symtrack_kernels.hip ------------------------------------------------------------------
+// SymTrack (yagi_hip.h): C independent receivers of one design, one lane per channel.  The state is the parts' own: one
+// AgcChan, SymsyncChan and EqlmsChan per channel, the synchroniser's [Ls][C] history, the equalizer's [h_len][C] weights
+// and window, plus one SymtrackChan (the oscillator's words, sync_index, num_syms, the stall reason).  All are updated in
+// place (a workgroup touches its own channels only).  taps as for launch_symsync; osc_tab as for launch_osc_mix; map = the
+// modem's M points followed, on the device, by reference[8] as floats.  status receives ny[C], the stall reason[C] and
+// the low word of num_syms[C].  sym may be null.
+constexpr int kSymtrackWg = 64;                        // channels per workgroup: one wave
+constexpr int kSymtrackAhead = 16;                     // input rows per chunk: requested one chunk ahead, staged in LDS
+constexpr size_t kSymtrackLdsMax = 160 * 1024;
+struct SymtrackChan {
+    uint32_t theta, d_theta;                           // Osc's words
+    uint32_t index, stall;                             // synchroniser outputs since reset (its parity is what counts);
+    unsigned long long num_syms;                       // YAGI_SYMTRACK_STALL_*; symbols since reset, as usize
+};
+static_assert(sizeof(SymtrackChan) == 24, "device layout");
+struct SymtrackLoop {                                  // travels to the kernel by value with every call
+    SymsyncLoop ss;
+    float agc_alpha, agc_scale, eq_mu, pll_alpha, pll_beta;
+    unsigned h_len, vco, strategy, M;
+    int kind, bps;                                     // MODEM_*, never PSK or DPSK
+    unsigned long long holdoff;
+    float ref[8];                                      // reference[]: read by the host form (the kernel reads it behind map)
+};
+struct SymtrackState {
+    AgcChan *agc;
+    SymsyncChan *ss;
+    EqlmsChan *eq;
+    SymtrackChan *st;
+    cf32 *ss_hist, *eq_w, *eq_hist;
+};
+constexpr size_t symtrack_stage_bytes() { return (size_t)kSymtrackAhead * kSymtrackWg * sizeof(cf32); }
+constexpr size_t symtrack_osc_bytes(unsigned vco) { return (size_t)1024 * (vco ? 4 : 2) * sizeof(float); }
+// the LDS a launch needs without the branch taps (which join where they still fit under kSymtrackLdsMax)
+size_t symtrack_lds_bytes(size_t Ls, size_t h_len, int vco, size_t M);
+int launch_symtrack(const SymtrackLoop &p, const float *taps, const void *osc_tab, const cf32 *map, const SymtrackState &s,
+                    size_t C, const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, uint8_t *sym,
+                    size_t sym_pitch, size_t ycap, unsigned *status, hipStream_t st);
+// the same on the host, channel after channel; every pointer a host pointer, map = the M points
+void symtrack_host(const SymtrackLoop &p, const float *taps, const void *osc_tab, const cf32 *map, const SymtrackState &s,
+                   size_t C, const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, uint8_t *sym,
+                   size_t sym_pitch, size_t ycap, unsigned *status);
+
 // ---- symstream_kernels.hip -----------------------------------------------------------------
 // SymStream (yagi_hip.h): samples [0, n) of a call that starts at buf_index p, from the carried window `win` (Ls values,
 // oldest first) and new symbols that come either from the caller's bytes (sym, flag = the result of

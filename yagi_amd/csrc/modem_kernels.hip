@@ -34,22 +34,15 @@
 
 #include "devmath.hpp"
 #include "kernels.hpp"
-
-#define MD_HD __host__ __device__ __forceinline__
+#include "modem_body.hpp"     // md_linear, md_arb_step, the constants: shared with symtrack_kernels.hip
 
 namespace yagi {
 namespace {
 
 constexpr int kWg = kModemWg;
-constexpr float kPi = 3.14159274101257324f;        // std::f32::consts::PI
-constexpr float kTwoPi = 6.28318548202514648f;     // 2.0 * PI
-constexpr float kSqrt2 = 1.41421353816986084f;     // SQRT_2
-constexpr float kRsqrt2 = 0.707106769084930420f;   // FRAC_1_SQRT_2
-
 struct __attribute__((packed, aligned(1))) md_b16 { unsigned v[4]; };     // 16 bytes at any byte address
 struct __attribute__((packed, aligned(8))) md_f16 { float v[4]; };        // two points at a point's alignment
 
-MD_HD unsigned md_gray_encode(unsigned s) { return s ^ (s >> 1); }
 MD_HD unsigned md_gray_decode(unsigned s) {        // modem.rs:521-537 on 8 bits
     s ^= s >> 4;
     s ^= s >> 2;
@@ -61,23 +54,6 @@ MD_HD uint8_t md_soft_byte(float v) {
     if (!(v >= 0.0f)) v = 0.0f;
     if (v > 255.0f) v = 255.0f;
     return (uint8_t)(int)v;
-}
-// demodulate_linear_array_ref :296-315
-template <int m>
-MD_HD unsigned md_linear(const float *ref, float v, float &res) {
-    unsigned s = 0;
-#pragma unroll
-    for (int k = 0; k < m; ++k) {
-        s <<= 1;
-        if (v > 0.0f) {
-            s |= 1;
-            v -= ref[m - k - 1];
-        } else {
-            v += ref[m - k - 1];
-        }
-    }
-    res = v;
-    return s;
 }
 MD_HD float md_atan2(float y, float x) { return atan2f(y, x); }
 MD_HD cf32 md_polar1(float a) {                     // Complex32::from_polar(1.0, a)
@@ -180,27 +156,6 @@ MD_HD unsigned md_demod(const ModemParams &P, const cf32 *map, const uint8_t *nb
     return s;
 }
 
-// One table entry of Arb's search for one sample (arb.rs:21-35 hard on squared distances, :37-74 soft with the bit of
-// the running best index).
-template <int BPS, bool SOFT>
-MD_HD void md_arb_step(cf32 x, cf32 c, unsigned idx, float &dmin, unsigned &s, float *d0, float *d1) {
-    const float er = x.re - c.re, ei = x.im - c.im;
-    const float d = er * er + ei * ei;
-    if (d < dmin) {
-        dmin = d;
-        s = idx;
-    }
-    if constexpr (SOFT) {
-#pragma unroll
-        for (int k = 0; k < BPS; ++k) {
-            // as selects on values: a select between the two ADDRESSES would send both arrays to scratch
-            const bool one = ((s >> (BPS - k - 1)) & 1u) != 0;
-            const float m0 = d < d0[k] ? d : d0[k], m1 = d < d1[k] ? d : d1[k];
-            d0[k] = one ? d0[k] : m0;
-            d1[k] = one ? m1 : d1[k];
-        }
-    }
-}
 template <int BPS>
 MD_HD void md_arb_soft(const ModemParams &P, const float *d0, const float *d1, uint8_t *sb) {
 #pragma unroll

@@ -12,7 +12,7 @@ template <int VCO> struct OscEntry { using E = float2; };    // NCO {sin, cos}
 template <> struct OscEntry<1> { using E = float4; };          // VCO {v_sin, s_sin, v_cos, s_cos}
 
 template <int VCO, bool DOWN>
-__device__ __forceinline__ float2 osc_one(const typename OscEntry<VCO>::E *tab, uint32_t theta, float xr, float xi) {
+__host__ __device__ __forceinline__ float2 osc_one(const typename OscEntry<VCO>::E *tab, uint32_t theta, float xr, float xi) {
     float s, c;
     if constexpr (!VCO) {
         const float2 e = tab[(theta + (1u << 21)) >> 22];
