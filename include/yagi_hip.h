@@ -1839,7 +1839,7 @@ int yagi_hip_symsync_crcf_execute_host(size_t channels, size_t k, size_t npfb, c
  *                             YAGI_EQLMS_EXECUTE for execute_block; w0[channels][h_len] may be NULL
  * Every result is independent of how the stream is cut into calls.  The pitches are in samples and >= channels; n is below
  * 2^31.  x, d and y must not overlap.
- * Not built: Eqrls, rrrf, per-channel designs or step sizes, sharding.
+ * Not built: rrrf, per-channel designs or step sizes, sharding.
  * Device form: eqlms_kernels.hip: one lane per channel, one wave per workgroup. */
 #define YAGI_EQLMS_LEN_MAX 128
 #define YAGI_EQLMS_CHANNELS_MAX 1048576
@@ -1873,6 +1873,96 @@ int yagi_hip_eqlms_cccf_decim_block_dev(yagi_hip_eqlms_cccf q, size_t k, int mod
 int yagi_hip_eqlms_cccf_execute_host(size_t channels, const yagi_cf32 *h, size_t h_len, float mu, int call, size_t k,
                                      const yagi_cf32 *x, size_t x_pitch, size_t n, const yagi_cf32 *d, size_t d_pitch,
                                      const yagi_cf32 *table, size_t M, yagi_cf32 *y, size_t y_pitch, yagi_cf32 *w0);
+
+/* ---- EqRls: recursive-least-squares equalizer for a bank of channels (src/equalization/eqrls.rs) --------------------
+ * EqRls(channels, h[p] or NULL, p): `channels` independent Eqrls<Complex32> objects of one design (cccf only).  A block is
+ * x[s x_pitch + c], step s, channel c < channels; per channel every output word and every word of w0, w1 and P0 equals
+ * the reference's sequential loop, in f32 with every product, sum and quotient rounded on its own (no FMA).  Products
+ * and quotients are num-complex's: a b = (a.re b.re - a.im b.im, a.re b.im + a.im b.re); a / b = ((a.re b.re + a.im b.im)
+ * / n, (a.im b.re - a.re b.im) / n) with n = b.re b.re + b.im b.im; sums fold from Complex(0, 0).
+ *     new (:31-62)         h0 = h as given (no reversal, no conjugate, unlike Eqlms); h = NULL: h0[p - 1] = 1;
+ *                          lambda = 0.99f, delta = 0.1f, w1 = 0
+ *     reset (:76-88)       P0 = diag(1.0f / 0.1f), w0 = h0, the window zeroed; w1 is NOT touched
+ *     execute (:106-110)   y = sum_i w0[i] r[i] over the window oldest first, NO conjugate
+ *     step(d, d_hat) (:112-146)   no buf_full gate, it updates from the first sample.  x = the window, oldest first:
+ *                          alpha = d - d_hat;  xp0[c] = sum_r x[r] P0[r][c];  zeta = (sum_c xp0[c] conj(x[c])) +
+ *                          Complex(lambda, 0);  g[r] = (sum_c P0[r][c] conj(x[c])) / zeta;  gxl[r][c] = (g[r] x[c]) /
+ *                          Complex(lambda, 0), the full complex quotient (n = lambda lambda + 0 0, re = (a.re lambda +
+ *                          a.im 0) / n), not a.re / lambda;  gxlp0[r][c] = sum_i gxl[r][i] P0[i][c], the p^3 term, never
+ *                          regrouped;  P1 = P0 / Complex(lambda, 0) - gxlp0;  w1[i] = w0[i] + alpha g[i];  w0 = w1, P0 = P1
+ * Every division is a true IEEE f32 division.  A NaN or Inf sample or a singular zeta changes its own channel only; there
+ * is no stall state.
+ *   create(channels, h, p)    p = 0 is YAGI_ERR_CONFIG as in the reference; 1 <= p <= YAGI_EQRLS_LEN_MAX, 1 <= channels <=
+ *                             YAGI_EQRLS_CHANNELS_MAX and channels p p <= 2^26 (512 MiB of P), decided before any device
+ *                             is asked for
+ *   recreate(h, p)            (:64-74) the same p: h0 = h where h is given, NOTHING else changes (no reset); another p: a
+ *                             new object of the same channel count, stream and constellation (lambda back to 0.99f)
+ *   destroy / clone / set_stream / reset / reset_channel(c)
+ *   set_bw(lambda) / get_bw   lambda outside [0, 1] or NaN is YAGI_ERR_CONFIG; lambda = 0 is accepted and gives the bank
+ *                             Inf / NaN, as in the reference; one value for the bank
+ *   get_length / get_channels
+ *   get_coefficients(out[channels][p])   w0.   get_weights(out[channels][p])   w1 REVERSED (:148-156), not w0: zero between
+ *                             create and the first update, and after reset() still the weights from before the reset.
+ *                             The library reproduces this.   get_matrix(out[channels][p][p])   P0.   They synchronise
+ *   set_constellation(table, M)   DECISION's table, 1 <= M <= YAGI_EQLMS_TABLE_MAX, copied
+ *   step_block(k, mode, x, x_pitch, n, d, d_pitch, y, y_pitch)   n rows in, a multiple of k >= 1; per symbol i < n / k:
+ *                             push x[i k], y[i] = execute(), the update, THEN push the other k - 1 rows.  The update
+ *                             comes BEFORE the trailing pushes, because the gain must be formed from the window that
+ *                             produced d_hat (the reference's train, :169-173, is push, execute, step).  This differs
+ *                             from EqLms.decim_block, which updates after them.  mode: YAGI_EQRLS_NONE no update; TRAIN
+ *                             step(d[i d_pitch + c], y); DECISION step(table[j], y) with EqLms's decision rule (its
+ *                             deviation 2).  d is read by TRAIN only
+ *   train(w[channels][p], x, x_pitch, n, d, d_pitch)   (:158-176) n < p is YAGI_ERR_CONFIG; reset(), w0[i] = w[p - 1 - i],
+ *                             n TRAIN steps at k = 1 (the outputs are dropped), get_weights written back into w
+ *   step_block_dev / train_dev   the same on device pointers, asynchronous on the object's stream; train_dev's w is a
+ *                             HOST array, read before the launch, and is not written: call get_weights afterwards
+ *   execute_host(channels, h, p, lambda, mode, k, x, x_pitch, n, d, d_pitch, table, M, y, y_pitch, w0, w1, P0)   the
+ *                             definition on the host alone, one call from reset(), no device needed; w0, w1[channels][p]
+ *                             and P0[channels][p][p] may be NULL
+ *   plan(channels, p, L, lds_bytes, admissible)   the launch shape: L lanes share one channel's step (a power of two), a
+ *                             wave holds 64 / L channels in lds_bytes of LDS; bit b of admissible = (L = 2^b may be set)
+ *   set_lanes(L) / get_lanes  override the planner; 0 gives the choice back to it.  For every admissible L the results
+ *                             are the same words
+ * Every result is independent of how the stream is cut into calls.  The pitches are in samples and >= channels; n is below
+ * 2^31.  x, d and y must not overlap.
+ * Not built: rrrf, blind (CM) updates, per-channel lambda or designs, an O(p^2) regrouped recursion (it changes the
+ * words), SymTrack with an RLS equalizer, sharding.
+ * Device form: eqrls_kernels.hip: L lanes per channel, one wave per workgroup. */
+#define YAGI_EQRLS_LEN_MAX 32
+#define YAGI_EQRLS_CHANNELS_MAX 1048576
+#define YAGI_EQRLS_MATRIX_MAX 67108864 /* channels p p */
+enum { YAGI_EQRLS_NONE = 0, YAGI_EQRLS_TRAIN = 1, YAGI_EQRLS_DECISION = 3 };   /* numbered as YAGI_EQLMS_* */
+typedef struct yagi_hip_eqrls_cccf_s *yagi_hip_eqrls_cccf;
+int yagi_hip_eqrls_cccf_create(size_t channels, const yagi_cf32 *h, size_t p, yagi_hip_eqrls_cccf *q);
+int yagi_hip_eqrls_cccf_recreate(yagi_hip_eqrls_cccf q, const yagi_cf32 *h, size_t p);
+int yagi_hip_eqrls_cccf_destroy(yagi_hip_eqrls_cccf q);
+int yagi_hip_eqrls_cccf_clone(yagi_hip_eqrls_cccf q, yagi_hip_eqrls_cccf *out);
+int yagi_hip_eqrls_cccf_set_stream(yagi_hip_eqrls_cccf q, yagi_stream_t s);
+int yagi_hip_eqrls_cccf_reset(yagi_hip_eqrls_cccf q);
+int yagi_hip_eqrls_cccf_reset_channel(yagi_hip_eqrls_cccf q, size_t c);
+int yagi_hip_eqrls_cccf_set_bw(yagi_hip_eqrls_cccf q, float lambda);
+int yagi_hip_eqrls_cccf_get_bw(yagi_hip_eqrls_cccf q, float *lambda);
+int yagi_hip_eqrls_cccf_get_length(yagi_hip_eqrls_cccf q, size_t *p);
+int yagi_hip_eqrls_cccf_get_channels(yagi_hip_eqrls_cccf q, size_t *channels);
+int yagi_hip_eqrls_cccf_get_coefficients(yagi_hip_eqrls_cccf q, yagi_cf32 *w0);
+int yagi_hip_eqrls_cccf_get_weights(yagi_hip_eqrls_cccf q, yagi_cf32 *w);
+int yagi_hip_eqrls_cccf_get_matrix(yagi_hip_eqrls_cccf q, yagi_cf32 *P0);
+int yagi_hip_eqrls_cccf_set_constellation(yagi_hip_eqrls_cccf q, const yagi_cf32 *table, size_t M);
+int yagi_hip_eqrls_cccf_set_lanes(yagi_hip_eqrls_cccf q, size_t L);
+int yagi_hip_eqrls_cccf_get_lanes(yagi_hip_eqrls_cccf q, size_t *L);
+int yagi_hip_eqrls_cccf_step_block(yagi_hip_eqrls_cccf q, size_t k, int mode, const yagi_cf32 *x, size_t x_pitch, size_t n,
+                                   const yagi_cf32 *d, size_t d_pitch, yagi_cf32 *y, size_t y_pitch);
+int yagi_hip_eqrls_cccf_step_block_dev(yagi_hip_eqrls_cccf q, size_t k, int mode, const yagi_cf32 *x_dev, size_t x_pitch,
+                                       size_t n, const yagi_cf32 *d_dev, size_t d_pitch, yagi_cf32 *y_dev, size_t y_pitch);
+int yagi_hip_eqrls_cccf_train(yagi_hip_eqrls_cccf q, yagi_cf32 *w, const yagi_cf32 *x, size_t x_pitch, size_t n,
+                              const yagi_cf32 *d, size_t d_pitch);
+int yagi_hip_eqrls_cccf_train_dev(yagi_hip_eqrls_cccf q, const yagi_cf32 *w, const yagi_cf32 *x_dev, size_t x_pitch, size_t n,
+                                  const yagi_cf32 *d_dev, size_t d_pitch);
+int yagi_hip_eqrls_cccf_execute_host(size_t channels, const yagi_cf32 *h, size_t p, float lambda, int mode, size_t k,
+                                     const yagi_cf32 *x, size_t x_pitch, size_t n, const yagi_cf32 *d, size_t d_pitch,
+                                     const yagi_cf32 *table, size_t M, yagi_cf32 *y, size_t y_pitch, yagi_cf32 *w0,
+                                     yagi_cf32 *w1, yagi_cf32 *P0);
+int yagi_hip_eqrls_plan(size_t channels, size_t p, size_t *L, size_t *lds_bytes, unsigned *admissible);
 
 /* ---- Agc: automatic gain control for a bank of channels (src/agc/agc.rs) ---------------------------------------------
  * Agc(channels): `channels` independent Agc<T> objects of one set of settings, T = Complex<f32> (crcf) or f32 (rrrf).  A

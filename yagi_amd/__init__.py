@@ -21,6 +21,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     PreambleDetector           (absent from the reference: a bank of known-preamble correlators, threshold and events)
     SymSync                    src/filter/symsync.rs:37-276, one object per channel of a bank
     EqLms, EqLmsUpdate         src/equalization/eqlms.rs:25-199, one object per channel of a bank
+    EqRls, EqRlsUpdate         src/equalization/eqrls.rs:31-176, one object per channel of a bank
     SymTrack, SymTrackEq       (src/framing/symtrack.rs is empty: Agc -> SymSync -> Osc -> EqLms -> Modem, loops closed)
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
@@ -40,7 +41,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "EqLms", "EqLmsUpdate", "SymTrack", "SymTrackEq", "symtrack_host", "SYMTRACK_CHANNELS_MAX", "SYMTRACK_PLL_ARG_MAX", "SYMTRACK_STALL_CAPACITY", "SYMTRACK_STALL_PLL", "EQLMS_LEN_MAX", "EQLMS_CHANNELS_MAX", "EQLMS_TABLE_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "EqLms", "EqLmsUpdate", "EqRls", "EqRlsUpdate", "eqrls_plan", "EQRLS_LEN_MAX", "EQRLS_CHANNELS_MAX", "EQRLS_MATRIX_MAX", "SymTrack", "SymTrackEq", "symtrack_host", "SYMTRACK_CHANNELS_MAX", "SYMTRACK_PLL_ARG_MAX", "SYMTRACK_STALL_CAPACITY", "SYMTRACK_STALL_PLL", "EQLMS_LEN_MAX", "EQLMS_CHANNELS_MAX", "EQLMS_TABLE_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "SpgramPlan", "plan_spgram", "MsResamp2Plan", "Resamp2Plan", "plan_msresamp2", "plan_resamp2", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
@@ -2461,7 +2462,203 @@ class EqLms(_Handle):
         return y, w0
 
 
-AGC_CHANNELS_MAX = 1 << 20         # YAGI_AGC_CHANNELS_MAX
+EQRLS_LEN_MAX = 32                 # YAGI_EQRLS_LEN_MAX: the largest order p of EqRls
+EQRLS_CHANNELS_MAX = 1 << 20       # YAGI_EQRLS_CHANNELS_MAX
+EQRLS_MATRIX_MAX = 1 << 26         # YAGI_EQRLS_MATRIX_MAX: channels p p, 512 MiB of P
+
+
+class EqRlsUpdate(enum.IntEnum):
+    """what EqRls.step_block does after each symbol's output, numbered as YAGI_EQRLS_* (and so as EqLmsUpdate)"""
+    NONE = 0        # a fixed filter
+    TRAIN = 1       # step(d, y) against known symbols
+    DECISION = 3    # step(table[j], y) against the nearest point of set_constellation's table
+
+
+def eqrls_plan(channels, p):
+    """the launch shape of EqRls(channels, p): (L, lds_bytes, admissible).  L lanes share one channel's step, a wave
+    holds 64 // L channels in lds_bytes of LDS; admissible lists every L that set_lanes accepts.  No device needed"""
+    channels, p = _symsync_size(channels, "channels"), _symsync_size(p, "p")
+    L, lds, mask = C.c_size_t(), C.c_size_t(), C.c_uint()
+    _check(lib.yagi_hip_eqrls_plan(channels, p, C.byref(L), C.byref(lds), C.byref(mask)))
+    return L.value, lds.value, [1 << b for b in range(7) if mask.value >> b & 1]
+
+
+class EqRls(_Handle):
+    """EqRls(channels, p, h=None): `channels` independent equalization::eqrls::Eqrls<Complex32> objects of one design
+    (src/equalization/eqrls.rs), Complex<f32> only.  A block is x[n, channels] (step, channel); per channel every output
+    word and every word of w0, w1 and P0 is the reference's sequential loop bit for bit: y = sum w0[i] r[i] over the window
+    oldest first (no conjugate), and the O(p^3) update of step (:112-146) with every product, sum and complex quotient
+    rounded on its own (yagi_hip.h).  lambda = 0.99 and delta = 0.1 after create.
+    get_weights is w1 reversed, not w0, as in the reference: zero before the first update and kept across reset().
+    The block calls run eqrls_kernels.hip, L lanes per channel (eqrls_plan, set_lanes); the words do not depend on L.
+    p <= EQRLS_LEN_MAX, channels <= EQRLS_CHANNELS_MAX, channels p p <= EQRLS_MATRIX_MAX."""
+    _prefix = "yagi_hip_eqrls_cccf_"
+
+    def __init__(self, channels, p, h=None, kind="cccf"):
+        """Eqrls::new (:31-62): h0 = h as given; h = None: h0[p - 1] = 1"""
+        if kind != "cccf":
+            raise ConfigError(f"unknown type combination {kind!r}")
+        channels, p = _symsync_size(channels, "channels"), _symsync_size(p, "p")
+        h = self._taps(h, p)
+        hd = C.c_void_p()
+        _check(self._fn("create")(channels, None if h is None else _ptr(h), p, C.byref(hd)))
+        self._set(hd, channels)
+
+    @staticmethod
+    def _taps(h, p):
+        if h is not None:
+            h = _arr(h, np.complex64)
+            if h.ndim != 1 or h.size != p:
+                raise ConfigError("the taps are one-dimensional, p of them")
+        return h
+
+    def _set(self, hd, channels):
+        self._h, self.kind, self.T, self.channels = hd, "cccf", np.complex64, channels
+        v = C.c_size_t()
+        _check(self._fn("get_length")(self._h, C.byref(v)))
+        self.p = v.value
+
+    def recreate(self, p, h=None):
+        """Eqrls::recreate (:64-74): the same p only replaces h0 (where h is given) and resets nothing; another p is a new
+        bank of the same channel count"""
+        p = _symsync_size(p, "p")
+        h = self._taps(h, p)
+        _check(self._fn("recreate")(self._h, None if h is None else _ptr(h), p))
+        self._set(self._h, self.channels)
+
+    def clone(self):
+        new, hd = object.__new__(type(self)), C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._set(hd, self.channels)
+        return new
+
+    def reset_channel(self, c):
+        _check(self._fn("reset_channel")(self._h, _symsync_size(c, "channel")))
+
+    def set_bw(self, lam):
+        """the forgetting factor lambda in [0, 1], one value for the bank"""
+        _check(self._fn("set_bw")(self._h, lam))
+
+    def get_bw(self):
+        v = C.c_float()
+        _check(self._fn("get_bw")(self._h, C.byref(v)))
+        return v.value
+
+    def get_length(self):
+        return self.p
+
+    def set_lanes(self, L):
+        """L lanes per channel instead of the planner's choice (0 gives the choice back); L must be admissible for p"""
+        _check(self._fn("set_lanes")(self._h, _symsync_size(L, "L")))
+
+    def get_lanes(self):
+        v = C.c_size_t()
+        _check(self._fn("get_lanes")(self._h, C.byref(v)))
+        return v.value
+
+    def get_coefficients(self):
+        """w0[channels, p]; synchronises"""
+        out = np.zeros((self.channels, self.p), self.T)
+        _check(self._fn("get_coefficients")(self._h, _ptr(out)))
+        return out
+
+    def get_weights(self):
+        """w1 reversed, [channels, p] (:148-156); synchronises"""
+        out = np.zeros((self.channels, self.p), self.T)
+        _check(self._fn("get_weights")(self._h, _ptr(out)))
+        return out
+
+    def get_matrix(self):
+        """P0[channels, p, p]; synchronises"""
+        out = np.zeros((self.channels, self.p, self.p), self.T)
+        _check(self._fn("get_matrix")(self._h, _ptr(out)))
+        return out
+
+    def set_constellation(self, table):
+        """DECISION's table, 1 .. EQLMS_TABLE_MAX points"""
+        table = _arr(table, self.T)
+        if table.ndim != 1:
+            raise ConfigError("the constellation is one-dimensional")
+        _check(self._fn("set_constellation")(self._h, _ptr(table), table.size))
+
+    def _block(self, x):
+        x = _arr(x, self.T)
+        if x.ndim != 2 or x.shape[1] != self.channels:
+            raise ConfigError(f"the block is [steps, {self.channels}]")
+        return x
+
+    def step_block(self, k, mode, x, d=None):
+        """x[n k, channels] -> y[n, channels]: per symbol push x[i k], y[i] = execute(), one update of `mode` (EqRlsUpdate),
+        then the other k - 1 pushes; d[n, channels] are TRAIN's known symbols"""
+        x, k = self._block(x), _symsync_size(k, "k")
+        if d is not None:
+            d = self._block(d)
+            if k and d.shape[0] * k != x.shape[0]:
+                raise ConfigError("d holds one row per symbol")
+        y = np.zeros((x.shape[0] // max(k, 1), self.channels), self.T)
+        _check(self._fn("step_block")(self._h, k, int(mode), _ptr(x), self.channels, x.shape[0],
+                                      None if d is None else _ptr(d), self.channels, _ptr(y), self.channels))
+        return y
+
+    def train(self, w, x, d):
+        """Eqrls::train (:158-176): reset(), w0[i] = w[c, p - 1 - i], one TRAIN step per row of x[n, channels] against
+        d[n, channels]; returns get_weights()"""
+        w, x, d = _arr(w, self.T).copy(), self._block(x), self._block(d)
+        if w.shape != (self.channels, self.p):
+            raise ConfigError("w is [channels, p]")
+        if d.shape != x.shape:
+            raise ConfigError("d holds one row per row of x")
+        _check(self._fn("train")(self._h, _ptr(w), _ptr(x), self.channels, x.shape[0], _ptr(d), self.channels))
+        return w
+
+    def step_block_devptr(self, k, mode, x_dev, x_pitch, n, d_dev, d_pitch, y_dev, y_pitch):
+        """x_dev: n rows (a multiple of k); d_dev: n / k rows of known symbols, None unless TRAIN; y_dev: n / k rows.
+        Asynchronous on the object's stream (the C ABI's step_block_dev)"""
+        x_dev, d_dev, y_dev = (None if p is None else _devptr(p) for p in (x_dev, d_dev, y_dev))
+        _check(self._fn("step_block_dev")(self._h, k, int(mode), x_dev, x_pitch, n, d_dev, d_pitch, y_dev, y_pitch))
+
+    def train_devptr(self, w, x_dev, x_pitch, n, d_dev, d_pitch):
+        """train on device pointers (the C ABI's train_dev): w[channels, p] is a host array read before the launch; the
+        call is asynchronous on the object's stream and get_weights() returns the result"""
+        w = _arr(w, self.T)
+        if w.shape != (self.channels, self.p):
+            raise ConfigError("w is [channels, p]")
+        x_dev, d_dev = (None if p is None else _devptr(p) for p in (x_dev, d_dev))
+        _check(self._fn("train_dev")(self._h, _ptr(w), x_dev, x_pitch, n, d_dev, d_pitch))
+
+    @staticmethod
+    def execute_host(channels, p, h, lam, k, x, mode=EqRlsUpdate.NONE, d=None, table=None, x_pitch=None, d_pitch=None,
+                     y_pitch=None):
+        """the definition on the host alone, no device needed: one step_block call from reset().  x is [n, x_pitch] (the
+        pitches default to channels); returns (y[rows, y_pitch], w0[channels, p], w1[channels, p], P0[channels, p, p]).
+        The library's own sequential form, slow and meant for checks"""
+        channels, p, k = (_symsync_size(v, "argument") for v in (channels, p, k))
+        if not 1 <= channels <= EQRLS_CHANNELS_MAX:
+            raise ConfigError("channels must be in 1 .. EQRLS_CHANNELS_MAX")
+        x_pitch, d_pitch, y_pitch = (channels if v is None else _symsync_size(v, "pitch") for v in (x_pitch, d_pitch, y_pitch))
+        x = _arr(x, np.complex64)
+        if x.ndim != 2 or x.shape[1] != x_pitch:
+            raise ConfigError("the block is [steps, x_pitch]")
+        h = EqRls._taps(h, p)
+        if d is not None:
+            d = _arr(d, np.complex64)
+            if d.ndim != 2 or d.shape[1] != d_pitch or d.shape[0] * max(k, 1) != x.shape[0]:
+                raise ConfigError("d is [symbols, d_pitch]")
+        if table is not None:
+            table = _arr(table, np.complex64).reshape(-1)
+        n = x.shape[0]
+        y = np.zeros((n // max(k, 1), y_pitch), np.complex64)
+        pc = min(p, EQRLS_LEN_MAX)
+        w0, w1 = np.zeros((channels, pc), np.complex64), np.zeros((channels, pc), np.complex64)
+        P0 = np.zeros((channels, pc, pc) if channels * pc * pc <= EQRLS_MATRIX_MAX else (0, pc, pc), np.complex64)
+        _check(lib.yagi_hip_eqrls_cccf_execute_host(
+            channels, None if h is None else _ptr(h), p, lam, int(mode), k, _ptr(x), x_pitch, n,
+            None if d is None else _ptr(d), d_pitch, None if table is None else _ptr(table),
+            0 if table is None else table.size, _ptr(y), y_pitch, _ptr(w0), _ptr(w1), _ptr(P0)))
+        return y, w0, w1, P0
+
+
+AGC_CHANNELS_MAX = 1 << 20        # YAGI_AGC_CHANNELS_MAX
 
 
 class AgcSquelchMode(enum.IntEnum):

@@ -711,8 +711,34 @@ _sig(_p + "decim_block", vp, sz, ci, vp, sz, sz, vp, sz, vp, sz)
 _sig(_p + "decim_block_dev", vp, sz, ci, vp, sz, sz, vp, sz, vp, sz)
 _sig(_p + "execute_host", sz, vp, sz, f32, ci, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz, vp)
 
+# ---- EqRls -------------------------------------------------------------------------------------
+_p = "yagi_hip_eqrls_cccf_"
+_sig(_p + "create", sz, vp, sz, pvp)
+_sig(_p + "recreate", vp, vp, sz)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "reset", vp)
+_sig(_p + "reset_channel", vp, sz)
+_sig(_p + "set_bw", vp, f32)
+_sig(_p + "get_bw", vp, C.POINTER(f32))
+_sig(_p + "get_length", vp, C.POINTER(sz))
+_sig(_p + "get_channels", vp, C.POINTER(sz))
+_sig(_p + "get_coefficients", vp, vp)
+_sig(_p + "get_weights", vp, vp)
+_sig(_p + "get_matrix", vp, vp)
+_sig(_p + "set_constellation", vp, vp, sz)
+_sig(_p + "set_lanes", vp, sz)
+_sig(_p + "get_lanes", vp, C.POINTER(sz))
+_sig(_p + "step_block", vp, sz, ci, vp, sz, sz, vp, sz, vp, sz)
+_sig(_p + "step_block_dev", vp, sz, ci, vp, sz, sz, vp, sz, vp, sz)
+_sig(_p + "train", vp, vp, vp, sz, sz, vp, sz)
+_sig(_p + "train_dev", vp, vp, vp, sz, sz, vp, sz)
+_sig(_p + "execute_host", sz, vp, sz, f32, ci, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz, vp, vp, vp)
+_sig("yagi_hip_eqrls_plan", sz, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_uint))
+
 # ---- Agc ---------------------------------------------------------------------------------------
-u8p = C.POINTER(C.c_uint8)
+u8p =C.POINTER(C.c_uint8)
 for _n in ("lnf", "expf", "log10f"):
     _sig("yagi_hip_" + _n, vp, sz, vp)
 for _k in ("crcf", "rrrf"):

@@ -7417,6 +7417,400 @@ int yagi_hip_eqlms_cccf_execute_host(size_t channels, const cf32 *h, size_t h_le
 
 }  // extern "C"
 
+// ---- EqRls (src/equalization/eqrls.rs, one object per channel) -----------------------------------------------------
+// The state is P0 [p p][channels], w0, w1 and the window, [p][channels] each; eqrls_kernels.hip updates all four in place
+// on the device.  reset, reset_channel, recreate, train's preparation, the getters and clone work on a host mirror; the two
+// copies are synchronised lazily (Mirror).  lambda, k, the mode and the lanes per channel travel to the kernel by value.
+namespace yagi {
+
+struct EqrlsObj {
+    hipStream_t st = nullptr;
+    size_t C = 0, p = 0, lanes = 0;                       // lanes: set_lanes' override, 0 = the planner's choice
+    float lambda = 0.99f;
+    std::vector<cf32> h0, table;
+    DevBuf P_dev, w0_dev, w1_dev, hist_dev, table_dev;
+    std::vector<cf32> hP, hw0, hw1, hh;                   // host mirror: [p p][C] and [p][C]
+    Mirror mirror;
+    Staging ws, wsd;                                      // host block forms: x and a compact y; the rows of d
+
+    // reset (:76-88): w1 stays
+    void reset_chan(size_t c) {
+        const float d = 1.0f / 0.1f;
+        for (size_t i = 0; i < p; ++i) {
+            for (size_t j = 0; j < p; ++j) hP[(i * p + j) * C + c] = cf32{i == j ? d : 0.0f, 0.0f};
+            hw0[i * C + c] = h0[i];
+            hh[i * C + c] = cf32{0.0f, 0.0f};
+        }
+    }
+    // new (:31-62); everything that needs no device
+    static int check_design(size_t channels, size_t p_) {
+        if (channels == 0 || channels > (size_t)YAGI_EQRLS_CHANNELS_MAX)
+            return fail(YAGI_ERR_CONFIG, "eqrls: %zu channels are outside 1 .. YAGI_EQRLS_CHANNELS_MAX", channels);
+        if (p_ == 0) return fail(YAGI_ERR_CONFIG, "equalizer length must be greater than 0");
+        if (p_ > (size_t)YAGI_EQRLS_LEN_MAX)
+            return fail(YAGI_ERR_CONFIG, "eqrls: %zu taps are more than YAGI_EQRLS_LEN_MAX", p_);
+        if (channels * p_ * p_ > (size_t)YAGI_EQRLS_MATRIX_MAX)
+            return fail(YAGI_ERR_CONFIG, "eqrls: %zu channels of %zu x %zu are more than YAGI_EQRLS_MATRIX_MAX", channels, p_, p_);
+        return YAGI_OK;
+    }
+    int configure(size_t channels, const cf32 *h, size_t p_) {
+        YG_TRY(check_design(channels, p_));
+        C = channels, p = p_, lambda = 0.99f, lanes = 0;
+        h0.assign(p, cf32{0.0f, 0.0f});
+        if (h)
+            std::copy(h, h + p, h0.begin());
+        else
+            h0[p - 1] = cf32{1.0f, 0.0f};
+        hP.assign(p * p * C, cf32{});
+        hw0.assign(p * C, cf32{});
+        hw1.assign(p * C, cf32{});
+        hh.assign(p * C, cf32{});
+        for (size_t c = 0; c < C; ++c) reset_chan(c);
+        return YAGI_OK;
+    }
+    int alloc() {
+        YG_TRY(require_device());
+        YG_TRY(P_dev.alloc(p * p * C * sizeof(cf32)));
+        YG_TRY(w0_dev.alloc(p * C * sizeof(cf32)));
+        YG_TRY(w1_dev.alloc(p * C * sizeof(cf32)));
+        YG_TRY(hist_dev.alloc(p * C * sizeof(cf32)));
+        if (!table.empty()) {
+            YG_TRY(fill(table_dev, table.data(), table.size() * sizeof(cf32), st));
+        }
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] {
+            YG_TRY(download(hP.data(), P_dev.p, p * p * C * sizeof(cf32), st));
+            YG_TRY(download(hw0.data(), w0_dev.p, p * C * sizeof(cf32), st));
+            YG_TRY(download(hw1.data(), w1_dev.p, p * C * sizeof(cf32), st));
+            return download(hh.data(), hist_dev.p, p * C * sizeof(cf32), st);
+        });
+    }
+    int ensure_dev() {
+        return mirror.need_dev([&] {
+            YG_TRY(upload(P_dev.p, hP.data(), p * p * C * sizeof(cf32), st));
+            YG_TRY(upload(w0_dev.p, hw0.data(), p * C * sizeof(cf32), st));
+            YG_TRY(upload(w1_dev.p, hw1.data(), p * C * sizeof(cf32), st));
+            return upload(hist_dev.p, hh.data(), p * C * sizeof(cf32), st);
+        });
+    }
+    int reset_channel(size_t c) {
+        if (c >= C) return fail(YAGI_ERR_CONFIG, "eqrls: channel %zu of %zu", c, C);
+        YG_TRY(ensure_host());
+        reset_chan(c);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int reset() {
+        YG_TRY(ensure_host());
+        for (size_t c = 0; c < C; ++c) reset_chan(c);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    static int set_bw(float l, float *lambda) {             // (:94-100)
+        if (!(l >= 0.0f && l <= 1.0f)) return fail(YAGI_ERR_CONFIG, "learning rate must be in (0,1)");
+        *lambda = l;
+        return YAGI_OK;
+    }
+    static int check_lanes(size_t p, size_t L) {
+        unsigned b = 0;
+        while (b < 6 && ((size_t)1 << b) < L) ++b;
+        if (((size_t)1 << b) != L || !(eqrls_admissible(p) >> b & 1u))
+            return fail(YAGI_ERR_CONFIG, "eqrls: %zu lanes per channel are not admissible at p = %zu", L, p);
+        return YAGI_OK;
+    }
+    // sets the rows of y
+    static int check_block(size_t C, int mode, size_t k, size_t x_pitch, size_t n, bool have_d, size_t d_pitch, size_t M,
+                           size_t y_pitch, size_t *rows) {
+        if (mode != YAGI_EQRLS_NONE && mode != YAGI_EQRLS_TRAIN && mode != YAGI_EQRLS_DECISION)
+            return fail(YAGI_ERR_CONFIG, "eqrls: unknown update mode %d", mode);
+        if (k == 0) return fail(YAGI_ERR_CONFIG, "eqrls: k must be greater than 0");
+        if (n >= ((size_t)1 << 31) || k >= ((size_t)1 << 31)) return fail(YAGI_ERR_CONFIG, "eqrls: n and k must be below 2^31");
+        if (x_pitch < C || y_pitch < C || x_pitch >= ((size_t)1 << 31) || y_pitch >= ((size_t)1 << 31))
+            return fail(YAGI_ERR_CONFIG, "eqrls: the pitches are in samples, at least the channel count and below 2^31");
+        if (n % k != 0) return fail(YAGI_ERR_CONFIG, "eqrls: step_block takes whole symbols, %zu rows at k = %zu", n, k);
+        *rows = n / k;
+        if (mode == YAGI_EQRLS_TRAIN && *rows != 0) {
+            if (!have_d) return fail(YAGI_ERR_CONFIG, "eqrls: TRAIN needs the known symbols d");
+            if (d_pitch < C || d_pitch >= ((size_t)1 << 31))
+                return fail(YAGI_ERR_CONFIG, "eqrls: the pitches are in samples, at least the channel count and below 2^31");
+        }
+        if (mode == YAGI_EQRLS_DECISION && M == 0)
+            return fail(YAGI_ERR_CONFIG, "eqrls: DECISION needs set_constellation first");
+        return YAGI_OK;
+    }
+    int block_dev(int mode, size_t k, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, cf32 *y,
+                  size_t y_pitch) {
+        if (n == 0) return YAGI_OK;
+        YG_TRY(ensure_dev());
+        YG_TRY(launch_eqrls(mode, p, lanes ? lanes : eqrls_plan(C, p), lambda, P_dev.as<cf32>(), w0_dev.as<cf32>(),
+                            w1_dev.as<cf32>(), hist_dev.as<cf32>(), C, k, x, x_pitch, n, d, d_pitch, table_dev.as<cf32>(),
+                            table.size(), y, y_pitch, st));
+        mirror.dev_written();
+        return YAGI_OK;
+    }
+    int block_host(int mode, size_t k, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, cf32 *y,
+                   size_t y_pitch) {
+        size_t rows = 0;
+        YG_TRY(check_block(C, mode, k, x_pitch, n, d != nullptr, d_pitch, table.size(), y_pitch, &rows));
+        if (n == 0) return YAGI_OK;
+        if (!x || !y) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        YG_TRY(ws.put(st, x, (n - 1) * x_pitch + C));
+        const bool train = mode == YAGI_EQRLS_TRAIN;
+        if (train) {
+            YG_TRY(wsd.put(st, d, (rows - 1) * d_pitch + C));
+        }
+        YG_TRY(ws.y.ensure(rows * C * sizeof(cf32)));
+        YG_TRY(block_dev(mode, k, ws.x.as<cf32>(), x_pitch, n, train ? wsd.x.as<cf32>() : nullptr, d_pitch, ws.y.as<cf32>(), C));
+        std::vector<cf32> t(rows * C);
+        YG_TRY(download(t.data(), ws.y.p, rows * C * sizeof(cf32), st));
+        for (size_t j = 0; j < rows; ++j) std::copy(t.begin() + j * C, t.begin() + (j + 1) * C, y + j * y_pitch);
+        return YAGI_OK;
+    }
+    // train (:158-176) up to its loop: the checks, reset() and w0[i] = w[p - 1 - i], on the host mirror
+    int train_prepare(const cf32 *w, size_t x_pitch, size_t n, bool have_d, size_t d_pitch) {
+        if (n < p) return fail(YAGI_ERR_CONFIG, "training sequence less than filter order");
+        size_t rows = 0;
+        YG_TRY(check_block(C, YAGI_EQRLS_TRAIN, 1, x_pitch, n, have_d, d_pitch, 0, C, &rows));
+        if (!w) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        YG_TRY(reset());
+        for (size_t c = 0; c < C; ++c)
+            for (size_t i = 0; i < p; ++i) hw0[i * C + c] = w[c * p + (p - 1 - i)];
+        return YAGI_OK;
+    }
+    void weights(cf32 *w) const {                           // get_weights (:148-156): w1 reversed
+        for (size_t c = 0; c < C; ++c)
+            for (size_t i = 0; i < p; ++i) w[c * p + i] = hw1[(p - 1 - i) * C + c];
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_eqrls_cccf_s : EqrlsObj {};
+
+extern "C" {
+
+int yagi_hip_eqrls_plan(size_t channels, size_t p, size_t *L, size_t *lds_bytes, unsigned *admissible) try {
+    CHECK_PTR(L);
+    YG_TRY(EqrlsObj::check_design(channels, p));
+    *L = eqrls_plan(channels, p);
+    if (lds_bytes) *lds_bytes = eqrls_lds_bytes(p, *L);
+    if (admissible) *admissible = eqrls_admissible(p);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_create(size_t channels, const cf32 *h, size_t p, yagi_hip_eqrls_cccf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    auto o = std::make_unique<yagi_hip_eqrls_cccf_s>();
+    YG_TRY(o->configure(channels, h, p));
+    YG_TRY(o->alloc());
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_recreate(yagi_hip_eqrls_cccf q, const cf32 *h, size_t p) try {
+    CHECK_Q(q);
+    if (p == q->p) {
+        if (h) std::copy(h, h + p, q->h0.begin());
+        return YAGI_OK;
+    }
+    YG_TRY(EqrlsObj::check_design(q->C, p));                  // the object is left as it was where the new design is refused
+    YG_HIP(hipStreamSynchronize(q->st));
+    YG_TRY(q->configure(q->C, h, p));
+    q->mirror.in_sync();
+    return q->alloc();
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_destroy(yagi_hip_eqrls_cccf q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_clone(yagi_hip_eqrls_cccf q, yagi_hip_eqrls_cccf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_eqrls_cccf_s>();
+    o->st = q->st;
+    o->C = q->C, o->p = q->p, o->lanes = q->lanes, o->lambda = q->lambda;
+    o->h0 = q->h0, o->table = q->table, o->hP = q->hP, o->hw0 = q->hw0, o->hw1 = q->hw1, o->hh = q->hh;
+    YG_TRY(o->alloc());
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_set_stream(yagi_hip_eqrls_cccf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_reset(yagi_hip_eqrls_cccf q) try {
+    CHECK_Q(q);
+    return q->reset();
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_reset_channel(yagi_hip_eqrls_cccf q, size_t c) try {
+    CHECK_Q(q);
+    return q->reset_channel(c);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_set_bw(yagi_hip_eqrls_cccf q, float lambda) try {
+    CHECK_Q(q);
+    return EqrlsObj::set_bw(lambda, &q->lambda);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_get_bw(yagi_hip_eqrls_cccf q, float *lambda) try {
+    CHECK_Q(q);
+    CHECK_PTR(lambda);
+    *lambda = q->lambda;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_get_length(yagi_hip_eqrls_cccf q, size_t *p) try {
+    CHECK_Q(q);
+    CHECK_PTR(p);
+    *p = q->p;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_get_channels(yagi_hip_eqrls_cccf q, size_t *channels) try {
+    CHECK_Q(q);
+    CHECK_PTR(channels);
+    *channels = q->C;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_get_coefficients(yagi_hip_eqrls_cccf q, cf32 *w0) try {
+    CHECK_Q(q);
+    CHECK_PTR(w0);
+    YG_TRY(q->ensure_host());
+    for (size_t c = 0; c < q->C; ++c)
+        for (size_t i = 0; i < q->p; ++i) w0[c * q->p + i] = q->hw0[i * q->C + c];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_get_weights(yagi_hip_eqrls_cccf q, cf32 *w) try {
+    CHECK_Q(q);
+    CHECK_PTR(w);
+    YG_TRY(q->ensure_host());
+    q->weights(w);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_get_matrix(yagi_hip_eqrls_cccf q, cf32 *P0) try {
+    CHECK_Q(q);
+    CHECK_PTR(P0);
+    YG_TRY(q->ensure_host());
+    const size_t pp = q->p * q->p;
+    for (size_t c = 0; c < q->C; ++c)
+        for (size_t e = 0; e < pp; ++e) P0[c * pp + e] = q->hP[e * q->C + c];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_set_constellation(yagi_hip_eqrls_cccf q, const cf32 *table, size_t M) try {
+    CHECK_Q(q);
+    YG_TRY(EqlmsObj::check_table(table, M));
+    YG_HIP(hipStreamSynchronize(q->st));                     // a launch in flight may still read the table
+    q->table.assign(table, table + M);
+    return fill(q->table_dev, q->table.data(), M * sizeof(cf32), q->st);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_set_lanes(yagi_hip_eqrls_cccf q, size_t L) try {
+    CHECK_Q(q);
+    if (L != 0) {
+        YG_TRY(EqrlsObj::check_lanes(q->p, L));
+    }
+    q->lanes = L;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_get_lanes(yagi_hip_eqrls_cccf q, size_t *L) try {
+    CHECK_Q(q);
+    CHECK_PTR(L);
+    *L = q->lanes ? q->lanes : eqrls_plan(q->C, q->p);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_step_block(yagi_hip_eqrls_cccf q, size_t k, int mode, const cf32 *x, size_t x_pitch, size_t n,
+                                   const cf32 *d, size_t d_pitch, cf32 *y, size_t y_pitch) try {
+    CHECK_Q(q);
+    return q->block_host(mode, k, x, x_pitch, n, d, d_pitch, y, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_step_block_dev(yagi_hip_eqrls_cccf q, size_t k, int mode, const cf32 *x_dev, size_t x_pitch, size_t n,
+                                       const cf32 *d_dev, size_t d_pitch, cf32 *y_dev, size_t y_pitch) try {
+    CHECK_Q(q);
+    size_t rows = 0;
+    YG_TRY(EqrlsObj::check_block(q->C, mode, k, x_pitch, n, d_dev != nullptr, d_pitch, q->table.size(), y_pitch, &rows));
+    if (n != 0) {
+        CHECK_PTR(x_dev);
+        CHECK_PTR(y_dev);
+    }
+    return q->block_dev(mode, k, x_dev, x_pitch, n, d_dev, d_pitch, y_dev, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_train(yagi_hip_eqrls_cccf q, cf32 *w, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d,
+                              size_t d_pitch) try {
+    CHECK_Q(q);
+    YG_TRY(q->train_prepare(w, x_pitch, n, d != nullptr, d_pitch));
+    if (n != 0) {
+        CHECK_PTR(x);
+        std::vector<cf32> y(n * q->C);
+        YG_TRY(q->block_host(YAGI_EQRLS_TRAIN, 1, x, x_pitch, n, d, d_pitch, y.data(), q->C));
+    }
+    YG_TRY(q->ensure_host());
+    q->weights(w);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_train_dev(yagi_hip_eqrls_cccf q, const cf32 *w, const cf32 *x_dev, size_t x_pitch, size_t n,
+                                  const cf32 *d_dev, size_t d_pitch) try {
+    CHECK_Q(q);
+    YG_TRY(q->train_prepare(w, x_pitch, n, d_dev != nullptr, d_pitch));
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x_dev);
+    YG_TRY(q->ws.y.ensure(n * q->C * sizeof(cf32)));         // the outputs are dropped
+    return q->block_dev(YAGI_EQRLS_TRAIN, 1, x_dev, x_pitch, n, d_dev, d_pitch, q->ws.y.as<cf32>(), q->C);
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_eqrls_cccf_execute_host(size_t channels, const cf32 *h, size_t p, float lambda, int mode, size_t k, const cf32 *x,
+                                     size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, const cf32 *table, size_t M,
+                                     cf32 *y, size_t y_pitch, cf32 *w0, cf32 *w1, cf32 *P0) try {
+    EqrlsObj o;
+    YG_TRY(o.configure(channels, h, p));
+    YG_TRY(EqrlsObj::set_bw(lambda, &o.lambda));
+    if (mode == YAGI_EQRLS_DECISION) {
+        YG_TRY(EqlmsObj::check_table(table, M));
+    }
+    size_t rows = 0;
+    YG_TRY(EqrlsObj::check_block(channels, mode, k, x_pitch, n, d != nullptr, d_pitch, M, y_pitch, &rows));
+    if (n != 0) {
+        CHECK_PTR(x);
+        CHECK_PTR(y);
+    }
+    eqrls_host(mode, p, o.lambda, o.hP.data(), o.hw0.data(), o.hw1.data(), o.hh.data(), channels, k, x, x_pitch, n, d, d_pitch,
+               table, M, y, y_pitch);
+    for (size_t c = 0; c < channels; ++c) {
+        for (size_t i = 0; i < p; ++i) {
+            if (w0) w0[c * p + i] = o.hw0[i * channels + c];
+            if (w1) w1[c * p + i] = o.hw1[i * channels + c];
+        }
+        if (P0)
+            for (size_t e = 0; e < p * p; ++e) P0[c * p * p + e] = o.hP[e * channels + c];
+    }
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
 // ---- Agc (src/agc/agc.rs, one object per channel) ------------------------------------------------------------------
 // The state is one AgcChan per channel; agc_kernels.hip updates it in place on the device.  reset, the setters and getters
 // that touch g, the locks and the squelch modes work on a host mirror; the two copies are synchronised lazily (Mirror).

@@ -670,6 +670,55 @@ void eqlms_host(int call, size_t h_len, float mu, cf32 *w, cf32 *hist, EqlmsChan
                 size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, const cf32 *table, size_t M, cf32 *y,
                 size_t y_pitch);
 
+// ---- eqrls_kernels.hip ---------------------------------------------------------------------
+// EqRls (yagi_hip.h): C independent Eqrls<Complex32> loops of one design.  A group of L lanes (a power of two, 1 .. 64)
+// runs one channel's step, so a workgroup of one wave holds 64 / L channels.  P = the recursion matrix, [p p][C], row
+// major; w0 and w1 = the two weight vectors, [p][C]; hist = the window, [p][C], oldest first.  All four are updated in
+// place (a workgroup touches its own channels only); w1 is written only by a call that runs at least one update.
+// mode = YAGI_EQRLS_NONE / TRAIN / DECISION; n input rows, a multiple of k, n / k rows of y; d = n / k rows of known
+// symbols for TRAIN; table = M points for DECISION.
+constexpr int kEqrlsWg = 64;                           // lanes per workgroup: one wave
+constexpr int kEqrlsAhead = 8;                         // input rows per chunk: requested one chunk ahead, staged in LDS
+constexpr size_t kEqrlsLdsMax = 160 * 1024;            // the LDS of a CU
+// the row pitch of P in LDS: odd, so that the L lanes of a group that read one row each (the numerators of g) fall on
+// different banks, as the lanes that read one column each do by the [element][channel-in-wave] layout alone
+constexpr size_t eqrls_pitch(size_t p) { return p | 1; }
+// per channel two matrices (P0 and the buffer P1 is formed in), the window, w0, xp0, g and two rows of gxl; per
+// workgroup the staged input rows of its 64 / L channels and the DECISION table
+constexpr size_t eqrls_chan_elems(size_t p) { return 2 * p * eqrls_pitch(p) + 6 * p; }
+constexpr size_t eqrls_lds_bytes(size_t p, size_t L) {
+    return ((size_t)(kEqrlsWg / L) * (eqrls_chan_elems(p) + kEqrlsAhead) + YAGI_EQLMS_TABLE_MAX) * sizeof(cf32);
+}
+static_assert(eqrls_lds_bytes(YAGI_EQRLS_LEN_MAX, 8) <= kEqrlsLdsMax, "p = 32 runs at L = 8");
+// The admissible L for p: a power of two whose 64 / L channels fit in LDS, and no more lanes than twice the columns they
+// share (L / 2 < p).  Returned as a mask, bit b = (L = 2^b).
+constexpr unsigned eqrls_admissible(size_t p) {
+    unsigned m = 0;
+    for (unsigned b = 0; b <= 6; ++b) {
+        const size_t L = (size_t)1 << b;
+        if (eqrls_lds_bytes(p, L) <= kEqrlsLdsMax && (L == 1 || L / 2 < p)) m |= 1u << b;
+    }
+    return m;
+}
+// The planner's choice: the largest admissible L, whatever the channel count.  The p^3 term of a step spreads over the L
+// lanes of a group and a wave of fewer channels needs less LDS, so more waves fit a CU; measured on the MI355X at p = 4,
+// 8, 16 and 32 and C = 64 .. 262144 the largest L is the fastest at every shape, by 1.2 to 1.9 times over the next one
+// (profiles/r25_kbench_eqrls.txt).  C stays an argument: the choice is the planner's to change.
+constexpr unsigned eqrls_plan(size_t C, size_t p) {
+    (void)C;
+    const unsigned m = eqrls_admissible(p);
+    unsigned b = 6;
+    while (!(m >> b & 1u)) --b;
+    return 1u << b;
+}
+int launch_eqrls(int mode, size_t p, size_t L, float lambda, cf32 *P, cf32 *w0, cf32 *w1, cf32 *hist, size_t C, size_t k,
+                 const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, const cf32 *table, size_t M, cf32 *y,
+                 size_t y_pitch, hipStream_t st);
+// the same on the host, channel after channel
+void eqrls_host(int mode, size_t p, float lambda, cf32 *P, cf32 *w0, cf32 *w1, cf32 *hist, size_t C, size_t k, const cf32 *x,
+                size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, const cf32 *table, size_t M, cf32 *y,
+                size_t y_pitch);
+
 // ---- agc_kernels.hip -----------------------------------------------------------------------
 // Agc (yagi_hip.h): C independent Agc<T> loops of one set of settings, one lane per channel, T = cf32 or float.  state is
 // one AgcChan per channel, updated in place.  n rows in, n rows out; status (may be null) receives the squelch mode after
