@@ -2198,6 +2198,123 @@ int yagi_hip_symtrack_cccf_execute_host(size_t channels, int ftype, size_t k, si
                                         const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y, size_t y_pitch,
                                         uint8_t *sym, size_t sym_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled);
 
+/* ---- Channel (channel_cccf): multipath, carrier offset and AWGN for a bank of links ----------------------------------
+ * The reference's src/channel/mod.rs is an empty module, so the object is defined here from parts this library already
+ * pins.  Channel(channels, L, osc_scheme) is `channels` independent links of one shape; the input is x[s x_pitch + c],
+ * the output y[s y_pitch + c], one output per input; the broadcast form reads one stream x[s] for every link.
+ * Channel: the definition.  Per link c, per input sample x at that link's sample counter t (a u64, 0 after reset):
+ *     win.push(x)                                   Window<Complex32> of length L, zero after reset
+ *     v = sum_{j=0..L-1} hrev_c[j] * win.read()[j]  hrev_c[j] = h_c[L-1-j]; oldest sample first; sequential from 0;
+ *                                                   num-complex's product (hr xr - hi xi, hr xi + hi xr); every product
+ *                                                   and add rounded on its own in f32
+ *     w = nco_c.mix_up(v); nco_c.step()             Osc's words (NCO or VCO, fixed at creation); the phase of sample j of
+ *                                                   a call is theta_c + (u32)j d_theta_c
+ *     y.re = w.re gamma_c + nstd_c (R C)
+ *     y.im = w.im gamma_c + nstd_c (R S)            four products, two adds, each rounded on its own
+ *     t += 1
+ * The order (multipath, carrier offset, gain and noise) follows liquid-dsp's channel_cccf as recalled; that could not be
+ * checked against its source, so this is a note and no parity claim.
+ * The noise words (channel_words.hpp, one source for host and device; tests/channel_ref.py restates them):
+ *     seed_c = splitmix64_at(seed, c)               the synthetic-input generator's function (splitmix.hpp)
+ *     a = splitmix64_at(seed_c, 2t), b = splitmix64_at(seed_c, 2t+1)       u64 arithmetic, wrapping
+ *     k1 = (a >> 40) + 1 in [1, 2^24];  k2 = b >> 40 in [0, 2^24)
+ *     R = (float)sqrt(-ln64((double)k1 2^-24))      ln64 of the Agc block; an f64 root; k1 = 2^24 gives -0, which is kept
+ *     (C, S) = the f32 roundings of f64 evaluations of cos and sin(2 pi k2 / 2^24):  oct = k2 >> 21, r = k2 & (2^21 - 1),
+ *         m = 2^21 - r in an odd octant, else r;  x = fl(m) 0x1.921fb54442d18p-22;  z = x x;
+ *         p = fl(-1/15!); then p = p z + c for c = fl(1/13!), fl(-1/11!), fl(1/9!), fl(-1/7!), fl(1/5!), fl(-1/3!);
+ *         sn = x + (x z) p;  q = fl(1/16!); then q = q z + c for c = fl(-1/14!), fl(1/12!), fl(-1/10!), fl(1/8!),
+ *         fl(-1/6!), fl(1/4!), -1/2;  cs = 1 + z q;  ss = 0 - sn in an odd octant, else sn;  quad = ((oct + 1) >> 1) & 3:
+ *         (C, S) = (cs, ss), (0 - ss, cs), (0 - cs, 0 - ss), (ss, 0 - cs) for quad = 0, 1, 2, 3.
+ *         Every operation is an IEEE f64 + - * rounded on its own; the f64 error is at most E = 2^-45
+ *         (YAGI_CHANNEL_COSSIN_E); k2 = 0, 2^22, 2^23, 3 2^22 give exactly (1, 0), (0, 1), (-1, 0), (0, -1).
+ *     With these words E|R (C + jS)|^2 = 1, so nstd^2 is the noise power.
+ * Where nstd_c is zero and both w gamma_c parts are nonzero the noise term is a signed zero that changes no bit; the
+ * implementation skips the draw there.  Non-finite samples follow the words as written: they touch only their own link
+ * and only the L outputs whose window holds them.
+ *   create(channels, L, osc_scheme)   1 <= channels <= YAGI_CHANNEL_CHANNELS_MAX, 1 <= L <= YAGI_CHANNEL_TAPS_MAX,
+ *                             YAGI_OSC_NCO or YAGI_OSC_VCO; anything else is YAGI_ERR_CONFIG, decided before any device is
+ *                             asked for.  h_c = (1, 0, .., 0), gamma 1, nstd 0, offset and phase 0, seed 0, t = 0
+ *   destroy / clone / set_stream    a clone writes what its original would write
+ *   reset / reset_channel(c)  clears the window, t = 0, the oscillator back to the phi last set; the parameters stay
+ *   set_awgn(c, n0_db, snr_db) / set_awgn_all(n0_db[channels], snr_db[channels])   nstd = p10(n0_db / 20), gamma =
+ *                             p10((snr_db + n0_db) / 20), the argument formed in f32, p10(t) = (float)exp64((double)t LN10),
+ *                             LN10 = 0x1.26bb1bbb55516p+1 (Agc's set_rssi word); a NaN argument gives a NaN word
+ *   set_gain_noise(c, gamma, nstd) / set_gain_noise_all   the raw words, any f32
+ *   set_carrier_offset(c, dphi, phi) / set_carrier_offset_all   Osc's set_frequency and set_phase, constrain() included:
+ *                             YAGI_ERR_CONFIG where the reference's loops would not end; then nothing is changed
+ *   set_multipath(c, h[L]) / set_multipath_all(h[channels][L]) / get_multipath(h[channels][L])
+ *   set_seed(seed) / get_seed;  set_position(c, t) / set_position_all(t[channels])   seek the noise, t a u64
+ *   get_gain_noise(gamma[channels], nstd[channels]) / get_osc_state(theta[channels], d_theta[channels]) /
+ *   get_position(t[channels]) / get_channels / get_taps (L)   either output pointer of a pair may be NULL
+ *   execute(x, x_pitch, n, y, y_pitch) / execute_dev   host slices staged through the device / device pointers,
+ *                             asynchronous on the object's stream
+ *   execute_bcast(x[n], n, y, y_pitch) / execute_bcast_dev   one input stream goes to every link
+ *   execute_host(channels, L, osc_scheme, bcast, seed, h[channels][L], gamma, nstd, theta, d_theta, t (each [channels]),
+ *                x, x_pitch, n, y, y_pitch)   the definition on the host alone, one call from reset() with the raw words
+ *                             given; no device needed; x_pitch is ignored where bcast
+ *   set_shape(links, rows) / get_shape / yagi_hip_channel_plan   the launch arrangement: a workgroup of 256 lanes is
+ *                             `links` links wide (a power of two, 1 .. 64) and 256 / links steps deep, and a lane writes
+ *                             `rows` outputs (1, 2, 4, 8, 16).  set_shape(0, 0) returns to the planner.  Every
+ *                             admissible arrangement gives the same words.  plan reports the arrangement, the steps per
+ *                             tile and the LDS bytes of a call (bcast or not) of n steps.
+ * The pitches are in elements and >= channels; n is below 2^31; n = 0 touches nothing; x and y must not overlap; device
+ * sample pointers are 8-byte aligned.
+ * Not built: shadowing, time-varying taps, per-link L, rrrf, fusion with SymStream or Agc.
+ * Device form: channel_kernels.hip. */
+#define YAGI_CHANNEL_CHANNELS_MAX 1048576
+#define YAGI_CHANNEL_TAPS_MAX 64      /* (16 rows x 256 lanes + 63 halo rows x 64 links + 64 x 64 taps) x 8 B + 16 KiB: 112 KiB of LDS */
+#define YAGI_CHANNEL_COSSIN_E 0x1p-45
+typedef struct yagi_hip_channel_cccf_s *yagi_hip_channel_cccf;
+typedef struct {
+    unsigned links, rows;        /* links per workgroup row; outputs per lane */
+    size_t tile_steps, lds_bytes;
+} yagi_hip_channel_shape;
+int yagi_hip_channel_plan(size_t channels, size_t L, size_t n, int osc_scheme, int bcast, yagi_hip_channel_shape *plan);
+int yagi_hip_channel_cccf_create(size_t channels, size_t L, int osc_scheme, yagi_hip_channel_cccf *q);
+int yagi_hip_channel_cccf_destroy(yagi_hip_channel_cccf q);
+int yagi_hip_channel_cccf_clone(yagi_hip_channel_cccf q, yagi_hip_channel_cccf *out);
+int yagi_hip_channel_cccf_set_stream(yagi_hip_channel_cccf q, yagi_stream_t s);
+int yagi_hip_channel_cccf_reset(yagi_hip_channel_cccf q);
+int yagi_hip_channel_cccf_reset_channel(yagi_hip_channel_cccf q, size_t c);
+int yagi_hip_channel_cccf_set_awgn(yagi_hip_channel_cccf q, size_t c, float n0_db, float snr_db);
+int yagi_hip_channel_cccf_set_awgn_all(yagi_hip_channel_cccf q, const float *n0_db, const float *snr_db);
+int yagi_hip_channel_cccf_set_gain_noise(yagi_hip_channel_cccf q, size_t c, float gamma, float nstd);
+int yagi_hip_channel_cccf_set_gain_noise_all(yagi_hip_channel_cccf q, const float *gamma, const float *nstd);
+int yagi_hip_channel_cccf_set_carrier_offset(yagi_hip_channel_cccf q, size_t c, float dphi, float phi);
+int yagi_hip_channel_cccf_set_carrier_offset_all(yagi_hip_channel_cccf q, const float *dphi, const float *phi);
+int yagi_hip_channel_cccf_set_multipath(yagi_hip_channel_cccf q, size_t c, const yagi_cf32 *h);
+int yagi_hip_channel_cccf_set_multipath_all(yagi_hip_channel_cccf q, const yagi_cf32 *h);
+int yagi_hip_channel_cccf_get_multipath(yagi_hip_channel_cccf q, yagi_cf32 *h);
+int yagi_hip_channel_cccf_set_seed(yagi_hip_channel_cccf q, uint64_t seed);
+int yagi_hip_channel_cccf_get_seed(yagi_hip_channel_cccf q, uint64_t *seed);
+int yagi_hip_channel_cccf_set_position(yagi_hip_channel_cccf q, size_t c, uint64_t t);
+int yagi_hip_channel_cccf_set_position_all(yagi_hip_channel_cccf q, const uint64_t *t);
+int yagi_hip_channel_cccf_get_position(yagi_hip_channel_cccf q, uint64_t *t);
+int yagi_hip_channel_cccf_get_gain_noise(yagi_hip_channel_cccf q, float *gamma, float *nstd);
+int yagi_hip_channel_cccf_get_osc_state(yagi_hip_channel_cccf q, uint32_t *theta, uint32_t *d_theta);
+int yagi_hip_channel_cccf_get_channels(yagi_hip_channel_cccf q, size_t *channels);
+int yagi_hip_channel_cccf_get_taps(yagi_hip_channel_cccf q, size_t *L);
+int yagi_hip_channel_cccf_set_shape(yagi_hip_channel_cccf q, unsigned links, unsigned rows);
+int yagi_hip_channel_cccf_get_shape(yagi_hip_channel_cccf q, size_t n, int bcast, yagi_hip_channel_shape *shape);
+int yagi_hip_channel_cccf_execute(yagi_hip_channel_cccf q, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
+                                  size_t y_pitch);
+int yagi_hip_channel_cccf_execute_dev(yagi_hip_channel_cccf q, const yagi_cf32 *x_dev, size_t x_pitch, size_t n,
+                                      yagi_cf32 *y_dev, size_t y_pitch);
+int yagi_hip_channel_cccf_execute_bcast(yagi_hip_channel_cccf q, const yagi_cf32 *x, size_t n, yagi_cf32 *y, size_t y_pitch);
+int yagi_hip_channel_cccf_execute_bcast_dev(yagi_hip_channel_cccf q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev,
+                                            size_t y_pitch);
+int yagi_hip_channel_cccf_execute_host(size_t channels, size_t L, int osc_scheme, int bcast, uint64_t seed, const yagi_cf32 *h,
+                                       const float *gamma, const float *nstd, const uint32_t *theta, const uint32_t *d_theta,
+                                       const uint64_t *t, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
+                                       size_t y_pitch);
+/* the words on arrays, host only: awgn's (gamma, nstd); (C, S)[k2] as f64 before the f32 rounding; R[k1]; the noise of
+ * (seed, link) at counters first .. first + n - 1 */
+int yagi_hip_channel_awgn_words(float n0_db, float snr_db, float *gamma, float *nstd);
+int yagi_hip_channel_cos_sin(const uint32_t *k2, size_t n, double *c, double *s);
+int yagi_hip_channel_radius(const uint32_t *k1, size_t n, float *r);
+int yagi_hip_channel_noise(uint64_t seed, uint64_t link, uint64_t first, size_t n, yagi_cf32 *out);
+int yagi_hip_channel_constrain(float phi, uint32_t *word);      /* Osc's constrain(): the word of a phase or frequency */
+
 /* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */
 

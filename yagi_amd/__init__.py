@@ -2879,6 +2879,243 @@ class Agc(_Handle):
         return y, st, g, mode
 
 
+CHANNEL_CHANNELS_MAX = 1 << 20     # YAGI_CHANNEL_CHANNELS_MAX
+CHANNEL_TAPS_MAX = 64              # YAGI_CHANNEL_TAPS_MAX: the most taps of a link
+CHANNEL_COSSIN_E = 2.0 ** -45      # YAGI_CHANNEL_COSSIN_E: the f64 error bound of the noise's cos and sin words
+CHANNEL_SHAPE = np.dtype([("links", "u4"), ("rows", "u4"), ("tile_steps", "u8"), ("lds_bytes", "u8")])
+
+
+def _channel_scheme(scheme):
+    return scheme.value if isinstance(scheme, OscScheme) else int(scheme)
+
+
+def _channel_u64(v, what):
+    if not (isinstance(v, (int, np.integer)) and 0 <= v < 2 ** 64):
+        raise ConfigError(f"{what} must be an unsigned 64-bit integer")
+    return int(v)
+
+
+def _channel_shape(s):
+    return {"links": s.links, "rows": s.rows, "tile_steps": s.tile_steps, "lds_bytes": s.lds_bytes}
+
+
+def channel_plan(channels, L, n, osc_scheme=OscScheme.Nco, bcast=False):
+    """yagi_hip_channel_plan: the arrangement a Channel call of n steps runs at: links per workgroup row, outputs per
+    lane, steps per tile and the LDS bytes"""
+    s = _capi.channel_shape()
+    _check(lib.yagi_hip_channel_plan(_symsync_size(channels, "channels"), _symsync_size(L, "L"), _symsync_size(n, "n"),
+                                     _channel_scheme(osc_scheme), int(bool(bcast)), C.byref(s)))
+    return _channel_shape(s)
+
+
+def channel_awgn_words(n0_db, snr_db):
+    """(gamma, nstd) of Channel.set_awgn"""
+    g, s = C.c_float(), C.c_float()
+    _check(lib.yagi_hip_channel_awgn_words(n0_db, snr_db, C.byref(g), C.byref(s)))
+    return np.float32(g.value), np.float32(s.value)
+
+
+def channel_cos_sin(k2):
+    """the f64 evaluations (C, S) of cos and sin(2 pi k2 / 2^24) of Channel's noise, before the f32 rounding"""
+    k2 = _arr(k2, np.uint32)
+    c, s = np.empty(k2.shape, np.float64), np.empty(k2.shape, np.float64)
+    _check(lib.yagi_hip_channel_cos_sin(_ptr(k2), k2.size, _ptr(c), _ptr(s)))
+    return c, s
+
+
+def channel_radius(k1):
+    """R[k1] of Channel's noise, k1 in 1 .. 2^24"""
+    k1 = _arr(k1, np.uint32)
+    r = np.empty(k1.shape, np.float32)
+    _check(lib.yagi_hip_channel_radius(_ptr(k1), k1.size, _ptr(r)))
+    return r
+
+
+def channel_noise(seed, link, first, n):
+    """the noise samples of (seed, link) at counters first .. first + n - 1, on the host"""
+    out = np.empty(_symsync_size(n, "n"), np.complex64)
+    _check(lib.yagi_hip_channel_noise(_channel_u64(seed, "seed"), _channel_u64(link, "link"), _channel_u64(first, "first"),
+                                      out.size, _ptr(out)))
+    return out
+
+
+def channel_constrain(phi):
+    """Osc's constrain(): the u32 word of a phase or frequency in radians"""
+    w = C.c_uint32()
+    _check(lib.yagi_hip_channel_constrain(phi, C.byref(w)))
+    return w.value
+
+
+class Channel(_Handle):
+    """Channel(channels, L=1, osc_scheme=OscScheme.Nco): `channels` independent links of one shape (yagi_hip.h,
+    "Channel: the definition"): an L-tap multipath filter, a carrier offset (Osc's words) and gain plus white Gaussian
+    noise from a counter-based generator, per link.  A block is x[n, channels] (step, channel) or, broadcast, one
+    stream x[n] for every link; one output per input.  Every output word equals the definition's sequential loop bit
+    for bit at every launch arrangement.  The block calls run channel_kernels.hip."""
+    _prefix = "yagi_hip_channel_cccf_"
+
+    def __init__(self, channels, L=1, osc_scheme=OscScheme.Nco):
+        channels, L = _symsync_size(channels, "channels"), _symsync_size(L, "L")
+        hd = C.c_void_p()
+        _check(self._fn("create")(channels, L, _channel_scheme(osc_scheme), C.byref(hd)))
+        self._h, self.channels, self.L = hd, channels, L
+
+    def clone(self):
+        new, hd = object.__new__(type(self)), C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._h, new.channels, new.L = hd, self.channels, self.L
+        return new
+
+    def _call(self, name, *args):
+        _check(self._fn(name)(self._h, *args))
+
+    def _vector(self, v, dt, what, shape=None):
+        v = _arr(v, dt)
+        if v.shape != (shape or (self.channels,)):
+            raise ConfigError(f"{what} holds one value per channel")
+        return v
+
+    def reset_channel(self, c):
+        self._call("reset_channel", _symsync_size(c, "channel"))
+
+    def set_awgn(self, c, n0_db, snr_db):
+        """noise floor n0_db and signal-to-noise ratio snr_db of link c: nstd = 10^(n0_db / 20), gamma = 10^((snr_db +
+        n0_db) / 20)"""
+        self._call("set_awgn", _symsync_size(c, "channel"), n0_db, snr_db)
+
+    def set_awgn_all(self, n0_db, snr_db):
+        self._call("set_awgn_all", _ptr(self._vector(n0_db, np.float32, "n0_db")),
+                   _ptr(self._vector(snr_db, np.float32, "snr_db")))
+
+    def set_gain_noise(self, c, gamma, nstd):
+        self._call("set_gain_noise", _symsync_size(c, "channel"), gamma, nstd)
+
+    def set_gain_noise_all(self, gamma, nstd):
+        self._call("set_gain_noise_all", _ptr(self._vector(gamma, np.float32, "gamma")),
+                   _ptr(self._vector(nstd, np.float32, "nstd")))
+
+    def set_carrier_offset(self, c, dphi, phi=0.0):
+        """radians per sample and the phase now, through Osc's set_frequency and set_phase"""
+        self._call("set_carrier_offset", _symsync_size(c, "channel"), dphi, phi)
+
+    def set_carrier_offset_all(self, dphi, phi):
+        self._call("set_carrier_offset_all", _ptr(self._vector(dphi, np.float32, "dphi")),
+                   _ptr(self._vector(phi, np.float32, "phi")))
+
+    def set_multipath(self, c, h):
+        h = _arr(h, np.complex64)
+        if h.shape != (self.L,):
+            raise ConfigError(f"a link has {self.L} taps")
+        self._call("set_multipath", _symsync_size(c, "channel"), _ptr(h))
+
+    def set_multipath_all(self, h):
+        self._call("set_multipath_all", _ptr(self._vector(h, np.complex64, "h", (self.channels, self.L))))
+
+    def get_multipath(self):
+        h = np.zeros((self.channels, self.L), np.complex64)
+        self._call("get_multipath", _ptr(h))
+        return h
+
+    def set_seed(self, seed):
+        self._call("set_seed", _channel_u64(seed, "seed"))
+
+    def get_seed(self):
+        v = C.c_uint64()
+        self._call("get_seed", C.byref(v))
+        return v.value
+
+    def set_position(self, c, t):
+        """seek link c's noise: the counter of its next sample"""
+        self._call("set_position", _symsync_size(c, "channel"), _channel_u64(t, "t"))
+
+    def set_position_all(self, t):
+        self._call("set_position_all", _ptr(self._vector(t, np.uint64, "t")))
+
+    def get_position(self):
+        t = np.zeros(self.channels, np.uint64)
+        self._call("get_position", _ptr(t))
+        return t
+
+    def get_gain_noise(self):
+        """(gamma[channels], nstd[channels])"""
+        g, s = np.zeros(self.channels, np.float32), np.zeros(self.channels, np.float32)
+        self._call("get_gain_noise", _ptr(g), _ptr(s))
+        return g, s
+
+    def get_osc_state(self):
+        """the oscillators' raw words (theta[channels], d_theta[channels])"""
+        th, d = np.zeros(self.channels, np.uint32), np.zeros(self.channels, np.uint32)
+        self._call("get_osc_state", _ptr(th), _ptr(d))
+        return th, d
+
+    def set_shape(self, links=0, rows=0):
+        """override the launch arrangement (links a power of two up to 64, rows 1, 2, 4, 8 or 16); (0, 0): the planner"""
+        self._call("set_shape", links, rows)
+
+    def get_shape(self, n, bcast=False):
+        s = _capi.channel_shape()
+        self._call("get_shape", _symsync_size(n, "n"), int(bool(bcast)), C.byref(s))
+        return _channel_shape(s)
+
+    def execute(self, x):
+        """x[n, channels] -> y[n, channels]"""
+        x = _arr(x, np.complex64)
+        if x.ndim != 2 or x.shape[1] != self.channels:
+            raise ConfigError(f"the block is [steps, {self.channels}]")
+        y = np.zeros_like(x)
+        self._call("execute", _ptr(x), self.channels, x.shape[0], _ptr(y), self.channels)
+        return y
+
+    def execute_bcast(self, x):
+        """x[n], the same stream into every link -> y[n, channels]"""
+        x = _arr(x, np.complex64)
+        if x.ndim != 1:
+            raise ConfigError("the broadcast input is one stream")
+        y = np.zeros((x.size, self.channels), np.complex64)
+        self._call("execute_bcast", _ptr(x), x.size, _ptr(y), self.channels)
+        return y
+
+    def execute_devptr(self, x_dev, x_pitch, n, y_dev, y_pitch):
+        """n rows of pitch x_pitch, y_pitch elements; asynchronous on the object's stream (the C ABI's execute_dev)"""
+        self._call("execute_dev", None if x_dev is None else _devptr(x_dev), x_pitch, n,
+                   None if y_dev is None else _devptr(y_dev), y_pitch)
+
+    def execute_bcast_devptr(self, x_dev, n, y_dev, y_pitch):
+        self._call("execute_bcast_dev", None if x_dev is None else _devptr(x_dev), n,
+                   None if y_dev is None else _devptr(y_dev), y_pitch)
+
+    @staticmethod
+    def execute_host(h, gamma, nstd, theta, d_theta, t, x, osc_scheme=OscScheme.Nco, seed=0, bcast=False, x_pitch=None,
+                     y_pitch=None, y=None):
+        """the definition on the host alone, no device needed: one call from reset() with the raw words given.
+        h[channels, L]; gamma, nstd, theta, d_theta, t are [channels]; x is [n, x_pitch], or [n] where bcast; y, where
+        given, is the [n, y_pitch] array that is written.  The library's own sequential form, slow and meant for checks"""
+        h = _arr(h, np.complex64)
+        if h.ndim != 2:
+            raise ConfigError("h is [channels, L]")
+        channels, L = h.shape
+        words = [_arr(v, dt) for v, dt in ((gamma, np.float32), (nstd, np.float32), (theta, np.uint32),
+                                            (d_theta, np.uint32), (t, np.uint64))]
+        if any(w.shape != (channels,) for w in words):
+            raise ConfigError("every word array holds one value per channel")
+        x_pitch, y_pitch = (channels if p is None else _symsync_size(p, "pitch") for p in (x_pitch, y_pitch))
+        x = _arr(x, np.complex64)
+        if bcast:
+            if x.ndim != 1:
+                raise ConfigError("the broadcast input is one stream")
+        elif x.ndim != 2 or x.shape[1] != x_pitch:
+            raise ConfigError("the block is [steps, x_pitch]")
+        n = x.shape[0]
+        if y is None:
+            y = np.zeros((n, y_pitch), np.complex64)
+        elif not (isinstance(y, np.ndarray) and y.dtype == np.complex64 and y.flags.c_contiguous and y.shape == (n, y_pitch)):
+            raise ConfigError("y is a C-contiguous [steps, y_pitch] complex64 array")
+        _check(lib.yagi_hip_channel_cccf_execute_host(channels, L, _channel_scheme(osc_scheme), int(bool(bcast)),
+                                                      _channel_u64(seed, "seed"), _ptr(h),
+                                                      *(_ptr(w) for w in words), _ptr(x), x_pitch, n, _ptr(y), y_pitch))
+        return y
+
+
 SYMTRACK_CHANNELS_MAX = 1 << 20    # YAGI_SYMTRACK_CHANNELS_MAX
 SYMTRACK_PLL_ARG_MAX = 256.0       # YAGI_SYMTRACK_PLL_ARG_MAX: a pll_step argument of this magnitude stalls the channel
 SYMTRACK_STALL_CAPACITY = 1        # YAGI_SYMTRACK_STALL_CAPACITY: the channel would have written symbol number ycap

@@ -792,6 +792,46 @@ _sig(_p + "execute_dev", vp, vp, sz, sz, vp, sz, vp, sz, sz, vp)
 _sig(_p + "execute_host", sz, ci, sz, sz, f32, ci, vp, sz, ci, sz, sz, f32, ci, u64, vp, vp, vp, sz, sz, vp, sz, vp, sz, sz,
      vp, vp)
 
+# ---- Channel -----------------------------------------------------------------------------------
+class channel_shape(C.Structure):
+    """yagi_hip_channel_shape"""
+    _fields_ = [("links", C.c_uint), ("rows", C.c_uint), ("tile_steps", sz), ("lds_bytes", sz)]
+
+
+_p = "yagi_hip_channel_cccf_"
+_sig("yagi_hip_channel_plan", sz, sz, sz, ci, ci, C.POINTER(channel_shape))
+_sig(_p + "create", sz, sz, ci, pvp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+_sig(_p + "destroy", vp)
+_sig(_p + "reset", vp)
+_sig(_p + "reset_channel", vp, sz)
+for _n in ("set_awgn", "set_gain_noise", "set_carrier_offset"):
+    _sig(_p + _n, vp, sz, f32, f32)
+    _sig(_p + _n + "_all", vp, vp, vp)
+_sig(_p + "set_multipath", vp, sz, vp)
+for _n in ("set_multipath_all", "get_multipath", "set_position_all", "get_position"):
+    _sig(_p + _n, vp, vp)
+_sig(_p + "set_seed", vp, u64)
+_sig(_p + "get_seed", vp, C.POINTER(u64))
+_sig(_p + "set_position", vp, sz, u64)
+for _n in ("get_gain_noise", "get_osc_state"):
+    _sig(_p + _n, vp, vp, vp)
+for _n in ("get_channels", "get_taps"):
+    _sig(_p + _n, vp, C.POINTER(sz))
+_sig(_p + "set_shape", vp, C.c_uint, C.c_uint)
+_sig(_p + "get_shape", vp, sz, ci, C.POINTER(channel_shape))
+for _n in ("execute", "execute_dev"):
+    _sig(_p + _n, vp, vp, sz, sz, vp, sz)
+for _n in ("execute_bcast", "execute_bcast_dev"):
+    _sig(_p + _n, vp, vp, sz, vp, sz)
+_sig(_p + "execute_host", sz, sz, ci, ci, u64, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, sz)
+_sig("yagi_hip_channel_awgn_words", f32, f32, C.POINTER(f32), C.POINTER(f32))
+_sig("yagi_hip_channel_cos_sin", vp, sz, vp, vp)
+_sig("yagi_hip_channel_radius", vp, sz, vp)
+_sig("yagi_hip_channel_noise", u64, u64, u64, sz, vp)
+_sig("yagi_hip_channel_constrain", f32, C.POINTER(C.c_uint32))
+
 # ---- SymStream ---------------------------------------------------------------------------------
 _p = "yagi_hip_symstreamcf_"
 _sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)

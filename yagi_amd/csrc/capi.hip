@@ -8647,6 +8647,426 @@ int yagi_hip_symtrack_cccf_execute_host(size_t channels, int ftype, size_t k, si
 
 }  // extern "C"
 
+// ---- Channel (yagi_hip.h; src/channel/mod.rs is empty) ---------------------------------------------------------------
+// Every parameter is the host's: one ChannelLink per link as of the last parameter change plus `adv`, the samples
+// executed since, so a block call passes adv by value and advances it at once, as Osc does with theta, and nothing is
+// ever read back for them.  Only the carried window ([L - 1][C], ping-pong: channel_kernels.hip writes the next one) is
+// the device's; reset, reset_channel and clone reach it through a host mirror (Mirror).
+namespace yagi {
+
+struct ChannelObj {
+    hipStream_t st = nullptr;
+    size_t C = 0, L = 0;
+    int vco = 0;
+    uint64_t seed = 0, adv = 0;
+    ChannelShape forced{0, 0};                              // set_shape; cw = 0: the planner's
+    std::vector<ChannelLink> link;                          // as of adv = 0
+    std::vector<uint32_t> phi;                              // the phase word last set: where reset puts theta
+    std::vector<cf32> hrev, hwin;                           // [L][C] taps, reversed; [L - 1][C] window mirror
+    DevBuf tab, link_dev, taps_dev;
+    PingPong<> win;
+    bool link_dirty = true, taps_dirty = true;
+    Mirror mirror;
+    Staging ws;
+
+    static int check_create(size_t channels, size_t taps, int scheme) {
+        if (channels == 0 || channels > (size_t)YAGI_CHANNEL_CHANNELS_MAX)
+            return fail(YAGI_ERR_CONFIG, "channel: %zu channels are outside 1 .. YAGI_CHANNEL_CHANNELS_MAX", channels);
+        if (taps == 0 || taps > (size_t)YAGI_CHANNEL_TAPS_MAX)
+            return fail(YAGI_ERR_CONFIG, "channel: %zu taps are outside 1 .. YAGI_CHANNEL_TAPS_MAX", taps);
+        if (scheme != YAGI_OSC_NCO && scheme != YAGI_OSC_VCO) return fail(YAGI_ERR_CONFIG, "osc: unknown scheme %d", scheme);
+        return YAGI_OK;
+    }
+    int configure(size_t channels, size_t taps, int scheme) {
+        YG_TRY(check_create(channels, taps, scheme));
+        C = channels, L = taps, vco = scheme == YAGI_OSC_VCO;
+        link.assign(C, ChannelLink{1.0f, 0.0f, 0u, 0u, 0ull});
+        phi.assign(C, 0u);
+        hrev.assign(L * C, cf32{0.0f, 0.0f});
+        for (size_t c = 0; c < C; ++c) hrev[(L - 1) * C + c] = cf32{1.0f, 0.0f};      // h = (1, 0, .., 0)
+        hwin.assign((L - 1) * C, cf32{0.0f, 0.0f});
+        return YAGI_OK;
+    }
+    int alloc() {
+        YG_TRY(require_device());
+        std::vector<float> h;
+        osc_device_table(vco, h);
+        YG_TRY(fill(tab, h.data(), h.size() * sizeof(float), st));
+        YG_TRY(link_dev.alloc(C * sizeof(ChannelLink)));
+        YG_TRY(taps_dev.alloc(L * C * sizeof(cf32)));
+        YG_TRY(win.alloc((L - 1) * C * sizeof(cf32)));
+        link_dirty = taps_dirty = true;
+        mirror.in_sync();
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int ensure_host() {
+        return mirror.need_host([&] { return download(hwin.data(), win.cur(), hwin.size() * sizeof(cf32), st); });
+    }
+    int ensure_dev() {
+        if (link_dirty) YG_TRY(upload(link_dev.p, link.data(), C * sizeof(ChannelLink), st));
+        if (taps_dirty) YG_TRY(upload(taps_dev.p, hrev.data(), hrev.size() * sizeof(cf32), st));
+        link_dirty = taps_dirty = false;
+        return mirror.need_dev([&] { return upload(win.cur(), hwin.data(), hwin.size() * sizeof(cf32), st); });
+    }
+    void fold() {                                           // bring the words of every link to the present: adv = 0
+        if (adv != 0)
+            for (ChannelLink &k : link) {
+                k.theta += (uint32_t)adv * k.d_theta;
+                k.t += adv;
+            }
+        adv = 0;
+        link_dirty = true;
+    }
+    int check_link(size_t c) const {
+        if (c >= C) return fail(YAGI_ERR_CONFIG, "channel: link %zu of %zu", c, C);
+        return YAGI_OK;
+    }
+    void reset_link(size_t c) {
+        link[c].theta = phi[c];
+        link[c].t = 0;
+        for (size_t j = 0; j + 1 < L; ++j) hwin[j * C + c] = cf32{0.0f, 0.0f};
+    }
+    int reset(size_t first, size_t count) {
+        if (count == C) {                                   // both copies of the window are rewritten: no download
+            mirror.in_sync();
+        } else {
+            YG_TRY(ensure_host());
+        }
+        fold();
+        for (size_t c = first; c < first + count; ++c) reset_link(c);
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    ChannelShape shape(size_t n) const { return forced.cw ? forced : channel_plan(C, L, n); }
+    static int check_block(size_t C, bool bcast, const cf32 *x, size_t x_pitch, size_t n, const cf32 *y, size_t y_pitch) {
+        if (n >= ((size_t)1 << 31)) return fail(YAGI_ERR_CONFIG, "channel: n must be below 2^31");
+        if ((!bcast && x_pitch < C) || y_pitch < C)
+            return fail(YAGI_ERR_CONFIG, "channel: the pitches are in elements, at least the channel count");
+        if (n == 0) return YAGI_OK;
+        if (!x || !y) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        const size_t nx = bcast ? n : (n - 1) * x_pitch + C, ny = (n - 1) * y_pitch + C;
+        return check_noalias(x, nx * sizeof(cf32), y, ny * sizeof(cf32));
+    }
+    int block_dev(bool bcast, const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch) {
+        if (n == 0) return YAGI_OK;
+        if (((uintptr_t)x | (uintptr_t)y) & 7) return fail(YAGI_ERR_CONFIG, "channel: sample buffers must be 8-byte aligned");
+        YG_TRY(ensure_dev());
+        YG_TRY(launch_channel(shape(n), vco, bcast, tab.p, link_dev.as<ChannelLink>(), taps_dev.as<cf32>(), win.cur<cf32>(),
+                              win.next<cf32>(), seed, adv, C, L, x, x_pitch, n, y, y_pitch, st));
+        if (L > 1) {
+            win.flip();
+            mirror.dev_written();
+        }
+        adv += n;
+        return YAGI_OK;
+    }
+    int block_host(bool bcast, const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch) {
+        YG_TRY(check_block(C, bcast, x, x_pitch, n, y, y_pitch));
+        if (n == 0) return YAGI_OK;
+        YG_TRY(ws.put(st, x, bcast ? n : (n - 1) * x_pitch + C));
+        YG_TRY(ws.y.ensure(n * C * sizeof(cf32)));
+        YG_TRY(block_dev(bcast, ws.x.as<cf32>(), x_pitch, n, ws.y.as<cf32>(), C));
+        std::vector<cf32> t(n * C);
+        YG_TRY(download(t.data(), ws.y.p, n * C * sizeof(cf32), st));
+        for (size_t j = 0; j < n; ++j) std::copy(t.begin() + j * C, t.begin() + (j + 1) * C, y + j * y_pitch);
+        return YAGI_OK;
+    }
+    void put_taps(size_t c, const cf32 *h) {               // hrev_c[j] = h_c[L - 1 - j]
+        for (size_t j = 0; j < L; ++j) hrev[j * C + c] = h[L - 1 - j];
+        taps_dirty = true;
+    }
+    static void fill_shape(ChannelShape s, size_t taps, int vco, bool bcast, yagi_hip_channel_shape *out) {
+        out->links = s.cw, out->rows = s.rows;
+        out->tile_steps = channel_tile_steps(s);
+        out->lds_bytes = channel_lds_bytes(s, taps, vco, bcast);
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_channel_cccf_s : ChannelObj {};
+
+extern "C" {
+
+int yagi_hip_channel_plan(size_t channels, size_t L, size_t n, int osc_scheme, int bcast, yagi_hip_channel_shape *plan) try {
+    CHECK_PTR(plan);
+    YG_TRY(ChannelObj::check_create(channels, L, osc_scheme));
+    if (n >= ((size_t)1 << 31)) return fail(YAGI_ERR_CONFIG, "channel: n must be below 2^31");
+    ChannelObj::fill_shape(channel_plan(channels, L, n), L, osc_scheme == YAGI_OSC_VCO, bcast != 0, plan);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_create(size_t channels, size_t L, int osc_scheme, yagi_hip_channel_cccf *q) try {
+    CHECK_PTR(q);
+    *q = nullptr;
+    auto o = std::make_unique<yagi_hip_channel_cccf_s>();
+    YG_TRY(o->configure(channels, L, osc_scheme));
+    YG_TRY(o->alloc());
+    *q = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_destroy(yagi_hip_channel_cccf q) try {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_clone(yagi_hip_channel_cccf q, yagi_hip_channel_cccf *out) try {
+    CHECK_Q(q);
+    CHECK_PTR(out);
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<yagi_hip_channel_cccf_s>();
+    o->st = q->st, o->C = q->C, o->L = q->L, o->vco = q->vco, o->seed = q->seed, o->adv = q->adv, o->forced = q->forced;
+    o->link = q->link, o->phi = q->phi, o->hrev = q->hrev, o->hwin = q->hwin;
+    YG_TRY(o->alloc());
+    *out = o.release();
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_stream(yagi_hip_channel_cccf q, yagi_stream_t s) try {
+    CHECK_Q(q);
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_reset(yagi_hip_channel_cccf q) try {
+    CHECK_Q(q);
+    return q->reset(0, q->C);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_reset_channel(yagi_hip_channel_cccf q, size_t c) try {
+    CHECK_Q(q);
+    YG_TRY(q->check_link(c));
+    return q->reset(c, 1);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_awgn(yagi_hip_channel_cccf q, size_t c, float n0_db, float snr_db) try {
+    CHECK_Q(q);
+    YG_TRY(q->check_link(c));
+    channel_awgn_words(n0_db, snr_db, &q->link[c].gamma, &q->link[c].nstd);
+    q->link_dirty = true;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_awgn_all(yagi_hip_channel_cccf q, const float *n0_db, const float *snr_db) try {
+    CHECK_Q(q);
+    CHECK_PTR(n0_db);
+    CHECK_PTR(snr_db);
+    for (size_t c = 0; c < q->C; ++c) channel_awgn_words(n0_db[c], snr_db[c], &q->link[c].gamma, &q->link[c].nstd);
+    q->link_dirty = true;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_gain_noise(yagi_hip_channel_cccf q, size_t c, float gamma, float nstd) try {
+    CHECK_Q(q);
+    YG_TRY(q->check_link(c));
+    q->link[c].gamma = gamma, q->link[c].nstd = nstd;
+    q->link_dirty = true;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_gain_noise_all(yagi_hip_channel_cccf q, const float *gamma, const float *nstd) try {
+    CHECK_Q(q);
+    CHECK_PTR(gamma);
+    CHECK_PTR(nstd);
+    for (size_t c = 0; c < q->C; ++c) q->link[c].gamma = gamma[c], q->link[c].nstd = nstd[c];
+    q->link_dirty = true;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_carrier_offset(yagi_hip_channel_cccf q, size_t c, float dphi, float phi) try {
+    CHECK_Q(q);
+    YG_TRY(q->check_link(c));
+    uint32_t df = 0, ph = 0;
+    YG_TRY(osc_constrain(dphi, &df));                       // both words first: no half update
+    YG_TRY(osc_constrain(phi, &ph));
+    q->fold();
+    q->link[c].d_theta = df, q->link[c].theta = ph, q->phi[c] = ph;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_carrier_offset_all(yagi_hip_channel_cccf q, const float *dphi, const float *phi) try {
+    CHECK_Q(q);
+    CHECK_PTR(dphi);
+    CHECK_PTR(phi);
+    std::vector<uint32_t> w(2 * q->C);
+    for (size_t c = 0; c < q->C; ++c) {
+        YG_TRY(osc_constrain(dphi[c], &w[2 * c]));
+        YG_TRY(osc_constrain(phi[c], &w[2 * c + 1]));
+    }
+    q->fold();
+    for (size_t c = 0; c < q->C; ++c) q->link[c].d_theta = w[2 * c], q->link[c].theta = q->phi[c] = w[2 * c + 1];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_multipath(yagi_hip_channel_cccf q, size_t c, const yagi_cf32 *h) try {
+    CHECK_Q(q);
+    CHECK_PTR(h);
+    YG_TRY(q->check_link(c));
+    q->put_taps(c, h);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_multipath_all(yagi_hip_channel_cccf q, const yagi_cf32 *h) try {
+    CHECK_Q(q);
+    CHECK_PTR(h);
+    for (size_t c = 0; c < q->C; ++c) q->put_taps(c, h + c * q->L);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_get_multipath(yagi_hip_channel_cccf q, yagi_cf32 *h) try {
+    CHECK_Q(q);
+    CHECK_PTR(h);
+    for (size_t c = 0; c < q->C; ++c)
+        for (size_t j = 0; j < q->L; ++j) h[c * q->L + j] = q->hrev[(q->L - 1 - j) * q->C + c];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_seed(yagi_hip_channel_cccf q, uint64_t seed) try {
+    CHECK_Q(q);
+    q->seed = seed;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_get_seed(yagi_hip_channel_cccf q, uint64_t *seed) try {
+    CHECK_Q(q);
+    CHECK_PTR(seed);
+    *seed = q->seed;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_position(yagi_hip_channel_cccf q, size_t c, uint64_t t) try {
+    CHECK_Q(q);
+    YG_TRY(q->check_link(c));
+    q->fold();
+    q->link[c].t = t;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_position_all(yagi_hip_channel_cccf q, const uint64_t *t) try {
+    CHECK_Q(q);
+    CHECK_PTR(t);
+    q->fold();
+    for (size_t c = 0; c < q->C; ++c) q->link[c].t = t[c];
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_get_position(yagi_hip_channel_cccf q, uint64_t *t) try {
+    CHECK_Q(q);
+    CHECK_PTR(t);
+    for (size_t c = 0; c < q->C; ++c) t[c] = q->link[c].t + q->adv;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_get_gain_noise(yagi_hip_channel_cccf q, float *gamma, float *nstd) try {
+    CHECK_Q(q);
+    for (size_t c = 0; c < q->C; ++c) {
+        if (gamma) gamma[c] = q->link[c].gamma;
+        if (nstd) nstd[c] = q->link[c].nstd;
+    }
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_get_osc_state(yagi_hip_channel_cccf q, uint32_t *theta, uint32_t *d_theta) try {
+    CHECK_Q(q);
+    for (size_t c = 0; c < q->C; ++c) {
+        if (theta) theta[c] = q->link[c].theta + (uint32_t)q->adv * q->link[c].d_theta;
+        if (d_theta) d_theta[c] = q->link[c].d_theta;
+    }
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_get_channels(yagi_hip_channel_cccf q, size_t *channels) try {
+    CHECK_Q(q);
+    CHECK_PTR(channels);
+    *channels = q->C;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_get_taps(yagi_hip_channel_cccf q, size_t *L) try {
+    CHECK_Q(q);
+    CHECK_PTR(L);
+    *L = q->L;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_set_shape(yagi_hip_channel_cccf q, unsigned links, unsigned rows) try {
+    CHECK_Q(q);
+    if (links == 0 && rows == 0) {
+        q->forced = ChannelShape{0, 0};
+        return YAGI_OK;
+    }
+    if (!channel_shape_ok(ChannelShape{links, rows}))
+        return fail(YAGI_ERR_CONFIG, "channel: the shape (%u links, %u rows) is not admissible", links, rows);
+    q->forced = ChannelShape{links, rows};
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_get_shape(yagi_hip_channel_cccf q, size_t n, int bcast, yagi_hip_channel_shape *shape) try {
+    CHECK_Q(q);
+    CHECK_PTR(shape);
+    ChannelObj::fill_shape(q->shape(n), q->L, q->vco, bcast != 0, shape);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_execute(yagi_hip_channel_cccf q, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
+                                  size_t y_pitch) try {
+    CHECK_Q(q);
+    return q->block_host(false, x, x_pitch, n, y, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_execute_dev(yagi_hip_channel_cccf q, const yagi_cf32 *x_dev, size_t x_pitch, size_t n,
+                                      yagi_cf32 *y_dev, size_t y_pitch) try {
+    CHECK_Q(q);
+    YG_TRY(ChannelObj::check_block(q->C, false, x_dev, x_pitch, n, y_dev, y_pitch));
+    return q->block_dev(false, x_dev, x_pitch, n, y_dev, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_execute_bcast(yagi_hip_channel_cccf q, const yagi_cf32 *x, size_t n, yagi_cf32 *y,
+                                        size_t y_pitch) try {
+    CHECK_Q(q);
+    return q->block_host(true, x, 0, n, y, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_execute_bcast_dev(yagi_hip_channel_cccf q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev,
+                                            size_t y_pitch) try {
+    CHECK_Q(q);
+    YG_TRY(ChannelObj::check_block(q->C, true, x_dev, 0, n, y_dev, y_pitch));
+    return q->block_dev(true, x_dev, 0, n, y_dev, y_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cccf_execute_host(size_t channels, size_t L, int osc_scheme, int bcast, uint64_t seed, const yagi_cf32 *h,
+                                       const float *gamma, const float *nstd, const uint32_t *theta, const uint32_t *d_theta,
+                                       const uint64_t *t, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
+                                       size_t y_pitch) try {
+    ChannelObj o;
+    YG_TRY(o.configure(channels, L, osc_scheme));
+    CHECK_PTR(h);
+    CHECK_PTR(gamma);
+    CHECK_PTR(nstd);
+    CHECK_PTR(theta);
+    CHECK_PTR(d_theta);
+    CHECK_PTR(t);
+    YG_TRY(ChannelObj::check_block(channels, bcast != 0, x, x_pitch, n, y, y_pitch));
+    for (size_t c = 0; c < channels; ++c) {
+        o.put_taps(c, h + c * L);
+        o.link[c] = ChannelLink{gamma[c], nstd[c], theta[c], d_theta[c], t[c]};
+    }
+    std::vector<float> tab;
+    osc_device_table(o.vco, tab);
+    channel_host(o.vco, bcast != 0, tab.data(), o.link.data(), o.hrev.data(), seed, channels, L, x, x_pitch, n, y, y_pitch);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_awgn_words(float n0_db, float snr_db, float *gamma, float *nstd) try {
+    CHECK_PTR(gamma);
+    CHECK_PTR(nstd);
+    channel_awgn_words(n0_db, snr_db, gamma, nstd);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_cos_sin(const uint32_t *k2, size_t n, double *c, double *s) try {
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(k2);
+    CHECK_PTR(c);
+    CHECK_PTR(s);
+    channel_cos_sin_host(k2, n, c, s);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_radius(const uint32_t *k1, size_t n, float *r) try {
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(k1);
+    CHECK_PTR(r);
+    for (size_t i = 0; i < n; ++i)
+        if (k1[i] < 1 || k1[i] > (1u << 24)) return fail(YAGI_ERR_CONFIG, "channel: k1 is in 1 .. 2^24");
+    channel_radius_host(k1, n, r);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_noise(uint64_t seed, uint64_t link, uint64_t first, size_t n, yagi_cf32 *out) try {
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(out);
+    channel_noise_host(seed, link, first, n, out);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_channel_constrain(float phi, uint32_t *word) try {
+    CHECK_PTR(word);
+    return osc_constrain(phi, word);
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

@@ -796,6 +796,49 @@ void symtrack_host(const SymtrackLoop &p, const float *taps, const void *osc_tab
                    size_t C, const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, uint8_t *sym,
                    size_t sym_pitch, size_t ycap, unsigned *status);
 
+// ---- channel_kernels.hip -------------------------------------------------------------------
+// Channel (yagi_hip.h): C independent links of one shape, L taps each.  Nothing feeds back along time, so the grid runs
+// over tiles of cw links x tile_steps steps; a workgroup of kChannelWg lanes is cw links wide and kChannelWg / cw steps
+// deep, and every lane writes `rows` outputs.  link = one ChannelLink per link as of the object's last parameter
+// change, `adv` the samples executed since (the phase and the counter of sample j of the call are link.theta +
+// (u32)(adv + j) link.d_theta and link.t + adv + j).  taps = hrev [L][C]; win = the carried window, [L - 1][C], oldest
+// first; win_next receives the window the call leaves (the caller flips).  x is [n][x_pitch], or one stream of n samples
+// for every link where bcast.
+constexpr int kChannelWg = 256;
+constexpr size_t kChannelLdsMax = 160 * 1024;
+constexpr size_t kChannelGridMax = (size_t)1 << 20;  // workgroups per launch: beyond that a workgroup loops over tiles
+constexpr unsigned kChannelRowsMax = 16;               // outputs per lane: 1, 2, 4, 8 or 16
+struct ChannelLink {
+    float gamma, nstd;
+    uint32_t theta, d_theta;                           // Osc's words
+    unsigned long long t;                              // the noise counter
+};
+static_assert(kChannelGridMax >= YAGI_CHANNEL_CHANNELS_MAX, "one workgroup per link tile at least");
+static_assert(sizeof(ChannelLink) == 24, "device layout");
+struct ChannelShape {
+    unsigned cw, rows;                                 // links per wave row (a power of two, 1 .. 64); outputs per lane
+};
+constexpr size_t channel_tile_steps(ChannelShape s) { return (size_t)(kChannelWg / s.cw) * s.rows; }
+constexpr size_t channel_lds_bytes(ChannelShape s, size_t L, int vco, bool bcast) {
+    return (size_t)1024 * (vco ? 4 : 2) * sizeof(float) + L * s.cw * sizeof(cf32) +
+           (bcast ? channel_tile_steps(s) + (L - 1) + (L - 1) * s.cw : (channel_tile_steps(s) + (L - 1)) * s.cw) * sizeof(cf32);
+}
+static_assert(channel_lds_bytes(ChannelShape{64, kChannelRowsMax}, YAGI_CHANNEL_TAPS_MAX, 1, false) <= kChannelLdsMax,
+              "the largest tile fits with the longest taps");
+bool channel_shape_ok(ChannelShape s);
+ChannelShape channel_plan(size_t C, size_t L, size_t n);      // the shape a call of n steps runs at where none is set
+int launch_channel(ChannelShape s, int vco, bool bcast, const void *osc_tab, const ChannelLink *link, const cf32 *taps,
+                   const cf32 *win, cf32 *win_next, uint64_t seed, uint64_t adv, size_t C, size_t L, const cf32 *x,
+                   size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, hipStream_t st);
+// the same on the host, link after link, from a window of zeros (osc_tab = osc_device_table's image, host memory)
+void channel_host(int vco, bool bcast, const void *osc_tab, const ChannelLink *link, const cf32 *taps, uint64_t seed, size_t C,
+                  size_t L, const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch);
+void channel_awgn_words(float n0_db, float snr_db, float *gamma, float *nstd);   // set_awgn's two words
+// the words of channel_words.hpp on arrays: (C, S)[k2] as f64, R[k1], the noise of (seed, link, counter first + i)
+void channel_cos_sin_host(const uint32_t *k2, size_t n, double *c, double *s);
+void channel_radius_host(const uint32_t *k1, size_t n, float *r);
+void channel_noise_host(uint64_t seed, uint64_t link, uint64_t first, size_t n, cf32 *out);
+
 // ---- symstream_kernels.hip -----------------------------------------------------------------
 // SymStream (yagi_hip.h): samples [0, n) of a call that starts at buf_index p, from the carried window `win` (Ls values,
 // oldest first) and new symbols that come either from the caller's bytes (sym, flag = the result of

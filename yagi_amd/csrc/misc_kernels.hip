@@ -2,19 +2,14 @@
 // (trait DotProd, src/dotprod/mod.rs:13-73) and the filter-window update.
 #include "devmath.hpp"
 #include "kernels.hpp"
+#include "splitmix.hpp"
 
 namespace yagi {
 
 // ---------------------------------------------------------------------------------------------
 // synthetic input: counter-based SplitMix64 + Box-Muller (shape of random/normal.rs:9-44)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t splitmix64_at(uint64_t seed, uint64_t idx) {
-    uint64_t z = seed + (idx + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
+// splitmix64_at: splitmix.hpp, shared with Channel's noise
 template <bool COMPLEX>
 __global__ void __launch_bounds__(256) gen_kernel(uint64_t seed, uint64_t first, size_t n, float *out) {
     const float two_pi = 6.283185307179586f;
