@@ -6713,19 +6713,15 @@ int yagi_hip_pdet_cccf_detect_host(const cf32 *p, size_t L, const float *dphi, s
 // kernel by value with every call.
 namespace yagi {
 
-struct SymsyncObj {
-    hipStream_t st = nullptr;
+// everything that needs no device
+struct SymsyncHost {
     size_t C = 0, k = 0, npfb = 0, Ls = 0, k_out = 1;
     SymsyncLoop p{};
     std::vector<float> taps;                              // [npfb][Ls] entries (H, D)
-    DevBuf taps_dev, state_dev, hist_dev;
     std::vector<SymsyncChan> hs;                          // host mirror
     std::vector<cf32> hh;
-    Mirror mirror;
-    Staging ws;                                           // host block form: x as given; y compact [ycap][C]
-    DevBuf wstatus;
 
-    // everything that needs no device
+    void reset_chan(size_t c) { symsync_reset_chan(&hs[c], k, k_out); }
     int configure(size_t channels, size_t k_, size_t npfb_, const float *h, size_t h_len) {
         if (channels == 0 || channels > (size_t)YAGI_SYMSYNC_CHANNELS_MAX)
             return fail(YAGI_ERR_CONFIG, "symsync: %zu channels are outside 1 .. YAGI_SYMSYNC_CHANNELS_MAX", channels);
@@ -6739,9 +6735,31 @@ struct SymsyncObj {
         YG_TRY(symsync_set_bw(0.01f, &p));
         hs.assign(C, SymsyncChan{});
         hh.assign(Ls * C, cf32{});
-        for (auto &s : hs) symsync_reset_chan(&s, k, k_out);
+        for (size_t c = 0; c < C; ++c) reset_chan(c);
         return YAGI_OK;
     }
+    // the output rate of a design that has not run yet: every channel starts over at it
+    int start_at_rate(size_t k_out_) {
+        if (k_out_ == 0) return fail(YAGI_ERR_CONFIG, "output rate must be greater than 0");
+        k_out = k_out_;
+        p.k_out = k_out_;
+        for (size_t c = 0; c < C; ++c) reset_chan(c);
+        return YAGI_OK;
+    }
+    static int check_block(size_t C, size_t x_pitch, size_t n, size_t y_pitch, size_t ycap) {
+        if (n >= ((size_t)1 << 31) || ycap >= ((size_t)1 << 31))
+            return fail(YAGI_ERR_CONFIG, "symsync: n and ycap must be below 2^31");
+        if (x_pitch < C || y_pitch < C || x_pitch >= ((size_t)1 << 31) || y_pitch >= ((size_t)1 << 31))
+            return fail(YAGI_ERR_CONFIG, "symsync: the pitches are in samples, at least the channel count and below 2^31");
+        return YAGI_OK;
+    }
+};
+
+struct SymsyncObj : SymsyncHost, BankObj<SymsyncObj> {
+    using Host = SymsyncHost;
+    static constexpr const char *kFamily = "symsync";
+    DevBuf taps_dev, state_dev, hist_dev, wstatus;
+
     int alloc() {
         YG_TRY(require_device());
         YG_TRY(fill(taps_dev, taps.data(), taps.size() * sizeof(float), st));
@@ -6751,49 +6769,21 @@ struct SymsyncObj {
         mirror.host_written();
         return YAGI_OK;
     }
-    int ensure_host() {
-        return mirror.need_host([&] {
-            YG_TRY(download(hs.data(), state_dev.p, C * sizeof(SymsyncChan), st));
-            return download(hh.data(), hist_dev.p, Ls * C * sizeof(cf32), st);
-        });
-    }
-    int ensure_dev() {
-        return mirror.need_dev([&] {
-            YG_TRY(upload(state_dev.p, hs.data(), C * sizeof(SymsyncChan), st));
-            return upload(hist_dev.p, hh.data(), Ls * C * sizeof(cf32), st);
-        });
+    template <class F>
+    int each_array(F &&f) {
+        YG_TRY(f(state_dev, hs.data(), C * sizeof(SymsyncChan)));
+        return f(hist_dev, hh.data(), Ls * C * sizeof(cf32));
     }
     int set_output_rate(size_t k_out_) {
         if (k_out_ == 0) return fail(YAGI_ERR_CONFIG, "output rate must be greater than 0");
-        YG_TRY(ensure_host());
-        k_out = k_out_;
-        p.k_out = k_out_;
-        for (auto &s : hs) {
-            s.rate = (float)k / (float)k_out;
-            s.del = s.rate;
-        }
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    int reset_channel(size_t c) {
-        if (c >= C) return fail(YAGI_ERR_CONFIG, "symsync: channel %zu of %zu", c, C);
-        YG_TRY(ensure_host());
-        symsync_reset_chan(&hs[c], k, k_out);
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    int reset() {
-        YG_TRY(ensure_host());
-        for (auto &s : hs) symsync_reset_chan(&s, k, k_out);
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    static int check_block(size_t C, size_t x_pitch, size_t n, size_t y_pitch, size_t ycap) {
-        if (n >= ((size_t)1 << 31) || ycap >= ((size_t)1 << 31))
-            return fail(YAGI_ERR_CONFIG, "symsync: n and ycap must be below 2^31");
-        if (x_pitch < C || y_pitch < C || x_pitch >= ((size_t)1 << 31) || y_pitch >= ((size_t)1 << 31))
-            return fail(YAGI_ERR_CONFIG, "symsync: the pitches are in samples, at least the channel count and below 2^31");
-        return YAGI_OK;
+        return edit([&] {
+            k_out = k_out_;
+            p.k_out = k_out_;
+            for (auto &s : hs) {
+                s.rate = (float)k / (float)k_out;
+                s.del = s.rate;
+            }
+        });
     }
     int block_dev(const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, size_t ycap, unsigned *status) {
         YG_TRY(ensure_dev());
@@ -6809,15 +6799,6 @@ struct SymsyncObj {
 struct yagi_hip_symsync_crcf_s : SymsyncObj {};
 
 namespace {
-
-int symsync_make(yagi_hip_symsync_crcf *q, size_t channels, size_t k, size_t npfb, const float *h, size_t h_len) {
-    *q = nullptr;
-    auto o = std::make_unique<yagi_hip_symsync_crcf_s>();
-    YG_TRY(o->configure(channels, k, npfb, h, h_len));
-    YG_TRY(o->alloc());
-    *q = o.release();
-    return YAGI_OK;
-}
 
 // create_rnyquist (:112-131) and create_kaiser (:133-158): the prototype
 int symsync_rnyquist_taps(int ftype, size_t k, size_t m, float beta, size_t npfb, std::vector<float> &h) {
@@ -6848,8 +6829,7 @@ extern "C" {
 
 int yagi_hip_symsync_crcf_create(size_t channels, size_t k, size_t npfb, const float *h, size_t h_len,
                                  yagi_hip_symsync_crcf *q) try {
-    CHECK_PTR(q);
-    return symsync_make(q, channels, k, npfb, h, h_len);
+    return bank_create(q, channels, k, npfb, h, h_len);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_create_rnyquist(size_t channels, int ftype, size_t k, size_t m, float beta, size_t npfb,
@@ -6858,7 +6838,7 @@ int yagi_hip_symsync_crcf_create_rnyquist(size_t channels, int ftype, size_t k, 
     *q = nullptr;
     std::vector<float> h;
     YG_TRY(symsync_rnyquist_taps(ftype, k, m, beta, npfb, h));
-    return symsync_make(q, channels, k, npfb, h.data(), h.size());
+    return bank_create(q, channels, k, npfb, h.data(), h.size());
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_create_kaiser(size_t channels, size_t k, size_t m, float beta, size_t npfb,
@@ -6867,7 +6847,7 @@ int yagi_hip_symsync_crcf_create_kaiser(size_t channels, size_t k, size_t m, flo
     *q = nullptr;
     std::vector<float> h;
     YG_TRY(symsync_kaiser_taps(k, m, beta, npfb, h));
-    return symsync_make(q, channels, k, npfb, h.data(), h.size());
+    return bank_create(q, channels, k, npfb, h.data(), h.size());
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_rnyquist_taps(int ftype, size_t k, size_t m, float beta, size_t npfb, float *h) try {
@@ -6887,31 +6867,15 @@ int yagi_hip_symsync_crcf_kaiser_taps(size_t k, size_t m, float beta, size_t npf
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_destroy(yagi_hip_symsync_crcf q) try {
-    if (q) (void)hipStreamSynchronize(q->st);
-    delete q;
-    return YAGI_OK;
+    return bank_destroy(q);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_clone(yagi_hip_symsync_crcf q, yagi_hip_symsync_crcf *out) try {
-    CHECK_Q(q);
-    CHECK_PTR(out);
-    *out = nullptr;
-    YG_TRY(q->ensure_host());
-    auto o = std::make_unique<yagi_hip_symsync_crcf_s>();
-    o->st = q->st;
-    o->C = q->C, o->k = q->k, o->npfb = q->npfb, o->Ls = q->Ls, o->k_out = q->k_out, o->p = q->p;
-    o->taps = q->taps, o->hs = q->hs, o->hh = q->hh;
-    YG_TRY(o->alloc());
-    *out = o.release();
-    return YAGI_OK;
+    return bank_clone(q, out);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_set_stream(yagi_hip_symsync_crcf q, yagi_stream_t s) try {
-    CHECK_Q(q);
-    if (q->st == to_stream(s)) return YAGI_OK;
-    YG_HIP(hipStreamSynchronize(q->st));
-    q->st = to_stream(s);
-    return YAGI_OK;
+    return bank_set_stream(q, s);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_reset(yagi_hip_symsync_crcf q) try {
@@ -6937,10 +6901,7 @@ int yagi_hip_symsync_crcf_unlock(yagi_hip_symsync_crcf q) try {
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_is_locked(yagi_hip_symsync_crcf q, int *locked) try {
-    CHECK_Q(q);
-    CHECK_PTR(locked);
-    *locked = q->p.locked != 0;
-    return YAGI_OK;
+    return bank_get(q, locked, [](auto &o) { return o.p.locked != 0; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_set_output_rate(yagi_hip_symsync_crcf q, size_t k_out) try {
@@ -6954,40 +6915,26 @@ int yagi_hip_symsync_crcf_set_lf_bw(yagi_hip_symsync_crcf q, float bw) try {
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_get_channels(yagi_hip_symsync_crcf q, size_t *channels) try {
-    CHECK_Q(q);
-    CHECK_PTR(channels);
-    *channels = q->C;
-    return YAGI_OK;
+    return bank_get(q, channels, [](auto &o) { return o.C; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_get_branch_length(yagi_hip_symsync_crcf q, size_t *Ls) try {
-    CHECK_Q(q);
-    CHECK_PTR(Ls);
-    *Ls = q->Ls;
-    return YAGI_OK;
+    return bank_get(q, Ls, [](auto &o) { return o.Ls; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_get_tau(yagi_hip_symsync_crcf q, float *tau) try {
-    CHECK_Q(q);
-    CHECK_PTR(tau);
-    YG_TRY(q->ensure_host());
-    for (size_t c = 0; c < q->C; ++c) tau[c] = q->hs[c].tau_decim;
-    return YAGI_OK;
+    return bank_get_each(q, tau, [](auto &o, size_t c) { return o.hs[c].tau_decim; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_get_stalled(yagi_hip_symsync_crcf q, uint32_t *stalled) try {
-    CHECK_Q(q);
-    CHECK_PTR(stalled);
-    YG_TRY(q->ensure_host());
-    for (size_t c = 0; c < q->C; ++c) stalled[c] = q->hs[c].stalled;
-    return YAGI_OK;
+    return bank_get_each(q, stalled, [](auto &o, size_t c) { return o.hs[c].stalled; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_execute_dev(yagi_hip_symsync_crcf q, const cf32 *x_dev, size_t x_pitch, size_t n, cf32 *y_dev,
                                       size_t y_pitch, size_t ycap, uint32_t *status_dev) try {
     CHECK_Q(q);
     CHECK_PTR(status_dev);
-    YG_TRY(SymsyncObj::check_block(q->C, x_pitch, n, y_pitch, ycap));
+    YG_TRY(SymsyncHost::check_block(q->C, x_pitch, n, y_pitch, ycap));
     if (n != 0) CHECK_PTR(x_dev);
     if (ycap != 0) CHECK_PTR(y_dev);
     return q->block_dev(x_dev, x_pitch, n, y_dev, y_pitch, ycap, status_dev);
@@ -6999,27 +6946,14 @@ int yagi_hip_symsync_crcf_execute(yagi_hip_symsync_crcf q, const cf32 *x, size_t
     CHECK_PTR(ny);
     CHECK_PTR(stalled);
     const size_t C = q->C;
-    YG_TRY(SymsyncObj::check_block(C, x_pitch, n, y_pitch, ycap));
+    YG_TRY(SymsyncHost::check_block(C, x_pitch, n, y_pitch, ycap));
     if (n != 0) CHECK_PTR(x);
     if (ycap != 0) CHECK_PTR(y);
     const size_t nx = n ? (n - 1) * x_pitch + C : 0;
     YG_TRY(q->ws.put(q->st, x, nx));
     YG_TRY(q->ws.y.ensure(ycap * C * sizeof(cf32)));
     YG_TRY(q->block_dev(q->ws.x.as<cf32>(), x_pitch, n, q->ws.y.as<cf32>(), C, ycap, q->wstatus.as<unsigned>()));
-    std::vector<unsigned> status(2 * C);
-    YG_TRY(download(status.data(), q->wstatus.p, 2 * C * sizeof(unsigned), q->st));
-    size_t rows = 0;
-    for (size_t c = 0; c < C; ++c) {
-        ny[c] = status[c];
-        stalled[c] = status[C + c];
-        rows = std::max(rows, (size_t)status[c]);
-    }
-    std::vector<cf32> t(rows * C);
-    YG_TRY(download(t.data(), q->ws.y.p, rows * C * sizeof(cf32), q->st));
-    for (size_t j = 0; j < rows; ++j)
-        for (size_t c = 0; c < C; ++c)
-            if (j < ny[c]) y[j * y_pitch + c] = t[j * C + c];
-    return YAGI_OK;
+    return q->fetch_ragged(q->wstatus, 2 * C, ny, stalled, y, y_pitch);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symsync_crcf_execute_host(size_t channels, size_t k, size_t npfb, const float *h, size_t h_len, size_t k_out,
@@ -7027,15 +6961,12 @@ int yagi_hip_symsync_crcf_execute_host(size_t channels, size_t k, size_t npfb, c
                                        size_t y_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled, float *tau) try {
     CHECK_PTR(ny);
     CHECK_PTR(stalled);
-    SymsyncObj o;
+    SymsyncHost o;
     YG_TRY(o.configure(channels, k, npfb, h, h_len));
-    if (k_out == 0) return fail(YAGI_ERR_CONFIG, "output rate must be greater than 0");
-    o.k_out = k_out;
-    o.p.k_out = k_out;
-    for (auto &s : o.hs) symsync_reset_chan(&s, k, k_out);
+    YG_TRY(o.start_at_rate(k_out));
     YG_TRY(symsync_set_bw(bw, &o.p));
     o.p.locked = locked != 0;
-    YG_TRY(SymsyncObj::check_block(channels, x_pitch, n, y_pitch, ycap));
+    YG_TRY(SymsyncHost::check_block(channels, x_pitch, n, y_pitch, ycap));
     if (n != 0) CHECK_PTR(x);
     if (ycap != 0) CHECK_PTR(y);
     symsync_host(o.p, o.taps.data(), o.hs.data(), o.hh.data(), channels, x, x_pitch, n, y, y_pitch, ycap, ny, stalled);
@@ -7052,16 +6983,60 @@ int yagi_hip_symsync_crcf_execute_host(size_t channels, size_t k, size_t npfb, c
 // copies are synchronised lazily (Mirror).  mu, k and the mode travel to the kernel by value with every call.
 namespace yagi {
 
-struct EqlmsObj {
-    hipStream_t st = nullptr;
+// set_constellation's table, of EqLms and EqRls alike
+static int eq_check_table(const cf32 *t, size_t M) {
+    if (M == 0 || M > (size_t)YAGI_EQLMS_TABLE_MAX)
+        return fail(YAGI_ERR_CONFIG, "eqlms: a constellation of %zu points is outside 1 .. YAGI_EQLMS_TABLE_MAX", M);
+    if (!t) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    return YAGI_OK;
+}
+
+// What the device halves of EqLms and EqRls share: DECISION's table and the host block form.  D supplies kTrain,
+// check_block(..) and block_dev(..), and its host struct the table.
+template <class D>
+struct EqBankObj : BankObj<D> {
+    DevBuf table_dev;
+    Staging wsd;                                          // host block form: the rows of d
+
+    int alloc_table() {
+        D &o = this->self();
+        if (o.table.empty()) return YAGI_OK;
+        return fill(table_dev, o.table.data(), o.table.size() * sizeof(cf32), this->st);
+    }
+    int set_constellation(const cf32 *table, size_t M) {
+        D &o = this->self();
+        YG_TRY(eq_check_table(table, M));
+        YG_HIP(hipStreamSynchronize(this->st));              // a launch in flight may still read the table
+        o.table.assign(table, table + M);
+        return fill(table_dev, o.table.data(), M * sizeof(cf32), this->st);
+    }
+    int block_host(int mode, size_t k, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, cf32 *y,
+                   size_t y_pitch) {
+        D &o = this->self();
+        const size_t C = o.C;
+        Staging &ws = this->ws;
+        size_t rows = 0;
+        YG_TRY(D::check_block(C, mode, k, x_pitch, n, d != nullptr, d_pitch, o.table.size(), y_pitch, &rows));
+        if (n == 0) return YAGI_OK;
+        if (!x || !y) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        YG_TRY(ws.put(this->st, x, (n - 1) * x_pitch + C));
+        const bool train = mode == D::kTrain;
+        if (train) {
+            YG_TRY(wsd.put(this->st, d, (rows - 1) * d_pitch + C));
+        }
+        YG_TRY(ws.y.ensure(rows * C * sizeof(cf32)));
+        YG_TRY(o.block_dev(mode, k, ws.x.as<cf32>(), x_pitch, n, train ? wsd.x.as<cf32>() : nullptr, d_pitch, ws.y.as<cf32>(), C));
+        return download_rows(this->st, ws.y, rows, C, y, y_pitch);
+    }
+};
+
+// everything that needs no device
+struct EqlmsHost {
     size_t C = 0, h_len = 0;
     float mu = 0.5f;
     std::vector<cf32> h0, table;
-    DevBuf w_dev, hist_dev, state_dev, table_dev;
     std::vector<cf32> hw, hh;                             // host mirror: [h_len][C]
     std::vector<EqlmsChan> hs;
-    Mirror mirror;
-    Staging ws, wsd;                                      // host block forms: x and a compact y; the rows of d
 
     void reset_chan(size_t c) {
         for (size_t i = 0; i < h_len; ++i) {
@@ -7070,7 +7045,7 @@ struct EqlmsObj {
         }
         hs[c] = EqlmsChan{};
     }
-    // new (:25-49); everything that needs no device
+    // new (:25-49)
     int configure(size_t channels, const cf32 *h, size_t h_len_) {
         if (channels == 0 || channels > (size_t)YAGI_EQLMS_CHANNELS_MAX)
             return fail(YAGI_ERR_CONFIG, "eqlms: %zu channels are outside 1 .. YAGI_EQLMS_CHANNELS_MAX", channels);
@@ -7089,53 +7064,9 @@ struct EqlmsObj {
         for (size_t c = 0; c < C; ++c) reset_chan(c);
         return YAGI_OK;
     }
-    int alloc() {
-        YG_TRY(require_device());
-        YG_TRY(w_dev.alloc(h_len * C * sizeof(cf32)));
-        YG_TRY(hist_dev.alloc(h_len * C * sizeof(cf32)));
-        YG_TRY(state_dev.alloc(C * sizeof(EqlmsChan)));
-        if (!table.empty()) {
-            YG_TRY(fill(table_dev, table.data(), table.size() * sizeof(cf32), st));
-        }
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    int ensure_host() {
-        return mirror.need_host([&] {
-            YG_TRY(download(hw.data(), w_dev.p, h_len * C * sizeof(cf32), st));
-            YG_TRY(download(hh.data(), hist_dev.p, h_len * C * sizeof(cf32), st));
-            return download(hs.data(), state_dev.p, C * sizeof(EqlmsChan), st);
-        });
-    }
-    int ensure_dev() {
-        return mirror.need_dev([&] {
-            YG_TRY(upload(w_dev.p, hw.data(), h_len * C * sizeof(cf32), st));
-            YG_TRY(upload(hist_dev.p, hh.data(), h_len * C * sizeof(cf32), st));
-            return upload(state_dev.p, hs.data(), C * sizeof(EqlmsChan), st);
-        });
-    }
-    int reset_channel(size_t c) {
-        if (c >= C) return fail(YAGI_ERR_CONFIG, "eqlms: channel %zu of %zu", c, C);
-        YG_TRY(ensure_host());
-        reset_chan(c);
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    int reset() {
-        YG_TRY(ensure_host());
-        for (size_t c = 0; c < C; ++c) reset_chan(c);
-        mirror.host_written();
-        return YAGI_OK;
-    }
     static int set_bw(float mu_, float *mu) {               // (:105-111)
         if (mu_ < 0.0f) return fail(YAGI_ERR_CONFIG, "learning rate cannot be less than zero");
         *mu = mu_;
-        return YAGI_OK;
-    }
-    static int check_table(const cf32 *t, size_t M) {
-        if (M == 0 || M > (size_t)YAGI_EQLMS_TABLE_MAX)
-            return fail(YAGI_ERR_CONFIG, "eqlms: a constellation of %zu points is outside 1 .. YAGI_EQLMS_TABLE_MAX", M);
-        if (!t) return fail(YAGI_ERR_CONFIG, "null pointer argument");
         return YAGI_OK;
     }
     // call = a mode (decim_block) or YAGI_EQLMS_EXECUTE; sets the rows of y
@@ -7160,6 +7091,40 @@ struct EqlmsObj {
             return fail(YAGI_ERR_CONFIG, "eqlms: DECISION needs set_constellation first");
         return YAGI_OK;
     }
+    void coefficients(cf32 *w0) const {
+        for (size_t c = 0; c < C; ++c)
+            for (size_t i = 0; i < h_len; ++i) w0[c * h_len + i] = hw[i * C + c];
+    }
+    void weights(cf32 *w) const {                           // get_weights (:121-123)
+        for (size_t c = 0; c < C; ++c)
+            for (size_t i = 0; i < h_len; ++i) {
+                const cf32 v = hw[(h_len - 1 - i) * C + c];
+                w[c * h_len + i] = cf32{v.re, -v.im};
+            }
+    }
+};
+
+struct EqlmsObj : EqlmsHost, EqBankObj<EqlmsObj> {
+    using Host = EqlmsHost;
+    static constexpr const char *kFamily = "eqlms";
+    static constexpr int kTrain = YAGI_EQLMS_TRAIN;
+    DevBuf w_dev, hist_dev, state_dev;
+
+    int alloc() {
+        YG_TRY(require_device());
+        YG_TRY(w_dev.alloc(h_len * C * sizeof(cf32)));
+        YG_TRY(hist_dev.alloc(h_len * C * sizeof(cf32)));
+        YG_TRY(state_dev.alloc(C * sizeof(EqlmsChan)));
+        YG_TRY(alloc_table());
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    template <class F>
+    int each_array(F &&f) {
+        YG_TRY(f(w_dev, hw.data(), h_len * C * sizeof(cf32)));
+        YG_TRY(f(hist_dev, hh.data(), h_len * C * sizeof(cf32)));
+        return f(state_dev, hs.data(), C * sizeof(EqlmsChan));
+    }
     int block_dev(int call, size_t k, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, cf32 *y,
                   size_t y_pitch) {
         if (n == 0) return YAGI_OK;
@@ -7169,24 +7134,6 @@ struct EqlmsObj {
         mirror.dev_written();
         return YAGI_OK;
     }
-    int block_host(int call, size_t k, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, cf32 *y,
-                   size_t y_pitch) {
-        size_t rows = 0;
-        YG_TRY(check_block(C, call, k, x_pitch, n, d != nullptr, d_pitch, table.size(), y_pitch, &rows));
-        if (n == 0) return YAGI_OK;
-        if (!x || !y) return fail(YAGI_ERR_CONFIG, "null pointer argument");
-        YG_TRY(ws.put(st, x, (n - 1) * x_pitch + C));
-        const bool train = call == YAGI_EQLMS_TRAIN;
-        if (train) {
-            YG_TRY(wsd.put(st, d, (rows - 1) * d_pitch + C));
-        }
-        YG_TRY(ws.y.ensure(rows * C * sizeof(cf32)));
-        YG_TRY(block_dev(call, k, ws.x.as<cf32>(), x_pitch, n, train ? wsd.x.as<cf32>() : nullptr, d_pitch, ws.y.as<cf32>(), C));
-        std::vector<cf32> t(rows * C);
-        YG_TRY(download(t.data(), ws.y.p, rows * C * sizeof(cf32), st));
-        for (size_t j = 0; j < rows; ++j) std::copy(t.begin() + j * C, t.begin() + (j + 1) * C, y + j * y_pitch);
-        return YAGI_OK;
-    }
 };
 
 }  // namespace yagi
@@ -7194,15 +7141,6 @@ struct EqlmsObj {
 struct yagi_hip_eqlms_cccf_s : EqlmsObj {};
 
 namespace {
-
-int eqlms_make(yagi_hip_eqlms_cccf *q, size_t channels, const cf32 *h, size_t h_len) {
-    *q = nullptr;
-    auto o = std::make_unique<yagi_hip_eqlms_cccf_s>();
-    YG_TRY(o->configure(channels, h, h_len));
-    YG_TRY(o->alloc());
-    *q = o.release();
-    return YAGI_OK;
-}
 
 // new_rnyquist (:51-76): the prototype over fl(k), as complex taps
 int eqlms_rnyquist_taps(int ftype, size_t k, size_t m, float beta, float dt, std::vector<cf32> &hc) {
@@ -7240,8 +7178,7 @@ int eqlms_lowpass_taps(size_t h_len, float fc, std::vector<cf32> &hc) {
 extern "C" {
 
 int yagi_hip_eqlms_cccf_create(size_t channels, const cf32 *h, size_t h_len, yagi_hip_eqlms_cccf *q) try {
-    CHECK_PTR(q);
-    return eqlms_make(q, channels, h, h_len);
+    return bank_create(q, channels, h, h_len);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_create_rnyquist(size_t channels, int ftype, size_t k, size_t m, float beta, float dt,
@@ -7250,7 +7187,7 @@ int yagi_hip_eqlms_cccf_create_rnyquist(size_t channels, int ftype, size_t k, si
     *q = nullptr;
     std::vector<cf32> hc;
     YG_TRY(eqlms_rnyquist_taps(ftype, k, m, beta, dt, hc));
-    return eqlms_make(q, channels, hc.data(), hc.size());
+    return bank_create(q, channels, hc.data(), hc.size());
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_create_lowpass(size_t channels, size_t h_len, float fc, yagi_hip_eqlms_cccf *q) try {
@@ -7258,35 +7195,19 @@ int yagi_hip_eqlms_cccf_create_lowpass(size_t channels, size_t h_len, float fc, 
     *q = nullptr;
     std::vector<cf32> hc;
     YG_TRY(eqlms_lowpass_taps(h_len, fc, hc));
-    return eqlms_make(q, channels, hc.data(), hc.size());
+    return bank_create(q, channels, hc.data(), hc.size());
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_destroy(yagi_hip_eqlms_cccf q) try {
-    if (q) (void)hipStreamSynchronize(q->st);
-    delete q;
-    return YAGI_OK;
+    return bank_destroy(q);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_clone(yagi_hip_eqlms_cccf q, yagi_hip_eqlms_cccf *out) try {
-    CHECK_Q(q);
-    CHECK_PTR(out);
-    *out = nullptr;
-    YG_TRY(q->ensure_host());
-    auto o = std::make_unique<yagi_hip_eqlms_cccf_s>();
-    o->st = q->st;
-    o->C = q->C, o->h_len = q->h_len, o->mu = q->mu;
-    o->h0 = q->h0, o->table = q->table, o->hw = q->hw, o->hh = q->hh, o->hs = q->hs;
-    YG_TRY(o->alloc());
-    *out = o.release();
-    return YAGI_OK;
+    return bank_clone(q, out);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_set_stream(yagi_hip_eqlms_cccf q, yagi_stream_t s) try {
-    CHECK_Q(q);
-    if (q->st == to_stream(s)) return YAGI_OK;
-    YG_HIP(hipStreamSynchronize(q->st));
-    q->st = to_stream(s);
-    return YAGI_OK;
+    return bank_set_stream(q, s);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_reset(yagi_hip_eqlms_cccf q) try {
@@ -7301,57 +7222,40 @@ int yagi_hip_eqlms_cccf_reset_channel(yagi_hip_eqlms_cccf q, size_t c) try {
 
 int yagi_hip_eqlms_cccf_set_bw(yagi_hip_eqlms_cccf q, float mu) try {
     CHECK_Q(q);
-    return EqlmsObj::set_bw(mu, &q->mu);
+    return EqlmsHost::set_bw(mu, &q->mu);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_get_bw(yagi_hip_eqlms_cccf q, float *mu) try {
-    CHECK_Q(q);
-    CHECK_PTR(mu);
-    *mu = q->mu;
-    return YAGI_OK;
+    return bank_get(q, mu, [](auto &o) { return o.mu; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_get_length(yagi_hip_eqlms_cccf q, size_t *h_len) try {
-    CHECK_Q(q);
-    CHECK_PTR(h_len);
-    *h_len = q->h_len;
-    return YAGI_OK;
+    return bank_get(q, h_len, [](auto &o) { return o.h_len; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_get_channels(yagi_hip_eqlms_cccf q, size_t *channels) try {
-    CHECK_Q(q);
-    CHECK_PTR(channels);
-    *channels = q->C;
-    return YAGI_OK;
+    return bank_get(q, channels, [](auto &o) { return o.C; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_get_coefficients(yagi_hip_eqlms_cccf q, cf32 *w0) try {
     CHECK_Q(q);
     CHECK_PTR(w0);
     YG_TRY(q->ensure_host());
-    for (size_t c = 0; c < q->C; ++c)
-        for (size_t i = 0; i < q->h_len; ++i) w0[c * q->h_len + i] = q->hw[i * q->C + c];
+    q->coefficients(w0);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 
-int yagi_hip_eqlms_cccf_get_weights(yagi_hip_eqlms_cccf q, cf32 *w) try {      // (:121-123)
+int yagi_hip_eqlms_cccf_get_weights(yagi_hip_eqlms_cccf q, cf32 *w) try {
     CHECK_Q(q);
     CHECK_PTR(w);
     YG_TRY(q->ensure_host());
-    for (size_t c = 0; c < q->C; ++c)
-        for (size_t i = 0; i < q->h_len; ++i) {
-            const cf32 v = q->hw[(q->h_len - 1 - i) * q->C + c];
-            w[c * q->h_len + i] = cf32{v.re, -v.im};
-        }
+    q->weights(w);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_set_constellation(yagi_hip_eqlms_cccf q, const cf32 *table, size_t M) try {
     CHECK_Q(q);
-    YG_TRY(EqlmsObj::check_table(table, M));
-    YG_HIP(hipStreamSynchronize(q->st));                     // a launch in flight may still read the table
-    q->table.assign(table, table + M);
-    return fill(q->table_dev, q->table.data(), M * sizeof(cf32), q->st);
+    return q->set_constellation(table, M);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqlms_cccf_execute_block(yagi_hip_eqlms_cccf q, size_t k, const cf32 *x, size_t x_pitch, size_t n, cf32 *y,
@@ -7364,7 +7268,7 @@ int yagi_hip_eqlms_cccf_execute_block_dev(yagi_hip_eqlms_cccf q, size_t k, const
                                           cf32 *y_dev, size_t y_pitch) try {
     CHECK_Q(q);
     size_t rows = 0;
-    YG_TRY(EqlmsObj::check_block(q->C, YAGI_EQLMS_EXECUTE, k, x_pitch, n, false, 0, 0, y_pitch, &rows));
+    YG_TRY(EqlmsHost::check_block(q->C, YAGI_EQLMS_EXECUTE, k, x_pitch, n, false, 0, 0, y_pitch, &rows));
     if (n != 0) {
         CHECK_PTR(x_dev);
         CHECK_PTR(y_dev);
@@ -7384,7 +7288,7 @@ int yagi_hip_eqlms_cccf_decim_block_dev(yagi_hip_eqlms_cccf q, size_t k, int mod
     CHECK_Q(q);
     if (mode == YAGI_EQLMS_EXECUTE) return fail(YAGI_ERR_CONFIG, "eqlms: unknown update mode %d", mode);
     size_t rows = 0;
-    YG_TRY(EqlmsObj::check_block(q->C, mode, k, x_pitch, n, d_dev != nullptr, d_pitch, q->table.size(), y_pitch, &rows));
+    YG_TRY(EqlmsHost::check_block(q->C, mode, k, x_pitch, n, d_dev != nullptr, d_pitch, q->table.size(), y_pitch, &rows));
     if (n != 0) {
         CHECK_PTR(x_dev);
         CHECK_PTR(y_dev);
@@ -7395,23 +7299,21 @@ int yagi_hip_eqlms_cccf_decim_block_dev(yagi_hip_eqlms_cccf q, size_t k, int mod
 int yagi_hip_eqlms_cccf_execute_host(size_t channels, const cf32 *h, size_t h_len, float mu, int call, size_t k,
                                      const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch,
                                      const cf32 *table, size_t M, cf32 *y, size_t y_pitch, cf32 *w0) try {
-    EqlmsObj o;
+    EqlmsHost o;
     YG_TRY(o.configure(channels, h, h_len));
-    YG_TRY(EqlmsObj::set_bw(mu, &o.mu));
+    YG_TRY(EqlmsHost::set_bw(mu, &o.mu));
     if (call == YAGI_EQLMS_DECISION) {
-        YG_TRY(EqlmsObj::check_table(table, M));
+        YG_TRY(eq_check_table(table, M));
     }
     size_t rows = 0;
-    YG_TRY(EqlmsObj::check_block(channels, call, k, x_pitch, n, d != nullptr, d_pitch, M, y_pitch, &rows));
+    YG_TRY(EqlmsHost::check_block(channels, call, k, x_pitch, n, d != nullptr, d_pitch, M, y_pitch, &rows));
     if (n != 0) {
         CHECK_PTR(x);
         CHECK_PTR(y);
     }
     eqlms_host(call, h_len, o.mu, o.hw.data(), o.hh.data(), o.hs.data(), channels, k, x, x_pitch, n, d, d_pitch, table, M, y,
                y_pitch);
-    if (w0)
-        for (size_t c = 0; c < channels; ++c)
-            for (size_t i = 0; i < h_len; ++i) w0[c * h_len + i] = o.hw[i * channels + c];
+    if (w0) o.coefficients(w0);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 
@@ -7423,15 +7325,12 @@ int yagi_hip_eqlms_cccf_execute_host(size_t channels, const cf32 *h, size_t h_le
 // copies are synchronised lazily (Mirror).  lambda, k, the mode and the lanes per channel travel to the kernel by value.
 namespace yagi {
 
-struct EqrlsObj {
-    hipStream_t st = nullptr;
+// everything that needs no device
+struct EqrlsHost {
     size_t C = 0, p = 0, lanes = 0;                       // lanes: set_lanes' override, 0 = the planner's choice
     float lambda = 0.99f;
     std::vector<cf32> h0, table;
-    DevBuf P_dev, w0_dev, w1_dev, hist_dev, table_dev;
     std::vector<cf32> hP, hw0, hw1, hh;                   // host mirror: [p p][C] and [p][C]
-    Mirror mirror;
-    Staging ws, wsd;                                      // host block forms: x and a compact y; the rows of d
 
     // reset (:76-88): w1 stays
     void reset_chan(size_t c) {
@@ -7442,7 +7341,7 @@ struct EqrlsObj {
             hh[i * C + c] = cf32{0.0f, 0.0f};
         }
     }
-    // new (:31-62); everything that needs no device
+    // new (:31-62)
     static int check_design(size_t channels, size_t p_) {
         if (channels == 0 || channels > (size_t)YAGI_EQRLS_CHANNELS_MAX)
             return fail(YAGI_ERR_CONFIG, "eqrls: %zu channels are outside 1 .. YAGI_EQRLS_CHANNELS_MAX", channels);
@@ -7466,47 +7365,6 @@ struct EqrlsObj {
         hw1.assign(p * C, cf32{});
         hh.assign(p * C, cf32{});
         for (size_t c = 0; c < C; ++c) reset_chan(c);
-        return YAGI_OK;
-    }
-    int alloc() {
-        YG_TRY(require_device());
-        YG_TRY(P_dev.alloc(p * p * C * sizeof(cf32)));
-        YG_TRY(w0_dev.alloc(p * C * sizeof(cf32)));
-        YG_TRY(w1_dev.alloc(p * C * sizeof(cf32)));
-        YG_TRY(hist_dev.alloc(p * C * sizeof(cf32)));
-        if (!table.empty()) {
-            YG_TRY(fill(table_dev, table.data(), table.size() * sizeof(cf32), st));
-        }
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    int ensure_host() {
-        return mirror.need_host([&] {
-            YG_TRY(download(hP.data(), P_dev.p, p * p * C * sizeof(cf32), st));
-            YG_TRY(download(hw0.data(), w0_dev.p, p * C * sizeof(cf32), st));
-            YG_TRY(download(hw1.data(), w1_dev.p, p * C * sizeof(cf32), st));
-            return download(hh.data(), hist_dev.p, p * C * sizeof(cf32), st);
-        });
-    }
-    int ensure_dev() {
-        return mirror.need_dev([&] {
-            YG_TRY(upload(P_dev.p, hP.data(), p * p * C * sizeof(cf32), st));
-            YG_TRY(upload(w0_dev.p, hw0.data(), p * C * sizeof(cf32), st));
-            YG_TRY(upload(w1_dev.p, hw1.data(), p * C * sizeof(cf32), st));
-            return upload(hist_dev.p, hh.data(), p * C * sizeof(cf32), st);
-        });
-    }
-    int reset_channel(size_t c) {
-        if (c >= C) return fail(YAGI_ERR_CONFIG, "eqrls: channel %zu of %zu", c, C);
-        YG_TRY(ensure_host());
-        reset_chan(c);
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    int reset() {
-        YG_TRY(ensure_host());
-        for (size_t c = 0; c < C; ++c) reset_chan(c);
-        mirror.host_written();
         return YAGI_OK;
     }
     static int set_bw(float l, float *lambda) {             // (:94-100)
@@ -7541,6 +7399,40 @@ struct EqrlsObj {
             return fail(YAGI_ERR_CONFIG, "eqrls: DECISION needs set_constellation first");
         return YAGI_OK;
     }
+    // c-major copies of a mirrored array of `len` rows, as the getters hand them out
+    void gather(const std::vector<cf32> &a, size_t len, cf32 *out) const {
+        for (size_t c = 0; c < C; ++c)
+            for (size_t e = 0; e < len; ++e) out[c * len + e] = a[e * C + c];
+    }
+    void weights(cf32 *w) const {                           // get_weights (:148-156): w1 reversed
+        for (size_t c = 0; c < C; ++c)
+            for (size_t i = 0; i < p; ++i) w[c * p + i] = hw1[(p - 1 - i) * C + c];
+    }
+};
+
+struct EqrlsObj : EqrlsHost, EqBankObj<EqrlsObj> {
+    using Host = EqrlsHost;
+    static constexpr const char *kFamily = "eqrls";
+    static constexpr int kTrain = YAGI_EQRLS_TRAIN;
+    DevBuf P_dev, w0_dev, w1_dev, hist_dev;
+
+    int alloc() {
+        YG_TRY(require_device());
+        YG_TRY(P_dev.alloc(p * p * C * sizeof(cf32)));
+        YG_TRY(w0_dev.alloc(p * C * sizeof(cf32)));
+        YG_TRY(w1_dev.alloc(p * C * sizeof(cf32)));
+        YG_TRY(hist_dev.alloc(p * C * sizeof(cf32)));
+        YG_TRY(alloc_table());
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    template <class F>
+    int each_array(F &&f) {
+        YG_TRY(f(P_dev, hP.data(), p * p * C * sizeof(cf32)));
+        YG_TRY(f(w0_dev, hw0.data(), p * C * sizeof(cf32)));
+        YG_TRY(f(w1_dev, hw1.data(), p * C * sizeof(cf32)));
+        return f(hist_dev, hh.data(), p * C * sizeof(cf32));
+    }
     int block_dev(int mode, size_t k, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, cf32 *y,
                   size_t y_pitch) {
         if (n == 0) return YAGI_OK;
@@ -7549,24 +7441,6 @@ struct EqrlsObj {
                             w1_dev.as<cf32>(), hist_dev.as<cf32>(), C, k, x, x_pitch, n, d, d_pitch, table_dev.as<cf32>(),
                             table.size(), y, y_pitch, st));
         mirror.dev_written();
-        return YAGI_OK;
-    }
-    int block_host(int mode, size_t k, const cf32 *x, size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, cf32 *y,
-                   size_t y_pitch) {
-        size_t rows = 0;
-        YG_TRY(check_block(C, mode, k, x_pitch, n, d != nullptr, d_pitch, table.size(), y_pitch, &rows));
-        if (n == 0) return YAGI_OK;
-        if (!x || !y) return fail(YAGI_ERR_CONFIG, "null pointer argument");
-        YG_TRY(ws.put(st, x, (n - 1) * x_pitch + C));
-        const bool train = mode == YAGI_EQRLS_TRAIN;
-        if (train) {
-            YG_TRY(wsd.put(st, d, (rows - 1) * d_pitch + C));
-        }
-        YG_TRY(ws.y.ensure(rows * C * sizeof(cf32)));
-        YG_TRY(block_dev(mode, k, ws.x.as<cf32>(), x_pitch, n, train ? wsd.x.as<cf32>() : nullptr, d_pitch, ws.y.as<cf32>(), C));
-        std::vector<cf32> t(rows * C);
-        YG_TRY(download(t.data(), ws.y.p, rows * C * sizeof(cf32), st));
-        for (size_t j = 0; j < rows; ++j) std::copy(t.begin() + j * C, t.begin() + (j + 1) * C, y + j * y_pitch);
         return YAGI_OK;
     }
     // train (:158-176) up to its loop: the checks, reset() and w0[i] = w[p - 1 - i], on the host mirror
@@ -7580,10 +7454,6 @@ struct EqrlsObj {
             for (size_t i = 0; i < p; ++i) hw0[i * C + c] = w[c * p + (p - 1 - i)];
         return YAGI_OK;
     }
-    void weights(cf32 *w) const {                           // get_weights (:148-156): w1 reversed
-        for (size_t c = 0; c < C; ++c)
-            for (size_t i = 0; i < p; ++i) w[c * p + i] = hw1[(p - 1 - i) * C + c];
-    }
 };
 
 }  // namespace yagi
@@ -7594,7 +7464,7 @@ extern "C" {
 
 int yagi_hip_eqrls_plan(size_t channels, size_t p, size_t *L, size_t *lds_bytes, unsigned *admissible) try {
     CHECK_PTR(L);
-    YG_TRY(EqrlsObj::check_design(channels, p));
+    YG_TRY(EqrlsHost::check_design(channels, p));
     *L = eqrls_plan(channels, p);
     if (lds_bytes) *lds_bytes = eqrls_lds_bytes(p, *L);
     if (admissible) *admissible = eqrls_admissible(p);
@@ -7602,13 +7472,7 @@ int yagi_hip_eqrls_plan(size_t channels, size_t p, size_t *L, size_t *lds_bytes,
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_create(size_t channels, const cf32 *h, size_t p, yagi_hip_eqrls_cccf *q) try {
-    CHECK_PTR(q);
-    *q = nullptr;
-    auto o = std::make_unique<yagi_hip_eqrls_cccf_s>();
-    YG_TRY(o->configure(channels, h, p));
-    YG_TRY(o->alloc());
-    *q = o.release();
-    return YAGI_OK;
+    return bank_create(q, channels, h, p);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_recreate(yagi_hip_eqrls_cccf q, const cf32 *h, size_t p) try {
@@ -7617,7 +7481,7 @@ int yagi_hip_eqrls_cccf_recreate(yagi_hip_eqrls_cccf q, const cf32 *h, size_t p)
         if (h) std::copy(h, h + p, q->h0.begin());
         return YAGI_OK;
     }
-    YG_TRY(EqrlsObj::check_design(q->C, p));                  // the object is left as it was where the new design is refused
+    YG_TRY(EqrlsHost::check_design(q->C, p));                 // the object is left as it was where the new design is refused
     YG_HIP(hipStreamSynchronize(q->st));
     YG_TRY(q->configure(q->C, h, p));
     q->mirror.in_sync();
@@ -7625,31 +7489,15 @@ int yagi_hip_eqrls_cccf_recreate(yagi_hip_eqrls_cccf q, const cf32 *h, size_t p)
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_destroy(yagi_hip_eqrls_cccf q) try {
-    if (q) (void)hipStreamSynchronize(q->st);
-    delete q;
-    return YAGI_OK;
+    return bank_destroy(q);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_clone(yagi_hip_eqrls_cccf q, yagi_hip_eqrls_cccf *out) try {
-    CHECK_Q(q);
-    CHECK_PTR(out);
-    *out = nullptr;
-    YG_TRY(q->ensure_host());
-    auto o = std::make_unique<yagi_hip_eqrls_cccf_s>();
-    o->st = q->st;
-    o->C = q->C, o->p = q->p, o->lanes = q->lanes, o->lambda = q->lambda;
-    o->h0 = q->h0, o->table = q->table, o->hP = q->hP, o->hw0 = q->hw0, o->hw1 = q->hw1, o->hh = q->hh;
-    YG_TRY(o->alloc());
-    *out = o.release();
-    return YAGI_OK;
+    return bank_clone(q, out);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_set_stream(yagi_hip_eqrls_cccf q, yagi_stream_t s) try {
-    CHECK_Q(q);
-    if (q->st == to_stream(s)) return YAGI_OK;
-    YG_HIP(hipStreamSynchronize(q->st));
-    q->st = to_stream(s);
-    return YAGI_OK;
+    return bank_set_stream(q, s);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_reset(yagi_hip_eqrls_cccf q) try {
@@ -7664,36 +7512,26 @@ int yagi_hip_eqrls_cccf_reset_channel(yagi_hip_eqrls_cccf q, size_t c) try {
 
 int yagi_hip_eqrls_cccf_set_bw(yagi_hip_eqrls_cccf q, float lambda) try {
     CHECK_Q(q);
-    return EqrlsObj::set_bw(lambda, &q->lambda);
+    return EqrlsHost::set_bw(lambda, &q->lambda);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_get_bw(yagi_hip_eqrls_cccf q, float *lambda) try {
-    CHECK_Q(q);
-    CHECK_PTR(lambda);
-    *lambda = q->lambda;
-    return YAGI_OK;
+    return bank_get(q, lambda, [](auto &o) { return o.lambda; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_get_length(yagi_hip_eqrls_cccf q, size_t *p) try {
-    CHECK_Q(q);
-    CHECK_PTR(p);
-    *p = q->p;
-    return YAGI_OK;
+    return bank_get(q, p, [](auto &o) { return o.p; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_get_channels(yagi_hip_eqrls_cccf q, size_t *channels) try {
-    CHECK_Q(q);
-    CHECK_PTR(channels);
-    *channels = q->C;
-    return YAGI_OK;
+    return bank_get(q, channels, [](auto &o) { return o.C; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_get_coefficients(yagi_hip_eqrls_cccf q, cf32 *w0) try {
     CHECK_Q(q);
     CHECK_PTR(w0);
     YG_TRY(q->ensure_host());
-    for (size_t c = 0; c < q->C; ++c)
-        for (size_t i = 0; i < q->p; ++i) w0[c * q->p + i] = q->hw0[i * q->C + c];
+    q->gather(q->hw0, q->p, w0);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 
@@ -7709,34 +7547,26 @@ int yagi_hip_eqrls_cccf_get_matrix(yagi_hip_eqrls_cccf q, cf32 *P0) try {
     CHECK_Q(q);
     CHECK_PTR(P0);
     YG_TRY(q->ensure_host());
-    const size_t pp = q->p * q->p;
-    for (size_t c = 0; c < q->C; ++c)
-        for (size_t e = 0; e < pp; ++e) P0[c * pp + e] = q->hP[e * q->C + c];
+    q->gather(q->hP, q->p * q->p, P0);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_set_constellation(yagi_hip_eqrls_cccf q, const cf32 *table, size_t M) try {
     CHECK_Q(q);
-    YG_TRY(EqlmsObj::check_table(table, M));
-    YG_HIP(hipStreamSynchronize(q->st));                     // a launch in flight may still read the table
-    q->table.assign(table, table + M);
-    return fill(q->table_dev, q->table.data(), M * sizeof(cf32), q->st);
+    return q->set_constellation(table, M);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_set_lanes(yagi_hip_eqrls_cccf q, size_t L) try {
     CHECK_Q(q);
     if (L != 0) {
-        YG_TRY(EqrlsObj::check_lanes(q->p, L));
+        YG_TRY(EqrlsHost::check_lanes(q->p, L));
     }
     q->lanes = L;
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_get_lanes(yagi_hip_eqrls_cccf q, size_t *L) try {
-    CHECK_Q(q);
-    CHECK_PTR(L);
-    *L = q->lanes ? q->lanes : eqrls_plan(q->C, q->p);
-    return YAGI_OK;
+    return bank_get(q, L, [](auto &o) { return o.lanes ? o.lanes : eqrls_plan(o.C, o.p); });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_eqrls_cccf_step_block(yagi_hip_eqrls_cccf q, size_t k, int mode, const cf32 *x, size_t x_pitch, size_t n,
@@ -7749,7 +7579,7 @@ int yagi_hip_eqrls_cccf_step_block_dev(yagi_hip_eqrls_cccf q, size_t k, int mode
                                        const cf32 *d_dev, size_t d_pitch, cf32 *y_dev, size_t y_pitch) try {
     CHECK_Q(q);
     size_t rows = 0;
-    YG_TRY(EqrlsObj::check_block(q->C, mode, k, x_pitch, n, d_dev != nullptr, d_pitch, q->table.size(), y_pitch, &rows));
+    YG_TRY(EqrlsHost::check_block(q->C, mode, k, x_pitch, n, d_dev != nullptr, d_pitch, q->table.size(), y_pitch, &rows));
     if (n != 0) {
         CHECK_PTR(x_dev);
         CHECK_PTR(y_dev);
@@ -7784,28 +7614,23 @@ int yagi_hip_eqrls_cccf_train_dev(yagi_hip_eqrls_cccf q, const cf32 *w, const cf
 int yagi_hip_eqrls_cccf_execute_host(size_t channels, const cf32 *h, size_t p, float lambda, int mode, size_t k, const cf32 *x,
                                      size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, const cf32 *table, size_t M,
                                      cf32 *y, size_t y_pitch, cf32 *w0, cf32 *w1, cf32 *P0) try {
-    EqrlsObj o;
+    EqrlsHost o;
     YG_TRY(o.configure(channels, h, p));
-    YG_TRY(EqrlsObj::set_bw(lambda, &o.lambda));
+    YG_TRY(EqrlsHost::set_bw(lambda, &o.lambda));
     if (mode == YAGI_EQRLS_DECISION) {
-        YG_TRY(EqlmsObj::check_table(table, M));
+        YG_TRY(eq_check_table(table, M));
     }
     size_t rows = 0;
-    YG_TRY(EqrlsObj::check_block(channels, mode, k, x_pitch, n, d != nullptr, d_pitch, M, y_pitch, &rows));
+    YG_TRY(EqrlsHost::check_block(channels, mode, k, x_pitch, n, d != nullptr, d_pitch, M, y_pitch, &rows));
     if (n != 0) {
         CHECK_PTR(x);
         CHECK_PTR(y);
     }
     eqrls_host(mode, p, o.lambda, o.hP.data(), o.hw0.data(), o.hw1.data(), o.hh.data(), channels, k, x, x_pitch, n, d, d_pitch,
                table, M, y, y_pitch);
-    for (size_t c = 0; c < channels; ++c) {
-        for (size_t i = 0; i < p; ++i) {
-            if (w0) w0[c * p + i] = o.hw0[i * channels + c];
-            if (w1) w1[c * p + i] = o.hw1[i * channels + c];
-        }
-        if (P0)
-            for (size_t e = 0; e < p * p; ++e) P0[c * p * p + e] = o.hP[e * channels + c];
-    }
+    if (w0) o.gather(o.hw0, p, w0);
+    if (w1) o.gather(o.hw1, p, w1);
+    if (P0) o.gather(o.hP, p * p, P0);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 
@@ -7817,21 +7642,18 @@ int yagi_hip_eqrls_cccf_execute_host(size_t channels, const cf32 *h, size_t p, f
 // alpha, scale, threshold and timeout travel to the kernel by value with every call.
 namespace yagi {
 
-template <class T>
-struct AgcObj {
-    hipStream_t st = nullptr;
+// everything that needs no device
+struct AgcHost {
     size_t C = 0;
     AgcSettings g;
-    DevBuf state_dev, sum_dev, stat_dev;
     std::vector<AgcChan> hs;                              // host mirror
-    Mirror mirror;
-    Staging ws;                                           // host block forms: x and a compact y (stat_dev: the status)
 
     static void reset_chan(AgcChan &s) {                  // reset (:60-69)
         s.g = 1.0f, s.y2p = 1.0f, s.locked = 0;
         s.mode = s.mode == YAGI_AGC_SQUELCH_DISABLED ? YAGI_AGC_SQUELCH_DISABLED : YAGI_AGC_SQUELCH_ENABLED;
     }
-    // new (:37-58); everything that needs no device
+    void reset_chan(size_t c) { reset_chan(hs[c]); }
+    // new (:37-58)
     int configure(size_t channels) {
         if (channels == 0 || channels > (size_t)YAGI_AGC_CHANNELS_MAX)
             return fail(YAGI_ERR_CONFIG, "agc: %zu channels are outside 1 .. YAGI_AGC_CHANNELS_MAX", channels);
@@ -7841,26 +7663,6 @@ struct AgcObj {
         s.mode = YAGI_AGC_SQUELCH_DISABLED;
         reset_chan(s);
         hs.assign(C, s);
-        return YAGI_OK;
-    }
-    int alloc() {
-        YG_TRY(require_device());
-        YG_TRY(state_dev.alloc(C * sizeof(AgcChan)));
-        YG_TRY(sum_dev.alloc(C * sizeof(float)));
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    int ensure_host() {
-        return mirror.need_host([&] { return download(hs.data(), state_dev.p, C * sizeof(AgcChan), st); });
-    }
-    int ensure_dev() {
-        return mirror.need_dev([&] { return upload(state_dev.p, hs.data(), C * sizeof(AgcChan), st); });
-    }
-    template <class F>
-    int edit(F &&f) {                                       // f(AgcChan &, channel) on the host mirror
-        YG_TRY(ensure_host());
-        for (size_t c = 0; c < C; ++c) f(hs[c], c);
-        mirror.host_written();
         return YAGI_OK;
     }
     static int check_bandwidth(float bt) {
@@ -7880,6 +7682,7 @@ struct AgcObj {
         if (x_pitch < C) return fail(YAGI_ERR_CONFIG, "agc: the pitches are in elements, at least the channel count");
         return YAGI_OK;
     }
+    template <class T>
     static int check_block(size_t C, const T *x, size_t x_pitch, size_t n, const T *y, size_t y_pitch, const uint8_t *status,
                            size_t status_pitch) {
         YG_TRY(check_rows(C, x_pitch, n));
@@ -7896,43 +7699,63 @@ struct AgcObj {
         if (xa < ye && ya < xe) return fail(YAGI_ERR_CONFIG, "agc: x and y overlap and are not the same block");
         return YAGI_OK;
     }
-    int block_dev(const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch, uint8_t *status, size_t status_pitch) {
-        if (n == 0) return YAGI_OK;
-        YG_TRY(ensure_dev());
-        YG_TRY(launch_agc<T>(g, state_dev.as<AgcChan>(), C, x, x_pitch, n, y, y_pitch, status, status_pitch, st));
-        mirror.dev_written();
-        return YAGI_OK;
-    }
-    int block_host(const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch, uint8_t *status, size_t status_pitch) {
-        YG_TRY(check_block(C, x, x_pitch, n, y, y_pitch, status, status_pitch));
-        if (n == 0) return YAGI_OK;
-        YG_TRY(ws.put(st, x, (n - 1) * x_pitch + C));
-        YG_TRY(ws.y.ensure(n * C * sizeof(T)));
-        if (status) {
-            YG_TRY(stat_dev.ensure(n * C));
-        }
-        YG_TRY(block_dev(ws.x.template as<T>(), x_pitch, n, ws.y.template as<T>(), C, status ? stat_dev.as<uint8_t>() : nullptr, C));
-        std::vector<T> t(n * C);
-        YG_TRY(download(t.data(), ws.y.p, n * C * sizeof(T), st));
-        for (size_t j = 0; j < n; ++j) std::copy(t.begin() + j * C, t.begin() + (j + 1) * C, y + j * y_pitch);
-        if (status) {
-            std::vector<uint8_t> sb(n * C);
-            YG_TRY(download(sb.data(), stat_dev.p, n * C, st));
-            for (size_t j = 0; j < n; ++j) std::copy(sb.begin() + j * C, sb.begin() + (j + 1) * C, status + j * status_pitch);
-        }
-        return YAGI_OK;
-    }
+    template <class T>
     static int check_init(size_t C, const T *x, size_t x_pitch, size_t n) {
         if (n == 0) return fail(YAGI_ERR_CONFIG, "number of samples must be greater than zero");
         YG_TRY(check_rows(C, x_pitch, n));
         if (!x) return fail(YAGI_ERR_CONFIG, "null pointer argument");
         return YAGI_OK;
     }
+};
+
+template <class T>
+struct AgcObj : AgcHost, BankObj<AgcObj<T>> {
+    using Host = AgcHost;
+    static constexpr const char *kFamily = "agc";
+    DevBuf state_dev, sum_dev, stat_dev;                  // stat_dev: the status plane of the host block form
+
+    int alloc() {
+        YG_TRY(require_device());
+        YG_TRY(state_dev.alloc(C * sizeof(AgcChan)));
+        YG_TRY(sum_dev.alloc(C * sizeof(float)));
+        this->mirror.host_written();
+        return YAGI_OK;
+    }
+    template <class F>
+    int each_array(F &&f) {
+        return f(state_dev, hs.data(), C * sizeof(AgcChan));
+    }
+    template <class F>
+    int each_chan(F &&f) {                                  // f(AgcChan &, channel) on the host mirror
+        return this->edit([&] {
+            for (size_t c = 0; c < C; ++c) f(hs[c], c);
+        });
+    }
+    int block_dev(const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch, uint8_t *status, size_t status_pitch) {
+        if (n == 0) return YAGI_OK;
+        YG_TRY(this->ensure_dev());
+        YG_TRY(launch_agc<T>(g, state_dev.as<AgcChan>(), C, x, x_pitch, n, y, y_pitch, status, status_pitch, this->st));
+        this->mirror.dev_written();
+        return YAGI_OK;
+    }
+    int block_host(const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch, uint8_t *status, size_t status_pitch) {
+        Staging &ws = this->ws;
+        YG_TRY(check_block(C, x, x_pitch, n, y, y_pitch, status, status_pitch));
+        if (n == 0) return YAGI_OK;
+        YG_TRY(ws.put(this->st, x, (n - 1) * x_pitch + C));
+        YG_TRY(ws.y.ensure(n * C * sizeof(T)));
+        if (status) {
+            YG_TRY(stat_dev.ensure(n * C));
+        }
+        YG_TRY(block_dev(ws.x.as<T>(), x_pitch, n, ws.y.as<T>(), C, status ? stat_dev.as<uint8_t>() : nullptr, C));
+        YG_TRY(download_rows(this->st, ws.y, n, C, y, y_pitch));
+        return status ? download_rows(this->st, stat_dev, n, C, status, status_pitch) : YAGI_OK;
+    }
     int init_dev(const T *x, size_t x_pitch, size_t n) {    // init (:171-178)
-        YG_TRY(launch_agc_init<T>(x, x_pitch, n, C, sum_dev.as<float>(), st));
+        YG_TRY(launch_agc_init<T>(x, x_pitch, n, C, sum_dev.as<float>(), this->st));
         std::vector<float> sum(C);
-        YG_TRY(download(sum.data(), sum_dev.p, C * sizeof(float), st));
-        return edit([&](AgcChan &s, size_t c) { s.g = agc_level_gain(sum[c], n), s.y2p = 1.0f; });
+        YG_TRY(download(sum.data(), sum_dev.p, C * sizeof(float), this->st));
+        return each_chan([&](AgcChan &s, size_t c) { s.g = agc_level_gain(sum[c], n), s.y2p = 1.0f; });
     }
 };
 
@@ -7942,53 +7765,32 @@ struct AgcObj {
     struct yagi_hip_agc_##K##_s : AgcObj<T> {};                                                     \
     extern "C" {                                                                                    \
     int yagi_hip_agc_##K##_create(size_t channels, yagi_hip_agc_##K *q) try {                       \
-        CHECK_PTR(q);                                                                               \
-        *q = nullptr;                                                                               \
-        auto o = std::make_unique<yagi_hip_agc_##K##_s>();                                          \
-        YG_TRY(o->configure(channels));                                                             \
-        YG_TRY(o->alloc());                                                                         \
-        *q = o.release();                                                                           \
-        return YAGI_OK;                                                                             \
+        return bank_create(q, channels);                                                            \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_destroy(yagi_hip_agc_##K q) try {                                        \
-        if (q) (void)hipStreamSynchronize(q->st);                                                   \
-        delete q;                                                                                   \
-        return YAGI_OK;                                                                             \
+        return bank_destroy(q);                                                                     \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_clone(yagi_hip_agc_##K q, yagi_hip_agc_##K *out) try {                   \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(out);                                                                             \
-        *out = nullptr;                                                                             \
-        YG_TRY(q->ensure_host());                                                                   \
-        auto o = std::make_unique<yagi_hip_agc_##K##_s>();                                          \
-        o->st = q->st, o->C = q->C, o->g = q->g, o->hs = q->hs;                                     \
-        YG_TRY(o->alloc());                                                                         \
-        *out = o.release();                                                                         \
-        return YAGI_OK;                                                                             \
+        return bank_clone(q, out);                                                                  \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_set_stream(yagi_hip_agc_##K q, yagi_stream_t s) try {                    \
-        CHECK_Q(q);                                                                                 \
-        if (q->st == to_stream(s)) return YAGI_OK;                                                  \
-        YG_HIP(hipStreamSynchronize(q->st));                                                        \
-        q->st = to_stream(s);                                                                       \
-        return YAGI_OK;                                                                             \
+        return bank_set_stream(q, s);                                                               \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_reset(yagi_hip_agc_##K q) try {                                          \
         CHECK_Q(q);                                                                                 \
-        return q->edit([](AgcChan &s, size_t) { AgcObj<T>::reset_chan(s); });                       \
+        return q->reset();                                                                          \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_reset_channel(yagi_hip_agc_##K q, size_t c) try {                        \
         CHECK_Q(q);                                                                                 \
-        if (c >= q->C) return fail(YAGI_ERR_CONFIG, "agc: channel %zu of %zu", c, q->C);            \
-        return q->edit([c](AgcChan &s, size_t i) { if (i == c) AgcObj<T>::reset_chan(s); });        \
+        return q->reset_channel(c);                                                                 \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_lock(yagi_hip_agc_##K q) try {                                           \
         CHECK_Q(q);                                                                                 \
-        return q->edit([](AgcChan &s, size_t) { s.locked = 1; });                                   \
+        return q->each_chan([](AgcChan &s, size_t) { s.locked = 1; });                              \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_unlock(yagi_hip_agc_##K q) try {                                         \
         CHECK_Q(q);                                                                                 \
-        return q->edit([](AgcChan &s, size_t) { s.locked = 0; });                                   \
+        return q->each_chan([](AgcChan &s, size_t) { s.locked = 0; });                              \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_is_locked(yagi_hip_agc_##K q, int *locked) try {                         \
         CHECK_Q(q);                                                                                 \
@@ -8001,103 +7803,75 @@ struct AgcObj {
     int yagi_hip_agc_##K##_set_locked(yagi_hip_agc_##K q, const uint8_t *locked) try {              \
         CHECK_Q(q);                                                                                 \
         CHECK_PTR(locked);                                                                          \
-        return q->edit([locked](AgcChan &s, size_t c) { s.locked = locked[c] ? 1 : 0; });           \
+        return q->each_chan([locked](AgcChan &s, size_t c) { s.locked = locked[c] ? 1 : 0; });      \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_get_locked(yagi_hip_agc_##K q, uint8_t *locked) try {                    \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(locked);                                                                          \
-        YG_TRY(q->ensure_host());                                                                   \
-        for (size_t c = 0; c < q->C; ++c) locked[c] = q->hs[c].locked;                              \
-        return YAGI_OK;                                                                             \
+        return bank_get_each(q, locked, [](auto &o, size_t c) { return o.hs[c].locked; });          \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_set_bandwidth(yagi_hip_agc_##K q, float bt) try {                        \
         CHECK_Q(q);                                                                                 \
-        YG_TRY(AgcObj<T>::check_bandwidth(bt));                                                     \
+        YG_TRY(AgcHost::check_bandwidth(bt));                                                       \
         q->g.alpha = bt;                                                                            \
         return YAGI_OK;                                                                             \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_get_bandwidth(yagi_hip_agc_##K q, float *bt) try {                       \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(bt);                                                                              \
-        *bt = q->g.alpha;                                                                           \
-        return YAGI_OK;                                                                             \
+        return bank_get(q, bt, [](auto &o) { return o.g.alpha; });                                  \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_set_scale(yagi_hip_agc_##K q, float scale) try {                         \
         CHECK_Q(q);                                                                                 \
-        YG_TRY(AgcObj<T>::check_positive(scale, "scale"));                                          \
+        YG_TRY(AgcHost::check_positive(scale, "scale"));                                            \
         q->g.scale = scale;                                                                         \
         return YAGI_OK;                                                                             \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_get_scale(yagi_hip_agc_##K q, float *scale) try {                        \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(scale);                                                                           \
-        *scale = q->g.scale;                                                                        \
-        return YAGI_OK;                                                                             \
+        return bank_get(q, scale, [](auto &o) { return o.g.scale; });                               \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_set_gain(yagi_hip_agc_##K q, float gain) try {                           \
         CHECK_Q(q);                                                                                 \
-        YG_TRY(AgcObj<T>::check_positive(gain, "gain"));                                            \
-        return q->edit([gain](AgcChan &s, size_t) { s.g = gain; });                                 \
+        YG_TRY(AgcHost::check_positive(gain, "gain"));                                              \
+        return q->each_chan([gain](AgcChan &s, size_t) { s.g = gain; });                            \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_set_signal_level(yagi_hip_agc_##K q, float x2) try {                     \
         CHECK_Q(q);                                                                                 \
-        YG_TRY(AgcObj<T>::check_positive(x2, "signal level"));                                      \
+        YG_TRY(AgcHost::check_positive(x2, "signal level"));                                        \
         const float gain = 1.0f / x2;                                                               \
-        return q->edit([gain](AgcChan &s, size_t) { s.g = gain, s.y2p = 1.0f; });                   \
+        return q->each_chan([gain](AgcChan &s, size_t) { s.g = gain, s.y2p = 1.0f; });              \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_set_rssi(yagi_hip_agc_##K q, float rssi) try {                           \
         CHECK_Q(q);                                                                                 \
         const float gain = agc_rssi_gain(rssi);                                                     \
-        return q->edit([gain](AgcChan &s, size_t) { s.g = gain, s.y2p = 1.0f; });                   \
+        return q->each_chan([gain](AgcChan &s, size_t) { s.g = gain, s.y2p = 1.0f; });              \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_set_gains(yagi_hip_agc_##K q, const float *gain) try {                   \
         CHECK_Q(q);                                                                                 \
         CHECK_PTR(gain);                                                                            \
-        for (size_t c = 0; c < q->C; ++c) YG_TRY(AgcObj<T>::check_positive(gain[c], "gain"));       \
-        return q->edit([gain](AgcChan &s, size_t c) { s.g = gain[c]; });                            \
+        for (size_t c = 0; c < q->C; ++c) YG_TRY(AgcHost::check_positive(gain[c], "gain"));         \
+        return q->each_chan([gain](AgcChan &s, size_t c) { s.g = gain[c]; });                       \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_get_gain(yagi_hip_agc_##K q, float *gain) try {                          \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(gain);                                                                            \
-        YG_TRY(q->ensure_host());                                                                   \
-        for (size_t c = 0; c < q->C; ++c) gain[c] = q->hs[c].g;                                     \
-        return YAGI_OK;                                                                             \
+        return bank_get_each(q, gain, [](auto &o, size_t c) { return o.hs[c].g; });                 \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_get_signal_level(yagi_hip_agc_##K q, float *level) try {                 \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(level);                                                                           \
-        YG_TRY(q->ensure_host());                                                                   \
-        for (size_t c = 0; c < q->C; ++c) level[c] = 1.0f / q->hs[c].g;                             \
-        return YAGI_OK;                                                                             \
+        return bank_get_each(q, level, [](auto &o, size_t c) { return 1.0f / o.hs[c].g; });         \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_get_rssi(yagi_hip_agc_##K q, float *rssi) try {                          \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(rssi);                                                                            \
-        YG_TRY(q->ensure_host());                                                                   \
-        for (size_t c = 0; c < q->C; ++c) rssi[c] = agc_rssi(q->hs[c].g);                           \
-        return YAGI_OK;                                                                             \
+        return bank_get_each(q, rssi, [](auto &o, size_t c) { return agc_rssi(o.hs[c].g); });       \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_get_channels(yagi_hip_agc_##K q, size_t *channels) try {                 \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(channels);                                                                        \
-        *channels = q->C;                                                                           \
-        return YAGI_OK;                                                                             \
+        return bank_get(q, channels, [](auto &o) { return o.C; });                                  \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_squelch_enable(yagi_hip_agc_##K q) try {                                 \
         CHECK_Q(q);                                                                                 \
         q->g.squelch = true;                                                                        \
-        return q->edit([](AgcChan &s, size_t) { s.mode = YAGI_AGC_SQUELCH_ENABLED; });              \
+        return q->each_chan([](AgcChan &s, size_t) { s.mode = YAGI_AGC_SQUELCH_ENABLED; });         \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_squelch_disable(yagi_hip_agc_##K q) try {                                \
         CHECK_Q(q);                                                                                 \
         q->g.squelch = false;                                                                       \
-        return q->edit([](AgcChan &s, size_t) { s.mode = YAGI_AGC_SQUELCH_DISABLED; });             \
+        return q->each_chan([](AgcChan &s, size_t) { s.mode = YAGI_AGC_SQUELCH_DISABLED; });        \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_squelch_is_enabled(yagi_hip_agc_##K q, int *enabled) try {               \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(enabled);                                                                         \
-        *enabled = q->g.squelch ? 1 : 0;                                                            \
-        return YAGI_OK;                                                                             \
+        return bank_get(q, enabled, [](auto &o) { return o.g.squelch ? 1 : 0; });                   \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_squelch_set_threshold(yagi_hip_agc_##K q, float threshold) try {         \
         CHECK_Q(q);                                                                                 \
@@ -8105,39 +7879,29 @@ struct AgcObj {
         return YAGI_OK;                                                                             \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_squelch_get_threshold(yagi_hip_agc_##K q, float *threshold) try {        \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(threshold);                                                                       \
-        *threshold = q->g.threshold;                                                                \
-        return YAGI_OK;                                                                             \
+        return bank_get(q, threshold, [](auto &o) { return o.g.threshold; });                       \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_squelch_set_timeout(yagi_hip_agc_##K q, uint64_t timeout) try {          \
         CHECK_Q(q);                                                                                 \
-        YG_TRY(AgcObj<T>::check_timeout(timeout));                                                  \
+        YG_TRY(AgcHost::check_timeout(timeout));                                                    \
         q->g.timeout = (unsigned)timeout;                                                           \
         return YAGI_OK;                                                                             \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_squelch_get_timeout(yagi_hip_agc_##K q, uint64_t *timeout) try {         \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(timeout);                                                                         \
-        *timeout = q->g.timeout;                                                                    \
-        return YAGI_OK;                                                                             \
+        return bank_get(q, timeout, [](auto &o) { return o.g.timeout; });                           \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_squelch_get_status(yagi_hip_agc_##K q, uint8_t *mode) try {              \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(mode);                                                                            \
-        YG_TRY(q->ensure_host());                                                                   \
-        for (size_t c = 0; c < q->C; ++c) mode[c] = q->hs[c].mode;                                  \
-        return YAGI_OK;                                                                             \
+        return bank_get_each(q, mode, [](auto &o, size_t c) { return o.hs[c].mode; });              \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_init(yagi_hip_agc_##K q, const T *x, size_t x_pitch, size_t n) try {     \
         CHECK_Q(q);                                                                                 \
-        YG_TRY(AgcObj<T>::check_init(q->C, x, x_pitch, n));                                         \
+        YG_TRY(AgcHost::check_init(q->C, x, x_pitch, n));                                           \
         YG_TRY(q->ws.put(q->st, x, (n - 1) * x_pitch + q->C));                                      \
         return q->init_dev(q->ws.x.as<T>(), x_pitch, n);                                            \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_init_dev(yagi_hip_agc_##K q, const T *x_dev, size_t x_pitch, size_t n) try { \
         CHECK_Q(q);                                                                                 \
-        YG_TRY(AgcObj<T>::check_init(q->C, x_dev, x_pitch, n));                                     \
+        YG_TRY(AgcHost::check_init(q->C, x_dev, x_pitch, n));                                       \
         return q->init_dev(x_dev, x_pitch, n);                                                      \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_execute_block(yagi_hip_agc_##K q, const T *x, size_t x_pitch, size_t n, T *y, size_t y_pitch, \
@@ -8148,20 +7912,20 @@ struct AgcObj {
     int yagi_hip_agc_##K##_execute_block_dev(yagi_hip_agc_##K q, const T *x_dev, size_t x_pitch, size_t n, T *y_dev, \
                                              size_t y_pitch, uint8_t *status_dev, size_t status_pitch) try { \
         CHECK_Q(q);                                                                                 \
-        YG_TRY(AgcObj<T>::check_block(q->C, x_dev, x_pitch, n, y_dev, y_pitch, status_dev, status_pitch)); \
+        YG_TRY(AgcHost::check_block<T>(q->C, x_dev, x_pitch, n, y_dev, y_pitch, status_dev, status_pitch)); \
         return q->block_dev(x_dev, x_pitch, n, y_dev, y_pitch, status_dev, status_pitch);           \
     } catch (...) { return ::yagi::api_exception(); }                                               \
     int yagi_hip_agc_##K##_execute_host(size_t channels, float bandwidth, float scale, float g0, int locked, int squelch, \
                                         float threshold, uint64_t timeout, const T *x, size_t x_pitch, size_t n, T *y, \
                                         size_t y_pitch, uint8_t *status, size_t status_pitch, float *g_out, \
                                         uint8_t *mode_out) try {                                    \
-        AgcObj<T> o;                                                                                \
+        AgcHost o;                                                                                  \
         YG_TRY(o.configure(channels));                                                              \
-        YG_TRY(AgcObj<T>::check_bandwidth(bandwidth));                                              \
-        YG_TRY(AgcObj<T>::check_positive(scale, "scale"));                                          \
-        YG_TRY(AgcObj<T>::check_positive(g0, "gain"));                                              \
-        YG_TRY(AgcObj<T>::check_timeout(timeout));                                                  \
-        YG_TRY(AgcObj<T>::check_block(channels, x, x_pitch, n, y, y_pitch, status, status_pitch));  \
+        YG_TRY(AgcHost::check_bandwidth(bandwidth));                                                \
+        YG_TRY(AgcHost::check_positive(scale, "scale"));                                            \
+        YG_TRY(AgcHost::check_positive(g0, "gain"));                                                \
+        YG_TRY(AgcHost::check_timeout(timeout));                                                    \
+        YG_TRY(AgcHost::check_block<T>(channels, x, x_pitch, n, y, y_pitch, status, status_pitch)); \
         o.g.alpha = bandwidth, o.g.scale = scale, o.g.threshold = threshold, o.g.timeout = (unsigned)timeout; \
         o.g.squelch = squelch != 0;                                                                 \
         for (AgcChan &s : o.hs) {                                                                   \
@@ -8214,17 +7978,17 @@ int yagi_hip_log10f(const float *x, size_t n, float *y) try {
 
 // ---- SymTrack (src/framing/symtrack.rs is empty: the composition of yagi_hip.h) ------------------------------------------
 // The state is the parts' own records and arrays plus one SymtrackChan per channel; symtrack_kernels.hip updates all of
-// them in place on the device.  The host side of the parts (their configure(), reset and mirrors) is reused as it is;
-// their device buffers are never allocated.  Setters that touch per-channel state, the getters and clone work on the
+// them in place on the device.  The parts are the host structs of SymSync, EqLms and Agc (their configure(), reset and
+// mirrors) as they are; the device half is SymTrack's own.  Setters that touch per-channel state, the getters and clone work on the
 // host mirror; the two copies are synchronised lazily (Mirror).  The loop settings travel to the kernel by value.
 namespace yagi {
 
-struct SymtrackObj {
-    hipStream_t st = nullptr;
+// everything that needs no device; the parts are their host structs
+struct SymtrackHost {
     size_t C = 0, k = 0;
-    SymsyncObj sy;                                        // host parts only: taps, p, hs, hh
-    EqlmsObj eq;                                          // h0, mu, hw, hh, hs
-    AgcObj<cf32> ag;                                      // g, hs
+    SymsyncHost sy;
+    EqlmsHost eq;
+    AgcHost ag;
     ModemParams P{};
     std::vector<cf32> map;
     std::vector<uint8_t> nbr;
@@ -8233,11 +7997,8 @@ struct SymtrackObj {
     float pll_alpha = 0.0f, pll_beta = 0.0f, bw = 0.0f;
     uint64_t holdoff = 200;
     std::vector<SymtrackChan> hst;
-    DevBuf taps_dev, osc_dev, map_dev, agc_dev, ss_dev, eq_dev, st_dev, sshist_dev, eqw_dev, eqhist_dev, wstatus, wsym;
-    Mirror mirror;
-    Staging ws;                                           // host block form: x as given; y compact [ycap][C]
 
-    // everything that needs no device; table = nullptr takes `scheme`
+    // table = nullptr takes `scheme`
     int configure(size_t channels, int ftype, size_t k_, size_t m, float beta, int scheme, const cf32 *table, size_t M,
                   int osc_scheme, size_t npfb, size_t eq_len) {
         if (channels == 0 || channels > (size_t)YAGI_SYMTRACK_CHANNELS_MAX)
@@ -8258,9 +8019,7 @@ struct SymtrackObj {
         std::vector<float> h;
         YG_TRY(symsync_rnyquist_taps(ftype, k_, m, beta, npfb, h));
         YG_TRY(sy.configure(channels, k_, npfb, h.data(), h.size()));
-        sy.k_out = 2;
-        sy.p.k_out = 2;
-        for (auto &s : sy.hs) symsync_reset_chan(&s, k_, 2);
+        YG_TRY(sy.start_at_rate(2));
         std::vector<cf32> hc;
         YG_TRY(eqlms_lowpass_taps(eq_len, 0.45f, hc));
         YG_TRY(eq.configure(channels, hc.data(), hc.size()));
@@ -8279,10 +8038,10 @@ struct SymtrackObj {
     }
     int set_bandwidths(float a, float s, float e, float pl) {
         SymsyncLoop t = sy.p;
-        YG_TRY(AgcObj<cf32>::check_bandwidth(a));
+        YG_TRY(AgcHost::check_bandwidth(a));
         YG_TRY(symsync_set_bw(s, &t));
         float mu = 0.0f;
-        YG_TRY(EqlmsObj::set_bw(e, &mu));
+        YG_TRY(EqlmsHost::set_bw(e, &mu));
         if (!(e >= 0.0f)) return fail(YAGI_ERR_CONFIG, "learning rate cannot be less than zero");
         if (!(pl >= 0.0f)) return fail(YAGI_ERR_CONFIG, "Bandwidth must be positive");
         ag.g.alpha = a;
@@ -8299,6 +8058,11 @@ struct SymtrackObj {
         bw = bw_;
         return YAGI_OK;
     }
+    static int check_strategy(int strategy) {
+        if (strategy < YAGI_SYMTRACK_EQ_OFF || strategy > YAGI_SYMTRACK_EQ_DD)
+            return fail(YAGI_ERR_CONFIG, "symtrack: unknown equalizer strategy %d", strategy);
+        return YAGI_OK;
+    }
     SymtrackLoop loop() const {
         SymtrackLoop p{};
         p.ss = sy.p;
@@ -8312,6 +8076,27 @@ struct SymtrackObj {
     SymtrackState host_state() {
         return SymtrackState{ag.hs.data(), sy.hs.data(), eq.hs.data(), hst.data(), sy.hh.data(), eq.hw.data(), eq.hh.data()};
     }
+    void reset_chan(size_t c) {
+        ag.reset_chan(c);
+        sy.reset_chan(c);
+        eq.reset_chan(c);
+        hst[c] = SymtrackChan{};
+    }
+    static int check_block(size_t C, size_t x_pitch, size_t n, size_t y_pitch, bool have_sym, size_t sym_pitch, size_t ycap) {
+        if (n >= ((size_t)1 << 31) || ycap >= ((size_t)1 << 31))
+            return fail(YAGI_ERR_CONFIG, "symtrack: n and ycap must be below 2^31");
+        if (x_pitch < C || y_pitch < C || x_pitch >= ((size_t)1 << 31) || y_pitch >= ((size_t)1 << 31) ||
+            (have_sym && (sym_pitch < C || sym_pitch >= ((size_t)1 << 31))))
+            return fail(YAGI_ERR_CONFIG, "symtrack: the pitches are in elements, at least the channel count and below 2^31");
+        return YAGI_OK;
+    }
+};
+
+struct SymtrackObj : SymtrackHost, BankObj<SymtrackObj> {
+    using Host = SymtrackHost;
+    static constexpr const char *kFamily = "symtrack";
+    DevBuf taps_dev, osc_dev, map_dev, agc_dev, ss_dev, eq_dev, st_dev, sshist_dev, eqw_dev, eqhist_dev, wstatus, wsym;
+
     SymtrackState dev_state() {
         return SymtrackState{agc_dev.as<AgcChan>(),  ss_dev.as<SymsyncChan>(), eq_dev.as<EqlmsChan>(), st_dev.as<SymtrackChan>(),
                              sshist_dev.as<cf32>(), eqw_dev.as<cf32>(),       eqhist_dev.as<cf32>()};
@@ -8336,7 +8121,7 @@ struct SymtrackObj {
         return YAGI_OK;
     }
     template <class F>
-    int each_array(F &&f) {                                 // f(device buffer, host pointer, bytes)
+    int each_array(F &&f) {
         YG_TRY(f(agc_dev, ag.hs.data(), C * sizeof(AgcChan)));
         YG_TRY(f(ss_dev, sy.hs.data(), C * sizeof(SymsyncChan)));
         YG_TRY(f(eq_dev, eq.hs.data(), C * sizeof(EqlmsChan)));
@@ -8345,31 +8130,6 @@ struct SymtrackObj {
         YG_TRY(f(eqw_dev, eq.hw.data(), eq.h_len * C * sizeof(cf32)));
         return f(eqhist_dev, eq.hh.data(), eq.h_len * C * sizeof(cf32));
     }
-    int ensure_host() {
-        return mirror.need_host([&] { return each_array([&](DevBuf &d, void *h, size_t b) { return download(h, d.p, b, st); }); });
-    }
-    int ensure_dev() {
-        return mirror.need_dev([&] { return each_array([&](DevBuf &d, void *h, size_t b) { return upload(d.p, h, b, st); }); });
-    }
-    void reset_chan(size_t c) {
-        AgcObj<cf32>::reset_chan(ag.hs[c]);
-        symsync_reset_chan(&sy.hs[c], k, 2);
-        eq.reset_chan(c);
-        hst[c] = SymtrackChan{};
-    }
-    int reset_channel(size_t c) {
-        if (c >= C) return fail(YAGI_ERR_CONFIG, "symtrack: channel %zu of %zu", c, C);
-        YG_TRY(ensure_host());
-        reset_chan(c);
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    int reset() {
-        YG_TRY(ensure_host());
-        for (size_t c = 0; c < C; ++c) reset_chan(c);
-        mirror.host_written();
-        return YAGI_OK;
-    }
     // the words of set_frequency / set_phase for channels [c0, c0 + count): nothing changes where one of them fails
     int set_nco(size_t c0, size_t count, const float *frequency, const float *phase) {
         std::vector<uint32_t> w(2 * count);
@@ -8377,18 +8137,9 @@ struct SymtrackObj {
             YG_TRY(osc_constrain(frequency[i], &w[2 * i]));
             YG_TRY(osc_constrain(phase[i], &w[2 * i + 1]));
         }
-        YG_TRY(ensure_host());
-        for (size_t i = 0; i < count; ++i) hst[c0 + i].d_theta = w[2 * i], hst[c0 + i].theta = w[2 * i + 1];
-        mirror.host_written();
-        return YAGI_OK;
-    }
-    static int check_block(size_t C, size_t x_pitch, size_t n, size_t y_pitch, bool have_sym, size_t sym_pitch, size_t ycap) {
-        if (n >= ((size_t)1 << 31) || ycap >= ((size_t)1 << 31))
-            return fail(YAGI_ERR_CONFIG, "symtrack: n and ycap must be below 2^31");
-        if (x_pitch < C || y_pitch < C || x_pitch >= ((size_t)1 << 31) || y_pitch >= ((size_t)1 << 31) ||
-            (have_sym && (sym_pitch < C || sym_pitch >= ((size_t)1 << 31))))
-            return fail(YAGI_ERR_CONFIG, "symtrack: the pitches are in elements, at least the channel count and below 2^31");
-        return YAGI_OK;
+        return edit([&] {
+            for (size_t i = 0; i < count; ++i) hst[c0 + i].d_theta = w[2 * i], hst[c0 + i].theta = w[2 * i + 1];
+        });
     }
     int block_dev(const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch, uint8_t *sym, size_t sym_pitch,
                   size_t ycap, unsigned *status) {
@@ -8404,35 +8155,11 @@ struct SymtrackObj {
 
 struct yagi_hip_symtrack_cccf_s : SymtrackObj {};
 
-namespace {
-
-int symtrack_make(yagi_hip_symtrack_cccf *q, size_t channels, int ftype, size_t k, size_t m, float beta, int scheme,
-                  const cf32 *table, size_t M, int osc_scheme, size_t npfb, size_t eq_len) {
-    *q = nullptr;
-    auto o = std::make_unique<yagi_hip_symtrack_cccf_s>();
-    YG_TRY(o->configure(channels, ftype, k, m, beta, scheme, table, M, osc_scheme, npfb, eq_len));
-    YG_TRY(o->alloc());
-    *q = o.release();
-    return YAGI_OK;
-}
-
-}  // namespace
-
-#define SYMTRACK_GET(name, T, expr)                                                                 \
-    int yagi_hip_symtrack_cccf_##name(yagi_hip_symtrack_cccf q, T *out) try {                       \
-        CHECK_Q(q);                                                                                 \
-        CHECK_PTR(out);                                                                             \
-        YG_TRY(q->ensure_host());                                                                   \
-        for (size_t c = 0; c < q->C; ++c) out[c] = (expr);                                          \
-        return YAGI_OK;                                                                             \
-    } catch (...) { return ::yagi::api_exception(); }
-
 extern "C" {
 
 int yagi_hip_symtrack_cccf_create(size_t channels, int ftype, size_t k, size_t m, float beta, int scheme, int osc_scheme,
                                   size_t npfb, size_t eq_len, yagi_hip_symtrack_cccf *q) try {
-    CHECK_PTR(q);
-    return symtrack_make(q, channels, ftype, k, m, beta, scheme, nullptr, 0, osc_scheme, npfb, eq_len);
+    return bank_create(q, channels, ftype, k, m, beta, scheme, (const cf32 *)nullptr, (size_t)0, osc_scheme, npfb, eq_len);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_create_from_table(size_t channels, int ftype, size_t k, size_t m, float beta, const cf32 *table,
@@ -8441,43 +8168,19 @@ int yagi_hip_symtrack_cccf_create_from_table(size_t channels, int ftype, size_t 
     CHECK_PTR(q);
     *q = nullptr;
     CHECK_PTR(table);
-    return symtrack_make(q, channels, ftype, k, m, beta, YAGI_MODEM_ARB, table, M, osc_scheme, npfb, eq_len);
+    return bank_create(q, channels, ftype, k, m, beta, (int)YAGI_MODEM_ARB, table, M, osc_scheme, npfb, eq_len);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_destroy(yagi_hip_symtrack_cccf q) try {
-    if (q) (void)hipStreamSynchronize(q->st);
-    delete q;
-    return YAGI_OK;
+    return bank_destroy(q);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_clone(yagi_hip_symtrack_cccf q, yagi_hip_symtrack_cccf *out) try {
-    CHECK_Q(q);
-    CHECK_PTR(out);
-    *out = nullptr;
-    YG_TRY(q->ensure_host());
-    auto o = std::make_unique<yagi_hip_symtrack_cccf_s>();
-    o->st = q->st;
-    o->C = q->C, o->k = q->k;
-    o->sy.C = q->sy.C, o->sy.k = q->sy.k, o->sy.npfb = q->sy.npfb, o->sy.Ls = q->sy.Ls, o->sy.k_out = q->sy.k_out;
-    o->sy.p = q->sy.p, o->sy.taps = q->sy.taps, o->sy.hs = q->sy.hs, o->sy.hh = q->sy.hh;
-    o->eq.C = q->eq.C, o->eq.h_len = q->eq.h_len, o->eq.mu = q->eq.mu;
-    o->eq.h0 = q->eq.h0, o->eq.hw = q->eq.hw, o->eq.hh = q->eq.hh, o->eq.hs = q->eq.hs;
-    o->ag.C = q->ag.C, o->ag.g = q->ag.g, o->ag.hs = q->ag.hs;
-    o->P = q->P, o->map = q->map, o->nbr = q->nbr;
-    o->vco = q->vco, o->strategy = q->strategy, o->osc = q->osc;
-    o->pll_alpha = q->pll_alpha, o->pll_beta = q->pll_beta, o->bw = q->bw, o->holdoff = q->holdoff;
-    o->hst = q->hst;
-    YG_TRY(o->alloc());
-    *out = o.release();
-    return YAGI_OK;
+    return bank_clone(q, out);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_set_stream(yagi_hip_symtrack_cccf q, yagi_stream_t s) try {
-    CHECK_Q(q);
-    if (q->st == to_stream(s)) return YAGI_OK;
-    YG_HIP(hipStreamSynchronize(q->st));
-    q->st = to_stream(s);
-    return YAGI_OK;
+    return bank_set_stream(q, s);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_reset(yagi_hip_symtrack_cccf q) try {
@@ -8496,10 +8199,7 @@ int yagi_hip_symtrack_cccf_set_bandwidth(yagi_hip_symtrack_cccf q, float bw) try
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_get_bandwidth(yagi_hip_symtrack_cccf q, float *bw) try {
-    CHECK_Q(q);
-    CHECK_PTR(bw);
-    *bw = q->bw;
-    return YAGI_OK;
+    return bank_get(q, bw, [](auto &o) { return o.bw; });
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_set_bandwidths(yagi_hip_symtrack_cccf q, float agc, float sync, float eq, float pll) try {
@@ -8509,8 +8209,7 @@ int yagi_hip_symtrack_cccf_set_bandwidths(yagi_hip_symtrack_cccf q, float agc, f
 
 int yagi_hip_symtrack_cccf_set_eq_strategy(yagi_hip_symtrack_cccf q, int strategy) try {
     CHECK_Q(q);
-    if (strategy < YAGI_SYMTRACK_EQ_OFF || strategy > YAGI_SYMTRACK_EQ_DD)
-        return fail(YAGI_ERR_CONFIG, "symtrack: unknown equalizer strategy %d", strategy);
+    YG_TRY(SymtrackHost::check_strategy(strategy));
     q->strategy = strategy;
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
@@ -8535,19 +8234,36 @@ int yagi_hip_symtrack_cccf_set_nco_all(yagi_hip_symtrack_cccf q, const float *fr
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_get_channels(yagi_hip_symtrack_cccf q, size_t *channels) try {
-    CHECK_Q(q);
-    CHECK_PTR(channels);
-    *channels = q->C;
-    return YAGI_OK;
+    return bank_get(q, channels, [](auto &o) { return o.C; });
 } catch (...) { return ::yagi::api_exception(); }
 
-SYMTRACK_GET(get_tau, float, q->sy.hs[c].tau_decim)
-SYMTRACK_GET(get_gain, float, q->ag.hs[c].g)
-SYMTRACK_GET(get_rssi, float, agc_rssi(q->ag.hs[c].g))
-SYMTRACK_GET(get_nco_frequency, float, osc_frequency(q->hst[c].d_theta))
-SYMTRACK_GET(get_nco_phase, float, osc_phase(q->hst[c].theta))
-SYMTRACK_GET(get_num_syms, uint64_t, (uint64_t)q->hst[c].num_syms)
-SYMTRACK_GET(get_stalled, uint32_t, q->hst[c].stall)
+int yagi_hip_symtrack_cccf_get_tau(yagi_hip_symtrack_cccf q, float *tau) try {
+    return bank_get_each(q, tau, [](auto &o, size_t c) { return o.sy.hs[c].tau_decim; });
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_get_gain(yagi_hip_symtrack_cccf q, float *gain) try {
+    return bank_get_each(q, gain, [](auto &o, size_t c) { return o.ag.hs[c].g; });
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_get_rssi(yagi_hip_symtrack_cccf q, float *rssi) try {
+    return bank_get_each(q, rssi, [](auto &o, size_t c) { return agc_rssi(o.ag.hs[c].g); });
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_get_nco_frequency(yagi_hip_symtrack_cccf q, float *frequency) try {
+    return bank_get_each(q, frequency, [](auto &o, size_t c) { return osc_frequency(o.hst[c].d_theta); });
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_get_nco_phase(yagi_hip_symtrack_cccf q, float *phase) try {
+    return bank_get_each(q, phase, [](auto &o, size_t c) { return osc_phase(o.hst[c].theta); });
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_get_num_syms(yagi_hip_symtrack_cccf q, uint64_t *num_syms) try {
+    return bank_get_each(q, num_syms, [](auto &o, size_t c) { return (uint64_t)o.hst[c].num_syms; });
+} catch (...) { return ::yagi::api_exception(); }
+
+int yagi_hip_symtrack_cccf_get_stalled(yagi_hip_symtrack_cccf q, uint32_t *stalled) try {
+    return bank_get_each(q, stalled, [](auto &o, size_t c) { return o.hst[c].stall; });
+} catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_get_nco_state(yagi_hip_symtrack_cccf q, uint32_t *theta, uint32_t *d_theta) try {
     CHECK_Q(q);
@@ -8562,12 +8278,7 @@ int yagi_hip_symtrack_cccf_get_weights(yagi_hip_symtrack_cccf q, cf32 *w) try {
     CHECK_Q(q);
     CHECK_PTR(w);
     YG_TRY(q->ensure_host());
-    const size_t L = q->eq.h_len;
-    for (size_t c = 0; c < q->C; ++c)
-        for (size_t i = 0; i < L; ++i) {
-            const cf32 v = q->eq.hw[(L - 1 - i) * q->C + c];
-            w[c * L + i] = cf32{v.re, -v.im};
-        }
+    q->eq.weights(w);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 
@@ -8576,7 +8287,7 @@ int yagi_hip_symtrack_cccf_execute_dev(yagi_hip_symtrack_cccf q, const cf32 *x_d
                                        uint32_t *status_dev) try {
     CHECK_Q(q);
     CHECK_PTR(status_dev);
-    YG_TRY(SymtrackObj::check_block(q->C, x_pitch, n, y_pitch, sym_dev != nullptr, sym_pitch, ycap));
+    YG_TRY(SymtrackHost::check_block(q->C, x_pitch, n, y_pitch, sym_dev != nullptr, sym_pitch, ycap));
     if (n != 0) CHECK_PTR(x_dev);
     if (ycap != 0) CHECK_PTR(y_dev);
     return q->block_dev(x_dev, x_pitch, n, y_dev, y_pitch, sym_dev, sym_pitch, ycap, status_dev);
@@ -8588,7 +8299,7 @@ int yagi_hip_symtrack_cccf_execute(yagi_hip_symtrack_cccf q, const cf32 *x, size
     CHECK_PTR(ny);
     CHECK_PTR(stalled);
     const size_t C = q->C;
-    YG_TRY(SymtrackObj::check_block(C, x_pitch, n, y_pitch, sym != nullptr, sym_pitch, ycap));
+    YG_TRY(SymtrackHost::check_block(C, x_pitch, n, y_pitch, sym != nullptr, sym_pitch, ycap));
     if (n != 0) CHECK_PTR(x);
     if (ycap != 0) CHECK_PTR(y);
     const size_t nx = n ? (n - 1) * x_pitch + C : 0;
@@ -8597,25 +8308,7 @@ int yagi_hip_symtrack_cccf_execute(yagi_hip_symtrack_cccf q, const cf32 *x, size
     if (sym) YG_TRY(q->wsym.ensure(ycap * C));
     YG_TRY(q->block_dev(q->ws.x.as<cf32>(), x_pitch, n, q->ws.y.as<cf32>(), C, sym ? q->wsym.as<uint8_t>() : nullptr, C, ycap,
                         q->wstatus.as<unsigned>()));
-    std::vector<unsigned> status(3 * C);
-    YG_TRY(download(status.data(), q->wstatus.p, 3 * C * sizeof(unsigned), q->st));
-    size_t rows = 0;
-    for (size_t c = 0; c < C; ++c) {
-        ny[c] = status[c];
-        stalled[c] = status[C + c];
-        rows = std::max(rows, (size_t)status[c]);
-    }
-    std::vector<cf32> t(rows * C);
-    YG_TRY(download(t.data(), q->ws.y.p, rows * C * sizeof(cf32), q->st));
-    std::vector<uint8_t> tb(sym ? rows * C : 0);
-    if (sym) YG_TRY(download(tb.data(), q->wsym.p, rows * C, q->st));
-    for (size_t j = 0; j < rows; ++j)
-        for (size_t c = 0; c < C; ++c)
-            if (j < ny[c]) {
-                y[j * y_pitch + c] = t[j * C + c];
-                if (sym) sym[j * sym_pitch + c] = tb[j * C + c];
-            }
-    return YAGI_OK;
+    return q->fetch_ragged(q->wstatus, 3 * C, ny, stalled, y, y_pitch, &q->wsym, sym, sym_pitch);
 } catch (...) { return ::yagi::api_exception(); }
 
 int yagi_hip_symtrack_cccf_execute_host(size_t channels, int ftype, size_t k, size_t m, float beta, int scheme,
@@ -8625,17 +8318,16 @@ int yagi_hip_symtrack_cccf_execute_host(size_t channels, int ftype, size_t k, si
                                         size_t sym_pitch, size_t ycap, uint32_t *ny, uint32_t *stalled) try {
     CHECK_PTR(ny);
     CHECK_PTR(stalled);
-    SymtrackObj o;
+    SymtrackHost o;
     YG_TRY(o.configure(channels, ftype, k, m, beta, scheme, table, M, osc_scheme, npfb, eq_len));
     YG_TRY(o.set_bandwidth(bw));
-    if (strategy < YAGI_SYMTRACK_EQ_OFF || strategy > YAGI_SYMTRACK_EQ_DD)
-        return fail(YAGI_ERR_CONFIG, "symtrack: unknown equalizer strategy %d", strategy);
+    YG_TRY(SymtrackHost::check_strategy(strategy));
     o.strategy = strategy, o.holdoff = holdoff;
     for (size_t c = 0; c < channels; ++c) {
         if (nco_frequency) YG_TRY(osc_constrain(nco_frequency[c], &o.hst[c].d_theta));
         if (nco_phase) YG_TRY(osc_constrain(nco_phase[c], &o.hst[c].theta));
     }
-    YG_TRY(SymtrackObj::check_block(channels, x_pitch, n, y_pitch, sym != nullptr, sym_pitch, ycap));
+    YG_TRY(SymtrackHost::check_block(channels, x_pitch, n, y_pitch, sym != nullptr, sym_pitch, ycap));
     if (n != 0) CHECK_PTR(x);
     if (ycap != 0) CHECK_PTR(y);
     std::vector<unsigned> status(3 * channels);
@@ -8654,8 +8346,8 @@ int yagi_hip_symtrack_cccf_execute_host(size_t channels, int ftype, size_t k, si
 // the device's; reset, reset_channel and clone reach it through a host mirror (Mirror).
 namespace yagi {
 
-struct ChannelObj {
-    hipStream_t st = nullptr;
+// everything that needs no device
+struct ChannelHost {
     size_t C = 0, L = 0;
     int vco = 0;
     uint64_t seed = 0, adv = 0;
@@ -8663,11 +8355,6 @@ struct ChannelObj {
     std::vector<ChannelLink> link;                          // as of adv = 0
     std::vector<uint32_t> phi;                              // the phase word last set: where reset puts theta
     std::vector<cf32> hrev, hwin;                           // [L][C] taps, reversed; [L - 1][C] window mirror
-    DevBuf tab, link_dev, taps_dev;
-    PingPong<> win;
-    bool link_dirty = true, taps_dirty = true;
-    Mirror mirror;
-    Staging ws;
 
     static int check_create(size_t channels, size_t taps, int scheme) {
         if (channels == 0 || channels > (size_t)YAGI_CHANNEL_CHANNELS_MAX)
@@ -8687,6 +8374,54 @@ struct ChannelObj {
         hwin.assign((L - 1) * C, cf32{0.0f, 0.0f});
         return YAGI_OK;
     }
+    void fold() {                                           // bring the words of every link to the present: adv = 0
+        if (adv != 0)
+            for (ChannelLink &k : link) {
+                k.theta += (uint32_t)adv * k.d_theta;
+                k.t += adv;
+            }
+        adv = 0;
+    }
+    int check_link(size_t c) const {
+        if (c >= C) return fail(YAGI_ERR_CONFIG, "channel: link %zu of %zu", c, C);
+        return YAGI_OK;
+    }
+    void reset_link(size_t c) {
+        link[c].theta = phi[c];
+        link[c].t = 0;
+        for (size_t j = 0; j + 1 < L; ++j) hwin[j * C + c] = cf32{0.0f, 0.0f};
+    }
+    ChannelShape shape(size_t n) const { return forced.cw ? forced : channel_plan(C, L, n); }
+    static int check_block(size_t C, bool bcast, const cf32 *x, size_t x_pitch, size_t n, const cf32 *y, size_t y_pitch) {
+        if (n >= ((size_t)1 << 31)) return fail(YAGI_ERR_CONFIG, "channel: n must be below 2^31");
+        if ((!bcast && x_pitch < C) || y_pitch < C)
+            return fail(YAGI_ERR_CONFIG, "channel: the pitches are in elements, at least the channel count");
+        if (n == 0) return YAGI_OK;
+        if (!x || !y) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        const size_t nx = bcast ? n : (n - 1) * x_pitch + C, ny = (n - 1) * y_pitch + C;
+        return check_noalias(x, nx * sizeof(cf32), y, ny * sizeof(cf32));
+    }
+    void put_taps(size_t c, const cf32 *h) {               // hrev_c[j] = h_c[L - 1 - j]
+        for (size_t j = 0; j < L; ++j) hrev[j * C + c] = h[L - 1 - j];
+    }
+    static void fill_shape(ChannelShape s, size_t taps, int vco, bool bcast, yagi_hip_channel_shape *out) {
+        out->links = s.cw, out->rows = s.rows;
+        out->tile_steps = channel_tile_steps(s);
+        out->lds_bytes = channel_lds_bytes(s, taps, vco, bcast);
+    }
+};
+
+// Not a BankObj: the links and taps go up by dirty flag, not through the mirror, the window is a ping-pong pair, and a
+// full reset rewrites both copies of it without a download.
+struct ChannelObj : ChannelHost {
+    using Host = ChannelHost;
+    hipStream_t st = nullptr;
+    DevBuf tab, link_dev, taps_dev;
+    PingPong<> win;
+    bool link_dirty = true, taps_dirty = true;
+    Mirror mirror;
+    Staging ws;
+
     int alloc() {
         YG_TRY(require_device());
         std::vector<float> h;
@@ -8709,23 +8444,13 @@ struct ChannelObj {
         link_dirty = taps_dirty = false;
         return mirror.need_dev([&] { return upload(win.cur(), hwin.data(), hwin.size() * sizeof(cf32), st); });
     }
-    void fold() {                                           // bring the words of every link to the present: adv = 0
-        if (adv != 0)
-            for (ChannelLink &k : link) {
-                k.theta += (uint32_t)adv * k.d_theta;
-                k.t += adv;
-            }
-        adv = 0;
+    void fold() {                                           // whoever folds goes on to change a link
+        Host::fold();
         link_dirty = true;
     }
-    int check_link(size_t c) const {
-        if (c >= C) return fail(YAGI_ERR_CONFIG, "channel: link %zu of %zu", c, C);
-        return YAGI_OK;
-    }
-    void reset_link(size_t c) {
-        link[c].theta = phi[c];
-        link[c].t = 0;
-        for (size_t j = 0; j + 1 < L; ++j) hwin[j * C + c] = cf32{0.0f, 0.0f};
+    void put_taps(size_t c, const cf32 *h) {
+        Host::put_taps(c, h);
+        taps_dirty = true;
     }
     int reset(size_t first, size_t count) {
         if (count == C) {                                   // both copies of the window are rewritten: no download
@@ -8737,16 +8462,6 @@ struct ChannelObj {
         for (size_t c = first; c < first + count; ++c) reset_link(c);
         mirror.host_written();
         return YAGI_OK;
-    }
-    ChannelShape shape(size_t n) const { return forced.cw ? forced : channel_plan(C, L, n); }
-    static int check_block(size_t C, bool bcast, const cf32 *x, size_t x_pitch, size_t n, const cf32 *y, size_t y_pitch) {
-        if (n >= ((size_t)1 << 31)) return fail(YAGI_ERR_CONFIG, "channel: n must be below 2^31");
-        if ((!bcast && x_pitch < C) || y_pitch < C)
-            return fail(YAGI_ERR_CONFIG, "channel: the pitches are in elements, at least the channel count");
-        if (n == 0) return YAGI_OK;
-        if (!x || !y) return fail(YAGI_ERR_CONFIG, "null pointer argument");
-        const size_t nx = bcast ? n : (n - 1) * x_pitch + C, ny = (n - 1) * y_pitch + C;
-        return check_noalias(x, nx * sizeof(cf32), y, ny * sizeof(cf32));
     }
     int block_dev(bool bcast, const cf32 *x, size_t x_pitch, size_t n, cf32 *y, size_t y_pitch) {
         if (n == 0) return YAGI_OK;
@@ -8767,19 +8482,7 @@ struct ChannelObj {
         YG_TRY(ws.put(st, x, bcast ? n : (n - 1) * x_pitch + C));
         YG_TRY(ws.y.ensure(n * C * sizeof(cf32)));
         YG_TRY(block_dev(bcast, ws.x.as<cf32>(), x_pitch, n, ws.y.as<cf32>(), C));
-        std::vector<cf32> t(n * C);
-        YG_TRY(download(t.data(), ws.y.p, n * C * sizeof(cf32), st));
-        for (size_t j = 0; j < n; ++j) std::copy(t.begin() + j * C, t.begin() + (j + 1) * C, y + j * y_pitch);
-        return YAGI_OK;
-    }
-    void put_taps(size_t c, const cf32 *h) {               // hrev_c[j] = h_c[L - 1 - j]
-        for (size_t j = 0; j < L; ++j) hrev[j * C + c] = h[L - 1 - j];
-        taps_dirty = true;
-    }
-    static void fill_shape(ChannelShape s, size_t taps, int vco, bool bcast, yagi_hip_channel_shape *out) {
-        out->links = s.cw, out->rows = s.rows;
-        out->tile_steps = channel_tile_steps(s);
-        out->lds_bytes = channel_lds_bytes(s, taps, vco, bcast);
+        return download_rows(st, ws.y, n, C, y, y_pitch);
     }
 };
 
@@ -8791,43 +8494,22 @@ extern "C" {
 
 int yagi_hip_channel_plan(size_t channels, size_t L, size_t n, int osc_scheme, int bcast, yagi_hip_channel_shape *plan) try {
     CHECK_PTR(plan);
-    YG_TRY(ChannelObj::check_create(channels, L, osc_scheme));
+    YG_TRY(ChannelHost::check_create(channels, L, osc_scheme));
     if (n >= ((size_t)1 << 31)) return fail(YAGI_ERR_CONFIG, "channel: n must be below 2^31");
-    ChannelObj::fill_shape(channel_plan(channels, L, n), L, osc_scheme == YAGI_OSC_VCO, bcast != 0, plan);
+    ChannelHost::fill_shape(channel_plan(channels, L, n), L, osc_scheme == YAGI_OSC_VCO, bcast != 0, plan);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_create(size_t channels, size_t L, int osc_scheme, yagi_hip_channel_cccf *q) try {
-    CHECK_PTR(q);
-    *q = nullptr;
-    auto o = std::make_unique<yagi_hip_channel_cccf_s>();
-    YG_TRY(o->configure(channels, L, osc_scheme));
-    YG_TRY(o->alloc());
-    *q = o.release();
-    return YAGI_OK;
+    return bank_create(q, channels, L, osc_scheme);
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_destroy(yagi_hip_channel_cccf q) try {
-    if (q) (void)hipStreamSynchronize(q->st);
-    delete q;
-    return YAGI_OK;
+    return bank_destroy(q);
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_clone(yagi_hip_channel_cccf q, yagi_hip_channel_cccf *out) try {
-    CHECK_Q(q);
-    CHECK_PTR(out);
-    *out = nullptr;
-    YG_TRY(q->ensure_host());
-    auto o = std::make_unique<yagi_hip_channel_cccf_s>();
-    o->st = q->st, o->C = q->C, o->L = q->L, o->vco = q->vco, o->seed = q->seed, o->adv = q->adv, o->forced = q->forced;
-    o->link = q->link, o->phi = q->phi, o->hrev = q->hrev, o->hwin = q->hwin;
-    YG_TRY(o->alloc());
-    *out = o.release();
-    return YAGI_OK;
+    return bank_clone(q, out);
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_set_stream(yagi_hip_channel_cccf q, yagi_stream_t s) try {
-    CHECK_Q(q);
-    if (q->st == to_stream(s)) return YAGI_OK;
-    YG_HIP(hipStreamSynchronize(q->st));
-    q->st = to_stream(s);
-    return YAGI_OK;
+    return bank_set_stream(q, s);
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_reset(yagi_hip_channel_cccf q) try {
     CHECK_Q(q);
@@ -8917,10 +8599,7 @@ int yagi_hip_channel_cccf_set_seed(yagi_hip_channel_cccf q, uint64_t seed) try {
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_get_seed(yagi_hip_channel_cccf q, uint64_t *seed) try {
-    CHECK_Q(q);
-    CHECK_PTR(seed);
-    *seed = q->seed;
-    return YAGI_OK;
+    return bank_get(q, seed, [](auto &o) { return o.seed; });
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_set_position(yagi_hip_channel_cccf q, size_t c, uint64_t t) try {
     CHECK_Q(q);
@@ -8959,16 +8638,10 @@ int yagi_hip_channel_cccf_get_osc_state(yagi_hip_channel_cccf q, uint32_t *theta
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_get_channels(yagi_hip_channel_cccf q, size_t *channels) try {
-    CHECK_Q(q);
-    CHECK_PTR(channels);
-    *channels = q->C;
-    return YAGI_OK;
+    return bank_get(q, channels, [](auto &o) { return o.C; });
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_get_taps(yagi_hip_channel_cccf q, size_t *L) try {
-    CHECK_Q(q);
-    CHECK_PTR(L);
-    *L = q->L;
-    return YAGI_OK;
+    return bank_get(q, L, [](auto &o) { return o.L; });
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_set_shape(yagi_hip_channel_cccf q, unsigned links, unsigned rows) try {
     CHECK_Q(q);
@@ -8984,7 +8657,7 @@ int yagi_hip_channel_cccf_set_shape(yagi_hip_channel_cccf q, unsigned links, uns
 int yagi_hip_channel_cccf_get_shape(yagi_hip_channel_cccf q, size_t n, int bcast, yagi_hip_channel_shape *shape) try {
     CHECK_Q(q);
     CHECK_PTR(shape);
-    ChannelObj::fill_shape(q->shape(n), q->L, q->vco, bcast != 0, shape);
+    ChannelHost::fill_shape(q->shape(n), q->L, q->vco, bcast != 0, shape);
     return YAGI_OK;
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_execute(yagi_hip_channel_cccf q, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
@@ -8995,7 +8668,7 @@ int yagi_hip_channel_cccf_execute(yagi_hip_channel_cccf q, const yagi_cf32 *x, s
 int yagi_hip_channel_cccf_execute_dev(yagi_hip_channel_cccf q, const yagi_cf32 *x_dev, size_t x_pitch, size_t n,
                                       yagi_cf32 *y_dev, size_t y_pitch) try {
     CHECK_Q(q);
-    YG_TRY(ChannelObj::check_block(q->C, false, x_dev, x_pitch, n, y_dev, y_pitch));
+    YG_TRY(ChannelHost::check_block(q->C, false, x_dev, x_pitch, n, y_dev, y_pitch));
     return q->block_dev(false, x_dev, x_pitch, n, y_dev, y_pitch);
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_execute_bcast(yagi_hip_channel_cccf q, const yagi_cf32 *x, size_t n, yagi_cf32 *y,
@@ -9006,14 +8679,14 @@ int yagi_hip_channel_cccf_execute_bcast(yagi_hip_channel_cccf q, const yagi_cf32
 int yagi_hip_channel_cccf_execute_bcast_dev(yagi_hip_channel_cccf q, const yagi_cf32 *x_dev, size_t n, yagi_cf32 *y_dev,
                                             size_t y_pitch) try {
     CHECK_Q(q);
-    YG_TRY(ChannelObj::check_block(q->C, true, x_dev, 0, n, y_dev, y_pitch));
+    YG_TRY(ChannelHost::check_block(q->C, true, x_dev, 0, n, y_dev, y_pitch));
     return q->block_dev(true, x_dev, 0, n, y_dev, y_pitch);
 } catch (...) { return ::yagi::api_exception(); }
 int yagi_hip_channel_cccf_execute_host(size_t channels, size_t L, int osc_scheme, int bcast, uint64_t seed, const yagi_cf32 *h,
                                        const float *gamma, const float *nstd, const uint32_t *theta, const uint32_t *d_theta,
                                        const uint64_t *t, const yagi_cf32 *x, size_t x_pitch, size_t n, yagi_cf32 *y,
                                        size_t y_pitch) try {
-    ChannelObj o;
+    ChannelHost o;
     YG_TRY(o.configure(channels, L, osc_scheme));
     CHECK_PTR(h);
     CHECK_PTR(gamma);
@@ -9021,7 +8694,7 @@ int yagi_hip_channel_cccf_execute_host(size_t channels, size_t L, int osc_scheme
     CHECK_PTR(theta);
     CHECK_PTR(d_theta);
     CHECK_PTR(t);
-    YG_TRY(ChannelObj::check_block(channels, bcast != 0, x, x_pitch, n, y, y_pitch));
+    YG_TRY(ChannelHost::check_block(channels, bcast != 0, x, x_pitch, n, y, y_pitch));
     for (size_t c = 0; c < channels; ++c) {
         o.put_taps(c, h + c * L);
         o.link[c] = ChannelLink{gamma[c], nstd[c], theta[c], d_theta[c], t[c]};

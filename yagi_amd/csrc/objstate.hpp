@@ -90,6 +90,135 @@ public:
     }
 };
 
+// rows x C elements, compact on the device, to the caller's rows of pitch y_pitch
+template <class T>
+int download_rows(hipStream_t st, const DevBuf &src, size_t rows, size_t C, T *y, size_t y_pitch) {
+    std::vector<T> t(rows * C);
+    YG_TRY(download(t.data(), src.p, rows * C * sizeof(T), st));
+    for (size_t j = 0; j < rows; ++j) std::copy(t.begin() + j * C, t.begin() + (j + 1) * C, y + j * y_pitch);
+    return YAGI_OK;
+}
+
+// What the objects that hold a bank of independent channels share.  Such an object D is two halves: a plain copyable
+// host struct D::Host (configuration, the host mirror of the per-channel state, everything that needs no device: C,
+// reset_chan(c)), from which it derives, and this device half.  D supplies kFamily (the name its messages start with),
+// alloc() and each_array(f), its one list of mirrored arrays: f(DevBuf &, void *host, size_t bytes) for each.
+template <class D>
+struct BankObj {
+    hipStream_t st = nullptr;
+    Mirror mirror;
+    Staging ws;                                           // host block forms: x as given, y compact [rows][C]
+
+    D &self() { return *static_cast<D *>(this); }
+    int ensure_host() {
+        return mirror.need_host(
+            [&] { return self().each_array([&](DevBuf &d, void *h, size_t b) { return download(h, d.p, b, st); }); });
+    }
+    int ensure_dev() {
+        return mirror.need_dev(
+            [&] { return self().each_array([&](DevBuf &d, void *h, size_t b) { return upload(d.p, h, b, st); }); });
+    }
+    template <class F>
+    int edit(F &&f) {                                       // f() changes the host mirror
+        YG_TRY(ensure_host());
+        f();
+        mirror.host_written();
+        return YAGI_OK;
+    }
+    int reset() {
+        return edit([&] {
+            for (size_t c = 0; c < self().C; ++c) self().reset_chan(c);
+        });
+    }
+    int reset_channel(size_t c) {
+        if (c >= self().C) return fail(YAGI_ERR_CONFIG, "%s: channel %zu of %zu", D::kFamily, c, self().C);
+        return edit([&] { self().reset_chan(c); });
+    }
+    // The tail of a host call whose channels write different numbers of rows: `status` holds ny[C], stalled[C] (and
+    // more, `words` in all); row j of ws.y, and of the byte plane symsrc where sym is given, goes out for j < ny[c].
+    int fetch_ragged(const DevBuf &status, size_t words, uint32_t *ny, uint32_t *stalled, cf32 *y, size_t y_pitch,
+                     const DevBuf *symsrc = nullptr, uint8_t *sym = nullptr, size_t sym_pitch = 0) {
+        const size_t C = self().C;
+        std::vector<unsigned> s(words);
+        YG_TRY(download(s.data(), status.p, words * sizeof(unsigned), st));
+        size_t rows = 0;
+        for (size_t c = 0; c < C; ++c) {
+            ny[c] = s[c];
+            stalled[c] = s[C + c];
+            rows = std::max(rows, (size_t)s[c]);
+        }
+        std::vector<cf32> t(rows * C);
+        YG_TRY(download(t.data(), ws.y.p, rows * C * sizeof(cf32), st));
+        std::vector<uint8_t> tb(sym ? rows * C : 0);
+        if (sym) YG_TRY(download(tb.data(), symsrc->p, rows * C, st));
+        for (size_t j = 0; j < rows; ++j)
+            for (size_t c = 0; c < C; ++c)
+                if (j < ny[c]) {
+                    y[j * y_pitch + c] = t[j * C + c];
+                    if (sym) sym[j * sym_pitch + c] = tb[j * C + c];
+                }
+        return YAGI_OK;
+    }
+};
+
+// The bodies of the entry points every bank object has.  S is the handle's struct: it has st, configure(args...),
+// alloc(), ensure_host() and names its host struct S::Host.
+template <class S, class... A>
+int bank_create(S **q, A... args) {
+    if (!q) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    *q = nullptr;
+    auto o = std::make_unique<S>();
+    YG_TRY(o->configure(args...));
+    YG_TRY(o->alloc());
+    *q = o.release();
+    return YAGI_OK;
+}
+template <class S>
+int bank_destroy(S *q) {
+    if (q) (void)hipStreamSynchronize(q->st);
+    delete q;
+    return YAGI_OK;
+}
+// on the source's stream: the host struct whole, then fresh device buffers and staging
+template <class S>
+int bank_clone(S *q, S **out) {
+    if (!q) return fail(YAGI_ERR_CONFIG, "null handle");
+    if (!out) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    *out = nullptr;
+    YG_TRY(q->ensure_host());
+    auto o = std::make_unique<S>();
+    static_cast<typename S::Host &>(*o) = static_cast<const typename S::Host &>(*q);
+    o->st = q->st;
+    YG_TRY(o->alloc());
+    *out = o.release();
+    return YAGI_OK;
+}
+template <class S>
+int bank_set_stream(S *q, yagi_stream_t s) {
+    if (!q) return fail(YAGI_ERR_CONFIG, "null handle");
+    if (q->st == to_stream(s)) return YAGI_OK;
+    YG_HIP(hipStreamSynchronize(q->st));
+    q->st = to_stream(s);
+    return YAGI_OK;
+}
+// *out = f(object): a setting
+template <class S, class T, class F>
+int bank_get(S *q, T *out, F &&f) {
+    if (!q) return fail(YAGI_ERR_CONFIG, "null handle");
+    if (!out) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    *out = f(*q);
+    return YAGI_OK;
+}
+// out[c] = f(object, c) for every channel, on the host mirror
+template <class S, class T, class F>
+int bank_get_each(S *q, T *out, F &&f) {
+    if (!q) return fail(YAGI_ERR_CONFIG, "null handle");
+    if (!out) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    YG_TRY(q->ensure_host());
+    for (size_t c = 0; c < q->C; ++c) out[c] = f(*q, c);
+    return YAGI_OK;
+}
+
 }  // namespace yagi
 
 #pragma GCC visibility pop
