@@ -2315,6 +2315,93 @@ int yagi_hip_channel_radius(const uint32_t *k1, size_t n, float *r);
 int yagi_hip_channel_noise(uint64_t seed, uint64_t link, uint64_t first, size_t n, yagi_cf32 *out);
 int yagi_hip_channel_constrain(float phi, uint32_t *word);      /* Osc's constrain(): the word of a phase or frequency */
 
+/* ---- ConvCode: convolutional encoder and Viterbi decoder for a bank of frames ------------------------------------------
+ * The reference's src/fec/mod.rs is an empty module, so the object is defined here.  ConvCode(K, g[R], P[R][p],
+ * terminated) holds a code; every call works on F frames, one per row: frame f starts at byte f * pitch.  No call
+ * carries state from one call to the next.
+ * ConvCode: the definition.  3 <= K <= 9, S = 2^(K-1) states; 2 <= R <= 4 generator words, 0 < g[r] < 2^K.
+ *   encoder     sr = 0; per input bit b: sr = ((sr << 1) | b) & (2^K - 1); output bit r = parity(sr & g[r]), r = 0 .. R-1.
+ *               Message bits come most significant bit first from packed bytes; `terminated` appends K - 1 zero bits:
+ *               T = n + K - 1 trellis steps, else T = n.
+ *   puncturing  optional R x p matrix of 0 / 1 (row r = generator r, p <= 32), given row major; bit (step t, output r) is
+ *               kept iff P[r][t mod p] == 1; every column keeps at least one bit; kept bits follow in (t, r) order.
+ *               ncoded(n) = (T / p) kp + (kept bits of the columns below T mod p), kp the kept bits of a period.
+ *   coded       one byte per kept bit: the encoder writes 0 or 1; the decoder reads soft bytes s = 0 .. 255, 255 a
+ *               confident 1 (Modem's soft bits).
+ *   decoder     path metrics are u32, the smallest wins; pm[0] = 0, pm[s] = 2^30 otherwise.  At step t the new state ns has
+ *               input bit b = ns & 1 and the predecessors p0 = ns >> 1, p1 = p0 | 2^(K-2).  The branch cost from p is the
+ *               sum over the kept outputs r of (e ? 255 - s : s), e = parity(((p << 1) | b) & g[r]), s that position's
+ *               soft byte; punctured positions add nothing.  m0 = pm[p0] + c0, m1 = pm[p1] + c1; d[t][ns] = (m1 < m0)
+ *               (a tie keeps p0); pm'[ns] = d ? m1 : m0.  The end state is 0 where terminated, else the state of the
+ *               smallest metric, the lowest index on a tie.  Traceback from the end state e for t = T-1 .. 0: bit t =
+ *               e & 1; e = (e >> 1) | (d[t][e] << (K-2)).  The first n bits are the message, packed most significant
+ *               bit first into ceil(n / 8) bytes, pad bits zero.  metric = the end state's pm.  T <= 65536 and a step
+ *               adds at most 1020, so no sum reaches 2^31 and nothing is renormalised.
+ * Catastrophic codes are not detected.
+ *   create(K, g, R, puncture, p, terminated)   puncture may be NULL (then p is ignored); anything outside the limits
+ *                             above is YAGI_ERR_CONFIG, decided before any device is asked for
+ *   destroy / clone / set_stream
+ *   get_K / get_R / get_rate(kept, p) (kp kept bits per p steps; R and 1 where not punctured) / get_ncoded(n, &count) /
+ *   get_nmax   the longest message: the decisions of a frame, T S / 8 bytes, fit YAGI_CONVCODE_DECISION_BYTES and
+ *                             T <= YAGI_CONVCODE_STEPS_MAX; a longer frame, or n = 0, is YAGI_ERR_CONFIG
+ *   encode_block(msg, msg_pitch, n, F, coded, coded_pitch)   F rows of ceil(n / 8) message bytes (pad bits ignored) ->
+ *                             F rows of ncoded(n) bytes
+ *   decode_block(soft, soft_pitch, n, F, msg, msg_pitch, metric)   F rows of ncoded(n) soft bytes -> F rows of
+ *                             ceil(n / 8) bytes; metric, where not NULL, receives one u32 per frame
+ *   encode_block_dev / decode_block_dev   device pointers, asynchronous on the object's stream
+ *   encode_host / decode_host   the definition's sequential loops on the host alone; no device needed
+ *   set_shape(frames_per_wave, waves) / get_shape / yagi_hip_convcode_plan   the decoder's launch arrangement.  A lane
+ *                             holds states_per_lane = max(1, S / 64) states; a wave holds frames_per_wave frames (a power
+ *                             of two, max(1, 8 / S) .. max(1, 64 / S)); a workgroup is 1, 2 or 4 waves; the soft bytes are
+ *                             staged chunk_steps steps at a time.  set_shape(0, 0) returns to the planner.  Every
+ *                             admissible arrangement gives the same bytes; one whose LDS does not hold a call's frames
+ *                             is YAGI_ERR_CONFIG at that call.
+ * The pitches are in bytes and at least the row length; F <= YAGI_CONVCODE_FRAMES_MAX; F = 0 touches nothing; the
+ * operands of a _dev call must not overlap; a device metric pointer is 4-byte aligned.  The decoder loads the soft bytes
+ * as the aligned 4-byte words that contain them.
+ * Not built: lane-per-frame arrangement, decisions in global memory, sliding-window traceback,
+ * parallel traceback, tail-biting, [step][channel] soft input, fused descrambling or interleaving, block codes, CRC.
+ * Device form: convcode_kernels.hip. */
+#define YAGI_CONVCODE_DECISION_BYTES 131072
+#define YAGI_CONVCODE_STEPS_MAX 65536
+#define YAGI_CONVCODE_FRAMES_MAX 1048576
+#define YAGI_CONVCODE_PERIOD_MAX 32
+typedef struct yagi_hip_convcode_s *yagi_hip_convcode;
+typedef struct {
+    unsigned frames_per_wave, waves, states_per_lane, chunk_steps;
+    size_t frames_per_wg, lds_bytes;
+} yagi_hip_convcode_shape;
+int yagi_hip_convcode_plan(int K, int terminated, size_t n, size_t F, yagi_hip_convcode_shape *plan);
+int yagi_hip_convcode_create(int K, const unsigned *g, int R, const uint8_t *puncture, int p, int terminated,
+                             yagi_hip_convcode *q);
+int yagi_hip_convcode_destroy(yagi_hip_convcode q);
+int yagi_hip_convcode_clone(yagi_hip_convcode q, yagi_hip_convcode *out);
+int yagi_hip_convcode_set_stream(yagi_hip_convcode q, yagi_stream_t s);
+int yagi_hip_convcode_get_K(yagi_hip_convcode q, int *K);
+int yagi_hip_convcode_get_R(yagi_hip_convcode q, int *R);
+int yagi_hip_convcode_get_rate(yagi_hip_convcode q, size_t *kept, size_t *p);
+int yagi_hip_convcode_get_ncoded(yagi_hip_convcode q, size_t n, size_t *ncoded);
+int yagi_hip_convcode_get_nmax(yagi_hip_convcode q, size_t *nmax);
+int yagi_hip_convcode_set_shape(yagi_hip_convcode q, unsigned frames_per_wave, unsigned waves);
+int yagi_hip_convcode_get_shape(yagi_hip_convcode q, size_t n, size_t F, yagi_hip_convcode_shape *shape);
+int yagi_hip_convcode_encode_block(yagi_hip_convcode q, const uint8_t *msg, size_t msg_pitch, size_t n, size_t F,
+                                   uint8_t *coded, size_t coded_pitch);
+int yagi_hip_convcode_encode_block_dev(yagi_hip_convcode q, const uint8_t *msg_dev, size_t msg_pitch, size_t n, size_t F,
+                                       uint8_t *coded_dev, size_t coded_pitch);
+int yagi_hip_convcode_decode_block(yagi_hip_convcode q, const uint8_t *soft, size_t soft_pitch, size_t n, size_t F,
+                                   uint8_t *msg, size_t msg_pitch, uint32_t *metric);
+int yagi_hip_convcode_decode_block_dev(yagi_hip_convcode q, const uint8_t *soft_dev, size_t soft_pitch, size_t n, size_t F,
+                                       uint8_t *msg_dev, size_t msg_pitch, uint32_t *metric_dev);
+int yagi_hip_convcode_encode_host(int K, const unsigned *g, int R, const uint8_t *puncture, int p, int terminated,
+                                  const uint8_t *msg, size_t msg_pitch, size_t n, size_t F, uint8_t *coded,
+                                  size_t coded_pitch);
+int yagi_hip_convcode_decode_host(int K, const unsigned *g, int R, const uint8_t *puncture, int p, int terminated,
+                                  const uint8_t *soft, size_t soft_pitch, size_t n, size_t F, uint8_t *msg, size_t msg_pitch,
+                                  uint32_t *metric);
+/* ncoded(n) and nmax of a code on the host alone; either output pointer may be NULL (n is checked only for ncoded) */
+int yagi_hip_convcode_ncoded_host(int K, int R, const uint8_t *puncture, int p, int terminated, size_t n, size_t *ncoded,
+                                  size_t *nmax);
+
 /* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */
 

@@ -23,6 +23,7 @@ The classes keep the reference's names, argument meaning and error behaviour
     EqLms, EqLmsUpdate         src/equalization/eqlms.rs:25-199, one object per channel of a bank
     EqRls, EqRlsUpdate         src/equalization/eqrls.rs:31-176, one object per channel of a bank
     SymTrack, SymTrackEq       (src/framing/symtrack.rs is empty: Agc -> SymSync -> Osc -> EqLms -> Modem, loops closed)
+    ConvCode                   (src/fec/mod.rs is empty: convolutional encoder and Viterbi decoder for a bank of frames)
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -41,7 +42,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "EqLms", "EqLmsUpdate", "EqRls", "EqRlsUpdate", "eqrls_plan", "EQRLS_LEN_MAX", "EQRLS_CHANNELS_MAX", "EQRLS_MATRIX_MAX", "SymTrack", "SymTrackEq", "symtrack_host", "SYMTRACK_CHANNELS_MAX", "SYMTRACK_PLL_ARG_MAX", "SYMTRACK_STALL_CAPACITY", "SYMTRACK_STALL_PLL", "EQLMS_LEN_MAX", "EQLMS_CHANNELS_MAX", "EQLMS_TABLE_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "EqLms", "EqLmsUpdate", "EqRls", "EqRlsUpdate", "eqrls_plan", "EQRLS_LEN_MAX", "EQRLS_CHANNELS_MAX", "EQRLS_MATRIX_MAX", "ConvCode", "convcode_plan", "CONVCODE_DECISION_BYTES", "CONVCODE_STEPS_MAX", "CONVCODE_FRAMES_MAX", "CONVCODE_PERIOD_MAX", "SymTrack", "SymTrackEq", "symtrack_host", "SYMTRACK_CHANNELS_MAX", "SYMTRACK_PLL_ARG_MAX", "SYMTRACK_STALL_CAPACITY", "SYMTRACK_STALL_PLL", "EQLMS_LEN_MAX", "EQLMS_CHANNELS_MAX", "EQLMS_TABLE_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "SpgramPlan", "plan_spgram", "MsResamp2Plan", "Resamp2Plan", "plan_msresamp2", "plan_resamp2", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
@@ -3114,6 +3115,215 @@ class Channel(_Handle):
                                                       _channel_u64(seed, "seed"), _ptr(h),
                                                       *(_ptr(w) for w in words), _ptr(x), x_pitch, n, _ptr(y), y_pitch))
         return y
+
+
+CONVCODE_DECISION_BYTES = 131072   # YAGI_CONVCODE_DECISION_BYTES: the decisions of one frame, T S / 8 bytes
+CONVCODE_STEPS_MAX = 65536         # YAGI_CONVCODE_STEPS_MAX
+CONVCODE_FRAMES_MAX = 1 << 20      # YAGI_CONVCODE_FRAMES_MAX
+CONVCODE_PERIOD_MAX = 32           # YAGI_CONVCODE_PERIOD_MAX
+
+
+def _convcode_shape(s):
+    return {"frames_per_wave": s.frames_per_wave, "waves": s.waves, "states_per_lane": s.states_per_lane,
+            "chunk_steps": s.chunk_steps, "frames_per_wg": s.frames_per_wg, "lds_bytes": s.lds_bytes}
+
+
+def _convcode_code(K, polys, puncture):
+    """(K, g, R, P or None, p) as the C ABI takes them; what it would misread is a ConfigError here"""
+    polys = list(polys)
+    if not all(isinstance(v, (int, np.integer)) and 0 <= v < 2 ** 32 for v in polys):
+        raise ConfigError("the generator words are unsigned integers")
+    g = np.array(polys, np.uint32)
+    if puncture is None:
+        return int(K), g, g.size, None, 1
+    P = np.asarray(puncture)
+    if P.ndim != 2 or P.shape[0] != g.size or not np.isin(P, (0, 1)).all():
+        raise ConfigError("the puncture matrix is [generators, p] of 0 and 1")
+    return int(K), g, g.size, _arr(P, np.uint8), P.shape[1]
+
+
+def _convcode_rows(a, width, what):
+    """a 2-D uint8 plane of at least `width` bytes per row -> (array, rows, pitch)"""
+    a = _arr(a, np.uint8)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2 or a.shape[1] < width:
+        raise ConfigError(f"{what} is [frames, at least {width} bytes]")
+    return a, a.shape[0], a.shape[1]
+
+
+def _convcode_out(out, F, width):
+    if out is None:
+        return np.zeros((F, width), np.uint8)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.ndim == 2
+            and out.shape[0] == F and out.shape[1] >= width):
+        raise ConfigError(f"the output is a C-contiguous uint8 array [{F}, at least {width}]")
+    return out
+
+
+def convcode_plan(K, n, F, terminated=True):
+    """yagi_hip_convcode_plan: the arrangement ConvCode.decode_block runs F frames of n bits at"""
+    s = _capi.convcode_shape()
+    _check(lib.yagi_hip_convcode_plan(int(K), int(bool(terminated)), _symsync_size(n, "n"), _symsync_size(F, "F"), C.byref(s)))
+    return _convcode_shape(s)
+
+
+class ConvCode(_Handle):
+    """ConvCode(K, polys, puncture=None, terminated=True): a convolutional code of constraint length K (3 .. 9) with
+    2 .. 4 generator words and an optional [generators, p] puncture matrix, over a bank of frames (yagi_hip.h, "ConvCode:
+    the definition").  encode_block turns rows of packed message bytes (most significant bit first) into rows of one byte
+    per coded bit; decode_block is a Viterbi decoder over rows of soft bytes (0 .. 255, 255 a confident 1: Modem's soft
+    bits) and returns the packed messages and the path metric of each frame.  Everything is integer arithmetic: every
+    byte equals the definition's sequential loop.  The block calls run convcode_kernels.hip; no call keeps state."""
+    _prefix = "yagi_hip_convcode_"
+
+    def __init__(self, K, polys, puncture=None, terminated=True):
+        K, g, R, P, p = _convcode_code(K, polys, puncture)
+        hd = C.c_void_p()
+        _check(self._fn("create")(K, _ptr(g), R, None if P is None else _ptr(P), p, int(bool(terminated)), C.byref(hd)))
+        self._h, self.K, self.R, self.terminated = hd, K, R, bool(terminated)
+
+    # the public Voyager / CCSDS words
+    @classmethod
+    def v27(cls):
+        return cls(7, (0x6d, 0x4f))
+
+    @classmethod
+    def v29(cls):
+        return cls(9, (0x1af, 0x11d))
+
+    @classmethod
+    def v39(cls):
+        return cls(9, (0x1ed, 0x19b, 0x127))
+
+    @classmethod
+    def v27p23(cls):
+        return cls(7, (0x6d, 0x4f), [[1, 1], [1, 0]])
+
+    @classmethod
+    def v27p34(cls):
+        return cls(7, (0x6d, 0x4f), [[1, 1, 0], [1, 0, 1]])
+
+    def clone(self):
+        new, hd = object.__new__(type(self)), C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._h, new.K, new.R, new.terminated = hd, self.K, self.R, self.terminated
+        return new
+
+    def _call(self, name, *args):
+        _check(self._fn(name)(self._h, *args))
+
+    def get_K(self):
+        v = C.c_int()
+        self._call("get_K", C.byref(v))
+        return v.value
+
+    def get_R(self):
+        v = C.c_int()
+        self._call("get_R", C.byref(v))
+        return v.value
+
+    def rate(self):
+        """(kept, p): kept coded bits per p message bits"""
+        k, p = C.c_size_t(), C.c_size_t()
+        self._call("get_rate", C.byref(k), C.byref(p))
+        return k.value, p.value
+
+    def ncoded(self, n):
+        """coded bytes of a frame of n message bits"""
+        v = C.c_size_t()
+        self._call("get_ncoded", _symsync_size(n, "n"), C.byref(v))
+        return v.value
+
+    def nmax(self):
+        v = C.c_size_t()
+        self._call("get_nmax", C.byref(v))
+        return v.value
+
+    def set_shape(self, frames_per_wave=0, waves=0):
+        """override the decoder's launch arrangement; (0, 0): the planner"""
+        self._call("set_shape", frames_per_wave, waves)
+
+    def get_shape(self, n, F):
+        s = _capi.convcode_shape()
+        self._call("get_shape", _symsync_size(n, "n"), _symsync_size(F, "F"), C.byref(s))
+        return _convcode_shape(s)
+
+    def encode_block(self, msg, n, out=None):
+        """msg[F, >= ceil(n / 8)] packed bytes -> coded[F, ncoded(n)] of 0 / 1 (or into the leading columns of out)"""
+        n = _symsync_size(n, "n")
+        msg, F, pitch = _convcode_rows(msg, (n + 7) // 8, "msg")
+        out = _convcode_out(out, F, self.ncoded(n))
+        self._call("encode_block", _ptr(msg), pitch, n, F, _ptr(out), out.shape[1])
+        return out
+
+    def decode_block(self, soft, n, out=None, metric=True):
+        """soft[F, >= ncoded(n)] -> (msg[F, ceil(n / 8)], metric[F] uint32), or msg alone where metric is False"""
+        n = _symsync_size(n, "n")
+        soft, F, pitch = _convcode_rows(soft, self.ncoded(n), "soft")
+        out = _convcode_out(out, F, (n + 7) // 8)
+        m = np.zeros(F, np.uint32) if metric else None
+        self._call("decode_block", _ptr(soft), pitch, n, F, _ptr(out), out.shape[1], None if m is None else _ptr(m))
+        return (out, m) if metric else out
+
+    def encode_block_devptr(self, msg_dev, msg_pitch, n, F, coded_dev, coded_pitch):
+        """device pointers, pitches in bytes; asynchronous on the object's stream (the C ABI's encode_block_dev)"""
+        self._call("encode_block_dev", None if msg_dev is None else _devptr(msg_dev), msg_pitch, n, F,
+                   None if coded_dev is None else _devptr(coded_dev), coded_pitch)
+
+    def decode_block_devptr(self, soft_dev, soft_pitch, n, F, msg_dev, msg_pitch, metric_dev=None):
+        self._call("decode_block_dev", None if soft_dev is None else _devptr(soft_dev), soft_pitch, n, F,
+                   None if msg_dev is None else _devptr(msg_dev), msg_pitch, None if metric_dev is None else _devptr(metric_dev))
+
+    # the definition on the host alone, no device needed: the library's own sequential loops, slow and meant for checks
+    @staticmethod
+    def ncoded_host(K, R, n, puncture=None, terminated=True):
+        K, g, R, P, p = _convcode_code(K, [1] * int(R), puncture)
+        v = C.c_size_t()
+        _check(lib.yagi_hip_convcode_ncoded_host(K, R, None if P is None else _ptr(P), p, int(bool(terminated)),
+                                                 _symsync_size(n, "n"), C.byref(v), None))
+        return v.value
+
+    @staticmethod
+    def nmax_host(K, R=2, puncture=None, terminated=True):
+        K, g, R, P, p = _convcode_code(K, [1] * int(R), puncture)
+        v = C.c_size_t()
+        _check(lib.yagi_hip_convcode_ncoded_host(K, R, None if P is None else _ptr(P), p, int(bool(terminated)), 0, None,
+                                                 C.byref(v)))
+        return v.value
+
+    @staticmethod
+    def encode_host(K, polys, msg, n, puncture=None, terminated=True, out=None, msg_pitch=None, coded_pitch=None):
+        """msg[F, pitch] -> coded[F, coded_pitch]; the pitches default to the arrays' widths (given explicitly they are
+        handed to the library as they are, for its argument checks)"""
+        K, g, R, P, p = _convcode_code(K, polys, puncture)
+        n = _symsync_size(n, "n")
+        msg = _arr(msg, np.uint8)
+        msg = msg[None, :] if msg.ndim == 1 else msg
+        F = msg.shape[0]
+        if out is None:
+            out = np.zeros((F, ConvCode.ncoded_host(K, R, n, puncture, terminated)), np.uint8)
+        _check(lib.yagi_hip_convcode_encode_host(K, _ptr(g), R, None if P is None else _ptr(P), p, int(bool(terminated)),
+                                                 _ptr(msg), msg.shape[1] if msg_pitch is None else msg_pitch, n, F, _ptr(out),
+                                                 out.shape[1] if coded_pitch is None else coded_pitch))
+        return out
+
+    @staticmethod
+    def decode_host(K, polys, soft, n, puncture=None, terminated=True, out=None, metric=True, soft_pitch=None, msg_pitch=None):
+        """soft[F, pitch] -> (msg[F, ceil(n / 8)], metric[F]), or msg alone where metric is False"""
+        K, g, R, P, p = _convcode_code(K, polys, puncture)
+        n = _symsync_size(n, "n")
+        soft = _arr(soft, np.uint8)
+        soft = soft[None, :] if soft.ndim == 1 else soft
+        F = soft.shape[0]
+        if out is None:
+            out = np.zeros((F, (n + 7) // 8), np.uint8)
+        m = np.zeros(F, np.uint32) if metric else None
+        _check(lib.yagi_hip_convcode_decode_host(K, _ptr(g), R, None if P is None else _ptr(P), p, int(bool(terminated)),
+                                                 _ptr(soft), soft.shape[1] if soft_pitch is None else soft_pitch, n, F,
+                                                 _ptr(out), out.shape[1] if msg_pitch is None else msg_pitch,
+                                                 None if m is None else _ptr(m)))
+        return (out, m) if metric else out
 
 
 SYMTRACK_CHANNELS_MAX = 1 << 20    # YAGI_SYMTRACK_CHANNELS_MAX

@@ -832,6 +832,34 @@ _sig("yagi_hip_channel_radius", vp, sz, vp)
 _sig("yagi_hip_channel_noise", u64, u64, u64, sz, vp)
 _sig("yagi_hip_channel_constrain", f32, C.POINTER(C.c_uint32))
 
+# ---- ConvCode ----------------------------------------------------------------------------------
+class convcode_shape(C.Structure):
+    """yagi_hip_convcode_shape"""
+    _fields_ = [("frames_per_wave", C.c_uint), ("waves", C.c_uint), ("states_per_lane", C.c_uint), ("chunk_steps", C.c_uint),
+                ("frames_per_wg", sz), ("lds_bytes", sz)]
+
+
+_p = "yagi_hip_convcode_"
+_sig(_p + "plan", ci, ci, sz, sz, C.POINTER(convcode_shape))
+_sig(_p + "create", ci, vp, ci, vp, ci, ci, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+for _n in ("get_K", "get_R"):
+    _sig(_p + _n, vp, C.POINTER(ci))
+_sig(_p + "get_rate", vp, C.POINTER(sz), C.POINTER(sz))
+_sig(_p + "get_ncoded", vp, sz, C.POINTER(sz))
+_sig(_p + "get_nmax", vp, C.POINTER(sz))
+_sig(_p + "set_shape", vp, C.c_uint, C.c_uint)
+_sig(_p + "get_shape", vp, sz, sz, C.POINTER(convcode_shape))
+for _n in ("encode_block", "encode_block_dev"):
+    _sig(_p + _n, vp, vp, sz, sz, sz, vp, sz)
+for _n in ("decode_block", "decode_block_dev"):
+    _sig(_p + _n, vp, vp, sz, sz, sz, vp, sz, vp)
+_sig(_p + "encode_host", ci, vp, ci, vp, ci, ci, vp, sz, sz, sz, vp, sz)
+_sig(_p + "decode_host", ci, vp, ci, vp, ci, ci, vp, sz, sz, sz, vp, sz, vp)
+_sig(_p + "ncoded_host", ci, ci, vp, ci, ci, sz, C.POINTER(sz), C.POINTER(sz))
+
 # ---- SymStream ---------------------------------------------------------------------------------
 _p = "yagi_hip_symstreamcf_"
 _sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)

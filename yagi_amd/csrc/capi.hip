@@ -8740,6 +8740,241 @@ int yagi_hip_channel_constrain(float phi, uint32_t *word) try {
 
 }  // extern "C"
 
+// ---- ConvCode (yagi_hip.h; src/fec/mod.rs is empty) ------------------------------------------------------------------
+// No call carries state: the object is the code, its puncture table on the device and the staging of the host forms, so
+// there is no mirror and it is not a BankObj.
+namespace yagi {
+
+// everything that needs no device
+struct ConvHost : ConvCode {
+    ConvShape forced{0, 0};                                 // set_shape; fpw = 0: the planner's
+
+    static int check_K(int K_) {
+        if (K_ < 3 || K_ > 9) return fail(YAGI_ERR_CONFIG, "convcode: the constraint length %d is outside 3 .. 9", K_);
+        return YAGI_OK;
+    }
+    int configure(int K_, const unsigned *g_, int R_, const uint8_t *puncture, int p_, int terminated_) {
+        YG_TRY(check_K(K_));
+        if (R_ < 2 || R_ > 4) return fail(YAGI_ERR_CONFIG, "convcode: %d generators are outside 2 .. 4", R_);
+        if (!g_) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        for (int r = 0; r < R_; ++r)
+            if (g_[r] == 0 || g_[r] >= (1u << K_))
+                return fail(YAGI_ERR_CONFIG, "convcode: generator %d (0x%x) is outside 1 .. 2^%d - 1", r, g_[r], K_);
+        if (!puncture) p_ = 1;
+        if (p_ < 1 || p_ > YAGI_CONVCODE_PERIOD_MAX)
+            return fail(YAGI_ERR_CONFIG, "convcode: the puncture period %d is outside 1 .. YAGI_CONVCODE_PERIOD_MAX", p_);
+        K = K_, R = R_, p = p_, terminated = terminated_ != 0, kp = 0;
+        for (int r = 0; r < 4; ++r) g[r] = r < R ? g_[r] : 0u;
+        for (int j = 0; j < YAGI_CONVCODE_PERIOD_MAX; ++j) off[j] = keep[j] = 0;
+        for (int j = 0; j < p; ++j) {
+            for (int r = 0; r < R; ++r) {
+                const unsigned v = puncture ? puncture[(size_t)r * p + j] : 1u;
+                if (v > 1) return fail(YAGI_ERR_CONFIG, "convcode: the puncture matrix holds 0 and 1 only");
+                off[j] |= kp << (8 * r);
+                keep[j] |= v << r;
+                kp += v;
+            }
+            for (int r = R; r < 4; ++r) off[j] |= kp << (8 * r);
+            if (keep[j] == 0) return fail(YAGI_ERR_CONFIG, "convcode: puncture column %d keeps no bit", j);
+        }
+        return YAGI_OK;
+    }
+    int check_n(size_t n) const {
+        if (n == 0) return fail(YAGI_ERR_CONFIG, "convcode: a frame holds at least one bit");
+        if (n > nmax())
+            return fail(YAGI_ERR_CONFIG,
+                        "convcode: %zu bits are more than %zu: the decisions of a frame fit YAGI_CONVCODE_DECISION_BYTES and its "
+                        "steps YAGI_CONVCODE_STEPS_MAX", n, nmax());
+        return YAGI_OK;
+    }
+    // rows of a bytes in, rows of b bytes out (and F metric words): the pitches, the pointers and the overlaps
+    int check_block(size_t n, size_t F, const void *in, size_t in_pitch, size_t a, const void *out, size_t out_pitch, size_t b,
+                    const uint32_t *metric) const {
+        YG_TRY(check_n(n));
+        if (F > (size_t)YAGI_CONVCODE_FRAMES_MAX) return fail(YAGI_ERR_CONFIG, "convcode: %zu frames are more than YAGI_CONVCODE_FRAMES_MAX", F);
+        if (in_pitch < a || out_pitch < b)
+            return fail(YAGI_ERR_CONFIG, "convcode: the pitches are in bytes, at least the row length (%zu in, %zu out)", a, b);
+        if (F == 0) return YAGI_OK;
+        if (!in || !out) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        const size_t nin = (F - 1) * in_pitch + a, nout = (F - 1) * out_pitch + b;
+        YG_TRY(check_noalias(in, nin, out, nout));
+        if (metric) {
+            if ((uintptr_t)metric & 3) return fail(YAGI_ERR_CONFIG, "convcode: the metric words are 4-byte aligned");
+            YG_TRY(check_noalias(in, nin, metric, F * sizeof(uint32_t)));
+            YG_TRY(check_noalias(out, nout, metric, F * sizeof(uint32_t)));
+        }
+        return YAGI_OK;
+    }
+    ConvShape shape(size_t n, size_t F) const { return forced.fpw ? forced : conv_plan(K, steps(n), F); }
+    void fill_shape(ConvShape s, size_t n, yagi_hip_convcode_shape *out) const {
+        out->frames_per_wave = s.fpw, out->waves = s.waves, out->states_per_lane = conv_spl(K), out->chunk_steps = conv_chunk(s);
+        out->frames_per_wg = (size_t)s.fpw * s.waves;
+        out->lds_bytes = conv_lds_bytes(K, s, steps(n));
+    }
+};
+
+struct ConvObj : ConvHost {
+    using Host = ConvHost;
+    hipStream_t st = nullptr;
+    DevBuf tab, wm;                                         // the puncture table; the metric words of a host call
+    Staging ws;
+
+    int alloc() {
+        YG_TRY(require_device());
+        uint32_t words[kConvTableWords];
+        conv_table(*this, words);
+        return fill(tab, words, sizeof(words), st);
+    }
+    int ensure_host() { return YAGI_OK; }                   // bank_clone's hook: nothing lives on the device alone
+    int encode_dev(const uint8_t *msg, size_t msg_pitch, size_t n, size_t F, uint8_t *coded, size_t coded_pitch) {
+        return launch_conv_encode(*this, tab.as<uint32_t>(), msg, msg_pitch, n, F, coded, coded_pitch, st);
+    }
+    int decode_dev(const uint8_t *soft, size_t soft_pitch, size_t n, size_t F, uint8_t *msg, size_t msg_pitch, uint32_t *metric) {
+        return launch_conv_decode(*this, shape(n, F), tab.as<uint32_t>(), soft, soft_pitch, n, F, msg, msg_pitch, metric, st);
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_convcode_s : ConvObj {};
+
+extern "C" {
+
+int yagi_hip_convcode_plan(int K, int terminated, size_t n, size_t F, yagi_hip_convcode_shape *plan) try {
+    CHECK_PTR(plan);
+    YG_TRY(ConvHost::check_K(K));
+    ConvHost o;
+    o.K = K, o.terminated = terminated != 0;
+    YG_TRY(o.check_n(n));
+    if (F > (size_t)YAGI_CONVCODE_FRAMES_MAX) return fail(YAGI_ERR_CONFIG, "convcode: %zu frames are more than YAGI_CONVCODE_FRAMES_MAX", F);
+    o.fill_shape(o.shape(n, F), n, plan);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_create(int K, const unsigned *g, int R, const uint8_t *puncture, int p, int terminated,
+                             yagi_hip_convcode *q) try {
+    return bank_create(q, K, g, R, puncture, p, terminated);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_destroy(yagi_hip_convcode q) try {
+    return bank_destroy(q);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_clone(yagi_hip_convcode q, yagi_hip_convcode *out) try {
+    return bank_clone(q, out);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_set_stream(yagi_hip_convcode q, yagi_stream_t s) try {
+    return bank_set_stream(q, s);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_get_K(yagi_hip_convcode q, int *K) try {
+    return bank_get(q, K, [](auto &o) { return o.K; });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_get_R(yagi_hip_convcode q, int *R) try {
+    return bank_get(q, R, [](auto &o) { return o.R; });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_get_rate(yagi_hip_convcode q, size_t *kept, size_t *p) try {
+    CHECK_Q(q);
+    CHECK_PTR(kept);
+    CHECK_PTR(p);
+    *kept = q->kp, *p = (size_t)q->p;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_get_ncoded(yagi_hip_convcode q, size_t n, size_t *ncoded) try {
+    CHECK_Q(q);
+    CHECK_PTR(ncoded);
+    YG_TRY(q->check_n(n));
+    *ncoded = q->ncoded(n);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_get_nmax(yagi_hip_convcode q, size_t *nmax) try {
+    return bank_get(q, nmax, [](auto &o) { return o.nmax(); });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_set_shape(yagi_hip_convcode q, unsigned frames_per_wave, unsigned waves) try {
+    CHECK_Q(q);
+    if (frames_per_wave == 0 && waves == 0) {
+        q->forced = ConvShape{0, 0};
+        return YAGI_OK;
+    }
+    const ConvShape s{frames_per_wave, waves};
+    if (!conv_shape_ok(q->K, s))
+        return fail(YAGI_ERR_CONFIG, "convcode: the shape (%u frames per wave, %u waves) is not admissible at K = %d",
+                    frames_per_wave, waves, q->K);
+    q->forced = s;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_get_shape(yagi_hip_convcode q, size_t n, size_t F, yagi_hip_convcode_shape *shape) try {
+    CHECK_Q(q);
+    CHECK_PTR(shape);
+    YG_TRY(q->check_n(n));
+    q->fill_shape(q->shape(n, F), n, shape);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_encode_block_dev(yagi_hip_convcode q, const uint8_t *msg_dev, size_t msg_pitch, size_t n, size_t F,
+                                       uint8_t *coded_dev, size_t coded_pitch) try {
+    CHECK_Q(q);
+    YG_TRY(q->check_block(n, F, msg_dev, msg_pitch, (n + 7) / 8, coded_dev, coded_pitch, q->ncoded(n), nullptr));
+    return q->encode_dev(msg_dev, msg_pitch, n, F, coded_dev, coded_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_decode_block_dev(yagi_hip_convcode q, const uint8_t *soft_dev, size_t soft_pitch, size_t n, size_t F,
+                                       uint8_t *msg_dev, size_t msg_pitch, uint32_t *metric_dev) try {
+    CHECK_Q(q);
+    YG_TRY(q->check_block(n, F, soft_dev, soft_pitch, q->ncoded(n), msg_dev, msg_pitch, (n + 7) / 8, metric_dev));
+    return q->decode_dev(soft_dev, soft_pitch, n, F, msg_dev, msg_pitch, metric_dev);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_encode_block(yagi_hip_convcode q, const uint8_t *msg, size_t msg_pitch, size_t n, size_t F,
+                                   uint8_t *coded, size_t coded_pitch) try {
+    CHECK_Q(q);
+    const size_t a = (n + 7) / 8, b = q->ncoded(n);
+    YG_TRY(q->check_block(n, F, msg, msg_pitch, a, coded, coded_pitch, b, nullptr));
+    if (F == 0) return YAGI_OK;
+    YG_TRY(q->ws.put(q->st, msg, (F - 1) * msg_pitch + a));
+    YG_TRY(q->ws.y.ensure(F * b));
+    YG_TRY(q->encode_dev(q->ws.x.as<uint8_t>(), msg_pitch, n, F, q->ws.y.as<uint8_t>(), b));
+    return download_rows(q->st, q->ws.y, F, b, coded, coded_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_decode_block(yagi_hip_convcode q, const uint8_t *soft, size_t soft_pitch, size_t n, size_t F,
+                                   uint8_t *msg, size_t msg_pitch, uint32_t *metric) try {
+    CHECK_Q(q);
+    const size_t a = q->ncoded(n), b = (n + 7) / 8;
+    YG_TRY(q->check_block(n, F, soft, soft_pitch, a, msg, msg_pitch, b, metric));
+    if (F == 0) return YAGI_OK;
+    YG_TRY(q->ws.put(q->st, soft, (F - 1) * soft_pitch + a));
+    YG_TRY(q->ws.y.ensure(F * b));
+    if (metric) YG_TRY(q->wm.ensure(F * sizeof(uint32_t)));
+    YG_TRY(q->decode_dev(q->ws.x.as<uint8_t>(), soft_pitch, n, F, q->ws.y.as<uint8_t>(), b, metric ? q->wm.as<uint32_t>() : nullptr));
+    YG_TRY(download_rows(q->st, q->ws.y, F, b, msg, msg_pitch));
+    return metric ? download(metric, q->wm.p, F * sizeof(uint32_t), q->st) : YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_encode_host(int K, const unsigned *g, int R, const uint8_t *puncture, int p, int terminated,
+                                  const uint8_t *msg, size_t msg_pitch, size_t n, size_t F, uint8_t *coded,
+                                  size_t coded_pitch) try {
+    ConvHost o;
+    YG_TRY(o.configure(K, g, R, puncture, p, terminated));
+    YG_TRY(o.check_block(n, F, msg, msg_pitch, (n + 7) / 8, coded, coded_pitch, o.ncoded(n), nullptr));
+    conv_encode_host(o, msg, msg_pitch, n, F, coded, coded_pitch);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_decode_host(int K, const unsigned *g, int R, const uint8_t *puncture, int p, int terminated,
+                                  const uint8_t *soft, size_t soft_pitch, size_t n, size_t F, uint8_t *msg, size_t msg_pitch,
+                                  uint32_t *metric) try {
+    ConvHost o;
+    YG_TRY(o.configure(K, g, R, puncture, p, terminated));
+    YG_TRY(o.check_block(n, F, soft, soft_pitch, o.ncoded(n), msg, msg_pitch, (n + 7) / 8, metric));
+    conv_decode_host(o, soft, soft_pitch, n, F, msg, msg_pitch, metric);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_convcode_ncoded_host(int K, int R, const uint8_t *puncture, int p, int terminated, size_t n, size_t *ncoded,
+                                  size_t *nmax) try {
+    ConvHost o;
+    const unsigned ones[4] = {1, 1, 1, 1};                  // the count does not depend on the generators
+    YG_TRY(o.configure(K, ones, R, puncture, p, terminated));
+    if (nmax) *nmax = o.nmax();
+    if (ncoded) {
+        YG_TRY(o.check_n(n));
+        *ncoded = o.ncoded(n);
+    }
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

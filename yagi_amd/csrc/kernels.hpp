@@ -882,4 +882,62 @@ int launch_symstreamr(const cf32 *swin, const float *shb, int Ls, float scale, c
                       uint32_t p0, size_t need, size_t ny, cf32 *ya, size_t split, cf32 *yb, cf32 *swin_next,
                       cf32 *rwin_next, cf32 *buf, hipStream_t st);
 
+// ---- convcode_kernels.hip ------------------------------------------------------------------
+// ConvCode (yagi_hip.h): a convolutional code and its puncture table; F frames per call, one per row of a byte plane.
+// off[j] holds, a byte per output r, the index within a period of bit (column j, output r): the kept bits of the columns
+// below j plus those of column j below r; keep[j] has bit r set where that bit is kept.  Unpunctured codes are p = 1.
+struct ConvCode {
+    int K = 0, R = 0, p = 1, terminated = 1;
+    unsigned g[4] = {0, 0, 0, 0};
+    unsigned kp = 0;                                   // kept bits of a period
+    uint32_t off[YAGI_CONVCODE_PERIOD_MAX] = {}, keep[YAGI_CONVCODE_PERIOD_MAX] = {};
+    size_t states() const { return (size_t)1 << (K - 1); }
+    size_t steps(size_t n) const { return n + (terminated ? (size_t)(K - 1) : 0); }
+    size_t pos(size_t t) const { return t / (size_t)p * kp + (off[t % (size_t)p] & 0xffu); }   // kept bits before step t
+    size_t ncoded(size_t n) const { return pos(steps(n)); }
+    size_t nmax() const {
+        size_t T = (size_t)YAGI_CONVCODE_DECISION_BYTES * 8 / states();
+        if (T > (size_t)YAGI_CONVCODE_STEPS_MAX) T = YAGI_CONVCODE_STEPS_MAX;
+        return T - (terminated ? (size_t)(K - 1) : 0);
+    }
+};
+constexpr size_t kConvTableWords = 2 * YAGI_CONVCODE_PERIOD_MAX;      // the device image: off[32], keep[32]
+constexpr size_t kConvLdsMax = 160 * 1024;
+constexpr unsigned kConvStage = 256;                   // staged (frame, step) pairs per wave and chunk
+// The decoder's arrangement: a lane holds spl = max(1, S / 64) states, a wave fpw frames (fpw S <= 64 lanes), a workgroup
+// `waves` waves; each wave stages the soft bytes of its frames chunk = kConvStage / fpw steps at a time.
+struct ConvShape {
+    unsigned fpw, waves;
+};
+constexpr unsigned conv_spl(int K) { return K > 7 ? 1u << (K - 7) : 1u; }
+constexpr unsigned conv_fpw_max(int K) { return K < 7 ? 1u << (7 - K) : 1u; }
+constexpr unsigned conv_fpw_min(int K) { return K < 4 ? 2u : 1u; }     // a wave's step is at least one whole byte of decisions
+constexpr unsigned conv_chunk(ConvShape s) { return kConvStage / s.fpw; }
+// decision bytes of one wave and step: the fpw S bits of its frames, or spl ballots
+constexpr size_t conv_step_bytes(int K, ConvShape s) { return K > 7 ? (size_t)8 << (K - 7) : ((size_t)s.fpw << (K - 1)) / 8; }
+// per wave: the decisions of T steps (padded to 8 bytes), kConvStage expanded steps of 8 bytes, and per frame the raw bytes
+// of a chunk (4 per step at most, plus the 8 of two partial words); per workgroup the table
+constexpr size_t conv_wave_bytes(int K, ConvShape s, size_t T) {
+    return ((T * conv_step_bytes(K, s) + 7) & ~(size_t)7) + (size_t)kConvStage * 8 + (size_t)s.fpw * (conv_chunk(s) * 4 + 8);
+}
+constexpr size_t conv_lds_bytes(int K, ConvShape s, size_t T) {
+    return kConvTableWords * 4 + s.waves * conv_wave_bytes(K, s, T);
+}
+static_assert(conv_lds_bytes(7, ConvShape{1, 1}, 16384) <= kConvLdsMax && conv_lds_bytes(9, ConvShape{1, 1}, 4096) <= kConvLdsMax &&
+              conv_lds_bytes(3, ConvShape{2, 1}, YAGI_CONVCODE_STEPS_MAX) <= kConvLdsMax,
+              "the longest frame of every K fits at the narrowest arrangement");
+bool conv_shape_ok(int K, ConvShape s);
+ConvShape conv_plan(int K, size_t T, size_t F);       // the shape a call of F frames of T steps runs at where none is set
+void conv_table(const ConvCode &c, uint32_t *words);   // kConvTableWords words
+// device forms; tab = conv_table's image on the device
+int launch_conv_encode(const ConvCode &c, const uint32_t *tab, const uint8_t *msg, size_t msg_pitch, size_t n, size_t F,
+                       uint8_t *coded, size_t coded_pitch, hipStream_t st);
+int launch_conv_decode(const ConvCode &c, ConvShape s, const uint32_t *tab, const uint8_t *soft, size_t soft_pitch, size_t n,
+                       size_t F, uint8_t *msg, size_t msg_pitch, uint32_t *metric, hipStream_t st);
+// the definition's sequential loops on the host, frame after frame
+void conv_encode_host(const ConvCode &c, const uint8_t *msg, size_t msg_pitch, size_t n, size_t F, uint8_t *coded,
+                      size_t coded_pitch);
+void conv_decode_host(const ConvCode &c, const uint8_t *soft, size_t soft_pitch, size_t n, size_t F, uint8_t *msg,
+                      size_t msg_pitch, uint32_t *metric);
+
 }  // namespace yagi
