@@ -2360,7 +2360,8 @@ int yagi_hip_channel_constrain(float phi, uint32_t *word);      /* Osc's constra
  * operands of a _dev call must not overlap; a device metric pointer is 4-byte aligned.  The decoder loads the soft bytes
  * as the aligned 4-byte words that contain them.
  * Not built: lane-per-frame arrangement, decisions in global memory, sliding-window traceback,
- * parallel traceback, tail-biting, [step][channel] soft input, fused descrambling or interleaving, block codes, CRC.
+ * parallel traceback, tail-biting, [step][channel] soft input, block codes.  Descrambling, interleaving and a CRC fused
+ * around this code are Packetizer's (below).
  * Device form: convcode_kernels.hip. */
 #define YAGI_CONVCODE_DECISION_BYTES 131072
 #define YAGI_CONVCODE_STEPS_MAX 65536
@@ -2401,6 +2402,106 @@ int yagi_hip_convcode_decode_host(int K, const unsigned *g, int R, const uint8_t
 /* ncoded(n) and nmax of a code on the host alone; either output pointer may be NULL (n is checked only for ncoded) */
 int yagi_hip_convcode_ncoded_host(int K, int R, const uint8_t *puncture, int p, int terminated, size_t n, size_t *ncoded,
                                   size_t *nmax);
+
+/* ---- Packetizer: CRC, ConvCode, block interleaver and scrambler for a bank of frames, one launch per direction ------------
+ * The reference has the scrambler (src/random/scramble.rs: scramble_data, unscramble_data, unscramble_data_soft) and an
+ * empty fec module, so the rest is defined here.  Packetizer(n, crc, K, g[R], P[R][p], terminated, columns, scramble) turns
+ * n >= 1 payload bytes per frame into a plane of transmit bits and soft bytes back into payloads with a `valid` flag; every
+ * call works on F frames, one per row: frame f starts at byte f * pitch.  No call carries state.  All of it is integer
+ * arithmetic: there is no tolerance anywhere.
+ * Packetizer: the definition.
+ *   CRC         five schemes in the Rocksoft model (width, poly, init, reflected in and out, xorout; the value on the nine
+ *               bytes "123456789"):
+ *                 YAGI_CRC_NONE   0   -            -            -    -            -
+ *                 YAGI_CRC_8      8   0x07         0x00         no   0x00         0xF4
+ *                 YAGI_CRC_16    16   0x1021       0xFFFF       no   0x0000       0x29B1
+ *                 YAGI_CRC_24    24   0x864CFB     0xB704CE     no   0x000000     0x21CF02
+ *                 YAGI_CRC_32    32   0x04C11DB7   0xFFFFFFFF   yes  0xFFFFFFFF   0xCBF43926
+ *               The CRC of the n payload bytes follows them as w = width / 8 bytes, most significant byte first.  The
+ *               message is these 8 (n + w) bits, most significant bit first; more than the code's get_nmax is
+ *               YAGI_ERR_CONFIG.
+ *   code        ConvCode's definition, unchanged: K, g, puncturing, terminated.  N = ncoded(8 (n + w)) coded bits in coder
+ *               order i = 0 .. N-1.
+ *   interleaver 1 <= columns = C <= YAGI_PACKETIZER_COLUMNS_MAX.  Coder-order bit i sits at row i div C, column i mod C of a
+ *               matrix of C columns; transmission is column by column; the cells the last row lacks are skipped.  With
+ *               q = N div C, r = N mod C the transmit position is pi(i) = (i mod C) q + min(i mod C, r) + i div C; its
+ *               inverse, for j < r (q + 1): c = j div (q + 1), rho = j mod (q + 1); else c = r + (j - r (q + 1)) div q,
+ *               rho = (j - r (q + 1)) mod q; i = rho C + c.  C = 1 and C >= N are the identity.  N = 7, C = 3 transmits
+ *               0 3 6 1 4 2 5.
+ *   scrambler   where scramble != 0, transmit bit j is XORed with m(j) = (MASK[(j div 8) mod 4] >> (7 - j mod 8)) & 1,
+ *               MASK = CA CC 53 5F (scramble.rs :2-5); the receiver replaces the soft byte s at j by 255 - s where
+ *               m(j) = 1.  On packed bytes this is scramble_data, on whole groups of eight soft bytes
+ *               unscramble_data_soft.  The reference's soft routine leaves a trailing group of fewer than eight bytes
+ *               alone (chunks_exact) while its packed routine masks the last byte whole; the Packetizer masks every bit
+ *               j < N, so its two directions agree at every N.
+ *   transmit    encode_block(payload, bps), 1 <= bps <= 8, writes nsym(bps) = ceil(N / bps) bytes per frame, each holding
+ *               bps consecutive transmit bits, the first uppermost; the missing bits of the last symbol are 0.  bps = 1 is
+ *               ConvCode's byte per bit; bps = 2 is what Modem(Qpsk).modulate_block takes.
+ *   receive     decode_block(soft): rows of at least N soft bytes (0 .. 255, 255 a confident 1: Modem's soft bits) in
+ *               transmit order; bytes from N on are never read.  payload[F][n] receives the first n decoded bytes and
+ *               nothing beyond them; valid[F] (u8) is 1 where the CRC of the decoded payload equals the decoded CRC field,
+ *               always 1 with YAGI_CRC_NONE; crc[F] (u32, may be NULL) is the CRC computed over the decoded payload, 0 for
+ *               NONE; metric[F] (u32, may be NULL) is ConvCode's.
+ *   create(n, crc, K, g, R, puncture, p, terminated, columns, scramble)   anything outside the limits is YAGI_ERR_CONFIG,
+ *                             decided before any device is asked for
+ *   destroy / clone / set_stream
+ *   get_payload_len (n) / get_crc_len (w) / get_msg_bits (8 (n + w)) / get_enc_len (N) / get_nsym(bps, &count) / get_columns
+ *   set_shape / get_shape(F) / yagi_hip_packetizer_plan   ConvCode's arrangement: the same admissible set, the same planner
+ *                             (on the steps of the message) and the same yagi_hip_convcode_shape; lds_bytes is what the
+ *                             Packetizer's decoder allocates (no staged raw words; a 2 KiB table where there is a CRC)
+ *   encode_block / decode_block, encode_block_dev / decode_block_dev (device pointers, asynchronous on the object's stream)
+ *   encode_host / decode_host   the definition's sequential loops on the host alone, around ConvCode's; no device needed
+ *   yagi_hip_crc_host(scheme, data, n, &crc) / yagi_hip_packetizer_permutation(N, columns, pi)   pi[i] for i < N
+ *   yagi_hip_scramble_data / yagi_hip_unscramble_data / yagi_hip_unscramble_data_soft   the reference's three functions
+ *                             exactly, in place, the chunks_exact behaviour of the soft one included
+ * The pitches are in bytes and at least the row length; F <= YAGI_CONVCODE_FRAMES_MAX; F = 0 touches nothing; the operands
+ * of a _dev call must not overlap; device crc and metric pointers are 4-byte aligned.  The decoder loads soft bytes one by
+ * one, so nothing outside a row's first N bytes is read.
+ * Not built: custom CRC polynomials, block codes and a second (outer) code, convolutional or
+ * per-symbol interleavers, [step][channel] soft input, a payload length per frame, a stand-alone device CRC or
+ * interleaver object, Modem fused into either side.
+ * Device form: packetizer_kernels.hip, convcode_body.hpp. */
+#define YAGI_CRC_NONE 0
+#define YAGI_CRC_8 1
+#define YAGI_CRC_16 2
+#define YAGI_CRC_24 3
+#define YAGI_CRC_32 4
+#define YAGI_PACKETIZER_COLUMNS_MAX 1048576
+typedef struct yagi_hip_packetizer_s *yagi_hip_packetizer;
+int yagi_hip_packetizer_plan(int K, int terminated, size_t n, int crc, size_t F, yagi_hip_convcode_shape *plan);
+int yagi_hip_packetizer_create(size_t n, int crc, int K, const unsigned *g, int R, const uint8_t *puncture, int p, int terminated,
+                               size_t columns, int scramble, yagi_hip_packetizer *q);
+int yagi_hip_packetizer_destroy(yagi_hip_packetizer q);
+int yagi_hip_packetizer_clone(yagi_hip_packetizer q, yagi_hip_packetizer *out);
+int yagi_hip_packetizer_set_stream(yagi_hip_packetizer q, yagi_stream_t s);
+int yagi_hip_packetizer_get_payload_len(yagi_hip_packetizer q, size_t *n);
+int yagi_hip_packetizer_get_crc_len(yagi_hip_packetizer q, size_t *w);
+int yagi_hip_packetizer_get_msg_bits(yagi_hip_packetizer q, size_t *bits);
+int yagi_hip_packetizer_get_enc_len(yagi_hip_packetizer q, size_t *N);
+int yagi_hip_packetizer_get_nsym(yagi_hip_packetizer q, unsigned bps, size_t *nsym);
+int yagi_hip_packetizer_get_columns(yagi_hip_packetizer q, size_t *columns);
+int yagi_hip_packetizer_set_shape(yagi_hip_packetizer q, unsigned frames_per_wave, unsigned waves);
+int yagi_hip_packetizer_get_shape(yagi_hip_packetizer q, size_t F, yagi_hip_convcode_shape *shape);
+int yagi_hip_packetizer_encode_block(yagi_hip_packetizer q, const uint8_t *payload, size_t payload_pitch, size_t F, unsigned bps,
+                                     uint8_t *tx, size_t tx_pitch);
+int yagi_hip_packetizer_encode_block_dev(yagi_hip_packetizer q, const uint8_t *payload_dev, size_t payload_pitch, size_t F,
+                                         unsigned bps, uint8_t *tx_dev, size_t tx_pitch);
+int yagi_hip_packetizer_decode_block(yagi_hip_packetizer q, const uint8_t *soft, size_t soft_pitch, size_t F, uint8_t *payload,
+                                     size_t payload_pitch, uint8_t *valid, uint32_t *crc, uint32_t *metric);
+int yagi_hip_packetizer_decode_block_dev(yagi_hip_packetizer q, const uint8_t *soft_dev, size_t soft_pitch, size_t F,
+                                         uint8_t *payload_dev, size_t payload_pitch, uint8_t *valid_dev, uint32_t *crc_dev,
+                                         uint32_t *metric_dev);
+int yagi_hip_packetizer_encode_host(size_t n, int crc, int K, const unsigned *g, int R, const uint8_t *puncture, int p,
+                                    int terminated, size_t columns, int scramble, const uint8_t *payload, size_t payload_pitch,
+                                    size_t F, unsigned bps, uint8_t *tx, size_t tx_pitch);
+int yagi_hip_packetizer_decode_host(size_t n, int crc, int K, const unsigned *g, int R, const uint8_t *puncture, int p,
+                                    int terminated, size_t columns, int scramble, const uint8_t *soft, size_t soft_pitch, size_t F,
+                                    uint8_t *payload, size_t payload_pitch, uint8_t *valid, uint32_t *crc_out, uint32_t *metric);
+int yagi_hip_crc_host(int scheme, const uint8_t *data, size_t n, uint32_t *crc);
+int yagi_hip_packetizer_permutation(size_t N, size_t columns, uint32_t *pi);
+int yagi_hip_scramble_data(uint8_t *x, size_t n);
+int yagi_hip_unscramble_data(uint8_t *x, size_t n);
+int yagi_hip_unscramble_data_soft(uint8_t *x, size_t n);
 
 /* ---- design helpers exposed for hosts that want the taps; no device needed ---------------- */
 int yagi_hip_fir_design_kaiser(size_t n, float fc, float as_, float mu, float *h);      /* kaiser.rs:16-51 */

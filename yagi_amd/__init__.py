@@ -24,6 +24,8 @@ The classes keep the reference's names, argument meaning and error behaviour
     EqRls, EqRlsUpdate         src/equalization/eqrls.rs:31-176, one object per channel of a bank
     SymTrack, SymTrackEq       (src/framing/symtrack.rs is empty: Agc -> SymSync -> Osc -> EqLms -> Modem, loops closed)
     ConvCode                   (src/fec/mod.rs is empty: convolutional encoder and Viterbi decoder for a bank of frames)
+    Packetizer, CrcScheme      src/random/scramble.rs for the mask; CRC, ConvCode, block interleaver and scrambler fused
+    scramble_data, unscramble_data, unscramble_data_soft    src/random/scramble.rs:7-53 (host)
 
 Generic parameters <T, Coeff> are spelled with liquid-dsp's suffixes: "rrrf" = <f32,f32>,
 "crcf" = <Complex32,f32>, "cccf" = <Complex32,Complex32>.  Every numeric result comes from a HIP
@@ -42,7 +44,7 @@ from ._capi import cf32, lib
 __all__ = [
     "YagiError", "InternalError", "ConfigError", "ValueError_", "RangeError", "ModeError",
     "NoConvergenceError", "DeviceError", "Direction", "dotprod", "FirFilter", "FirDecimationFilter",
-    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "EqLms", "EqLmsUpdate", "EqRls", "EqRlsUpdate", "eqrls_plan", "EQRLS_LEN_MAX", "EQRLS_CHANNELS_MAX", "EQRLS_MATRIX_MAX", "ConvCode", "convcode_plan", "CONVCODE_DECISION_BYTES", "CONVCODE_STEPS_MAX", "CONVCODE_FRAMES_MAX", "CONVCODE_PERIOD_MAX", "SymTrack", "SymTrackEq", "symtrack_host", "SYMTRACK_CHANNELS_MAX", "SYMTRACK_PLL_ARG_MAX", "SYMTRACK_STALL_CAPACITY", "SYMTRACK_STALL_PLL", "EQLMS_LEN_MAX", "EQLMS_CHANNELS_MAX", "EQLMS_TABLE_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
+    "FirPfbFilter", "FirInterpolationFilter", "Rresamp", "Resamp", "MsResamp", "IirFilter", "IirFilterShape", "iir_design_lowpass_sos", "IirDecimationFilter", "IirInterpolationFilter", "IirHilbertFilter", "Osc", "OscScheme", "Ddc", "Duc", "FirHilbertFilter", "Fdelay", "OrdFilt", "ORDFILT_NMAX", "ORDFILT_TILE", "ORDFILT_REG_NMAX", "Autocorr", "BurstDetector", "BURST_EVENT", "BURSTDET_SEGMAX", "burst_detect_host", "PreambleDetector", "PREAMBLE_EVENT", "PDET_LMAX", "PDET_KMAX", "PDET_TILE", "PDET_SEGMAX", "preamble_templates", "preamble_detect_host", "SymSync", "SYMSYNC_NPFB_MAX", "SYMSYNC_LS_MAX", "SYMSYNC_CHANNELS_MAX", "EqLms", "EqLmsUpdate", "EqRls", "EqRlsUpdate", "eqrls_plan", "EQRLS_LEN_MAX", "EQRLS_CHANNELS_MAX", "EQRLS_MATRIX_MAX", "ConvCode", "convcode_plan", "CONVCODE_DECISION_BYTES", "CONVCODE_STEPS_MAX", "CONVCODE_FRAMES_MAX", "CONVCODE_PERIOD_MAX", "Packetizer", "CrcScheme", "crc", "packetizer_permutation", "packetizer_plan", "scramble_data", "unscramble_data", "unscramble_data_soft", "PACKETIZER_COLUMNS_MAX", "SymTrack", "SymTrackEq", "symtrack_host", "SYMTRACK_CHANNELS_MAX", "SYMTRACK_PLL_ARG_MAX", "SYMTRACK_STALL_CAPACITY", "SYMTRACK_STALL_PLL", "EQLMS_LEN_MAX", "EQLMS_CHANNELS_MAX", "EQLMS_TABLE_MAX", "AUTOCORR_WMAX", "AUTOCORR_DMAX", "AUTOCORR_TILE", "MSequence", "BSequence", "MSEQUENCE_TILE", "BSEQUENCE_TILE", "BSEQUENCE_NMAX", "Modem", "ModulationScheme", "gray_encode", "gray_decode", "pack_soft_bits", "unpack_soft_bits", "FftFilt", "Fft", "FftPath", "FftInfo", "fft_run", "Spgram", "WindowType", "FirFftStream", "FirPfbCh", "FirPfbCh2", "FirPfbChr", "DeviceArray",
     "Plan", "SpgramPlan", "plan_spgram", "MsResamp2Plan", "Resamp2Plan", "plan_msresamp2", "plan_resamp2", "plan_fir_block","plan_firpfb_all", "plan_rresamp", "plan_resamp", "plan_fir_block_range",
     "plan_firpfb_all_range", "plan_rresamp_range", "plan_resamp_range",
     "fir_design_kaiser", "firhilb_design", "FirFilterShape", "fir_design_prototype",
@@ -3324,6 +3326,232 @@ class ConvCode(_Handle):
                                                  _ptr(out), out.shape[1] if msg_pitch is None else msg_pitch,
                                                  None if m is None else _ptr(m)))
         return (out, m) if metric else out
+
+
+PACKETIZER_COLUMNS_MAX = 1 << 20   # YAGI_PACKETIZER_COLUMNS_MAX
+
+
+class CrcScheme(enum.IntEnum):
+    """the Packetizer's CRC, numbered as YAGI_CRC_* (yagi_hip.h gives the Rocksoft parameters of each)"""
+    NONE = 0
+    CRC_8 = 1       # poly 0x07, init 0x00
+    CRC_16 = 2      # poly 0x1021, init 0xFFFF (CCITT-FALSE)
+    CRC_24 = 3      # poly 0x864CFB, init 0xB704CE (OpenPGP)
+    CRC_32 = 4      # poly 0x04C11DB7 reflected, init and xorout 0xFFFFFFFF (zlib's)
+
+
+def _crc_scheme(scheme):
+    if not isinstance(scheme, (int, np.integer)):
+        raise ConfigError("the CRC scheme is a CrcScheme")
+    return int(scheme)
+
+
+def crc(scheme, data):
+    """yagi_hip_crc_host: the CRC of a byte string under one of the Packetizer's schemes"""
+    data = _arr(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8).reshape(-1)
+    v = C.c_uint32()
+    _check(lib.yagi_hip_crc_host(_crc_scheme(scheme), _ptr(data), data.size, C.byref(v)))
+    return v.value
+
+
+def packetizer_permutation(N, columns):
+    """yagi_hip_packetizer_permutation: pi[i], the transmit position of coder-order bit i of N through C columns"""
+    N = _symsync_size(N, "N")
+    pi = np.zeros(N, np.uint32)
+    _check(lib.yagi_hip_packetizer_permutation(N, _symsync_size(columns, "columns"), _ptr(pi)))
+    return pi
+
+
+def _scramble(fn, x):
+    x = np.array(_arr(x, np.uint8).reshape(-1))
+    _check(fn(_ptr(x), x.size))
+    return x
+
+
+def scramble_data(x):
+    """random::scramble::scramble_data (scramble.rs :7-29) on a copy of the bytes"""
+    return _scramble(lib.yagi_hip_scramble_data, x)
+
+
+def unscramble_data(x):
+    """random::scramble::unscramble_data (scramble.rs :31-34) on a copy"""
+    return _scramble(lib.yagi_hip_unscramble_data, x)
+
+
+def unscramble_data_soft(x):
+    """random::scramble::unscramble_data_soft (scramble.rs :37-53) on a copy: whole groups of eight soft bytes"""
+    return _scramble(lib.yagi_hip_unscramble_data_soft, x)
+
+
+def packetizer_plan(K, n, crc, F, terminated=True):
+    """yagi_hip_packetizer_plan: the arrangement Packetizer.decode_block runs F frames of n payload bytes at"""
+    s = _capi.convcode_shape()
+    _check(lib.yagi_hip_packetizer_plan(int(K), int(bool(terminated)), _symsync_size(n, "n"), _crc_scheme(crc),
+                                        _symsync_size(F, "F"), C.byref(s)))
+    return _convcode_shape(s)
+
+
+def _packetizer_code(n, crc, K, polys, puncture, terminated, columns, scramble):
+    """the ten leading arguments of create and of the host forms, with what must stay alive"""
+    K, g, R, P, p = _convcode_code(K, polys, puncture)
+    args = (_symsync_size(n, "n"), _crc_scheme(crc), K, _ptr(g), R, None if P is None else _ptr(P), p, int(bool(terminated)),
+            _symsync_size(columns, "columns"), int(bool(scramble)))
+    return args, (g, P)
+
+
+class Packetizer(_Handle):
+    """Packetizer(n, crc, K, polys, puncture=None, terminated=True, columns=1, scramble=True): n payload bytes per frame, a
+    CRC behind them, ConvCode's code over both, a block interleaver of `columns` columns and the reference's scrambler
+    (random::scramble), for a bank of frames and in one launch per direction (yagi_hip.h, "Packetizer: the definition").
+    encode_block(payload, bps) gives the transmit plane, bps bits per byte (bps = 2 feeds Modem(Qpsk).modulate_block);
+    decode_block(soft) takes Modem's soft bytes in transmit order and returns the payloads, a valid flag per frame, the
+    CRC computed over each decoded payload and ConvCode's path metric.  Everything is integer arithmetic: every byte equals
+    the definition's sequential loops.  The block calls run packetizer_kernels.hip; no call keeps state."""
+    _prefix = "yagi_hip_packetizer_"
+
+    def __init__(self, n, crc, K, polys, puncture=None, terminated=True, columns=1, scramble=True):
+        args, keep = _packetizer_code(n, crc, K, polys, puncture, terminated, columns, scramble)
+        hd = C.c_void_p()
+        _check(self._fn("create")(*args, C.byref(hd)))
+        self._h, self.n, self.crc, self.K, self.terminated = hd, args[0], CrcScheme(args[1]), args[2], bool(terminated)
+        self.columns, self.scramble = args[8], bool(scramble)
+
+    # ConvCode's named codes
+    @classmethod
+    def v27(cls, n, crc=CrcScheme.CRC_32, **kw):
+        return cls(n, crc, 7, (0x6d, 0x4f), **kw)
+
+    @classmethod
+    def v29(cls, n, crc=CrcScheme.CRC_32, **kw):
+        return cls(n, crc, 9, (0x1af, 0x11d), **kw)
+
+    @classmethod
+    def v39(cls, n, crc=CrcScheme.CRC_32, **kw):
+        return cls(n, crc, 9, (0x1ed, 0x19b, 0x127), **kw)
+
+    @classmethod
+    def v27p23(cls, n, crc=CrcScheme.CRC_32, **kw):
+        return cls(n, crc, 7, (0x6d, 0x4f), [[1, 1], [1, 0]], **kw)
+
+    @classmethod
+    def v27p34(cls, n, crc=CrcScheme.CRC_32, **kw):
+        return cls(n, crc, 7, (0x6d, 0x4f), [[1, 1, 0], [1, 0, 1]], **kw)
+
+    def clone(self):
+        new, hd = object.__new__(type(self)), C.c_void_p()
+        _check(self._fn("clone")(self._h, C.byref(hd)))
+        new._h = hd
+        for k in ("n", "crc", "K", "terminated", "columns", "scramble"):
+            setattr(new, k, getattr(self, k))
+        return new
+
+    def _call(self, name, *args):
+        _check(self._fn(name)(self._h, *args))
+
+    def _size(self, name, *args):
+        v = C.c_size_t()
+        self._call(name, *args, C.byref(v))
+        return v.value
+
+    def payload_len(self):
+        return self._size("get_payload_len")
+
+    def crc_len(self):
+        return self._size("get_crc_len")
+
+    def msg_bits(self):
+        return self._size("get_msg_bits")
+
+    def enc_len(self):
+        """N: coded (= transmit) bits of a frame"""
+        return self._size("get_enc_len")
+
+    def nsym(self, bps=1):
+        """bytes of a frame's row of the transmit plane at bps bits per byte"""
+        return self._size("get_nsym", self._bps(bps))
+
+    def get_columns(self):
+        return self._size("get_columns")
+
+    @staticmethod
+    def _bps(bps):
+        if not (isinstance(bps, (int, np.integer)) and 0 <= bps < 2 ** 32):
+            raise ConfigError("bps is 1 .. 8")
+        return int(bps)
+
+    def set_shape(self, frames_per_wave=0, waves=0):
+        """override the decoder's launch arrangement (ConvCode's admissible set); (0, 0): the planner"""
+        self._call("set_shape", frames_per_wave, waves)
+
+    def get_shape(self, F):
+        s = _capi.convcode_shape()
+        self._call("get_shape", _symsync_size(F, "F"), C.byref(s))
+        return _convcode_shape(s)
+
+    def encode_block(self, payload, bps=1, out=None):
+        """payload[F, >= n] -> tx[F, nsym(bps)] (or into the leading columns of out)"""
+        bps = self._bps(bps)
+        payload, F, pitch = _convcode_rows(payload, self.n, "payload")
+        out = _convcode_out(out, F, self.nsym(bps))
+        self._call("encode_block", _ptr(payload), pitch, F, bps, _ptr(out), out.shape[1])
+        return out
+
+    def decode_block(self, soft, out=None, crc=True, metric=True):
+        """soft[F, >= N] -> (payload[F, n], valid[F] uint8, crc[F] uint32, metric[F] uint32); crc and metric are None where
+        not asked for"""
+        soft, F, pitch = _convcode_rows(soft, self.enc_len(), "soft")
+        out = _convcode_out(out, F, self.n)
+        valid = np.zeros(F, np.uint8)
+        c = np.zeros(F, np.uint32) if crc else None
+        m = np.zeros(F, np.uint32) if metric else None
+        self._call("decode_block", _ptr(soft), pitch, F, _ptr(out), out.shape[1], _ptr(valid), None if c is None else _ptr(c),
+                   None if m is None else _ptr(m))
+        return out, valid, c, m
+
+    def encode_block_devptr(self, payload_dev, payload_pitch, F, bps, tx_dev, tx_pitch):
+        """device pointers, pitches in bytes; asynchronous on the object's stream (the C ABI's encode_block_dev)"""
+        self._call("encode_block_dev", None if payload_dev is None else _devptr(payload_dev), payload_pitch, F, self._bps(bps),
+                   None if tx_dev is None else _devptr(tx_dev), tx_pitch)
+
+    def decode_block_devptr(self, soft_dev, soft_pitch, F, payload_dev, payload_pitch, valid_dev, crc_dev=None, metric_dev=None):
+        opt = [None if v is None else _devptr(v) for v in (soft_dev, payload_dev, valid_dev, crc_dev, metric_dev)]
+        self._call("decode_block_dev", opt[0], soft_pitch, F, opt[1], payload_pitch, opt[2], opt[3], opt[4])
+
+    # the definition on the host alone, no device needed: the library's own sequential loops, slow and meant for checks
+    @staticmethod
+    def encode_host(n, crc, K, polys, payload, bps=1, puncture=None, terminated=True, columns=1, scramble=True, out=None,
+                    payload_pitch=None, tx_pitch=None):
+        """payload[F, pitch] -> tx[F, tx_pitch]; the pitches default to the arrays' widths (given explicitly they are handed
+        to the library as they are, for its argument checks); out is needed where the sizes are not valid ones"""
+        args, keep = _packetizer_code(n, crc, K, polys, puncture, terminated, columns, scramble)
+        payload = _arr(payload, np.uint8)
+        payload = payload[None, :] if payload.ndim == 1 else payload
+        F = payload.shape[0]
+        if out is None:
+            w = (0, 1, 2, 3, 4)[args[1]] if 0 <= args[1] <= 4 else 0
+            N = ConvCode.ncoded_host(K, len(list(polys)), 8 * (args[0] + w), puncture, terminated)
+            out = np.zeros((F, -(-N // max(1, int(bps)))), np.uint8)
+        _check(lib.yagi_hip_packetizer_encode_host(*args, _ptr(payload), payload.shape[1] if payload_pitch is None else payload_pitch,
+                                                   F, Packetizer._bps(bps), _ptr(out), out.shape[1] if tx_pitch is None else tx_pitch))
+        return out
+
+    @staticmethod
+    def decode_host(n, crc, K, polys, soft, puncture=None, terminated=True, columns=1, scramble=True, out=None, soft_pitch=None,
+                    payload_pitch=None, want_crc=True, metric=True):
+        """soft[F, pitch] -> (payload[F, n], valid[F], crc[F] or None, metric[F] or None)"""
+        args, keep = _packetizer_code(n, crc, K, polys, puncture, terminated, columns, scramble)
+        soft = _arr(soft, np.uint8)
+        soft = soft[None, :] if soft.ndim == 1 else soft
+        F = soft.shape[0]
+        if out is None:
+            out = np.zeros((F, args[0]), np.uint8)
+        valid = np.zeros(F, np.uint8)
+        c = np.zeros(F, np.uint32) if want_crc else None
+        m = np.zeros(F, np.uint32) if metric else None
+        _check(lib.yagi_hip_packetizer_decode_host(*args, _ptr(soft), soft.shape[1] if soft_pitch is None else soft_pitch, F,
+                                                   _ptr(out), out.shape[1] if payload_pitch is None else payload_pitch, _ptr(valid),
+                                                   None if c is None else _ptr(c), None if m is None else _ptr(m)))
+        return out, valid, c, m
 
 
 SYMTRACK_CHANNELS_MAX = 1 << 20    # YAGI_SYMTRACK_CHANNELS_MAX

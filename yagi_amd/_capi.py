@@ -860,6 +860,29 @@ _sig(_p + "encode_host", ci, vp, ci, vp, ci, ci, vp, sz, sz, sz, vp, sz)
 _sig(_p + "decode_host", ci, vp, ci, vp, ci, ci, vp, sz, sz, sz, vp, sz, vp)
 _sig(_p + "ncoded_host", ci, ci, vp, ci, ci, sz, C.POINTER(sz), C.POINTER(sz))
 
+# ---- Packetizer --------------------------------------------------------------------------------
+_p = "yagi_hip_packetizer_"
+_sig(_p + "plan", ci, ci, sz, ci, sz, C.POINTER(convcode_shape))
+_sig(_p + "create", sz, ci, ci, vp, ci, vp, ci, ci, sz, ci, pvp)
+_sig(_p + "destroy", vp)
+_sig(_p + "clone", vp, pvp)
+_sig(_p + "set_stream", vp, vp)
+for _n in ("get_payload_len", "get_crc_len", "get_msg_bits", "get_enc_len", "get_columns"):
+    _sig(_p + _n, vp, C.POINTER(sz))
+_sig(_p + "get_nsym", vp, C.c_uint, C.POINTER(sz))
+_sig(_p + "set_shape", vp, C.c_uint, C.c_uint)
+_sig(_p + "get_shape", vp, sz, C.POINTER(convcode_shape))
+for _n in ("encode_block", "encode_block_dev"):
+    _sig(_p + _n, vp, vp, sz, sz, C.c_uint, vp, sz)
+for _n in ("decode_block", "decode_block_dev"):
+    _sig(_p + _n, vp, vp, sz, sz, vp, sz, vp, vp, vp)
+_sig(_p + "encode_host", sz, ci, ci, vp, ci, vp, ci, ci, sz, ci, vp, sz, sz, C.c_uint, vp, sz)
+_sig(_p + "decode_host", sz, ci, ci, vp, ci, vp, ci, ci, sz, ci, vp, sz, sz, vp, sz, vp, vp, vp)
+_sig(_p + "permutation", sz, sz, vp)
+_sig("yagi_hip_crc_host", ci, vp, sz, C.POINTER(C.c_uint32))
+for _n in ("scramble_data", "unscramble_data", "unscramble_data_soft"):
+    _sig("yagi_hip_" + _n, vp, sz)
+
 # ---- SymStream ---------------------------------------------------------------------------------
 _p = "yagi_hip_symstreamcf_"
 _sig(_p + "create_linear", ci, sz, sz, f32, ci, vp, pvp)

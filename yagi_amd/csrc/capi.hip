@@ -8975,6 +8975,248 @@ int yagi_hip_convcode_ncoded_host(int K, int R, const uint8_t *puncture, int p, 
 
 }  // extern "C"
 
+// ---- Packetizer (yagi_hip.h; src/random/scramble.rs for the mask) ------------------------------------------------------
+// As ConvCode: no call carries state; the object is its description, one table on the device and the staging of the host
+// forms.
+namespace yagi {
+
+// everything that needs no device
+struct PktHost : Packetizer {
+    ConvShape forced{0, 0};                                 // set_shape; fpw = 0: ConvCode's planner
+
+    int configure(size_t n_, int scheme_, int K_, const unsigned *g_, int R_, const uint8_t *puncture, int p_, int terminated_,
+                  size_t columns_, int scramble_) {
+        ConvHost c;
+        YG_TRY(c.configure(K_, g_, R_, puncture, p_, terminated_));
+        code = c;
+        if (!crc_params(scheme_, &crc)) return fail(YAGI_ERR_CONFIG, "packetizer: the CRC scheme %d is none of YAGI_CRC_*", scheme_);
+        if (n_ == 0) return fail(YAGI_ERR_CONFIG, "packetizer: a frame holds at least one payload byte");
+        if (columns_ < 1 || columns_ > (size_t)YAGI_PACKETIZER_COLUMNS_MAX)
+            return fail(YAGI_ERR_CONFIG, "packetizer: %zu columns are outside 1 .. YAGI_PACKETIZER_COLUMNS_MAX", columns_);
+        if (n_ > code.nmax() / 8 || 8 * (n_ + w()) > code.nmax())
+            return fail(YAGI_ERR_CONFIG, "packetizer: %zu payload and %zu CRC bytes are more than the code's %zu message bits", n_, w(),
+                        code.nmax());
+        scheme = scheme_, n = n_, columns = columns_, scramble = scramble_ != 0;
+        return YAGI_OK;
+    }
+    static int check_bps(unsigned bps) {
+        if (bps < 1 || bps > 8) return fail(YAGI_ERR_CONFIG, "packetizer: %u bits per symbol are outside 1 .. 8", bps);
+        return YAGI_OK;
+    }
+    // rows of a bytes in, rows of b bytes out; up to three planes of one element per frame
+    int check_block(size_t F, const void *in, size_t in_pitch, size_t a, const void *out, size_t out_pitch, size_t b,
+                    const uint8_t *valid, bool want_valid, const uint32_t *crcw, const uint32_t *metric) const {
+        if (F > (size_t)YAGI_CONVCODE_FRAMES_MAX) return fail(YAGI_ERR_CONFIG, "packetizer: %zu frames are more than YAGI_CONVCODE_FRAMES_MAX", F);
+        if (in_pitch < a || out_pitch < b)
+            return fail(YAGI_ERR_CONFIG, "packetizer: the pitches are in bytes, at least the row length (%zu in, %zu out)", a, b);
+        if (F == 0) return YAGI_OK;
+        if (!in || !out || (want_valid && !valid)) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+        if (((uintptr_t)crcw | (uintptr_t)metric) & 3) return fail(YAGI_ERR_CONFIG, "packetizer: the crc and metric words are 4-byte aligned");
+        const void *ptr[5] = {in, out, valid, crcw, metric};
+        const size_t len[5] = {(F - 1) * in_pitch + a, (F - 1) * out_pitch + b, F, F * sizeof(uint32_t), F * sizeof(uint32_t)};
+        for (int i = 0; i < 5; ++i)
+            for (int j = i + 1; j < 5; ++j)
+                if (ptr[i] && ptr[j]) YG_TRY(check_noalias(ptr[i], len[i], ptr[j], len[j]));
+        return YAGI_OK;
+    }
+    size_t steps() const { return code.steps(msg_bits()); }
+    ConvShape shape(size_t F) const { return forced.fpw ? forced : conv_plan(code.K, steps(), F); }
+    void fill_shape(ConvShape s, yagi_hip_convcode_shape *out) const {
+        out->frames_per_wave = s.fpw, out->waves = s.waves, out->states_per_lane = conv_spl(code.K), out->chunk_steps = conv_chunk(s);
+        out->frames_per_wg = (size_t)s.fpw * s.waves;
+        out->lds_bytes = pkt_lds_bytes(code.K, s, steps(), crc.width != 0);
+    }
+};
+
+struct PktObj : PktHost {
+    using Host = PktHost;
+    hipStream_t st = nullptr;
+    DevBuf tab, wv, wc, wm;                                 // the table; valid, crc and metric of a host call
+    Staging ws;
+
+    int alloc() {
+        YG_TRY(require_device());
+        std::vector<uint32_t> words(kPktTableWords);
+        pkt_table(*this, words.data());
+        return fill(tab, words.data(), words.size() * sizeof(uint32_t), st);
+    }
+    int ensure_host() { return YAGI_OK; }
+    int encode_dev(const uint8_t *payload, size_t pitch, size_t F, unsigned bps, uint8_t *tx, size_t tx_pitch) {
+        return launch_pkt_encode(*this, tab.as<uint32_t>(), payload, pitch, F, bps, tx, tx_pitch, st);
+    }
+    int decode_dev(const uint8_t *soft, size_t soft_pitch, size_t F, uint8_t *payload, size_t pitch, uint8_t *valid, uint32_t *crcw,
+                   uint32_t *metric) {
+        return launch_pkt_decode(*this, shape(F), tab.as<uint32_t>(), soft, soft_pitch, F, payload, pitch, valid, crcw, metric, st);
+    }
+};
+
+}  // namespace yagi
+
+struct yagi_hip_packetizer_s : PktObj {};
+
+extern "C" {
+
+int yagi_hip_packetizer_plan(int K, int terminated, size_t n, int crc, size_t F, yagi_hip_convcode_shape *plan) try {
+    CHECK_PTR(plan);
+    const unsigned ones[4] = {1, 1, 1, 1};                  // the arrangement does not depend on the generators
+    PktHost o;
+    YG_TRY(o.configure(n, crc, K, ones, 2, nullptr, 1, terminated, 1, 0));
+    if (F > (size_t)YAGI_CONVCODE_FRAMES_MAX) return fail(YAGI_ERR_CONFIG, "packetizer: %zu frames are more than YAGI_CONVCODE_FRAMES_MAX", F);
+    o.fill_shape(o.shape(F), plan);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_create(size_t n, int crc, int K, const unsigned *g, int R, const uint8_t *puncture, int p, int terminated,
+                               size_t columns, int scramble, yagi_hip_packetizer *q) try {
+    return bank_create(q, n, crc, K, g, R, puncture, p, terminated, columns, scramble);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_destroy(yagi_hip_packetizer q) try {
+    return bank_destroy(q);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_clone(yagi_hip_packetizer q, yagi_hip_packetizer *out) try {
+    return bank_clone(q, out);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_set_stream(yagi_hip_packetizer q, yagi_stream_t s) try {
+    return bank_set_stream(q, s);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_get_payload_len(yagi_hip_packetizer q, size_t *n) try {
+    return bank_get(q, n, [](auto &o) { return o.n; });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_get_crc_len(yagi_hip_packetizer q, size_t *w) try {
+    return bank_get(q, w, [](auto &o) { return o.w(); });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_get_msg_bits(yagi_hip_packetizer q, size_t *bits) try {
+    return bank_get(q, bits, [](auto &o) { return o.msg_bits(); });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_get_enc_len(yagi_hip_packetizer q, size_t *N) try {
+    return bank_get(q, N, [](auto &o) { return o.N(); });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_get_nsym(yagi_hip_packetizer q, unsigned bps, size_t *nsym) try {
+    CHECK_Q(q);
+    CHECK_PTR(nsym);
+    YG_TRY(PktHost::check_bps(bps));
+    *nsym = q->nsym(bps);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_get_columns(yagi_hip_packetizer q, size_t *columns) try {
+    return bank_get(q, columns, [](auto &o) { return o.columns; });
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_set_shape(yagi_hip_packetizer q, unsigned frames_per_wave, unsigned waves) try {
+    CHECK_Q(q);
+    if (frames_per_wave == 0 && waves == 0) {
+        q->forced = ConvShape{0, 0};
+        return YAGI_OK;
+    }
+    const ConvShape s{frames_per_wave, waves};
+    if (!conv_shape_ok(q->code.K, s))
+        return fail(YAGI_ERR_CONFIG, "packetizer: the shape (%u frames per wave, %u waves) is not admissible at K = %d",
+                    frames_per_wave, waves, q->code.K);
+    q->forced = s;
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_get_shape(yagi_hip_packetizer q, size_t F, yagi_hip_convcode_shape *shape) try {
+    CHECK_Q(q);
+    CHECK_PTR(shape);
+    q->fill_shape(q->shape(F), shape);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_encode_block_dev(yagi_hip_packetizer q, const uint8_t *payload_dev, size_t payload_pitch, size_t F,
+                                         unsigned bps, uint8_t *tx_dev, size_t tx_pitch) try {
+    CHECK_Q(q);
+    YG_TRY(PktHost::check_bps(bps));
+    YG_TRY(q->check_block(F, payload_dev, payload_pitch, q->n, tx_dev, tx_pitch, q->nsym(bps), nullptr, false, nullptr, nullptr));
+    return q->encode_dev(payload_dev, payload_pitch, F, bps, tx_dev, tx_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_decode_block_dev(yagi_hip_packetizer q, const uint8_t *soft_dev, size_t soft_pitch, size_t F,
+                                         uint8_t *payload_dev, size_t payload_pitch, uint8_t *valid_dev, uint32_t *crc_dev,
+                                         uint32_t *metric_dev) try {
+    CHECK_Q(q);
+    YG_TRY(q->check_block(F, soft_dev, soft_pitch, q->N(), payload_dev, payload_pitch, q->n, valid_dev, true, crc_dev, metric_dev));
+    return q->decode_dev(soft_dev, soft_pitch, F, payload_dev, payload_pitch, valid_dev, crc_dev, metric_dev);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_encode_block(yagi_hip_packetizer q, const uint8_t *payload, size_t payload_pitch, size_t F, unsigned bps,
+                                     uint8_t *tx, size_t tx_pitch) try {
+    CHECK_Q(q);
+    YG_TRY(PktHost::check_bps(bps));
+    const size_t a = q->n, b = q->nsym(bps);
+    YG_TRY(q->check_block(F, payload, payload_pitch, a, tx, tx_pitch, b, nullptr, false, nullptr, nullptr));
+    if (F == 0) return YAGI_OK;
+    YG_TRY(q->ws.put(q->st, payload, (F - 1) * payload_pitch + a));
+    YG_TRY(q->ws.y.ensure(F * b));
+    YG_TRY(q->encode_dev(q->ws.x.as<uint8_t>(), payload_pitch, F, bps, q->ws.y.as<uint8_t>(), b));
+    return download_rows(q->st, q->ws.y, F, b, tx, tx_pitch);
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_decode_block(yagi_hip_packetizer q, const uint8_t *soft, size_t soft_pitch, size_t F, uint8_t *payload,
+                                     size_t payload_pitch, uint8_t *valid, uint32_t *crc, uint32_t *metric) try {
+    CHECK_Q(q);
+    const size_t a = q->N(), b = q->n;
+    YG_TRY(q->check_block(F, soft, soft_pitch, a, payload, payload_pitch, b, valid, true, crc, metric));
+    if (F == 0) return YAGI_OK;
+    YG_TRY(q->ws.put(q->st, soft, (F - 1) * soft_pitch + a));
+    YG_TRY(q->ws.y.ensure(F * b));
+    YG_TRY(q->wv.ensure(F));
+    if (crc) YG_TRY(q->wc.ensure(F * sizeof(uint32_t)));
+    if (metric) YG_TRY(q->wm.ensure(F * sizeof(uint32_t)));
+    YG_TRY(q->decode_dev(q->ws.x.as<uint8_t>(), soft_pitch, F, q->ws.y.as<uint8_t>(), b, q->wv.as<uint8_t>(),
+                         crc ? q->wc.as<uint32_t>() : nullptr, metric ? q->wm.as<uint32_t>() : nullptr));
+    YG_TRY(download_rows(q->st, q->ws.y, F, b, payload, payload_pitch));
+    YG_TRY(download(valid, q->wv.p, F, q->st));
+    if (crc) YG_TRY(download(crc, q->wc.p, F * sizeof(uint32_t), q->st));
+    return metric ? download(metric, q->wm.p, F * sizeof(uint32_t), q->st) : YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_encode_host(size_t n, int crc, int K, const unsigned *g, int R, const uint8_t *puncture, int p,
+                                    int terminated, size_t columns, int scramble, const uint8_t *payload, size_t payload_pitch,
+                                    size_t F, unsigned bps, uint8_t *tx, size_t tx_pitch) try {
+    PktHost o;
+    YG_TRY(o.configure(n, crc, K, g, R, puncture, p, terminated, columns, scramble));
+    YG_TRY(PktHost::check_bps(bps));
+    YG_TRY(o.check_block(F, payload, payload_pitch, o.n, tx, tx_pitch, o.nsym(bps), nullptr, false, nullptr, nullptr));
+    pkt_encode_host(o, payload, payload_pitch, F, bps, tx, tx_pitch);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_decode_host(size_t n, int crc, int K, const unsigned *g, int R, const uint8_t *puncture, int p,
+                                    int terminated, size_t columns, int scramble, const uint8_t *soft, size_t soft_pitch, size_t F,
+                                    uint8_t *payload, size_t payload_pitch, uint8_t *valid, uint32_t *crc_out, uint32_t *metric) try {
+    PktHost o;
+    YG_TRY(o.configure(n, crc, K, g, R, puncture, p, terminated, columns, scramble));
+    YG_TRY(o.check_block(F, soft, soft_pitch, o.N(), payload, payload_pitch, o.n, valid, true, crc_out, metric));
+    pkt_decode_host(o, soft, soft_pitch, F, payload, payload_pitch, valid, crc_out, metric);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_crc_host(int scheme, const uint8_t *data, size_t n, uint32_t *crc) try {
+    CHECK_PTR(crc);
+    CrcParams c;
+    if (!crc_params(scheme, &c)) return fail(YAGI_ERR_CONFIG, "crc: the scheme %d is none of YAGI_CRC_*", scheme);
+    if (n && !data) return fail(YAGI_ERR_CONFIG, "null pointer argument");
+    *crc = crc_host(c, data, n);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_packetizer_permutation(size_t N, size_t columns, uint32_t *pi) try {
+    if (columns < 1 || columns > (size_t)YAGI_PACKETIZER_COLUMNS_MAX)
+        return fail(YAGI_ERR_CONFIG, "packetizer: %zu columns are outside 1 .. YAGI_PACKETIZER_COLUMNS_MAX", columns);
+    if (N > ((size_t)1 << 31)) return fail(YAGI_ERR_CONFIG, "packetizer: the positions of %zu bits do not fit the words", N);
+    if (N == 0) return YAGI_OK;
+    CHECK_PTR(pi);
+    pkt_permutation(N, columns, pi);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_scramble_data(uint8_t *x, size_t n) try {
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    scramble_data_host(x, n);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_unscramble_data(uint8_t *x, size_t n) try {
+    return yagi_hip_scramble_data(x, n);                    // scramble.rs :31-34
+} catch (...) { return ::yagi::api_exception(); }
+int yagi_hip_unscramble_data_soft(uint8_t *x, size_t n) try {
+    if (n == 0) return YAGI_OK;
+    CHECK_PTR(x);
+    unscramble_soft_host(x, n);
+    return YAGI_OK;
+} catch (...) { return ::yagi::api_exception(); }
+
+}  // extern "C"
+
 // ---- MSequence (src/sequence/msequence.rs) -------------------------------------------------------------------------
 // The state is one word and lives on the host alone.  The device holds only the object's two tables of jump matrices
 // (sequence_kernels.hip); a block call hands the state to the kernel by value and then advances the host word by the

@@ -940,4 +940,55 @@ void conv_encode_host(const ConvCode &c, const uint8_t *msg, size_t msg_pitch, s
 void conv_decode_host(const ConvCode &c, const uint8_t *soft, size_t soft_pitch, size_t n, size_t F, uint8_t *msg,
                       size_t msg_pitch, uint32_t *metric);
 
+// ---- packetizer_kernels.hip ----------------------------------------------------------------
+// Packetizer (yagi_hip.h): n payload bytes, a CRC of w bytes behind them, ConvCode over the 8 (n + w) message bits, a block
+// interleaver of `columns` columns over the N coded bits and the scrambler's mask; F frames per call, one per row.
+struct CrcParams {
+    int width;                                         // 0, 8, 16, 24, 32
+    uint32_t poly, init, xorout;
+    bool reflected;                                    // input bytes and the result
+};
+bool crc_params(int scheme, CrcParams *out);           // YAGI_CRC_*; false where the scheme is none of them
+uint32_t crc_host(const CrcParams &c, const uint8_t *data, size_t n);
+struct Packetizer {
+    ConvCode code;
+    CrcParams crc{};
+    int scheme = 0;
+    size_t n = 0, columns = 1;
+    bool scramble = true;
+    size_t w() const { return (size_t)crc.width / 8; }
+    size_t msg_bits() const { return 8 * (n + w()); }
+    size_t N() const { return code.ncoded(msg_bits()); }
+    size_t nsym(unsigned bps) const { return (N() + bps - 1) / bps; }
+    size_t cols() const { return columns < N() ? columns : N(); }      // C >= N is the identity, as C = N is
+};
+// the device image: ConvCode's table; the coded index within a period -> step | output << 8; the encoder's per-lane powers
+// x^(8 * bytes behind the lane's slice) mod P; the decoder's (T[i], i) pairs for the CRC register run backwards
+constexpr size_t kPktInvAt = kConvTableWords, kPktInvWords = 4 * YAGI_CONVCODE_PERIOD_MAX;
+constexpr size_t kPktZAt = kPktInvAt + kPktInvWords, kPktZWords = 256;
+constexpr size_t kPktRevAt = kPktZAt + kPktZWords, kPktRevWords = 512;
+constexpr size_t kPktTableWords = kPktRevAt + kPktRevWords;
+constexpr size_t pkt_slice(size_t n) { return (n + kPktZWords - 1) / kPktZWords; }     // payload bytes per encoder lane
+// per wave: the decisions and the expanded steps (no raw words); per workgroup ConvCode's table and, with a CRC, the pairs
+constexpr size_t pkt_wave_bytes(int K, ConvShape s, size_t T) {
+    return ((T * conv_step_bytes(K, s) + 7) & ~(size_t)7) + (size_t)kConvStage * 8;
+}
+constexpr size_t pkt_lds_bytes(int K, ConvShape s, size_t T, bool with_crc) {
+    return kConvTableWords * 4 + s.waves * pkt_wave_bytes(K, s, T) + (with_crc ? kPktRevWords * 4 : 0);
+}
+void pkt_table(const Packetizer &k, uint32_t *words);  // kPktTableWords words
+void pkt_permutation(size_t N, size_t C, uint32_t *pi);                // pi[i], the transmit position of coder-order bit i
+void scramble_data_host(uint8_t *x, size_t n);         // scramble.rs scramble_data (= unscramble_data)
+void unscramble_soft_host(uint8_t *x, size_t n);       // scramble.rs unscramble_data_soft
+// device forms; tab = pkt_table's image on the device; the decoder runs at ConvCode's arrangement s
+int launch_pkt_encode(const Packetizer &k, const uint32_t *tab, const uint8_t *payload, size_t payload_pitch, size_t F,
+                      unsigned bps, uint8_t *tx, size_t tx_pitch, hipStream_t st);
+int launch_pkt_decode(const Packetizer &k, ConvShape s, const uint32_t *tab, const uint8_t *soft, size_t soft_pitch, size_t F,
+                      uint8_t *payload, size_t payload_pitch, uint8_t *valid, uint32_t *crc, uint32_t *metric, hipStream_t st);
+// the definition's loops on the host, around conv_encode_host / conv_decode_host
+void pkt_encode_host(const Packetizer &k, const uint8_t *payload, size_t payload_pitch, size_t F, unsigned bps, uint8_t *tx,
+                     size_t tx_pitch);
+void pkt_decode_host(const Packetizer &k, const uint8_t *soft, size_t soft_pitch, size_t F, uint8_t *payload,
+                     size_t payload_pitch, uint8_t *valid, uint32_t *crc, uint32_t *metric);
+
 }  // namespace yagi
