@@ -15,6 +15,8 @@
 // In place (y == x at the same pitch) is safe: a lane reads its sample of a row before it writes it, and touches no
 // other lane's.  A bank of few channels uses few lanes of its one wave.  Accepted.
 //
+// The launch is bank_launch (bank_lane.hpp); the kernel keeps its own prefetch: on RowQueue the instances that write
+// the status plane without squelch ran 4.5 % longer (profiles/r29_kbench_bank_lanes.txt).
 // The host form lives here too, with the array forms of the words: host.cpp and capi.hip are built with contraction on.
 #pragma clang fp contract(off)
 
@@ -22,6 +24,7 @@
 
 #include "agc_body.hpp"       // agc_step and its helpers: shared with symtrack_kernels.hip
 #include "agc_words.hpp"
+#include "bank_lane.hpp"
 #include "devmath.hpp"
 #include "kernels.hpp"
 
@@ -87,10 +90,7 @@ __global__ __launch_bounds__(kAgcWg) void agc_init_kernel(const T *x, size_t x_p
 
 template <class T, bool SQUELCH, bool STATUS>
 int agc_launch(const AgcArgs<T> &a, hipStream_t st) {
-    const unsigned grid = (unsigned)((a.C + kAgcWg - 1) / kAgcWg);
-    hipLaunchKernelGGL((agc_kernel<T, SQUELCH, STATUS>), dim3(grid), dim3(kAgcWg), 0, st, a);
-    YG_LAUNCH_CHECK();
-    return YAGI_OK;
+    return bank_launch(agc_kernel<T, SQUELCH, STATUS>, a.C, kAgcWg, kAgcWg, 0, st, a);
 }
 
 }  // namespace
@@ -113,10 +113,7 @@ template int launch_agc<float>(const AgcSettings &, AgcChan *, size_t, const flo
 
 template <class T>
 int launch_agc_init(const T *x, size_t x_pitch, size_t n, size_t C, float *sum, hipStream_t st) {
-    const unsigned grid = (unsigned)((C + kAgcWg - 1) / kAgcWg);
-    hipLaunchKernelGGL(agc_init_kernel<T>, dim3(grid), dim3(kAgcWg), 0, st, x, x_pitch, (unsigned)n, C, sum);
-    YG_LAUNCH_CHECK();
-    return YAGI_OK;
+    return bank_launch(agc_init_kernel<T>, C, kAgcWg, kAgcWg, 0, st, x, x_pitch, (unsigned)n, C, sum);
 }
 template int launch_agc_init<cf32>(const cf32 *, size_t, size_t, size_t, float *, hipStream_t);
 template int launch_agc_init<float>(const float *, size_t, size_t, size_t, float *, hipStream_t);

@@ -24,11 +24,15 @@
 // count differs between lanes only after reset_channel(c); the buf_full gate and execute_block's update test are per
 // lane for that reason and uniform otherwise.  A bank of few channels uses few lanes of its one wave.  Accepted.
 //
+// The launch is bank_launch and the host form fills and stores its window through Ring (bank_lane.hpp).  The kernel keeps
+// its own prefetch and ring: on RowQueue alone DECISION ran 0.4 to 1 % longer (the other four up to 10 % shorter), on Ring
+// alone NONE and DECISION 5 to 13 % longer (profiles/r29_kbench_bank_lanes.txt).
 // The host form lives here too: host.cpp is built with contraction on.
 #pragma clang fp contract(off)
 
 #include <cmath>
 
+#include "bank_lane.hpp"
 #include "eqlms_body.hpp"     // eq_push .. eq_desired: shared with symtrack_kernels.hip
 #include "kernels.hpp"
 
@@ -157,14 +161,7 @@ __global__ __launch_bounds__(kEqlmsWg) void eqlms_cccf_kernel(const EqArgs a) {
 
 template <int CALL>
 int eq_launch(const EqArgs &a, hipStream_t st) {
-    const size_t need = eqlms_lds_bytes(a.h_len);
-    auto fn = eqlms_cccf_kernel<CALL>;
-    if (need > 64 * 1024)
-        YG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    const unsigned grid = (unsigned)((a.C + kEqlmsWg - 1) / kEqlmsWg);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kEqlmsWg), need, st, a);
-    YG_LAUNCH_CHECK();
-    return YAGI_OK;
+    return bank_launch(eqlms_cccf_kernel<CALL>, a.C, kEqlmsWg, kEqlmsWg, eqlms_lds_bytes(a.h_len), st, a);
 }
 
 }  // namespace
@@ -192,45 +189,39 @@ void eqlms_host(int call, size_t h_len_, float mu, cf32 *w, cf32 *hist, EqlmsCha
                 size_t x_pitch, size_t n, const cf32 *d, size_t d_pitch, const cf32 *table, size_t M, cf32 *y,
                 size_t y_pitch) {
     const unsigned h_len = (unsigned)h_len_, k = (unsigned)k_;
-    std::vector<cf32> ring(h_len), wv(h_len);
+    std::vector<cf32> rv(h_len), wv(h_len);
     for (size_t c = 0; c < C; ++c) {
         EqlmsChan s = state[c];
-        for (unsigned j = 0; j < h_len; ++j) {
-            ring[j] = hist[(size_t)j * C + c];
-            wv[j] = w[(size_t)j * C + c];
-        }
-        unsigned head = 0;
+        Ring<cf32> ring{rv.data(), 1, h_len, 0};
+        ring.fill(hist, C, c);
+        for (unsigned j = 0; j < h_len; ++j) wv[j] = w[(size_t)j * C + c];
         for (size_t row = 0; row < n; ++row) {
-            eq_push(ring.data(), 1, head, h_len, x[row * x_pitch + c], s.x2_sum);
+            eq_push(ring.col, 1, ring.head, h_len, x[row * x_pitch + c], s.x2_sum);
             s.count += 1;
             const bool full = s.count >= h_len;
             if (call == kEqlmsExec) {
-                const cf32 yv = eq_execute(ring.data(), wv.data(), 1, head, h_len);
+                const cf32 yv = eq_execute(ring.col, wv.data(), 1, ring.head, h_len);
                 y[row * y_pitch + c] = yv;
                 if ((s.count + k - 1) % k == 0 && full)
-                    eq_step(ring.data(), wv.data(), 1, head, h_len, mu, s.x2_sum, eq_unit(yv, 1.0), yv, 1.0);
+                    eq_step(ring.col, wv.data(), 1, ring.head, h_len, mu, s.x2_sum, eq_unit(yv, 1.0), yv, 1.0);
             } else if (row % k == 0) {
                 const size_t sym = row / k;
-                const cf32 yv = eq_execute(ring.data(), wv.data(), 1, head, h_len);
+                const cf32 yv = eq_execute(ring.col, wv.data(), 1, ring.head, h_len);
                 y[sym * y_pitch + c] = yv;
                 for (unsigned u = 1; u < k; ++u) {          // the symbol's k - 1 trailing pushes, then one update
                     ++row;
-                    eq_push(ring.data(), 1, head, h_len, x[row * x_pitch + c], s.x2_sum);
+                    eq_push(ring.col, 1, ring.head, h_len, x[row * x_pitch + c], s.x2_sum);
                     s.count += 1;
                 }
                 if (call != YAGI_EQLMS_NONE && s.count >= h_len) {
                     const cf32 dk = call == YAGI_EQLMS_TRAIN ? d[sym * d_pitch + c] : cf32{0.0f, 0.0f};
-                    eq_step(ring.data(), wv.data(), 1, head, h_len, mu, s.x2_sum, eq_desired(call, yv, dk, table, (unsigned)M, 1.0),
-                            yv, 1.0);
+                    eq_step(ring.col, wv.data(), 1, ring.head, h_len, mu, s.x2_sum,
+                            eq_desired(call, yv, dk, table, (unsigned)M, 1.0), yv, 1.0);
                 }
             }
         }
-        for (unsigned j = 0; j < h_len; ++j) {
-            unsigned sl = head + j;
-            sl = sl >= h_len ? sl - h_len : sl;
-            hist[(size_t)j * C + c] = ring[sl];
-            w[(size_t)j * C + c] = wv[j];
-        }
+        ring.store(hist, C, c);
+        for (unsigned j = 0; j < h_len; ++j) w[(size_t)j * C + c] = wv[j];
         state[c] = s;
     }
 }

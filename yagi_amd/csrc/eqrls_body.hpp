@@ -7,6 +7,7 @@
 // rows t, t + L, t + 2 L ...  Lanes hand finished values to each other through the arrays of RlsView and `sync()`; there
 // is no cross-lane reduction.  Element e of an array of the view is at [e * stride].
 #pragma once
+#include "bank_lane.hpp"
 #include "eqlms_body.hpp"     // eq_quot, eq_window, eq_desired
 
 namespace yagi {
@@ -14,7 +15,8 @@ namespace {
 
 struct RlsView {
     cf32 *P0, *P1;            // the recursion matrix and the buffer its successor is written to, [p][pp] each
-    cf32 *ring, *w;           // the window (a ring, oldest sample at `head`) and w0, [p] each
+    Ring<cf32> ring;          // the window, [p], at the arrays' stride
+    cf32 *w;                  // w0, [p]
     cf32 *xp0, *g, *row;      // [p], [p] and two rows of gxl, [2][p]
     unsigned stride, p, pp;   // pp: the row pitch of P0 and P1 in elements
 };
@@ -28,18 +30,11 @@ EQ_HD cf32 rls_quot(cf32 a, cf32 b, float n, double one) {
     return cf32{eq_quot(re, n, one), eq_quot(im, n, one)};
 }
 
-// the i-th oldest sample of the window
-EQ_HD cf32 rls_x(const RlsView v, unsigned head, unsigned i) {
-    unsigned sl = head + i;
-    sl = sl >= v.p ? sl - v.p : sl;
-    return v.ring[sl * v.stride];
-}
-
 // execute (:106-110): y = sum_i w0[i] r[i], no conjugate, folded from Complex(0, 0); every lane forms it
-EQ_HD cf32 rls_execute(const RlsView v, unsigned head) {
+EQ_HD cf32 rls_execute(const RlsView v) {
     float yr = 0.0f, yi = 0.0f;
-    eq_window(head, v.p, [&](unsigned i, unsigned sl) {
-        const cf32 t = rls_mul(v.w[i * v.stride], v.ring[sl * v.stride]);
+    eq_window(v.ring.head, v.p, [&](unsigned i, unsigned sl) {
+        const cf32 t = rls_mul(v.w[i * v.stride], v.ring.col[sl * v.stride]);
         yr = yr + t.re;
         yi = yi + t.im;
     });
@@ -49,14 +44,14 @@ EQ_HD cf32 rls_execute(const RlsView v, unsigned head) {
 // step(d, d_hat) (:112-146).  On entry every lane of the group has finished rls_execute; on return P1 is the new matrix
 // (the caller lets the two buffers change places, rls_swap), w the new weights, and every lane may read them.
 template <class Sync>
-EQ_HD void rls_step(const RlsView v, unsigned head, unsigned t, unsigned L, float lambda, cf32 d, cf32 y, double one, Sync sync) {
+EQ_HD void rls_step(const RlsView v, unsigned t, unsigned L, float lambda, cf32 d, cf32 y, double one, Sync sync) {
     const unsigned p = v.p, pp = v.pp, S = v.stride;
     const cf32 alpha{d.re - y.re, d.im - y.im};
     // xp0[c] = sum_r x[r] P0[r][c] for the lane's columns; the numerators of g for its rows
     for (unsigned c = t; c < p; c += L) {
         float sr = 0.0f, si = 0.0f, gr = 0.0f, gi = 0.0f;
         for (unsigned r = 0; r < p; ++r) {
-            const cf32 xr = rls_x(v, head, r);
+            const cf32 xr = v.ring(r);
             const cf32 a = rls_mul(xr, v.P0[(r * pp + c) * S]);
             sr = sr + a.re;
             si = si + a.im;
@@ -71,7 +66,7 @@ EQ_HD void rls_step(const RlsView v, unsigned head, unsigned t, unsigned L, floa
     // zeta = (sum_c xp0[c] conj(x[c])) + Complex(lambda, 0): p terms, formed by every lane
     float zr = 0.0f, zi = 0.0f;
     for (unsigned c = 0; c < p; ++c) {
-        const cf32 a = rls_mul(v.xp0[c * S], rls_conj(rls_x(v, head, c)));
+        const cf32 a = rls_mul(v.xp0[c * S], rls_conj(v.ring(c)));
         zr = zr + a.re;
         zi = zi + a.im;
     }
@@ -93,7 +88,7 @@ EQ_HD void rls_step(const RlsView v, unsigned head, unsigned t, unsigned L, floa
     for (unsigned r = 0; r < p; ++r) {
         cf32 *row = v.row + (r & 1u) * p * S;
         const cf32 gr = v.g[r * S];
-        for (unsigned i = t; i < p; i += L) row[i * S] = rls_quot(rls_mul(gr, rls_x(v, head, i)), lam, ln, one);
+        for (unsigned i = t; i < p; i += L) row[i * S] = rls_quot(rls_mul(gr, v.ring(i)), lam, ln, one);
         sync();
         for (unsigned c = t; c < p; c += L) {
             float sr = 0.0f, si = 0.0f;

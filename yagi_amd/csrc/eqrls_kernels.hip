@@ -23,8 +23,9 @@
 // so the L / 2 groups' worth of t inside a 32-lane half fall on different banks.  State is read from and written back to
 // the object's [element][channel] arrays once per call.
 //
-// Input rows are requested a chunk of kEqrlsAhead ahead into the registers of each group's lane 0 and staged in LDS;
-// TRAIN's symbol is requested one symbol ahead by every lane of the group (one address per group), behind a step that
+// Input rows go through the bank kernels' row queue (bank_lane.hpp) in chunks of kEqrlsAhead, held and staged by each
+// group's lane 0; the window is that header's Ring at stride G, written by lane 0 and advanced by every lane.  TRAIN's
+// symbol is requested one symbol ahead by every lane of the group (one address per group), behind a step that
 // is much longer than the round trip.  Control flow is uniform across the wave: a group beyond the last channel runs on
 // zeros and stores nothing.
 //
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(kEqrlsWg) void eqrls_cccf_kernel(const RlsArgs a) {
     v.stride = G, v.p = p, v.pp = pp;
     v.P0 = base, base += (size_t)p * pp * G;
     v.P1 = base, base += (size_t)p * pp * G;
-    v.ring = base, base += (size_t)p * G;
+    v.ring = Ring<cf32>{base, G, p, 0}, base += (size_t)p * G;
     v.w = base, base += (size_t)p * G;
     v.xp0 = base, base += (size_t)p * G;
     v.g = base, base += (size_t)p * G;
@@ -83,44 +84,31 @@ __global__ __launch_bounds__(kEqrlsWg) void eqrls_cccf_kernel(const RlsArgs a) {
     const bool act = c < a.C, first = act && t == 0;
     for (unsigned r = 0; r < p; ++r)
         for (unsigned j = t; j < p; j += L) v.P0[(r * pp + j) * G] = act ? a.P[((size_t)r * p + j) * a.C + c] : cf32{0.0f, 0.0f};
-    for (unsigned j = t; j < p; j += L) {
-        v.ring[j * G] = act ? a.hist[(size_t)j * a.C + c] : cf32{0.0f, 0.0f};
-        v.w[j * G] = act ? a.w0[(size_t)j * a.C + c] : cf32{0.0f, 0.0f};
-    }
-    unsigned head = 0;                                      // the oldest slot, where the next sample goes
+    for (unsigned j = t; j < p; j += L) v.w[j * G] = act ? a.w0[(size_t)j * a.C + c] : cf32{0.0f, 0.0f};
+    v.ring.fill(a.hist, a.C, c, act, t, L);
     unsigned dp = 0, sym = 0;                               // the row's place in its symbol, the symbol
     const unsigned nsym = a.n / k;
 
-    cf32 xq[kEqrlsAhead];
-#pragma unroll
-    for (int u = 0; u < kEqrlsAhead; ++u) xq[u] = first && (unsigned)u < a.n ? a.x[(size_t)u * a.x_pitch + c] : cf32{0.0f, 0.0f};
+    auto load = [&](size_t row, bool in_range) { return first && in_range ? a.x[row * a.x_pitch + c] : cf32{0.0f, 0.0f}; };
+    RowQueue<cf32, kEqrlsAhead> xq;                         // held by each group's lane 0
+    xq.prime(a.n, load);
     cf32 dnext = MODE == YAGI_EQRLS_TRAIN && act && nsym ? a.d[c] : cf32{0.0f, 0.0f};
     rls_sync();
 
     for (unsigned s0 = 0; s0 < a.n; s0 += kEqrlsAhead) {
-        if (t == 0) {
-#pragma unroll
-            for (int u = 0; u < kEqrlsAhead; ++u) stage[u * G] = xq[u];
-        }
-#pragma unroll
-        for (int u = 0; u < kEqrlsAhead; ++u) {
-            const size_t ahead = (size_t)s0 + kEqrlsAhead + u;
-            xq[u] = first && ahead < a.n ? a.x[ahead * a.x_pitch + c] : cf32{0.0f, 0.0f};
-        }
-        const unsigned steps = a.n - s0 < (unsigned)kEqrlsAhead ? a.n - s0 : (unsigned)kEqrlsAhead;
+        const unsigned steps = xq.next(s0, a.n, lane_stage(stage, G, t == 0), load);
         for (unsigned u = 0; u < steps; ++u) {
-            if (t == 0) v.ring[head * G] = stage[u * G];    // push: the oldest sample leaves
-            head = head + 1 == p ? 0 : head + 1;
+            v.ring.push(stage[u * G], t == 0);              // the oldest sample leaves; lane 0 of the group writes
             rls_sync();
             if (dp == 0) {                                  // the symbol's first row: execute, then the update
-                const cf32 yv = rls_execute(v, head);
+                const cf32 yv = rls_execute(v);
                 if (first) a.y[(size_t)sym * a.y_pitch + c] = yv;
                 if (MODE != YAGI_EQRLS_NONE) {
                     const cf32 dk = dnext;
                     if (MODE == YAGI_EQRLS_TRAIN)
                         dnext = act && sym + 1 < nsym ? a.d[(size_t)(sym + 1) * a.d_pitch + c] : cf32{0.0f, 0.0f};
                     rls_sync();                             // every lane has its y before a lane writes w
-                    rls_step(v, head, t, L, a.lambda, eq_desired(MODE, yv, dk, tl, a.M, a.one), yv, a.one,
+                    rls_step(v, t, L, a.lambda, eq_desired(MODE, yv, dk, tl, a.M, a.one), yv, a.one,
                              [] { rls_sync(); });
                     rls_swap(v);
                 }
@@ -135,10 +123,8 @@ __global__ __launch_bounds__(kEqrlsWg) void eqrls_cccf_kernel(const RlsArgs a) {
     for (unsigned r = 0; r < p; ++r)
         for (unsigned j = t; j < p; j += L) a.P[((size_t)r * p + j) * a.C + c] = v.P0[(r * pp + j) * G];
     const bool stepped = MODE != YAGI_EQRLS_NONE && nsym != 0;
-    for (unsigned j = t; j < p; j += L) {                   // the window, oldest first, and the weights
-        unsigned sl = head + j;
-        sl = sl >= p ? sl - p : sl;
-        a.hist[(size_t)j * a.C + c] = v.ring[sl * G];
+    v.ring.store(a.hist, a.C, c, t, L);
+    for (unsigned j = t; j < p; j += L) {
         const cf32 w = v.w[j * G];
         a.w0[(size_t)j * a.C + c] = w;
         if (stepped) a.w1[(size_t)j * a.C + c] = w;         // step leaves w1 = w0 (:140-143)
@@ -148,14 +134,7 @@ __global__ __launch_bounds__(kEqrlsWg) void eqrls_cccf_kernel(const RlsArgs a) {
 template <int MODE>
 int rls_launch(const RlsArgs &a, hipStream_t st) {
     const size_t L = (size_t)1 << a.lgL, G = kEqrlsWg / L;
-    const size_t need = eqrls_lds_bytes(a.p, L);
-    auto fn = eqrls_cccf_kernel<MODE>;
-    if (need > 64 * 1024)
-        YG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    const unsigned grid = (unsigned)((a.C + G - 1) / G);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kEqrlsWg), need, st, a);
-    YG_LAUNCH_CHECK();
-    return YAGI_OK;
+    return bank_launch(eqrls_cccf_kernel<MODE>, a.C, G, kEqrlsWg, eqrls_lds_bytes(a.p, L), st, a);
 }
 
 }  // namespace
@@ -188,31 +167,25 @@ void eqrls_host(int mode, size_t p_, float lambda, cf32 *P, cf32 *w0, cf32 *w1, 
     std::vector<cf32> Pa((size_t)p * p), Pb((size_t)p * p), ring(p), wv(p), xp0(p), gv(p), row(2 * (size_t)p);
     for (size_t c = 0; c < C; ++c) {
         for (size_t e = 0; e < (size_t)p * p; ++e) Pa[e] = P[e * C + c];
-        for (unsigned j = 0; j < p; ++j) {
-            ring[j] = hist[(size_t)j * C + c];
-            wv[j] = w0[(size_t)j * C + c];
-        }
-        RlsView v{Pa.data(), Pb.data(), ring.data(), wv.data(), xp0.data(), gv.data(), row.data(), 1, p, p};
-        unsigned head = 0;
+        for (unsigned j = 0; j < p; ++j) wv[j] = w0[(size_t)j * C + c];
+        RlsView v{Pa.data(), Pb.data(), Ring<cf32>{ring.data(), 1, p, 0}, wv.data(), xp0.data(), gv.data(), row.data(), 1, p, p};
+        v.ring.fill(hist, C, c);
         bool stepped = false;
         for (size_t r = 0; r < n; ++r) {
-            ring[head] = x[r * x_pitch + c];
-            head = head + 1 == p ? 0 : head + 1;
+            v.ring.push(x[r * x_pitch + c]);
             if (r % k != 0) continue;
             const size_t sym = r / k;
-            const cf32 yv = rls_execute(v, head);
+            const cf32 yv = rls_execute(v);
             y[sym * y_pitch + c] = yv;
             if (mode == YAGI_EQRLS_NONE) continue;
             const cf32 dk = mode == YAGI_EQRLS_TRAIN ? d[sym * d_pitch + c] : cf32{0.0f, 0.0f};
-            rls_step(v, head, 0, 1, lambda, eq_desired(mode, yv, dk, table, (unsigned)M, 1.0), yv, 1.0, [] {});
+            rls_step(v, 0, 1, lambda, eq_desired(mode, yv, dk, table, (unsigned)M, 1.0), yv, 1.0, [] {});
             rls_swap(v);
             stepped = true;
         }
         for (size_t e = 0; e < (size_t)p * p; ++e) P[e * C + c] = v.P0[e];
+        v.ring.store(hist, C, c);
         for (unsigned j = 0; j < p; ++j) {
-            unsigned sl = head + j;
-            sl = sl >= p ? sl - p : sl;
-            hist[(size_t)j * C + c] = ring[sl];
             w0[(size_t)j * C + c] = wv[j];
             if (stepped) w1[(size_t)j * C + c] = wv[j];
         }

@@ -1,9 +1,11 @@
-// symsync_body.hpp -- the per-output arithmetic of SymSync (one iteration of step's while loop, symsync.rs:230-276),
-// shared by symsync_kernels.hip and symtrack_kernels.hip.  Both files are built with -ffp-contract=off (Makefile): every
+// symsync_body.hpp -- SymSync's input row (step, symsync.rs:230-266: ss_row) and its per-output arithmetic (one iteration
+// of step's while loop, :230-276: ss_output), shared by the kernels and the host forms of symsync_kernels.hip and
+// symtrack_kernels.hip.  Both files are built with -ffp-contract=off (Makefile): every
 // product and add of the sums and of the loop filter keeps its own rounding.
 #pragma once
 #include <cmath>
 
+#include "bank_lane.hpp"
 #include "kernels.hpp"
 
 namespace yagi {
@@ -81,6 +83,46 @@ __host__ __device__ __forceinline__ cf32 ss_output(SymsyncChan &s, const Symsync
     s.bf = s.tau * p.npfbf;
     s.b = ss_round_usize(s.bf);
     return y;
+}
+
+// One input row x of a channel: push, then every output that falls into this row, then the advance of tau, bf and b.
+//   stall       the channel's stall code, 0 while it runs; a stalled channel's row does nothing but push (its column is dead)
+//   room        outputs that still fit at the row's start: the loop is counted, 2 room + 1, so it ends whatever the state holds
+//   any(m)      whether the select of ss_output<true> is needed: the host forms pass m through, a wave asks all of its lanes
+//   full()      the capacity rule: an iteration about to store an output that does not fit does not run (stall = cap_code)
+//   emit(y)     takes the output and returns 0, or the stall code that ends the channel's call behind this output
+//   on_stall()  runs at the moment the channel stalls: the kernels write the window out, it is as the history has to keep it
+template <class Stall, class Count, class Any, class Full, class Emit, class OnStall>
+__host__ __device__ __forceinline__ void ss_row(SymsyncChan &s, const SymsyncLoop &p, Ring<cf32> &win, const SsTap *taps,
+                                                cf32 x, Stall &stall, Stall cap_code, Count room, double zero, Any any,
+                                                Full full, Emit emit, OnStall on_stall) {
+    win.push(x);                                            // mf.push(x); dmf.push(x)
+    if (!stall && s.since < p.Ls) s.since += 1;
+    const unsigned z = p.Ls - s.since;
+    const bool young = any(!stall && z != 0);
+    Count budget = 2 * room + 1;
+    while (!stall && s.b < p.npfb) {
+        if (budget == 0 || full()) {                        // budget == 0 cannot happen
+            stall = cap_code;
+            on_stall();
+            break;
+        }
+        --budget;
+        const SsTap *row = taps + (size_t)s.b * p.Ls;
+        auto tap = [&](unsigned j) { return row[j]; };
+        const cf32 y = young ? ss_output<true>(s, p, z, win, tap, zero) : ss_output<false>(s, p, z, win, tap, zero);
+        const Stall code = emit(y);
+        if (code) {
+            stall = code;
+            on_stall();
+            break;
+        }
+    }
+    if (!stall) {
+        s.tau = s.tau - 1.0f;
+        s.bf = s.bf - p.npfbf;
+        s.b -= p.npfb;
+    }
 }
 
 }  // namespace

@@ -25,13 +25,16 @@
 // Capacity: an iteration about to store output number ycap does not run; the lane stalls, writes its window out at once
 // and does nothing more.  The inner loop is also counted, 2 (ycap - ny) + 1 per step, so it ends whatever the state holds.
 //
+// The ring, the row queue and the launch are bank_lane.hpp's, in the kernel and in the host form; the host form's row is
+// ss_row (symsync_body.hpp).  The kernel spells its row out: on ss_row it ran 2 to 4 % longer
+// (profiles/r29_kbench_bank_lanes.txt).
 // The host form lives here too: host.cpp is built with contraction on.
 #pragma clang fp contract(off)
 
 #include <cmath>
 
 #include "kernels.hpp"
-#include "symsync_body.hpp"   // SsTap, ss_output: shared with symtrack_kernels.hip
+#include "symsync_body.hpp"   // SsTap, ss_row, ss_output: shared with symtrack_kernels.hip
 
 namespace yagi {
 namespace {
@@ -63,45 +66,22 @@ __global__ __launch_bounds__(kSymsyncWg) void symsync_crcf_kernel(const SsArgs a
     s.stalled = 1;                                          // a lane beyond the last channel does nothing
     if (live) s = a.state[c];
     const bool was_stalled = s.stalled != 0;
-    for (unsigned j = 0; j < Ls; ++j) ring[j * kSymsyncWg + lane] = live ? a.hist[(size_t)j * a.C + c] : cf32{0.0f, 0.0f};
+    Ring<cf32> win{ring + lane, kSymsyncWg, Ls, 0};
+    win.fill(a.hist, a.C, c, live);
     if (LDS_TAPS)
         for (unsigned i = lane; i < p.npfb * Ls; i += kSymsyncWg) tl[i] = a.taps[i];
     __syncthreads();
 
-    unsigned head = 0, ny = 0;                              // head: the oldest slot, where the next sample goes
-    auto window_out = [&]() {                               // the lane's window, oldest first, to the object's history
-        for (unsigned j = 0; j < Ls; ++j) {
-            unsigned sl = head + j;
-            sl = sl >= Ls ? sl - Ls : sl;
-            a.hist[(size_t)j * a.C + c] = ring[sl * kSymsyncWg + lane];
-        }
-    };
-    auto win = [&](unsigned j) {
-        unsigned sl = head + j;
-        sl = sl >= Ls ? sl - Ls : sl;
-        return ring[sl * kSymsyncWg + lane];
-    };
-
-    // The call's rows come in chunks of kSymsyncAhead: a chunk is requested into registers while the chunk before it is
-    // worked through, and moves to its LDS stage when its turn comes, so a step never waits for a memory round trip.
+    unsigned ny = 0;
+    auto window_out = [&] { win.store(a.hist, a.C, c); };   // the lane's window, oldest first, to the object's history
     cf32 *stage = reinterpret_cast<cf32 *>(ss_smem + symsync_ring_bytes(Ls) + (LDS_TAPS ? symsync_table_bytes(p.npfb, Ls) : 0));
-    cf32 xq[kSymsyncAhead];
-#pragma unroll
-    for (int u = 0; u < kSymsyncAhead; ++u)
-        xq[u] = (live && (unsigned)u < a.n) ? a.x[(size_t)u * a.x_pitch + c] : cf32{0.0f, 0.0f};
-
+    auto load = [&](size_t row, bool in_range) { return live && in_range ? a.x[row * a.x_pitch + c] : cf32{0.0f, 0.0f}; };
+    RowQueue<cf32, kSymsyncAhead> xq;
+    xq.prime(a.n, load);
     for (unsigned s0 = 0; s0 < a.n; s0 += kSymsyncAhead) {
-#pragma unroll
-        for (int u = 0; u < kSymsyncAhead; ++u) stage[u * kSymsyncWg + lane] = xq[u];
-#pragma unroll
-        for (int u = 0; u < kSymsyncAhead; ++u) {
-            const size_t ahead = (size_t)s0 + kSymsyncAhead + u;
-            xq[u] = (live && ahead < a.n) ? a.x[ahead * a.x_pitch + c] : cf32{0.0f, 0.0f};
-        }
-        const unsigned steps = a.n - s0 < (unsigned)kSymsyncAhead ? a.n - s0 : (unsigned)kSymsyncAhead;
+        const unsigned steps = xq.next(s0, a.n, lane_stage(stage + lane, kSymsyncWg), load);
         for (unsigned u = 0; u < steps; ++u) {
-            ring[head * kSymsyncWg + lane] = stage[u * kSymsyncWg + lane];   // mf.push(x); dmf.push(x)
-            head = head + 1 == Ls ? 0 : head + 1;
+            win.push(stage[u * kSymsyncWg + lane]);         // mf.push(x); dmf.push(x)
             if (!s.stalled && s.since < Ls) s.since += 1;
             const unsigned z = Ls - s.since;
             const bool young = __any(!s.stalled && z != 0) != 0;
@@ -205,13 +185,7 @@ int launch_symsync(const SymsyncLoop &p, const float *taps, SymsyncChan *state, 
     const size_t ring = symsync_ring_bytes(p.Ls), both = ring + symsync_table_bytes(p.npfb, p.Ls);
     const bool lds_taps = both + symsync_stage_bytes() <= kSymsyncLdsMax;
     const size_t need = (lds_taps ? both : ring) + symsync_stage_bytes();
-    auto fn = lds_taps ? symsync_crcf_kernel<true> : symsync_crcf_kernel<false>;
-    if (need > 64 * 1024)
-        YG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    const unsigned grid = (unsigned)((C + kSymsyncWg - 1) / kSymsyncWg);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kSymsyncWg), need, st, a);
-    YG_LAUNCH_CHECK();
-    return YAGI_OK;
+    return bank_launch(lds_taps ? symsync_crcf_kernel<true> : symsync_crcf_kernel<false>, C, kSymsyncWg, kSymsyncWg, need, st, a);
 }
 
 void symsync_host(const SymsyncLoop &p, const float *taps_, SymsyncChan *state, cf32 *hist, size_t C, const cf32 *x,
@@ -223,38 +197,18 @@ void symsync_host(const SymsyncLoop &p, const float *taps_, SymsyncChan *state, 
         SymsyncChan s = state[c];
         unsigned ny = 0;
         if (!s.stalled) {
-            for (unsigned j = 0; j < Ls; ++j) ring[j] = hist[(size_t)j * C + c];
-            unsigned head = 0;
-            auto win = [&](unsigned j) {
-                unsigned sl = head + j;
-                sl = sl >= Ls ? sl - Ls : sl;
-                return ring[sl];
+            Ring<cf32> win{ring.data(), 1, Ls, 0};
+            win.fill(hist, C, c);
+            auto full = [&] { return ny >= ycap; };
+            auto emit = [&](cf32 yv) {
+                y[(size_t)ny * y_pitch + c] = yv;
+                ++ny;
+                return 0u;
             };
-            for (size_t step = 0; step < n && !s.stalled; ++step) {
-                ring[head] = x[step * x_pitch + c];
-                head = head + 1 == Ls ? 0 : head + 1;
-                if (s.since < Ls) s.since += 1;
-                const unsigned z = Ls - s.since;
-                size_t budget = 2 * (ycap - ny) + 1;
-                while (s.b < p.npfb) {
-                    if (budget == 0 || ny >= ycap) {
-                        s.stalled = 1;
-                        break;
-                    }
-                    --budget;
-                    const SsTap *row = taps + (size_t)s.b * Ls;
-                    auto tap = [&](unsigned j) { return row[j]; };
-                    y[(size_t)ny * y_pitch + c] = z != 0 ? ss_output<true>(s, p, z, win, tap, 0.0)
-                                                         : ss_output<false>(s, p, z, win, tap, 0.0);
-                    ++ny;
-                }
-                if (!s.stalled) {
-                    s.tau = s.tau - 1.0f;
-                    s.bf = s.bf - p.npfbf;
-                    s.b -= p.npfb;
-                }
-            }
-            for (unsigned j = 0; j < Ls; ++j) hist[(size_t)j * C + c] = win(j);
+            for (size_t step = 0; step < n && !s.stalled; ++step)
+                ss_row(s, p, win, taps, x[step * x_pitch + c], s.stalled, 1u, ycap - ny, 0.0, [](bool m) { return m; }, full, emit,
+                       [] {});
+            win.store(hist, C, c);
             state[c] = s;
         }
         ny_[c] = ny;

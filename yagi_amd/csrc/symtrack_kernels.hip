@@ -15,9 +15,10 @@
 //               equalizer's window (a ring with a head per lane: a lane pushes once per synchroniser output) and weights
 //   LDS shared  the staged input rows, the oscillator table (NCO float2, VCO float4), the constellation with reference[],
 //               and the interleaved (H, D) branch taps where they fit (else they stay in global memory)
-// Input rows are requested a chunk of kSymtrackAhead ahead into registers and staged in LDS.  The oscillator scheme, the
-// equalizer strategy and the modem's kind and bps are wave-uniform run-time branches; only LDS_TAPS, which sits in the
-// tap loop, is a template parameter.  Lanes that emit on different rows serialise in the inner loop.  Accepted.
+// The two rings, the rows requested a chunk of kSymtrackAhead ahead and the launch are the bank kernels' scaffold
+// (bank_lane.hpp); the synchroniser's row is ss_row (symsync_body.hpp) with st_after_sync behind it.  The oscillator
+// scheme, the equalizer strategy and the modem's kind and bps are wave-uniform run-time branches; only LDS_TAPS, which
+// sits in the tap loop, is a template parameter.  Lanes that emit on different rows serialise in the inner loop.  Accepted.
 //
 // Stalls: an iteration about to emit symbol number ycap does not run (CAPACITY); a pll_step whose argument reaches
 // YAGI_SYMTRACK_PLL_ARG_MAX does not run, nor anything behind it in that iteration (PLL).  A stalled lane writes its
@@ -64,22 +65,20 @@ struct StRegs {
     SymtrackChan st;
     float x2_sum;
     unsigned long long count;
-    unsigned eq_head;
 };
 
 // Everything of one iteration behind the synchroniser's output s: returns 0 where nothing is emitted (an odd output),
 // 1 where (d_hat, sym) is, and -1 where the PLL rule stalls the channel.
 ST_HD int st_after_sync(StRegs &r, const SymtrackLoop &p, const void *osc_tab, const float *ref, const cf32 *map,
-                        cf32 *eq_ring, cf32 *eq_w, unsigned stride, cf32 s, cf32 &d_hat, unsigned &sym, double zero,
-                        double one) {
+                        Ring<cf32> &eq_ring, cf32 *eq_w, cf32 s, cf32 &d_hat, unsigned &sym, double zero, double one) {
     const cf32 u = st_mix_down((int)p.vco, osc_tab, r.st.theta, s);
     r.st.theta += r.st.d_theta;
-    eq_push(eq_ring, stride, r.eq_head, p.h_len, u, r.x2_sum);
+    eq_push(eq_ring.col, eq_ring.stride, eq_ring.head, p.h_len, u, r.x2_sum);
     r.count += 1;
     const unsigned j = r.st.index;
     r.st.index = j + 1;
     if (j & 1u) return 0;
-    d_hat = eq_execute(eq_ring, eq_w, stride, r.eq_head, p.h_len);
+    d_hat = eq_execute(eq_ring.col, eq_w, eq_ring.stride, eq_ring.head, p.h_len);
     cf32 xh;
     sym = md_hard(p.kind, p.bps, ref, map, d_hat, xh);
     const float e = d_hat.re * (-xh.im) + d_hat.im * xh.re;             // (r * conj(x_hat)).im
@@ -89,7 +88,7 @@ ST_HD int st_after_sync(StRegs &r, const SymtrackLoop &p, const void *osc_tab, c
     r.st.theta += st_constrain(fb, zero);
     if (r.st.num_syms > p.holdoff && p.strategy != YAGI_SYMTRACK_EQ_OFF && r.count >= p.h_len) {
         const cf32 d = p.strategy == YAGI_SYMTRACK_EQ_CM ? eq_unit(d_hat, one) : xh;
-        eq_step(eq_ring, eq_w, stride, r.eq_head, p.h_len, p.eq_mu, r.x2_sum, d, d_hat, one);
+        eq_step(eq_ring.col, eq_w, eq_ring.stride, eq_ring.head, p.h_len, p.eq_mu, r.x2_sum, d, d_hat, one);
     }
     r.st.num_syms += 1;
     return 1;
@@ -118,13 +117,13 @@ __global__ __launch_bounds__(kSymtrackWg) void symtrack_cccf_kernel(const StArgs
     const SymsyncLoop ssl = a.p.ss;
     const unsigned Ls = ssl.Ls, L = p.h_len, lane = threadIdx.x;
     unsigned char *at = st_smem;
-    cf32 *ring = reinterpret_cast<cf32 *>(at);
+    Ring<cf32> win{reinterpret_cast<cf32 *>(at) + lane, S, Ls, 0};       // the synchroniser's window
     at += symsync_ring_bytes(Ls);
-    cf32 *eq_ring = reinterpret_cast<cf32 *>(at) + lane;
+    Ring<cf32> eq_ring{reinterpret_cast<cf32 *>(at) + lane, S, L, 0};
     at += eqlms_taps_bytes(L);
     cf32 *eq_w = reinterpret_cast<cf32 *>(at) + lane;
     at += eqlms_taps_bytes(L);
-    cf32 *stage = reinterpret_cast<cf32 *>(at);
+    cf32 *stage = reinterpret_cast<cf32 *>(at) + lane;
     at += symtrack_stage_bytes();
     float *osc_l = reinterpret_cast<float *>(at);
     at += symtrack_osc_bytes(p.vco);
@@ -148,11 +147,9 @@ __global__ __launch_bounds__(kSymtrackWg) void symtrack_cccf_kernel(const StArgs
         r.count = e.count;
     }
     const bool was_stalled = r.st.stall != 0;
-    for (unsigned j = 0; j < Ls; ++j) ring[j * S + lane] = live ? a.s.ss_hist[(size_t)j * a.C + c] : cf32{0.0f, 0.0f};
-    for (unsigned j = 0; j < L; ++j) {
-        eq_ring[j * S] = live ? a.s.eq_hist[(size_t)j * a.C + c] : cf32{0.0f, 0.0f};
-        eq_w[j * S] = live ? a.s.eq_w[(size_t)j * a.C + c] : cf32{0.0f, 0.0f};
-    }
+    win.fill(a.s.ss_hist, a.C, c, live);
+    for (unsigned j = 0; j < L; ++j) eq_w[j * S] = live ? a.s.eq_w[(size_t)j * a.C + c] : cf32{0.0f, 0.0f};
+    eq_ring.fill(a.s.eq_hist, a.C, c, live);
     {
         const float *g = static_cast<const float *>(a.osc_tab);
         const unsigned words = (unsigned)(symtrack_osc_bytes(p.vco) / sizeof(float));
@@ -165,75 +162,34 @@ __global__ __launch_bounds__(kSymtrackWg) void symtrack_cccf_kernel(const StArgs
     }
     __syncthreads();
 
-    unsigned head = 0, ny = 0;                              // head: the oldest slot of the synchroniser's ring
-    auto window_out = [&]() {
-        for (unsigned j = 0; j < Ls; ++j) {
-            unsigned sl = head + j;
-            sl = sl >= Ls ? sl - Ls : sl;
-            a.s.ss_hist[(size_t)j * a.C + c] = ring[sl * S + lane];
+    unsigned ny = 0;
+    const SsTap *taps = LDS_TAPS ? tl : a.taps;
+    auto window_out = [&] { win.store(a.s.ss_hist, a.C, c); };          // a lane that stalls writes its window out at once
+    auto any = [](bool m) { return __any(m) != 0; };
+    auto full = [&] { return !(r.st.index & 1u) && ny >= a.ycap; };
+    auto emit = [&](cf32 sv) -> uint32_t {
+        cf32 d_hat{0.0f, 0.0f};
+        unsigned sym = 0;
+        const int got = st_after_sync(r, p, osc_l, ref_l, map_l, eq_ring, eq_w, sv, d_hat, sym, a.zero, a.one);
+        if (got < 0) return YAGI_SYMTRACK_STALL_PLL;
+        if (got > 0) {
+            a.y[(size_t)ny * a.y_pitch + c] = d_hat;
+            if (a.sym) a.sym[(size_t)ny * a.sym_pitch + c] = (uint8_t)sym;
+            ++ny;
         }
-    };
-    auto win = [&](unsigned j) {
-        unsigned sl = head + j;
-        sl = sl >= Ls ? sl - Ls : sl;
-        return ring[sl * S + lane];
+        return 0u;
     };
 
-    // The call's rows come in chunks of kSymtrackAhead: a chunk is requested into registers while the chunk before it is
-    // worked through, and moves to its LDS stage when its turn comes, so a row never waits for a memory round trip.
-    cf32 xq[kSymtrackAhead];
-#pragma unroll
-    for (int u = 0; u < kSymtrackAhead; ++u)
-        xq[u] = (live && (unsigned)u < a.n) ? a.x[(size_t)u * a.x_pitch + c] : cf32{0.0f, 0.0f};
-
+    auto load = [&](size_t row, bool in_range) { return live && in_range ? a.x[row * a.x_pitch + c] : cf32{0.0f, 0.0f}; };
+    RowQueue<cf32, kSymtrackAhead> xq;
+    xq.prime(a.n, load);
     for (unsigned s0 = 0; s0 < a.n; s0 += kSymtrackAhead) {
-#pragma unroll
-        for (int u = 0; u < kSymtrackAhead; ++u) stage[u * S + lane] = xq[u];
-#pragma unroll
-        for (int u = 0; u < kSymtrackAhead; ++u) {
-            const size_t ahead = (size_t)s0 + kSymtrackAhead + u;
-            xq[u] = (live && ahead < a.n) ? a.x[ahead * a.x_pitch + c] : cf32{0.0f, 0.0f};
-        }
-        const unsigned steps = a.n - s0 < (unsigned)kSymtrackAhead ? a.n - s0 : (unsigned)kSymtrackAhead;
+        const unsigned steps = xq.next(s0, a.n, lane_stage(stage, S), load);
         for (unsigned u = 0; u < steps; ++u) {
-            cf32 v = stage[u * S + lane];
+            cf32 v = stage[u * S];
             if (!r.st.stall) v = agc_step<false>(r.ag, v, p.agc_alpha, p.agc_scale, 0.0f, 0u);
-            ring[head * S + lane] = v;                      // mf.push(v); dmf.push(v): a stalled lane's column is dead
-            head = head + 1 == Ls ? 0 : head + 1;
-            if (!r.st.stall && r.ss.since < Ls) r.ss.since += 1;
-            const unsigned z = Ls - r.ss.since;
-            const bool young = __any(!r.st.stall && z != 0) != 0;
-            unsigned budget = 2u * (a.ycap - ny) + 1u;
-            while (!r.st.stall && r.ss.b < ssl.npfb) {
-                if (budget == 0 || (!(r.st.index & 1u) && ny >= a.ycap)) {      // the capacity rule
-                    r.st.stall = YAGI_SYMTRACK_STALL_CAPACITY;
-                    window_out();
-                    break;
-                }
-                --budget;
-                const SsTap *row = (LDS_TAPS ? tl : a.taps) + (size_t)r.ss.b * Ls;
-                auto tap = [&](unsigned j) { return row[j]; };
-                const cf32 sv = young ? ss_output<true>(r.ss, ssl, z, win, tap, a.zero)
-                                      : ss_output<false>(r.ss, ssl, z, win, tap, a.zero);
-                cf32 d_hat{0.0f, 0.0f};
-                unsigned sym = 0;
-                const int got = st_after_sync(r, p, osc_l, ref_l, map_l, eq_ring, eq_w, S, sv, d_hat, sym, a.zero, a.one);
-                if (got < 0) {
-                    r.st.stall = YAGI_SYMTRACK_STALL_PLL;
-                    window_out();
-                    break;
-                }
-                if (got > 0) {
-                    a.y[(size_t)ny * a.y_pitch + c] = d_hat;
-                    if (a.sym) a.sym[(size_t)ny * a.sym_pitch + c] = (uint8_t)sym;
-                    ++ny;
-                }
-            }
-            if (!r.st.stall) {
-                r.ss.tau = r.ss.tau - 1.0f;
-                r.ss.bf = r.ss.bf - ssl.npfbf;
-                r.ss.b -= ssl.npfb;
-            }
+            ss_row(r.ss, ssl, win, taps, v, r.st.stall, (uint32_t)YAGI_SYMTRACK_STALL_CAPACITY, a.ycap - ny, a.zero, any, full,
+                   emit, window_out);
         }
     }
 
@@ -248,12 +204,8 @@ __global__ __launch_bounds__(kSymtrackWg) void symtrack_cccf_kernel(const StArgs
             e.count = r.count;
             a.s.eq[c] = e;
             if (!r.st.stall) window_out();
-            for (unsigned j = 0; j < L; ++j) {              // the equalizer's window, oldest first, and the weights
-                unsigned sl = r.eq_head + j;
-                sl = sl >= L ? sl - L : sl;
-                a.s.eq_hist[(size_t)j * a.C + c] = eq_ring[sl * S];
-                a.s.eq_w[(size_t)j * a.C + c] = eq_w[j * S];
-            }
+            eq_ring.store(a.s.eq_hist, a.C, c);
+            for (unsigned j = 0; j < L; ++j) a.s.eq_w[(size_t)j * a.C + c] = eq_w[j * S];
         }
         a.status[c] = ny;
         a.status[a.C + c] = r.st.stall;
@@ -283,13 +235,8 @@ int launch_symtrack(const SymtrackLoop &p, const float *taps, const void *osc_ta
     const size_t with_taps = fixed + symsync_table_bytes(p.ss.npfb, p.ss.Ls);
     const bool lds_taps = with_taps <= kSymtrackLdsMax;
     const size_t need = lds_taps ? with_taps : fixed;
-    auto fn = lds_taps ? symtrack_cccf_kernel<true> : symtrack_cccf_kernel<false>;
-    if (need > 64 * 1024)
-        YG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    const unsigned grid = (unsigned)((C + kSymtrackWg - 1) / kSymtrackWg);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kSymtrackWg), need, st, a);
-    YG_LAUNCH_CHECK();
-    return YAGI_OK;
+    return bank_launch(lds_taps ? symtrack_cccf_kernel<true> : symtrack_cccf_kernel<false>, C, kSymtrackWg, kSymtrackWg, need, st,
+                       a);
 }
 
 void symtrack_host(const SymtrackLoop &p, const float *taps_, const void *osc_tab, const cf32 *map, const SymtrackState &s,
@@ -298,7 +245,7 @@ void symtrack_host(const SymtrackLoop &p, const float *taps_, const void *osc_ta
     const SsTap *taps = reinterpret_cast<const SsTap *>(taps_);
     const SymsyncLoop &ssl = p.ss;
     const unsigned Ls = ssl.Ls, L = p.h_len;
-    std::vector<cf32> ring(Ls), eq_ring(L), eq_w(L);
+    std::vector<cf32> wv(Ls), ev(L), eq_w(L);
     for (size_t c = 0; c < C; ++c) {
         StRegs r{};
         r.ag = agc_unpack(s.agc[c]);
@@ -308,62 +255,32 @@ void symtrack_host(const SymtrackLoop &p, const float *taps_, const void *osc_ta
         r.count = s.eq[c].count;
         unsigned ny = 0;
         if (!r.st.stall) {
-            for (unsigned j = 0; j < Ls; ++j) ring[j] = s.ss_hist[(size_t)j * C + c];
-            for (unsigned j = 0; j < L; ++j) {
-                eq_ring[j] = s.eq_hist[(size_t)j * C + c];
-                eq_w[j] = s.eq_w[(size_t)j * C + c];
-            }
-            unsigned head = 0;
-            auto win = [&](unsigned j) {
-                unsigned sl = head + j;
-                sl = sl >= Ls ? sl - Ls : sl;
-                return ring[sl];
+            Ring<cf32> win{wv.data(), 1, Ls, 0}, eq_ring{ev.data(), 1, L, 0};
+            win.fill(s.ss_hist, C, c);
+            eq_ring.fill(s.eq_hist, C, c);
+            for (unsigned j = 0; j < L; ++j) eq_w[j] = s.eq_w[(size_t)j * C + c];
+            auto full = [&] { return !(r.st.index & 1u) && ny >= ycap; };
+            auto emit = [&](cf32 sv) -> uint32_t {
+                cf32 d_hat{0.0f, 0.0f};
+                unsigned sy = 0;
+                const int got = st_after_sync(r, p, osc_tab, p.ref, map, eq_ring, eq_w.data(), sv, d_hat, sy, 0.0, 1.0);
+                if (got < 0) return YAGI_SYMTRACK_STALL_PLL;
+                if (got > 0) {
+                    y[(size_t)ny * y_pitch + c] = d_hat;
+                    if (sym) sym[(size_t)ny * sym_pitch + c] = (uint8_t)sy;
+                    ++ny;
+                }
+                return 0u;
             };
             for (size_t row = 0; row < n && !r.st.stall; ++row) {
                 const cf32 v = agc_step<false>(r.ag, x[row * x_pitch + c], p.agc_alpha, p.agc_scale, 0.0f, 0u);
-                ring[head] = v;
-                head = head + 1 == Ls ? 0 : head + 1;
-                if (r.ss.since < Ls) r.ss.since += 1;
-                const unsigned z = Ls - r.ss.since;
-                size_t budget = 2 * (ycap - ny) + 1;
-                while (r.ss.b < ssl.npfb) {
-                    if (budget == 0 || (!(r.st.index & 1u) && ny >= ycap)) {
-                        r.st.stall = YAGI_SYMTRACK_STALL_CAPACITY;
-                        break;
-                    }
-                    --budget;
-                    const SsTap *trow = taps + (size_t)r.ss.b * Ls;
-                    auto tap = [&](unsigned j) { return trow[j]; };
-                    const cf32 sv = z != 0 ? ss_output<true>(r.ss, ssl, z, win, tap, 0.0)
-                                           : ss_output<false>(r.ss, ssl, z, win, tap, 0.0);
-                    cf32 d_hat{0.0f, 0.0f};
-                    unsigned sy = 0;
-                    const int got = st_after_sync(r, p, osc_tab, p.ref, map, eq_ring.data(), eq_w.data(), 1, sv, d_hat, sy,
-                                                  0.0, 1.0);
-                    if (got < 0) {
-                        r.st.stall = YAGI_SYMTRACK_STALL_PLL;
-                        break;
-                    }
-                    if (got > 0) {
-                        y[(size_t)ny * y_pitch + c] = d_hat;
-                        if (sym) sym[(size_t)ny * sym_pitch + c] = (uint8_t)sy;
-                        ++ny;
-                    }
-                }
-                if (!r.st.stall) {
-                    r.ss.tau = r.ss.tau - 1.0f;
-                    r.ss.bf = r.ss.bf - ssl.npfbf;
-                    r.ss.b -= ssl.npfb;
-                }
+                ss_row(r.ss, ssl, win, taps, v, r.st.stall, (uint32_t)YAGI_SYMTRACK_STALL_CAPACITY, ycap - ny, 0.0,
+                       [](bool m) { return m; }, full, emit, [] {});
             }
             r.ss.stalled = r.st.stall != 0;
-            for (unsigned j = 0; j < Ls; ++j) s.ss_hist[(size_t)j * C + c] = win(j);
-            for (unsigned j = 0; j < L; ++j) {
-                unsigned sl = r.eq_head + j;
-                sl = sl >= L ? sl - L : sl;
-                s.eq_hist[(size_t)j * C + c] = eq_ring[sl];
-                s.eq_w[(size_t)j * C + c] = eq_w[j];
-            }
+            win.store(s.ss_hist, C, c);
+            eq_ring.store(s.eq_hist, C, c);
+            for (unsigned j = 0; j < L; ++j) s.eq_w[(size_t)j * C + c] = eq_w[j];
             s.agc[c] = agc_pack(r.ag);
             s.ss[c] = r.ss;
             s.st[c] = r.st;
